@@ -18,8 +18,14 @@ max-over-ranks kernel time alone.
 Rank 0 prints ONE JSON line.  `roofline` is computed from the ALGORITHMIC
 bytes of the rank-local launch (SURVEY.md section 8d:
 nnz*(8+4) + 4*(rows+1) + 8*ncols + 8*rows) and the launch's average duration
-measured with HIP events on the launch stream; `cpu_baseline` times the CPU
-oracle (single thread, like the reference) on the same matrix, N = 1 only.
+measured with HIP events on the launch stream.
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full
+adds what the headline does not need: `cpu_baseline` (the CPU oracle, single
+thread like the reference, on the same matrix, N = 1 only, with the GPU's y
+compared against it in full), the copy ceiling and, on the default line, the
+records of the other configs (`other_configs`).  --dump-outputs DIR writes the
+last timed step's result as .npy files for comparing two builds.
 """
 from __future__ import annotations
 
@@ -47,12 +53,12 @@ def parse():
                          "1 = the reference's CPU-sized case (10k x 10k, 100k triplets) end to end")
     ap.add_argument("--dist", default="banded", choices=["banded", "uniform", "ragged"],
                     help="column distribution: banded W=4096 (headline), uniform (stress row: columns anywhere), "
-                         "ragged (robustness row of SURVEY 8d: banded columns, row length 1 + next() % 27)")
+                         "ragged (robustness row of SURVEY 8d: banded columns, row length 1 + next() %% 27)")
     ap.add_argument("--dtype", default="f64", choices=["f64", "f32"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline legs")
     ap.add_argument("--no-ceiling", action="store_true",
-                    help="skip the copy-ceiling child process (profiling runs: one process under the profiler)")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU baseline time budget")
+                    help="--full without the copy-ceiling child process (profiling runs: one process under the profiler)")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU baseline time budget (--full)")
     ap.add_argument("--opt", action="append", default=[], help="kernel option key=value (tuning)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="torch.distributed backend; gloo only to rehearse the N > 1 path on a 1-GPU box")
@@ -85,12 +91,50 @@ def parse():
     ap.add_argument("--torch-vectors", action="store_true",
                     help="one GPU: x and y from torch's allocator instead of the handle's placed vectors (spal_csr_alloc_vectors)")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="default run (config 3, banded, f64, one GPU): do not append the compact records of configs "
-                         "1, 2, 4, 5 and of config 3 in f32 (child processes of this script, ~40 s)")
+                    help="--full on the default line (config 3, banded, f64, one GPU): do not append the compact records "
+                         "of configs 1, 2, 4, 5 and of config 3 in f32 (child processes of this script, ~40 s)")
     ap.add_argument("--extras", action="store_true",
                     help="N > 1, --exchange end: also time K steps with an all-gather after every step and "
                          "report it beside the headline (extra collectives; off by default)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the CPU baseline legs (with their full-size "
+                         "parity checks against the oracle), the copy-ceiling child process and, on the default line, the "
+                         "compact records of the other configs (--no-cpu-baseline / --no-ceiling / --no-other-configs "
+                         "still drop one of them).  Off by default: a plain run sets up, warms up, times the K steps and "
+                         "prints its line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy "
+                         "(float32 / float64, at most 64 MB in all: larger arrays as a fixed, seeded sample beside the "
+                         "positions it was taken at, DIR/<name>_positions.npy)")
     return ap.parse_args()
+
+
+DUMP_BUDGET_BYTES = 64_000_000
+DUMP_SEED = 0xD0305
+
+
+def dump_outputs(dirpath, arrays):
+    """Write the 1-D arrays `arrays` (name -> array) as dirpath/<name>.npy, float32 / float64 (integer arrays as float64:
+    exact below 2**53).  Within DUMP_BUDGET_BYTES in all they are written whole; otherwise every array larger than its
+    even share is replaced by a sample at positions drawn from a fixed seed (sorted, duplicates dropped), written beside
+    it as <name>_positions.npy (float64), so that two runs with the same arguments write the same positions."""
+    os.makedirs(dirpath, exist_ok=True)
+    conv = {}
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(np.asarray(a).reshape(-1))
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64)
+        conv[name] = a
+    whole = sum(a.nbytes for a in conv.values()) <= DUMP_BUDGET_BYTES
+    share = DUMP_BUDGET_BYTES // max(1, len(conv)) - 4096
+    for name, a in conv.items():
+        if whole or a.nbytes <= share:
+            np.save(os.path.join(dirpath, name + ".npy"), a)
+            continue
+        m = share // (a.itemsize + 8)
+        pos = np.unique(np.random.default_rng(DUMP_SEED).integers(0, a.size, size=m, dtype=np.int64))
+        np.save(os.path.join(dirpath, name + ".npy"), a[pos])
+        np.save(os.path.join(dirpath, name + "_positions.npy"), pos.astype(np.float64))
 
 
 def timed(fn, steps, warmup, torch):
@@ -108,12 +152,13 @@ def timed(fn, steps, warmup, torch):
 
 
 def rotating(fns):
-    """Call fns[0], fns[1], ... in turn, one per invocation."""
+    """Call fns[0], fns[1], ... in turn, one per invocation; call.last() is the index of the one called last."""
     state = {"i": 0}
 
     def call():
         fns[state["i"] % len(fns)]()
         state["i"] += 1
+    call.last = lambda: (state["i"] - 1) % len(fns)
     return call
 
 
@@ -179,7 +224,10 @@ def bench_csc(args):
     y_transposed = y.clone()
     for d in devs:
         d.set_option("kernel", 1)
-    ms = timed(rotating(launches), args.steps, args.warmup, torch)
+    scatter = rotating(launches)
+    ms = timed(scatter, args.steps, args.warmup, torch)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"y": ys[scatter.last()].cpu().numpy()})
     nnz = n * per_row
     B = synth.spmv_bytes(nnz, n, n, n, esz)
     out = base_record(args, "CSC SpMV GFLOP/s (f64, 1Mx1M, 14M nnz, atomic scatter)",
@@ -205,7 +253,7 @@ def bench_csc(args):
                                "agrees_with_scatter": bool(torch.allclose(y, y_transposed, rtol=1e-10, atol=1e-12)),
                                "note": "kernel=2 (library default): device CSC->CSR once, then csr_spmv_stream; "
                                        "deterministic, bit-identical to the reference's k-ascending order"}
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         import oracle  # CPU baseline leg only
         t0, passes = time.perf_counter(), 0
         while True:
@@ -237,6 +285,8 @@ def bench_small(args):
     x = torch.from_numpy(synth.vector(nc, dtype=np_dt)).cuda()
     y = torch.empty(nr, dtype=x.dtype, device="cuda")
     ms = timed(lambda: csr.spmv_torch(x, out=y), args.steps, args.warmup, torch)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"y": y.cpu().numpy()})
     t0 = time.perf_counter()
     for _ in range(20):
         d.assemble_csr().close()
@@ -256,7 +306,7 @@ def bench_small(args):
                        "kernel_ms": round(ms, 6), "algorithmic_bytes_per_launch": B,
                        "note": "1.4 MB of work: the launch itself is the cost"}
     out["assembly_ms"] = round(asm_ms, 4)
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         import oracle  # CPU baseline leg only
         t0 = time.perf_counter()
         p, i, w = oracle.coo_to_csr(nr, nc, r, c, v)
@@ -293,8 +343,8 @@ def bench_coo(args):
     coo = sp.CooMatrix.with_triplets(nr, nr, r, c, v)
     d = coo.upload()      # triplets + workspace resident in HBM before the timed region
     torch.cuda.synchronize()
-    steps = max(1, min(args.steps, 20))
-    warm = max(1, min(args.warmup, 3))
+    steps = max(1, args.steps)
+    warm = max(1, args.warmup)
     for _ in range(warm):
         d.assemble_csr().close()
     torch.cuda.synchronize()
@@ -312,6 +362,10 @@ def bench_coo(args):
     ms = (time.perf_counter() - t0) * 1e3 / steps
     if os.environ.get("SPAL_BENCH_DEBUG"):
         print("per-step ms:", [round(t, 2) for t in per_step], file=sys.stderr)
+    if args.dump_outputs:
+        grp, gci, gva = csr.download()      # the last step's result, the CsrMatrix a caller receives
+        dump_outputs(args.dump_outputs, {"rowptr": grp, "colind": gci, "values": gva})
+        del grp, gci, gva
     # the assembled matrix multiplies (the config's second half).  Setup of the product on the result, each timed once with
     # the host clock around call + synchronise: the kernels' plan (spal_csr_plan), then the first product (which builds the
     # column-blocked copy where the plan wants one).
@@ -356,7 +410,7 @@ def bench_coo(args):
                              "algorithmic_bytes_per_launch": rb, "roofline_frac": round(rb / (spmv_ms * 1e-3) / 8e12, 4),
                              "traffic": traffic_entry("config5_result_spmv_f64") if args.dtype == "f64" else None,
                              "plan": {k: rd.get(k) for k in ("cblock_form", "cblock_run", "cblock_rows", "cblock_cols", "cblock_col_blocks", "cblock_row_blocks")}}
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         import oracle  # CPU baseline leg only
         sample = min(length, 50_000_000)   # the whole config-5 input: 5-15 s on one core
         t0 = time.perf_counter()
@@ -440,6 +494,8 @@ def bench_mg(args):
     total_ms = (time.perf_counter() - t0) * 1e3
     ms_per_step = total_ms / args.steps
     y = mg.y_gathered()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"y": y})
     # steady-state pieces: wall clock around call + synchronize, and the library's HIP events (longest over the GPUs)
     comm = {}
     for name, fn, phase in (("x_distribution", dist_x, "x_distribution"), ("y_collection", mg.gather_y, "y_collection")):
@@ -478,7 +534,7 @@ def bench_mg(args):
                 "bytes_per_step": eb["halo"]}
     # cpu_baseline leg: the oracle timed on one core, and GPU 0's gathered y compared with it (bit for bit on the stream path)
     exact, cpu = None, None
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         import oracle  # CPU baseline leg only
         t0 = time.perf_counter()
         yh = oracle.csr_spmv(rp, ci, va, xh)
@@ -557,7 +613,7 @@ def other_configs(args):
     for name, extra in runs.items():
         t0 = time.perf_counter()
         try:
-            p = subprocess.run([sys.executable, os.path.abspath(__file__), "--gpus", "1"] + extra,
+            p = subprocess.run([sys.executable, os.path.abspath(__file__), "--gpus", "1", "--full"] + extra,
                                capture_output=True, text=True, timeout=240)
             line = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
             if p.returncode != 0 or not line:
@@ -838,6 +894,11 @@ def main():
         step()
     total_ms = timed_region(x_mode, y_mode)
     ms_per_step = total_ms / args.steps
+    if args.dump_outputs and rank == 0:
+        # the whole y of the last step: the last copy's own y on one GPU, the gathered y on rank 0 with N > 1
+        y_last = ([y] + [k[2] for k in keep])[single_step.last()] if world == 1 else y
+        dump_outputs(args.dump_outputs, {"y": y_last.cpu().numpy()})
+        del y_last
     # N > 1, --exchange end: the SAME region with the other pair of collectives, so that both end-to-end totals are
     # headline fields: north_star's wording to the letter (ncclBroadcast of all of x, all-gather of the y slices) and
     # the windows form (each GPU receives only the columns its rows read; y slices gathered on rank 0)
@@ -1083,14 +1144,14 @@ def main():
     add_hbm_frac(out["roofline"], peak)
     if world == 1:
         # the ceiling next to which `frac` is read: what this box's HBM delivers for the same footprint
-        ceil = None if args.no_ceiling else copy_ceiling(nrows, max(1, nnz // nrows))
+        ceil = copy_ceiling(nrows, max(1, nnz // nrows)) if args.full and not args.no_ceiling else None
         if ceil:
             out["roofline"]["copy_ceiling_gbs"] = ceil["footprint_gbs"]
             out["roofline"]["moved_frac_of_ceiling"] = round(moved / ceil["footprint_gbs"], 4)
             out["roofline"]["ceiling"] = dict(ceil, note="child process tools/micro/stream_ceiling --quick, same run, same GPU: the stream "
                                                          "kernel's loads and stores without gather or arithmetic; copy16 / read16 = plain "
                                                          "16-byte copy (read + write bytes) / read of the values array")
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         import oracle  # CPU baseline leg only: the oracle is the thing timed here, never the product
         rp32, ci32 = rp.astype(np.uint32), ci.astype(np.uint32)
         yh = np.empty(nrows, dtype=np_dt)
@@ -1175,8 +1236,8 @@ def main():
         except Exception as exc:  # noqa: BLE001  (informational only)
             out["cpu_baseline_threads"] = {"error": str(exc)}
     if (world == 1 and args.config == 3 and args.dist == "banded" and args.dtype == "f64" and not args.opt
-            and not args.no_other_configs):
-        # the driver runs only this default line: every other BASELINE config rides along as a compact record
+            and args.full and not args.no_other_configs):
+        # --full on the default line: every other BASELINE config rides along as a compact record
         out["other_configs"] = other_configs(args)
     print(json.dumps(out))
     if world > 1:

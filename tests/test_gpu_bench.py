@@ -23,8 +23,8 @@ def run_bench(*flags):
     return json.loads(lines[0])
 
 
-@pytest.mark.parametrize("config, flags", [(1, ["--steps", "20", "--warmup", "3"]),
-                                           (2, ["--steps", "10", "--warmup", "3", "--cpu-seconds", "1", "--no-ceiling"])])
+@pytest.mark.parametrize("config, flags", [(1, ["--steps", "20", "--warmup", "3", "--full"]),
+                                           (2, ["--steps", "10", "--warmup", "3", "--full", "--cpu-seconds", "1", "--no-ceiling"])])
 def test_bench_line_contract(config, flags):
     d = run_bench("--config", str(config), *flags)
     assert REQUIRED <= set(d), sorted(REQUIRED - set(d))
@@ -58,7 +58,30 @@ def test_config5_record_carries_the_product_on_the_result():
 def test_config4_record_is_the_scatter_path_over_row_tiles():
     """config 4 names the atomic scatter path: `value` is that path (over row tiles on this band), the transposed route is
     reported beside it and agrees; the launches rotate over handles that own their arrays"""
-    d = run_bench("--config", "4", "--steps", "50", "--warmup", "5", "--cpu-seconds", "1")
+    d = run_bench("--config", "4", "--steps", "50", "--warmup", "5", "--full", "--cpu-seconds", "1")
     assert d["roofline"]["kernel"].startswith("csc_spmv_rowtiles") and d["config"]["plan"]["row_tiles"] == 1, d["roofline"]
     assert d["transposed_route"]["agrees_with_scatter"] is True and d["cpu_baseline"]["gpu_agrees_with_cpu"] is True
     assert "3 independent copies" in d["config"]["workload"]
+
+
+def test_plain_run_is_lean_and_dumps_the_last_step(tmp_path):
+    """without --full the line carries no CPU baseline or copy ceiling; --steps sets the timed steps; --dump-outputs writes
+    the y of the last timed step, which is the oracle's y = A*x for config 1's inputs"""
+    import numpy as np
+    import oracle
+    import spal_synth as synth
+    from tests.util import assert_spmv_close
+    d = run_bench("--config", "1", "--steps", "7", "--warmup", "2", "--dump-outputs", str(tmp_path))
+    assert d["steps"] == 7 and d["ms_per_step"] > 0 and "cpu_baseline" not in d
+    y = np.load(tmp_path / "y.npy")
+    cfg = synth.CONFIGS[1]
+    r, c, v = synth.coo(cfg["nrows"], cfg["ncols"], cfg["length"], synth.matrix_seed(1))
+    p, i, w = oracle.coo_to_csr(cfg["nrows"], cfg["ncols"], r, c, v)
+    x = synth.vector(cfg["ncols"])
+    assert y.dtype == np.float64 and y.shape == (cfg["nrows"],)
+    assert_spmv_close(y, oracle.csr_spmv(p, i, w, x), oracle.csr_abs_bound(p, i, w, x), 1e-10)
+
+
+def test_config5_honours_steps():
+    d = run_bench("--config", "5", "--steps", "25", "--warmup", "1")
+    assert d["steps"] == 25 and "cpu_baseline" not in d

@@ -223,7 +223,7 @@ def test_eight_shard_rehearsal_at_config3_size_through_the_c_abi():
     import json
     bench = os.path.join(ROOT, "bench.py")
     out = subprocess.run([sys.executable, bench, "--host", "mg", "--gpus", "8", "--devices", "0,0,0,0,0,0,0,0", "--steps", "5",
-                          "--warmup", "2"], capture_output=True, text=True, timeout=900)
+                          "--warmup", "2", "--full"], capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1

@@ -8,7 +8,7 @@
 set -u
 export TMPDIR=/tmp
 O=gpurun_out/r4; mkdir -p $O
-timeout -k 10 600 python bench.py --host mg --gpus 8 --devices 0,0,0,0,0,0,0,0 --steps 20 --warmup 5 > $O/rehearsal_mg_8_shards.log 2>&1; rc=$?
+timeout -k 10 600 python bench.py --host mg --gpus 8 --devices 0,0,0,0,0,0,0,0 --steps 20 --warmup 5 --full > $O/rehearsal_mg_8_shards.log 2>&1; rc=$?
 grep "^{" $O/rehearsal_mg_8_shards.log | tail -n 1 > $O/rehearsal_mg_8_shards.json; echo "mg host rc=$rc $(wc -c < $O/rehearsal_mg_8_shards.json) bytes"
 [ $rc -ne 0 ] && exit $rc
 timeout -k 10 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 5 --master-addr 127.0.0.1 --master-port 29766 bench.py --gpus 5 --steps 20 --warmup 5 --backend gloo --same-device > $O/rehearsal_dist_5_ranks.log 2>&1; rc=$?
