@@ -265,6 +265,24 @@ int spal_csc_status(spal_csc_t a, int *invalid_products);
 int spal_csc_to_csr(spal_csc_t a, spal_csr_t *out);
 int spal_csr_to_csc(spal_csr_t a, spal_csc_t *out);
 
+/* ---- C = A * B, sparse x sparse, on the device ----------------------------------
+ * Row-wise Gustavson (LDS hash tables per row, expand-sort-compress for rows with more products than the LDS holds).
+ * Structure: every (i, j) reached by some k with A[i,k] and B[k,j] stored, sums that are exactly 0.0 KEPT (the
+ * reference's Mul drops nothing), columns ascending in every row.  Arithmetic: the products of one (i, j) combined in
+ * ascending k, the first one assigned (-x * 0.0 gives -0.0), each rounded before the add (no FMA); f32 in f32.
+ * Deterministic: no float atomics.  Options on the LEFT operand (spal_csr_set_option / spal_csc_set_option):
+ * "spgemm_route" 0 = auto, 1 = LDS tiers wherever they fit, 2 = every row through the large-row tier; "spgemm_lds_cap"
+ * 0 = default, else the largest per-row product count sent to the LDS tiers (at most 4096).  Row-block operands (more than
+ * 2^32 - 65537 entries) and products whose nnz or large-row product count passes that limit: SPAL_ERR_UNSUPPORTED.
+ * The result plans eagerly; spal_csr_describe / spal_csc_describe on it add a "spgemm" object (rows per tier, products,
+ * nnz, route, plan_ms = the result's plan, call_ms). */
+/* C = A * B: `impl Mul for &CsrMatrix<T>` (src/csr/ops/mul.rs:5-59), bit-identical. Enqueued on `stream`
+ * (NULL = default), synchronised on it (the output size is data dependent). A.ncols must equal B.nrows
+ * (assert_eq!, mul.rs:9), same device, same element size. Returns a new, independent handle. */
+int spal_csr_mul(spal_csr_t a, spal_csr_t b, void *stream, spal_csr_t *out);
+/* `impl Mul for &CscMatrix<T>` (src/csc/ops/mul.rs:5-60). */
+int spal_csc_mul(spal_csc_t a, spal_csc_t b, void *stream, spal_csc_t *out);
+
 /* ---- COO -> CSR assembly on the device -------------------------------------
  * Replaces `impl From<&CooMatrix<T>> for CsrMatrix<T>`
  * (src/csr/conv/coo.rs:4-115): stable order by (row, col), duplicates summed

@@ -12,6 +12,7 @@
 //   a * x  (x a dense std::vector<T>)
 //       == `&a * &x_as_matrix`, bound in Rust as
 //          impl Mul<&[T]> for &CsrMatrix<T>              src/csr/ops/mul.rs:5-59
+//   a * b  (b a CsrMatrix<T>) == impl Mul for &CsrMatrix<T>  src/csr/ops/mul.rs:5-59
 //   CsrMatrix<T>::from(coo)  == CsrMatrix::from(&coo)    src/csr/conv/coo.rs:3-116
 //   CscMatrix<T>, CooMatrix<T> likewise                  src/csc.rs, src/coo.rs
 //
@@ -130,6 +131,17 @@ class CsrMatrix {
         return y;
     }
 
+    // C = A * B: `impl Mul for &CsrMatrix<T>` (src/csr/ops/mul.rs:5-59) on the device, bit-identical.
+    // Panics when ncols != rhs.nrows (assert_eq!, mul.rs:9).
+    CsrMatrix operator*(const CsrMatrix &rhs) const {
+        if (ncols_ != rhs.nrows_)
+            throw Panic(SPAL_ERR_INVALID_ARGUMENT, "assertion failed: ncols == rhs.nrows (left: " +
+                                                       std::to_string(ncols_) + ", right: " + std::to_string(rhs.nrows_) + ")");
+        spal_csr_t h = nullptr;
+        detail::check(spal_csr_mul(device_handle(), rhs.device_handle(), nullptr, &h));
+        return adopt(h);
+    }
+
     // CsrMatrix::from(&coo): assembled on the device, bit-identical to the reference.
     static CsrMatrix from(const CooMatrix<T> &coo, int device = 0);
     // CsrMatrix::from(&csc)  (src/csr/conv/csc.rs:4-52): device stable sort by row.
@@ -199,6 +211,15 @@ class CscMatrix {
         std::vector<T> y(nrows_);
         detail::check(detail::Abi<T>::csc_spmv(device_handle(), x.data(), x.size(), y.data(), y.size()));
         return y;
+    }
+    // C = A * B: `impl Mul for &CscMatrix<T>` (src/csc/ops/mul.rs:5-60) on the device, bit-identical.
+    CscMatrix operator*(const CscMatrix &rhs) const {
+        if (ncols_ != rhs.nrows_)
+            throw Panic(SPAL_ERR_INVALID_ARGUMENT, "assertion failed: ncols == rhs.nrows (left: " +
+                                                       std::to_string(ncols_) + ", right: " + std::to_string(rhs.nrows_) + ")");
+        spal_csc_t h = nullptr;
+        detail::check(spal_csc_mul(device_handle(), rhs.device_handle(), nullptr, &h));
+        return adopt(h);
     }
     // CscMatrix::from(&csr)  (src/csc/conv/csr.rs:4-52) and CscMatrix::from(&coo)
     // (src/csc/conv/coo.rs:3-116), both on the device.

@@ -124,6 +124,14 @@ impl<T: HipScalar> DeviceCsr<T> {
         unsafe { ffi::check(ffi::spal_csr_to_csc(self.h, &mut out)); }
         DeviceCsc { h: out, _t: PhantomData }
     }
+
+    /// Device twin of `impl Mul for &CsrMatrix<T>` (src/csr/ops/mul.rs:5-59), bit-identical; synchronises `stream`
+    /// (null = the default stream).  Panics when `self.ncols() != rhs.nrows()` (mul.rs:9).
+    pub fn mul_mat(&self, rhs: &DeviceCsr<T>, stream: *mut c_void) -> DeviceCsr<T> {
+        let mut out = std::ptr::null_mut();
+        unsafe { ffi::check(ffi::spal_csr_mul(self.h, rhs.h, stream, &mut out)); }
+        DeviceCsr::from_raw(out)
+    }
 }
 
 impl<T: HipScalar> DeviceCsc<T> {
@@ -182,6 +190,13 @@ impl<T: HipScalar> DeviceCsc<T> {
         let mut out = std::ptr::null_mut();
         unsafe { ffi::check(ffi::spal_csc_to_csr(self.h, &mut out)); }
         DeviceCsr::from_raw(out)
+    }
+
+    /// Device twin of `impl Mul for &CscMatrix<T>` (src/csc/ops/mul.rs:5-60), bit-identical.
+    pub fn mul_mat(&self, rhs: &DeviceCsc<T>, stream: *mut c_void) -> DeviceCsc<T> {
+        let mut out = std::ptr::null_mut();
+        unsafe { ffi::check(ffi::spal_csc_mul(self.h, rhs.h, stream, &mut out)); }
+        DeviceCsc { h: out, _t: PhantomData }
     }
 }
 

@@ -16,6 +16,17 @@ impl<T: HipScalar> Mul<&[T]> for &DeviceCsc<T> {
     fn mul(self, x: &[T]) -> Vec<T> { self.mul_vec(x) }
 }
 
+/// C = A * B between resident matrices: the reference's own operator (src/csr/ops/mul.rs:5-59,
+/// src/csc/ops/mul.rs:5-60) on the device, bit-identical.  Panics when `a.ncols() != b.nrows()` (mul.rs:9).
+impl<T: HipScalar> Mul for &DeviceCsr<T> {
+    type Output = DeviceCsr<T>;
+    fn mul(self, rhs: &DeviceCsr<T>) -> DeviceCsr<T> { self.mul_mat(rhs, std::ptr::null_mut()) }
+}
+impl<T: HipScalar> Mul for &DeviceCsc<T> {
+    type Output = DeviceCsc<T>;
+    fn mul(self, rhs: &DeviceCsc<T>) -> DeviceCsc<T> { self.mul_mat(rhs, std::ptr::null_mut()) }
+}
+
 /// One-shot convenience with the reference's operator shape: uploads `self`, multiplies, frees the device copy.
 /// The upload dominates (1.7 GB for 140M entries); keep a `DeviceCsr` (`DeviceCsr::from(&a)`) for repeated
 /// products.  Panics when `x.len() != ncols` (src/csr/ops/mul.rs:9).
@@ -63,3 +74,12 @@ pub fn csr_from_coo_hip<T: HipScalar>(coo: &CooMatrix<T>) -> CsrMatrix<T> { Devi
 pub fn csc_from_coo_hip<T: HipScalar>(coo: &CooMatrix<T>) -> CscMatrix<T> { DeviceCsc::from(coo).download() }
 pub fn csr_from_csc_hip<T: HipScalar>(a: &CscMatrix<T>) -> CsrMatrix<T> { DeviceCsc::new(a, 0).to_csr().download() }
 pub fn csc_from_csr_hip<T: HipScalar>(a: &CsrMatrix<T>) -> CscMatrix<T> { DeviceCsr::new(a, 0).to_csc().download() }
+/// `&a * &b` with the reference's signatures (src/csr/ops/mul.rs:5, src/csc/ops/mul.rs:5), computed on the device.
+pub fn csr_mul_hip<T: HipScalar>(a: &CsrMatrix<T>, b: &CsrMatrix<T>) -> CsrMatrix<T> {
+    assert_eq!(a.ncols(), b.nrows());
+    (&DeviceCsr::new(a, 0) * &DeviceCsr::new(b, 0)).download()
+}
+pub fn csc_mul_hip<T: HipScalar>(a: &CscMatrix<T>, b: &CscMatrix<T>) -> CscMatrix<T> {
+    assert_eq!(a.ncols(), b.nrows());
+    (&DeviceCsc::new(a, 0) * &DeviceCsc::new(b, 0)).download()
+}

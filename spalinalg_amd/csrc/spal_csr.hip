@@ -2223,6 +2223,10 @@ int spal_csr_download_f32(spal_csr_t a, uint64_t *rowptr, uint64_t *colind, floa
 
 int spal_csr_set_option(spal_csr_t a, const char *key, int64_t value) {
     if (!a || !key) return fail(SPAL_ERR_INVALID_ARGUMENT, "spal_csr_set_option: null argument");
+    {   // options of the sparse x sparse product (this handle as its left operand): no plan involved
+        int st = SPAL_OK;
+        if (spgemm_option(key, value, &a->spgemm_route, &a->spgemm_lds_cap, &st)) return st;
+    }
     if (!a->parts.empty()) {   // row blocks: every block takes the option (each plans for its own rows)
         for (spal_csr *part : a->parts) SPAL_TRY(spal_csr_set_option(part, key, value));
         return SPAL_OK;
@@ -2576,8 +2580,13 @@ int spal_csr_plan(spal_csr_t a) {
     if (guard.status != SPAL_OK) return guard.status;
     return csr_ensure_plan(a, nullptr, false);
 }
+static int csr_describe_plan(spal_csr_t a, char *buf, size_t buf_len);
 int spal_csr_describe(spal_csr_t a, char *buf, size_t buf_len) {
     if (!a || !buf || !buf_len) return fail(SPAL_ERR_INVALID_ARGUMENT, "spal_csr_describe: null argument");
+    SPAL_TRY(csr_describe_plan(a, buf, buf_len));
+    return spgemm_describe_append(buf, buf_len, a->spgemm_info);   // a product of spal_csr_mul: how it was built
+}
+static int csr_describe_plan(spal_csr_t a, char *buf, size_t buf_len) {
     if (!a->parts.empty()) {   // row blocks: the shape of the whole, the cuts, and the first block's plan
         std::string rows = "[";
         for (size_t b = 0; b < a->part_row0.size(); ++b) rows += (b ? ", " : "") + std::to_string(a->part_row0[b]);

@@ -190,6 +190,11 @@ int transpose_device(int device, int elem_size, uint64_t nmajor, uint64_t nminor
                      const uint32_t *d_ptr, const uint32_t *d_ind, const void *d_val,
                      hipStream_t st, uint32_t **out_ptr, uint32_t **out_ind, void **out_val,
                      uint64_t *out_cap);
+// implemented in spal_spgemm.hip: the options "spgemm_route" / "spgemm_lds_cap" of either handle type (1 = the key is one
+// of them and *status says how setting it went, 0 = another key)
+int spgemm_option(const char *key, int64_t value, int *route, int64_t *lds_cap, int *status);
+// ... and the "spgemm" object a product handle adds to its describe() line (no-op for an empty `info`)
+int spgemm_describe_append(char *buf, size_t buf_len, const std::string &info);
 // implemented in spal_csc.hip: handle around device arrays it takes ownership of
 int csc_adopt_device(int device, int elem_size, uint64_t nrows, uint64_t ncols, uint64_t nnz,
                      uint32_t *d_colptr, uint32_t *d_rowind, void *d_values, spal_csc **out);
@@ -270,6 +275,10 @@ struct spal_csr {
     // one after the other on the caller's stream, block b writing y[part_row0[b] ...).
     std::vector<spal_csr *> parts;
     std::vector<uint64_t> part_row0, part_entry0;   // first row / first entry of every block, then nrows / nnz
+    // sparse x sparse (spal_spgemm.hip): options of this handle as the LEFT operand, and what built it if it is a product
+    int spgemm_route = 0;          // option "spgemm_route": 0 auto, 1 LDS tiers wherever they fit, 2 every row through the large tier
+    int64_t spgemm_lds_cap = 0;    // option "spgemm_lds_cap": 0 default, else the largest product count of a row sent to LDS
+    std::string spgemm_info;       // the "spgemm" object of spal_csr_describe (empty: not a product)
 };
 
 struct spal_csc {
@@ -329,6 +338,9 @@ struct spal_csc {
     std::mutex mu;
     void *d_x = nullptr, *d_y = nullptr;
     hipStream_t stream = nullptr;
+    int spgemm_route = 0;          // as spal_csr's
+    int64_t spgemm_lds_cap = 0;
+    std::string spgemm_info;
 };
 
 struct spal_coo {

@@ -9,6 +9,8 @@ Names, argument meaning and error behaviour follow the reference
 * ``a * x`` / ``a @ x`` with a dense vector: the product the reference only
   reaches through ``&a * &x_as_matrix`` (src/csr/ops/mul.rs:5-59); what a Rust
   binding adds as ``impl Mul<&[T]> for &CsrMatrix<T>``.
+* ``a * b`` / ``a @ b`` with a matrix of the same format: the reference's own
+  ``impl Mul for &CsrMatrix<T>`` / ``&CscMatrix<T>``, on the device, bit-identical.
 * ``CsrMatrix.from_coo(coo)`` == ``CsrMatrix::from(&coo)``
   (src/csr/conv/coo.rs:3-116), assembled on the device.
 * ``CscMatrix`` / ``CooMatrix`` likewise (src/csc.rs, src/coo.rs).
@@ -196,6 +198,15 @@ class DeviceCsr(_DeviceMatrix):
         check(_ffi.lib().spal_csr_to_csc(self._h, C.byref(out)))
         return DeviceCsc(out, self.dtype, self.device)
 
+    def mul(self, other: "DeviceCsr", stream=None) -> "DeviceCsr":
+        """C = self * other on the device (spal_csr_mul: `impl Mul for &CsrMatrix<T>`, src/csr/ops/mul.rs:5-59,
+        bit-identical); synchronises `stream`.  Options "spgemm_route" / "spgemm_lds_cap" are read from self."""
+        if not isinstance(other, DeviceCsr):
+            raise TypeError("DeviceCsr.mul needs a DeviceCsr (the reference has no mixed CSR x CSC Mul)")
+        out = vp()
+        check(_ffi.lib().spal_csr_mul(self._h, other._h, _stream_ptr(stream), C.byref(out)))
+        return DeviceCsr(out, self.dtype, self.device)
+
 
 class DeviceCsc(_DeviceMatrix):
     _kind = "csc"
@@ -220,6 +231,14 @@ class DeviceCsc(_DeviceMatrix):
         out = vp()
         check(_ffi.lib().spal_csc_to_csr(self._h, C.byref(out)))
         return DeviceCsr(out, self.dtype, self.device)
+
+    def mul(self, other: "DeviceCsc", stream=None) -> "DeviceCsc":
+        """C = self * other on the device (spal_csc_mul: `impl Mul for &CscMatrix<T>`, src/csc/ops/mul.rs:5-60)."""
+        if not isinstance(other, DeviceCsc):
+            raise TypeError("DeviceCsc.mul needs a DeviceCsc (the reference has no mixed CSR x CSC Mul)")
+        out = vp()
+        check(_ffi.lib().spal_csc_mul(self._h, other._h, _stream_ptr(stream), C.byref(out)))
+        return DeviceCsc(out, self.dtype, self.device)
 
 
 class DeviceCoo:
@@ -461,7 +480,24 @@ class _Compressed:
                         f"assertion failed: ncols == x.len() (left: {self._ncols}, right: {x.shape[0]})")
         return self.device().spmv(x.astype(self.dtype, copy=False))
 
+    def _mul_mat(self, other, device: int = 0):
+        """`&self * &other` (src/csr/ops/mul.rs:5-59 / src/csc/ops/mul.rs:5-60) on the device; the result is downloaded
+        and keeps its device handle, as from_coo does."""
+        if type(other) is not type(self):
+            raise TypeError(f"{type(self).__name__} * {type(other).__name__}: the reference has no mixed Mul")
+        if self._ncols != other._nrows:
+            # assert_eq!(self.ncols(), rhs.nrows())  mul.rs:9
+            raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT,
+                        f"assertion failed: ncols == rhs.nrows (left: {self._ncols}, right: {other._nrows})")
+        dev = self.device(device).mul(other.device(device))
+        ptr, ind, val = dev.download()
+        out = type(self)._trusted(self._nrows, other._ncols, ptr, ind, val)
+        out._dev[device] = dev
+        return out
+
     def __mul__(self, x):
+        if isinstance(x, _Compressed):
+            return self._mul_mat(x)
         return self._mul_vec(x)
 
     __matmul__ = __mul__
