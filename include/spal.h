@@ -283,6 +283,36 @@ int spal_csr_mul(spal_csr_t a, spal_csr_t b, void *stream, spal_csr_t *out);
 /* `impl Mul for &CscMatrix<T>` (src/csc/ops/mul.rs:5-60). */
 int spal_csc_mul(spal_csc_t a, spal_csc_t b, void *stream, spal_csc_t *out);
 
+/* ---- C = A + B, C = A - B, C = -A, on the device ----------------------------------
+ * A merge of the two operands' entry streams, cut into equal tiles of the merged sequence.  A and B are both
+ * CSR or both CSC, of one shape, device and element type (for CSC read "column" for "row" below).
+ * Structure: row i of C holds the union of the columns stored in row i of A and of B, ascending; sums that are exactly
+ * zero are KEPT (A - A stores +0.0 at every position of A); nothing is dropped, nothing added.
+ * Values: one IEEE operation in the operand type (f32 in f32) -- stored in A only: `a` (bits copied); in B only: `b` for
+ * Add, `-b` for Sub (the sign bit flipped: a B-only +0.0 gives -0.0, sub.rs:47); in both: `a + b` / `a - b`.  Equal to
+ * the reference bit for bit for finite inputs (subnormals included, no flush to zero) and infinities; a NaN produced by
+ * the arithmetic sits at the reference's position, its payload is not part of the contract.  Neg flips the sign bit of
+ * every value (+-0, +-inf and NaN included) and copies the structure.
+ * Shapes: the reference's CSR and CSC Add / Sub label their transposed intermediate with the untransposed dimensions
+ * (SURVEY F9): for nrows > ncols their final transpose indexes out of bounds, for nrows < ncols entries in columns at or
+ * beyond nrows are lost and the result is labelled ncols x nrows.  These calls return the union above for every shape.
+ * Checks, in the reference's order: null arguments; assert_eq!(nrows, rhs.nrows) then ncols (add.rs:9-10, sub.rs:9-10)
+ * -> SPAL_ERR_INVALID_ARGUMENT "assertion failed: nrows == rhs.nrows (left: .., right: ..)"; different devices or element
+ * sizes -> SPAL_ERR_INVALID_ARGUMENT; a row-block operand (more than 2^32 - 65537 entries) or a result with more entries
+ * than that -> SPAL_ERR_UNSUPPORTED.  Nothing leaks on failure.
+ * Calls: enqueued on `stream` (NULL = default) and synchronised on it once (the size of C is data dependent); the
+ * operands are only read (several threads may use them at once); each call returns a new, independent handle, planned
+ * eagerly.  Option on the LEFT operand (spal_csr_set_option / spal_csc_set_option): "spadd_tile" 0 = default (2048), else
+ * a power of two in [16, 2048], the merged elements of one workgroup.  spal_csr_describe / spal_csc_describe on the
+ * result add a "spadd" object (op, tile, tiles, matched pairs, nnz, kernel_ms = device time of the kernels, plan_ms =
+ * the result's plan, call_ms). */
+int spal_csr_add(spal_csr_t a, spal_csr_t b, void *stream, spal_csr_t *out);  /* src/csr/ops/add.rs:5-75 */
+int spal_csr_sub(spal_csr_t a, spal_csr_t b, void *stream, spal_csr_t *out);  /* src/csr/ops/sub.rs:5-75 */
+int spal_csr_neg(spal_csr_t a, void *stream, spal_csr_t *out);                /* src/csr/ops/neg.rs:5-17 */
+int spal_csc_add(spal_csc_t a, spal_csc_t b, void *stream, spal_csc_t *out);  /* src/csc/ops/add.rs:5-70 */
+int spal_csc_sub(spal_csc_t a, spal_csc_t b, void *stream, spal_csc_t *out);  /* src/csc/ops/sub.rs:5-70 */
+int spal_csc_neg(spal_csc_t a, void *stream, spal_csc_t *out);                /* src/csc/ops/neg.rs:5-17 */
+
 /* ---- COO -> CSR assembly on the device -------------------------------------
  * Replaces `impl From<&CooMatrix<T>> for CsrMatrix<T>`
  * (src/csr/conv/coo.rs:4-115): stable order by (row, col), duplicates summed

@@ -13,6 +13,7 @@
 //       == `&a * &x_as_matrix`, bound in Rust as
 //          impl Mul<&[T]> for &CsrMatrix<T>              src/csr/ops/mul.rs:5-59
 //   a * b  (b a CsrMatrix<T>) == impl Mul for &CsrMatrix<T>  src/csr/ops/mul.rs:5-59
+//   a + b, a - b, -a          == impl Add / Sub / Neg for &CsrMatrix<T>  src/csr/ops/{add,sub,neg}.rs
 //   CsrMatrix<T>::from(coo)  == CsrMatrix::from(&coo)    src/csr/conv/coo.rs:3-116
 //   CscMatrix<T>, CooMatrix<T> likewise                  src/csc.rs, src/coo.rs
 //
@@ -77,6 +78,15 @@ template <> struct Abi<float> {
     static constexpr auto coo_to_csc = spal_coo_to_csc_f32;
     static constexpr auto csc_download = spal_csc_download_f32;
 };
+// assert_eq!(self.nrows(), rhs.nrows()); assert_eq!(self.ncols(), rhs.ncols())  (src/csr/ops/add.rs:9-10, sub.rs:9-10)
+inline void check_same_shape(usize nrows, usize ncols, usize rhs_nrows, usize rhs_ncols) {
+    if (nrows != rhs_nrows)
+        throw Panic(SPAL_ERR_INVALID_ARGUMENT, "assertion failed: nrows == rhs.nrows (left: " + std::to_string(nrows) +
+                                                   ", right: " + std::to_string(rhs_nrows) + ")");
+    if (ncols != rhs_ncols)
+        throw Panic(SPAL_ERR_INVALID_ARGUMENT, "assertion failed: ncols == rhs.ncols (left: " + std::to_string(ncols) +
+                                                   ", right: " + std::to_string(rhs_ncols) + ")");
+}
 struct CsrDeleter { void operator()(spal_csr *h) const { spal_csr_destroy(h); } };
 struct CscDeleter { void operator()(spal_csc *h) const { spal_csc_destroy(h); } };
 }  // namespace detail
@@ -142,6 +152,16 @@ class CsrMatrix {
         return adopt(h);
     }
 
+    // C = A + B / A - B / -A: `impl Add / Sub / Neg for &CsrMatrix<T>` (src/csr/ops/{add,sub,neg}.rs) on the device,
+    // bit-identical.  Panics when the shapes differ (assert_eq!, add.rs:9-10 / sub.rs:9-10), before any device call.
+    CsrMatrix operator+(const CsrMatrix &rhs) const { return add_sub(rhs, spal_csr_add); }
+    CsrMatrix operator-(const CsrMatrix &rhs) const { return add_sub(rhs, spal_csr_sub); }
+    CsrMatrix operator-() const {
+        spal_csr_t h = nullptr;
+        detail::check(spal_csr_neg(device_handle(), nullptr, &h));
+        return adopt(h);
+    }
+
     // CsrMatrix::from(&coo): assembled on the device, bit-identical to the reference.
     static CsrMatrix from(const CooMatrix<T> &coo, int device = 0);
     // CsrMatrix::from(&csc)  (src/csr/conv/csc.rs:4-52): device stable sort by row.
@@ -154,6 +174,12 @@ class CsrMatrix {
               std::vector<T> va)
         : nrows_(nrows), ncols_(ncols), rowptr_(std::move(rp)), colind_(std::move(ci)),
           values_(std::move(va)) {}
+    CsrMatrix add_sub(const CsrMatrix &rhs, int (*op)(spal_csr_t, spal_csr_t, void *, spal_csr_t *)) const {
+        detail::check_same_shape(nrows_, ncols_, rhs.nrows_, rhs.ncols_);
+        spal_csr_t h = nullptr;
+        detail::check(op(device_handle(), rhs.device_handle(), nullptr, &h));
+        return adopt(h);
+    }
     static CsrMatrix adopt(spal_csr_t h) {   // downloads h into a host matrix that also owns h
         std::unique_ptr<spal_csr, detail::CsrDeleter> guard(h);
         uint64_t nr = 0, nc = 0, nz = 0;
@@ -221,6 +247,14 @@ class CscMatrix {
         detail::check(spal_csc_mul(device_handle(), rhs.device_handle(), nullptr, &h));
         return adopt(h);
     }
+    // C = A + B / A - B / -A: `impl Add / Sub / Neg for &CscMatrix<T>` (src/csc/ops/{add,sub,neg}.rs), bit-identical.
+    CscMatrix operator+(const CscMatrix &rhs) const { return add_sub(rhs, spal_csc_add); }
+    CscMatrix operator-(const CscMatrix &rhs) const { return add_sub(rhs, spal_csc_sub); }
+    CscMatrix operator-() const {
+        spal_csc_t h = nullptr;
+        detail::check(spal_csc_neg(device_handle(), nullptr, &h));
+        return adopt(h);
+    }
     // CscMatrix::from(&csr)  (src/csc/conv/csr.rs:4-52) and CscMatrix::from(&coo)
     // (src/csc/conv/coo.rs:3-116), both on the device.
     static CscMatrix from(const CsrMatrix<T> &csr, int device = 0) {
@@ -237,6 +271,12 @@ class CscMatrix {
               std::vector<T> va)
         : nrows_(nrows), ncols_(ncols), colptr_(std::move(cp)), rowind_(std::move(ri)),
           values_(std::move(va)) {}
+    CscMatrix add_sub(const CscMatrix &rhs, int (*op)(spal_csc_t, spal_csc_t, void *, spal_csc_t *)) const {
+        detail::check_same_shape(nrows_, ncols_, rhs.nrows_, rhs.ncols_);
+        spal_csc_t h = nullptr;
+        detail::check(op(device_handle(), rhs.device_handle(), nullptr, &h));
+        return adopt(h);
+    }
     static CscMatrix adopt(spal_csc_t h) {
         std::unique_ptr<spal_csc, detail::CscDeleter> guard(h);
         uint64_t nr = 0, nc = 0, nz = 0;

@@ -132,6 +132,24 @@ impl<T: HipScalar> DeviceCsr<T> {
         unsafe { ffi::check(ffi::spal_csr_mul(self.h, rhs.h, stream, &mut out)); }
         DeviceCsr::from_raw(out)
     }
+
+    /// Device twins of `impl Add / Sub / Neg for &CsrMatrix<T>` (src/csr/ops/{add,sub,neg}.rs), bit-identical;
+    /// synchronise `stream`.  Panic when the shapes differ (add.rs:9-10, sub.rs:9-10).
+    pub fn add_mat(&self, rhs: &DeviceCsr<T>, stream: *mut c_void) -> DeviceCsr<T> {
+        let mut out = std::ptr::null_mut();
+        unsafe { ffi::check(ffi::spal_csr_add(self.h, rhs.h, stream, &mut out)); }
+        DeviceCsr::from_raw(out)
+    }
+    pub fn sub_mat(&self, rhs: &DeviceCsr<T>, stream: *mut c_void) -> DeviceCsr<T> {
+        let mut out = std::ptr::null_mut();
+        unsafe { ffi::check(ffi::spal_csr_sub(self.h, rhs.h, stream, &mut out)); }
+        DeviceCsr::from_raw(out)
+    }
+    pub fn neg_mat(&self, stream: *mut c_void) -> DeviceCsr<T> {
+        let mut out = std::ptr::null_mut();
+        unsafe { ffi::check(ffi::spal_csr_neg(self.h, stream, &mut out)); }
+        DeviceCsr::from_raw(out)
+    }
 }
 
 impl<T: HipScalar> DeviceCsc<T> {
@@ -196,6 +214,23 @@ impl<T: HipScalar> DeviceCsc<T> {
     pub fn mul_mat(&self, rhs: &DeviceCsc<T>, stream: *mut c_void) -> DeviceCsc<T> {
         let mut out = std::ptr::null_mut();
         unsafe { ffi::check(ffi::spal_csc_mul(self.h, rhs.h, stream, &mut out)); }
+        DeviceCsc { h: out, _t: PhantomData }
+    }
+
+    /// Device twins of `impl Add / Sub / Neg for &CscMatrix<T>` (src/csc/ops/{add,sub,neg}.rs), bit-identical.
+    pub fn add_mat(&self, rhs: &DeviceCsc<T>, stream: *mut c_void) -> DeviceCsc<T> {
+        let mut out = std::ptr::null_mut();
+        unsafe { ffi::check(ffi::spal_csc_add(self.h, rhs.h, stream, &mut out)); }
+        DeviceCsc { h: out, _t: PhantomData }
+    }
+    pub fn sub_mat(&self, rhs: &DeviceCsc<T>, stream: *mut c_void) -> DeviceCsc<T> {
+        let mut out = std::ptr::null_mut();
+        unsafe { ffi::check(ffi::spal_csc_sub(self.h, rhs.h, stream, &mut out)); }
+        DeviceCsc { h: out, _t: PhantomData }
+    }
+    pub fn neg_mat(&self, stream: *mut c_void) -> DeviceCsc<T> {
+        let mut out = std::ptr::null_mut();
+        unsafe { ffi::check(ffi::spal_csc_neg(self.h, stream, &mut out)); }
         DeviceCsc { h: out, _t: PhantomData }
     }
 }

@@ -63,6 +63,12 @@ extern "C" {
     pub fn spal_csr_to_csc(a: *mut spal_csr, out: *mut *mut spal_csc) -> c_int;
     pub fn spal_csr_mul(a: *mut spal_csr, b: *mut spal_csr, stream: *mut c_void, out: *mut *mut spal_csr) -> c_int;
     pub fn spal_csc_mul(a: *mut spal_csc, b: *mut spal_csc, stream: *mut c_void, out: *mut *mut spal_csc) -> c_int;
+    pub fn spal_csr_add(a: *mut spal_csr, b: *mut spal_csr, stream: *mut c_void, out: *mut *mut spal_csr) -> c_int;
+    pub fn spal_csr_sub(a: *mut spal_csr, b: *mut spal_csr, stream: *mut c_void, out: *mut *mut spal_csr) -> c_int;
+    pub fn spal_csr_neg(a: *mut spal_csr, stream: *mut c_void, out: *mut *mut spal_csr) -> c_int;
+    pub fn spal_csc_add(a: *mut spal_csc, b: *mut spal_csc, stream: *mut c_void, out: *mut *mut spal_csc) -> c_int;
+    pub fn spal_csc_sub(a: *mut spal_csc, b: *mut spal_csc, stream: *mut c_void, out: *mut *mut spal_csc) -> c_int;
+    pub fn spal_csc_neg(a: *mut spal_csc, stream: *mut c_void, out: *mut *mut spal_csc) -> c_int;
     pub fn spal_coo_upload_f64(device: c_int, nrows: u64, ncols: u64, len: u64, rows: *const u64, cols: *const u64, vals: *const f64, out: *mut *mut spal_coo) -> c_int;
     pub fn spal_coo_upload_f32(device: c_int, nrows: u64, ncols: u64, len: u64, rows: *const u64, cols: *const u64, vals: *const f32, out: *mut *mut spal_coo) -> c_int;
     pub fn spal_coo_destroy(c: *mut spal_coo) -> c_int;

@@ -1,6 +1,6 @@
 //! The operator and conversion impls the reference lacks for dense vectors (its only route to `A * x` is
 //! `&a * &x_as_matrix`, src/csr/ops/mul.rs:5-59), over the device handles of `device.rs`.
-use std::ops::Mul;
+use std::ops::{Add, Mul, Neg, Sub};
 
 use super::device::{DeviceCoo, DeviceCsc, DeviceCsr};
 use super::scalar::HipScalar;
@@ -25,6 +25,33 @@ impl<T: HipScalar> Mul for &DeviceCsr<T> {
 impl<T: HipScalar> Mul for &DeviceCsc<T> {
     type Output = DeviceCsc<T>;
     fn mul(self, rhs: &DeviceCsc<T>) -> DeviceCsc<T> { self.mul_mat(rhs, std::ptr::null_mut()) }
+}
+
+/// C = A + B, A - B, -A between resident matrices: the reference's operators (src/csr/ops/{add,sub,neg}.rs,
+/// src/csc/ops/{add,sub,neg}.rs) on the device, bit-identical.  Panic when the shapes differ (add.rs:9-10).
+impl<T: HipScalar> Add for &DeviceCsr<T> {
+    type Output = DeviceCsr<T>;
+    fn add(self, rhs: &DeviceCsr<T>) -> DeviceCsr<T> { self.add_mat(rhs, std::ptr::null_mut()) }
+}
+impl<T: HipScalar> Sub for &DeviceCsr<T> {
+    type Output = DeviceCsr<T>;
+    fn sub(self, rhs: &DeviceCsr<T>) -> DeviceCsr<T> { self.sub_mat(rhs, std::ptr::null_mut()) }
+}
+impl<T: HipScalar> Neg for &DeviceCsr<T> {
+    type Output = DeviceCsr<T>;
+    fn neg(self) -> DeviceCsr<T> { self.neg_mat(std::ptr::null_mut()) }
+}
+impl<T: HipScalar> Add for &DeviceCsc<T> {
+    type Output = DeviceCsc<T>;
+    fn add(self, rhs: &DeviceCsc<T>) -> DeviceCsc<T> { self.add_mat(rhs, std::ptr::null_mut()) }
+}
+impl<T: HipScalar> Sub for &DeviceCsc<T> {
+    type Output = DeviceCsc<T>;
+    fn sub(self, rhs: &DeviceCsc<T>) -> DeviceCsc<T> { self.sub_mat(rhs, std::ptr::null_mut()) }
+}
+impl<T: HipScalar> Neg for &DeviceCsc<T> {
+    type Output = DeviceCsc<T>;
+    fn neg(self) -> DeviceCsc<T> { self.neg_mat(std::ptr::null_mut()) }
 }
 
 /// One-shot convenience with the reference's operator shape: uploads `self`, multiplies, frees the device copy.
@@ -83,3 +110,27 @@ pub fn csc_mul_hip<T: HipScalar>(a: &CscMatrix<T>, b: &CscMatrix<T>) -> CscMatri
     assert_eq!(a.ncols(), b.nrows());
     (&DeviceCsc::new(a, 0) * &DeviceCsc::new(b, 0)).download()
 }
+/// `&a + &b`, `&a - &b`, `-&a` with the reference's signatures (src/csr/ops/{add,sub,neg}.rs,
+/// src/csc/ops/{add,sub,neg}.rs), computed on the device.
+pub fn csr_add_hip<T: HipScalar>(a: &CsrMatrix<T>, b: &CsrMatrix<T>) -> CsrMatrix<T> {
+    assert_eq!(a.nrows(), b.nrows());
+    assert_eq!(a.ncols(), b.ncols());
+    (&DeviceCsr::new(a, 0) + &DeviceCsr::new(b, 0)).download()
+}
+pub fn csr_sub_hip<T: HipScalar>(a: &CsrMatrix<T>, b: &CsrMatrix<T>) -> CsrMatrix<T> {
+    assert_eq!(a.nrows(), b.nrows());
+    assert_eq!(a.ncols(), b.ncols());
+    (&DeviceCsr::new(a, 0) - &DeviceCsr::new(b, 0)).download()
+}
+pub fn csr_neg_hip<T: HipScalar>(a: &CsrMatrix<T>) -> CsrMatrix<T> { (-&DeviceCsr::new(a, 0)).download() }
+pub fn csc_add_hip<T: HipScalar>(a: &CscMatrix<T>, b: &CscMatrix<T>) -> CscMatrix<T> {
+    assert_eq!(a.nrows(), b.nrows());
+    assert_eq!(a.ncols(), b.ncols());
+    (&DeviceCsc::new(a, 0) + &DeviceCsc::new(b, 0)).download()
+}
+pub fn csc_sub_hip<T: HipScalar>(a: &CscMatrix<T>, b: &CscMatrix<T>) -> CscMatrix<T> {
+    assert_eq!(a.nrows(), b.nrows());
+    assert_eq!(a.ncols(), b.ncols());
+    (&DeviceCsc::new(a, 0) - &DeviceCsc::new(b, 0)).download()
+}
+pub fn csc_neg_hip<T: HipScalar>(a: &CscMatrix<T>) -> CscMatrix<T> { (-&DeviceCsc::new(a, 0)).download() }

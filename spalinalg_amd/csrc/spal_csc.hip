@@ -982,6 +982,7 @@ int spal_csc_set_option(spal_csc_t a, const char *key, int64_t value) {
     {   // options of the sparse x sparse product (this handle as its left operand)
         int st = SPAL_OK;
         if (spgemm_option(key, value, &a->spgemm_route, &a->spgemm_lds_cap, &st)) return st;
+        if (spadd_option(key, value, &a->spadd_tile, &st)) return st;   // ... and of A + B / A - B
     }
     DeviceGuard guard(a->device);
     if (guard.status != SPAL_OK) return guard.status;
@@ -1072,7 +1073,8 @@ int spal_csc_describe(spal_csc_t a, char *buf, size_t buf_len) {
              a->handoff_timeouts + ((a->h_gave_up && __atomic_load_n(a->h_gave_up, __ATOMIC_RELAXED)) ? 1 : 0),
              a->uniform_cols ? 1 : 0,
              (a->rowtiles && a->rowtiles_user != 0 && a->flush == 0) ? 1 : 0, a->rt_rows, a->rt_ntiles, a->rt_xcap, a->rowtiles_failed);
-    return spgemm_describe_append(buf, buf_len, a->spgemm_info);   // a product of spal_csc_mul: how it was built
+    SPAL_TRY(spgemm_describe_append(buf, buf_len, a->spgemm_info));   // a product of spal_csc_mul: how it was built
+    return spadd_describe_append(buf, buf_len, a->spadd_info);        // a result of spal_csc_add / _sub / _neg
 }
 
 }  // extern "C"

@@ -195,6 +195,10 @@ int transpose_device(int device, int elem_size, uint64_t nmajor, uint64_t nminor
 int spgemm_option(const char *key, int64_t value, int *route, int64_t *lds_cap, int *status);
 // ... and the "spgemm" object a product handle adds to its describe() line (no-op for an empty `info`)
 int spgemm_describe_append(char *buf, size_t buf_len, const std::string &info);
+// implemented in spal_spadd.hip: the option "spadd_tile" of either handle type (as spgemm_option), and the "spadd" object
+// a handle built by spal_*_add / _sub / _neg adds to its describe() line
+int spadd_option(const char *key, int64_t value, uint32_t *tile, int *status);
+int spadd_describe_append(char *buf, size_t buf_len, const std::string &info);
 // implemented in spal_csc.hip: handle around device arrays it takes ownership of
 int csc_adopt_device(int device, int elem_size, uint64_t nrows, uint64_t ncols, uint64_t nnz,
                      uint32_t *d_colptr, uint32_t *d_rowind, void *d_values, spal_csc **out);
@@ -279,6 +283,9 @@ struct spal_csr {
     int spgemm_route = 0;          // option "spgemm_route": 0 auto, 1 LDS tiers wherever they fit, 2 every row through the large tier
     int64_t spgemm_lds_cap = 0;    // option "spgemm_lds_cap": 0 default, else the largest product count of a row sent to LDS
     std::string spgemm_info;       // the "spgemm" object of spal_csr_describe (empty: not a product)
+    // A + B, A - B, -A (spal_spadd.hip): the option of this handle as the LEFT operand, and what built it if it is a sum
+    uint32_t spadd_tile = 0;       // option "spadd_tile": merged elements per workgroup, 0 = default
+    std::string spadd_info;        // the "spadd" object of spal_csr_describe (empty: not a sum)
 };
 
 struct spal_csc {
@@ -341,6 +348,8 @@ struct spal_csc {
     int spgemm_route = 0;          // as spal_csr's
     int64_t spgemm_lds_cap = 0;
     std::string spgemm_info;
+    uint32_t spadd_tile = 0;       // as spal_csr's
+    std::string spadd_info;
 };
 
 struct spal_coo {

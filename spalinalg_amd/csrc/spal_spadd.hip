@@ -1,0 +1,634 @@
+// spal_spadd.hip -- C = A + B, C = A - B and C = -A for CSR and CSC on the device: `impl Add / Sub / Neg for
+// &CsrMatrix<T>` (src/csr/ops/{add,sub,neg}.rs) and the same for `&CscMatrix<T>` (src/csc/ops/...), bit-identical to
+// the reference.  CSC runs the same driver on (colptr, rowind): "row" below reads "column" there.
+//
+// MERGE PATH over the two entry streams.  A's entries in stored order are sorted by the key (row, col), and so are
+// B's.  C's entries are the distinct keys of the merge of the two sequences, in merge order, with A before B on equal
+// keys: a matched pair is adjacent, A first.  A B element whose key equals its predecessor's is a DUPLICATE; all other
+// elements are written.  Row i's part of the merged sequence starts at s_i = A.ptr[i] + B.ptr[i] (rows are found by
+// binary search on s: no row ids, no walk over empty rows), and C.ptr[i] = s_i - (duplicates in rows < i).
+//
+// The merged sequence (64-bit positions: nnz(A) + nnz(B) may pass 2^32) is cut into tiles of `tile` elements, so every
+// workgroup gets the same work whatever the row lengths:
+//   spadd_partition  every tile boundary d: the row r with s_r <= d < s_{r+1}, then the A/B split of the diagonal
+//                    d - s_r inside row r (A first on equal keys) -> the tile's slices of A and B are contiguous
+//   spadd_tile<count> the tile's column slices into LDS (coalesced); each thread merges its own `tile / 256` elements
+//                    from a diagonal search in LDS: the tile's non-duplicates, the duplicates per row (integer atomics)
+//   two exclusive scans (tile counts -> output offsets, duplicates per row -> C.ptr), nnz(C) read back once
+//   spadd_tile<fill>  the same walk again: every non-duplicate goes to LDS at its in-tile prefix, then coalesced to C
+// PAIRS SPLIT ACROSS TILES: every tile also reads one element past each end of its slices -- A's entry before its first
+// (a B element at the head of a row that began in an earlier tile compares with it) and B's entry after its last (an A
+// element at the tail compares with it, and a matched one reads that B value from global memory).  Boundaries stay
+// where the arithmetic puts them.
+// Values follow the reference's loop: A only `a`, B only `b` (Add) or `-b` (Sub, an fneg), both `a + b` / `a - b`.
+#include <chrono>
+
+#include <rocprim/device/device_scan.hpp>
+
+#include "spal_internal.hpp"
+
+#pragma clang fp contract(off)
+
+namespace spal {
+namespace {
+
+constexpr int kThreads = 256;              // threads of a tile
+constexpr uint32_t kTileMax = 2048;        // the default tile: 8 merged elements per thread
+constexpr uint32_t kTileMin = 16;
+constexpr uint64_t kOutPad = 256;          // spare entries behind C's arrays (the SpMV kernels' over-read margin)
+
+// the largest r in [lo, hi] with s_r = ap[r] + bp[r] <= d (s_lo <= d)
+__device__ __forceinline__ uint32_t row_of(const uint32_t *__restrict__ ap, const uint32_t *__restrict__ bp, uint32_t lo,
+                                           uint32_t hi, uint64_t d) {
+    while (lo < hi) {
+        const uint32_t mid = (uint32_t)(((uint64_t)lo + hi + 1) / 2);
+        if ((uint64_t)ap[mid] + bp[mid] <= d) lo = mid;
+        else hi = mid - 1;
+    }
+    return lo;
+}
+
+// part[0 .. P): first A entry of every tile, part[P .. 2P): first B entry, part[2P .. 3P): row of the first element;
+// P = tiles + 1 (the last boundary is the end of both operands)
+__global__ __launch_bounds__(256) void spadd_partition(const uint32_t *__restrict__ ap, const uint32_t *__restrict__ ai,
+                                                       const uint32_t *__restrict__ bp, const uint32_t *__restrict__ bi,
+                                                       uint32_t m, uint64_t total, uint32_t tile, uint64_t P,
+                                                       uint32_t *__restrict__ part) {
+    const uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= P) return;
+    const uint64_t d = std::min<uint64_t>(t * tile, total);
+    const uint32_t r = row_of(ap, bp, 0, m - 1, d);
+    const uint32_t sa = ap[r], sb = bp[r];
+    const uint64_t la = ap[r + 1] - sa, lb = bp[r + 1] - sb;
+    const uint64_t k = d - ((uint64_t)sa + sb);
+    uint64_t lo = k > lb ? k - lb : 0, hi = std::min(k, la);
+    while (lo < hi) {   // A entries among the row's first k merged elements (A first on equal columns)
+        const uint64_t mid = (lo + hi) / 2;
+        if (ai[sa + mid] <= bi[sb + (k - 1 - mid)]) lo = mid + 1;
+        else hi = mid;
+    }
+    part[t] = (uint32_t)(sa + lo);
+    part[P + t] = (uint32_t)(sb + (k - lo));
+    part[2 * P + t] = r;
+}
+
+__device__ __forceinline__ uint32_t block_exclusive_sum(uint32_t v, uint32_t *s_wave, uint32_t *total) {
+    const int lane = (int)threadIdx.x % 64, w = (int)threadIdx.x / 64;
+    uint32_t inc = v;
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t u = __shfl_up(inc, o, 64);
+        if (lane >= o) inc += u;
+    }
+    if (lane == 63) s_wave[w] = inc;
+    __syncthreads();
+    uint32_t before = inc - v, all = 0;
+    for (int u = 0; u < kThreads / 64; ++u) {
+        if (u < w) before += s_wave[u];
+        all += s_wave[u];
+    }
+    *total = all;
+    return before;
+}
+
+// what every thread of a tile knows: the operands' pointers, the slices (in LDS) and the elements past their ends
+struct TileCtx {
+    const uint32_t *ap, *bp, *sa, *sb;
+    uint32_t a0, b0, b1, na, nb, r1, a_prev, b_next;
+    uint64_t d0;
+};
+
+// a thread's place in the tile's merge: next A / B entry (tile-local), the current row and its ends in the slices
+struct Cursor {
+    uint32_t r, xa, xb, ea, eb;
+    int64_t ra;         // the row's first A entry, tile-local (negative: the row began before the slice)
+    bool b_beyond;      // the row's B entries go on past the slice
+};
+
+// one merged element: flag = an A element is matched / a B element is a duplicate
+struct Elem {
+    bool from_a, flag;
+    uint32_t xa, xb, row;
+};
+
+__device__ __forceinline__ void enter_row(const TileCtx &c, Cursor &w, uint32_t q) {
+    w.r = q;
+    const uint32_t pa = c.ap[q], pa1 = c.ap[q + 1], pb1 = c.bp[q + 1];
+    w.ra = (int64_t)pa - c.a0;
+    w.ea = std::min(pa1 - c.a0, c.na);
+    w.eb = std::min(pb1 - c.b0, c.nb);
+    w.b_beyond = pb1 > c.b1;
+}
+
+__device__ __forceinline__ Cursor cursor_at(const TileCtx &c, uint32_t r, uint32_t ja, uint32_t jb, bool any) {
+    Cursor w{r, ja, jb, 0, 0, 0, false};
+    if (any) enter_row(c, w, r);
+    return w;
+}
+
+// the element at tile-local position p (the cursor's next one)
+__device__ __forceinline__ Elem step(const TileCtx &c, Cursor &w, uint32_t p) {
+    if (w.xa == w.ea && w.xb == w.eb) {   // the row is done: the next row with elements (binary search over empty ones)
+        const uint64_t d = c.d0 + p;
+        uint32_t q = w.r + 1;
+        if (q < c.r1 && (uint64_t)c.ap[q + 1] + c.bp[q + 1] <= d) q = row_of(c.ap, c.bp, q + 1, c.r1, d);
+        enter_row(c, w, q);
+    }
+    Elem e;
+    e.xa = w.xa;
+    e.xb = w.xb;
+    e.row = w.r;
+    if (w.xa < w.ea && (w.xb >= w.eb || c.sa[w.xa] <= c.sb[w.xb])) {
+        const uint32_t col = c.sa[w.xa];
+        e.from_a = true;
+        e.flag = w.xb < w.eb ? c.sb[w.xb] == col : (w.b_beyond && c.b_next == col);
+        ++w.xa;
+    } else {
+        const uint32_t col = c.sb[w.xb];
+        const int64_t pa = (int64_t)w.xa - 1;   // the row's A entry before this one, if any
+        e.from_a = false;
+        e.flag = pa >= w.ra && (pa >= 0 ? c.sa[pa] : c.a_prev) == col;
+        ++w.xb;
+    }
+    return e;
+}
+
+// One tile of the merged sequence per workgroup.  FILL = false: the tile's non-duplicates -> tile_cnt[t], duplicates
+// per row -> row_dup[r] (atomics).  FILL = true: the tile's entries of C at tile_off[t] ...
+template <typename T, bool FILL, bool SUB>
+__global__ __launch_bounds__(kThreads) void spadd_tile(const uint32_t *__restrict__ ap, const uint32_t *__restrict__ ai,
+                                                       const T *__restrict__ av, const uint32_t *__restrict__ bp,
+                                                       const uint32_t *__restrict__ bi, const T *__restrict__ bv,
+                                                       uint32_t nnz_b, uint32_t tile, const uint32_t *__restrict__ part,
+                                                       uint64_t P, unsigned long long *__restrict__ tile_cnt,
+                                                       uint32_t *__restrict__ row_dup,
+                                                       const unsigned long long *__restrict__ tile_off,
+                                                       uint32_t *__restrict__ cci, T *__restrict__ cv) {
+    __shared__ uint32_t s_col[kTileMax];                 // A's columns [0, na), then B's [na, na + nb)
+    __shared__ T s_val[FILL ? kTileMax : 1];
+    __shared__ uint32_t o_col[FILL ? kTileMax : 1];      // the tile's part of C
+    __shared__ T o_val[FILL ? kTileMax : 1];
+    __shared__ uint32_t s_wave[kThreads / 64];
+    const uint64_t t = blockIdx.x;
+    const uint32_t a0 = part[t], a1 = part[t + 1], b0 = part[P + t], b1 = part[P + t + 1];
+    const uint32_t r0 = part[2 * P + t], r1 = part[2 * P + t + 1];
+    const uint32_t na = a1 - a0, n = na + (b1 - b0), nb = b1 - b0;
+    const uint64_t d0 = t * tile;
+    {   // the slices into LDS: every thread issues all its loads (one per kThreads elements) before it stores any
+        constexpr int L = kTileMax / kThreads;
+        uint32_t col[L];
+        T val[L];
+#pragma unroll
+        for (int k = 0; k < L; ++k) {
+            const uint32_t x = threadIdx.x + k * kThreads;
+            if (x < n) {
+                const bool from_a = x < na;
+                const uint64_t q = from_a ? (uint64_t)a0 + x : (uint64_t)b0 + (x - na);
+                col[k] = (from_a ? ai : bi)[q];
+                if constexpr (FILL) val[k] = (from_a ? av : bv)[q];
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < L; ++k) {
+            const uint32_t x = threadIdx.x + k * kThreads;
+            if (x < n) {
+                s_col[x] = col[k];
+                if constexpr (FILL) s_val[x] = val[k];
+            }
+        }
+    }
+    // one element past each end: A's entry before the slice, B's entry after it
+    const uint32_t a_prev = a0 ? ai[a0 - 1] : 0u;
+    const uint32_t b_next = b1 < nnz_b ? bi[b1] : 0u;
+    __syncthreads();
+    const uint32_t *sa = s_col, *sb = s_col + na;
+
+    // this thread's first element: its row, then the split of the row's diagonal (inside the tile's slices)
+    const uint32_t E = (tile + kThreads - 1) / kThreads;
+    const uint32_t p0 = std::min<uint32_t>(threadIdx.x * E, n), pend = std::min<uint32_t>(p0 + E, n);
+    uint32_t r = r0, ja = 0, jb = 0;
+    if (p0 < pend) {
+        const uint64_t d = d0 + p0;
+        r = row_of(ap, bp, r0, r1, d);
+        const int64_t SA = ap[r], SB = bp[r];
+        const int64_t K = (int64_t)(d - (uint64_t)SA - (uint64_t)SB);
+        const int64_t LA = (int64_t)ap[r + 1] - SA, LB = (int64_t)bp[r + 1] - SB;
+        int64_t lo = std::max(std::max<int64_t>(0, K - LB), std::max<int64_t>((int64_t)a0 - SA, K - ((int64_t)b1 - SB)));
+        int64_t hi = std::min(std::min(K, LA), std::min<int64_t>((int64_t)a1 - SA, K - ((int64_t)b0 - SB)));
+        while (lo < hi) {
+            const int64_t mid = (lo + hi) / 2;
+            if (sa[SA + mid - a0] <= sb[SB + (K - 1 - mid) - b0]) lo = mid + 1;
+            else hi = mid;
+        }
+        ja = (uint32_t)(SA + lo - a0);
+        jb = p0 - ja;
+    }
+
+    const TileCtx c{ap, bp, sa, sb, a0, b0, b1, na, nb, r1, a_prev, b_next, d0};
+    if constexpr (!FILL) {
+        Cursor w = cursor_at(c, r, ja, jb, p0 < pend);
+        uint32_t keep = 0, dups = 0, dup_row = r;
+        for (uint32_t p = p0; p < pend; ++p) {
+            const Elem e = step(c, w, p);
+            if (!e.from_a && e.flag) {
+                if (e.row != dup_row) {
+                    if (dups) atomicAdd(&row_dup[dup_row], dups);
+                    dups = 0;
+                    dup_row = e.row;
+                }
+                ++dups;
+            } else {
+                ++keep;
+            }
+        }
+        if (dups) atomicAdd(&row_dup[dup_row], dups);
+        uint32_t total = 0;
+        (void)block_exclusive_sum(keep, s_wave, &total);
+        if (threadIdx.x == 0) tile_cnt[t] = total;
+    } else {
+        uint32_t keep = 0;
+        Cursor w = cursor_at(c, r, ja, jb, p0 < pend);
+        for (uint32_t p = p0; p < pend; ++p) {
+            const Elem e = step(c, w, p);
+            keep += (e.from_a || !e.flag) ? 1u : 0u;
+        }
+        uint32_t total = 0;
+        uint32_t o = block_exclusive_sum(keep, s_wave, &total);
+        w = cursor_at(c, r, ja, jb, p0 < pend);
+        for (uint32_t p = p0; p < pend; ++p) {
+            const Elem e = step(c, w, p);
+            if (e.from_a) {
+                const T a = s_val[e.xa];
+                T v = a;
+                if (e.flag) {
+                    const T b = e.xb < nb ? s_val[na + e.xb] : bv[b1];   // (the pair's B entry past the slice)
+                    v = SUB ? a - b : a + b;
+                }
+                o_col[o] = sa[e.xa];
+                o_val[o] = v;
+                ++o;
+            } else if (!e.flag) {
+                const T b = s_val[na + e.xb];
+                o_col[o] = sb[e.xb];
+                o_val[o] = SUB ? -b : b;
+                ++o;
+            }
+        }
+        __syncthreads();
+        const unsigned long long base = tile_off[t];
+        for (uint32_t x = threadIdx.x; x < total; x += kThreads) {
+            cci[base + x] = o_col[x];
+            cv[base + x] = o_val[x];
+        }
+    }
+}
+
+// C.ptr[i] = s_i - (duplicates in rows < i)
+__global__ __launch_bounds__(256) void spadd_rowptr(const uint32_t *__restrict__ ap, const uint32_t *__restrict__ bp,
+                                                    const uint32_t *__restrict__ dscan, uint64_t n,
+                                                    uint32_t *__restrict__ cp) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) cp[i] = (uint32_t)((uint64_t)ap[i] + bp[i] - dscan[i]);
+}
+
+// y = -x, 16 bytes per thread (an fneg: the sign bit flips for +-0, +-inf and NaN alike); the tail element-wise
+template <typename T>
+__global__ __launch_bounds__(256) void spadd_neg(const T *__restrict__ x, T *__restrict__ y, uint64_t n) {
+    constexpr int W = 16 / sizeof(T);
+    typedef T V __attribute__((ext_vector_type(W)));
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    const uint64_t nv = n / W;
+    if (i < nv) {
+        reinterpret_cast<V *>(y)[i] = -reinterpret_cast<const V *>(x)[i];
+    } else if (i - nv < n % W) {
+        const uint64_t e = nv * W + (i - nv);
+        y[e] = -x[e];
+    }
+}
+
+// ---- host ----------------------------------------------------------------------------------------------------------
+struct Operand {
+    uint64_t nmajor;
+    uint64_t nnz;
+    const uint32_t *ptr, *ind;
+    const void *val;
+};
+
+struct Sum {
+    uint32_t *ptr = nullptr, *ind = nullptr;
+    void *val = nullptr;
+    uint64_t nnz = 0, cap = 0, matched = 0, tiles = 0;
+    uint32_t tile = 0;
+    float kernel_ms = 0.f;
+};
+
+inline unsigned grid_of(uint64_t n, unsigned per) { return (unsigned)((n + per - 1) / per); }
+
+// device time of the kernels: [e[0], e[1]) the count pass and the scans, [e[2], e[3]) the fill (not the host's read
+// back and allocation between them)
+struct Events {
+    hipEvent_t e[4] = {};
+    ~Events() {
+        for (hipEvent_t x : e)
+            if (x) (void)hipEventDestroy(x);
+    }
+    hipError_t create() {
+        for (hipEvent_t &x : e) {
+            const hipError_t r = hipEventCreate(&x);
+            if (r != hipSuccess) return r;
+        }
+        return hipSuccess;
+    }
+    static float span(hipEvent_t a, hipEvent_t b) {
+        float v = 0.f;
+        return hipEventElapsedTime(&v, a, b) == hipSuccess ? v : 0.f;
+    }
+    float ms(bool two) const { return span(e[0], e[1]) + (two ? span(e[2], e[3]) : 0.f); }
+};
+
+// the two exclusive scans of the count pass, sharing one temporary block; synchronises `st`
+hipError_t scan_two(const unsigned long long *tin, unsigned long long *tout, uint64_t tn, const uint32_t *rin,
+                    uint32_t *rout, uint64_t rn, hipStream_t st) {
+    size_t b1 = 0, b2 = 0;
+    hipError_t e = rocprim::exclusive_scan(nullptr, b1, tin, tout, 0ull, (size_t)tn, rocprim::plus<unsigned long long>(), st);
+    if (e == hipSuccess) e = rocprim::exclusive_scan(nullptr, b2, rin, rout, 0u, (size_t)rn, rocprim::plus<uint32_t>(), st);
+    if (e != hipSuccess) return e;
+    DevBuf tmp;
+    e = tmp.alloc(std::max(b1, b2));
+    if (e == hipSuccess) e = rocprim::exclusive_scan(tmp.p, b1, tin, tout, 0ull, (size_t)tn, rocprim::plus<unsigned long long>(), st);
+    if (e == hipSuccess) e = rocprim::exclusive_scan(tmp.p, b2, rin, rout, 0u, (size_t)rn, rocprim::plus<uint32_t>(), st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);   // (tmp returns to the allocator on exit)
+    return e;
+}
+
+template <typename T, bool SUB>
+int spadd_t(const char *fn, const Operand &A, const Operand &B, uint32_t tile, hipStream_t st, Sum &out) {
+    const uint64_t m = A.nmajor, total = A.nnz + B.nnz;
+    const uint64_t tiles = (total + tile - 1) / tile, P = tiles + 1;
+    out.tile = tile;
+    out.tiles = tiles;
+    Events ev;
+    SPAL_HIP_TRY(ev.create());
+    DevBuf part, tcnt, toff, rdup, rscan;
+    SPAL_HIP_TRY(part.alloc(P * 3 * 4));
+    SPAL_HIP_TRY(tcnt.alloc(P * 8));
+    SPAL_HIP_TRY(toff.alloc(P * 8));
+    SPAL_HIP_TRY(rdup.alloc((m + 1) * 4));
+    SPAL_HIP_TRY(rscan.alloc((m + 1) * 4));
+    SPAL_HIP_TRY(hipEventRecord(ev.e[0], st));
+    SPAL_HIP_TRY(hipMemsetAsync(rdup.p, 0, (m + 1) * 4, st));
+    SPAL_HIP_TRY(hipMemsetAsync(tcnt.as<unsigned long long>() + tiles, 0, 8, st));
+    const uint32_t *part_p = part.as<uint32_t>();
+    if (tiles) {
+        hipLaunchKernelGGL(spadd_partition, dim3(grid_of(P, 256)), dim3(256), 0, st, A.ptr, A.ind, B.ptr, B.ind,
+                           (uint32_t)m, total, tile, P, part.as<uint32_t>());
+        hipLaunchKernelGGL((spadd_tile<T, false, SUB>), dim3((unsigned)tiles), dim3(kThreads), 0, st, A.ptr, A.ind,
+                           (const T *)A.val, B.ptr, B.ind, (const T *)B.val, (uint32_t)B.nnz, tile, part_p, P,
+                           tcnt.as<unsigned long long>(), rdup.as<uint32_t>(), nullptr, nullptr, nullptr);
+        SPAL_HIP_TRY(hipGetLastError());
+    }
+    SPAL_HIP_TRY(scan_two(tcnt.as<unsigned long long>(), toff.as<unsigned long long>(), P, rdup.as<uint32_t>(),
+                          rscan.as<uint32_t>(), m + 1, st));
+    SPAL_HIP_TRY(hipEventRecord(ev.e[1], st));
+    unsigned long long nnz = 0;
+    uint32_t matched = 0;
+    SPAL_HIP_TRY(hipMemcpyAsync(&nnz, toff.as<unsigned long long>() + tiles, 8, hipMemcpyDeviceToHost, st));
+    SPAL_HIP_TRY(hipMemcpyAsync(&matched, rscan.as<uint32_t>() + m, 4, hipMemcpyDeviceToHost, st));
+    SPAL_HIP_TRY(hipStreamSynchronize(st));
+    if (nnz + matched != total)
+        return fail(SPAL_ERR_HIP, "%s: internal error: %llu entries + %u matched pairs != %llu merged", fn, nnz, matched,
+                    (unsigned long long)total);
+    if (nnz > kMaxEntries)
+        return fail(SPAL_ERR_UNSUPPORTED, "%s: the result has %llu entries, more than 32-bit device offsets address", fn, nnz);
+    DevBuf cp, ci, cv;
+    const uint64_t cap = nnz + kOutPad;
+    SPAL_HIP_TRY(cp.alloc((m + 1) * 4));
+    SPAL_HIP_TRY(ci.alloc(cap * 4));
+    SPAL_HIP_TRY(cv.alloc(cap * sizeof(T)));
+    SPAL_HIP_TRY(hipMemsetAsync((char *)ci.p + nnz * 4, 0, kOutPad * 4, st));
+    SPAL_HIP_TRY(hipMemsetAsync((char *)cv.p + nnz * sizeof(T), 0, kOutPad * sizeof(T), st));
+    SPAL_HIP_TRY(hipEventRecord(ev.e[2], st));
+    hipLaunchKernelGGL(spadd_rowptr, dim3(grid_of(m + 1, 256)), dim3(256), 0, st, A.ptr, B.ptr, rscan.as<uint32_t>(),
+                       m + 1, cp.as<uint32_t>());
+    if (tiles)
+        hipLaunchKernelGGL((spadd_tile<T, true, SUB>), dim3((unsigned)tiles), dim3(kThreads), 0, st, A.ptr, A.ind,
+                           (const T *)A.val, B.ptr, B.ind, (const T *)B.val, (uint32_t)B.nnz, tile, part_p, P, nullptr,
+                           nullptr, toff.as<unsigned long long>(), ci.as<uint32_t>(), cv.as<T>());
+    SPAL_HIP_TRY(hipGetLastError());
+    SPAL_HIP_TRY(hipEventRecord(ev.e[3], st));
+    SPAL_HIP_TRY(hipStreamSynchronize(st));
+    out.kernel_ms = ev.ms(true);
+    out.nnz = nnz;
+    out.matched = matched;
+    out.cap = cap;
+    out.ptr = (uint32_t *)cp.release();
+    out.ind = (uint32_t *)ci.release();
+    out.val = cv.release();
+    return SPAL_OK;
+}
+
+int spadd(const char *fn, int elem_size, bool sub, const Operand &A, const Operand &B, uint32_t tile, hipStream_t st,
+          Sum &out) {
+    tile = tile ? tile : kTileMax;
+    if (elem_size == 8)
+        return sub ? spadd_t<double, true>(fn, A, B, tile, st, out) : spadd_t<double, false>(fn, A, B, tile, st, out);
+    return sub ? spadd_t<float, true>(fn, A, B, tile, st, out) : spadd_t<float, false>(fn, A, B, tile, st, out);
+}
+
+// -A: the index arrays copied, the values negated
+int spneg(int elem_size, const Operand &A, hipStream_t st, Sum &out) {
+    const uint64_t m = A.nmajor, nnz = A.nnz, cap = nnz + kOutPad;
+    Events ev;
+    SPAL_HIP_TRY(ev.create());
+    DevBuf cp, ci, cv;
+    SPAL_HIP_TRY(cp.alloc((m + 1) * 4));
+    SPAL_HIP_TRY(ci.alloc(cap * 4));
+    SPAL_HIP_TRY(cv.alloc(cap * elem_size));
+    SPAL_HIP_TRY(hipEventRecord(ev.e[0], st));
+    SPAL_HIP_TRY(hipMemcpyAsync(cp.p, A.ptr, (m + 1) * 4, hipMemcpyDeviceToDevice, st));
+    if (nnz) SPAL_HIP_TRY(hipMemcpyAsync(ci.p, A.ind, nnz * 4, hipMemcpyDeviceToDevice, st));
+    SPAL_HIP_TRY(hipMemsetAsync((char *)ci.p + nnz * 4, 0, kOutPad * 4, st));
+    SPAL_HIP_TRY(hipMemsetAsync((char *)cv.p + nnz * elem_size, 0, kOutPad * elem_size, st));
+    if (nnz) {
+        const uint64_t threads = nnz / (16 / elem_size) + 16 / elem_size;
+        if (elem_size == 8)
+            hipLaunchKernelGGL(spadd_neg<double>, dim3(grid_of(threads, 256)), dim3(256), 0, st, (const double *)A.val,
+                               cv.as<double>(), nnz);
+        else
+            hipLaunchKernelGGL(spadd_neg<float>, dim3(grid_of(threads, 256)), dim3(256), 0, st, (const float *)A.val,
+                               cv.as<float>(), nnz);
+        SPAL_HIP_TRY(hipGetLastError());
+    }
+    SPAL_HIP_TRY(hipEventRecord(ev.e[1], st));
+    SPAL_HIP_TRY(hipStreamSynchronize(st));
+    out.kernel_ms = ev.ms(false);
+    out.nnz = nnz;
+    out.cap = cap;
+    out.ptr = (uint32_t *)cp.release();
+    out.ind = (uint32_t *)ci.release();
+    out.val = cv.release();
+    return SPAL_OK;
+}
+
+std::string info_json(const char *op, const Sum &r, double plan_ms, double ms) {
+    char buf[384];
+    snprintf(buf, sizeof buf,
+             "{\"op\": \"%s\", \"tile\": %u, \"tiles\": %llu, \"matched\": %llu, \"nnz\": %llu, \"kernel_ms\": %.4f, "
+             "\"plan_ms\": %.3f, \"call_ms\": %.3f}",
+             op, r.tile, (unsigned long long)r.tiles, (unsigned long long)r.matched, (unsigned long long)r.nnz,
+             (double)r.kernel_ms, plan_ms, ms);
+    return buf;
+}
+
+double ms_since(std::chrono::steady_clock::time_point t0) {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+void free_sum(Sum &r) {
+    (void)dev_free(r.ptr);
+    (void)dev_free(r.ind);
+    (void)dev_free(r.val);
+    r.ptr = r.ind = nullptr;
+    r.val = nullptr;
+}
+
+// the checks of add.rs:9-10 / sub.rs:9-10 in their order, then what the device needs
+template <typename H>
+int check_pair(const char *fn, H a, H b, H *out) {
+    if (!a || !b || !out) return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: null argument", fn);
+    *out = nullptr;
+    if (a->nrows != b->nrows)
+        return fail(SPAL_ERR_INVALID_ARGUMENT, "assertion failed: nrows == rhs.nrows (left: %llu, right: %llu)",
+                    (unsigned long long)a->nrows, (unsigned long long)b->nrows);
+    if (a->ncols != b->ncols)
+        return fail(SPAL_ERR_INVALID_ARGUMENT, "assertion failed: ncols == rhs.ncols (left: %llu, right: %llu)",
+                    (unsigned long long)a->ncols, (unsigned long long)b->ncols);
+    if (a->device != b->device)
+        return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: operands on devices %d and %d", fn, a->device, b->device);
+    if (a->elem_size != b->elem_size)
+        return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: operands of element sizes %d and %d", fn, a->elem_size, b->elem_size);
+    return SPAL_OK;
+}
+
+int csr_binary(const char *fn, bool sub, spal_csr_t a, spal_csr_t b, void *stream, spal_csr_t *out) {
+    SPAL_TRY(check_pair(fn, a, b, out));
+    if (!a->parts.empty() || !b->parts.empty())
+        return fail(SPAL_ERR_UNSUPPORTED, "%s: an operand of more than 2^32 - 65537 entries (row blocks)", fn);
+    DeviceGuard guard(a->device);
+    if (guard.status != SPAL_OK) return guard.status;
+    const auto t0 = std::chrono::steady_clock::now();
+    const Operand A{a->nrows, a->nnz, a->d_rowptr, a->d_colind, a->d_values};
+    const Operand B{b->nrows, b->nnz, b->d_rowptr, b->d_colind, b->d_values};
+    Sum r;
+    SPAL_TRY(spadd(fn, a->elem_size, sub, A, B, a->spadd_tile, (hipStream_t)stream, r));
+    const auto tp = std::chrono::steady_clock::now();
+    // eager plan, as spal_csr_mul's result (a lazily planned handle can reach csr_blockwin_or_split re-entrantly)
+    const int st = csr_adopt_device(a->device, a->elem_size, a->nrows, a->ncols, r.nnz, r.cap, r.ptr, r.ind, r.val, out,
+                                    nullptr, true, false);
+    if (st != SPAL_OK) {
+        free_sum(r);
+        return st;
+    }
+    (*out)->spadd_info = info_json(sub ? "sub" : "add", r, ms_since(tp), ms_since(t0));
+    return SPAL_OK;
+}
+
+int csc_binary(const char *fn, bool sub, spal_csc_t a, spal_csc_t b, void *stream, spal_csc_t *out) {
+    SPAL_TRY(check_pair(fn, a, b, out));
+    DeviceGuard guard(a->device);
+    if (guard.status != SPAL_OK) return guard.status;
+    const auto t0 = std::chrono::steady_clock::now();
+    const Operand A{a->ncols, a->nnz, a->d_colptr, a->d_rowind, a->d_values};
+    const Operand B{b->ncols, b->nnz, b->d_colptr, b->d_rowind, b->d_values};
+    Sum r;
+    SPAL_TRY(spadd(fn, a->elem_size, sub, A, B, a->spadd_tile, (hipStream_t)stream, r));
+    const auto tp = std::chrono::steady_clock::now();
+    const int st = csc_adopt_device(a->device, a->elem_size, a->nrows, a->ncols, r.nnz, r.ptr, r.ind, r.val, out);
+    if (st != SPAL_OK) {
+        free_sum(r);
+        return st;
+    }
+    (*out)->spadd_info = info_json(sub ? "sub" : "add", r, ms_since(tp), ms_since(t0));
+    return SPAL_OK;
+}
+
+}  // namespace
+
+int spadd_option(const char *key, int64_t value, uint32_t *tile, int *status) {
+    if (strcmp(key, "spadd_tile")) return 0;
+    const bool pow2 = value > 0 && (value & (value - 1)) == 0;
+    *status = (value == 0 || (pow2 && value >= (int64_t)kTileMin && value <= (int64_t)kTileMax))
+                  ? SPAL_OK
+                  : fail(SPAL_ERR_INVALID_ARGUMENT, "spadd_tile must be 0 (default, %u) or a power of two in [%u, %u]",
+                         kTileMax, kTileMin, kTileMax);
+    if (*status == SPAL_OK) *tile = (uint32_t)value;
+    return 1;
+}
+
+int spadd_describe_append(char *buf, size_t buf_len, const std::string &info) {
+    if (info.empty()) return SPAL_OK;
+    const size_t len = strnlen(buf, buf_len);
+    if (len == 0 || buf[len - 1] != '}' || len + info.size() + 16 > buf_len)
+        return fail(SPAL_ERR_INVALID_ARGUMENT, "describe: buffer of %zu bytes too small", buf_len);
+    snprintf(buf + len - 1, buf_len - (len - 1), ", \"spadd\": %s}", info.c_str());
+    return SPAL_OK;
+}
+
+}  // namespace spal
+
+using namespace spal;
+
+extern "C" {
+
+int spal_csr_add(spal_csr_t a, spal_csr_t b, void *stream, spal_csr_t *out) {
+    return csr_binary("spal_csr_add", false, a, b, stream, out);
+}
+int spal_csr_sub(spal_csr_t a, spal_csr_t b, void *stream, spal_csr_t *out) {
+    return csr_binary("spal_csr_sub", true, a, b, stream, out);
+}
+int spal_csc_add(spal_csc_t a, spal_csc_t b, void *stream, spal_csc_t *out) {
+    return csc_binary("spal_csc_add", false, a, b, stream, out);
+}
+int spal_csc_sub(spal_csc_t a, spal_csc_t b, void *stream, spal_csc_t *out) {
+    return csc_binary("spal_csc_sub", true, a, b, stream, out);
+}
+
+int spal_csr_neg(spal_csr_t a, void *stream, spal_csr_t *out) {
+    if (!a || !out) return fail(SPAL_ERR_INVALID_ARGUMENT, "spal_csr_neg: null argument");
+    *out = nullptr;
+    if (!a->parts.empty())
+        return fail(SPAL_ERR_UNSUPPORTED, "spal_csr_neg: an operand of more than 2^32 - 65537 entries (row blocks)");
+    DeviceGuard guard(a->device);
+    if (guard.status != SPAL_OK) return guard.status;
+    const auto t0 = std::chrono::steady_clock::now();
+    Sum r;
+    SPAL_TRY(spneg(a->elem_size, Operand{a->nrows, a->nnz, a->d_rowptr, a->d_colind, a->d_values}, (hipStream_t)stream, r));
+    const auto tp = std::chrono::steady_clock::now();
+    const int st = csr_adopt_device(a->device, a->elem_size, a->nrows, a->ncols, r.nnz, r.cap, r.ptr, r.ind, r.val, out,
+                                    nullptr, true, false);
+    if (st != SPAL_OK) {
+        free_sum(r);
+        return st;
+    }
+    (*out)->spadd_info = info_json("neg", r, ms_since(tp), ms_since(t0));
+    return SPAL_OK;
+}
+
+int spal_csc_neg(spal_csc_t a, void *stream, spal_csc_t *out) {
+    if (!a || !out) return fail(SPAL_ERR_INVALID_ARGUMENT, "spal_csc_neg: null argument");
+    *out = nullptr;
+    DeviceGuard guard(a->device);
+    if (guard.status != SPAL_OK) return guard.status;
+    const auto t0 = std::chrono::steady_clock::now();
+    Sum r;
+    SPAL_TRY(spneg(a->elem_size, Operand{a->ncols, a->nnz, a->d_colptr, a->d_rowind, a->d_values}, (hipStream_t)stream, r));
+    const auto tp = std::chrono::steady_clock::now();
+    const int st = csc_adopt_device(a->device, a->elem_size, a->nrows, a->ncols, r.nnz, r.ptr, r.ind, r.val, out);
+    if (st != SPAL_OK) {
+        free_sum(r);
+        return st;
+    }
+    (*out)->spadd_info = info_json("neg", r, ms_since(tp), ms_since(t0));
+    return SPAL_OK;
+}
+
+}  // extern "C"

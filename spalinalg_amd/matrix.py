@@ -11,6 +11,8 @@ Names, argument meaning and error behaviour follow the reference
   binding adds as ``impl Mul<&[T]> for &CsrMatrix<T>``.
 * ``a * b`` / ``a @ b`` with a matrix of the same format: the reference's own
   ``impl Mul for &CsrMatrix<T>`` / ``&CscMatrix<T>``, on the device, bit-identical.
+* ``a + b``, ``a - b`` and ``-a``: ``impl Add / Sub / Neg`` of the same types
+  (src/csr/ops/{add,sub,neg}.rs, src/csc/ops/...), on the device, bit-identical.
 * ``CsrMatrix.from_coo(coo)`` == ``CsrMatrix::from(&coo)``
   (src/csr/conv/coo.rs:3-116), assembled on the device.
 * ``CscMatrix`` / ``CooMatrix`` likewise (src/csc.rs, src/coo.rs).
@@ -139,6 +141,14 @@ class _DeviceMatrix:
         return (torch.as_tensor(_View(self, xp, ncols, self.dtype), device=dev),
                 torch.as_tensor(_View(self, yp, nrows, self.dtype), device=dev))
 
+    def _binary(self, op: str, other, stream):
+        """spal_<kind>_add / _sub: a new handle of this class (both operands of one format, as in the reference)."""
+        if type(other) is not type(self):
+            raise TypeError(f"{type(self).__name__}.{op} needs a {type(self).__name__} (the reference has no mixed operands)")
+        out = vp()
+        check(self._fn(op)(self._h, other._h, _stream_ptr(stream), C.byref(out)))
+        return type(self)(out, self.dtype, self.device)
+
     def autotune(self, x, y, iters: int = 30) -> dict:
         """Times the plan's kernel variants on torch device vectors x, y and keeps
         the fastest (setup-time; synchronises the current stream)."""
@@ -207,6 +217,21 @@ class DeviceCsr(_DeviceMatrix):
         check(_ffi.lib().spal_csr_mul(self._h, other._h, _stream_ptr(stream), C.byref(out)))
         return DeviceCsr(out, self.dtype, self.device)
 
+    def add(self, other: "DeviceCsr", stream=None) -> "DeviceCsr":
+        """C = self + other on the device (spal_csr_add: `impl Add for &CsrMatrix<T>`, src/csr/ops/add.rs:5-75,
+        bit-identical); synchronises `stream`.  Option "spadd_tile" is read from self."""
+        return self._binary("add", other, stream)
+
+    def sub(self, other: "DeviceCsr", stream=None) -> "DeviceCsr":
+        """C = self - other (spal_csr_sub: `impl Sub for &CsrMatrix<T>`, src/csr/ops/sub.rs:5-75)."""
+        return self._binary("sub", other, stream)
+
+    def neg(self, stream=None) -> "DeviceCsr":
+        """C = -self (spal_csr_neg: `impl Neg for &CsrMatrix<T>`, src/csr/ops/neg.rs:5-17)."""
+        out = vp()
+        check(_ffi.lib().spal_csr_neg(self._h, _stream_ptr(stream), C.byref(out)))
+        return DeviceCsr(out, self.dtype, self.device)
+
 
 class DeviceCsc(_DeviceMatrix):
     _kind = "csc"
@@ -238,6 +263,20 @@ class DeviceCsc(_DeviceMatrix):
             raise TypeError("DeviceCsc.mul needs a DeviceCsc (the reference has no mixed CSR x CSC Mul)")
         out = vp()
         check(_ffi.lib().spal_csc_mul(self._h, other._h, _stream_ptr(stream), C.byref(out)))
+        return DeviceCsc(out, self.dtype, self.device)
+
+    def add(self, other: "DeviceCsc", stream=None) -> "DeviceCsc":
+        """C = self + other on the device (spal_csc_add: `impl Add for &CscMatrix<T>`, src/csc/ops/add.rs:5-70)."""
+        return self._binary("add", other, stream)
+
+    def sub(self, other: "DeviceCsc", stream=None) -> "DeviceCsc":
+        """C = self - other (spal_csc_sub: `impl Sub for &CscMatrix<T>`, src/csc/ops/sub.rs:5-70)."""
+        return self._binary("sub", other, stream)
+
+    def neg(self, stream=None) -> "DeviceCsc":
+        """C = -self (spal_csc_neg: `impl Neg for &CscMatrix<T>`, src/csc/ops/neg.rs:5-17)."""
+        out = vp()
+        check(_ffi.lib().spal_csc_neg(self._h, _stream_ptr(stream), C.byref(out)))
         return DeviceCsc(out, self.dtype, self.device)
 
 
@@ -501,6 +540,40 @@ class _Compressed:
         return self._mul_vec(x)
 
     __matmul__ = __mul__
+
+    def _add_sub(self, op: str, other, device: int = 0):
+        """`&self + &other` / `&self - &other` (src/csr/ops/{add,sub}.rs:5-75, src/csc/ops/...) on the device; the result
+        is downloaded and keeps its device handle, as `_mul_mat`'s does."""
+        if not isinstance(other, _Compressed):
+            return NotImplemented
+        sign = "+" if op == "add" else "-"
+        if type(other) is not type(self):
+            raise TypeError(f"{type(self).__name__} {sign} {type(other).__name__}: the reference has no mixed {op.title()}")
+        # assert_eq!(self.nrows(), rhs.nrows()); assert_eq!(self.ncols(), rhs.ncols())  add.rs:9-10, sub.rs:9-10
+        if self._nrows != other._nrows:
+            raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT,
+                        f"assertion failed: nrows == rhs.nrows (left: {self._nrows}, right: {other._nrows})")
+        if self._ncols != other._ncols:
+            raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT,
+                        f"assertion failed: ncols == rhs.ncols (left: {self._ncols}, right: {other._ncols})")
+        dev = getattr(self.device(device), op)(other.device(device))
+        return self._adopt_result(dev, device)
+
+    def _adopt_result(self, dev, device: int):
+        ptr, ind, val = dev.download()
+        out = type(self)._trusted(self._nrows, self._ncols, ptr, ind, val)
+        out._dev[device] = dev
+        return out
+
+    def __add__(self, other):
+        return self._add_sub("add", other)
+
+    def __sub__(self, other):
+        return self._add_sub("sub", other)
+
+    def __neg__(self):
+        """`-&self` (src/csr/ops/neg.rs:5-17 / src/csc/ops/neg.rs:5-17) on the device."""
+        return self._adopt_result(self.device().neg(), 0)
 
 
 class CsrMatrix(_Compressed):
