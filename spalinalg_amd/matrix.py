@@ -258,7 +258,8 @@ class DeviceCsc(_DeviceMatrix):
         return DeviceCsr(out, self.dtype, self.device)
 
     def mul(self, other: "DeviceCsc", stream=None) -> "DeviceCsc":
-        """C = self * other on the device (spal_csc_mul: `impl Mul for &CscMatrix<T>`, src/csc/ops/mul.rs:5-60)."""
+        """C = self * other on the device (spal_csc_mul: `impl Mul for &CscMatrix<T>`, src/csc/ops/mul.rs:5-60,
+        bit-identical); synchronises `stream`.  Options "spgemm_route" / "spgemm_lds_cap" are read from self."""
         if not isinstance(other, DeviceCsc):
             raise TypeError("DeviceCsc.mul needs a DeviceCsc (the reference has no mixed CSR x CSC Mul)")
         out = vp()

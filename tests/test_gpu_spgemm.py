@@ -9,6 +9,7 @@ import pytest
 import spalinalg_amd as sp
 import spal_synth as synth
 from spalinalg_amd import _ffi
+from tests import spgemm_cases
 from tests.util import assert_spmv_close, random_csr
 
 pytestmark = pytest.mark.gpu
@@ -185,12 +186,18 @@ def power_law(n, seed, dtype=np.float64, maxlen=3000, scale=4, half_window=2000)
     return rp, c2.astype(np.uint64), rng.uniform(-1, 1, c2.size).astype(dtype)
 
 
-@pytest.fixture(scope="module")
-def power_law_operands():
+def power_law_operand_arrays(synth):
+    """(n, power-law A, banded B); tests/test_spgemm_cases_host.py checks on the CPU that under route 1 both A * A and
+    A * B put a row in every LDS tier"""
     n = 50_000
     a = power_law(n, 17)
     b = synth.banded_csr(n, n, 14, 4096, 3)
     return n, a, b
+
+
+@pytest.fixture(scope="module")
+def power_law_operands():
+    return power_law_operand_arrays(synth)
 
 
 @pytest.mark.timeout(900)
@@ -199,6 +206,7 @@ def test_every_route_bit_for_bit(oracle, power_law_operands, rhs):
     n, a, banded = power_law_operands
     b = a if rhs == "self" else banded
     ref = oracle.csr_mul((n, n), a, (n, n), b)
+    route_of = {"auto": (0, 0), "lds": (1, 0), "large": (2, 0), "cap": (0, 48)}
     runs = {}
     for name, opts in (("auto", {}), ("lds", {"spgemm_route": 1}), ("large", {"spgemm_route": 2}),
                        ("cap", {"spgemm_lds_cap": 48})):
@@ -211,10 +219,12 @@ def test_every_route_bit_for_bit(oracle, power_law_operands, rhs):
         assert d["nnz"] == int(ref[0][-1]) and d["products"] > 0 and d["plan_ms"] >= 0, d
         t = d["tier_rows"]
         assert sum(t.values()) == n
+        assert spgemm_cases.reported(d) == spgemm_cases.expected(a, b, *route_of[name], nnz=int(ref[0][-1])), d
         if name == "auto":
             assert t["g16"] > 0 and t["large"] > 0, t
         elif name == "lds":
             assert sum(t[k] for k in LDS_TIERS) > 0 and t["block8k"] + t["large"] > 0, t
+            assert all(t[k] > 0 for k in LDS_TIERS), t
         elif name == "large":
             assert d["route"] == 2 and sum(t[k] for k in LDS_TIERS) == 0 and t["large"] == n - t["empty"], t
         else:

@@ -31,7 +31,7 @@ def assert_spmv_close(y, y_ref, bound, tol):
     assert np.array_equal(np.isnan(y), np.isnan(y_ref))
     fin = np.isfinite(y_ref)
     assert np.array_equal(y[~fin & ~np.isnan(y_ref)], y_ref[~fin & ~np.isnan(y_ref)])
-    err = np.abs(y - y_ref)[fin]
+    err = np.abs(y[fin] - y_ref[fin])
     scale = np.max(np.abs(y_ref[fin])) if fin.any() else 0.0
     if scale > 0:
         assert err.max() <= tol * scale, f"normwise {err.max() / scale:.3e} > {tol}"
