@@ -255,6 +255,53 @@ int spal_csc_describe(spal_csc_t a, char *buf, size_t buf_len);
  * must stay alive until the handle has been used on another stream or destroyed (or use one stream per handle). */
 int spal_csc_status(spal_csc_t a, int *invalid_products);
 
+/* ---- Y = A * X for a dense block of k vectors (SpMM), CSR and CSC --------------------
+ * `&A * &X` of src/csr/ops/mul.rs:5-59 with every entry of X stored.  X is ncols x k, Y is nrows x k, both dense
+ * and ROW-MAJOR: element (i, j) at [i * ld + j], ld >= k (so the k values a stored entry A[i,c] needs, X[c, 0..k),
+ * are contiguous; a C-contiguous numpy / torch 2-D array is this layout with ld = k).  k * ld offsets are 64-bit.
+ * Value of Y[i,j]: the stored entries of row i taken in ascending column, the first product ASSIGNED, every later
+ * one added; multiply and add rounded separately (no FMA), in the operand type (f32 in f32); a row without stored
+ * entries gives +0.0.  That is bit for bit the reference's Mul for a fully stored X.  No float atomics, no tree
+ * reduction: the result is deterministic and does not depend on k, on ldx / ldy or on the column tile that ran.
+ * (spal_csr_spmv_* promises those bits on its streaming kernels only: with one or two vectors spmv is the faster
+ * call, with four or more spmm is -- the library never reroutes one to the other.)
+ * Every element Y[i, 0..k) of every row is overwritten; the padding Y[i, k..ldy) is not touched.  X and Y must not
+ * overlap.  No alignment of the pointers or leading dimensions beyond the element's own is needed.
+ * SPAL_ERR_INVALID_ARGUMENT before any device work: null handle or pointers; k == 0; ldx < k or ldy < k; the host
+ * form: x_rows != ncols ("assertion failed: ncols == rhs.nrows (left: .., right: ..)", mul.rs:9) or
+ * y_rows != nrows; an _f64 entry on an f32 handle or the reverse.
+ * k is not limited: a block wider than the column tile is covered by several tiles inside ONE pass over the matrix.
+ * Row-block handles (more entries than 32-bit offsets address) are supported: block b writes its own rows of Y.
+ * The kernel reads the handle's row pointers, 32-bit columns and values only: it needs nothing from the SpMV plan
+ * and does not build it, so on a handle assembled on the device it may be the first call, also on a stream that is
+ * being captured into a graph (the _dev forms allocate nothing and synchronise nothing).
+ * The _dev forms are safe for concurrent calls on one handle (read-only on the matrix, no scratch memory); the host
+ * forms serialise on the handle.
+ * CSC handles run on their CSR twin (the one the default "kernel" = 2 product uses, built on the device on first
+ * use) whatever "kernel" says for SpMV -- hence the same bits as CSR.  The atomic scatter routes have no SpMM form;
+ * on a "kernel" = 1 handle the first SpMM builds the twin and therefore cannot be captured into a graph.
+ * Option "spmm_tile" (spal_csr_set_option / spal_csc_set_option): the column tile KT -- a wave is 64 / KT rows x KT
+ * columns of X.  0 = automatic (the narrowest tile that holds k, at most 32), else one of
+ * 1, 2, 4, 8, 16, 32; anything else SPAL_ERR_INVALID_ARGUMENT.  After the first SpMM the handle's describe() line
+ * carries an "spmm" object: tile and k of the last call, its column tiles, rows of a workgroup, long rows (rows a
+ * whole wave walks, apart from the tiles). */
+int spal_csr_spmm_f64(spal_csr_t a, uint64_t k, const double *x, uint64_t ldx, uint64_t x_rows,
+                      double *y, uint64_t ldy, uint64_t y_rows);                 /* host arrays: H2D, kernel, D2H */
+int spal_csr_spmm_f32(spal_csr_t a, uint64_t k, const float *x, uint64_t ldx, uint64_t x_rows,
+                      float *y, uint64_t ldy, uint64_t y_rows);
+int spal_csr_spmm_dev_f64(spal_csr_t a, uint64_t k, const double *x_dev, uint64_t ldx,
+                          double *y_dev, uint64_t ldy, void *stream);            /* enqueued, not synchronised */
+int spal_csr_spmm_dev_f32(spal_csr_t a, uint64_t k, const float *x_dev, uint64_t ldx,
+                          float *y_dev, uint64_t ldy, void *stream);
+int spal_csc_spmm_f64(spal_csc_t a, uint64_t k, const double *x, uint64_t ldx, uint64_t x_rows,
+                      double *y, uint64_t ldy, uint64_t y_rows);
+int spal_csc_spmm_f32(spal_csc_t a, uint64_t k, const float *x, uint64_t ldx, uint64_t x_rows,
+                      float *y, uint64_t ldy, uint64_t y_rows);
+int spal_csc_spmm_dev_f64(spal_csc_t a, uint64_t k, const double *x_dev, uint64_t ldx,
+                          double *y_dev, uint64_t ldy, void *stream);
+int spal_csc_spmm_dev_f32(spal_csc_t a, uint64_t k, const float *x_dev, uint64_t ldx,
+                          float *y_dev, uint64_t ldy, void *stream);
+
 /* ---- CSR <-> CSC on the device ------------------------------------------------
  * Replace `impl From<&CscMatrix<T>> for CsrMatrix<T>` (src/csr/conv/csc.rs:4-52)
  * and `impl From<&CsrMatrix<T>> for CscMatrix<T>` (src/csc/conv/csr.rs:4-52),

@@ -61,9 +61,11 @@ template <typename T> struct Abi;
 template <> struct Abi<double> {
     static constexpr auto csr_create = spal_csr_create_f64;
     static constexpr auto csr_spmv = spal_csr_spmv_f64;
+    static constexpr auto csr_spmm = spal_csr_spmm_f64;
     static constexpr auto csr_download = spal_csr_download_f64;
     static constexpr auto csc_create = spal_csc_create_f64;
     static constexpr auto csc_spmv = spal_csc_spmv_f64;
+    static constexpr auto csc_spmm = spal_csc_spmm_f64;
     static constexpr auto coo_to_csr = spal_coo_to_csr_f64;
     static constexpr auto coo_to_csc = spal_coo_to_csc_f64;
     static constexpr auto csc_download = spal_csc_download_f64;
@@ -71,9 +73,11 @@ template <> struct Abi<double> {
 template <> struct Abi<float> {
     static constexpr auto csr_create = spal_csr_create_f32;
     static constexpr auto csr_spmv = spal_csr_spmv_f32;
+    static constexpr auto csr_spmm = spal_csr_spmm_f32;
     static constexpr auto csr_download = spal_csr_download_f32;
     static constexpr auto csc_create = spal_csc_create_f32;
     static constexpr auto csc_spmv = spal_csc_spmv_f32;
+    static constexpr auto csc_spmm = spal_csc_spmm_f32;
     static constexpr auto coo_to_csr = spal_coo_to_csr_f32;
     static constexpr auto coo_to_csc = spal_coo_to_csc_f32;
     static constexpr auto csc_download = spal_csc_download_f32;
@@ -138,6 +142,18 @@ class CsrMatrix {
             throw Panic(SPAL_ERR_INVALID_ARGUMENT, "assertion failed: `(left == right)` ncols vs x.len()");
         std::vector<T> y(nrows_);
         detail::check(detail::Abi<T>::csr_spmv(device_handle(), x.data(), x.size(), y.data(), y.size()));
+        return y;
+    }
+
+    // Y = A * X for a dense ROW-MAJOR block of k vectors (x.size() == ncols * k, element (i, j) at i * k + j): one pass
+    // over the matrix for all k columns, bit for bit `&A * &X` with every entry of X stored.  Panics when X has another
+    // number of rows than ncols (assert_eq!, src/csr/ops/mul.rs:9).  With one or two vectors operator* is the faster call.
+    std::vector<T> mul(const std::vector<T> &x, usize k) const {
+        if (k == 0 || x.size() % k != 0 || x.size() / k != ncols_)
+            throw Panic(SPAL_ERR_INVALID_ARGUMENT, "assertion failed: ncols == rhs.nrows (left: " + std::to_string(ncols_) +
+                                                       ", right: " + std::to_string(k ? x.size() / k : 0) + ")");
+        std::vector<T> y(nrows_ * k);
+        detail::check(detail::Abi<T>::csr_spmm(device_handle(), k, x.data(), k, ncols_, y.data(), k, nrows_));
         return y;
     }
 
@@ -236,6 +252,18 @@ class CscMatrix {
             throw Panic(SPAL_ERR_INVALID_ARGUMENT, "assertion failed: `(left == right)` ncols vs x.len()");
         std::vector<T> y(nrows_);
         detail::check(detail::Abi<T>::csc_spmv(device_handle(), x.data(), x.size(), y.data(), y.size()));
+        return y;
+    }
+
+    // Y = A * X for a dense ROW-MAJOR block of k vectors (x.size() == ncols * k, element (i, j) at i * k + j): one pass
+    // over the matrix for all k columns, bit for bit `&A * &X` with every entry of X stored.  Panics when X has another
+    // number of rows than ncols (assert_eq!, src/csc/ops/mul.rs:9).  With one or two vectors operator* is the faster call.
+    std::vector<T> mul(const std::vector<T> &x, usize k) const {
+        if (k == 0 || x.size() % k != 0 || x.size() / k != ncols_)
+            throw Panic(SPAL_ERR_INVALID_ARGUMENT, "assertion failed: ncols == rhs.nrows (left: " + std::to_string(ncols_) +
+                                                       ", right: " + std::to_string(k ? x.size() / k : 0) + ")");
+        std::vector<T> y(nrows_ * k);
+        detail::check(detail::Abi<T>::csc_spmm(device_handle(), k, x.data(), k, ncols_, y.data(), k, nrows_));
         return y;
     }
     // C = A * B: `impl Mul for &CscMatrix<T>` (src/csc/ops/mul.rs:5-60) on the device, bit-identical.

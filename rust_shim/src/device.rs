@@ -4,7 +4,7 @@
 use std::marker::PhantomData;
 use std::os::raw::{c_int, c_void};
 
-use super::{ffi, scalar::HipScalar};
+use super::{ffi, scalar::{HipScalar, HipSpmm}};
 use crate::{CooMatrix, CscMatrix, CsrMatrix};
 
 /// `CsrMatrix<T>` resident on a GPU (include/spal.h: spal_csr_t).
@@ -78,6 +78,28 @@ impl<T: HipScalar> DeviceCsr<T> {
     /// the pointers must be valid device allocations of those lengths that do not overlap.
     pub unsafe fn mul_dev(&self, x_dev: *const T, y_dev: *mut T, stream: *mut c_void) {
         ffi::check(T::csr_spmv_dev(self.h, x_dev, y_dev, stream));
+    }
+
+    /// Y = A * X for a dense ROW-MAJOR block of `k` vectors (`x.len() == ncols * k`, element (i, j) at `i * k + j`):
+    /// one pass over the matrix for all k columns, bit for bit `&A * &X` with every entry of X stored.  Panics like
+    /// `assert_eq!(self.ncols(), rhs.nrows())` (src/csr/ops/mul.rs:9) when X has another number of rows.  With one or
+    /// two vectors `mul_vec` is the faster call.
+    pub fn spmm(&self, x: &[T], k: usize) -> Vec<T> where T: HipSpmm {
+        let (nrows, ncols, _) = self.shape();
+        assert!(k > 0 && x.len() % k == 0, "X must hold whole rows of k values");
+        assert_eq!(ncols, x.len() / k);
+        let mut y = vec![T::zero(); nrows * k];
+        unsafe { ffi::check(T::csr_spmm(self.h, k as u64, x, k as u64, ncols as u64, &mut y, k as u64, nrows as u64)); }
+        y
+    }
+
+    /// `spmm` on device pointers with leading dimensions, enqueued on `stream` and not synchronised.
+    ///
+    /// # Safety
+    /// `x_dev` must hold `(ncols - 1) * ldx + k` and `y_dev` `(nrows - 1) * ldy + k` elements; they must not overlap.
+    pub unsafe fn spmm_dev(&self, k: usize, x_dev: *const T, ldx: usize, y_dev: *mut T, ldy: usize, stream: *mut c_void)
+    where T: HipSpmm {
+        ffi::check(T::csr_spmm_dev(self.h, k as u64, x_dev, ldx as u64, y_dev, ldy as u64, stream));
     }
 
     /// Setup-time autotune on the caller's device vectors (kernel form, placement of the values array).
@@ -188,6 +210,23 @@ impl<T: HipScalar> DeviceCsc<T> {
     /// as `DeviceCsr::mul_dev`.
     pub unsafe fn mul_dev(&self, x_dev: *const T, y_dev: *mut T, stream: *mut c_void) {
         ffi::check(T::csc_spmv_dev(self.h, x_dev, y_dev, stream));
+    }
+
+    /// As `DeviceCsr::spmm`; runs on the handle's CSR twin whatever "kernel" says, hence the same bits.
+    pub fn spmm(&self, x: &[T], k: usize) -> Vec<T> where T: HipSpmm {
+        let (nrows, ncols, _) = self.shape();
+        assert!(k > 0 && x.len() % k == 0, "X must hold whole rows of k values");
+        assert_eq!(ncols, x.len() / k);   // src/csc/ops/mul.rs:9
+        let mut y = vec![T::zero(); nrows * k];
+        unsafe { ffi::check(T::csc_spmm(self.h, k as u64, x, k as u64, ncols as u64, &mut y, k as u64, nrows as u64)); }
+        y
+    }
+
+    /// # Safety
+    /// as `DeviceCsr::spmm_dev`.
+    pub unsafe fn spmm_dev(&self, k: usize, x_dev: *const T, ldx: usize, y_dev: *mut T, ldy: usize, stream: *mut c_void)
+    where T: HipSpmm {
+        ffi::check(T::csc_spmm_dev(self.h, k as u64, x_dev, ldx as u64, y_dev, ldy as u64, stream));
     }
 
     /// "kernel" = 1: atomic scatter, 2 (default): converted to CSR on the device once, deterministic.

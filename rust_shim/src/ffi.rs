@@ -59,6 +59,14 @@ extern "C" {
     pub fn spal_csc_autotune_f32(a: *mut spal_csc, x_dev: *const f32, y_dev: *mut f32, stream: *mut c_void, iters: c_int) -> c_int;
     pub fn spal_csc_describe(a: *mut spal_csc, buf: *mut c_char, buf_len: usize) -> c_int;
     pub fn spal_csc_status(a: *mut spal_csc, invalid_products: *mut c_int) -> c_int;
+    pub fn spal_csr_spmm_f64(a: *mut spal_csr, k: u64, x: *const f64, ldx: u64, x_rows: u64, y: *mut f64, ldy: u64, y_rows: u64) -> c_int;
+    pub fn spal_csr_spmm_f32(a: *mut spal_csr, k: u64, x: *const f32, ldx: u64, x_rows: u64, y: *mut f32, ldy: u64, y_rows: u64) -> c_int;
+    pub fn spal_csr_spmm_dev_f64(a: *mut spal_csr, k: u64, x_dev: *const f64, ldx: u64, y_dev: *mut f64, ldy: u64, stream: *mut c_void) -> c_int;
+    pub fn spal_csr_spmm_dev_f32(a: *mut spal_csr, k: u64, x_dev: *const f32, ldx: u64, y_dev: *mut f32, ldy: u64, stream: *mut c_void) -> c_int;
+    pub fn spal_csc_spmm_f64(a: *mut spal_csc, k: u64, x: *const f64, ldx: u64, x_rows: u64, y: *mut f64, ldy: u64, y_rows: u64) -> c_int;
+    pub fn spal_csc_spmm_f32(a: *mut spal_csc, k: u64, x: *const f32, ldx: u64, x_rows: u64, y: *mut f32, ldy: u64, y_rows: u64) -> c_int;
+    pub fn spal_csc_spmm_dev_f64(a: *mut spal_csc, k: u64, x_dev: *const f64, ldx: u64, y_dev: *mut f64, ldy: u64, stream: *mut c_void) -> c_int;
+    pub fn spal_csc_spmm_dev_f32(a: *mut spal_csc, k: u64, x_dev: *const f32, ldx: u64, y_dev: *mut f32, ldy: u64, stream: *mut c_void) -> c_int;
     pub fn spal_csc_to_csr(a: *mut spal_csc, out: *mut *mut spal_csr) -> c_int;
     pub fn spal_csr_to_csc(a: *mut spal_csr, out: *mut *mut spal_csc) -> c_int;
     pub fn spal_csr_mul(a: *mut spal_csr, b: *mut spal_csr, stream: *mut c_void, out: *mut *mut spal_csr) -> c_int;

@@ -75,3 +75,34 @@ impl_hip_scalar!(f64, spal_csr_create_f64, spal_csr_spmv_f64, spal_csr_spmv_dev_
 impl_hip_scalar!(f32, spal_csr_create_f32, spal_csr_spmv_f32, spal_csr_spmv_dev_f32, spal_csr_autotune_f32,
                  spal_csr_download_f32, spal_csc_create_f32, spal_csc_spmv_f32, spal_csc_spmv_dev_f32,
                  spal_csc_download_f32, spal_coo_upload_f32, spal_mg_csr_create_f32, spal_mg_csr_spmv_f32);
+
+/// Y = A * X for a dense row-major block (the spal_*_spmm_* entry points): `x` is ncols x k with leading dimension
+/// `ldx`, `y` nrows x k with `ldy`.
+#[allow(clippy::too_many_arguments)]
+pub trait HipSpmm: HipScalar {
+    unsafe fn csr_spmm(a: *mut ffi::spal_csr, k: u64, x: &[Self], ldx: u64, x_rows: u64, y: &mut [Self], ldy: u64, y_rows: u64) -> c_int;
+    unsafe fn csr_spmm_dev(a: *mut ffi::spal_csr, k: u64, x: *const Self, ldx: u64, y: *mut Self, ldy: u64, stream: *mut c_void) -> c_int;
+    unsafe fn csc_spmm(a: *mut ffi::spal_csc, k: u64, x: &[Self], ldx: u64, x_rows: u64, y: &mut [Self], ldy: u64, y_rows: u64) -> c_int;
+    unsafe fn csc_spmm_dev(a: *mut ffi::spal_csc, k: u64, x: *const Self, ldx: u64, y: *mut Self, ldy: u64, stream: *mut c_void) -> c_int;
+}
+
+macro_rules! impl_hip_spmm {
+    ($t:ty, $csr_spmm:ident, $csr_spmm_dev:ident, $csc_spmm:ident, $csc_spmm_dev:ident) => {
+        impl HipSpmm for $t {
+            unsafe fn csr_spmm(a: *mut ffi::spal_csr, k: u64, x: &[Self], ldx: u64, x_rows: u64, y: &mut [Self], ldy: u64, y_rows: u64) -> c_int {
+                ffi::$csr_spmm(a, k, x.as_ptr(), ldx, x_rows, y.as_mut_ptr(), ldy, y_rows)
+            }
+            unsafe fn csr_spmm_dev(a: *mut ffi::spal_csr, k: u64, x: *const Self, ldx: u64, y: *mut Self, ldy: u64, stream: *mut c_void) -> c_int {
+                ffi::$csr_spmm_dev(a, k, x, ldx, y, ldy, stream)
+            }
+            unsafe fn csc_spmm(a: *mut ffi::spal_csc, k: u64, x: &[Self], ldx: u64, x_rows: u64, y: &mut [Self], ldy: u64, y_rows: u64) -> c_int {
+                ffi::$csc_spmm(a, k, x.as_ptr(), ldx, x_rows, y.as_mut_ptr(), ldy, y_rows)
+            }
+            unsafe fn csc_spmm_dev(a: *mut ffi::spal_csc, k: u64, x: *const Self, ldx: u64, y: *mut Self, ldy: u64, stream: *mut c_void) -> c_int {
+                ffi::$csc_spmm_dev(a, k, x, ldx, y, ldy, stream)
+            }
+        }
+    };
+}
+impl_hip_spmm!(f64, spal_csr_spmm_f64, spal_csr_spmm_dev_f64, spal_csc_spmm_f64, spal_csc_spmm_dev_f64);
+impl_hip_spmm!(f32, spal_csr_spmm_f32, spal_csr_spmm_dev_f32, spal_csc_spmm_f32, spal_csc_spmm_dev_f32);

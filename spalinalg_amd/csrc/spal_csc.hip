@@ -695,6 +695,17 @@ static int csc_ensure_csr(spal_csc *a) {
     return st;
 }
 
+int csc_csr_twin(spal_csc *a, spal_csr **out) {
+    spal_csr *twin = __atomic_load_n(&a->as_csr, __ATOMIC_ACQUIRE);
+    if (!twin) {   // a scatter-route handle: built once, by the first caller (the others wait here)
+        std::lock_guard<std::mutex> lock(a->mu_twin);
+        SPAL_TRY(csc_ensure_csr(a));
+        twin = a->as_csr;
+    }
+    *out = twin;
+    return SPAL_OK;
+}
+
 int csc_adopt_device(int device, int elem_size, uint64_t nrows, uint64_t ncols, uint64_t nnz,
                      uint32_t *d_colptr, uint32_t *d_rowind, void *d_values, spal_csc **out) {
     spal_csc *a = new spal_csc;
@@ -983,6 +994,7 @@ int spal_csc_set_option(spal_csc_t a, const char *key, int64_t value) {
         int st = SPAL_OK;
         if (spgemm_option(key, value, &a->spgemm_route, &a->spgemm_lds_cap, &st)) return st;
         if (spadd_option(key, value, &a->spadd_tile, &st)) return st;   // ... and of A + B / A - B
+        if (spmm_option(key, value, &a->spmm_tile, &st)) return st;     // ... and of Y = A * X
     }
     DeviceGuard guard(a->device);
     if (guard.status != SPAL_OK) return guard.status;
@@ -1074,7 +1086,8 @@ int spal_csc_describe(spal_csc_t a, char *buf, size_t buf_len) {
              a->uniform_cols ? 1 : 0,
              (a->rowtiles && a->rowtiles_user != 0 && a->flush == 0) ? 1 : 0, a->rt_rows, a->rt_ntiles, a->rt_xcap, a->rowtiles_failed);
     SPAL_TRY(spgemm_describe_append(buf, buf_len, a->spgemm_info));   // a product of spal_csc_mul: how it was built
-    return spadd_describe_append(buf, buf_len, a->spadd_info);        // a result of spal_csc_add / _sub / _neg
+    SPAL_TRY(spadd_describe_append(buf, buf_len, a->spadd_info));     // a result of spal_csc_add / _sub / _neg
+    return spmm_describe_append(buf, buf_len, a->as_csr);             // an SpMM ran on it (on the CSR twin)
 }
 
 }  // extern "C"

@@ -2227,6 +2227,7 @@ int spal_csr_set_option(spal_csr_t a, const char *key, int64_t value) {
         int st = SPAL_OK;
         if (spgemm_option(key, value, &a->spgemm_route, &a->spgemm_lds_cap, &st)) return st;
         if (spadd_option(key, value, &a->spadd_tile, &st)) return st;   // ... and of A + B / A - B
+        if (spmm_option(key, value, &a->spmm_tile, &st)) return st;     // ... and of Y = A * X
     }
     if (!a->parts.empty()) {   // row blocks: every block takes the option (each plans for its own rows)
         for (spal_csr *part : a->parts) SPAL_TRY(spal_csr_set_option(part, key, value));
@@ -2586,7 +2587,8 @@ int spal_csr_describe(spal_csr_t a, char *buf, size_t buf_len) {
     if (!a || !buf || !buf_len) return fail(SPAL_ERR_INVALID_ARGUMENT, "spal_csr_describe: null argument");
     SPAL_TRY(csr_describe_plan(a, buf, buf_len));
     SPAL_TRY(spgemm_describe_append(buf, buf_len, a->spgemm_info));   // a product of spal_csr_mul: how it was built
-    return spadd_describe_append(buf, buf_len, a->spadd_info);        // a result of spal_csr_add / _sub / _neg
+    SPAL_TRY(spadd_describe_append(buf, buf_len, a->spadd_info));     // a result of spal_csr_add / _sub / _neg
+    return spmm_describe_append(buf, buf_len, a);                     // an SpMM ran on it
 }
 static int csr_describe_plan(spal_csr_t a, char *buf, size_t buf_len) {
     if (!a->parts.empty()) {   // row blocks: the shape of the whole, the cuts, and the first block's plan

@@ -199,6 +199,8 @@ int spgemm_describe_append(char *buf, size_t buf_len, const std::string &info);
 // a handle built by spal_*_add / _sub / _neg adds to its describe() line
 int spadd_option(const char *key, int64_t value, uint32_t *tile, int *status);
 int spadd_describe_append(char *buf, size_t buf_len, const std::string &info);
+// implemented in spal_spmm.hip: the option "spmm_tile" of either handle type (as spgemm_option)
+int spmm_option(const char *key, int64_t value, int *tile, int *status);
 // implemented in spal_csc.hip: handle around device arrays it takes ownership of
 int csc_adopt_device(int device, int elem_size, uint64_t nrows, uint64_t ncols, uint64_t nnz,
                      uint32_t *d_colptr, uint32_t *d_rowind, void *d_values, spal_csc **out);
@@ -286,6 +288,9 @@ struct spal_csr {
     // A + B, A - B, -A (spal_spadd.hip): the option of this handle as the LEFT operand, and what built it if it is a sum
     uint32_t spadd_tile = 0;       // option "spadd_tile": merged elements per workgroup, 0 = default
     std::string spadd_info;        // the "spadd" object of spal_csr_describe (empty: not a sum)
+    // Y = A * X (spal_spmm.hip)
+    int spmm_tile = 0;             // option "spmm_tile": column tile, 0 = automatic
+    uint64_t spmm_last = 0;        // {tile << 32 | k} of the last SpMM on this handle (0: none yet), for describe
 };
 
 struct spal_csc {
@@ -350,6 +355,8 @@ struct spal_csc {
     std::string spgemm_info;
     uint32_t spadd_tile = 0;       // as spal_csr's
     std::string spadd_info;
+    int spmm_tile = 0;             // as spal_csr's; SpMM always runs on as_csr
+    std::mutex mu_twin;            // ... which an SpMM on a scatter-route handle (kernel 1) is the first to build
 };
 
 struct spal_coo {
@@ -380,6 +387,13 @@ namespace spal {
 int csr_plan_build(spal_csr *a);
 int csr_launch(spal_csr *a, const void *x_dev, void *y_dev, hipStream_t stream);
 int csr_ensure_plan(spal_csr *a, hipStream_t launch_stream, bool from_launch);
+// implemented in spal_spmm.hip: Y = A * X enqueued on `stream` (tile 0 = automatic); reads a's plain arrays only, no plan
+int spmm_launch(spal_csr *a, int tile, uint64_t k, const void *x_dev, uint64_t ldx, void *y_dev, uint64_t ldy,
+                hipStream_t stream);
+// ... and the "spmm" object a handle (a may be null) adds to its describe() line once an SpMM ran on it
+int spmm_describe_append(char *buf, size_t buf_len, const spal_csr *a);
+// implemented in spal_csc.hip: the handle's CSR twin, built on the device by whoever asks first
+int csc_csr_twin(spal_csc *a, spal_csr **out);
 // implemented in spal_csr_slide.hip: the sliding-window kernel for a plan with plan.slide set
 hipError_t launch_slide(const spal_csr *a, const void *x, void *y, hipStream_t st);
 // ... and the column-panel kernel over a->d_ptiles

@@ -117,6 +117,72 @@ class _DeviceMatrix:
         """Device pointers; enqueued on `stream`, not synchronised."""
         check(self._fn(f"spmv_dev_{_sfx(self.dtype)}")(self._h, vp(x_ptr), vp(y_ptr), _stream_ptr(stream)))
 
+    def spmm(self, X) -> np.ndarray:
+        """Y = A * X for a host 2-D array X of shape (ncols, k): host (nrows, k) array out (H2D, one pass over the
+        matrix for all k columns, D2H).  Bit for bit the reference's `&A * &X` for a fully stored X, whatever k is.
+        With one or two vectors spmv() is the faster call; from about four on this one is."""
+        X = np.ascontiguousarray(X, dtype=self.dtype)
+        if X.ndim != 2:
+            raise TypeError("spmm() takes a 2-D block of vectors, shape (ncols, k)")
+        nrows = self.shape()[0]
+        k = X.shape[1]
+        Y = np.empty((nrows, k), dtype=self.dtype)
+        check(self._fn(f"spmm_{_sfx(self.dtype)}")(self._h, u64(k), _p(X), u64(k), u64(X.shape[0]),
+                                                   _p(Y), u64(k), u64(nrows)))
+        return Y
+
+    def spmm_dev(self, k: int, x_ptr: int, ldx: int, y_ptr: int, ldy: int, stream=None) -> None:
+        """Device pointers of row-major blocks (element (i, j) at i * ld + j); enqueued on `stream`, not synchronised."""
+        check(self._fn(f"spmm_dev_{_sfx(self.dtype)}")(self._h, u64(k), vp(x_ptr), u64(ldx), vp(y_ptr), u64(ldy),
+                                                       _stream_ptr(stream)))
+
+    def spmm_torch(self, X, out=None):
+        """X: (ncols, k) torch tensor on this handle's device with unit stride in its last dimension -- stride(0) is
+        passed as the leading dimension, so a column slice X[:, 2:6] of a wider tensor needs no copy; the same holds
+        for `out` (nrows, k).  Runs on torch's current stream."""
+        import torch
+        nrows, ncols, _ = self.shape()
+        tdt = torch.float64 if self.dtype == np.float64 else torch.float32
+
+        def rows_ok(t, rows):   # 2-D, unit stride inside a row, rows ld >= k apart
+            return (t.dim() == 2 and t.shape[0] == rows and t.shape[1] >= 1 and t.stride(1) == 1
+                    and (t.stride(0) >= t.shape[1] or t.shape[0] <= 1))
+
+        def span(t):            # [first byte, one past the last byte) the kernel may touch
+            n = (t.shape[0] - 1) * t.stride(0) + t.shape[1] if t.shape[0] else 0
+            return t.data_ptr(), t.data_ptr() + n * t.element_size()
+
+        if X.dtype != tdt or not X.is_cuda or X.dim() != 2:
+            raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT, f"X must be a 2-D {tdt} device tensor of shape (ncols = {ncols}, k)")
+        if X.shape[0] != ncols:
+            raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT,
+                        f"assertion failed: ncols == rhs.nrows (left: {ncols}, right: {X.shape[0]})")
+        if not rows_ok(X, ncols):
+            raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT, "X needs k >= 1 columns, unit stride in its last dimension and "
+                                                        "stride(0) >= k")
+        if X.device.index != self.device:
+            raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT,
+                        f"X lives on cuda:{X.device.index} but the matrix on cuda:{self.device}")
+        k = X.shape[1]
+        if out is None:
+            out = torch.empty((nrows, k), dtype=tdt, device=X.device)
+        elif out.dtype != tdt or not out.is_cuda or not rows_ok(out, nrows) or out.shape[1] != k:
+            raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT,
+                        f"out must be a {tdt} device tensor of shape (nrows = {nrows}, k = {k}) with unit stride in its "
+                        "last dimension")
+        elif out.device != X.device:
+            raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT, "out and X live on different devices")
+        else:
+            (x0, x1), (y0, y1) = span(X), span(out)
+            if y0 < x1 and x0 < y1:
+                # the spans meet: fine only for disjoint column ranges of one wider row-major buffer (same leading dimension)
+                ld, shift = X.stride(0), abs(y0 - x0) // X.element_size() % max(X.stride(0), 1)
+                if not (out.stride(0) == ld and k <= shift <= ld - k):
+                    raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT, "out overlaps X (Y = A*X is not computed in place)")
+        self.spmm_dev(k, X.data_ptr(), max(X.stride(0), k), out.data_ptr(), max(out.stride(0), k),
+                      torch.cuda.current_stream(X.device))
+        return out
+
     def alloc_vectors(self, stream=None):
         """Device pointers (x, y) of vectors owned by this handle and placed so that the stores of y do not collide
         with the matrix stream (spal_csr_alloc_vectors: a walk over the device's memory, setup time).  CSR handles."""
@@ -512,13 +578,23 @@ class _Compressed:
 
     def _mul_vec(self, x):
         x = np.asarray(x)
+        if x.ndim == 2:
+            return self._mul_block(x)
         if x.ndim != 1:
-            raise TypeError("right-hand side must be a dense vector")
+            raise TypeError("right-hand side must be a dense vector or a 2-D block of vectors")
         if x.shape[0] != self._ncols:
             # assert_eq!(self.ncols(), rhs.nrows())  src/csr/ops/mul.rs:9
             raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT,
                         f"assertion failed: ncols == x.len() (left: {self._ncols}, right: {x.shape[0]})")
         return self.device().spmv(x.astype(self.dtype, copy=False))
+
+    def _mul_block(self, X):
+        """`&self * &X` for a dense block X of shape (ncols, k): a (nrows, k) ndarray (SpMM, one pass over the matrix)."""
+        if X.shape[0] != self._ncols:
+            # assert_eq!(self.ncols(), rhs.nrows())  mul.rs:9 -- before any device copy is made
+            raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT,
+                        f"assertion failed: ncols == rhs.nrows (left: {self._ncols}, right: {X.shape[0]})")
+        return self.device().spmm(X.astype(self.dtype, copy=False))
 
     def _mul_mat(self, other, device: int = 0):
         """`&self * &other` (src/csr/ops/mul.rs:5-59 / src/csc/ops/mul.rs:5-60) on the device; the result is downloaded
