@@ -1084,7 +1084,7 @@ __global__ __launch_bounds__(kStreamBlock) void csr_spmv_overflow(
     }
 }
 
-// ---- the LONG rows of a row-split plan (spal_csr.hip: csr_try_row_split) -----------------------------------------
+// ---- the LONG rows of a row-split plan (spal_csr_split.hip: csr_try_row_split) -----------------------------------------
 // rows[i], i < nlong: rows of more than the split's threshold, longest first; the first nheavy (more than 1024 entries) take a
 // whole workgroup each and start first.  Otherwise a wave per row: consecutive lanes read consecutive entries
 // (coalesced, non-temporal), x gathered through L2, lane-partial sums folded by a shuffle tree -- rounded like every row the

@@ -27,7 +27,7 @@
 // the chain inside a phase -- a barrier, the row search, a row's dependent sums -- on a CU that holds one workgroup (counters: the
 // LDS pipe is busy a third of the time; 1.16 x the algorithmic bytes fetched, 4.4 TB/s) and the spread of the walks' ends
 // (54 ... 75 us although their entry counts are equal).
-// Chosen at setup by time against the row split (spal_csr.hip: csr_plan_build); option "blockwin" -1 / 0 / 1.
+// Chosen at setup by time against the row split (spal_csr_split.hip: csr_blockwin_or_split); option "blockwin" -1 / 0 / 1.
 #include <algorithm>
 #include <atomic>
 #include <cstdio>

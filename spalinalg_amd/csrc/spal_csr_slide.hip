@@ -1,4 +1,4 @@
-// spal_csr_slide.hip -- instantiations and launch of the sliding-window CSR kernel (csr_slide.hpp); a
+// spal_csr_slide.hip -- instantiations, launch and plan of the sliding-window CSR kernel (csr_slide.hpp); a
 // translation unit of its own so that the build compiles it beside spal_csr.hip.
 #include "csr_panel.hpp"
 #include "csr_slide.hpp"
@@ -108,6 +108,161 @@ static hipError_t launch_panel_rpt(const spal_csr *a, const void *x, void *y, hi
 
 hipError_t launch_panel(const spal_csr *a, const void *x, void *y, hipStream_t st) {
     return a->elem_size == 8 ? launch_panel_rpt<double>(a, x, y, st) : launch_panel_rpt<float>(a, x, y, st);
+}
+
+
+// ---- plan of the sliding-window kernel (csr_slide.hpp) -----------------------------------------------------
+// One workgroup per STEP of SR = 4 * rpt rows (SR <= 256: a row per thread): out[i] = {first column, one past the
+// last column (0: the step stores nothing), 1 + the length of every row if they are all equal else 0, the most
+// 128-entry steps one of its four tiles needs | a bit per tile << 8 that can go through the strip in two HALVES}.
+// A tile above the strip's 1024 entries whose halves (rpt / 2 rows each) both fit and that holds no row longer
+// than row_max is such a tile: the sliding kernel takes it in two passes instead of leaving it to
+// csr_spmv_overflow (rows of 1 ... 27 entries: 2 % of the 64-row tiles).  Its halves count for the step number,
+// a tile that is left to the overflow kernel does not.
+__global__ __launch_bounds__(256) void csr_slide_scan(const uint32_t *__restrict__ rowptr,
+                                                      const uint32_t *__restrict__ colind, uint32_t nrows,
+                                                      uint32_t rpt, uint32_t row_max, uint4 *__restrict__ out) {
+    __shared__ uint32_t s_min, s_max, s_ragged, s_steps, s_long, s_split;
+    const uint32_t t = threadIdx.x, SR = 4u * rpt;
+    if (t == 0) { s_min = 0xffffffffu; s_max = 0u; s_ragged = 0u; s_steps = 0u; s_long = 0u; s_split = 0u; }
+    __syncthreads();
+    const uint32_t row0 = blockIdx.x * SR, row1 = min(row0 + SR, nrows);
+    const uint32_t len0 = rowptr[row0 + 1] - rowptr[row0];
+    if (row0 + t < row1 && t < SR) {
+        const uint32_t a0 = rowptr[row0 + t], a1 = rowptr[row0 + t + 1];
+        if (a0 < a1) {
+            atomicMin(&s_min, colind[a0]);
+            atomicMax(&s_max, colind[a1 - 1] + 1u);
+        }
+        if (a1 - a0 != len0) s_ragged = 1u;
+        if (a1 - a0 > row_max) atomicOr(&s_long, 1u << (t / rpt));
+    }
+    __syncthreads();
+    if (t < 4u && row0 + t * rpt < row1) {
+        const uint32_t rb = row0 + t * rpt, re = min(rb + rpt, row1), rm = min(rb + rpt / 2u, re);
+        const uint32_t b = rowptr[rb], m = rowptr[rm], e = rowptr[re];
+        uint32_t steps = (e - (b & ~1u) + 127u) >> 7;
+        if (stream_tile_overflows(b, e)) {
+            const bool halves = rpt >= 2u && !((s_long >> t) & 1u) && !stream_tile_overflows(b, m) && !stream_tile_overflows(m, e);
+            steps = halves ? max((m - (b & ~1u) + 127u) >> 7, (e - (m & ~1u) + 127u) >> 7) : 0u;
+            if (halves) atomicOr(&s_split, 1u << t);
+        }
+        atomicMax(&s_steps, steps);
+    }
+    __syncthreads();
+    if (t == 0)
+        out[blockIdx.x] = make_uint4(s_min, s_max, (s_ragged == 0u && len0 < 4095u) ? len0 + 1u : 0u, s_steps | (s_split << 8));
+}
+
+// Decides whether the sliding kernel can run this stream plan and, if so, builds its step descriptors.
+// desc / skip: the chosen stream plan's super-tiles (16 tiles of rpt rows each); super_pages: the most
+// pages one of them stages (the one-super-tile-per-workgroup kernels read the same ring).
+int slide_plan(spal_csr *a, uint32_t rpt, const std::vector<uint4> &desc,
+                      const std::vector<uint32_t> &skip, uint32_t super_pages) {
+    CsrPlan &p = a->plan;
+    p.slide = 0;
+    p.ring_pages = 0;
+    if (a->d_sdesc) { SPAL_HIP_TRY(dev_free(a->d_sdesc)); a->d_sdesc = nullptr; }
+    if (a->d_ovtiles_slide) { SPAL_HIP_TRY(dev_free(a->d_ovtiles_slide)); a->d_ovtiles_slide = nullptr; }
+    a->n_ovtiles_slide = 0;
+    a->n_split_tiles = 0;
+    const uint32_t V = 16u / (uint32_t)a->elem_size;
+    if (p.slide_user == 0 || p.tiles_per_wave != 4 || rpt > 64u || p.skew || a->ncols < kPageCols || a->nnz == 0) return SPAL_OK;
+    for (const uint4 &d : desc)
+        if (d.z != kModeStream || !(d.w & 1u)) return SPAL_OK;   // a page list, x through L2, vector rows: not a band
+    const uint32_t SR = 4u * rpt;
+    const uint32_t nsteps = (uint32_t)((a->nrows + SR - 1) / SR);
+    DevBuf d_scan;   // (back to the allocator on every path out)
+    SPAL_HIP_TRY(d_scan.alloc((size_t)nsteps * sizeof(uint4)));
+    hipLaunchKernelGGL(csr_slide_scan, dim3(nsteps), dim3(256), 0, a->stream, a->d_rowptr, a->d_colind,
+                       (uint32_t)a->nrows, rpt, (uint32_t)p.stream_row_max, d_scan.as<uint4>());
+    std::vector<uint4> scan(nsteps);
+    SPAL_HIP_TRY(hipMemcpyAsync(scan.data(), d_scan.p, (size_t)nsteps * sizeof(uint4), hipMemcpyDeviceToHost, a->stream));
+    SPAL_HIP_TRY(hipStreamSynchronize(a->stream));
+    // windows: a step that stores nothing keeps its predecessor's window (nothing enters)
+    std::vector<uint2> sd(nsteps);
+    std::vector<uint32_t> left_over;     // first rows of the tiles csr_spmv_overflow computes when the sliding kernel runs
+    uint32_t n_split = 0;
+    uint32_t S = 1, ulen = scan[0].z;
+    bool uni = true;
+    uint32_t pf = 0, pn = 1;
+    for (uint32_t i = 0; i < nsteps; ++i) {
+        if (scan[i].y) {
+            pf = scan[i].x >> kPageShift;
+            pn = ((scan[i].y - 1u) >> kPageShift) - pf + 1u;
+        }
+        sd[i] = make_uint2(pf, pn);
+        uni = uni && scan[i].z != 0u && scan[i].z == ulen;
+        // tiles the stream kernels skip: those that fit the strip in two halves stay with the sliding kernel (split),
+        // the others go to csr_spmv_overflow and do not bound S
+        const uint32_t tile0 = i * 4u;
+        uint32_t sk = 0;
+        for (uint32_t w = 0; w < 4u; ++w) {
+            const uint32_t tl = tile0 + w, b = tl / 16u;
+            if (b < skip.size() && ((skip[b] >> (tl % 16u)) & 1u)) sk |= 1u << w;
+        }
+        const uint32_t sp = p.split_tiles_on ? (sk & ((scan[i].w >> 8) & 0xfu)) : 0u;
+        sd[i].y |= (sk << 8) | (sp << 20);
+        S = std::max(S, scan[i].w & 0xffu);
+        for (uint32_t w = 0; w < 4u; ++w) {
+            if ((sp >> w) & 1u) ++n_split;
+            else if ((sk >> w) & 1u) left_over.push_back((tile0 + w) * rpt);
+        }
+    }
+    if (S > (uint32_t)kStreamSteps) S = (uint32_t)kStreamSteps;   // (cannot be: the scan counts fitting tiles and halves only)
+    // ring size: what the largest super-tile stages, and room for the pages that enter with the next step
+    const uint32_t page_bytes = kPageCols * (uint32_t)a->elem_size;
+    const uint32_t strips = (uint32_t)kStreamWaves * (uint32_t)stream_strip<false>() * (uint32_t)a->elem_size;
+    const uint32_t cap2 = (80u * 1024u - strips) / page_bytes;            // two workgroups per CU
+    const uint32_t cap1 = std::min<uint32_t>(255u, (160u * 1024u - strips) / page_bytes);   // one
+    uint32_t want = super_pages;
+    for (uint32_t i = 0; i + 1 < nsteps; ++i) {
+        const uint32_t lo = std::min(sd[i].x, sd[i + 1].x);
+        const uint32_t hi = std::max(sd[i].x + (sd[i].y & 0xffu), sd[i + 1].x + (sd[i + 1].y & 0xffu));
+        want = std::max(want, hi - lo);
+    }
+    const uint32_t NP = want <= cap2 ? want : std::min(want, std::max(cap1, super_pages));
+    if (NP < super_pages || NP > 255u) return SPAL_OK;   // (cannot be: super_pages fits the budget it was planned for)
+    // which steps' entering pages are prefetched
+    const uint32_t safe_cols = (uint32_t)(a->ncols / V) * V;   // below this column, x is made of whole 16-byte vectors
+    const uint32_t VP = kPageCols / V;
+    for (uint32_t i = 1; i < nsteps; ++i) {
+        const uint32_t f0 = sd[i - 1].x, e0 = f0 + (sd[i - 1].y & 0xffu), f1 = sd[i].x, e1 = f1 + (sd[i].y & 0xffu);
+        const uint32_t lo = std::min(f0, f1), hi = std::max(e0, e1);
+        uint32_t entering = 0;
+        if (f0 >= e1 || e0 <= f1) entering = e1 - f1;
+        else entering = (f1 < f0 ? f0 - f1 : 0u) + (e1 > e0 ? e1 - e0 : 0u);
+        const bool whole = (uint64_t)e1 * kPageCols <= safe_cols;
+        if (hi - lo <= NP && entering * VP <= kSlideAsyncVecs * (uint32_t)kStreamBlock && whole) sd[i].y |= kSlideAsync;
+    }
+    SPAL_HIP_TRY(dev_alloc((void **)&a->d_sdesc, (size_t)nsteps * sizeof(uint2)));
+    SPAL_HIP_TRY(hipMemcpyAsync(a->d_sdesc, sd.data(), (size_t)nsteps * sizeof(uint2), hipMemcpyHostToDevice, a->stream));
+    a->n_ovtiles_slide = (uint32_t)left_over.size();
+    a->n_split_tiles = n_split;
+    if (!left_over.empty()) {
+        SPAL_HIP_TRY(dev_alloc((void **)&a->d_ovtiles_slide, left_over.size() * 4));
+        SPAL_HIP_TRY(hipMemcpyAsync(a->d_ovtiles_slide, left_over.data(), left_over.size() * 4, hipMemcpyHostToDevice, a->stream));
+    }
+    SPAL_HIP_TRY(hipStreamSynchronize(a->stream));   // `sd`, `left_over` go out of scope
+    p.slide = 1;
+    p.ring_pages = (int)NP;
+    p.slide_steps = nsteps;
+    p.slide_S = (int)S;
+    p.slide_uniform = (uni && ulen != 0u) ? (int)ulen : 0;
+    // every tile of the sliding kernel issues S loads per array (counted waits): where the tiles are on average less than
+    // 60 % of the largest one -- ragged short rows, the short part of a row split: 4 of 8 steps -- half its loads are
+    // re-reads, and the one-super-tile-per-workgroup kernel, which issues what a tile holds, is faster (power-law short
+    // part: 104 -> 68 us); the autotune still times both
+    {
+        const double tiles = (double)nsteps * kStreamWaves;
+        const double avg_steps = tiles > 0 ? (double)a->nnz / tiles / 128.0 : 0.0;
+        p.slide_fill_ok = (p.slide_fill_user >= 0) ? p.slide_fill_user : (avg_steps >= 0.6 * (double)std::max(4u, S) ? 1 : 0);
+    }
+    // every row of the matrix that long: all steps stream (no tile left to the overflow kernel, none split) and the entries
+    // add up
+    p.all_rows_uniform = (p.slide_uniform && left_over.empty() && n_split == 0 &&
+                          (uint64_t)a->nrows * (uint64_t)(ulen - 1u) == a->nnz) ? 1 : 0;
+    return SPAL_OK;
 }
 
 }  // namespace spal

@@ -1,0 +1,349 @@
+// spal_device.hip -- device resources every handle type shares: device selection, the caching allocator for device
+// blocks, the placement blocks, the stream pool, and the entry points of include/spal.h that take no handle.
+#include "spal_internal.hpp"
+
+namespace spal {
+
+DeviceGuard::DeviceGuard(int device) {
+    int count = 0;
+    hipError_t e = hipGetDeviceCount(&count);
+    if (e != hipSuccess || count == 0) {
+        status = fail(SPAL_ERR_NO_DEVICE, "no HIP device available (%s)",
+                      e == hipSuccess ? "device count is 0" : hipGetErrorString(e));
+        return;
+    }
+    if (device < 0 || device >= count) {
+        status = fail(SPAL_ERR_INVALID_ARGUMENT, "device %d out of range (0..%d)", device, count - 1);
+        return;
+    }
+    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+    if (prev != device) {
+        e = hipSetDevice(device);
+        if (e != hipSuccess) status = fail(SPAL_ERR_HIP, "hipSetDevice(%d): %s", device, hipGetErrorString(e));
+    }
+}
+DeviceGuard::~DeviceGuard() {
+    if (prev >= 0) (void)hipSetDevice(prev);
+}
+
+// ---- caching allocator for device blocks ------------------------------------------
+// hipMalloc / hipFree cost tens of microseconds (hipFree synchronises the device)
+// and, for the 600 MB blocks of an assembly, milliseconds on some hosts.  Blocks
+// are handed back to a per-process cache instead: large ones (>= 1 MiB) are
+// reused for requests up to 25 % smaller, small ones are rounded up to a power of
+// two (>= 256 B) and reused for the same class.
+namespace {
+struct DevCache {
+    std::mutex mu;
+    struct Block { void *p; size_t bytes; int device; };
+    std::vector<Block> free_blocks;
+    std::vector<Block> live;      // blocks handed out by dev_alloc (for their size at free time)
+    size_t cached_bytes = 0;
+    // default: a quarter of the device's memory (72 GB of 288), at least 8 GiB -- the 27 GB of output an
+    // assembly of 2.3e9 triplets allocates must be reusable or every call pays hipMalloc / hipFree again
+    // (SPAL_CACHE_BYTES overrides; when the device cannot be asked, or is small, the cache stays small: at most
+    //  half of what was free at first use)
+    size_t limit = [] {
+        if (const char *e = getenv("SPAL_CACHE_BYTES")) return (size_t)strtoull(e, nullptr, 10);
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); return (size_t)256 << 20; }
+        return std::min(free_b / 2, std::max((size_t)8 << 30, total_b / 4));
+    }();
+    ~DevCache() {}  // the process is going away; the driver reclaims device memory
+};
+DevCache &dev_cache() { static DevCache c; return c; }
+constexpr size_t kCacheLargeBytes = 1u << 20;
+size_t size_class(size_t bytes) {  // what is actually allocated for a request
+    if (bytes >= kCacheLargeBytes) return bytes;
+    size_t c = 256;
+    while (c < bytes) c <<= 1;
+    return c;
+}
+
+// Non-blocking streams are pooled: creating one costs ~100 us, and every handle
+// (including each assembled CSR result) owns one.
+struct StreamPool {
+    std::mutex mu;
+    std::vector<std::pair<int, hipStream_t>> idle;   // (device, stream)
+};
+StreamPool &stream_pool() { static StreamPool p; return p; }
+}  // namespace
+
+// ---- placement blocks ------------------------------------------------------------------------------------------------
+namespace {
+struct PlaceArenaBlock {
+    void *base = nullptr;
+    size_t size = 0;
+    std::vector<std::pair<size_t, size_t>> used;   // {offset, bytes}, sorted by offset
+};
+struct PlaceArena {
+    std::mutex mu;
+    std::vector<PlaceArenaBlock> blocks[64];        // per device
+    bool walked[64] = {};
+};
+PlaceArena &place_arena() {
+    static PlaceArena *a = new PlaceArena;          // (never destroyed: handles may outlive static destructors)
+    return *a;
+}
+}  // namespace
+int place_block_count(int device) {
+    PlaceArena &a = place_arena();
+    std::lock_guard<std::mutex> lock(a.mu);
+    return (int)a.blocks[device & 63].size();
+}
+PlaceBlock place_block(int device, int index) {
+    PlaceArena &a = place_arena();
+    std::lock_guard<std::mutex> lock(a.mu);
+    const auto &v = a.blocks[device & 63];
+    if (index < 0 || index >= (int)v.size()) return PlaceBlock{nullptr, 0};
+    return PlaceBlock{v[(size_t)index].base, v[(size_t)index].size};
+}
+void *place_alloc(int device, int index, size_t bytes) {
+    PlaceArena &a = place_arena();
+    std::lock_guard<std::mutex> lock(a.mu);
+    auto &v = a.blocks[device & 63];
+    if (index < 0 || index >= (int)v.size() || bytes == 0) return nullptr;
+    PlaceArenaBlock &b = v[(size_t)index];
+    bytes = (bytes + 4095) & ~(size_t)4095;
+    size_t at = 0;
+    size_t pos = 0;
+    for (; pos < b.used.size(); ++pos) {            // first fit
+        if (b.used[pos].first - at >= bytes) break;
+        at = b.used[pos].first + b.used[pos].second;
+    }
+    if (pos == b.used.size() && b.size - at < bytes) return nullptr;
+    b.used.insert(b.used.begin() + (long)pos, std::make_pair(at, bytes));
+    return (char *)b.base + at;
+}
+void place_free(int device, void *ptr) {
+    if (!ptr) return;
+    PlaceArena &a = place_arena();
+    std::lock_guard<std::mutex> lock(a.mu);
+    for (PlaceArenaBlock &b : a.blocks[device & 63]) {
+        if ((char *)ptr < (char *)b.base || (char *)ptr >= (char *)b.base + b.size) continue;
+        const size_t off = (size_t)((char *)ptr - (char *)b.base);
+        for (size_t i = 0; i < b.used.size(); ++i)
+            if (b.used[i].first == off) { b.used.erase(b.used.begin() + (long)i); return; }
+    }
+}
+void place_adopt(int device, void *base, size_t size) {
+    PlaceArena &a = place_arena();
+    std::lock_guard<std::mutex> lock(a.mu);
+    PlaceArenaBlock b;
+    b.base = base; b.size = size;
+    a.blocks[device & 63].push_back(b);
+}
+size_t place_free_bytes(int device) {
+    PlaceArena &a = place_arena();
+    std::lock_guard<std::mutex> lock(a.mu);
+    size_t n = 0;
+    for (const PlaceArenaBlock &b : a.blocks[device & 63]) {
+        size_t u = 0;
+        for (const auto &r : b.used) u += r.second;
+        n += b.size - u;
+    }
+    return n;
+}
+// placement blocks nobody holds a piece of go back to the driver (spal_cache_trim); a device left without any walks again
+void place_trim() {
+    PlaceArena &a = place_arena();
+    std::lock_guard<std::mutex> lock(a.mu);
+    int cur = 0;
+    (void)hipGetDevice(&cur);
+    for (int d = 0; d < 64; ++d) {
+        auto &v = a.blocks[d];
+        bool any = false;
+        for (size_t i = 0; i < v.size();) {
+            if (v[i].used.empty()) {
+                if (!any) { (void)hipSetDevice(d); any = true; }
+                (void)hipFree(v[i].base);
+                v.erase(v.begin() + (long)i);
+            } else {
+                ++i;
+            }
+        }
+        if (v.empty()) a.walked[d] = false;
+    }
+    (void)hipSetDevice(cur);
+}
+bool place_walked(int device) {
+    PlaceArena &a = place_arena();
+    std::lock_guard<std::mutex> lock(a.mu);
+    return a.walked[device & 63];
+}
+void place_set_walked(int device) {
+    PlaceArena &a = place_arena();
+    std::lock_guard<std::mutex> lock(a.mu);
+    a.walked[device & 63] = true;
+}
+
+hipError_t stream_acquire(hipStream_t *out) {
+    int device = 0;
+    hipError_t e = hipGetDevice(&device);
+    if (e != hipSuccess) return e;
+    {
+        StreamPool &p = stream_pool();
+        std::lock_guard<std::mutex> lock(p.mu);
+        for (size_t i = 0; i < p.idle.size(); ++i)
+            if (p.idle[i].first == device) {
+                *out = p.idle[i].second;
+                p.idle.erase(p.idle.begin() + i);
+                return hipSuccess;
+            }
+    }
+    return hipStreamCreateWithFlags(out, hipStreamNonBlocking);
+}
+void stream_release(hipStream_t s) {
+    if (!s) return;
+    int device = 0;
+    if (hipGetDevice(&device) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
+        (void)hipStreamDestroy(s);
+        return;
+    }
+    StreamPool &p = stream_pool();
+    std::lock_guard<std::mutex> lock(p.mu);
+    if (p.idle.size() < 64) p.idle.emplace_back(device, s);
+    else (void)hipStreamDestroy(s);
+}
+
+hipError_t dev_alloc(void **ptr, size_t bytes) {
+    *ptr = nullptr;
+    if (bytes == 0) bytes = 1;
+    int device = 0;
+    hipError_t e = hipGetDevice(&device);
+    if (e != hipSuccess) return e;
+    DevCache &c = dev_cache();
+    const size_t want = size_class(bytes);
+    {
+        std::lock_guard<std::mutex> lock(c.mu);
+        size_t best = (size_t)-1;
+        for (size_t i = 0; i < c.free_blocks.size(); ++i) {
+            const auto &b = c.free_blocks[i];
+            const bool fits = want >= kCacheLargeBytes ? (b.bytes >= want && b.bytes <= want + want / 4)
+                                                       : b.bytes == want;
+            if (b.device == device && fits && (best == (size_t)-1 || b.bytes < c.free_blocks[best].bytes))
+                best = i;
+        }
+        if (best != (size_t)-1) {
+            DevCache::Block b = c.free_blocks[best];
+            c.free_blocks.erase(c.free_blocks.begin() + best);
+            c.cached_bytes -= b.bytes;
+            c.live.push_back(b);
+            *ptr = b.p;
+            return hipSuccess;
+        }
+    }
+    e = hipMalloc(ptr, want);
+    if (e == hipErrorOutOfMemory) {  // give the cache back and retry once
+        (void)hipGetLastError();
+        dev_cache_trim();
+        e = hipMalloc(ptr, want);
+    }
+    if (e == hipSuccess) {
+        std::lock_guard<std::mutex> lock(c.mu);
+        c.live.push_back({*ptr, want, device});
+    }
+    return e;
+}
+
+hipError_t dev_free(void *ptr) {
+    if (!ptr) return hipSuccess;
+    DevCache &c = dev_cache();
+    DevCache::Block b{nullptr, 0, 0};
+    {
+        std::lock_guard<std::mutex> lock(c.mu);
+        for (size_t i = 0; i < c.live.size(); ++i)
+            if (c.live[i].p == ptr) { b = c.live[i]; c.live.erase(c.live.begin() + i); break; }
+    }
+    if (!b.p) return hipFree(ptr);  // not ours: straight back
+    // what hipFree would have done: no user of the block is still running -- on the block's OWN device, whatever
+    // device the caller has selected
+    int cur = -1;
+    (void)hipGetDevice(&cur);
+    if (cur != b.device) (void)hipSetDevice(b.device);
+    hipError_t e = hipDeviceSynchronize();
+    if (cur >= 0 && cur != b.device) (void)hipSetDevice(cur);
+    std::lock_guard<std::mutex> lock(c.mu);
+    if (e == hipSuccess && c.cached_bytes + b.bytes <= c.limit) {
+        c.free_blocks.push_back(b);
+        c.cached_bytes += b.bytes;
+        return hipSuccess;
+    }
+    if (cur != b.device) (void)hipSetDevice(b.device);
+    e = hipFree(ptr);
+    if (cur >= 0 && cur != b.device) (void)hipSetDevice(cur);
+    return e;
+}
+
+void dev_cache_trim() {
+    DevCache &c = dev_cache();
+    std::vector<DevCache::Block> blocks;
+    {
+        std::lock_guard<std::mutex> lock(c.mu);
+        blocks.swap(c.free_blocks);
+        c.cached_bytes = 0;
+    }
+    int prev = -1;
+    (void)hipGetDevice(&prev);
+    for (auto &b : blocks) { (void)hipSetDevice(b.device); (void)hipFree(b.p); }
+    if (prev >= 0) (void)hipSetDevice(prev);
+}
+
+}  // namespace spal
+
+using namespace spal;
+
+extern "C" {
+
+int spal_device_count(int *count) {
+    if (!count) return fail(SPAL_ERR_INVALID_ARGUMENT, "spal_device_count: count is NULL");
+    int n = 0;
+    hipError_t e = hipGetDeviceCount(&n);
+    if (e != hipSuccess) { (void)hipGetLastError(); n = 0; }
+    *count = n;
+    return SPAL_OK;
+}
+
+// ---- device memory helpers ---------------------------------------------------
+int spal_dev_malloc(int device, size_t bytes, void **ptr) {
+    if (!ptr) return fail(SPAL_ERR_INVALID_ARGUMENT, "spal_dev_malloc: ptr is NULL");
+    *ptr = nullptr;
+    DeviceGuard guard(device);
+    if (guard.status != SPAL_OK) return guard.status;
+    SPAL_HIP_TRY(dev_alloc((void **)ptr, bytes ? bytes : 1));
+    return SPAL_OK;
+}
+int spal_dev_free(int device, void *ptr) {
+    if (!ptr) return SPAL_OK;
+    DeviceGuard guard(device);
+    if (guard.status != SPAL_OK) return guard.status;
+    SPAL_HIP_TRY(dev_free(ptr));
+    return SPAL_OK;
+}
+int spal_memcpy_h2d(int device, void *dst_dev, const void *src_host, size_t bytes) {
+    if (bytes && (!dst_dev || !src_host)) return fail(SPAL_ERR_INVALID_ARGUMENT, "spal_memcpy_h2d: null pointer");
+    DeviceGuard guard(device);
+    if (guard.status != SPAL_OK) return guard.status;
+    if (bytes) SPAL_HIP_TRY(hipMemcpy(dst_dev, src_host, bytes, hipMemcpyHostToDevice));
+    return SPAL_OK;
+}
+int spal_memcpy_d2h(int device, void *dst_host, const void *src_dev, size_t bytes) {
+    if (bytes && (!dst_host || !src_dev)) return fail(SPAL_ERR_INVALID_ARGUMENT, "spal_memcpy_d2h: null pointer");
+    DeviceGuard guard(device);
+    if (guard.status != SPAL_OK) return guard.status;
+    if (bytes) SPAL_HIP_TRY(hipMemcpy(dst_host, src_dev, bytes, hipMemcpyDeviceToHost));
+    return SPAL_OK;
+}
+int spal_cache_trim(void) {
+    dev_cache_trim();
+    place_trim();
+    return SPAL_OK;
+}
+int spal_device_synchronize(int device) {
+    DeviceGuard guard(device);
+    if (guard.status != SPAL_OK) return guard.status;
+    SPAL_HIP_TRY(hipDeviceSynchronize());
+    return SPAL_OK;
+}
+
+}  // extern "C"

@@ -57,7 +57,9 @@ struct DeviceGuard {
 // cache of freed blocks (exact-fit-ish reuse, bounded by SPAL_CACHE_BYTES, default a quarter
 // of the device's memory, at least 8 GiB).  dev_free synchronises the device first,
 // like hipFree does, so a cached block is never handed out while work that used
-// it is still in flight.  Small blocks are rounded up to a power of two.
+// it is still in flight.  Small blocks are rounded up to a power of two.  (spal_device.hip, like the placement blocks and
+// the stream pool below.)
+
 // Stored entries a handle accepts: entry offsets are 32-bit on the device and the kernels compute
 // `offset + a batch` (at most a few thousand entries past the end, clamped afterwards) in 32 bits.
 constexpr uint64_t kMaxEntries = 0xffffffffull - 65536ull;
@@ -92,6 +94,36 @@ struct DevBuf {
 void dev_cache_trim();                            // releases every cached block
 hipError_t stream_acquire(hipStream_t *out);      // a non-blocking stream of the current device (pooled)
 void stream_release(hipStream_t s);               // synchronises it and returns it to the pool
+
+// ---- setup-time timer ----------------------------------------------------------
+// The planner, the autotune and the placement walk choose between forms of a product by time.  A SetupTimer owns two
+// events for its lifetime (created by the first run, destroyed on every path out of its scope) and does one thing: `warm`
+// untimed and `n` timed calls of `fn` -- which returns a status, e.g. a csr_launch -- on `st`; *ms = what the n took
+// together.  The first failing call of fn ends the run with its status, a failing HIP call with SPAL_ERR_HIP and
+// "<who>: <HIP's text>".
+struct SetupTimer {
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    SetupTimer() = default;
+    SetupTimer(const SetupTimer &) = delete;
+    SetupTimer &operator=(const SetupTimer &) = delete;
+    ~SetupTimer() {
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+    }
+    template <typename F>
+    int run(hipStream_t st, int warm, int n, F &&fn, float *ms, const char *who) {
+        *ms = 0.f;
+        hipError_t e = e0 ? hipSuccess : hipEventCreate(&e0);
+        if (e == hipSuccess && !e1) e = hipEventCreate(&e1);
+        for (int i = 0; i < warm && e == hipSuccess; ++i) SPAL_TRY(fn());
+        if (e == hipSuccess) e = hipEventRecord(e0, st);
+        for (int i = 0; i < n && e == hipSuccess; ++i) SPAL_TRY(fn());
+        if (e == hipSuccess) e = hipEventRecord(e1, st);
+        if (e == hipSuccess) e = hipEventSynchronize(e1);
+        if (e == hipSuccess) e = hipEventElapsedTime(ms, e0, e1);
+        return e == hipSuccess ? SPAL_OK : fail(SPAL_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+    }
+};
 
 // ---- host helpers ------------------------------------------------------------
 unsigned host_threads();
@@ -383,10 +415,17 @@ struct spal_coo {
 };
 
 namespace spal {
-// implemented in spal_csr.hip
+// implemented in spal_csr_plan.hip: chooses the kernel family of the products and builds its tables
 int csr_plan_build(spal_csr *a);
+constexpr uint32_t kWinBase = 256;     // rows per entry of spal_csr::win_base, the planner's cache of column windows
+// implemented in spal_csr_split.hip (for csr_plan_build): the row split, *did = it was built; and, once it is, the
+// block-window kernel timed against it (the faster form stays)
+int csr_try_row_split(spal_csr *a, bool *did);
+int csr_blockwin_or_split(spal_csr *a);
+// implemented in spal_csr.hip
 int csr_launch(spal_csr *a, const void *x_dev, void *y_dev, hipStream_t stream);
 int csr_ensure_plan(spal_csr *a, hipStream_t launch_stream, bool from_launch);
+void csr_free(spal_csr *a);            // the handle and everything it owns (NULL is fine)
 // implemented in spal_spmm.hip: Y = A * X enqueued on `stream` (tile 0 = automatic); reads a's plain arrays only, no plan
 int spmm_launch(spal_csr *a, int tile, uint64_t k, const void *x_dev, uint64_t ldx, void *y_dev, uint64_t ldy,
                 hipStream_t stream);
@@ -396,6 +435,8 @@ int spmm_describe_append(char *buf, size_t buf_len, const spal_csr *a);
 int csc_csr_twin(spal_csc *a, spal_csr **out);
 // implemented in spal_csr_slide.hip: the sliding-window kernel for a plan with plan.slide set
 hipError_t launch_slide(const spal_csr *a, const void *x, void *y, hipStream_t st);
+// ... its plan (for csr_plan_build): decides whether it can run the chosen stream plan and builds its step descriptors
+int slide_plan(spal_csr *a, uint32_t rpt, const std::vector<uint4> &desc, const std::vector<uint32_t> &skip, uint32_t super_pages);
 // ... and the column-panel kernel over a->d_ptiles
 hipError_t launch_panel(const spal_csr *a, const void *x, void *y, hipStream_t st);
 // implemented in spal_csc_rowtiles.hip: CSC scatter over row tiles

@@ -1337,3 +1337,87 @@ def test_row_split_on_power_law_rows(oracle, dtype):
     assert_spmv_close(dev.spmv(x), y_ref, bound, tol)
     dev.set_option("row_split", -1)
     assert dev.describe()["kernel"] == "split"
+
+
+# Every key spal_csr_set_option accepts: (values at the ends of what it takes, the nearest values it refuses on each side
+# -- and, where the accepted set has holes, one inside a hole --, the full text of spal_last_error() for a refusal).
+_M01 = "{} must be 0 or 1"
+_MAUTO = "{} must be -1 (auto), 0 or 1"
+_CSR_OPTIONS = {
+    "blockwin": ((-1, 1), (-2, 2), _MAUTO),
+    "row_split": ((-1, 1), (-2, 2), _MAUTO),
+    "row_split_threshold": ((1, 4096), (0, 4097), "row_split_threshold must be in [1, 4096]"),
+    "kernel": ((0, 2), (-1, 3), "kernel must be 0 (auto), 1 (vector) or 2 (stream)"),
+    "rows_per_block": ((0, 16, 65536), (-1, 15, 17, 65537, 65552), "rows_per_block must be a multiple of 16 in [16, 65536]"),
+    "lanes_per_row": ((0, 2, 64), (-1, 1, 3, 65, 128), "lanes_per_row must be one of 2,4,8,16,32,64"),
+    "lds_x": ((-1, 1), (-2, 2), _MAUTO),
+    "unroll": ((0, 1, 4), (-1, 3, 5), "unroll must be 1, 2 or 4"),
+    "stream_global": ((0, 1), (-1, 2), _M01),
+    "window_pages": ((0, 64), (-1, 65), "window_pages must be in [0, 64]"),
+    "col16": ((0, 1), (-1, 2), _M01),
+    "skew": ((-1, 1), (-2, 2), _MAUTO),
+    "stream_row_max": ((1, 1024), (0, 1025), "stream_row_max must be in [1, 1024]"),
+    "nt_store": ((0, 1), (-1, 2), _M01),
+    "persistent": ((0, 1), (-1, 2), _M01),
+    "persistent_blocks": ((0, 8, 4096), (-1, 7, 12, 4097, 4104), "persistent_blocks must be 0 (auto) or a multiple of 8 in [8, 4096]"),
+    "rows_per_tile": ((0, 8, 256), (-1, 7, 48, 257), "rows_per_tile must be 0 (auto), 256, 128, 64, 32, 24, 16, 12 or 8"),
+    "tiles_per_wave": ((4, 8), (3, 6, 9), "tiles_per_wave must be 4 or 8"),
+    "slide": ((-1, 1), (-2, 2), _MAUTO),
+    "panel_pages": ((0, 255), (-1, 256), "panel_pages must be in [0, 255]"),
+    "panel_window": ((0, 624), (-1, 625), "panel_window must be in [0, 624] pages"),
+    "panel_on": ((0, 1), (-1, 2), _M01),
+    "slide_run": ((0, 65535), (-1, 65536), "slide_run must be in [0, 65535]"),
+    "slide_on": ((0, 1), (-1, 2), _M01),
+    "slide_even": ((0, 1), (-1, 2), _M01),
+    "arith_bounds": ((0, 1), (-1, 2), _M01),
+    "split_tiles": ((0, 1), (-1, 2), _M01),
+    "place_tries": ((0, 16), (-1, 17), "place_tries must be in [0, 16]"),
+    "uniform_rows": ((0, 1), (-1, 2), _M01),
+    "prefetch": ((1, 2), (0, 3), "prefetch must be 1 or 2"),
+    # (this test runs the production library; an ablation build takes bits 8 ... 15)
+    "diag": ((), (0, 256), "diag: this library is not an ablation build (-DSPAL_DIAG)"),
+    "walk_blocks": ((1, 128), (0, 129), "walk_blocks must be in [1, 128]"),
+    "xcd_chunk": ((0, 4096), (-1, 4097), "xcd_chunk must be in [0, 4096]"),
+    "cblock": ((-1, 1), (-2, 2), _MAUTO),
+    "cblock_rows": ((0, 8192), (-1, 8193),
+                    "cblock_rows (rows of a row block of the column-blocked kernel) must be 0 (auto) or in [1, 8192]"),
+    "cblock_shift": ((0, 8, 24), (-1, 7, 25),
+                     "cblock_shift (log2 of the columns of a column block) must be 0 (auto: 2 MB of x) or in [8, 24]"),
+    "cblock_form": ((-1, 1), (-2, 2), "cblock_form must be -1 (auto), 0 (entry-parallel) or 1 (rows form)"),
+    "threads": ((0, 512, 1024), (-1, 511, 768, 1025), "threads must be 512 or 1024"),
+    # the keys of the other operations on this handle (spal_spgemm.hip, spal_spadd.hip, spal_spmm.hip)
+    "spgemm_route": ((0, 2), (-1, 3), "spgemm_route must be 0 (auto), 1 (LDS tiers wherever they fit) or 2 (large-row tier)"),
+    "spgemm_lds_cap": ((0, 4096), (-1, 4097), "spgemm_lds_cap must be 0 (default) or in [1, 4096]"),
+    "spadd_tile": ((0, 16, 2048), (-1, 8, 24, 2049, 4096), "spadd_tile must be 0 (default, 2048) or a power of two in [16, 2048]"),
+    "spmm_tile": ((0, 1, 32), (-1, 3, 33, 64), "spmm_tile must be 0 (automatic) or one of 1, 2, 4, 8, 16, 32"),
+    "no_such_option": ((), (0,), "unknown option 'no_such_option'"),
+}
+
+
+def test_every_option_at_its_boundaries(oracle):
+    """spal_csr_set_option, key by key, on a small band: the lowest and the highest value a key takes are taken, the
+    nearest values on each side are refused with SPAL_ERR_INVALID_ARGUMENT and the key's own message, and after EVERY
+    call -- taken or refused, a refusal goes through the restore of the saved plan -- the product agrees with the oracle.
+    (A fresh handle per key: no option is read in the light of another one set before it.)"""
+    from spalinalg_amd import _ffi
+    n = 50_000
+    rp, ci, va = synth.banded_csr(n, n, 14, 4096, 21)
+    x = synth.vector(n)
+    y_ref = oracle.csr_spmv(rp, ci, va, x)
+    bound = oracle.csr_abs_bound(rp, ci, va, x)
+    seen = 0
+    for key, (taken, refused, msg) in _CSR_OPTIONS.items():
+        dev = sp.CsrMatrix(n, n, rp, ci, va).device()
+        for value in taken + refused:
+            if value in taken:
+                dev.set_option(key, value)
+            else:
+                with pytest.raises(_ffi.Panic) as err:
+                    dev.set_option(key, value)
+                assert err.value.status == _ffi.SPAL_ERR_INVALID_ARGUMENT, (key, value)
+                assert str(err.value) == msg.format(key), (key, value)
+                assert _ffi.lib().spal_last_error().decode() == msg.format(key), (key, value)
+            assert_spmv_close(dev.spmv(x), y_ref, bound, 1e-10)
+            seen += 1
+        dev.close()
+    assert seen == sum(len(t) + len(r) for t, r, _ in _CSR_OPTIONS.values())
