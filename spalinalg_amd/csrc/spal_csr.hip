@@ -310,10 +310,9 @@ void csr_free(spal_csr *a) {
 
 int csr_adopt_device(int device, int elem_size, uint64_t nrows, uint64_t ncols, uint64_t nnz,
                      uint64_t cap_entries, uint32_t *d_rowptr, uint32_t *d_colind, void *d_values,
-                     spal_csr **out, const std::vector<uint2> *win256, bool eager_copies, bool lazy_plan,
+                     spal_csr **out, bool eager_copies, bool lazy_plan,
                      uint2 *d_win_groups, uint32_t win_groups, uint32_t win_group_bits) {
     spal_csr *a = new spal_csr;
-    if (win256 && win256->size() == (nrows + kWinBase - 1) / kWinBase) a->win_base = *win256;
     if (d_win_groups && win_group_bits <= 8 && win_groups == (uint32_t)((nrows + (1ull << win_group_bits) - 1) >> win_group_bits)) {
         a->d_win_groups = d_win_groups; a->win_groups = win_groups; a->win_group_bits = win_group_bits;
     } else if (d_win_groups) {
@@ -401,7 +400,7 @@ static int csr_create_rows(int device, uint64_t r0, uint64_t r1, uint64_t ncols,
                     "spal_csr_create: upload failed: %s", hipGetErrorString(e));
     }
     spal_csr *a = nullptr;
-    int st = csr_adopt_device(device, (int)sizeof(T), nrows, ncols, nnz, cap, d_rp, d_ci, d_v, &a, nullptr, true);
+    int st = csr_adopt_device(device, (int)sizeof(T), nrows, ncols, nnz, cap, d_rp, d_ci, d_v, &a, true);
     if (st != SPAL_OK) { cleanup(); return st; }
     *out = a;
     return SPAL_OK;

@@ -139,7 +139,7 @@ int csr_try_row_split(spal_csr *a, bool *did) {
     int st = e == hipSuccess ? SPAL_OK : SPAL_ERR_HIP;
     if (st == SPAL_OK) {
         // (a handle of its own: its plan is built here, eagerly, with this handle's user options that concern the stream kernels)
-        st = csr_adopt_device(a->device, a->elem_size, a->nrows, a->ncols, nnz_s, cap, d_rps, d_cis, d_vas, &child, nullptr, true, true);
+        st = csr_adopt_device(a->device, a->elem_size, a->nrows, a->ncols, nnz_s, cap, d_rps, d_cis, d_vas, &child, true, true);
         if (st == SPAL_OK) {
             child->split_child = 1;
             child->plan.row_split = 0;

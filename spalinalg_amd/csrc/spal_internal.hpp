@@ -215,7 +215,7 @@ struct CsrPlan {
          user_unroll = false, user_threads = false, user_rows_per_tile = false;
 };
 
-// implemented in spal_coo.hip: stable sort of the entries by their minor index
+// implemented in spal_transpose.hip: stable sort of the entries by their minor index
 // (compressed-by-major -> compressed-by-minor); outputs are hipMalloc'ed with
 // *out_cap entries (nnz + over-read margin) and owned by the caller
 int transpose_device(int device, int elem_size, uint64_t nmajor, uint64_t nminor, uint64_t nnz,
@@ -399,7 +399,7 @@ struct spal_coo {
     void *d_vals = nullptr;
     void *d_work = nullptr;   // sort buffers + scratch of the assembly, allocated at upload
     // a HINT only: the fullest group of rows [0] / columns [1] the last assembly met (it picks the group kernel's LDS
-    // capacity without a host round trip; the kernel verifies it, see coo_assemble_t).  Nothing else about the triplets
+    // capacity without a host round trip; the kernel verifies it, see coo_local_sort).  Nothing else about the triplets
     // is kept between assemblies.
     uint32_t cap_hint[2] = {0, 0};
     int loop_hint[2] = {0, 0};   // the last assembly by rows [0] / columns [1] met a row beyond the network form's reach
@@ -455,11 +455,11 @@ hipError_t blockwin_launch(const spal_csr *a, const void *x, void *y, hipStream_
 // assembly, which produces CSR directly on the device)
 // (cap_entries = allocated entries of d_colind / d_values; re-allocated with
 // padding when smaller than nnz + the kernels' over-read margin)
-// (win256: optional {first column, one past the last} of every 256 rows, if the caller has it; or d_win_groups: the same
-//  per group of 2^win_group_bits <= 256 rows, on the device, ownership passes to the handle)
+// (d_win_groups: optional {first column, one past the last} of every group of 2^win_group_bits <= 256 rows, on the
+//  device, if the caller has it; ownership passes to the handle)
 int csr_adopt_device(int device, int elem_size, uint64_t nrows, uint64_t ncols,
                      uint64_t nnz, uint64_t cap_entries, uint32_t *d_rowptr,
                      uint32_t *d_colind, void *d_values, spal_csr **out,
-                     const std::vector<uint2> *win256 = nullptr, bool eager_copies = false, bool lazy_plan = false,
+                     bool eager_copies = false, bool lazy_plan = false,
                      uint2 *d_win_groups = nullptr, uint32_t win_groups = 0, uint32_t win_group_bits = 0);
 }  // namespace spal

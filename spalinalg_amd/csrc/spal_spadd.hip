@@ -523,7 +523,7 @@ int csr_binary(const char *fn, bool sub, spal_csr_t a, spal_csr_t b, void *strea
     const auto tp = std::chrono::steady_clock::now();
     // eager plan, as spal_csr_mul's result (a lazily planned handle can reach csr_blockwin_or_split re-entrantly)
     const int st = csr_adopt_device(a->device, a->elem_size, a->nrows, a->ncols, r.nnz, r.cap, r.ptr, r.ind, r.val, out,
-                                    nullptr, true, false);
+                                    true, false);
     if (st != SPAL_OK) {
         free_sum(r);
         return st;
@@ -604,7 +604,7 @@ int spal_csr_neg(spal_csr_t a, void *stream, spal_csr_t *out) {
     SPAL_TRY(spneg(a->elem_size, Operand{a->nrows, a->nnz, a->d_rowptr, a->d_colind, a->d_values}, (hipStream_t)stream, r));
     const auto tp = std::chrono::steady_clock::now();
     const int st = csr_adopt_device(a->device, a->elem_size, a->nrows, a->ncols, r.nnz, r.cap, r.ptr, r.ind, r.val, out,
-                                    nullptr, true, false);
+                                    true, false);
     if (st != SPAL_OK) {
         free_sum(r);
         return st;

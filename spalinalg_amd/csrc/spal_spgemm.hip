@@ -552,7 +552,7 @@ int spal_csr_mul(spal_csr_t a, spal_csr_t b, void *stream, spal_csr_t *out) {
     const auto tp = std::chrono::steady_clock::now();
     // eager plan, like a handle built from host arrays (a lazily planned handle can reach csr_blockwin_or_split re-entrantly)
     int st = csr_adopt_device(a->device, a->elem_size, a->nrows, b->ncols, r.nnz, r.cap, r.ptr, r.ind, r.val, out,
-                              nullptr, true, false);
+                              true, false);
     if (st != SPAL_OK) {
         free_product(r);
         return st;

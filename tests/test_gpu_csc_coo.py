@@ -583,6 +583,31 @@ def test_coo_empty_and_all_cancelled(oracle):
     assert csr.nnz() == 0
 
 
+@pytest.mark.parametrize("shape", [(4, 4), (3, 5)])
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+def test_coo_empty_and_all_cancelled_to_csc(oracle, dtype, shape):
+    """The CSC twin of test_coo_empty_and_all_cancelled: an empty COO matrix assembled by columns is a complete CSC
+    handle (colptr of zeros, products of zeros, convertible to an empty CSR), and triplets that all cancel leave an
+    empty CSC matrix with the oracle's bits."""
+    nr, nc = shape
+    csc = sp.CscMatrix.from_coo(sp.CooMatrix(nr, nc, dtype))
+    assert csc.colptr().tolist() == [0] * (nc + 1)
+    assert csc.nnz() == 0
+    assert (csc * np.ones(nc, dtype=dtype)).tolist() == [0.0] * nr
+    csr = sp.CsrMatrix.from_csc(csc)
+    assert csr.nnz() == 0 and csr.rowptr().tolist() == [0] * (nr + 1)
+    assert (csr * np.ones(nc, dtype=dtype)).tolist() == [0.0] * nr
+    r = np.array([1, 1, 3, 3], dtype=np.uint64)
+    c = np.array([2, 2, 0, 0], dtype=np.uint64)
+    v = np.array([1.5, -1.5, 2.0, -2.0], dtype=dtype)
+    csc = sp.CscMatrix.from_coo(sp.CooMatrix.with_triplets(4, 4, r, c, v))
+    p, i, w = oracle.coo_to_csc(4, 4, r, c, v)
+    bits = np.uint64 if dtype == np.float64 else np.uint32
+    assert np.array_equal(csc.colptr(), p) and np.array_equal(csc.rowind(), i)
+    assert np.array_equal(csc.values().view(bits), w.view(bits))
+    assert csc.nnz() == 0
+
+
 def test_coo_long_runs_and_skew(oracle):
     """one (row, col) repeated 20000 times, and one row holding half of all
     entries: the sort and the run sums must not depend on balance."""
