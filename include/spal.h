@@ -302,6 +302,62 @@ int spal_csc_spmm_dev_f64(spal_csc_t a, uint64_t k, const double *x_dev, uint64_
 int spal_csc_spmm_dev_f32(spal_csc_t a, uint64_t k, const float *x_dev, uint64_t ldx,
                           float *y_dev, uint64_t ldy, void *stream);
 
+/* ---- L x = b, U x = b: sparse triangular solve, CSR and CSC --------------------------
+ * Not in the reference (it has no solve, as it has no SpMV); the contract is this sequential loop, which the device
+ * reproduces bit for bit in f32 and f64 (NaN by position).  A is square and stored as the handle stores it, columns
+ * strictly ascending inside a row.  `uplo` (0 lower, 1 upper) selects the triangle that is used; entries of the other
+ * triangle are ignored, so a full matrix can be swept as it is (Gauss-Seidel, SSOR, an ILU factor stored in one matrix).
+ *   lower, rows i = 0 .. n-1 (upper: i = n-1 .. 0, entries with j > i):
+ *     s = b[i]
+ *     for each stored (i, j, v) with j < i, in ascending column:  s = s - (v * x[j])   -- product rounded, then the
+ *                                                                  difference: no FMA
+ *     x[i] = s / d   (d = the stored (i, i) entry; IEEE division)      unit_diag = 1: x[i] = s, a stored (i, i) ignored
+ * A stored zero diagonal is not an error: the result is what the division gives (inf / NaN, propagating).
+ * SPAL_ERR_INVALID_ARGUMENT: A not square; unit_diag = 0 and some row stores no (i, i) entry (the message names the
+ * first such row); uplo or unit_diag outside {0, 1}; null pointers; wrong lengths; an _f64 entry on an f32 handle or
+ * the reverse.  SPAL_ERR_UNSUPPORTED: a handle held as row blocks (more than 2^32 - 65537 entries).
+ *
+ * spal_trsv_levels is the analysis, host only: level_of[i] = 0 when row i uses no off-diagonal entry of the chosen
+ * triangle, else 1 + the largest level_of[j] over the entries it uses; *nlevels = 1 + the largest level (0 for n = 0).
+ * One sequential O(nnz) pass.  A stored column >= n ("not square") and, with unit_diag = 0, a missing diagonal are
+ * refused as above.
+ *
+ * On a handle there is one plan per triangle, built by the first solve of that triangle or by spal_*_trsv_analyse:
+ * the row pointers and columns are copied back from the device (handles keep no host arrays), analysed on the host,
+ * and the rows uploaded ordered by level -- this synchronises `stream` and allocates; its cost is "analysis_ms" of
+ * describe().  Every later solve of that triangle allocates nothing and synchronises nothing: it enqueues the plan's
+ * recorded launches on the caller's stream (the host forms copy b up, solve in place, copy x back and synchronise).
+ * Rows of one level are independent and levels are ordered BY STREAM ORDER ONLY: a level wider than the option
+ * "trsv_chain_rows" is one launch (a thread per row); every maximal run of consecutive narrower levels is one launch of
+ * one workgroup that walks them with a barrier in between.  Nothing waits on another workgroup, so a solve cannot hang.
+ * "trsv_chain_rows" (spal_csr_set_option / spal_csc_set_option, >= 0): 0 = every level its own launch, a huge value =
+ * one launch for the whole solve; the bits do not depend on it.  Default 256.
+ * x_dev == b_dev is allowed (in place); otherwise b is not written and the two must not overlap partially.
+ * Calls on one handle serialise on the handle's lock (plan creation included), from any number of threads.
+ * CSC handles solve on their CSR twin (built on the device on first use), so the definition holds unchanged.
+ * describe() gains "trsv": {"analyses": plans built, "lower" / "upper": {levels, max_level_rows, launches,
+ * chain_launches, chain_rows, analysis_ms}} once a triangle was analysed. */
+int spal_trsv_levels(uint64_t n, const uint64_t *rowptr, const uint64_t *colind, int uplo, int unit_diag,
+                     uint64_t *level_of, uint64_t *nlevels);
+int spal_csr_trsv_analyse(spal_csr_t a, int uplo, int unit_diag, void *stream);
+int spal_csr_trsv_f64(spal_csr_t a, int uplo, int unit_diag, const double *b, uint64_t b_len,
+                      double *x, uint64_t x_len);                                /* host vectors */
+int spal_csr_trsv_f32(spal_csr_t a, int uplo, int unit_diag, const float *b, uint64_t b_len,
+                      float *x, uint64_t x_len);
+int spal_csr_trsv_dev_f64(spal_csr_t a, int uplo, int unit_diag, const double *b_dev, double *x_dev,
+                          void *stream);                                         /* enqueued, not synchronised */
+int spal_csr_trsv_dev_f32(spal_csr_t a, int uplo, int unit_diag, const float *b_dev, float *x_dev,
+                          void *stream);
+int spal_csc_trsv_analyse(spal_csc_t a, int uplo, int unit_diag, void *stream);
+int spal_csc_trsv_f64(spal_csc_t a, int uplo, int unit_diag, const double *b, uint64_t b_len,
+                      double *x, uint64_t x_len);
+int spal_csc_trsv_f32(spal_csc_t a, int uplo, int unit_diag, const float *b, uint64_t b_len,
+                      float *x, uint64_t x_len);
+int spal_csc_trsv_dev_f64(spal_csc_t a, int uplo, int unit_diag, const double *b_dev, double *x_dev,
+                          void *stream);
+int spal_csc_trsv_dev_f32(spal_csc_t a, int uplo, int unit_diag, const float *b_dev, float *x_dev,
+                          void *stream);
+
 /* ---- CSR <-> CSC on the device ------------------------------------------------
  * Replace `impl From<&CscMatrix<T>> for CsrMatrix<T>` (src/csr/conv/csc.rs:4-52)
  * and `impl From<&CsrMatrix<T>> for CscMatrix<T>` (src/csc/conv/csr.rs:4-52),

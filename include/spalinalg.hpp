@@ -62,10 +62,12 @@ template <> struct Abi<double> {
     static constexpr auto csr_create = spal_csr_create_f64;
     static constexpr auto csr_spmv = spal_csr_spmv_f64;
     static constexpr auto csr_spmm = spal_csr_spmm_f64;
+    static constexpr auto csr_trsv = spal_csr_trsv_f64;
     static constexpr auto csr_download = spal_csr_download_f64;
     static constexpr auto csc_create = spal_csc_create_f64;
     static constexpr auto csc_spmv = spal_csc_spmv_f64;
     static constexpr auto csc_spmm = spal_csc_spmm_f64;
+    static constexpr auto csc_trsv = spal_csc_trsv_f64;
     static constexpr auto coo_to_csr = spal_coo_to_csr_f64;
     static constexpr auto coo_to_csc = spal_coo_to_csc_f64;
     static constexpr auto csc_download = spal_csc_download_f64;
@@ -74,10 +76,12 @@ template <> struct Abi<float> {
     static constexpr auto csr_create = spal_csr_create_f32;
     static constexpr auto csr_spmv = spal_csr_spmv_f32;
     static constexpr auto csr_spmm = spal_csr_spmm_f32;
+    static constexpr auto csr_trsv = spal_csr_trsv_f32;
     static constexpr auto csr_download = spal_csr_download_f32;
     static constexpr auto csc_create = spal_csc_create_f32;
     static constexpr auto csc_spmv = spal_csc_spmv_f32;
     static constexpr auto csc_spmm = spal_csc_spmm_f32;
+    static constexpr auto csc_trsv = spal_csc_trsv_f32;
     static constexpr auto coo_to_csr = spal_coo_to_csr_f32;
     static constexpr auto coo_to_csc = spal_coo_to_csc_f32;
     static constexpr auto csc_download = spal_csc_download_f32;
@@ -155,6 +159,23 @@ class CsrMatrix {
         std::vector<T> y(nrows_ * k);
         detail::check(detail::Abi<T>::csr_spmm(device_handle(), k, x.data(), k, ncols_, y.data(), k, nrows_));
         return y;
+    }
+
+    // x with L x = b (the lower triangle of this matrix, `lower`) or U x = b; entries of the other triangle are ignored,
+    // `unit_diagonal` takes the diagonal as ones.  Substitution on the device, bit for bit the sequential loop of
+    // include/spal.h (spal_csr_trsv_*).  Panics when the matrix is not square, when b has another length than nrows,
+    // and (without unit_diagonal) when a row stores no diagonal entry.
+    std::vector<T> solve_triangular(const std::vector<T> &b, bool lower = true, bool unit_diagonal = false) const {
+        if (nrows_ != ncols_)
+            throw Panic(SPAL_ERR_INVALID_ARGUMENT, "solve_triangular: the matrix is not square (" + std::to_string(nrows_) +
+                                                       " x " + std::to_string(ncols_) + ")");
+        if (b.size() != nrows_)
+            throw Panic(SPAL_ERR_INVALID_ARGUMENT, "solve_triangular: b.len() = " + std::to_string(b.size()) +
+                                                       " but the matrix has " + std::to_string(nrows_) + " rows");
+        std::vector<T> x(nrows_);
+        detail::check(detail::Abi<T>::csr_trsv(device_handle(), lower ? 0 : 1, unit_diagonal ? 1 : 0, b.data(), b.size(),
+                                               x.data(), x.size()));
+        return x;
     }
 
     // C = A * B: `impl Mul for &CsrMatrix<T>` (src/csr/ops/mul.rs:5-59) on the device, bit-identical.
@@ -265,6 +286,23 @@ class CscMatrix {
         std::vector<T> y(nrows_ * k);
         detail::check(detail::Abi<T>::csc_spmm(device_handle(), k, x.data(), k, ncols_, y.data(), k, nrows_));
         return y;
+    }
+
+    // x with L x = b (the lower triangle of this matrix, `lower`) or U x = b; entries of the other triangle are ignored,
+    // `unit_diagonal` takes the diagonal as ones.  Substitution on the device, bit for bit the sequential loop of
+    // include/spal.h (spal_csc_trsv_*).  Panics when the matrix is not square, when b has another length than nrows,
+    // and (without unit_diagonal) when a row stores no diagonal entry.
+    std::vector<T> solve_triangular(const std::vector<T> &b, bool lower = true, bool unit_diagonal = false) const {
+        if (nrows_ != ncols_)
+            throw Panic(SPAL_ERR_INVALID_ARGUMENT, "solve_triangular: the matrix is not square (" + std::to_string(nrows_) +
+                                                       " x " + std::to_string(ncols_) + ")");
+        if (b.size() != nrows_)
+            throw Panic(SPAL_ERR_INVALID_ARGUMENT, "solve_triangular: b.len() = " + std::to_string(b.size()) +
+                                                       " but the matrix has " + std::to_string(nrows_) + " rows");
+        std::vector<T> x(nrows_);
+        detail::check(detail::Abi<T>::csc_trsv(device_handle(), lower ? 0 : 1, unit_diagonal ? 1 : 0, b.data(), b.size(),
+                                               x.data(), x.size()));
+        return x;
     }
     // C = A * B: `impl Mul for &CscMatrix<T>` (src/csc/ops/mul.rs:5-60) on the device, bit-identical.
     CscMatrix operator*(const CscMatrix &rhs) const {

@@ -4,7 +4,7 @@
 use std::marker::PhantomData;
 use std::os::raw::{c_int, c_void};
 
-use super::{ffi, scalar::{HipScalar, HipSpmm}};
+use super::{ffi, scalar::{HipScalar, HipSpmm, HipTrsv}};
 use crate::{CooMatrix, CscMatrix, CsrMatrix};
 
 /// `CsrMatrix<T>` resident on a GPU (include/spal.h: spal_csr_t).
@@ -100,6 +100,33 @@ impl<T: HipScalar> DeviceCsr<T> {
     pub unsafe fn spmm_dev(&self, k: usize, x_dev: *const T, ldx: usize, y_dev: *mut T, ldy: usize, stream: *mut c_void)
     where T: HipSpmm {
         ffi::check(T::csr_spmm_dev(self.h, k as u64, x_dev, ldx as u64, y_dev, ldy as u64, stream));
+    }
+
+    /// x with L x = b (`lower`) or U x = b for the chosen triangle of this square matrix; entries of the other triangle
+    /// are ignored, `unit_diagonal` takes the diagonal as ones.  Bit for bit the sequential substitution of
+    /// include/spal.h.  Panics when the matrix is not square, `b.len() != nrows`, or (without `unit_diagonal`) a row
+    /// stores no diagonal entry.
+    pub fn solve_triangular(&self, b: &[T], lower: bool, unit_diagonal: bool) -> Vec<T> where T: HipTrsv {
+        let (nrows, _, _) = self.shape();
+        assert_eq!(nrows, b.len());
+        let mut x = vec![T::zero(); nrows];
+        unsafe { ffi::check(T::csr_trsv(self.h, if lower { 0 } else { 1 }, unit_diagonal as c_int, b, &mut x)); }
+        x
+    }
+
+    /// `solve_triangular` on device pointers (`x_dev == b_dev` solves in place), enqueued on `stream` and not
+    /// synchronised once the triangle has its plan (`trsv_analyse`, or the first solve, builds it).
+    ///
+    /// # Safety
+    /// `b_dev` and `x_dev` must hold `nrows` elements each.
+    pub unsafe fn solve_triangular_dev(&self, lower: bool, unit_diagonal: bool, b_dev: *const T, x_dev: *mut T, stream: *mut c_void)
+    where T: HipTrsv {
+        ffi::check(T::csr_trsv_dev(self.h, if lower { 0 } else { 1 }, unit_diagonal as c_int, b_dev, x_dev, stream));
+    }
+
+    /// Builds the solve plan of one triangle now (host level analysis; synchronises `stream`).
+    pub fn trsv_analyse(&self, lower: bool, unit_diagonal: bool, stream: *mut c_void) {
+        unsafe { ffi::check(ffi::spal_csr_trsv_analyse(self.h, if lower { 0 } else { 1 }, unit_diagonal as c_int, stream)); }
     }
 
     /// Setup-time autotune on the caller's device vectors (kernel form, placement of the values array).
@@ -227,6 +254,33 @@ impl<T: HipScalar> DeviceCsc<T> {
     pub unsafe fn spmm_dev(&self, k: usize, x_dev: *const T, ldx: usize, y_dev: *mut T, ldy: usize, stream: *mut c_void)
     where T: HipSpmm {
         ffi::check(T::csc_spmm_dev(self.h, k as u64, x_dev, ldx as u64, y_dev, ldy as u64, stream));
+    }
+
+    /// x with L x = b (`lower`) or U x = b for the chosen triangle of this square matrix; entries of the other triangle
+    /// are ignored, `unit_diagonal` takes the diagonal as ones.  Bit for bit the sequential substitution of
+    /// include/spal.h.  Runs on the handle's CSR twin.  Panics when the matrix is not square, `b.len() != nrows`, or (without `unit_diagonal`) a row
+    /// stores no diagonal entry.
+    pub fn solve_triangular(&self, b: &[T], lower: bool, unit_diagonal: bool) -> Vec<T> where T: HipTrsv {
+        let (nrows, _, _) = self.shape();
+        assert_eq!(nrows, b.len());
+        let mut x = vec![T::zero(); nrows];
+        unsafe { ffi::check(T::csc_trsv(self.h, if lower { 0 } else { 1 }, unit_diagonal as c_int, b, &mut x)); }
+        x
+    }
+
+    /// `solve_triangular` on device pointers (`x_dev == b_dev` solves in place), enqueued on `stream` and not
+    /// synchronised once the triangle has its plan (`trsv_analyse`, or the first solve, builds it).
+    ///
+    /// # Safety
+    /// `b_dev` and `x_dev` must hold `nrows` elements each.
+    pub unsafe fn solve_triangular_dev(&self, lower: bool, unit_diagonal: bool, b_dev: *const T, x_dev: *mut T, stream: *mut c_void)
+    where T: HipTrsv {
+        ffi::check(T::csc_trsv_dev(self.h, if lower { 0 } else { 1 }, unit_diagonal as c_int, b_dev, x_dev, stream));
+    }
+
+    /// Builds the solve plan of one triangle now (host level analysis; synchronises `stream`).
+    pub fn trsv_analyse(&self, lower: bool, unit_diagonal: bool, stream: *mut c_void) {
+        unsafe { ffi::check(ffi::spal_csc_trsv_analyse(self.h, if lower { 0 } else { 1 }, unit_diagonal as c_int, stream)); }
     }
 
     /// "kernel" = 1: atomic scatter, 2 (default): converted to CSR on the device once, deterministic.

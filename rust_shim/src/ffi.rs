@@ -67,6 +67,17 @@ extern "C" {
     pub fn spal_csc_spmm_f32(a: *mut spal_csc, k: u64, x: *const f32, ldx: u64, x_rows: u64, y: *mut f32, ldy: u64, y_rows: u64) -> c_int;
     pub fn spal_csc_spmm_dev_f64(a: *mut spal_csc, k: u64, x_dev: *const f64, ldx: u64, y_dev: *mut f64, ldy: u64, stream: *mut c_void) -> c_int;
     pub fn spal_csc_spmm_dev_f32(a: *mut spal_csc, k: u64, x_dev: *const f32, ldx: u64, y_dev: *mut f32, ldy: u64, stream: *mut c_void) -> c_int;
+    pub fn spal_trsv_levels(n: u64, rowptr: *const u64, colind: *const u64, uplo: c_int, unit_diag: c_int, level_of: *mut u64, nlevels: *mut u64) -> c_int;
+    pub fn spal_csr_trsv_analyse(a: *mut spal_csr, uplo: c_int, unit_diag: c_int, stream: *mut c_void) -> c_int;
+    pub fn spal_csr_trsv_f64(a: *mut spal_csr, uplo: c_int, unit_diag: c_int, b: *const f64, b_len: u64, x: *mut f64, x_len: u64) -> c_int;
+    pub fn spal_csr_trsv_f32(a: *mut spal_csr, uplo: c_int, unit_diag: c_int, b: *const f32, b_len: u64, x: *mut f32, x_len: u64) -> c_int;
+    pub fn spal_csr_trsv_dev_f64(a: *mut spal_csr, uplo: c_int, unit_diag: c_int, b_dev: *const f64, x_dev: *mut f64, stream: *mut c_void) -> c_int;
+    pub fn spal_csr_trsv_dev_f32(a: *mut spal_csr, uplo: c_int, unit_diag: c_int, b_dev: *const f32, x_dev: *mut f32, stream: *mut c_void) -> c_int;
+    pub fn spal_csc_trsv_analyse(a: *mut spal_csc, uplo: c_int, unit_diag: c_int, stream: *mut c_void) -> c_int;
+    pub fn spal_csc_trsv_f64(a: *mut spal_csc, uplo: c_int, unit_diag: c_int, b: *const f64, b_len: u64, x: *mut f64, x_len: u64) -> c_int;
+    pub fn spal_csc_trsv_f32(a: *mut spal_csc, uplo: c_int, unit_diag: c_int, b: *const f32, b_len: u64, x: *mut f32, x_len: u64) -> c_int;
+    pub fn spal_csc_trsv_dev_f64(a: *mut spal_csc, uplo: c_int, unit_diag: c_int, b_dev: *const f64, x_dev: *mut f64, stream: *mut c_void) -> c_int;
+    pub fn spal_csc_trsv_dev_f32(a: *mut spal_csc, uplo: c_int, unit_diag: c_int, b_dev: *const f32, x_dev: *mut f32, stream: *mut c_void) -> c_int;
     pub fn spal_csc_to_csr(a: *mut spal_csc, out: *mut *mut spal_csr) -> c_int;
     pub fn spal_csr_to_csc(a: *mut spal_csr, out: *mut *mut spal_csc) -> c_int;
     pub fn spal_csr_mul(a: *mut spal_csr, b: *mut spal_csr, stream: *mut c_void, out: *mut *mut spal_csr) -> c_int;

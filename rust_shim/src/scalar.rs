@@ -106,3 +106,32 @@ macro_rules! impl_hip_spmm {
 }
 impl_hip_spmm!(f64, spal_csr_spmm_f64, spal_csr_spmm_dev_f64, spal_csc_spmm_f64, spal_csc_spmm_dev_f64);
 impl_hip_spmm!(f32, spal_csr_spmm_f32, spal_csr_spmm_dev_f32, spal_csc_spmm_f32, spal_csc_spmm_dev_f32);
+
+/// L x = b / U x = b (the spal_*_trsv_* entry points): `uplo` 0 lower / 1 upper, `unit_diag` 0 / 1.
+pub trait HipTrsv: HipScalar {
+    unsafe fn csr_trsv(a: *mut ffi::spal_csr, uplo: c_int, unit_diag: c_int, b: &[Self], x: &mut [Self]) -> c_int;
+    unsafe fn csr_trsv_dev(a: *mut ffi::spal_csr, uplo: c_int, unit_diag: c_int, b: *const Self, x: *mut Self, stream: *mut c_void) -> c_int;
+    unsafe fn csc_trsv(a: *mut ffi::spal_csc, uplo: c_int, unit_diag: c_int, b: &[Self], x: &mut [Self]) -> c_int;
+    unsafe fn csc_trsv_dev(a: *mut ffi::spal_csc, uplo: c_int, unit_diag: c_int, b: *const Self, x: *mut Self, stream: *mut c_void) -> c_int;
+}
+
+macro_rules! impl_hip_trsv {
+    ($t:ty, $csr_trsv:ident, $csr_trsv_dev:ident, $csc_trsv:ident, $csc_trsv_dev:ident) => {
+        impl HipTrsv for $t {
+            unsafe fn csr_trsv(a: *mut ffi::spal_csr, uplo: c_int, unit_diag: c_int, b: &[Self], x: &mut [Self]) -> c_int {
+                ffi::$csr_trsv(a, uplo, unit_diag, b.as_ptr(), b.len() as u64, x.as_mut_ptr(), x.len() as u64)
+            }
+            unsafe fn csr_trsv_dev(a: *mut ffi::spal_csr, uplo: c_int, unit_diag: c_int, b: *const Self, x: *mut Self, stream: *mut c_void) -> c_int {
+                ffi::$csr_trsv_dev(a, uplo, unit_diag, b, x, stream)
+            }
+            unsafe fn csc_trsv(a: *mut ffi::spal_csc, uplo: c_int, unit_diag: c_int, b: &[Self], x: &mut [Self]) -> c_int {
+                ffi::$csc_trsv(a, uplo, unit_diag, b.as_ptr(), b.len() as u64, x.as_mut_ptr(), x.len() as u64)
+            }
+            unsafe fn csc_trsv_dev(a: *mut ffi::spal_csc, uplo: c_int, unit_diag: c_int, b: *const Self, x: *mut Self, stream: *mut c_void) -> c_int {
+                ffi::$csc_trsv_dev(a, uplo, unit_diag, b, x, stream)
+            }
+        }
+    };
+}
+impl_hip_trsv!(f64, spal_csr_trsv_f64, spal_csr_trsv_dev_f64, spal_csc_trsv_f64, spal_csc_trsv_dev_f64);
+impl_hip_trsv!(f32, spal_csr_trsv_f32, spal_csr_trsv_dev_f32, spal_csc_trsv_f32, spal_csc_trsv_dev_f32);

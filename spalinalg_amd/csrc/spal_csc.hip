@@ -995,6 +995,14 @@ int spal_csc_set_option(spal_csc_t a, const char *key, int64_t value) {
         if (spgemm_option(key, value, &a->spgemm_route, &a->spgemm_lds_cap, &st)) return st;
         if (spadd_option(key, value, &a->spadd_tile, &st)) return st;   // ... and of A + B / A - B
         if (spmm_option(key, value, &a->spmm_tile, &st)) return st;     // ... and of Y = A * X
+        if (!strcmp(key, "trsv_chain_rows")) {   // ... and of the triangular solve, which runs on the CSR twin
+            DeviceGuard guard(a->device);
+            if (guard.status != SPAL_OK) return guard.status;
+            spal_csr *twin = nullptr;
+            SPAL_TRY(csc_csr_twin(a, &twin));
+            (void)trsv_option(twin, key, value, &st);
+            return st;
+        }
     }
     DeviceGuard guard(a->device);
     if (guard.status != SPAL_OK) return guard.status;
@@ -1087,7 +1095,8 @@ int spal_csc_describe(spal_csc_t a, char *buf, size_t buf_len) {
              (a->rowtiles && a->rowtiles_user != 0 && a->flush == 0) ? 1 : 0, a->rt_rows, a->rt_ntiles, a->rt_xcap, a->rowtiles_failed);
     SPAL_TRY(spgemm_describe_append(buf, buf_len, a->spgemm_info));   // a product of spal_csc_mul: how it was built
     SPAL_TRY(spadd_describe_append(buf, buf_len, a->spadd_info));     // a result of spal_csc_add / _sub / _neg
-    return spmm_describe_append(buf, buf_len, a->as_csr);             // an SpMM ran on it (on the CSR twin)
+    SPAL_TRY(spmm_describe_append(buf, buf_len, a->as_csr));          // an SpMM ran on it (on the CSR twin)
+    return trsv_describe_append(buf, buf_len, a->as_csr);             // ... or a triangular solve was analysed
 }
 
 }  // extern "C"

@@ -302,6 +302,7 @@ void csr_free(spal_csr *a) {
     else place_free(a->device, a->d_vec_block);
     (void)dev_free(a->d_win_groups);
     cblock_free(a);
+    trsv_free(a);
     (void)dev_free(a->d_x);
     (void)dev_free(a->d_y);
     stream_release(a->stream);
@@ -651,6 +652,7 @@ int spal_csr_set_option(spal_csr_t a, const char *key, int64_t value) {
         if (spgemm_option(key, value, &a->spgemm_route, &a->spgemm_lds_cap, &st)) return st;
         if (spadd_option(key, value, &a->spadd_tile, &st)) return st;   // ... and of A + B / A - B
         if (spmm_option(key, value, &a->spmm_tile, &st)) return st;     // ... and of Y = A * X
+        if (trsv_option(a, key, value, &st)) return st;                 // ... and of L x = b / U x = b
     }
     if (!a->parts.empty()) {   // row blocks: every block takes the option (each plans for its own rows)
         for (spal_csr *part : a->parts) SPAL_TRY(spal_csr_set_option(part, key, value));
@@ -861,7 +863,8 @@ int spal_csr_describe(spal_csr_t a, char *buf, size_t buf_len) {
     SPAL_TRY(csr_describe_plan(a, buf, buf_len));
     SPAL_TRY(spgemm_describe_append(buf, buf_len, a->spgemm_info));   // a product of spal_csr_mul: how it was built
     SPAL_TRY(spadd_describe_append(buf, buf_len, a->spadd_info));     // a result of spal_csr_add / _sub / _neg
-    return spmm_describe_append(buf, buf_len, a);                     // an SpMM ran on it
+    SPAL_TRY(spmm_describe_append(buf, buf_len, a));                  // an SpMM ran on it
+    return trsv_describe_append(buf, buf_len, a);                     // a triangle of it was analysed for a solve
 }
 
 }  // extern "C"

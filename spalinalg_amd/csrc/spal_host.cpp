@@ -1,5 +1,6 @@
 // spal_host.cpp -- host-only parts of libspal_hip.so: error state, the
-// constructor invariants of the reference and the row partitioner.  Nothing here touches a device.
+// constructor invariants of the reference, the row partitioner and the level analysis of the triangular solve.
+// Nothing here touches a device.
 #include "spal_internal.hpp"
 
 namespace spal {
@@ -109,6 +110,56 @@ const char *invariant_text(int reason, bool csr) {
     }
 }
 
+// ---------------------------------------------------------------------------
+// Level analysis of the triangular solve.  level_of[i] = 0 when row i uses no off-diagonal entry of the
+// chosen triangle, else 1 + the largest level of the rows it reads.  One sequential pass, ascending rows for the lower
+// triangle and descending for the upper one, so every level read is final.  dpos (optional) receives, per row, the
+// position of its first entry with column >= row: the strictly lower entries end there, the diagonal (if stored) sits
+// there, the strictly upper ones follow it.
+// ---------------------------------------------------------------------------
+template <typename Idx, typename Lev>
+int trsv_levels_impl(uint64_t n, const Idx *rowptr, const Idx *colind, int uplo, Lev *level_of, uint64_t *nlevels,
+                     uint64_t *first_missing_diag, Idx *dpos) {
+    uint64_t top = 0, missing = n;
+    for (uint64_t k = 0; k < n; ++k) {
+        const uint64_t i = uplo ? n - 1 - k : k;
+        const uint64_t b = rowptr[i], e = rowptr[i + 1];
+        if (e > b && (uint64_t)colind[e - 1] >= n)   // columns ascend: the last one is the largest
+            return fail(SPAL_ERR_INVALID_ARGUMENT,
+                        "triangular solve: the matrix is not square (row %llu stores column %llu, n = %llu)",
+                        (unsigned long long)i, (unsigned long long)colind[e - 1], (unsigned long long)n);
+        uint64_t p = b, lev = 0;
+        if (!uplo) {
+            for (; p < e && (uint64_t)colind[p] < i; ++p) lev = std::max<uint64_t>(lev, (uint64_t)level_of[colind[p]] + 1);
+        } else {
+            // (a binary search would not change the O(nnz) bound: the entries skipped here are read once)
+            while (p < e && (uint64_t)colind[p] < i) ++p;
+        }
+        const bool has_diag = p < e && (uint64_t)colind[p] == i;
+        if (dpos) dpos[i] = (Idx)p;
+        if (!has_diag && (missing == n || uplo)) missing = i;   // descending walk: the last one met is the first row
+        if (uplo)
+            for (uint64_t q = p + (has_diag ? 1 : 0); q < e; ++q)
+                lev = std::max<uint64_t>(lev, (uint64_t)level_of[colind[q]] + 1);
+        level_of[i] = (Lev)lev;
+        top = std::max(top, lev);
+    }
+    *nlevels = n ? top + 1 : 0;
+    *first_missing_diag = missing;
+    return SPAL_OK;
+}
+
+int trsv_levels_u32(uint64_t n, const uint32_t *rowptr, const uint32_t *colind, int uplo, uint32_t *level_of,
+                    uint64_t *nlevels, uint64_t *first_missing_diag, uint32_t *dpos) {
+    return trsv_levels_impl<uint32_t, uint32_t>(n, rowptr, colind, uplo, level_of, nlevels, first_missing_diag, dpos);
+}
+
+int trsv_missing_diag(const char *fn, uint64_t row) {
+    return fail(SPAL_ERR_INVALID_ARGUMENT,
+                "%s: row %llu stores no diagonal entry (a non-unit triangular solve divides by it)", fn,
+                (unsigned long long)row);
+}
+
 }  // namespace spal
 
 using namespace spal;
@@ -167,6 +218,18 @@ int spal_partition_rows(const uint64_t *rowptr, uint64_t nrows, uint32_t nparts,
         bounds[g] = std::max(cut, bounds[g - 1]);
     }
     bounds[nparts] = nrows;
+    return SPAL_OK;
+}
+
+int spal_trsv_levels(uint64_t n, const uint64_t *rowptr, const uint64_t *colind, int uplo, int unit_diag,
+                     uint64_t *level_of, uint64_t *nlevels) {
+    if (!rowptr || !level_of || !nlevels || (!colind && n && rowptr[n]))
+        return fail(SPAL_ERR_INVALID_ARGUMENT, "spal_trsv_levels: null array");
+    if ((uplo != 0 && uplo != 1) || (unit_diag != 0 && unit_diag != 1))
+        return fail(SPAL_ERR_INVALID_ARGUMENT, "spal_trsv_levels: uplo must be 0 (lower) or 1 (upper) and unit_diag 0 or 1");
+    uint64_t missing = n;
+    SPAL_TRY((trsv_levels_impl<uint64_t, uint64_t>(n, rowptr, colind, uplo, level_of, nlevels, &missing, nullptr)));
+    if (!unit_diag && missing < n) return trsv_missing_diag("spal_trsv_levels", missing);
     return SPAL_OK;
 }
 

@@ -233,9 +233,31 @@ int spadd_option(const char *key, int64_t value, uint32_t *tile, int *status);
 int spadd_describe_append(char *buf, size_t buf_len, const std::string &info);
 // implemented in spal_spmm.hip: the option "spmm_tile" of either handle type (as spgemm_option)
 int spmm_option(const char *key, int64_t value, int *tile, int *status);
+// implemented in spal_trsv.hip: the option "trsv_chain_rows" of a CSR handle (as spgemm_option; existing plans get their
+// launch lists rebuilt under the handle's lock)
+int trsv_option(spal_csr *a, const char *key, int64_t value, int *status);
+// implemented in spal_host.cpp: the level analysis of spal_trsv_levels on the device's 32-bit arrays; *first_missing_diag
+// = n when every row stores its diagonal (no error either way), dpos[i] = the first entry of row i with column >= i
+int trsv_levels_u32(uint64_t n, const uint32_t *rowptr, const uint32_t *colind, int uplo, uint32_t *level_of,
+                    uint64_t *nlevels, uint64_t *first_missing_diag, uint32_t *dpos);
+int trsv_missing_diag(const char *fn, uint64_t row);   // the error of a non-unit solve on such a matrix
 // implemented in spal_csc.hip: handle around device arrays it takes ownership of
 int csc_adopt_device(int device, int elem_size, uint64_t nrows, uint64_t ncols, uint64_t nnz,
                      uint32_t *d_colptr, uint32_t *d_rowind, void *d_values, spal_csc **out);
+
+// Triangular solve (spal_trsv.hip): the plan of one triangle of a handle.
+struct TrsvLaunch { uint32_t level0, level1; int chain; };   // levels [level0, level1); chain: one workgroup walks them
+struct TrsvPlan {
+    uint64_t levels = 0, max_level_rows = 0;
+    uint64_t first_missing_diag = 0;       // nrows when every row stores its diagonal
+    uint2 *d_rows = nullptr;               // nrows x {row, first entry with column >= row}, ordered by (level, row)
+    uint32_t *d_level_ptr = nullptr;       // levels + 1 offsets into d_rows
+    std::vector<uint32_t> level_ptr;       // ... and on the host, for the launch list
+    std::vector<TrsvLaunch> launches;
+    uint64_t chain_launches = 0;
+    double analysis_ms = 0.0;              // copy back + levels + ordering + upload, host clock
+};
+constexpr int64_t kTrsvChainRowsDefault = 256;
 }  // namespace spal
 
 // The opaque handle types of spal.h.
@@ -323,6 +345,10 @@ struct spal_csr {
     // Y = A * X (spal_spmm.hip)
     int spmm_tile = 0;             // option "spmm_tile": column tile, 0 = automatic
     uint64_t spmm_last = 0;        // {tile << 32 | k} of the last SpMM on this handle (0: none yet), for describe
+    // L x = b, U x = b (spal_trsv.hip); guarded by mu
+    int64_t trsv_chain_rows = spal::kTrsvChainRowsDefault;   // option "trsv_chain_rows": the widest level the chain kernel takes
+    spal::TrsvPlan *trsv[2] = {nullptr, nullptr};            // [uplo], built by the first solve or by spal_csr_trsv_analyse
+    int trsv_analyses = 0;         // plans built so far (describe)
 };
 
 struct spal_csc {
@@ -431,6 +457,10 @@ int spmm_launch(spal_csr *a, int tile, uint64_t k, const void *x_dev, uint64_t l
                 hipStream_t stream);
 // ... and the "spmm" object a handle (a may be null) adds to its describe() line once an SpMM ran on it
 int spmm_describe_append(char *buf, size_t buf_len, const spal_csr *a);
+// implemented in spal_trsv.hip: frees a handle's solve plans (csr_free), and the "trsv" object a handle (a may be null)
+// adds to its describe() line once a triangle was analysed
+void trsv_free(spal_csr *a);
+int trsv_describe_append(char *buf, size_t buf_len, spal_csr *a);
 // implemented in spal_csc.hip: the handle's CSR twin, built on the device by whoever asks first
 int csc_csr_twin(spal_csc *a, spal_csr **out);
 // implemented in spal_csr_slide.hip: the sliding-window kernel for a plan with plan.slide set

@@ -1,0 +1,412 @@
+// spal_trsv.hip -- sparse triangular solve L x = b / U x = b on a CSR handle.  The contract is a sequential
+// loop: rows ascending (lower) or descending (upper); s = b[i]; for every stored entry of row i in the chosen triangle
+// off the diagonal, in ascending column, s = s - (v * x[j]) with product and difference rounded separately; then
+// x[i] = s / d (d the stored diagonal) or x[i] = s (unit diagonal).  Entries of the other triangle are ignored.  Every
+// row's sum is sequential whatever runs in parallel, so the device returns those bits, f32 and f64.
+//
+// THE SCHEDULE IS LEVELS.  The host analysis (trsv_levels_u32, spal_host.cpp) gives every row its level: 0 when it reads
+// no other row, else one more than the deepest row it reads.  Rows of a level are independent; levels are ordered.  The
+// plan keeps the rows ordered by (level, row) with, per row, the position of its first entry at or past the diagonal;
+// the matrix arrays are read where they are.  ORDER BETWEEN WORKGROUPS COMES FROM STREAM ORDER ALONE: no flags, no spins,
+// no counters, no grid syncs -- a solve cannot hang and does not depend on which workgroups are resident.
+//   * trsv_level: one launch = one level, a thread per row.
+//   * trsv_chain: one launch = a run of consecutive narrow levels, walked by ONE workgroup of 1024 threads with a
+//     __syncthreads() between levels (the waves of a workgroup share a CU and its L1: workgroup-scope ordering covers
+//     the x it has just stored).  A level wider than the workgroup is looped over.  While a level is being summed the
+//     next level's row heads (row, bounds, b[row]) are already in flight: they do not depend on x.
+// Maximal runs of levels at most "trsv_chain_rows" wide are one chain launch; every wider level is a level launch.  The
+// list is recorded once; a solve after that allocates nothing and synchronises nothing.
+// A long row is walked by its one thread, kBatch gathers in flight at a time, the subtractions in stored order.
+#include "spal_internal.hpp"
+
+#include <chrono>
+
+#pragma clang fp contract(off)
+
+namespace spal {
+namespace {
+
+constexpr int kLevelThreads = 256;
+constexpr int kChainThreads = 1024;
+
+// What a row needs that does not depend on x.
+constexpr uint32_t kBatch = 8;   // gathers of x in flight per thread
+template <typename T>
+struct RowHead {
+    uint32_t row, p0, p1, dp;   // off-diagonal entries [p0, p1) of the triangle; dp: where the diagonal is, if stored
+    T rhs;
+};
+
+template <typename T, int UPLO>
+__device__ __forceinline__ RowHead<T> trsv_head(uint2 rd, const uint32_t *__restrict__ rowptr,
+                                                const uint32_t *__restrict__ colind, const T *b) {
+    RowHead<T> h;
+    h.row = rd.x;
+    h.dp = rd.y;
+    if (UPLO == 0) {
+        h.p0 = rowptr[rd.x];
+        h.p1 = rd.y;
+    } else {
+        h.p1 = rowptr[rd.x + 1];
+        h.p0 = rd.y + ((rd.y < h.p1 && colind[rd.y] == rd.x) ? 1u : 0u);
+    }
+    h.rhs = b[rd.x];
+    return h;
+}
+
+// b and x may be the same array: row i reads b[i] before it stores x[i], and nothing else of b.
+template <typename T>
+__device__ __forceinline__ void trsv_row(const RowHead<T> &h, const uint32_t *__restrict__ colind,
+                                         const T *__restrict__ values, T *x, int unit_diag) {
+    T s = h.rhs;
+    for (uint32_t p = h.p0; p < h.p1; p += kBatch) {
+        T xv[kBatch], v[kBatch];
+#pragma unroll
+        for (uint32_t u = 0; u < kBatch; ++u) {   // past the row's end the last entry's addresses repeat
+            const uint32_t q = min(p + u, h.p1 - 1);
+            xv[u] = x[colind[q]];
+            v[u] = values[q];
+        }
+#pragma unroll
+        for (uint32_t u = 0; u < kBatch; ++u)
+            if (p + u < h.p1) s = s - v[u] * xv[u];
+    }
+    x[h.row] = unit_diag ? s : s / values[h.dp];   // plain division: correctly rounded
+}
+
+template <typename T, int UPLO>
+__global__ __launch_bounds__(kLevelThreads) void trsv_level(const uint2 *__restrict__ rows, uint32_t k0, uint32_t k1,
+                                                            const uint32_t *__restrict__ rowptr,
+                                                            const uint32_t *__restrict__ colind,
+                                                            const T *__restrict__ values, const T *b, T *x,
+                                                            int unit_diag) {
+    const uint64_t k = (uint64_t)k0 + (uint64_t)blockIdx.x * kLevelThreads + threadIdx.x;
+    if (k >= k1) return;
+    trsv_row<T>(trsv_head<T, UPLO>(rows[k], rowptr, colind, b), colind, values, x, unit_diag);
+}
+
+template <typename T, int UPLO>
+__global__ __launch_bounds__(kChainThreads) void trsv_chain(const uint2 *__restrict__ rows,
+                                                            const uint32_t *__restrict__ level_ptr, uint32_t l0,
+                                                            uint32_t l1, const uint32_t *__restrict__ rowptr,
+                                                            const uint32_t *__restrict__ colind,
+                                                            const T *__restrict__ values, const T *b, T *x,
+                                                            int unit_diag) {
+    const uint32_t tid = threadIdx.x;
+    uint32_t a0 = level_ptr[l0], a1 = level_ptr[l0 + 1];
+    RowHead<T> cur = {};
+    if ((uint64_t)a0 + tid < a1) cur = trsv_head<T, UPLO>(rows[a0 + tid], rowptr, colind, b);
+    for (uint32_t l = l0; l < l1; ++l) {
+        const bool more = l + 1 < l1;
+        const uint32_t a2 = more ? level_ptr[l + 2] : a1;
+        RowHead<T> nxt = {};
+        if (more && (uint64_t)a1 + tid < a2) nxt = trsv_head<T, UPLO>(rows[a1 + tid], rowptr, colind, b);
+        if ((uint64_t)a0 + tid < a1) trsv_row<T>(cur, colind, values, x, unit_diag);
+        for (uint64_t k = (uint64_t)a0 + tid + kChainThreads; k < a1; k += kChainThreads)
+            trsv_row<T>(trsv_head<T, UPLO>(rows[k], rowptr, colind, b), colind, values, x, unit_diag);
+        __syncthreads();   // level l's x is stored and visible to the workgroup before level l + 1 gathers it
+        cur = nxt;
+        a0 = a1;
+        a1 = a2;
+    }
+}
+
+template <typename T, int UPLO>
+hipError_t run_list_t(const spal_csr *a, const TrsvPlan *p, int unit_diag, const T *b, T *x, hipStream_t st) {
+    const T *values = (const T *)a->d_values;
+    for (const TrsvLaunch &ln : p->launches) {
+        if (ln.chain) {
+            hipLaunchKernelGGL((trsv_chain<T, UPLO>), dim3(1), dim3(kChainThreads), 0, st, p->d_rows, p->d_level_ptr,
+                               ln.level0, ln.level1, a->d_rowptr, a->d_colind, values, b, x, unit_diag);
+        } else {
+            const uint32_t k0 = p->level_ptr[ln.level0], k1 = p->level_ptr[ln.level1];
+            hipLaunchKernelGGL((trsv_level<T, UPLO>), dim3((k1 - k0 + kLevelThreads - 1) / kLevelThreads),
+                               dim3(kLevelThreads), 0, st, p->d_rows, k0, k1, a->d_rowptr, a->d_colind, values, b, x,
+                               unit_diag);
+        }
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+// Maximal runs of consecutive levels of at most chain_rows rows are one chain launch, every other level a launch.
+void record_launches(TrsvPlan *p, int64_t chain_rows) {
+    p->launches.clear();
+    p->chain_launches = 0;
+    const uint32_t nl = (uint32_t)p->levels;
+    uint32_t run0 = 0;
+    bool in_run = false;
+    for (uint32_t l = 0; l <= nl; ++l) {
+        const bool narrow = l < nl && (int64_t)(p->level_ptr[l + 1] - p->level_ptr[l]) <= chain_rows;
+        if (narrow && !in_run) { run0 = l; in_run = true; }
+        if (!narrow && in_run) {
+            p->launches.push_back({run0, l, 1});
+            ++p->chain_launches;
+            in_run = false;
+        }
+        if (!narrow && l < nl) p->launches.push_back({l, l + 1, 0});
+    }
+}
+
+void plan_free(TrsvPlan *p) {
+    if (!p) return;
+    (void)dev_free(p->d_rows);
+    (void)dev_free(p->d_level_ptr);
+    delete p;
+}
+
+// Builds the plan of one triangle.  Called with a->mu held; calls nothing that plans lazily (copies, the host
+// analysis, two allocations).  The row pointers and columns come back from the device: a handle assembled there has
+// no host arrays, and one created from host arrays did not keep them.
+int plan_build(spal_csr *a, int uplo, hipStream_t st) {
+    const auto t0 = std::chrono::steady_clock::now();
+    const uint64_t n = a->nrows;
+    std::vector<uint32_t> rp(n + 1), ci(a->nnz), lev(n), dpos(n);
+    SPAL_HIP_TRY(hipMemcpyAsync(rp.data(), a->d_rowptr, rp.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    if (a->nnz)
+        SPAL_HIP_TRY(hipMemcpyAsync(ci.data(), a->d_colind, ci.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    SPAL_HIP_TRY(hipStreamSynchronize(st));
+    TrsvPlan *p = new TrsvPlan;
+    struct Guard {
+        TrsvPlan *&p;
+        ~Guard() { plan_free(p); }
+    } guard{p};
+    SPAL_TRY(trsv_levels_u32(n, rp.data(), ci.data(), uplo, lev.data(), &p->levels, &p->first_missing_diag, dpos.data()));
+    // rows by (level, row): a counting sort, stable
+    p->level_ptr.assign(p->levels + 1, 0);
+    for (uint64_t i = 0; i < n; ++i) ++p->level_ptr[lev[i] + 1];
+    for (uint64_t l = 0; l < p->levels; ++l) {
+        p->max_level_rows = std::max<uint64_t>(p->max_level_rows, p->level_ptr[l + 1]);
+        p->level_ptr[l + 1] += p->level_ptr[l];
+    }
+    std::vector<uint2> rows(n);
+    {
+        std::vector<uint32_t> at(p->level_ptr.begin(), p->level_ptr.end() - 1);
+        for (uint64_t i = 0; i < n; ++i) rows[at[lev[i]]++] = make_uint2((uint32_t)i, dpos[i]);
+    }
+    SPAL_HIP_TRY(dev_alloc((void **)&p->d_rows, n * sizeof(uint2)));
+    SPAL_HIP_TRY(dev_alloc((void **)&p->d_level_ptr, p->level_ptr.size() * sizeof(uint32_t)));
+    SPAL_HIP_TRY(hipMemcpyAsync(p->d_rows, rows.data(), n * sizeof(uint2), hipMemcpyHostToDevice, st));
+    SPAL_HIP_TRY(hipMemcpyAsync(p->d_level_ptr, p->level_ptr.data(), p->level_ptr.size() * sizeof(uint32_t),
+                                hipMemcpyHostToDevice, st));
+    SPAL_HIP_TRY(hipStreamSynchronize(st));
+    record_launches(p, a->trsv_chain_rows);
+    p->analysis_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    a->trsv[uplo] = p;
+    p = nullptr;   // the handle owns it now
+    ++a->trsv_analyses;
+    return SPAL_OK;
+}
+
+int check_flags(const char *fn, int uplo, int unit_diag) {
+    if (uplo != 0 && uplo != 1) return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: uplo = %d must be 0 (lower) or 1 (upper)", fn, uplo);
+    if (unit_diag != 0 && unit_diag != 1)
+        return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: unit_diag = %d must be 0 or 1", fn, unit_diag);
+    return SPAL_OK;
+}
+
+// The plan of `uplo`, built now if this is the first use; a->mu is held.
+int plan_get(const char *fn, spal_csr *a, int uplo, int unit_diag, hipStream_t st, TrsvPlan **out) {
+    if (!a->parts.empty())
+        return fail(SPAL_ERR_UNSUPPORTED, "%s: handles held as row blocks (more than 2^32 - 65537 entries) have no solve", fn);
+    if (a->nrows != a->ncols)
+        return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: the matrix is not square (%llu x %llu)", fn,
+                    (unsigned long long)a->nrows, (unsigned long long)a->ncols);
+    if (!a->trsv[uplo]) SPAL_TRY(plan_build(a, uplo, st));
+    TrsvPlan *p = a->trsv[uplo];
+    if (!unit_diag && p->first_missing_diag < a->nrows) return trsv_missing_diag(fn, p->first_missing_diag);
+    *out = p;
+    return SPAL_OK;
+}
+
+template <typename T>
+int solve_locked(const char *fn, spal_csr *a, int uplo, int unit_diag, const T *b, T *x, hipStream_t st) {
+    TrsvPlan *p = nullptr;
+    SPAL_TRY(plan_get(fn, a, uplo, unit_diag, st, &p));
+    const hipError_t e = uplo ? run_list_t<T, 1>(a, p, unit_diag, b, x, st) : run_list_t<T, 0>(a, p, unit_diag, b, x, st);
+    if (e != hipSuccess) return fail(SPAL_ERR_HIP, "%s: launch failed: %s", fn, hipGetErrorString(e));
+    return SPAL_OK;
+}
+
+template <typename T>
+int check_dtype(const char *fn, int elem_size) {
+    if (elem_size != (int)sizeof(T))
+        return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: handle holds %s values", fn, elem_size == 8 ? "f64" : "f32");
+    return SPAL_OK;
+}
+
+template <typename T>
+int solve_host(const char *fn, spal_csr *a, int uplo, int unit_diag, const T *b, uint64_t b_len, T *x, uint64_t x_len) {
+    if (!b || !x) return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: null vector", fn);
+    if (b_len != a->nrows || x_len != a->nrows)
+        return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: b.len() = %llu and x.len() = %llu but the matrix has %llu rows", fn,
+                    (unsigned long long)b_len, (unsigned long long)x_len, (unsigned long long)a->nrows);
+    std::lock_guard<std::mutex> lock(a->mu);
+    DevBuf v;
+    SPAL_HIP_TRY(v.alloc(a->nrows * sizeof(T)));
+    SPAL_HIP_TRY(hipMemcpyAsync(v.p, b, a->nrows * sizeof(T), hipMemcpyHostToDevice, a->stream));
+    SPAL_TRY(solve_locked<T>(fn, a, uplo, unit_diag, v.as<T>(), v.as<T>(), a->stream));
+    SPAL_HIP_TRY(hipMemcpyAsync(x, v.p, a->nrows * sizeof(T), hipMemcpyDeviceToHost, a->stream));
+    SPAL_HIP_TRY(hipStreamSynchronize(a->stream));
+    return SPAL_OK;
+}
+
+template <typename T>
+int csr_trsv_host(spal_csr *a, int uplo, int unit_diag, const T *b, uint64_t b_len, T *x, uint64_t x_len) {
+    const char *fn = "spal_csr_trsv";
+    if (!a) return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: handle is NULL", fn);
+    SPAL_TRY(check_dtype<T>(fn, a->elem_size));
+    SPAL_TRY(check_flags(fn, uplo, unit_diag));
+    DeviceGuard guard(a->device);
+    if (guard.status != SPAL_OK) return guard.status;
+    return solve_host<T>(fn, a, uplo, unit_diag, b, b_len, x, x_len);
+}
+
+template <typename T>
+int csr_trsv_dev(spal_csr *a, int uplo, int unit_diag, const T *b, T *x, void *stream) {
+    const char *fn = "spal_csr_trsv_dev";
+    if (!a) return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: handle is NULL", fn);
+    SPAL_TRY(check_dtype<T>(fn, a->elem_size));
+    SPAL_TRY(check_flags(fn, uplo, unit_diag));
+    if (!b || !x) return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: null vector", fn);
+    DeviceGuard guard(a->device);
+    if (guard.status != SPAL_OK) return guard.status;
+    std::lock_guard<std::mutex> lock(a->mu);
+    return solve_locked<T>(fn, a, uplo, unit_diag, b, x, (hipStream_t)stream);
+}
+
+int csr_trsv_analyse(const char *fn, spal_csr *a, int uplo, int unit_diag, void *stream) {
+    SPAL_TRY(check_flags(fn, uplo, unit_diag));
+    std::lock_guard<std::mutex> lock(a->mu);
+    TrsvPlan *p = nullptr;
+    return plan_get(fn, a, uplo, unit_diag, (hipStream_t)stream, &p);
+}
+
+template <typename T>
+int csc_trsv_host(spal_csc *a, int uplo, int unit_diag, const T *b, uint64_t b_len, T *x, uint64_t x_len) {
+    const char *fn = "spal_csc_trsv";
+    if (!a) return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: handle is NULL", fn);
+    SPAL_TRY(check_dtype<T>(fn, a->elem_size));
+    SPAL_TRY(check_flags(fn, uplo, unit_diag));
+    DeviceGuard guard(a->device);
+    if (guard.status != SPAL_OK) return guard.status;
+    spal_csr *twin = nullptr;
+    SPAL_TRY(csc_csr_twin(a, &twin));
+    return solve_host<T>(fn, twin, uplo, unit_diag, b, b_len, x, x_len);
+}
+
+template <typename T>
+int csc_trsv_dev(spal_csc *a, int uplo, int unit_diag, const T *b, T *x, void *stream) {
+    const char *fn = "spal_csc_trsv_dev";
+    if (!a) return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: handle is NULL", fn);
+    SPAL_TRY(check_dtype<T>(fn, a->elem_size));
+    SPAL_TRY(check_flags(fn, uplo, unit_diag));
+    if (!b || !x) return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: null vector", fn);
+    DeviceGuard guard(a->device);
+    if (guard.status != SPAL_OK) return guard.status;
+    spal_csr *twin = nullptr;
+    SPAL_TRY(csc_csr_twin(a, &twin));
+    std::lock_guard<std::mutex> lock(twin->mu);
+    return solve_locked<T>(fn, twin, uplo, unit_diag, b, x, (hipStream_t)stream);
+}
+
+}  // namespace
+
+int trsv_option(spal_csr *a, const char *key, int64_t value, int *status) {
+    if (strcmp(key, "trsv_chain_rows")) return 0;
+    if (value < 0) {
+        *status = fail(SPAL_ERR_INVALID_ARGUMENT, "trsv_chain_rows must be >= 0 (0: every level is a launch of its own)");
+        return 1;
+    }
+    std::lock_guard<std::mutex> lock(a->mu);
+    a->trsv_chain_rows = value;
+    for (TrsvPlan *p : a->trsv)
+        if (p) record_launches(p, value);
+    *status = SPAL_OK;
+    return 1;
+}
+
+void trsv_free(spal_csr *a) {
+    for (TrsvPlan *&p : a->trsv) {
+        plan_free(p);
+        p = nullptr;
+    }
+}
+
+int trsv_describe_append(char *buf, size_t buf_len, spal_csr *a) {
+    if (!a) return SPAL_OK;
+    std::string info;
+    {
+        std::lock_guard<std::mutex> lock(a->mu);
+        if (!a->trsv[0] && !a->trsv[1]) return SPAL_OK;
+        char part[384];
+        snprintf(part, sizeof part, ", \"trsv\": {\"analyses\": %d", a->trsv_analyses);
+        info = part;
+        for (int uplo = 0; uplo < 2; ++uplo) {
+            const TrsvPlan *p = a->trsv[uplo];
+            if (!p) continue;
+            snprintf(part, sizeof part,
+                     ", \"%s\": {\"levels\": %llu, \"max_level_rows\": %llu, \"launches\": %zu, \"chain_launches\": %llu, "
+                     "\"chain_rows\": %lld, \"analysis_ms\": %.3f}",
+                     uplo ? "upper" : "lower", (unsigned long long)p->levels, (unsigned long long)p->max_level_rows,
+                     p->launches.size(), (unsigned long long)p->chain_launches, (long long)a->trsv_chain_rows,
+                     p->analysis_ms);
+            info += part;
+        }
+        info += "}}";
+    }
+    const size_t len = strnlen(buf, buf_len);
+    if (len == 0 || buf[len - 1] != '}' || len + info.size() + 1 > buf_len)
+        return fail(SPAL_ERR_INVALID_ARGUMENT, "describe: buffer of %zu bytes too small", buf_len);
+    snprintf(buf + len - 1, buf_len - (len - 1), "%s", info.c_str());
+    return SPAL_OK;
+}
+
+}  // namespace spal
+
+using namespace spal;
+
+extern "C" {
+
+int spal_csr_trsv_analyse(spal_csr_t a, int uplo, int unit_diag, void *stream) {
+    if (!a) return fail(SPAL_ERR_INVALID_ARGUMENT, "spal_csr_trsv_analyse: handle is NULL");
+    DeviceGuard guard(a->device);
+    if (guard.status != SPAL_OK) return guard.status;
+    return csr_trsv_analyse("spal_csr_trsv_analyse", a, uplo, unit_diag, stream);
+}
+int spal_csr_trsv_f64(spal_csr_t a, int uplo, int unit_diag, const double *b, uint64_t b_len, double *x, uint64_t x_len) {
+    return csr_trsv_host<double>(a, uplo, unit_diag, b, b_len, x, x_len);
+}
+int spal_csr_trsv_f32(spal_csr_t a, int uplo, int unit_diag, const float *b, uint64_t b_len, float *x, uint64_t x_len) {
+    return csr_trsv_host<float>(a, uplo, unit_diag, b, b_len, x, x_len);
+}
+int spal_csr_trsv_dev_f64(spal_csr_t a, int uplo, int unit_diag, const double *b_dev, double *x_dev, void *stream) {
+    return csr_trsv_dev<double>(a, uplo, unit_diag, b_dev, x_dev, stream);
+}
+int spal_csr_trsv_dev_f32(spal_csr_t a, int uplo, int unit_diag, const float *b_dev, float *x_dev, void *stream) {
+    return csr_trsv_dev<float>(a, uplo, unit_diag, b_dev, x_dev, stream);
+}
+
+int spal_csc_trsv_analyse(spal_csc_t a, int uplo, int unit_diag, void *stream) {
+    if (!a) return fail(SPAL_ERR_INVALID_ARGUMENT, "spal_csc_trsv_analyse: handle is NULL");
+    DeviceGuard guard(a->device);
+    if (guard.status != SPAL_OK) return guard.status;
+    spal_csr *twin = nullptr;
+    SPAL_TRY(csc_csr_twin(a, &twin));
+    return csr_trsv_analyse("spal_csc_trsv_analyse", twin, uplo, unit_diag, stream);
+}
+int spal_csc_trsv_f64(spal_csc_t a, int uplo, int unit_diag, const double *b, uint64_t b_len, double *x, uint64_t x_len) {
+    return csc_trsv_host<double>(a, uplo, unit_diag, b, b_len, x, x_len);
+}
+int spal_csc_trsv_f32(spal_csc_t a, int uplo, int unit_diag, const float *b, uint64_t b_len, float *x, uint64_t x_len) {
+    return csc_trsv_host<float>(a, uplo, unit_diag, b, b_len, x, x_len);
+}
+int spal_csc_trsv_dev_f64(spal_csc_t a, int uplo, int unit_diag, const double *b_dev, double *x_dev, void *stream) {
+    return csc_trsv_dev<double>(a, uplo, unit_diag, b_dev, x_dev, stream);
+}
+int spal_csc_trsv_dev_f32(spal_csc_t a, int uplo, int unit_diag, const float *b_dev, float *x_dev, void *stream) {
+    return csc_trsv_dev<float>(a, uplo, unit_diag, b_dev, x_dev, stream);
+}
+
+}  // extern "C"

@@ -183,6 +183,34 @@ class _DeviceMatrix:
                       torch.cuda.current_stream(X.device))
         return out
 
+    def trsv_analyse(self, lower: bool = True, unit_diagonal: bool = False, stream=None) -> dict:
+        """Builds the solve plan of one triangle now (spal_*_trsv_analyse: levels on the host, setup time; synchronises
+        `stream`) instead of with the first trsv(); returns describe()["trsv"]."""
+        check(self._fn("trsv_analyse")(self._h, C.c_int(0 if lower else 1), C.c_int(1 if unit_diagonal else 0),
+                                       _stream_ptr(stream)))
+        return self.describe()["trsv"]
+
+    def trsv(self, b, lower: bool = True, unit_diagonal: bool = False) -> np.ndarray:
+        """Solves L x = b (lower) or U x = b with the chosen triangle of this square matrix; entries of the other
+        triangle are ignored.  Host vector in, host vector out.  Bit for bit the sequential substitution.
+        A float32 / float64 `b` is passed as it is: a dtype other than the handle's is refused by the library."""
+        b = np.ascontiguousarray(b)
+        if b.dtype not in (np.float32, np.float64):
+            b = b.astype(self.dtype)
+        if b.ndim != 1:
+            raise TypeError("trsv() takes one right-hand side, a 1-D vector")
+        x = np.empty_like(b)
+        check(self._fn(f"trsv_{_sfx(b.dtype)}")(self._h, C.c_int(0 if lower else 1), C.c_int(1 if unit_diagonal else 0),
+                                                _p(b), u64(b.size), _p(x), u64(x.size)))
+        return x
+
+    def trsv_dev(self, b_ptr: int, x_ptr: int, lower: bool = True, unit_diagonal: bool = False, stream=None) -> None:
+        """Device pointers (x_ptr == b_ptr solves in place); enqueued on `stream`, not synchronised once the triangle
+        has its plan (the first solve of a triangle builds it, which synchronises)."""
+        check(self._fn(f"trsv_dev_{_sfx(self.dtype)}")(self._h, C.c_int(0 if lower else 1),
+                                                       C.c_int(1 if unit_diagonal else 0), vp(b_ptr), vp(x_ptr),
+                                                       _stream_ptr(stream)))
+
     def alloc_vectors(self, stream=None):
         """Device pointers (x, y) of vectors owned by this handle and placed so that the stores of y do not collide
         with the matrix stream (spal_csr_alloc_vectors: a walk over the device's memory, setup time).  CSR handles."""
@@ -595,6 +623,20 @@ class _Compressed:
             raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT,
                         f"assertion failed: ncols == rhs.nrows (left: {self._ncols}, right: {X.shape[0]})")
         return self.device().spmm(X.astype(self.dtype, copy=False))
+
+    def solve_triangular(self, b, lower: bool = True, unit_diagonal: bool = False, device: int = 0) -> np.ndarray:
+        """x with L x = b (the lower triangle of self, `lower`) or U x = b; entries of the other triangle are ignored
+        and `unit_diagonal` takes the diagonal as ones.  Forward / backward substitution on the device, bit for bit
+        the sequential loop (spal_*_trsv_*).  The reference has no solve; a Rust binding adds it as a
+        method of the matrix types."""
+        b = np.asarray(b)
+        if self._nrows != self._ncols:
+            raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT,
+                        f"solve_triangular: the matrix is not square ({self._nrows} x {self._ncols})")
+        if b.ndim != 1 or b.shape[0] != self._nrows:
+            raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT,
+                        f"solve_triangular: b has shape {b.shape} but the matrix has {self._nrows} rows")
+        return self.device(device).trsv(b, lower, unit_diagonal)
 
     def _mul_mat(self, other, device: int = 0):
         """`&self * &other` (src/csr/ops/mul.rs:5-59 / src/csc/ops/mul.rs:5-60) on the device; the result is downloaded
