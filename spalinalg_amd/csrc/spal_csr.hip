@@ -216,7 +216,8 @@ static hipError_t launch_lanes(const spal_csr *a, const void *x, void *y, hipStr
 // shape, download, conversions work on its arrays -- but the plan of the PRODUCT kernels (tile heights, x windows, 16-bit
 // columns, ...: csr_plan_build, a dozen small kernels and host round trips, ~0.3 ms at config 5) is not part of
 // `CsrMatrix::from(&coo)` and is built when something first needs it: the first product, spal_csr_plan, set_option,
-// autotune, alloc_vectors or describe.  Under mu_cb, pending until finished, like the column-blocked copy below.
+// autotune, alloc_vectors or describe.  Under mu_cb, pending until finished, like the column-blocked copy below.  The build
+// never comes back here for the handle it is planning: what it launches, it launches through csr_launch_planned.
 int csr_ensure_plan(spal_csr *a, hipStream_t launch_stream, bool from_launch) {
     if (!__atomic_load_n(&a->plan_pending, __ATOMIC_ACQUIRE)) return SPAL_OK;
     std::lock_guard<std::mutex> lock(a->mu_cb);
@@ -234,10 +235,18 @@ int csr_ensure_plan(spal_csr *a, hipStream_t launch_stream, bool from_launch) {
 
 int csr_launch(spal_csr *a, const void *x_dev, void *y_dev, hipStream_t stream) {
     SPAL_TRY(csr_ensure_plan(a, stream, true));
+    return csr_launch_planned(a, x_dev, y_dev, stream);
+}
+
+// The product of a handle whose plan exists or is being built by the caller: never looks at plan_pending, never takes mu_cb
+// for the plan.  csr_plan_build times its candidate forms through this (csr_form1_faster) while csr_ensure_plan holds the
+// non-recursive mu_cb with plan_pending still set; csr_launch above would lock it a second time on the same thread.  The
+// parts of a row-block handle and the short part of a row split are planned before their parent can launch them.
+int csr_launch_planned(spal_csr *a, const void *x_dev, void *y_dev, hipStream_t stream) {
     auto typed = [&](auto fn) { return a->elem_size == 8 ? fn(double()) : fn(float()); };   // fn(T()), T = the handle's element type
     if (!a->parts.empty()) {   // row blocks: each writes its own rows of y
         for (size_t b = 0; b < a->parts.size(); ++b)
-            SPAL_TRY(csr_launch(a->parts[b], x_dev, (char *)y_dev + a->part_row0[b] * (uint64_t)a->elem_size, stream));
+            SPAL_TRY(csr_launch_planned(a->parts[b], x_dev, (char *)y_dev + a->part_row0[b] * (uint64_t)a->elem_size, stream));
         return SPAL_OK;
     }
     if (a->bw_on) {   // skewed rows, columns near the rows: the block-window kernel (spal_csr_blockwin.hip)
@@ -245,7 +254,7 @@ int csr_launch(spal_csr *a, const void *x_dev, void *y_dev, hipStream_t stream) 
         return SPAL_OK;
     }
     if (a->split_short) {   // row split: the short rows' handle writes every row of y, the long rows are then overwritten
-        SPAL_TRY(csr_launch(a->split_short, x_dev, y_dev, stream));
+        SPAL_TRY(csr_launch_planned(a->split_short, x_dev, y_dev, stream));
         const uint32_t grid = a->split_nheavy + (a->split_nlong - a->split_nheavy + kStreamWaves - 1) / kStreamWaves;
         SPAL_HIP_TRY(typed([&](auto t) {
             using T = decltype(t);

@@ -1,6 +1,6 @@
 // spal_csr_split.hip -- skewed row lengths: the ROW SPLIT (A = A_short + A_long) and, where both are built, its race
 // against the block-window kernel (spal_csr_blockwin.hip).  Called by csr_plan_build; products are launched through
-// csr_launch (spal_csr.hip) only.
+// csr_launch_planned (spal_csr.hip) only: the plan that csr_launch would ask for is the one being built here.
 #include "csr_kernels.hpp"
 #include "spal_internal.hpp"
 
@@ -27,7 +27,8 @@ __global__ __launch_bounds__(256) void csr_long_rows_scan(const uint32_t *__rest
 // Setup time: two forms of h's product, switched by set_form(0 / 1), each timed on scratch vectors (x zeroed: the time of a
 // product does not depend on the values) over 2 launches untimed and 5 timed.  us[] = microseconds per product of the two
 // forms (0 where the measurement did not get that far); true when form 1 measured strictly faster.  Any failure says
-// false: the second form is an optional one at both callers.
+// false: the second form is an optional one at both callers.  Both callers run under csr_plan_build, for a device-assembled
+// handle inside csr_ensure_plan's lock: the launches are csr_launch_planned, which does not ask for the plan again.
 template <typename F>
 static bool csr_form1_faster(spal_csr *h, F &&set_form, float us[2]) {
     const size_t es = (size_t)h->elem_size;
@@ -39,7 +40,7 @@ static bool csr_form1_faster(spal_csr *h, F &&set_form, float us[2]) {
               hipMemsetAsync(sx.p, 0, h->ncols * es, h->stream) == hipSuccess;
     for (int on = 0; on < 2 && ok; ++on) {
         set_form(on);
-        ok = timer.run(h->stream, 2, 5, [&] { return csr_launch(h, sx.p, sy.p, h->stream); }, &ms[on], "csr plan") == SPAL_OK;
+        ok = timer.run(h->stream, 2, 5, [&] { return csr_launch_planned(h, sx.p, sy.p, h->stream); }, &ms[on], "csr plan") == SPAL_OK;
     }
     us[0] = ms[0] * 200.f; us[1] = ms[1] * 200.f;   // (us per product: 5 launches)
     (void)hipGetLastError();

@@ -449,7 +449,8 @@ constexpr uint32_t kWinBase = 256;     // rows per entry of spal_csr::win_base, 
 int csr_try_row_split(spal_csr *a, bool *did);
 int csr_blockwin_or_split(spal_csr *a);
 // implemented in spal_csr.hip
-int csr_launch(spal_csr *a, const void *x_dev, void *y_dev, hipStream_t stream);
+int csr_launch(spal_csr *a, const void *x_dev, void *y_dev, hipStream_t stream);          // ensures the plan, then:
+int csr_launch_planned(spal_csr *a, const void *x_dev, void *y_dev, hipStream_t stream);  // (the plan exists or the caller is building it)
 int csr_ensure_plan(spal_csr *a, hipStream_t launch_stream, bool from_launch);
 void csr_free(spal_csr *a);            // the handle and everything it owns (NULL is fine)
 // implemented in spal_spmm.hip: Y = A * X enqueued on `stream` (tile 0 = automatic); reads a's plain arrays only, no plan

@@ -521,7 +521,9 @@ int csr_binary(const char *fn, bool sub, spal_csr_t a, spal_csr_t b, void *strea
     Sum r;
     SPAL_TRY(spadd(fn, a->elem_size, sub, A, B, a->spadd_tile, (hipStream_t)stream, r));
     const auto tp = std::chrono::steady_clock::now();
-    // eager plan, as spal_csr_mul's result (a lazily planned handle can reach csr_blockwin_or_split re-entrantly)
+    // eager plan, as spal_csr_mul's result: a choice, no longer a workaround (a lazily planned handle used to reach
+    // csr_blockwin_or_split re-entrantly; the planner's own launches are csr_launch_planned now).  describe()'s
+    // plan_ms reports the plan's cost, and the first product of the sum pays nothing.
     const int st = csr_adopt_device(a->device, a->elem_size, a->nrows, a->ncols, r.nnz, r.cap, r.ptr, r.ind, r.val, out,
                                     true, false);
     if (st != SPAL_OK) {
@@ -603,6 +605,7 @@ int spal_csr_neg(spal_csr_t a, void *stream, spal_csr_t *out) {
     Sum r;
     SPAL_TRY(spneg(a->elem_size, Operand{a->nrows, a->nnz, a->d_rowptr, a->d_colind, a->d_values}, (hipStream_t)stream, r));
     const auto tp = std::chrono::steady_clock::now();
+    // eager plan by choice, as the sum's above
     const int st = csr_adopt_device(a->device, a->elem_size, a->nrows, a->ncols, r.nnz, r.cap, r.ptr, r.ind, r.val, out,
                                     true, false);
     if (st != SPAL_OK) {

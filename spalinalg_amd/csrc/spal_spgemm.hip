@@ -550,7 +550,10 @@ int spal_csr_mul(spal_csr_t a, spal_csr_t b, void *stream, spal_csr_t *out) {
     Product r;
     SPAL_TRY(spgemm(a->device, a->elem_size, A, B, a->spgemm_route, a->spgemm_lds_cap, (hipStream_t)stream, r));
     const auto tp = std::chrono::steady_clock::now();
-    // eager plan, like a handle built from host arrays (a lazily planned handle can reach csr_blockwin_or_split re-entrantly)
+    // eager plan, like a handle built from host arrays.  This began as a workaround: a lazily planned handle reached
+    // csr_blockwin_or_split re-entrantly (csr_form1_faster -> csr_launch -> csr_ensure_plan under the lock it held).  That
+    // is fixed -- the planner launches through csr_launch_planned -- and eager planning stays as a choice: the plan's
+    // cost shows as plan_ms, and the first product of the result pays nothing.
     int st = csr_adopt_device(a->device, a->elem_size, a->nrows, b->ncols, r.nnz, r.cap, r.ptr, r.ind, r.val, out,
                               true, false);
     if (st != SPAL_OK) {

@@ -662,6 +662,30 @@ def test_coo_assembly_randomised(oracle, seed):
     assert_spmv_close(csr * x, oracle.csr_spmv(rp, ci, va, x), bound, 1e-10 if dtype == np.float64 else 1e-4)
 
 
+@pytest.mark.parametrize("seed", range(6))
+def test_coo_assembly_randomised_skewed(oracle, seed):
+    """test_coo_assembly_randomised's seeds never produce a matrix that meets the planner's automatic row-split test, so
+    none of its products runs the plan an assembled, skewed matrix gets (a timed race of the row split against the
+    block-window kernel, built lazily by that first product).  These six do (tests/lazy_cases.py, checked on the CPU by
+    tests/test_lazy_cases_host.py): power-law rows, height, duplicate rate and insertion order at random.  Arrays bit-exact,
+    then y = A*x: 1e-10 / 1e-4, rows of at most 32 entries in the reference's order."""
+    from tests import lazy_cases as zoo
+    nr, r, c, v, _ = zoo.random_skewed_coo(seed)
+    dtype = v.dtype
+    csr = assemble_and_compare(oracle, nr, nr, r, c, v)
+    rp, ci, va = csr.rowptr(), csr.colind(), csr.values()
+    assert zoo.auto_split_met(nr, rp)
+    x = np.random.default_rng(seed).uniform(-1, 1, nr).astype(dtype)
+    y_ref = oracle.csr_spmv(rp, ci, va, x)
+    bound = oracle.csr_abs_bound(rp, ci, va.astype(np.float64), x.astype(np.float64))
+    y = csr * x
+    print("plan:", csr.device().describe()["kernel"])
+    assert_spmv_close(y, y_ref, bound, 1e-10 if dtype == np.float64 else 1e-4)
+    short = np.diff(rp.astype(np.int64)) <= 32
+    bits = np.uint64 if dtype == np.float64 else np.uint32
+    assert np.array_equal(y[short].view(bits), y_ref[short].view(bits))
+
+
 def test_coo_wide_columns_take_the_unpacked_forms(oracle):
     """2^28 columns: column | row-in-group does not fit one word and column << 5 leaves no room for the place in the row, so
     the second pass writes key + column and the group kernel runs its loop form (rounds 1-3) -- offsets still from the two
