@@ -165,7 +165,7 @@ CooKnobs coo_read_knobs();
 // The assembly on (major, minor): for CSR major = rows, for CSC major = columns
 // (`From<&CooMatrix> for CscMatrix`, src/csc/conv/coo.rs:4-115, is the same code
 // with the two exchanged).  Produces the compressed arrays; the caller wraps
-// them in a handle.  Invariant: cap >= nnz + 256, the stream kernels' over-read margin (ind and val hold cap entries,
+// them in a handle.  Invariant: cap >= nnz + kStreamPad, the stream kernels' over-read margin (ind and val hold cap entries,
 // zeros behind the nnz-th), for the empty matrix too.
 struct Assembled {
     uint32_t *ptr = nullptr, *ind = nullptr;

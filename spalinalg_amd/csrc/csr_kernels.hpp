@@ -54,6 +54,12 @@ __device__ __forceinline__ T load_stream(const T *p) {
     return __builtin_nontemporal_load(p);
 }
 
+// relaxed, workgroup scope: ds_add_f64 / ds_add_f32, no return value (the CSC scatter kernels' y windows)
+template <typename T>
+__device__ __forceinline__ void lds_add(T *p, T v) {
+    __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+
 // Pins a loaded value so the compiler cannot sink its load into the (rarely
 // false) branch that consumes it; costs no instruction.
 __device__ __forceinline__ void keep_unconditional(double &v) { asm volatile("" : "+v"(v)); }
@@ -459,7 +465,6 @@ template <bool SKEW>
 constexpr int stream_strip() { return SKEW ? kStreamTileNnz + kStreamTileNnz / 16 : kStreamTileNnz; }   // entries of LDS per wave
 template <typename T, bool SKEW>
 __device__ __forceinline__ uint32_t strip_pos(uint32_t e) { return SKEW ? e + (e >> (sizeof(T) == 8 ? 4 : 5)) : e; }
-constexpr int kStreamPad = 256;  // device arrays are over-allocated by this many entries
 
 
 // Ablation builds only (-DSPAL_DIAG, tools/build_variant.sh; never in the shipped library): bits of the kernels'

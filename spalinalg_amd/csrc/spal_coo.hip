@@ -150,8 +150,7 @@ int spal_coo_assemble_csc(spal_coo_t c, void *stream, spal_csc_t *out) {
     SPAL_TRY(coo_assemble(c, true, (hipStream_t)stream, coo_read_knobs(), r));
     (void)dev_free(r.d_gwin);   // (the groups' ROW spans: the CSC planner has no use for them)
     r.d_gwin = nullptr;
-    // (csc handles expect the over-read margin too: Assembled's invariant)
-    int st = csc_adopt_device(c->device, c->elem_size, c->nrows, c->ncols, r.nnz, r.ptr, r.ind, r.val, out);
+    int st = csc_adopt_device(c->device, c->elem_size, c->nrows, c->ncols, r.nnz, r.cap, r.ptr, r.ind, r.val, out);
     if (st != SPAL_OK) { (void)dev_free(r.ptr); (void)dev_free(r.ind); (void)dev_free(r.val); }
     return st;
 }

@@ -1,6 +1,6 @@
 // spal_csc_rowtiles.hip -- CSC y = A*x by LDS-privatised atomic scatter over ROW TILES (config 4's path, round 3).
 //
-// The column-tiled scatter kernel (spal_csc.hip) gives a workgroup 4096 columns; the rows those touch overlap the
+// The column-tiled scatter kernel (spal_csc_scatter.hip) gives a workgroup 4096 columns; the rows those touch overlap the
 // neighbours' (a band as wide as the tile: every column adds to rows shared with BOTH neighbours), so the windows meet in
 // y through a hand-off -- own rows stored and acknowledged, a flag, the neighbour's poll, its read-add-write -- which costs
 // 5.6 of the launch's 36 us after the last entry and cannot start earlier (profiles/r03/csc_handoff.txt).  Here the
@@ -117,11 +117,6 @@ __global__ __launch_bounds__(256) void csc_rt_fill(const uint32_t *__restrict__ 
     if (threadIdx.x == 0 && base != ptr[blockIdx.x + 1]) atomicOr(bad, 1u);
 }
 
-template <typename T>
-__device__ __forceinline__ void rt_lds_add(T *p, T v) {
-    __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);   // ds_add_f64 / ds_add_f32, no return value
-}
-
 // desc[t] = {first row, rows, first column of the x window, columns of it}; ptr[t] = the tile's first entry.
 // LDS (dynamic): x window T[xcap] | y rows T[RT].
 template <typename T>
@@ -172,8 +167,8 @@ __global__ __launch_bounds__(kRtThreads, 1) void csc_spmv_rowtiles(const T *__re
 #pragma unroll
             for (uint32_t u = 0; u < U; ++u) {
                 const uint32_t e = batch0 + threadIdx.x * 2 + u * (kRtThreads * 2);
-                if (e >= p0 && e < p1) rt_lds_add(&yw[m[u].x & 0xffffu], v[u].x * xt[m[u].x >> 16]);
-                if (e + 1 >= p0 && e + 1 < p1) rt_lds_add(&yw[m[u].y & 0xffffu], v[u].y * xt[m[u].y >> 16]);
+                if (e >= p0 && e < p1) lds_add(&yw[m[u].x & 0xffffu], v[u].x * xt[m[u].x >> 16]);
+                if (e + 1 >= p0 && e + 1 < p1) lds_add(&yw[m[u].y & 0xffffu], v[u].y * xt[m[u].y >> 16]);
             }
             if (!more) break;
             batch0 = next0;
@@ -291,12 +286,10 @@ template <typename T>
 static hipError_t launch_rowtiles_t(const spal_csc *a, const void *x, void *y, hipStream_t st) {
     const size_t lds = ((size_t)a->rt_xcap + a->rt_rows) * sizeof(T);
     auto kern = csc_spmv_rowtiles<T>;
-    static std::atomic<uint64_t> configured{0};
-    const uint64_t bit = 1ull << (a->device & 63);
-    if (lds > 48 * 1024 && !(configured.load(std::memory_order_relaxed) & bit)) {
-        hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    static std::atomic<uint64_t> opted_in{0};
+    if (lds > 48 * 1024) {
+        const hipError_t e = lds_opt_in((const void *)kern, a->device, opted_in);
         if (e != hipSuccess) return e;
-        configured.fetch_or(bit, std::memory_order_relaxed);
     }
     const uint32_t per_xcd = (a->rt_ntiles + 7) / 8;
     hipLaunchKernelGGL(kern, dim3(per_xcd * 8), dim3(kRtThreads), lds, st, (const T *)a->d_rt_val, a->d_rt_meta, a->d_rt_ptr,

@@ -63,6 +63,20 @@ struct DeviceGuard {
 // Stored entries a handle accepts: entry offsets are 32-bit on the device and the kernels compute
 // `offset + a batch` (at most a few thousand entries past the end, clamped afterwards) in 32 bits.
 constexpr uint64_t kMaxEntries = 0xffffffffull - 65536ull;
+// THE padding contract: the entry arrays of every handle (indices, values, packed copies) are allocated with this many
+// spare entries behind the last one -- the streaming kernels read whole steps and clamp afterwards.  Whoever builds
+// arrays for csr_adopt_device / csc_adopt_device allocates nnz + kStreamPad and passes that capacity on.
+constexpr int kStreamPad = 256;
+
+// Kernels that use more than 48 KiB of dynamic LDS opt in once per device: `done` is the caller's word for ONE kernel
+// (a bit per device); `device` is the current one.
+inline hipError_t lds_opt_in(const void *kernel, int device, std::atomic<uint64_t> &done) {
+    const uint64_t bit = 1ull << (device & 63);
+    if (done.load(std::memory_order_relaxed) & bit) return hipSuccess;
+    const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (e == hipSuccess) done.fetch_or(bit, std::memory_order_relaxed);
+    return e;
+}
 
 // ---- placement blocks: blocks of 1 GiB found by ONE walk per process and device, kept, and shared by every
 // handle's vectors and 16-bit columns as pieces (first fit, 4 KB granules).  Two are kept when the walk met two classes of
@@ -241,8 +255,9 @@ int trsv_option(spal_csr *a, const char *key, int64_t value, int *status);
 int trsv_levels_u32(uint64_t n, const uint32_t *rowptr, const uint32_t *colind, int uplo, uint32_t *level_of,
                     uint64_t *nlevels, uint64_t *first_missing_diag, uint32_t *dpos);
 int trsv_missing_diag(const char *fn, uint64_t row);   // the error of a non-unit solve on such a matrix
-// implemented in spal_csc.hip: handle around device arrays it takes ownership of
-int csc_adopt_device(int device, int elem_size, uint64_t nrows, uint64_t ncols, uint64_t nnz,
+// implemented in spal_csc.hip: handle around device arrays it takes ownership of (on failure they stay with the caller);
+// cap_entries = allocated entries of d_rowind / d_values, refused when below nnz + kStreamPad
+int csc_adopt_device(int device, int elem_size, uint64_t nrows, uint64_t ncols, uint64_t nnz, uint64_t cap_entries,
                      uint32_t *d_colptr, uint32_t *d_rowind, void *d_values, spal_csc **out);
 
 // Triangular solve (spal_trsv.hip): the plan of one triangle of a handle.
@@ -403,7 +418,9 @@ struct spal_csc {
     double lds_col_fraction = 0.0;
     int use_lds = 1;
     int kernel = 2;                // 1 = atomic scatter (LDS-privatised / global), 2 = transposed (CSR kernels; default)
-    spal_csr *as_csr = nullptr;    // kernel 2: the same matrix as CSR, built on the device on first use
+    spal_csr *as_csr = nullptr;    // the CSR twin: the same matrix as CSR.  INVARIANT: every live spal_csc owns one, built on the
+                                   // device by its constructor (csc_finish) and kept until csc_free -- kernel 2, SpMM and the
+                                   // triangular solve read it without asking
     int lanes_per_col = 0;
     std::mutex mu;
     void *d_x = nullptr, *d_y = nullptr;
@@ -414,7 +431,6 @@ struct spal_csc {
     uint32_t spadd_tile = 0;       // as spal_csr's
     std::string spadd_info;
     int spmm_tile = 0;             // as spal_csr's; SpMM always runs on as_csr
-    std::mutex mu_twin;            // ... which an SpMM on a scatter-route handle (kernel 1) is the first to build
 };
 
 struct spal_coo {
@@ -462,14 +478,27 @@ int spmm_describe_append(char *buf, size_t buf_len, const spal_csr *a);
 // adds to its describe() line once a triangle was analysed
 void trsv_free(spal_csr *a);
 int trsv_describe_append(char *buf, size_t buf_len, spal_csr *a);
-// implemented in spal_csc.hip: the handle's CSR twin, built on the device by whoever asks first
-int csc_csr_twin(spal_csc *a, spal_csr **out);
 // implemented in spal_csr_slide.hip: the sliding-window kernel for a plan with plan.slide set
 hipError_t launch_slide(const spal_csr *a, const void *x, void *y, hipStream_t st);
 // ... its plan (for csr_plan_build): decides whether it can run the chosen stream plan and builds its step descriptors
 int slide_plan(spal_csr *a, uint32_t rpt, const std::vector<uint4> &desc, const std::vector<uint32_t> &skip, uint32_t super_pages);
 // ... and the column-panel kernel over a->d_ptiles
 hipError_t launch_panel(const spal_csr *a, const void *x, void *y, hipStream_t st);
+// The CSC scatter route over column tiles.  Implemented in spal_csc_plan.hip: windows, modes, hand-off eligibility, then
+// csc_rowtiles_plan
+int csc_plan_build(spal_csc *a);
+constexpr uint32_t kCscModeGlobal = 0, kCscModeLds = 1;   // desc[b].z of a super-tile: one global atomic per entry / LDS window
+constexpr uint32_t kCscChunk = 1024;                      // rows per chunk of the two-phase flush's cover lists
+// ... and in spal_csc_scatter.hip: the kernel's launcher (hipErrorLaunchTimeOut: an earlier product gave up in the
+// hand-off, nothing was launched), and what the plan asks about the kernel
+hipError_t launch_csc_scatter(spal_csc *a, const void *x, void *y, hipStream_t st);
+uint32_t csc_window_budget(const spal_csc *a, int cols);   // elements of the largest LDS y window beside `cols` columns of x
+size_t csc_scatter_lds_bytes(const spal_csc *a);           // dynamic LDS of a launch under the current plan
+int csc_scatter_per_cu(const spal_csc *a);                 // workgroups a CU holds at that size (0: the runtime cannot say)
+// the hand-off's give-up word: consumed under a->mu_launch (true: a product gave up since the last look; the handle
+// leaves the hand-off and counts it), and the invalid products so far, consumed or not
+bool csc_gave_up_consume(spal_csc *a);
+int csc_invalid_products(const spal_csc *a);
 // implemented in spal_csc_rowtiles.hip: CSC scatter over row tiles
 int csc_rowtiles_plan(spal_csc *a);
 void csc_rowtiles_free(spal_csc *a);

@@ -35,7 +35,6 @@ namespace {
 constexpr int kThreads = 256;              // threads of a tile
 constexpr uint32_t kTileMax = 2048;        // the default tile: 8 merged elements per thread
 constexpr uint32_t kTileMin = 16;
-constexpr uint64_t kOutPad = 256;          // spare entries behind C's arrays (the SpMV kernels' over-read margin)
 
 // the largest r in [lo, hi] with s_r = ap[r] + bp[r] <= d (s_lo <= d)
 __device__ __forceinline__ uint32_t row_of(const uint32_t *__restrict__ ap, const uint32_t *__restrict__ bp, uint32_t lo,
@@ -400,12 +399,12 @@ int spadd_t(const char *fn, const Operand &A, const Operand &B, uint32_t tile, h
     if (nnz > kMaxEntries)
         return fail(SPAL_ERR_UNSUPPORTED, "%s: the result has %llu entries, more than 32-bit device offsets address", fn, nnz);
     DevBuf cp, ci, cv;
-    const uint64_t cap = nnz + kOutPad;
+    const uint64_t cap = nnz + kStreamPad;
     SPAL_HIP_TRY(cp.alloc((m + 1) * 4));
     SPAL_HIP_TRY(ci.alloc(cap * 4));
     SPAL_HIP_TRY(cv.alloc(cap * sizeof(T)));
-    SPAL_HIP_TRY(hipMemsetAsync((char *)ci.p + nnz * 4, 0, kOutPad * 4, st));
-    SPAL_HIP_TRY(hipMemsetAsync((char *)cv.p + nnz * sizeof(T), 0, kOutPad * sizeof(T), st));
+    SPAL_HIP_TRY(hipMemsetAsync((char *)ci.p + nnz * 4, 0, kStreamPad * 4, st));
+    SPAL_HIP_TRY(hipMemsetAsync((char *)cv.p + nnz * sizeof(T), 0, kStreamPad * sizeof(T), st));
     SPAL_HIP_TRY(hipEventRecord(ev.e[2], st));
     hipLaunchKernelGGL(spadd_rowptr, dim3(grid_of(m + 1, 256)), dim3(256), 0, st, A.ptr, B.ptr, rscan.as<uint32_t>(),
                        m + 1, cp.as<uint32_t>());
@@ -436,7 +435,7 @@ int spadd(const char *fn, int elem_size, bool sub, const Operand &A, const Opera
 
 // -A: the index arrays copied, the values negated
 int spneg(int elem_size, const Operand &A, hipStream_t st, Sum &out) {
-    const uint64_t m = A.nmajor, nnz = A.nnz, cap = nnz + kOutPad;
+    const uint64_t m = A.nmajor, nnz = A.nnz, cap = nnz + kStreamPad;
     Events ev;
     SPAL_HIP_TRY(ev.create());
     DevBuf cp, ci, cv;
@@ -446,8 +445,8 @@ int spneg(int elem_size, const Operand &A, hipStream_t st, Sum &out) {
     SPAL_HIP_TRY(hipEventRecord(ev.e[0], st));
     SPAL_HIP_TRY(hipMemcpyAsync(cp.p, A.ptr, (m + 1) * 4, hipMemcpyDeviceToDevice, st));
     if (nnz) SPAL_HIP_TRY(hipMemcpyAsync(ci.p, A.ind, nnz * 4, hipMemcpyDeviceToDevice, st));
-    SPAL_HIP_TRY(hipMemsetAsync((char *)ci.p + nnz * 4, 0, kOutPad * 4, st));
-    SPAL_HIP_TRY(hipMemsetAsync((char *)cv.p + nnz * elem_size, 0, kOutPad * elem_size, st));
+    SPAL_HIP_TRY(hipMemsetAsync((char *)ci.p + nnz * 4, 0, kStreamPad * 4, st));
+    SPAL_HIP_TRY(hipMemsetAsync((char *)cv.p + nnz * elem_size, 0, kStreamPad * elem_size, st));
     if (nnz) {
         const uint64_t threads = nnz / (16 / elem_size) + 16 / elem_size;
         if (elem_size == 8)
@@ -544,7 +543,7 @@ int csc_binary(const char *fn, bool sub, spal_csc_t a, spal_csc_t b, void *strea
     Sum r;
     SPAL_TRY(spadd(fn, a->elem_size, sub, A, B, a->spadd_tile, (hipStream_t)stream, r));
     const auto tp = std::chrono::steady_clock::now();
-    const int st = csc_adopt_device(a->device, a->elem_size, a->nrows, a->ncols, r.nnz, r.ptr, r.ind, r.val, out);
+    const int st = csc_adopt_device(a->device, a->elem_size, a->nrows, a->ncols, r.nnz, r.cap, r.ptr, r.ind, r.val, out);
     if (st != SPAL_OK) {
         free_sum(r);
         return st;
@@ -625,7 +624,7 @@ int spal_csc_neg(spal_csc_t a, void *stream, spal_csc_t *out) {
     Sum r;
     SPAL_TRY(spneg(a->elem_size, Operand{a->ncols, a->nnz, a->d_colptr, a->d_rowind, a->d_values}, (hipStream_t)stream, r));
     const auto tp = std::chrono::steady_clock::now();
-    const int st = csc_adopt_device(a->device, a->elem_size, a->nrows, a->ncols, r.nnz, r.ptr, r.ind, r.val, out);
+    const int st = csc_adopt_device(a->device, a->elem_size, a->nrows, a->ncols, r.nnz, r.cap, r.ptr, r.ind, r.val, out);
     if (st != SPAL_OK) {
         free_sum(r);
         return st;

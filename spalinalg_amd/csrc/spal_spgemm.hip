@@ -27,7 +27,6 @@ namespace spal {
 namespace {
 
 constexpr uint32_t kEmpty = 0xffffffffu;   // a free hash slot (columns are < 2^32 - 1)
-constexpr uint64_t kOutPad = 256;          // spare entries behind C's arrays (the SpMV kernels' over-read margin)
 constexpr int kTiers = 7;                  // 0 empty, 1 g16, 2 g32, 3 wave, 4 block (4096 slots), 5 block (8192 slots), 6 large
 constexpr uint32_t kDefaultCap = 2048;     // route 0: rows above it go to the large tier
 constexpr uint32_t kMaxCap = 4096;         // the largest table the LDS holds (f64: 144 KB)
@@ -440,12 +439,12 @@ int spgemm_t(int device, const Operand &A, const Operand &B, int route, uint32_t
         return fail(SPAL_ERR_UNSUPPORTED, "spal_csr_mul: the product has %llu entries, more than 32-bit device offsets address",
                     nnz);
     DevBuf crp, cci, cva;
-    const uint64_t cap_entries = nnz + kOutPad;
+    const uint64_t cap_entries = nnz + kStreamPad;
     SPAL_HIP_TRY(crp.alloc((m + 1) * 4));
     SPAL_HIP_TRY(cci.alloc(cap_entries * 4));
     SPAL_HIP_TRY(cva.alloc(cap_entries * sizeof(T)));
-    SPAL_HIP_TRY(hipMemsetAsync((char *)cci.p + nnz * 4, 0, kOutPad * 4, st));
-    SPAL_HIP_TRY(hipMemsetAsync((char *)cva.p + nnz * sizeof(T), 0, kOutPad * sizeof(T), st));
+    SPAL_HIP_TRY(hipMemsetAsync((char *)cci.p + nnz * 4, 0, kStreamPad * 4, st));
+    SPAL_HIP_TRY(hipMemsetAsync((char *)cva.p + nnz * sizeof(T), 0, kStreamPad * sizeof(T), st));
     hipLaunchKernelGGL(spgemm_rowptr32, dim3(grid_of(m + 1, 256)), dim3(256), 0, st, d_off, m + 1, crp.as<uint32_t>());
     launch_lds_tiers<T>(true, lst, start, h.tier, A, B, d_cnt, d_off, cci.as<uint32_t>(), cva.as<T>(), st);
     if (nL)
@@ -585,7 +584,7 @@ int spal_csc_mul(spal_csc_t a, spal_csc_t b, void *stream, spal_csc_t *out) {
     Product r;
     SPAL_TRY(spgemm(a->device, a->elem_size, L, R, a->spgemm_route, a->spgemm_lds_cap, (hipStream_t)stream, r));
     const auto tp = std::chrono::steady_clock::now();
-    int st = csc_adopt_device(a->device, a->elem_size, a->nrows, b->ncols, r.nnz, r.ptr, r.ind, r.val, out);
+    int st = csc_adopt_device(a->device, a->elem_size, a->nrows, b->ncols, r.nnz, r.cap, r.ptr, r.ind, r.val, out);
     if (st != SPAL_OK) {
         free_product(r);
         return st;

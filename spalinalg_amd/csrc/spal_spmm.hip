@@ -320,10 +320,8 @@ int csc_spmm_host(spal_csc *a, uint64_t k, const T *x, uint64_t ldx, uint64_t x_
     SPAL_TRY(check_rows("spal_csc_spmm", a->nrows, a->ncols, x_rows, y_rows));
     DeviceGuard guard(a->device);
     if (guard.status != SPAL_OK) return guard.status;
-    spal_csr *twin = nullptr;
-    SPAL_TRY(csc_csr_twin(a, &twin));
     std::lock_guard<std::mutex> lock(a->mu);
-    return spmm_host<T>(twin, a->spmm_tile, a->stream, k, x, ldx, y, ldy);
+    return spmm_host<T>(a->as_csr, a->spmm_tile, a->stream, k, x, ldx, y, ldy);
 }
 
 template <typename T>
@@ -331,9 +329,7 @@ int csc_spmm_dev(spal_csc *a, uint64_t k, const T *x, uint64_t ldx, T *y, uint64
     SPAL_TRY(check_common<T>("spal_csc_spmm_dev", a, a ? a->elem_size : 0, k, x, ldx, y, ldy));
     DeviceGuard guard(a->device);
     if (guard.status != SPAL_OK) return guard.status;
-    spal_csr *twin = nullptr;
-    SPAL_TRY(csc_csr_twin(a, &twin));
-    return spmm_launch(twin, a->spmm_tile, k, x, ldx, y, ldy, (hipStream_t)stream);
+    return spmm_launch(a->as_csr, a->spmm_tile, k, x, ldx, y, ldy, (hipStream_t)stream);
 }
 
 }  // namespace

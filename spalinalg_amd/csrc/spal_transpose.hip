@@ -24,13 +24,13 @@ template <typename T>
 static int transpose_t(uint64_t nmajor, uint64_t nminor, uint64_t nnz,
                        const uint32_t *d_ptr, const uint32_t *d_ind, const T *d_val, hipStream_t st,
                        uint32_t **out_ptr, uint32_t **out_ind, T **out_val, uint64_t *out_cap) {
-    const uint64_t cap = nnz + 256;  // the stream kernel's over-read margin
+    const uint64_t cap = nnz + kStreamPad;  // the stream kernel's over-read margin
     DevBuf optr, oind, oval, work, major;   // (work, major: scratch, freed on return -- behind the synchronise below)
     SPAL_HIP_TRY(optr.alloc((nminor + 1) * 4));
     SPAL_HIP_TRY(oind.alloc(cap * 4));
     SPAL_HIP_TRY(oval.alloc(cap * sizeof(T)));
-    SPAL_HIP_TRY(hipMemsetAsync((char *)oind.p + nnz * 4, 0, 256 * 4, st));
-    SPAL_HIP_TRY(hipMemsetAsync((char *)oval.p + nnz * sizeof(T), 0, 256 * sizeof(T), st));
+    SPAL_HIP_TRY(hipMemsetAsync((char *)oind.p + nnz * 4, 0, kStreamPad * 4, st));
+    SPAL_HIP_TRY(hipMemsetAsync((char *)oval.p + nnz * sizeof(T), 0, kStreamPad * sizeof(T), st));
     if (nnz == 0) {
         SPAL_HIP_TRY(hipMemsetAsync(optr.p, 0, (nminor + 1) * 4, st));
     } else {

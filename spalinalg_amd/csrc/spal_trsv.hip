@@ -291,9 +291,7 @@ int csc_trsv_host(spal_csc *a, int uplo, int unit_diag, const T *b, uint64_t b_l
     SPAL_TRY(check_flags(fn, uplo, unit_diag));
     DeviceGuard guard(a->device);
     if (guard.status != SPAL_OK) return guard.status;
-    spal_csr *twin = nullptr;
-    SPAL_TRY(csc_csr_twin(a, &twin));
-    return solve_host<T>(fn, twin, uplo, unit_diag, b, b_len, x, x_len);
+    return solve_host<T>(fn, a->as_csr, uplo, unit_diag, b, b_len, x, x_len);
 }
 
 template <typename T>
@@ -305,10 +303,8 @@ int csc_trsv_dev(spal_csc *a, int uplo, int unit_diag, const T *b, T *x, void *s
     if (!b || !x) return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: null vector", fn);
     DeviceGuard guard(a->device);
     if (guard.status != SPAL_OK) return guard.status;
-    spal_csr *twin = nullptr;
-    SPAL_TRY(csc_csr_twin(a, &twin));
-    std::lock_guard<std::mutex> lock(twin->mu);
-    return solve_locked<T>(fn, twin, uplo, unit_diag, b, x, (hipStream_t)stream);
+    std::lock_guard<std::mutex> lock(a->as_csr->mu);
+    return solve_locked<T>(fn, a->as_csr, uplo, unit_diag, b, x, (hipStream_t)stream);
 }
 
 }  // namespace
@@ -392,9 +388,7 @@ int spal_csc_trsv_analyse(spal_csc_t a, int uplo, int unit_diag, void *stream) {
     if (!a) return fail(SPAL_ERR_INVALID_ARGUMENT, "spal_csc_trsv_analyse: handle is NULL");
     DeviceGuard guard(a->device);
     if (guard.status != SPAL_OK) return guard.status;
-    spal_csr *twin = nullptr;
-    SPAL_TRY(csc_csr_twin(a, &twin));
-    return csr_trsv_analyse("spal_csc_trsv_analyse", twin, uplo, unit_diag, stream);
+    return csr_trsv_analyse("spal_csc_trsv_analyse", a->as_csr, uplo, unit_diag, stream);
 }
 int spal_csc_trsv_f64(spal_csc_t a, int uplo, int unit_diag, const double *b, uint64_t b_len, double *x, uint64_t x_len) {
     return csc_trsv_host<double>(a, uplo, unit_diag, b, b_len, x, x_len);

@@ -980,3 +980,59 @@ def test_csc_handle_converted_on_the_device_scatters_over_row_tiles(oracle):
     assert_spmv_close(dcsc.spmv(x), y_ref, oracle.csr_abs_bound(rp, ci, va, x), 1e-10)
     dcsc.set_option("row_tiles", 0)
     assert_spmv_close(dcsc.spmv(x), y_ref, oracle.csr_abs_bound(rp, ci, va, x), 1e-10)
+
+
+# Every key spal_csc_set_option accepts: (values at the ends of what it takes, the nearest values it refuses on each side
+# -- and, where the accepted set has holes, one inside a hole --, the full text of spal_last_error() for a refusal).
+_CSC_OPTIONS = {
+    "lanes_per_col": ((0, 2, 64), (-1, 1, 3, 65), "lanes_per_col must be one of 2,4,8,16,32,64"),
+    "kernel": ((0, 2), (-1, 3), "kernel must be 0, 1 or 2"),
+    "flush": ((0, 2), (-1, 3), "flush must be 0, 1 or 2"),
+    "cols_per_block": ((0, 1024, 4096), (-1, 512, 3072, 4097), "cols_per_block must be 0 (auto), 1024, 2048 or 4096"),
+    "ticket": ((-1, 1), (-2, 2), "ticket must be -1 (auto), 0 or 1"),
+    "row_tiles": ((-1, 1), (-2, 2), "row_tiles must be -1 (auto), 0 or 1"),
+    "row_tile_rows": ((0, 1024, 4096), (-1, 512, 3072, 4097), "row_tile_rows must be 0 (auto), 1024, 2048 or 4096"),
+    "lds": ((0, 1), (-1, 2), "lds must be 0 or 1"),
+    # the keys of the other operations on this handle (spal_spgemm.hip, spal_spadd.hip, spal_spmm.hip, spal_trsv.hip)
+    "spgemm_route": ((0, 2), (-1, 3), "spgemm_route must be 0 (auto), 1 (LDS tiers wherever they fit) or 2 (large-row tier)"),
+    "spgemm_lds_cap": ((0, 4096), (-1, 4097), "spgemm_lds_cap must be 0 (default) or in [1, 4096]"),
+    "spadd_tile": ((0, 16, 2048), (-1, 8, 24, 2049), "spadd_tile must be 0 (default, 2048) or a power of two in [16, 2048]"),
+    "spmm_tile": ((0, 1, 32), (-1, 3, 33), "spmm_tile must be 0 (automatic) or one of 1, 2, 4, 8, 16, 32"),
+    "trsv_chain_rows": ((0, 2 ** 40), (-1,), "trsv_chain_rows must be >= 0 (0: every level is a launch of its own)"),
+    "no_such_option": ((), (0,), "unknown option 'no_such_option'"),
+}
+
+
+def test_every_csc_option_at_its_boundaries(oracle):
+    """spal_csc_set_option, key by key, on a band of 24 000 columns (six super-tiles at the widest column tile, six row
+    tiles at the tallest, a partial last tile), once on the default route and once on the scatter route ("kernel" = 1 set
+    first): the lowest and the highest value a key takes are taken, the nearest values on each side -- and one inside
+    every hole -- are refused with SPAL_ERR_INVALID_ARGUMENT and the key's own message, and after EVERY call, taken or
+    refused, the product agrees with the oracle; after every taken call describe() parses and names the route that was
+    set.  (A fresh handle per key and route: no option is read in the light of another one set before it.)"""
+    from spalinalg_amd import _ffi
+    n = 24_000
+    cp, ri, cv, x, y_ref, bound = _band_csc(oracle, n)
+    seen = expected = 0
+    for key, (taken, refused, msg) in _CSC_OPTIONS.items():
+        for scatter in (False, True) if key != "kernel" else (False,):
+            expected += len(taken) + len(refused)
+            dev = sp.CscMatrix(n, n, cp, ri, cv).device()
+            if scatter:
+                dev.set_option("kernel", 1)
+            for value in taken + refused:
+                if value in taken:
+                    dev.set_option(key, value)
+                    route = "transposed_csr" if not scatter else \
+                        "atomic_scatter" if (key, value) == ("lds", 0) else "lds_privatised_scatter"
+                    assert dev.describe()["kernel"] == route, (key, value, scatter)
+                else:
+                    with pytest.raises(_ffi.Panic) as err:
+                        dev.set_option(key, value)
+                    assert err.value.status == _ffi.SPAL_ERR_INVALID_ARGUMENT, (key, value, scatter)
+                    assert str(err.value) == msg, (key, value, scatter)
+                    assert _ffi.lib().spal_last_error().decode() == msg, (key, value, scatter)
+                assert_spmv_close(dev.spmv(x), y_ref, bound, 1e-10)
+                seen += 1
+            dev.close()
+    assert seen == expected == 2 * sum(len(t) + len(r) for t, r, _ in _CSC_OPTIONS.values()) - 4
