@@ -358,6 +358,36 @@ int spal_csc_trsv_dev_f64(spal_csc_t a, int uplo, int unit_diag, const double *b
 int spal_csc_trsv_dev_f32(spal_csc_t a, int uplo, int unit_diag, const float *b_dev, float *x_dev,
                           void *stream);
 
+/* ---- ILU(0): the incomplete LU factorisation without fill, CSR and CSC ------------------
+ * Not in the reference; the contract is this sequential loop, which the device reproduces bit for bit in f32 and f64
+ * (NaN by position).  A is square and stored as the handle stores it, columns strictly ascending inside a row, and every
+ * row stores its (i, i) entry.  F starts as a copy of A's values; its structure is A's and never changes (no fill).
+ *   for i = 0 .. n-1:
+ *     for each stored (i, k) with k < i, in ascending k, at position p:
+ *       w = F[p] / F[diag(k)]                 -- IEEE division; row k is final
+ *       F[p] = w
+ *       for each stored (k, j) with j > k, in ascending j, value u = F[(k, j)]:
+ *         if (i, j) is stored, at position q:  F[q] = F[q] - (w * u)   -- product rounded, then the difference: no FMA
+ * The result is a new, independent handle of a's shape, structure and element type (type-generic, like spal_csr_neg)
+ * that holds L strictly below the diagonal, its unit diagonal implied, and U on and above the diagonal.  M^-1 r is
+ * therefore two solves on that one handle: spal_*_trsv(uplo = 0, unit_diag = 1) for L y = r, then
+ * spal_*_trsv(uplo = 1, unit_diag = 0) for U z = y.  A zero or non-finite pivot is not an error: the result is what the
+ * division gives, propagating.  `a` is only read.
+ * SPAL_ERR_INVALID_ARGUMENT: null arguments; A not square; a row without a stored diagonal (the message names the first
+ * such row).  SPAL_ERR_UNSUPPORTED: a handle held as row blocks.  Nothing leaks on failure and *out is not written.
+ * The schedule is the lower solve's (row i needs exactly the rows k < i it stores): the call builds a's lower solve plan
+ * if a has none (counted in a's "analyses"), walks its launch list -- "trsv_chain_rows" governs both -- and
+ * synchronises `stream`.  The result's product plan is lazy (nobody multiplies by L\U); it receives a copy of a's lower
+ * solve plan, so its first lower solve analyses nothing; its upper plan is built by its first upper solve.
+ * A row is factorised by one thread, or, when the updates it has to look for (the sum, over its k, of the entries of
+ * row k past the diagonal) number at least the option "ilu_wide_work" (spal_csr_set_option / spal_csc_set_option,
+ * >= 0; 0 = every row with an entry below the diagonal, a huge value = none), by one wave whose lanes spread over row
+ * k; the bits do not depend on it.  CSC handles factorise their CSR twin and return the factor as CSC.
+ * describe() on the result gains "ilu0": {levels, launches, chain_launches, rows_row_form, rows_wide_form, wide_work,
+ * chain_rows, lds_stage_entries, kernel_ms = device time of the kernels, call_ms}. */
+int spal_csr_ilu0(spal_csr_t a, void *stream, spal_csr_t *out);
+int spal_csc_ilu0(spal_csc_t a, void *stream, spal_csc_t *out);
+
 /* ---- CSR <-> CSC on the device ------------------------------------------------
  * Replace `impl From<&CscMatrix<T>> for CsrMatrix<T>` (src/csr/conv/csc.rs:4-52)
  * and `impl From<&CsrMatrix<T>> for CscMatrix<T>` (src/csc/conv/csr.rs:4-52),

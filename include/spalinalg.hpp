@@ -199,6 +199,16 @@ class CsrMatrix {
         return adopt(h);
     }
 
+    // The ILU(0) factor of this square matrix (spal_csr_ilu0, include/spal.h): the same structure, L strictly below the
+    // diagonal with its unit diagonal implied, U on and above it, bit for bit the sequential loop without fill.
+    // M^-1 r is f.solve_triangular(f.solve_triangular(r, true, true), false).  Panics when the matrix is not square or
+    // a row stores no diagonal entry.
+    CsrMatrix ilu0() const {
+        spal_csr_t h = nullptr;
+        detail::check(spal_csr_ilu0(device_handle(), nullptr, &h));
+        return adopt(h);
+    }
+
     // CsrMatrix::from(&coo): assembled on the device, bit-identical to the reference.
     static CsrMatrix from(const CooMatrix<T> &coo, int device = 0);
     // CsrMatrix::from(&csc)  (src/csr/conv/csc.rs:4-52): device stable sort by row.
@@ -319,6 +329,12 @@ class CscMatrix {
     CscMatrix operator-() const {
         spal_csc_t h = nullptr;
         detail::check(spal_csc_neg(device_handle(), nullptr, &h));
+        return adopt(h);
+    }
+    // The ILU(0) factor (spal_csc_ilu0): as CsrMatrix::ilu0, returned by columns.
+    CscMatrix ilu0() const {
+        spal_csc_t h = nullptr;
+        detail::check(spal_csc_ilu0(device_handle(), nullptr, &h));
         return adopt(h);
     }
     // CscMatrix::from(&csr)  (src/csc/conv/csr.rs:4-52) and CscMatrix::from(&coo)

@@ -199,6 +199,16 @@ impl<T: HipScalar> DeviceCsr<T> {
         unsafe { ffi::check(ffi::spal_csr_neg(self.h, stream, &mut out)); }
         DeviceCsr::from_raw(out)
     }
+
+    /// The ILU(0) factor of this square matrix (spal_csr_ilu0): the same structure, L strictly below the diagonal
+    /// (unit diagonal implied), U on and above it, bit for bit the sequential loop without fill; synchronises
+    /// `stream`.  `M^-1 r` is `f.trsv(&f.trsv(r, true, true), false, false)`.  The result already has its lower solve
+    /// plan.  Panics when the matrix is not square or a row stores no diagonal entry.
+    pub fn ilu0(&self, stream: *mut c_void) -> DeviceCsr<T> {
+        let mut out = std::ptr::null_mut();
+        unsafe { ffi::check(ffi::spal_csr_ilu0(self.h, stream, &mut out)); }
+        DeviceCsr::from_raw(out)
+    }
 }
 
 impl<T: HipScalar> DeviceCsc<T> {
@@ -324,6 +334,13 @@ impl<T: HipScalar> DeviceCsc<T> {
     pub fn neg_mat(&self, stream: *mut c_void) -> DeviceCsc<T> {
         let mut out = std::ptr::null_mut();
         unsafe { ffi::check(ffi::spal_csc_neg(self.h, stream, &mut out)); }
+        DeviceCsc { h: out, _t: PhantomData }
+    }
+
+    /// The ILU(0) factor (spal_csc_ilu0): as `DeviceCsr::ilu0`, factorised on the CSR twin and returned by columns.
+    pub fn ilu0(&self, stream: *mut c_void) -> DeviceCsc<T> {
+        let mut out = std::ptr::null_mut();
+        unsafe { ffi::check(ffi::spal_csc_ilu0(self.h, stream, &mut out)); }
         DeviceCsc { h: out, _t: PhantomData }
     }
 }

@@ -78,6 +78,8 @@ extern "C" {
     pub fn spal_csc_trsv_f32(a: *mut spal_csc, uplo: c_int, unit_diag: c_int, b: *const f32, b_len: u64, x: *mut f32, x_len: u64) -> c_int;
     pub fn spal_csc_trsv_dev_f64(a: *mut spal_csc, uplo: c_int, unit_diag: c_int, b_dev: *const f64, x_dev: *mut f64, stream: *mut c_void) -> c_int;
     pub fn spal_csc_trsv_dev_f32(a: *mut spal_csc, uplo: c_int, unit_diag: c_int, b_dev: *const f32, x_dev: *mut f32, stream: *mut c_void) -> c_int;
+    pub fn spal_csr_ilu0(a: *mut spal_csr, stream: *mut c_void, out: *mut *mut spal_csr) -> c_int;
+    pub fn spal_csc_ilu0(a: *mut spal_csc, stream: *mut c_void, out: *mut *mut spal_csc) -> c_int;
     pub fn spal_csc_to_csr(a: *mut spal_csc, out: *mut *mut spal_csr) -> c_int;
     pub fn spal_csr_to_csc(a: *mut spal_csr, out: *mut *mut spal_csc) -> c_int;
     pub fn spal_csr_mul(a: *mut spal_csr, b: *mut spal_csr, stream: *mut c_void, out: *mut *mut spal_csr) -> c_int;

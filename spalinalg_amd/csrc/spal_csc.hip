@@ -311,6 +311,7 @@ int spal_csc_set_option(spal_csc_t a, const char *key, int64_t value) {
         if (spadd_option(key, value, &a->spadd_tile, &st)) return st;   // ... and of A + B / A - B
         if (spmm_option(key, value, &a->spmm_tile, &st)) return st;     // ... and of Y = A * X
         if (trsv_option(a->as_csr, key, value, &st)) return st;         // ... and of the triangular solve, which runs on the CSR twin
+        if (ilu_option(a->as_csr, key, value, &st)) return st;          // ... and of ILU(0), which does too
     }
     DeviceGuard guard(a->device);
     if (guard.status != SPAL_OK) return guard.status;
@@ -403,7 +404,8 @@ int spal_csc_describe(spal_csc_t a, char *buf, size_t buf_len) {
     SPAL_TRY(spgemm_describe_append(buf, buf_len, a->spgemm_info));   // a product of spal_csc_mul: how it was built
     SPAL_TRY(spadd_describe_append(buf, buf_len, a->spadd_info));     // a result of spal_csc_add / _sub / _neg
     SPAL_TRY(spmm_describe_append(buf, buf_len, a->as_csr));          // an SpMM ran on it (on the CSR twin)
-    return trsv_describe_append(buf, buf_len, a->as_csr);             // ... or a triangular solve was analysed
+    SPAL_TRY(trsv_describe_append(buf, buf_len, a->as_csr));          // ... or a triangular solve was analysed
+    return ilu_describe_append(buf, buf_len, a->ilu_info);            // a factor of spal_csc_ilu0: how it was built
 }
 
 }  // extern "C"

@@ -662,6 +662,7 @@ int spal_csr_set_option(spal_csr_t a, const char *key, int64_t value) {
         if (spadd_option(key, value, &a->spadd_tile, &st)) return st;   // ... and of A + B / A - B
         if (spmm_option(key, value, &a->spmm_tile, &st)) return st;     // ... and of Y = A * X
         if (trsv_option(a, key, value, &st)) return st;                 // ... and of L x = b / U x = b
+        if (ilu_option(a, key, value, &st)) return st;                  // ... and of ILU(0)
     }
     if (!a->parts.empty()) {   // row blocks: every block takes the option (each plans for its own rows)
         for (spal_csr *part : a->parts) SPAL_TRY(spal_csr_set_option(part, key, value));
@@ -873,7 +874,8 @@ int spal_csr_describe(spal_csr_t a, char *buf, size_t buf_len) {
     SPAL_TRY(spgemm_describe_append(buf, buf_len, a->spgemm_info));   // a product of spal_csr_mul: how it was built
     SPAL_TRY(spadd_describe_append(buf, buf_len, a->spadd_info));     // a result of spal_csr_add / _sub / _neg
     SPAL_TRY(spmm_describe_append(buf, buf_len, a));                  // an SpMM ran on it
-    return trsv_describe_append(buf, buf_len, a);                     // a triangle of it was analysed for a solve
+    SPAL_TRY(trsv_describe_append(buf, buf_len, a));                  // a triangle of it was analysed for a solve
+    return ilu_describe_append(buf, buf_len, a->ilu_info);            // a factor of spal_csr_ilu0: how it was built
 }
 
 }  // extern "C"

@@ -273,6 +273,14 @@ struct TrsvPlan {
     double analysis_ms = 0.0;              // copy back + levels + ordering + upload, host clock
 };
 constexpr int64_t kTrsvChainRowsDefault = 256;
+// ... the plan of `uplo`, built now (under a->mu, which the caller holds; counted in trsv_analyses) if the handle has
+// none; refuses row-block handles, matrices that are not square and, unless unit_diag, a row without a diagonal
+int trsv_plan_get(const char *fn, spal_csr *a, int uplo, int unit_diag, hipStream_t st, TrsvPlan **out);
+// ILU(0) (spal_ilu.hip): the option "ilu_wide_work" of a CSR handle (as spgemm_option), and the "ilu0"
+// object a factor adds to its describe() line
+constexpr int64_t kIluWideWorkDefault = 4096;
+int ilu_option(spal_csr *a, const char *key, int64_t value, int *status);
+int ilu_describe_append(char *buf, size_t buf_len, const std::string &info);
 }  // namespace spal
 
 // The opaque handle types of spal.h.
@@ -364,6 +372,9 @@ struct spal_csr {
     int64_t trsv_chain_rows = spal::kTrsvChainRowsDefault;   // option "trsv_chain_rows": the widest level the chain kernel takes
     spal::TrsvPlan *trsv[2] = {nullptr, nullptr};            // [uplo], built by the first solve or by spal_csr_trsv_analyse
     int trsv_analyses = 0;         // plans built so far (describe)
+    // ILU(0) (spal_ilu.hip); the option guarded by mu
+    int64_t ilu_wide_work = spal::kIluWideWorkDefault;   // option "ilu_wide_work": rows with at least this much work take the wide form
+    std::string ilu_info;          // the "ilu0" object of spal_csr_describe (empty: not a factor)
 };
 
 struct spal_csc {
@@ -431,6 +442,7 @@ struct spal_csc {
     uint32_t spadd_tile = 0;       // as spal_csr's
     std::string spadd_info;
     int spmm_tile = 0;             // as spal_csr's; SpMM always runs on as_csr
+    std::string ilu_info;          // as spal_csr's; the factorisation runs on as_csr
 };
 
 struct spal_coo {

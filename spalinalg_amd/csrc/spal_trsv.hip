@@ -309,6 +309,10 @@ int csc_trsv_dev(spal_csc *a, int uplo, int unit_diag, const T *b, T *x, void *s
 
 }  // namespace
 
+int trsv_plan_get(const char *fn, spal_csr *a, int uplo, int unit_diag, hipStream_t st, TrsvPlan **out) {
+    return plan_get(fn, a, uplo, unit_diag, st, out);
+}
+
 int trsv_option(spal_csr *a, const char *key, int64_t value, int *status) {
     if (strcmp(key, "trsv_chain_rows")) return 0;
     if (value < 0) {

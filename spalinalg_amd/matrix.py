@@ -326,6 +326,20 @@ class DeviceCsr(_DeviceMatrix):
         check(_ffi.lib().spal_csr_neg(self._h, _stream_ptr(stream), C.byref(out)))
         return DeviceCsr(out, self.dtype, self.device)
 
+    def ilu0(self, stream=None) -> "DeviceCsr":
+        """The ILU(0) factor of this square matrix as a new handle of the same structure (spal_csr_ilu0):
+        L strictly below the diagonal, its unit diagonal implied, U on and above it; bit for bit the sequential loop.
+        Synchronises `stream`.  Applying the preconditioner is two solves on the result::
+
+            f = a.ilu0()
+            z = f.trsv(f.trsv(r, lower=True, unit_diagonal=True), lower=False)      # z = U^-1 L^-1 r
+
+        The result already has its lower solve plan (a copy of self's); options "ilu_wide_work" and
+        "trsv_chain_rows" are read from self."""
+        out = vp()
+        check(_ffi.lib().spal_csr_ilu0(self._h, _stream_ptr(stream), C.byref(out)))
+        return DeviceCsr(out, self.dtype, self.device)
+
 
 class DeviceCsc(_DeviceMatrix):
     _kind = "csc"
@@ -372,6 +386,13 @@ class DeviceCsc(_DeviceMatrix):
         """C = -self (spal_csc_neg: `impl Neg for &CscMatrix<T>`, src/csc/ops/neg.rs:5-17)."""
         out = vp()
         check(_ffi.lib().spal_csc_neg(self._h, _stream_ptr(stream), C.byref(out)))
+        return DeviceCsc(out, self.dtype, self.device)
+
+    def ilu0(self, stream=None) -> "DeviceCsc":
+        """The ILU(0) factor as a new CSC handle (spal_csc_ilu0: the CSR twin is factorised, the factor returned by
+        columns); see DeviceCsr.ilu0 for the contract and the two-solve application."""
+        out = vp()
+        check(_ffi.lib().spal_csc_ilu0(self._h, _stream_ptr(stream), C.byref(out)))
         return DeviceCsc(out, self.dtype, self.device)
 
 
@@ -693,6 +714,18 @@ class _Compressed:
     def __neg__(self):
         """`-&self` (src/csr/ops/neg.rs:5-17 / src/csc/ops/neg.rs:5-17) on the device."""
         return self._adopt_result(self.device().neg(), 0)
+
+    def ilu0(self, device: int = 0):
+        """The ILU(0) factor of this square matrix, a matrix of the same class and structure (spal_*_ilu0, DESIGN
+        3.12): L strictly below the diagonal with its unit diagonal implied, U on and above it, bit for bit the
+        sequential loop without fill.  Every row must store its diagonal.  The result is downloaded and keeps its
+        device handle, which already has its lower solve plan.  Applying the preconditioner is two solves::
+
+            f = a.ilu0()
+            y = f.solve_triangular(r, lower=True, unit_diagonal=True)      # L y = r
+            z = f.solve_triangular(y, lower=False)                         # U z = y
+        """
+        return self._adopt_result(self.device(device).ilu0(), device)
 
 
 class CsrMatrix(_Compressed):
