@@ -3,7 +3,7 @@
 // spal_transpose.hip (CSR <-> CSC) and spal_coo.hip (handle, C ABI).
 #pragma once
 
-#include "spal_internal.hpp"
+#include "spal_ops.hpp"
 
 namespace spal {
 
@@ -167,10 +167,7 @@ CooKnobs coo_read_knobs();
 // with the two exchanged).  Produces the compressed arrays; the caller wraps
 // them in a handle.  Invariant: cap >= nnz + kStreamPad, the stream kernels' over-read margin (ind and val hold cap entries,
 // zeros behind the nnz-th), for the empty matrix too.
-struct Assembled {
-    uint32_t *ptr = nullptr, *ind = nullptr;
-    void *val = nullptr;
-    uint64_t nnz = 0, cap = 0;
+struct Assembled : OpArrays {   // (ptr, ind, val, nnz, cap: owned here until a handle adopts them)
     // {first, one past last} minor index of every group of 2^gwin_bits majors of the result, still on the device, when
     // the local sort produced it on the way (saves the CSR planner its own pass over the matrix; ownership passes to
     // whoever takes the result)

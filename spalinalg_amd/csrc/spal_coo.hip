@@ -135,11 +135,8 @@ int spal_coo_assemble_csr(spal_coo_t c, void *stream, spal_csr_t *out) {
     const CooKnobs knobs = coo_read_knobs();
     Assembled r;
     SPAL_TRY(coo_assemble(c, false, (hipStream_t)stream, knobs, r));
-    int st = csr_adopt_device(c->device, c->elem_size, c->nrows, c->ncols, r.nnz, r.cap, r.ptr, r.ind,
-                              r.val, out, false, !knobs.eager_plan,
-                              r.d_gwin, r.gwin_n, r.gwin_bits);   // (takes the spans' block, also when it fails)
-    if (st != SPAL_OK) { (void)dev_free(r.ptr); (void)dev_free(r.ind); (void)dev_free(r.val); }
-    return st;
+    return r.adopt(c->device, c->elem_size, c->nrows, c->ncols, out, false, !knobs.eager_plan,
+                   r.d_gwin, r.gwin_n, r.gwin_bits);   // (takes the spans' block, also when it fails)
 }
 int spal_coo_assemble_csc(spal_coo_t c, void *stream, spal_csc_t *out) {
     if (!c || !out) return fail(SPAL_ERR_INVALID_ARGUMENT, "spal_coo_assemble_csc: null argument");
@@ -150,9 +147,7 @@ int spal_coo_assemble_csc(spal_coo_t c, void *stream, spal_csc_t *out) {
     SPAL_TRY(coo_assemble(c, true, (hipStream_t)stream, coo_read_knobs(), r));
     (void)dev_free(r.d_gwin);   // (the groups' ROW spans: the CSC planner has no use for them)
     r.d_gwin = nullptr;
-    int st = csc_adopt_device(c->device, c->elem_size, c->nrows, c->ncols, r.nnz, r.cap, r.ptr, r.ind, r.val, out);
-    if (st != SPAL_OK) { (void)dev_free(r.ptr); (void)dev_free(r.ind); (void)dev_free(r.val); }
-    return st;
+    return r.adopt(c->device, c->elem_size, c->nrows, c->ncols, out);
 }
 int spal_coo_to_csr_f64(int device, uint64_t nrows, uint64_t ncols, uint64_t len, const uint64_t *rows,
                         const uint64_t *cols, const double *vals, spal_csr_t *out) {

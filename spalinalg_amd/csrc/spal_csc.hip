@@ -6,7 +6,7 @@
 // on the device by the constructor -- and the CSR kernels; "kernel" 1 scatters with LDS-privatised atomics, over row
 // tiles where the plan built them (spal_csc_rowtiles.hip), else over column tiles (spal_csc_scatter.hip, planned by
 // spal_csc_plan.hip).
-#include "spal_internal.hpp"
+#include "spal_ops.hpp"
 
 namespace spal {
 
@@ -32,14 +32,10 @@ static int csc_launch(spal_csc *a, const void *x, void *y, hipStream_t st) {
 
 // CSC -> CSR on the device (stable sort of the entries by row) into a new CSR handle; nothing is left behind on failure
 static int csc_to_csr_arrays(spal_csc *a, spal_csr **out) {
-    uint32_t *rp = nullptr, *ci = nullptr;
-    void *va = nullptr;
-    uint64_t cap = 0;
+    OpArrays t;
     SPAL_TRY(transpose_device(a->device, a->elem_size, a->ncols, a->nrows, a->nnz, a->d_colptr,
-                              a->d_rowind, a->d_values, a->stream, &rp, &ci, &va, &cap));
-    int st = csr_adopt_device(a->device, a->elem_size, a->nrows, a->ncols, a->nnz, cap, rp, ci, va, out);
-    if (st != SPAL_OK) { (void)dev_free(rp); (void)dev_free(ci); (void)dev_free(va); }
-    return st;
+                              a->d_rowind, a->d_values, a->stream, t));
+    return t.adopt(a->device, a->elem_size, a->nrows, a->ncols, out);
 }
 
 // what both constructors end with: the scatter plan, then the CSR twin (setup work, not the first product's)
@@ -271,14 +267,10 @@ int spal_csr_to_csc(spal_csr_t a, spal_csc_t *out) {
     DeviceGuard guard(a->device);
     if (guard.status != SPAL_OK) return guard.status;
     std::lock_guard<std::mutex> lock(a->mu);
-    uint32_t *cp = nullptr, *ri = nullptr;
-    void *va = nullptr;
-    uint64_t cap = 0;
+    OpArrays t;
     SPAL_TRY(transpose_device(a->device, a->elem_size, a->nrows, a->ncols, a->nnz, a->d_rowptr,
-                              a->d_colind, a->d_values, a->stream, &cp, &ri, &va, &cap));
-    int st = csc_adopt_device(a->device, a->elem_size, a->nrows, a->ncols, a->nnz, cap, cp, ri, va, out);
-    if (st != SPAL_OK) { (void)dev_free(cp); (void)dev_free(ri); (void)dev_free(va); }
-    return st;
+                              a->d_colind, a->d_values, a->stream, t));
+    return t.adopt(a->device, a->elem_size, a->nrows, a->ncols, out);
 }
 
 int spal_csc_download_f64(spal_csc_t a, uint64_t *colptr, uint64_t *rowind, double *values) {
@@ -305,13 +297,9 @@ int spal_csc_autotune_f32(spal_csc_t a, const float *x_dev, float *y_dev, void *
 
 int spal_csc_set_option(spal_csc_t a, const char *key, int64_t value) {
     if (!a || !key) return fail(SPAL_ERR_INVALID_ARGUMENT, "spal_csc_set_option: null argument");
-    {   // options of the sparse x sparse product (this handle as its left operand)
+    {   // options of the sparse operations (this handle as their left operand): no plan involved
         int st = SPAL_OK;
-        if (spgemm_option(key, value, &a->spgemm_route, &a->spgemm_lds_cap, &st)) return st;
-        if (spadd_option(key, value, &a->spadd_tile, &st)) return st;   // ... and of A + B / A - B
-        if (spmm_option(key, value, &a->spmm_tile, &st)) return st;     // ... and of Y = A * X
-        if (trsv_option(a->as_csr, key, value, &st)) return st;         // ... and of the triangular solve, which runs on the CSR twin
-        if (ilu_option(a->as_csr, key, value, &st)) return st;          // ... and of ILU(0), which does too
+        if (ops_set_option(a->ops, a->as_csr, key, value, &st)) return st;
     }
     DeviceGuard guard(a->device);
     if (guard.status != SPAL_OK) return guard.status;
@@ -401,11 +389,7 @@ int spal_csc_describe(spal_csc_t a, char *buf, size_t buf_len) {
              csc_invalid_products(a),
              a->uniform_cols ? 1 : 0,
              (a->rowtiles && a->rowtiles_user != 0 && a->flush == 0) ? 1 : 0, a->rt_rows, a->rt_ntiles, a->rt_xcap, a->rowtiles_failed);
-    SPAL_TRY(spgemm_describe_append(buf, buf_len, a->spgemm_info));   // a product of spal_csc_mul: how it was built
-    SPAL_TRY(spadd_describe_append(buf, buf_len, a->spadd_info));     // a result of spal_csc_add / _sub / _neg
-    SPAL_TRY(spmm_describe_append(buf, buf_len, a->as_csr));          // an SpMM ran on it (on the CSR twin)
-    SPAL_TRY(trsv_describe_append(buf, buf_len, a->as_csr));          // ... or a triangular solve was analysed
-    return ilu_describe_append(buf, buf_len, a->ilu_info);            // a factor of spal_csc_ilu0: how it was built
+    return ops_describe_append(buf, buf_len, a->ops, a->as_csr);   // "spgemm", "spadd", "spmm", "trsv", "ilu0": those that apply
 }
 
 }  // extern "C"

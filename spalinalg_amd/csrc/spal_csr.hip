@@ -3,7 +3,7 @@
 // C ABI entry points documented in include/spal.h.
 #include "csr_kernels.hpp"
 #include "csr_slide.hpp"
-#include "spal_internal.hpp"
+#include "spal_ops.hpp"
 
 namespace spal {
 
@@ -656,13 +656,9 @@ static const PlanIntOption kPlanIntOptions[] = {
 
 int spal_csr_set_option(spal_csr_t a, const char *key, int64_t value) {
     if (!a || !key) return fail(SPAL_ERR_INVALID_ARGUMENT, "spal_csr_set_option: null argument");
-    {   // options of the sparse x sparse product (this handle as its left operand): no plan involved
+    {   // options of the sparse operations (this handle as their left operand): no plan involved
         int st = SPAL_OK;
-        if (spgemm_option(key, value, &a->spgemm_route, &a->spgemm_lds_cap, &st)) return st;
-        if (spadd_option(key, value, &a->spadd_tile, &st)) return st;   // ... and of A + B / A - B
-        if (spmm_option(key, value, &a->spmm_tile, &st)) return st;     // ... and of Y = A * X
-        if (trsv_option(a, key, value, &st)) return st;                 // ... and of L x = b / U x = b
-        if (ilu_option(a, key, value, &st)) return st;                  // ... and of ILU(0)
+        if (ops_set_option(a->ops, a, key, value, &st)) return st;
     }
     if (!a->parts.empty()) {   // row blocks: every block takes the option (each plans for its own rows)
         for (spal_csr *part : a->parts) SPAL_TRY(spal_csr_set_option(part, key, value));
@@ -871,11 +867,7 @@ static int csr_describe_plan(spal_csr_t a, char *buf, size_t buf_len) {
 int spal_csr_describe(spal_csr_t a, char *buf, size_t buf_len) {
     if (!a || !buf || !buf_len) return fail(SPAL_ERR_INVALID_ARGUMENT, "spal_csr_describe: null argument");
     SPAL_TRY(csr_describe_plan(a, buf, buf_len));
-    SPAL_TRY(spgemm_describe_append(buf, buf_len, a->spgemm_info));   // a product of spal_csr_mul: how it was built
-    SPAL_TRY(spadd_describe_append(buf, buf_len, a->spadd_info));     // a result of spal_csr_add / _sub / _neg
-    SPAL_TRY(spmm_describe_append(buf, buf_len, a));                  // an SpMM ran on it
-    SPAL_TRY(trsv_describe_append(buf, buf_len, a));                  // a triangle of it was analysed for a solve
-    return ilu_describe_append(buf, buf_len, a->ilu_info);            // a factor of spal_csr_ilu0: how it was built
+    return ops_describe_append(buf, buf_len, a->ops, a);   // "spgemm", "spadd", "spmm", "trsv", "ilu0": those that apply
 }
 
 }  // extern "C"

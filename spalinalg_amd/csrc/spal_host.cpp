@@ -1,6 +1,6 @@
 // spal_host.cpp -- host-only parts of libspal_hip.so: error state, the
-// constructor invariants of the reference, the row partitioner and the level analysis of the triangular solve.
-// Nothing here touches a device.
+// constructor invariants of the reference, the row partitioner, the level analysis of the triangular solve and the
+// epilogue of describe()'s per-operation objects.  Nothing here touches a device.
 #include "spal_internal.hpp"
 
 namespace spal {
@@ -92,6 +92,17 @@ int compressed_validate(uint64_t nrows, uint64_t ncols, bool major_is_rows,
     });
     for (int f : bad9) if (f) return 9;
     return 0;
+}
+
+// The epilogue of every object a sparse operation adds to a describe() line (spal_ops.hpp): `, "<key>": <body>` goes
+// where the line's closing brace was, and the brace behind it.
+int describe_append(char *buf, size_t buf_len, const char *key, const std::string &body) {
+    if (body.empty()) return SPAL_OK;
+    const size_t len = strnlen(buf, buf_len), add = strlen(key) + body.size() + 6;   // `, "` and `": ` around the key
+    if (len == 0 || buf[len - 1] != '}' || len + add + 1 > buf_len)
+        return fail(SPAL_ERR_INVALID_ARGUMENT, "describe: buffer of %zu bytes too small", buf_len);
+    snprintf(buf + len - 1, buf_len - (len - 1), ", \"%s\": %s}", key, body.c_str());
+    return SPAL_OK;
 }
 
 const char *invariant_text(int reason, bool csr) {

@@ -22,9 +22,7 @@
 // that are uniform across the wave, nothing that waits for another wave inside a level.
 // The factor's values are read and written by one kernel (other rows' final values, this row's running ones): the
 // pointer is a plain T *, never const __restrict__.
-#include "spal_internal.hpp"
-
-#include <chrono>
+#include "spal_ops.hpp"
 
 #pragma clang fp contract(off)
 
@@ -205,18 +203,6 @@ hipError_t run_list(const TrsvPlan *p, const Structure &s, T *f, hipStream_t st)
     return hipSuccess;
 }
 
-struct Events {
-    hipEvent_t e[2] = {};
-    ~Events() {
-        for (hipEvent_t x : e)
-            if (x) (void)hipEventDestroy(x);
-    }
-    hipError_t create() {
-        hipError_t r = hipEventCreate(&e[0]);
-        return r == hipSuccess ? hipEventCreate(&e[1]) : r;
-    }
-};
-
 void plan_release(TrsvPlan *p) {
     if (!p) return;
     (void)dev_free(p->d_rows);
@@ -252,9 +238,7 @@ int plan_clone(const TrsvPlan *p, uint64_t n, hipStream_t st, TrsvPlan **out) {
 
 // The factor of `a` as three device arrays and a copy of a's lower plan, all the caller's until a handle adopts them.
 struct Factor {
-    uint32_t *ptr = nullptr, *ind = nullptr;
-    void *val = nullptr;
-    uint64_t cap = 0;
+    OpArrays f;
     TrsvPlan *plan = nullptr;
     uint64_t levels = 0, launches = 0, chain_launches = 0, rows_wide = 0, rows_row = 0;
     int64_t wide_work = 0, chain_rows = 0;
@@ -262,53 +246,45 @@ struct Factor {
     Factor() = default;
     Factor(const Factor &) = delete;
     Factor &operator=(const Factor &) = delete;
-    ~Factor() {
-        (void)dev_free(ptr);
-        (void)dev_free(ind);
-        (void)dev_free(val);
-        plan_release(plan);
-    }
+    ~Factor() { plan_release(plan); }
 };
 
 // Called with a->mu held (the plan and its launch list are the handle's); synchronises `st`.
 int factor_locked(const char *fn, spal_csr *a, hipStream_t st, Factor &out) {
     TrsvPlan *p = nullptr;
     SPAL_TRY(trsv_plan_get(fn, a, 0, 0, st, &p));   // row blocks, not square, a row without a diagonal: refused here
-    const uint64_t n = a->nrows, nnz = a->nnz, cap = nnz + kStreamPad;
+    const uint64_t n = a->nrows, nnz = a->nnz;
     const size_t es = (size_t)a->elem_size;
-    Events ev;
-    SPAL_HIP_TRY(ev.create());
-    DevBuf rp, ci, va, diag, wide, cnt;
-    SPAL_HIP_TRY(rp.alloc((n + 1) * 4));
-    SPAL_HIP_TRY(ci.alloc(cap * 4));
-    SPAL_HIP_TRY(va.alloc(cap * es));
+    EventSpans ev;
+    SPAL_HIP_TRY(ev.create(1));
+    OpArrays &f = out.f;
+    DevBuf diag, wide, cnt;
+    SPAL_TRY(f.alloc(n, nnz, es, st));
     SPAL_HIP_TRY(diag.alloc(n * 4));
     SPAL_HIP_TRY(wide.alloc(n));
     SPAL_HIP_TRY(cnt.alloc(4));
-    SPAL_HIP_TRY(hipMemcpyAsync(rp.p, a->d_rowptr, (n + 1) * 4, hipMemcpyDeviceToDevice, st));
+    SPAL_HIP_TRY(hipMemcpyAsync(f.ptr, a->d_rowptr, (n + 1) * 4, hipMemcpyDeviceToDevice, st));
     if (nnz) {
-        SPAL_HIP_TRY(hipMemcpyAsync(ci.p, a->d_colind, nnz * 4, hipMemcpyDeviceToDevice, st));
-        SPAL_HIP_TRY(hipMemcpyAsync(va.p, a->d_values, nnz * es, hipMemcpyDeviceToDevice, st));
+        SPAL_HIP_TRY(hipMemcpyAsync(f.ind, a->d_colind, nnz * 4, hipMemcpyDeviceToDevice, st));
+        SPAL_HIP_TRY(hipMemcpyAsync(f.val, a->d_values, nnz * es, hipMemcpyDeviceToDevice, st));
     }
-    SPAL_HIP_TRY(hipMemsetAsync((char *)ci.p + nnz * 4, 0, kStreamPad * 4, st));
-    SPAL_HIP_TRY(hipMemsetAsync((char *)va.p + nnz * es, 0, kStreamPad * es, st));
     SPAL_HIP_TRY(hipMemsetAsync(cnt.p, 0, 4, st));
     SPAL_HIP_TRY(hipEventRecord(ev.e[0], st));
     if (n) {
-        const unsigned grid = (unsigned)((n + 255) / 256);
+        const unsigned grid = grid_of(n, 256);
         hipLaunchKernelGGL(ilu_diag, dim3(grid), dim3(256), 0, st, p->d_rows, n, diag.as<uint32_t>());
         hipLaunchKernelGGL(ilu_classify, dim3(grid), dim3(256), 0, st, a->d_rowptr, a->d_colind, diag.as<uint32_t>(), n,
                            (uint64_t)a->ilu_wide_work, wide.as<uint8_t>(), cnt.as<uint32_t>());
         SPAL_HIP_TRY(hipGetLastError());
         const Structure s{a->d_rowptr, a->d_colind, diag.as<uint32_t>(), wide.as<uint8_t>()};
-        const hipError_t e = es == 8 ? run_list<double>(p, s, va.as<double>(), st) : run_list<float>(p, s, va.as<float>(), st);
+        const hipError_t e = es == 8 ? run_list<double>(p, s, (double *)f.val, st) : run_list<float>(p, s, (float *)f.val, st);
         if (e != hipSuccess) return fail(SPAL_ERR_HIP, "%s: launch failed: %s", fn, hipGetErrorString(e));
     }
     SPAL_HIP_TRY(hipEventRecord(ev.e[1], st));
     uint32_t nwide = 0;
     SPAL_HIP_TRY(hipMemcpyAsync(&nwide, cnt.p, 4, hipMemcpyDeviceToHost, st));
     SPAL_HIP_TRY(hipStreamSynchronize(st));
-    SPAL_HIP_TRY(hipEventElapsedTime(&out.kernel_ms, ev.e[0], ev.e[1]));
+    SPAL_HIP_TRY(ev.span(0, &out.kernel_ms));
     SPAL_TRY(plan_clone(p, n, st, &out.plan));
     out.levels = p->levels;
     out.launches = p->launches.size();
@@ -317,10 +293,6 @@ int factor_locked(const char *fn, spal_csr *a, hipStream_t st, Factor &out) {
     out.rows_row = n - nwide;
     out.wide_work = a->ilu_wide_work;
     out.chain_rows = a->trsv_chain_rows;
-    out.cap = cap;
-    out.ptr = (uint32_t *)rp.release();
-    out.ind = (uint32_t *)ci.release();
-    out.val = va.release();
     return SPAL_OK;
 }
 
@@ -336,10 +308,6 @@ std::string info_json(const Factor &r, double call_ms) {
     return buf;
 }
 
-double ms_since(std::chrono::steady_clock::time_point t0) {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
-
 // the result's handle takes the plan copy and the operand's schedule options (the copied launch list was recorded with them)
 void give_plan(spal_csr *dst, Factor &r) {
     std::lock_guard<std::mutex> lock(dst->mu);
@@ -347,6 +315,17 @@ void give_plan(spal_csr *dst, Factor &r) {
     dst->ilu_wide_work = r.wide_work;
     dst->trsv[0] = r.plan;
     r.plan = nullptr;
+}
+
+// what both entry points end with: a handle of a's type around `arrays` (the factor, by rows or by columns), the plan
+// copy handed to the CSR handle the solves will run on
+template <typename H>
+int adopt_factor(const H *a, OpArrays &arrays, Factor &r, std::chrono::steady_clock::time_point t0, H **out) {
+    // nobody multiplies by L\U: the product plan is left to whoever asks for one
+    SPAL_TRY(arrays.adopt(a->device, a->elem_size, a->nrows, a->ncols, out, false, true));
+    give_plan(solve_handle(*out), r);
+    (*out)->ops.ilu_info = info_json(r, ms_since(t0));
+    return SPAL_OK;
 }
 
 }  // namespace
@@ -363,15 +342,6 @@ int ilu_option(spal_csr *a, const char *key, int64_t value, int *status) {
     return 1;
 }
 
-int ilu_describe_append(char *buf, size_t buf_len, const std::string &info) {
-    if (info.empty()) return SPAL_OK;
-    const size_t len = strnlen(buf, buf_len);
-    if (len == 0 || buf[len - 1] != '}' || len + info.size() + 16 > buf_len)
-        return fail(SPAL_ERR_INVALID_ARGUMENT, "describe: buffer of %zu bytes too small", buf_len);
-    snprintf(buf + len - 1, buf_len - (len - 1), ", \"ilu0\": %s}", info.c_str());
-    return SPAL_OK;
-}
-
 }  // namespace spal
 
 using namespace spal;
@@ -381,6 +351,7 @@ extern "C" {
 int spal_csr_ilu0(spal_csr_t a, void *stream, spal_csr_t *out) {
     const char *fn = "spal_csr_ilu0";
     if (!a || !out) return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: null argument", fn);
+    *out = nullptr;
     DeviceGuard guard(a->device);
     if (guard.status != SPAL_OK) return guard.status;
     const auto t0 = std::chrono::steady_clock::now();
@@ -389,20 +360,13 @@ int spal_csr_ilu0(spal_csr_t a, void *stream, spal_csr_t *out) {
         std::lock_guard<std::mutex> lock(a->mu);
         SPAL_TRY(factor_locked(fn, a, (hipStream_t)stream, r));
     }
-    // nobody multiplies by L\U: the product plan is left to whoever asks for one
-    spal_csr *f = nullptr;
-    SPAL_TRY(csr_adopt_device(a->device, a->elem_size, a->nrows, a->ncols, a->nnz, r.cap, r.ptr, r.ind, r.val, &f, false, true));
-    r.ptr = r.ind = nullptr;   // the handle's now
-    r.val = nullptr;
-    give_plan(f, r);
-    f->ilu_info = info_json(r, ms_since(t0));
-    *out = f;
-    return SPAL_OK;
+    return adopt_factor(a, r.f, r, t0, out);
 }
 
 int spal_csc_ilu0(spal_csc_t a, void *stream, spal_csc_t *out) {
     const char *fn = "spal_csc_ilu0";
     if (!a || !out) return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: null argument", fn);
+    *out = nullptr;
     DeviceGuard guard(a->device);
     if (guard.status != SPAL_OK) return guard.status;
     const auto t0 = std::chrono::steady_clock::now();
@@ -413,23 +377,11 @@ int spal_csc_ilu0(spal_csc_t a, void *stream, spal_csc_t *out) {
         std::lock_guard<std::mutex> lock(twin->mu);
         SPAL_TRY(factor_locked(fn, twin, st, r));
     }
-    // the factor by columns (the existing transpose path), then a CSC handle around it; its constructor builds the twin
-    uint32_t *cp = nullptr, *ri = nullptr;
-    void *va = nullptr;
-    uint64_t cap = 0;
-    SPAL_TRY(transpose_device(a->device, a->elem_size, a->nrows, a->ncols, a->nnz, r.ptr, r.ind, r.val, st, &cp, &ri, &va, &cap));
-    spal_csc *f = nullptr;
-    const int status = csc_adopt_device(a->device, a->elem_size, a->nrows, a->ncols, a->nnz, cap, cp, ri, va, &f);
-    if (status != SPAL_OK) {
-        (void)dev_free(cp);
-        (void)dev_free(ri);
-        (void)dev_free(va);
-        return status;
-    }
-    give_plan(f->as_csr, r);   // the twin has the operand's twin's structure
-    f->ilu_info = info_json(r, ms_since(t0));
-    *out = f;
-    return SPAL_OK;
+    // the factor by columns (the existing transpose path), then a CSC handle around it; its constructor builds the twin,
+    // which has the operand's twin's structure
+    OpArrays bycol;
+    SPAL_TRY(transpose_device(a->device, a->elem_size, a->nrows, a->ncols, a->nnz, r.f.ptr, r.f.ind, r.f.val, st, bycol));
+    return adopt_factor(a, bycol, r, t0, out);
 }
 
 }  // extern "C"

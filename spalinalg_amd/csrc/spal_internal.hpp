@@ -229,27 +229,9 @@ struct CsrPlan {
          user_unroll = false, user_threads = false, user_rows_per_tile = false;
 };
 
-// implemented in spal_transpose.hip: stable sort of the entries by their minor index
-// (compressed-by-major -> compressed-by-minor); outputs are hipMalloc'ed with
-// *out_cap entries (nnz + over-read margin) and owned by the caller
-int transpose_device(int device, int elem_size, uint64_t nmajor, uint64_t nminor, uint64_t nnz,
-                     const uint32_t *d_ptr, const uint32_t *d_ind, const void *d_val,
-                     hipStream_t st, uint32_t **out_ptr, uint32_t **out_ind, void **out_val,
-                     uint64_t *out_cap);
-// implemented in spal_spgemm.hip: the options "spgemm_route" / "spgemm_lds_cap" of either handle type (1 = the key is one
-// of them and *status says how setting it went, 0 = another key)
-int spgemm_option(const char *key, int64_t value, int *route, int64_t *lds_cap, int *status);
-// ... and the "spgemm" object a product handle adds to its describe() line (no-op for an empty `info`)
-int spgemm_describe_append(char *buf, size_t buf_len, const std::string &info);
-// implemented in spal_spadd.hip: the option "spadd_tile" of either handle type (as spgemm_option), and the "spadd" object
-// a handle built by spal_*_add / _sub / _neg adds to its describe() line
-int spadd_option(const char *key, int64_t value, uint32_t *tile, int *status);
-int spadd_describe_append(char *buf, size_t buf_len, const std::string &info);
-// implemented in spal_spmm.hip: the option "spmm_tile" of either handle type (as spgemm_option)
-int spmm_option(const char *key, int64_t value, int *tile, int *status);
-// implemented in spal_trsv.hip: the option "trsv_chain_rows" of a CSR handle (as spgemm_option; existing plans get their
-// launch lists rebuilt under the handle's lock)
-int trsv_option(spal_csr *a, const char *key, int64_t value, int *status);
+// implemented in spal_host.cpp: appends `, "<key>": <body>` before the closing brace of the line in buf (no-op for an
+// empty body); refused, with buf unchanged, when the result and its NUL do not fit buf_len or buf does not end in '}'
+int describe_append(char *buf, size_t buf_len, const char *key, const std::string &body);
 // implemented in spal_host.cpp: the level analysis of spal_trsv_levels on the device's 32-bit arrays; *first_missing_diag
 // = n when every row stores its diagonal (no error either way), dpos[i] = the first entry of row i with column >= i
 int trsv_levels_u32(uint64_t n, const uint32_t *rowptr, const uint32_t *colind, int uplo, uint32_t *level_of,
@@ -276,11 +258,20 @@ constexpr int64_t kTrsvChainRowsDefault = 256;
 // ... the plan of `uplo`, built now (under a->mu, which the caller holds; counted in trsv_analyses) if the handle has
 // none; refuses row-block handles, matrices that are not square and, unless unit_diag, a row without a diagonal
 int trsv_plan_get(const char *fn, spal_csr *a, int uplo, int unit_diag, hipStream_t st, TrsvPlan **out);
-// ILU(0) (spal_ilu.hip): the option "ilu_wide_work" of a CSR handle (as spgemm_option), and the "ilu0"
-// object a factor adds to its describe() line
-constexpr int64_t kIluWideWorkDefault = 4096;
-int ilu_option(spal_csr *a, const char *key, int64_t value, int *status);
-int ilu_describe_append(char *buf, size_t buf_len, const std::string &info);
+constexpr int64_t kIluWideWorkDefault = 4096;   // ILU(0) (spal_ilu.hip): the option "ilu_wide_work"
+
+// What the sparse operations keep on a handle of either type (spal_ops.hpp sets and describes it): the options of this
+// handle as the LEFT operand, and what built it if it is a result.  An info string is the object of that name in
+// describe(), empty when the handle is no such result.
+struct OpState {
+    int spgemm_route = 0;          // option "spgemm_route": 0 auto, 1 LDS tiers wherever they fit, 2 every row through the large tier
+    int64_t spgemm_lds_cap = 0;    // option "spgemm_lds_cap": 0 default, else the largest product count of a row sent to LDS
+    uint32_t spadd_tile = 0;       // option "spadd_tile": merged elements per workgroup, 0 = default
+    int spmm_tile = 0;             // option "spmm_tile": column tile, 0 = automatic (SpMM always runs on the CSR handle or twin)
+    std::string spgemm_info;       // "spgemm": a product of spal_*_mul
+    std::string spadd_info;        // "spadd": a result of spal_*_add / _sub / _neg
+    std::string ilu_info;          // "ilu0": a factor of spal_*_ilu0
+};
 }  // namespace spal
 
 // The opaque handle types of spal.h.
@@ -358,15 +349,7 @@ struct spal_csr {
     // one after the other on the caller's stream, block b writing y[part_row0[b] ...).
     std::vector<spal_csr *> parts;
     std::vector<uint64_t> part_row0, part_entry0;   // first row / first entry of every block, then nrows / nnz
-    // sparse x sparse (spal_spgemm.hip): options of this handle as the LEFT operand, and what built it if it is a product
-    int spgemm_route = 0;          // option "spgemm_route": 0 auto, 1 LDS tiers wherever they fit, 2 every row through the large tier
-    int64_t spgemm_lds_cap = 0;    // option "spgemm_lds_cap": 0 default, else the largest product count of a row sent to LDS
-    std::string spgemm_info;       // the "spgemm" object of spal_csr_describe (empty: not a product)
-    // A + B, A - B, -A (spal_spadd.hip): the option of this handle as the LEFT operand, and what built it if it is a sum
-    uint32_t spadd_tile = 0;       // option "spadd_tile": merged elements per workgroup, 0 = default
-    std::string spadd_info;        // the "spadd" object of spal_csr_describe (empty: not a sum)
-    // Y = A * X (spal_spmm.hip)
-    int spmm_tile = 0;             // option "spmm_tile": column tile, 0 = automatic
+    spal::OpState ops;             // sparse x sparse, A +- B, Y = A * X, ILU(0): options and what built this handle
     uint64_t spmm_last = 0;        // {tile << 32 | k} of the last SpMM on this handle (0: none yet), for describe
     // L x = b, U x = b (spal_trsv.hip); guarded by mu
     int64_t trsv_chain_rows = spal::kTrsvChainRowsDefault;   // option "trsv_chain_rows": the widest level the chain kernel takes
@@ -374,7 +357,6 @@ struct spal_csr {
     int trsv_analyses = 0;         // plans built so far (describe)
     // ILU(0) (spal_ilu.hip); the option guarded by mu
     int64_t ilu_wide_work = spal::kIluWideWorkDefault;   // option "ilu_wide_work": rows with at least this much work take the wide form
-    std::string ilu_info;          // the "ilu0" object of spal_csr_describe (empty: not a factor)
 };
 
 struct spal_csc {
@@ -436,13 +418,7 @@ struct spal_csc {
     std::mutex mu;
     void *d_x = nullptr, *d_y = nullptr;
     hipStream_t stream = nullptr;
-    int spgemm_route = 0;          // as spal_csr's
-    int64_t spgemm_lds_cap = 0;
-    std::string spgemm_info;
-    uint32_t spadd_tile = 0;       // as spal_csr's
-    std::string spadd_info;
-    int spmm_tile = 0;             // as spal_csr's; SpMM always runs on as_csr
-    std::string ilu_info;          // as spal_csr's; the factorisation runs on as_csr
+    spal::OpState ops;             // as spal_csr's; SpMM, the solve and the factorisation run on as_csr
 };
 
 struct spal_coo {
@@ -484,12 +460,8 @@ void csr_free(spal_csr *a);            // the handle and everything it owns (NUL
 // implemented in spal_spmm.hip: Y = A * X enqueued on `stream` (tile 0 = automatic); reads a's plain arrays only, no plan
 int spmm_launch(spal_csr *a, int tile, uint64_t k, const void *x_dev, uint64_t ldx, void *y_dev, uint64_t ldy,
                 hipStream_t stream);
-// ... and the "spmm" object a handle (a may be null) adds to its describe() line once an SpMM ran on it
-int spmm_describe_append(char *buf, size_t buf_len, const spal_csr *a);
-// implemented in spal_trsv.hip: frees a handle's solve plans (csr_free), and the "trsv" object a handle (a may be null)
-// adds to its describe() line once a triangle was analysed
+// implemented in spal_trsv.hip: frees a handle's solve plans (csr_free)
 void trsv_free(spal_csr *a);
-int trsv_describe_append(char *buf, size_t buf_len, spal_csr *a);
 // implemented in spal_csr_slide.hip: the sliding-window kernel for a plan with plan.slide set
 hipError_t launch_slide(const spal_csr *a, const void *x, void *y, hipStream_t st);
 // ... its plan (for csr_plan_build): decides whether it can run the chosen stream plan and builds its step descriptors

@@ -21,11 +21,8 @@
 // element at the tail compares with it, and a matched one reads that B value from global memory).  Boundaries stay
 // where the arithmetic puts them.
 // Values follow the reference's loop: A only `a`, B only `b` (Add) or `-b` (Sub, an fneg), both `a + b` / `a - b`.
-#include <chrono>
-
-#include <rocprim/device/device_scan.hpp>
-
-#include "spal_internal.hpp"
+#define SPAL_OPS_SCAN
+#include "spal_ops.hpp"
 
 #pragma clang fp contract(off)
 
@@ -305,56 +302,23 @@ __global__ __launch_bounds__(256) void spadd_neg(const T *__restrict__ x, T *__r
 }
 
 // ---- host ----------------------------------------------------------------------------------------------------------
-struct Operand {
-    uint64_t nmajor;
-    uint64_t nnz;
-    const uint32_t *ptr, *ind;
-    const void *val;
-};
-
 struct Sum {
-    uint32_t *ptr = nullptr, *ind = nullptr;
-    void *val = nullptr;
-    uint64_t nnz = 0, cap = 0, matched = 0, tiles = 0;
+    OpArrays c;
+    uint64_t matched = 0, tiles = 0;
     uint32_t tile = 0;
-    float kernel_ms = 0.f;
+    float kernel_ms = 0.f;   // device time: the count pass and the scans, then the fill (EventSpans 0 and 1)
 };
 
-inline unsigned grid_of(uint64_t n, unsigned per) { return (unsigned)((n + per - 1) / per); }
-
-// device time of the kernels: [e[0], e[1]) the count pass and the scans, [e[2], e[3]) the fill (not the host's read
-// back and allocation between them)
-struct Events {
-    hipEvent_t e[4] = {};
-    ~Events() {
-        for (hipEvent_t x : e)
-            if (x) (void)hipEventDestroy(x);
-    }
-    hipError_t create() {
-        for (hipEvent_t &x : e) {
-            const hipError_t r = hipEventCreate(&x);
-            if (r != hipSuccess) return r;
-        }
-        return hipSuccess;
-    }
-    static float span(hipEvent_t a, hipEvent_t b) {
-        float v = 0.f;
-        return hipEventElapsedTime(&v, a, b) == hipSuccess ? v : 0.f;
-    }
-    float ms(bool two) const { return span(e[0], e[1]) + (two ? span(e[2], e[3]) : 0.f); }
-};
-
-// the two exclusive scans of the count pass, sharing one temporary block; synchronises `st`
+// the two exclusive scans of the count pass, sharing one temporary block and one synchronisation of `st`
 hipError_t scan_two(const unsigned long long *tin, unsigned long long *tout, uint64_t tn, const uint32_t *rin,
                     uint32_t *rout, uint64_t rn, hipStream_t st) {
     size_t b1 = 0, b2 = 0;
-    hipError_t e = rocprim::exclusive_scan(nullptr, b1, tin, tout, 0ull, (size_t)tn, rocprim::plus<unsigned long long>(), st);
-    if (e == hipSuccess) e = rocprim::exclusive_scan(nullptr, b2, rin, rout, 0u, (size_t)rn, rocprim::plus<uint32_t>(), st);
-    if (e != hipSuccess) return e;
     DevBuf tmp;
-    e = tmp.alloc(std::max(b1, b2));
-    if (e == hipSuccess) e = rocprim::exclusive_scan(tmp.p, b1, tin, tout, 0ull, (size_t)tn, rocprim::plus<unsigned long long>(), st);
-    if (e == hipSuccess) e = rocprim::exclusive_scan(tmp.p, b2, rin, rout, 0u, (size_t)rn, rocprim::plus<uint32_t>(), st);
+    hipError_t e = scan_step(nullptr, b1, tin, tout, tn, st);
+    if (e == hipSuccess) e = scan_step(nullptr, b2, rin, rout, rn, st);
+    if (e == hipSuccess) e = tmp.alloc(std::max(b1, b2));
+    if (e == hipSuccess) e = scan_step(tmp.p, b1, tin, tout, tn, st);
+    if (e == hipSuccess) e = scan_step(tmp.p, b2, rin, rout, rn, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);   // (tmp returns to the allocator on exit)
     return e;
 }
@@ -365,8 +329,8 @@ int spadd_t(const char *fn, const Operand &A, const Operand &B, uint32_t tile, h
     const uint64_t tiles = (total + tile - 1) / tile, P = tiles + 1;
     out.tile = tile;
     out.tiles = tiles;
-    Events ev;
-    SPAL_HIP_TRY(ev.create());
+    EventSpans ev;
+    SPAL_HIP_TRY(ev.create(2));
     DevBuf part, tcnt, toff, rdup, rscan;
     SPAL_HIP_TRY(part.alloc(P * 3 * 4));
     SPAL_HIP_TRY(tcnt.alloc(P * 8));
@@ -398,30 +362,19 @@ int spadd_t(const char *fn, const Operand &A, const Operand &B, uint32_t tile, h
                     (unsigned long long)total);
     if (nnz > kMaxEntries)
         return fail(SPAL_ERR_UNSUPPORTED, "%s: the result has %llu entries, more than 32-bit device offsets address", fn, nnz);
-    DevBuf cp, ci, cv;
-    const uint64_t cap = nnz + kStreamPad;
-    SPAL_HIP_TRY(cp.alloc((m + 1) * 4));
-    SPAL_HIP_TRY(ci.alloc(cap * 4));
-    SPAL_HIP_TRY(cv.alloc(cap * sizeof(T)));
-    SPAL_HIP_TRY(hipMemsetAsync((char *)ci.p + nnz * 4, 0, kStreamPad * 4, st));
-    SPAL_HIP_TRY(hipMemsetAsync((char *)cv.p + nnz * sizeof(T), 0, kStreamPad * sizeof(T), st));
+    SPAL_TRY(out.c.alloc(m, nnz, sizeof(T), st));
     SPAL_HIP_TRY(hipEventRecord(ev.e[2], st));
     hipLaunchKernelGGL(spadd_rowptr, dim3(grid_of(m + 1, 256)), dim3(256), 0, st, A.ptr, B.ptr, rscan.as<uint32_t>(),
-                       m + 1, cp.as<uint32_t>());
+                       m + 1, out.c.ptr);
     if (tiles)
         hipLaunchKernelGGL((spadd_tile<T, true, SUB>), dim3((unsigned)tiles), dim3(kThreads), 0, st, A.ptr, A.ind,
                            (const T *)A.val, B.ptr, B.ind, (const T *)B.val, (uint32_t)B.nnz, tile, part_p, P, nullptr,
-                           nullptr, toff.as<unsigned long long>(), ci.as<uint32_t>(), cv.as<T>());
+                           nullptr, toff.as<unsigned long long>(), out.c.ind, (T *)out.c.val);
     SPAL_HIP_TRY(hipGetLastError());
     SPAL_HIP_TRY(hipEventRecord(ev.e[3], st));
     SPAL_HIP_TRY(hipStreamSynchronize(st));
-    out.kernel_ms = ev.ms(true);
-    out.nnz = nnz;
+    out.kernel_ms = ev.ms(2);
     out.matched = matched;
-    out.cap = cap;
-    out.ptr = (uint32_t *)cp.release();
-    out.ind = (uint32_t *)ci.release();
-    out.val = cv.release();
     return SPAL_OK;
 }
 
@@ -435,36 +388,26 @@ int spadd(const char *fn, int elem_size, bool sub, const Operand &A, const Opera
 
 // -A: the index arrays copied, the values negated
 int spneg(int elem_size, const Operand &A, hipStream_t st, Sum &out) {
-    const uint64_t m = A.nmajor, nnz = A.nnz, cap = nnz + kStreamPad;
-    Events ev;
-    SPAL_HIP_TRY(ev.create());
-    DevBuf cp, ci, cv;
-    SPAL_HIP_TRY(cp.alloc((m + 1) * 4));
-    SPAL_HIP_TRY(ci.alloc(cap * 4));
-    SPAL_HIP_TRY(cv.alloc(cap * elem_size));
+    const uint64_t m = A.nmajor, nnz = A.nnz;
+    EventSpans ev;
+    SPAL_HIP_TRY(ev.create(1));
+    SPAL_TRY(out.c.alloc(m, nnz, (size_t)elem_size, st));
     SPAL_HIP_TRY(hipEventRecord(ev.e[0], st));
-    SPAL_HIP_TRY(hipMemcpyAsync(cp.p, A.ptr, (m + 1) * 4, hipMemcpyDeviceToDevice, st));
-    if (nnz) SPAL_HIP_TRY(hipMemcpyAsync(ci.p, A.ind, nnz * 4, hipMemcpyDeviceToDevice, st));
-    SPAL_HIP_TRY(hipMemsetAsync((char *)ci.p + nnz * 4, 0, kStreamPad * 4, st));
-    SPAL_HIP_TRY(hipMemsetAsync((char *)cv.p + nnz * elem_size, 0, kStreamPad * elem_size, st));
+    SPAL_HIP_TRY(hipMemcpyAsync(out.c.ptr, A.ptr, (m + 1) * 4, hipMemcpyDeviceToDevice, st));
     if (nnz) {
+        SPAL_HIP_TRY(hipMemcpyAsync(out.c.ind, A.ind, nnz * 4, hipMemcpyDeviceToDevice, st));
         const uint64_t threads = nnz / (16 / elem_size) + 16 / elem_size;
         if (elem_size == 8)
             hipLaunchKernelGGL(spadd_neg<double>, dim3(grid_of(threads, 256)), dim3(256), 0, st, (const double *)A.val,
-                               cv.as<double>(), nnz);
+                               (double *)out.c.val, nnz);
         else
             hipLaunchKernelGGL(spadd_neg<float>, dim3(grid_of(threads, 256)), dim3(256), 0, st, (const float *)A.val,
-                               cv.as<float>(), nnz);
+                               (float *)out.c.val, nnz);
         SPAL_HIP_TRY(hipGetLastError());
     }
     SPAL_HIP_TRY(hipEventRecord(ev.e[1], st));
     SPAL_HIP_TRY(hipStreamSynchronize(st));
-    out.kernel_ms = ev.ms(false);
-    out.nnz = nnz;
-    out.cap = cap;
-    out.ptr = (uint32_t *)cp.release();
-    out.ind = (uint32_t *)ci.release();
-    out.val = cv.release();
+    out.kernel_ms = ev.ms(1);
     return SPAL_OK;
 }
 
@@ -473,26 +416,14 @@ std::string info_json(const char *op, const Sum &r, double plan_ms, double ms) {
     snprintf(buf, sizeof buf,
              "{\"op\": \"%s\", \"tile\": %u, \"tiles\": %llu, \"matched\": %llu, \"nnz\": %llu, \"kernel_ms\": %.4f, "
              "\"plan_ms\": %.3f, \"call_ms\": %.3f}",
-             op, r.tile, (unsigned long long)r.tiles, (unsigned long long)r.matched, (unsigned long long)r.nnz,
+             op, r.tile, (unsigned long long)r.tiles, (unsigned long long)r.matched, (unsigned long long)r.c.nnz,
              (double)r.kernel_ms, plan_ms, ms);
     return buf;
 }
 
-double ms_since(std::chrono::steady_clock::time_point t0) {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
-
-void free_sum(Sum &r) {
-    (void)dev_free(r.ptr);
-    (void)dev_free(r.ind);
-    (void)dev_free(r.val);
-    r.ptr = r.ind = nullptr;
-    r.val = nullptr;
-}
-
 // the checks of add.rs:9-10 / sub.rs:9-10 in their order, then what the device needs
 template <typename H>
-int check_pair(const char *fn, H a, H b, H *out) {
+int check_pair(const char *fn, const H *a, const H *b, H **out) {
     if (!a || !b || !out) return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: null argument", fn);
     *out = nullptr;
     if (a->nrows != b->nrows)
@@ -501,77 +432,57 @@ int check_pair(const char *fn, H a, H b, H *out) {
     if (a->ncols != b->ncols)
         return fail(SPAL_ERR_INVALID_ARGUMENT, "assertion failed: ncols == rhs.ncols (left: %llu, right: %llu)",
                     (unsigned long long)a->ncols, (unsigned long long)b->ncols);
-    if (a->device != b->device)
-        return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: operands on devices %d and %d", fn, a->device, b->device);
-    if (a->elem_size != b->elem_size)
-        return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: operands of element sizes %d and %d", fn, a->elem_size, b->elem_size);
-    return SPAL_OK;
+    return check_same_device_and_dtype(fn, a, b);
 }
 
-int csr_binary(const char *fn, bool sub, spal_csr_t a, spal_csr_t b, void *stream, spal_csr_t *out) {
-    SPAL_TRY(check_pair(fn, a, b, out));
-    if (!a->parts.empty() || !b->parts.empty())
-        return fail(SPAL_ERR_UNSUPPORTED, "%s: an operand of more than 2^32 - 65537 entries (row blocks)", fn);
-    DeviceGuard guard(a->device);
-    if (guard.status != SPAL_OK) return guard.status;
-    const auto t0 = std::chrono::steady_clock::now();
-    const Operand A{a->nrows, a->nnz, a->d_rowptr, a->d_colind, a->d_values};
-    const Operand B{b->nrows, b->nnz, b->d_rowptr, b->d_colind, b->d_values};
-    Sum r;
-    SPAL_TRY(spadd(fn, a->elem_size, sub, A, B, a->spadd_tile, (hipStream_t)stream, r));
+// what every entry point ends with: a handle of a's type and shape around the result
+template <typename H>
+int adopt_sum(const char *op, const H *a, Sum &r, std::chrono::steady_clock::time_point t0, H **out) {
     const auto tp = std::chrono::steady_clock::now();
-    // eager plan, as spal_csr_mul's result: a choice, no longer a workaround (a lazily planned handle used to reach
+    // CSR: eager plan, as spal_csr_mul's result: a choice, no longer a workaround (a lazily planned handle used to reach
     // csr_blockwin_or_split re-entrantly; the planner's own launches are csr_launch_planned now).  describe()'s
     // plan_ms reports the plan's cost, and the first product of the sum pays nothing.
-    const int st = csr_adopt_device(a->device, a->elem_size, a->nrows, a->ncols, r.nnz, r.cap, r.ptr, r.ind, r.val, out,
-                                    true, false);
-    if (st != SPAL_OK) {
-        free_sum(r);
-        return st;
-    }
-    (*out)->spadd_info = info_json(sub ? "sub" : "add", r, ms_since(tp), ms_since(t0));
+    SPAL_TRY(r.c.adopt(a->device, a->elem_size, a->nrows, a->ncols, out, true, false));
+    (*out)->ops.spadd_info = info_json(op, r, ms_since(tp), ms_since(t0));
     return SPAL_OK;
 }
 
-int csc_binary(const char *fn, bool sub, spal_csc_t a, spal_csc_t b, void *stream, spal_csc_t *out) {
+template <typename H>
+int binary(const char *fn, bool sub, H *a, H *b, void *stream, H **out) {
     SPAL_TRY(check_pair(fn, a, b, out));
+    if (row_blocks(a) || row_blocks(b)) return refuse_row_blocks(fn);
     DeviceGuard guard(a->device);
     if (guard.status != SPAL_OK) return guard.status;
     const auto t0 = std::chrono::steady_clock::now();
-    const Operand A{a->ncols, a->nnz, a->d_colptr, a->d_rowind, a->d_values};
-    const Operand B{b->ncols, b->nnz, b->d_colptr, b->d_rowind, b->d_values};
     Sum r;
-    SPAL_TRY(spadd(fn, a->elem_size, sub, A, B, a->spadd_tile, (hipStream_t)stream, r));
-    const auto tp = std::chrono::steady_clock::now();
-    const int st = csc_adopt_device(a->device, a->elem_size, a->nrows, a->ncols, r.nnz, r.cap, r.ptr, r.ind, r.val, out);
-    if (st != SPAL_OK) {
-        free_sum(r);
-        return st;
-    }
-    (*out)->spadd_info = info_json(sub ? "sub" : "add", r, ms_since(tp), ms_since(t0));
-    return SPAL_OK;
+    SPAL_TRY(spadd(fn, a->elem_size, sub, operand_of(a), operand_of(b), a->ops.spadd_tile, (hipStream_t)stream, r));
+    return adopt_sum(sub ? "sub" : "add", a, r, t0, out);
+}
+
+template <typename H>
+int negate(const char *fn, H *a, void *stream, H **out) {
+    if (!a || !out) return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: null argument", fn);
+    *out = nullptr;
+    if (row_blocks(a)) return refuse_row_blocks(fn);
+    DeviceGuard guard(a->device);
+    if (guard.status != SPAL_OK) return guard.status;
+    const auto t0 = std::chrono::steady_clock::now();
+    Sum r;
+    SPAL_TRY(spneg(a->elem_size, operand_of(a), (hipStream_t)stream, r));
+    return adopt_sum("neg", a, r, t0, out);
 }
 
 }  // namespace
 
-int spadd_option(const char *key, int64_t value, uint32_t *tile, int *status) {
+int spadd_option(const char *key, int64_t value, OpState &s, int *status) {
     if (strcmp(key, "spadd_tile")) return 0;
     const bool pow2 = value > 0 && (value & (value - 1)) == 0;
     *status = (value == 0 || (pow2 && value >= (int64_t)kTileMin && value <= (int64_t)kTileMax))
                   ? SPAL_OK
                   : fail(SPAL_ERR_INVALID_ARGUMENT, "spadd_tile must be 0 (default, %u) or a power of two in [%u, %u]",
                          kTileMax, kTileMin, kTileMax);
-    if (*status == SPAL_OK) *tile = (uint32_t)value;
+    if (*status == SPAL_OK) s.spadd_tile = (uint32_t)value;
     return 1;
-}
-
-int spadd_describe_append(char *buf, size_t buf_len, const std::string &info) {
-    if (info.empty()) return SPAL_OK;
-    const size_t len = strnlen(buf, buf_len);
-    if (len == 0 || buf[len - 1] != '}' || len + info.size() + 16 > buf_len)
-        return fail(SPAL_ERR_INVALID_ARGUMENT, "describe: buffer of %zu bytes too small", buf_len);
-    snprintf(buf + len - 1, buf_len - (len - 1), ", \"spadd\": %s}", info.c_str());
-    return SPAL_OK;
 }
 
 }  // namespace spal
@@ -581,56 +492,18 @@ using namespace spal;
 extern "C" {
 
 int spal_csr_add(spal_csr_t a, spal_csr_t b, void *stream, spal_csr_t *out) {
-    return csr_binary("spal_csr_add", false, a, b, stream, out);
+    return binary("spal_csr_add", false, a, b, stream, out);
 }
 int spal_csr_sub(spal_csr_t a, spal_csr_t b, void *stream, spal_csr_t *out) {
-    return csr_binary("spal_csr_sub", true, a, b, stream, out);
+    return binary("spal_csr_sub", true, a, b, stream, out);
 }
 int spal_csc_add(spal_csc_t a, spal_csc_t b, void *stream, spal_csc_t *out) {
-    return csc_binary("spal_csc_add", false, a, b, stream, out);
+    return binary("spal_csc_add", false, a, b, stream, out);
 }
 int spal_csc_sub(spal_csc_t a, spal_csc_t b, void *stream, spal_csc_t *out) {
-    return csc_binary("spal_csc_sub", true, a, b, stream, out);
+    return binary("spal_csc_sub", true, a, b, stream, out);
 }
-
-int spal_csr_neg(spal_csr_t a, void *stream, spal_csr_t *out) {
-    if (!a || !out) return fail(SPAL_ERR_INVALID_ARGUMENT, "spal_csr_neg: null argument");
-    *out = nullptr;
-    if (!a->parts.empty())
-        return fail(SPAL_ERR_UNSUPPORTED, "spal_csr_neg: an operand of more than 2^32 - 65537 entries (row blocks)");
-    DeviceGuard guard(a->device);
-    if (guard.status != SPAL_OK) return guard.status;
-    const auto t0 = std::chrono::steady_clock::now();
-    Sum r;
-    SPAL_TRY(spneg(a->elem_size, Operand{a->nrows, a->nnz, a->d_rowptr, a->d_colind, a->d_values}, (hipStream_t)stream, r));
-    const auto tp = std::chrono::steady_clock::now();
-    // eager plan by choice, as the sum's above
-    const int st = csr_adopt_device(a->device, a->elem_size, a->nrows, a->ncols, r.nnz, r.cap, r.ptr, r.ind, r.val, out,
-                                    true, false);
-    if (st != SPAL_OK) {
-        free_sum(r);
-        return st;
-    }
-    (*out)->spadd_info = info_json("neg", r, ms_since(tp), ms_since(t0));
-    return SPAL_OK;
-}
-
-int spal_csc_neg(spal_csc_t a, void *stream, spal_csc_t *out) {
-    if (!a || !out) return fail(SPAL_ERR_INVALID_ARGUMENT, "spal_csc_neg: null argument");
-    *out = nullptr;
-    DeviceGuard guard(a->device);
-    if (guard.status != SPAL_OK) return guard.status;
-    const auto t0 = std::chrono::steady_clock::now();
-    Sum r;
-    SPAL_TRY(spneg(a->elem_size, Operand{a->ncols, a->nnz, a->d_colptr, a->d_rowind, a->d_values}, (hipStream_t)stream, r));
-    const auto tp = std::chrono::steady_clock::now();
-    const int st = csc_adopt_device(a->device, a->elem_size, a->nrows, a->ncols, r.nnz, r.cap, r.ptr, r.ind, r.val, out);
-    if (st != SPAL_OK) {
-        free_sum(r);
-        return st;
-    }
-    (*out)->spadd_info = info_json("neg", r, ms_since(tp), ms_since(t0));
-    return SPAL_OK;
-}
+int spal_csr_neg(spal_csr_t a, void *stream, spal_csr_t *out) { return negate("spal_csr_neg", a, stream, out); }
+int spal_csc_neg(spal_csc_t a, void *stream, spal_csc_t *out) { return negate("spal_csc_neg", a, stream, out); }
 
 }  // extern "C"

@@ -13,11 +13,8 @@
 // no two lanes touch one slot within a step; a step is complete and visible before the next (group_sync); the lane whose
 // CAS claims an empty slot assigns the product, every later touch adds.  The large tier keeps it by the stability of the
 // two transposes (equal columns stay in expansion order = k order) and a left-to-right fold.
-#include <chrono>
-
-#include <rocprim/device/device_scan.hpp>
-
-#include "spal_internal.hpp"
+#define SPAL_OPS_SCAN
+#include "spal_ops.hpp"
 
 // Products are rounded before they are added: no contraction into FMA (the reference's `vec[j] += a * b` is two
 // roundings).  tests/test_spgemm_host.py checks the kernels' ISA for fused forms.
@@ -306,21 +303,11 @@ __global__ __launch_bounds__(256) void spgemm_rowptr32(const unsigned long long 
 }
 
 // ---- host ----------------------------------------------------------------------------------------------------------
-struct Operand {
-    uint64_t nrows, ncols;
-    const uint32_t *ptr, *ind;
-    const void *val;
-};
-
 struct Product {
-    uint32_t *ptr = nullptr, *ind = nullptr;
-    void *val = nullptr;
-    uint64_t nnz = 0, cap = 0;
+    OpArrays c;
     uint32_t tier[kTiers] = {};
     uint64_t products = 0, large_products = 0;
 };
-
-inline unsigned grid_of(uint64_t n, unsigned per) { return (unsigned)((n + per - 1) / per); }
 
 template <typename T, int G, int TS, int GPB>
 void launch_tier(bool numeric, const uint32_t *rows, uint32_t n, const Operand &A, const Operand &B,
@@ -346,22 +333,10 @@ void launch_lds_tiers(bool numeric, const uint32_t *list, const uint32_t *tier_s
     launch_tier<T, 256, 8192, 1>(numeric, list + tier_start[5], tier_n[5], A, B, cnt, off, cci, cv, st);
 }
 
-template <typename U>
-hipError_t scan_exclusive(const U *in, U *out, uint64_t n, hipStream_t st) {
-    size_t bytes = 0;
-    hipError_t e = rocprim::exclusive_scan(nullptr, bytes, in, out, U(0), (size_t)n, rocprim::plus<U>(), st);
-    if (e != hipSuccess) return e;
-    DevBuf tmp;
-    e = tmp.alloc(bytes);
-    if (e == hipSuccess) e = rocprim::exclusive_scan(tmp.p, bytes, in, out, U(0), (size_t)n, rocprim::plus<U>(), st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);   // (tmp returns to the allocator on exit)
-    return e;
-}
-
-// C (A.nrows x B.ncols) = A * B on `st`; C's arrays are returned in `out` (owned by the caller on success).
+// C (A.nmajor x B.nminor) = A * B on `st`; C's arrays are returned in `out.c`.
 template <typename T>
 int spgemm_t(int device, const Operand &A, const Operand &B, int route, uint32_t cap, hipStream_t st, Product &out) {
-    const uint64_t m = A.nrows;
+    const uint64_t m = A.nmajor;
     DevBuf ub, tier, cnt, off, list, ctr;
     SPAL_HIP_TRY(ub.alloc(m * 4));
     SPAL_HIP_TRY(tier.alloc(m));
@@ -397,7 +372,8 @@ int spgemm_t(int device, const Operand &A, const Operand &B, int route, uint32_t
     // large tier: expand, two stable transposes (each row sorted by column, equal columns in k order), runs counted
     const uint32_t nL = h.tier[6];
     const uint32_t *lrows = lst + start[6];
-    DevBuf sptr, rp2, ci2, va2;
+    DevBuf sptr;
+    OpArrays sorted;   // the expansion, every row sorted by column
     if (nL) {
         const uint64_t L = h.large_products;
         {
@@ -414,20 +390,12 @@ int spgemm_t(int device, const Operand &A, const Operand &B, int route, uint32_t
             hipLaunchKernelGGL((spgemm_expand<T>), dim3(nL), dim3(256), 0, st, lrows, sptr.as<uint32_t>(), A.ptr, A.ind,
                                (const T *)A.val, B.ptr, B.ind, (const T *)B.val, sci.as<uint32_t>(), sv.as<T>());
             SPAL_HIP_TRY(hipGetLastError());
-            uint32_t *tp = nullptr, *ti = nullptr;
-            void *tv = nullptr;
-            uint64_t tcap = 0;
-            SPAL_TRY(transpose_device(device, (int)sizeof(T), nL, B.ncols, L, sptr.as<uint32_t>(), sci.as<uint32_t>(),
-                                      sv.p, st, &tp, &ti, &tv, &tcap));
-            DevBuf bp, bi, bv;   // by column
-            bp.p = tp; bi.p = ti; bv.p = tv;
-            uint32_t *rp = nullptr, *ri = nullptr;
-            void *rv = nullptr;
-            SPAL_TRY(transpose_device(device, (int)sizeof(T), B.ncols, nL, L, bp.as<uint32_t>(), bi.as<uint32_t>(), bv.p,
-                                      st, &rp, &ri, &rv, &tcap));
-            rp2.p = rp; ci2.p = ri; va2.p = rv;
+            OpArrays bycol;
+            SPAL_TRY(transpose_device(device, (int)sizeof(T), nL, B.nminor, L, sptr.as<uint32_t>(), sci.as<uint32_t>(),
+                                      sv.p, st, bycol));
+            SPAL_TRY(transpose_device(device, (int)sizeof(T), B.nminor, nL, L, bycol.ptr, bycol.ind, bycol.val, st, sorted));
         }
-        hipLaunchKernelGGL(spgemm_run_count, dim3(nL), dim3(256), 0, st, lrows, rp2.as<uint32_t>(), ci2.as<uint32_t>(), d_cnt);
+        hipLaunchKernelGGL(spgemm_run_count, dim3(nL), dim3(256), 0, st, lrows, sorted.ptr, sorted.ind, d_cnt);
         SPAL_HIP_TRY(hipGetLastError());
     }
     // offsets of C's rows; nnz(C) back to the host (the size of C's arrays)
@@ -438,25 +406,15 @@ int spgemm_t(int device, const Operand &A, const Operand &B, int route, uint32_t
     if (nnz > kMaxEntries)
         return fail(SPAL_ERR_UNSUPPORTED, "spal_csr_mul: the product has %llu entries, more than 32-bit device offsets address",
                     nnz);
-    DevBuf crp, cci, cva;
-    const uint64_t cap_entries = nnz + kStreamPad;
-    SPAL_HIP_TRY(crp.alloc((m + 1) * 4));
-    SPAL_HIP_TRY(cci.alloc(cap_entries * 4));
-    SPAL_HIP_TRY(cva.alloc(cap_entries * sizeof(T)));
-    SPAL_HIP_TRY(hipMemsetAsync((char *)cci.p + nnz * 4, 0, kStreamPad * 4, st));
-    SPAL_HIP_TRY(hipMemsetAsync((char *)cva.p + nnz * sizeof(T), 0, kStreamPad * sizeof(T), st));
-    hipLaunchKernelGGL(spgemm_rowptr32, dim3(grid_of(m + 1, 256)), dim3(256), 0, st, d_off, m + 1, crp.as<uint32_t>());
-    launch_lds_tiers<T>(true, lst, start, h.tier, A, B, d_cnt, d_off, cci.as<uint32_t>(), cva.as<T>(), st);
+    OpArrays &c = out.c;
+    SPAL_TRY(c.alloc(m, nnz, sizeof(T), st));
+    hipLaunchKernelGGL(spgemm_rowptr32, dim3(grid_of(m + 1, 256)), dim3(256), 0, st, d_off, m + 1, c.ptr);
+    launch_lds_tiers<T>(true, lst, start, h.tier, A, B, d_cnt, d_off, c.ind, (T *)c.val, st);
     if (nL)
-        hipLaunchKernelGGL((spgemm_run_fill<T>), dim3(nL), dim3(256), 0, st, lrows, rp2.as<uint32_t>(), ci2.as<uint32_t>(),
-                           va2.as<T>(), d_off, cci.as<uint32_t>(), cva.as<T>());
+        hipLaunchKernelGGL((spgemm_run_fill<T>), dim3(nL), dim3(256), 0, st, lrows, sorted.ptr, sorted.ind,
+                           (const T *)sorted.val, d_off, c.ind, (T *)c.val);
     SPAL_HIP_TRY(hipGetLastError());
     SPAL_HIP_TRY(hipStreamSynchronize(st));
-    out.nnz = nnz;
-    out.cap = cap_entries;
-    out.ptr = (uint32_t *)crp.release();
-    out.ind = (uint32_t *)cci.release();
-    out.val = cva.release();
     return SPAL_OK;
 }
 
@@ -478,49 +436,57 @@ std::string info_json(const Product &r, int route, double plan_ms, double ms) {
              "{\"route\": %d, \"tier_rows\": {%s}, \"products\": %llu, \"large_products\": %llu, \"nnz\": %llu, "
              "\"plan_ms\": %.3f, \"call_ms\": %.3f}",
              route, tiers.c_str(), (unsigned long long)r.products, (unsigned long long)r.large_products,
-             (unsigned long long)r.nnz, plan_ms, ms);
+             (unsigned long long)r.c.nnz, plan_ms, ms);
     return buf;
 }
 
-double ms_since(std::chrono::steady_clock::time_point t0) {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+// assert_eq!(self.ncols(), rhs.nrows()) of src/csr/ops/mul.rs:9 and src/csc/ops/mul.rs:9, then what the device needs
+template <typename H>
+int check_mul(const char *fn, const H *a, const H *b, H **out) {
+    if (!a || !b || !out) return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: null argument", fn);
+    *out = nullptr;
+    if (a->ncols != b->nrows)
+        return fail(SPAL_ERR_INVALID_ARGUMENT, "assertion failed: ncols == rhs.nrows (left: %llu, right: %llu)",
+                    (unsigned long long)a->ncols, (unsigned long long)b->nrows);
+    return check_same_device_and_dtype(fn, a, b);
 }
 
-void free_product(Product &r) {
-    (void)dev_free(r.ptr);
-    (void)dev_free(r.ind);
-    (void)dev_free(r.val);
-    r.ptr = r.ind = nullptr;
-    r.val = nullptr;
+// C = a * b as the product L * R of the handles' arrays, into a handle of their type
+template <typename H>
+int product(const H *a, const H *b, const Operand &L, const Operand &R, void *stream, H **out) {
+    DeviceGuard guard(a->device);
+    if (guard.status != SPAL_OK) return guard.status;
+    const auto t0 = std::chrono::steady_clock::now();
+    Product r;
+    SPAL_TRY(spgemm(a->device, a->elem_size, L, R, a->ops.spgemm_route, a->ops.spgemm_lds_cap, (hipStream_t)stream, r));
+    const auto tp = std::chrono::steady_clock::now();
+    // CSR: eager plan, like a handle built from host arrays.  This began as a workaround: a lazily planned handle reached
+    // csr_blockwin_or_split re-entrantly (csr_form1_faster -> csr_launch -> csr_ensure_plan under the lock it held).  That
+    // is fixed -- the planner launches through csr_launch_planned -- and eager planning stays as a choice: the plan's
+    // cost shows as plan_ms, and the first product of the result pays nothing.
+    SPAL_TRY(r.c.adopt(a->device, a->elem_size, a->nrows, b->ncols, out, true, false));
+    (*out)->ops.spgemm_info = info_json(r, a->ops.spgemm_route, ms_since(tp), ms_since(t0));
+    return SPAL_OK;
 }
 
 }  // namespace
 
-int spgemm_option(const char *key, int64_t value, int *route, int64_t *lds_cap, int *status) {
+int spgemm_option(const char *key, int64_t value, OpState &s, int *status) {
     if (!strcmp(key, "spgemm_route")) {
         *status = (value < 0 || value > 2)
                       ? fail(SPAL_ERR_INVALID_ARGUMENT, "spgemm_route must be 0 (auto), 1 (LDS tiers wherever they fit) or 2 (large-row tier)")
                       : SPAL_OK;
-        if (*status == SPAL_OK) *route = (int)value;
+        if (*status == SPAL_OK) s.spgemm_route = (int)value;
         return 1;
     }
     if (!strcmp(key, "spgemm_lds_cap")) {
         *status = (value < 0 || value > (int64_t)kMaxCap)
                       ? fail(SPAL_ERR_INVALID_ARGUMENT, "spgemm_lds_cap must be 0 (default) or in [1, %u]", kMaxCap)
                       : SPAL_OK;
-        if (*status == SPAL_OK) *lds_cap = value;
+        if (*status == SPAL_OK) s.spgemm_lds_cap = value;
         return 1;
     }
     return 0;
-}
-
-int spgemm_describe_append(char *buf, size_t buf_len, const std::string &info) {
-    if (info.empty()) return SPAL_OK;
-    const size_t len = strnlen(buf, buf_len);
-    if (len == 0 || buf[len - 1] != '}' || len + info.size() + 16 > buf_len)
-        return fail(SPAL_ERR_INVALID_ARGUMENT, "describe: buffer of %zu bytes too small", buf_len);
-    snprintf(buf + len - 1, buf_len - (len - 1), ", \"spgemm\": %s}", info.c_str());
-    return SPAL_OK;
 }
 
 }  // namespace spal
@@ -530,67 +496,17 @@ using namespace spal;
 extern "C" {
 
 int spal_csr_mul(spal_csr_t a, spal_csr_t b, void *stream, spal_csr_t *out) {
-    if (!a || !b || !out) return fail(SPAL_ERR_INVALID_ARGUMENT, "spal_csr_mul: null argument");
-    *out = nullptr;
-    if (a->ncols != b->nrows)   // assert_eq!(self.ncols(), rhs.nrows()), src/csr/ops/mul.rs:9
-        return fail(SPAL_ERR_INVALID_ARGUMENT, "assertion failed: ncols == rhs.nrows (left: %llu, right: %llu)",
-                    (unsigned long long)a->ncols, (unsigned long long)b->nrows);
-    if (a->device != b->device)
-        return fail(SPAL_ERR_INVALID_ARGUMENT, "spal_csr_mul: operands on devices %d and %d", a->device, b->device);
-    if (a->elem_size != b->elem_size)
-        return fail(SPAL_ERR_INVALID_ARGUMENT, "spal_csr_mul: operands of element sizes %d and %d", a->elem_size, b->elem_size);
-    if (!a->parts.empty() || !b->parts.empty())
-        return fail(SPAL_ERR_UNSUPPORTED, "spal_csr_mul: an operand of more than 2^32 - 65537 entries (row blocks)");
-    DeviceGuard guard(a->device);
-    if (guard.status != SPAL_OK) return guard.status;
-    const auto t0 = std::chrono::steady_clock::now();
-    const Operand A{a->nrows, a->ncols, a->d_rowptr, a->d_colind, a->d_values};
-    const Operand B{b->nrows, b->ncols, b->d_rowptr, b->d_colind, b->d_values};
-    Product r;
-    SPAL_TRY(spgemm(a->device, a->elem_size, A, B, a->spgemm_route, a->spgemm_lds_cap, (hipStream_t)stream, r));
-    const auto tp = std::chrono::steady_clock::now();
-    // eager plan, like a handle built from host arrays.  This began as a workaround: a lazily planned handle reached
-    // csr_blockwin_or_split re-entrantly (csr_form1_faster -> csr_launch -> csr_ensure_plan under the lock it held).  That
-    // is fixed -- the planner launches through csr_launch_planned -- and eager planning stays as a choice: the plan's
-    // cost shows as plan_ms, and the first product of the result pays nothing.
-    int st = csr_adopt_device(a->device, a->elem_size, a->nrows, b->ncols, r.nnz, r.cap, r.ptr, r.ind, r.val, out,
-                              true, false);
-    if (st != SPAL_OK) {
-        free_product(r);
-        return st;
-    }
-    (*out)->spgemm_info = info_json(r, a->spgemm_route, ms_since(tp), ms_since(t0));
-    return SPAL_OK;
+    SPAL_TRY(check_mul("spal_csr_mul", a, b, out));
+    if (row_blocks(a) || row_blocks(b)) return refuse_row_blocks("spal_csr_mul");
+    return product(a, b, operand_of(a), operand_of(b), stream, out);
 }
 
 // `impl Mul for &CscMatrix<T>`: the CSC arrays of A are the CSR arrays of A^T and (AB)^T = B^T A^T, so C's CSC arrays are
 // the CSR product of lhs = B's arrays (p x n) and rhs = A's arrays (n x m).  k runs in the same order.  The reference
 // sizes one workspace by the wrong extent here; this is the defined product where it would panic.
 int spal_csc_mul(spal_csc_t a, spal_csc_t b, void *stream, spal_csc_t *out) {
-    if (!a || !b || !out) return fail(SPAL_ERR_INVALID_ARGUMENT, "spal_csc_mul: null argument");
-    *out = nullptr;
-    if (a->ncols != b->nrows)   // src/csc/ops/mul.rs:9
-        return fail(SPAL_ERR_INVALID_ARGUMENT, "assertion failed: ncols == rhs.nrows (left: %llu, right: %llu)",
-                    (unsigned long long)a->ncols, (unsigned long long)b->nrows);
-    if (a->device != b->device)
-        return fail(SPAL_ERR_INVALID_ARGUMENT, "spal_csc_mul: operands on devices %d and %d", a->device, b->device);
-    if (a->elem_size != b->elem_size)
-        return fail(SPAL_ERR_INVALID_ARGUMENT, "spal_csc_mul: operands of element sizes %d and %d", a->elem_size, b->elem_size);
-    DeviceGuard guard(a->device);
-    if (guard.status != SPAL_OK) return guard.status;
-    const auto t0 = std::chrono::steady_clock::now();
-    const Operand L{b->ncols, b->nrows, b->d_colptr, b->d_rowind, b->d_values};   // B^T, p x n
-    const Operand R{a->ncols, a->nrows, a->d_colptr, a->d_rowind, a->d_values};   // A^T, n x m
-    Product r;
-    SPAL_TRY(spgemm(a->device, a->elem_size, L, R, a->spgemm_route, a->spgemm_lds_cap, (hipStream_t)stream, r));
-    const auto tp = std::chrono::steady_clock::now();
-    int st = csc_adopt_device(a->device, a->elem_size, a->nrows, b->ncols, r.nnz, r.cap, r.ptr, r.ind, r.val, out);
-    if (st != SPAL_OK) {
-        free_product(r);
-        return st;
-    }
-    (*out)->spgemm_info = info_json(r, a->spgemm_route, ms_since(tp), ms_since(t0));
-    return SPAL_OK;
+    SPAL_TRY(check_mul("spal_csc_mul", a, b, out));
+    return product(a, b, operand_of(b), operand_of(a), stream, out);   // B^T (p x n) times A^T (n x m)
 }
 
 }  // extern "C"

@@ -19,7 +19,7 @@
 //     split, only given to other lanes.
 // Nothing is read from CsrPlan and nothing is written to the handle or to scratch memory: the launch is safe on a
 // handle whose SpMV plan is still pending, under graph capture, and from several threads at once.
-#include "spal_internal.hpp"
+#include "spal_ops.hpp"
 
 #pragma clang fp contract(off)
 
@@ -254,8 +254,7 @@ template <typename T>
 int check_common(const char *fn, const void *a, int elem_size, uint64_t k, const void *x, uint64_t ldx, const void *y,
                  uint64_t ldy) {
     if (!a) return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: handle is NULL", fn);
-    if (elem_size != (int)sizeof(T))
-        return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: handle holds %s values", fn, elem_size == 8 ? "f64" : "f32");
+    SPAL_TRY(check_dtype<T>(fn, elem_size));
     if (!x || !y) return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: null block of vectors", fn);
     if (k == 0) return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: k = 0 (X and Y need at least one column)", fn);
     if (k > 0xffffffffull) return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: k = %llu does not fit 32 bits", fn, (unsigned long long)k);
@@ -294,42 +293,24 @@ int spmm_host(spal_csr *a, int tile, hipStream_t st, uint64_t k, const T *x, uin
     return SPAL_OK;
 }
 
-template <typename T>
-int csr_spmm_host(spal_csr *a, uint64_t k, const T *x, uint64_t ldx, uint64_t x_rows, T *y, uint64_t ldy,
-                  uint64_t y_rows) {
-    SPAL_TRY(check_common<T>("spal_csr_spmm", a, a ? a->elem_size : 0, k, x, ldx, y, ldy));
-    SPAL_TRY(check_rows("spal_csr_spmm", a->nrows, a->ncols, x_rows, y_rows));
+// The entry points, for either handle type: the handle's own lock, stream and option; the product on solve_handle(a).
+template <typename T, typename H>
+int spmm_host_entry(const char *fn, H *a, uint64_t k, const T *x, uint64_t ldx, uint64_t x_rows, T *y, uint64_t ldy,
+                    uint64_t y_rows) {
+    SPAL_TRY(check_common<T>(fn, a, a ? a->elem_size : 0, k, x, ldx, y, ldy));
+    SPAL_TRY(check_rows(fn, a->nrows, a->ncols, x_rows, y_rows));
     DeviceGuard guard(a->device);
     if (guard.status != SPAL_OK) return guard.status;
     std::lock_guard<std::mutex> lock(a->mu);
-    return spmm_host<T>(a, a->spmm_tile, a->stream, k, x, ldx, y, ldy);
+    return spmm_host<T>(solve_handle(a), a->ops.spmm_tile, a->stream, k, x, ldx, y, ldy);
 }
 
-template <typename T>
-int csr_spmm_dev(spal_csr *a, uint64_t k, const T *x, uint64_t ldx, T *y, uint64_t ldy, void *stream) {
-    SPAL_TRY(check_common<T>("spal_csr_spmm_dev", a, a ? a->elem_size : 0, k, x, ldx, y, ldy));
+template <typename T, typename H>
+int spmm_dev_entry(const char *fn, H *a, uint64_t k, const T *x, uint64_t ldx, T *y, uint64_t ldy, void *stream) {
+    SPAL_TRY(check_common<T>(fn, a, a ? a->elem_size : 0, k, x, ldx, y, ldy));
     DeviceGuard guard(a->device);
     if (guard.status != SPAL_OK) return guard.status;
-    return spmm_launch(a, a->spmm_tile, k, x, ldx, y, ldy, (hipStream_t)stream);
-}
-
-template <typename T>
-int csc_spmm_host(spal_csc *a, uint64_t k, const T *x, uint64_t ldx, uint64_t x_rows, T *y, uint64_t ldy,
-                  uint64_t y_rows) {
-    SPAL_TRY(check_common<T>("spal_csc_spmm", a, a ? a->elem_size : 0, k, x, ldx, y, ldy));
-    SPAL_TRY(check_rows("spal_csc_spmm", a->nrows, a->ncols, x_rows, y_rows));
-    DeviceGuard guard(a->device);
-    if (guard.status != SPAL_OK) return guard.status;
-    std::lock_guard<std::mutex> lock(a->mu);
-    return spmm_host<T>(a->as_csr, a->spmm_tile, a->stream, k, x, ldx, y, ldy);
-}
-
-template <typename T>
-int csc_spmm_dev(spal_csc *a, uint64_t k, const T *x, uint64_t ldx, T *y, uint64_t ldy, void *stream) {
-    SPAL_TRY(check_common<T>("spal_csc_spmm_dev", a, a ? a->elem_size : 0, k, x, ldx, y, ldy));
-    DeviceGuard guard(a->device);
-    if (guard.status != SPAL_OK) return guard.status;
-    return spmm_launch(a->as_csr, a->spmm_tile, k, x, ldx, y, ldy, (hipStream_t)stream);
+    return spmm_launch(solve_handle(a), a->ops.spmm_tile, k, x, ldx, y, ldy, (hipStream_t)stream);
 }
 
 }  // namespace
@@ -343,12 +324,12 @@ int spmm_launch(spal_csr *a, int tile, uint64_t k, const void *x_dev, uint64_t l
     return SPAL_OK;
 }
 
-int spmm_option(const char *key, int64_t value, int *tile, int *status) {
+int spmm_option(const char *key, int64_t value, OpState &s, int *status) {
     if (strcmp(key, "spmm_tile")) return 0;
     *status = (value == 0 || tile_instantiated(value))
                   ? SPAL_OK
                   : fail(SPAL_ERR_INVALID_ARGUMENT, "spmm_tile must be 0 (automatic) or one of 1, 2, 4, 8, 16, 32");
-    if (*status == SPAL_OK) *tile = (int)value;
+    if (*status == SPAL_OK) s.spmm_tile = (int)value;
     return 1;
 }
 
@@ -365,14 +346,10 @@ int spmm_describe_append(char *buf, size_t buf_len, const spal_csr *a) {
     const spal_csr *first = a->parts.empty() ? a : a->parts[0];
     char info[256];
     snprintf(info, sizeof info,
-             ", \"spmm\": {\"tile\": %u, \"k\": %u, \"column_tiles\": %u, \"tile_rows\": %u, \"strip_entries\": %u, "
-             "\"long_row_threshold\": %u, \"long_rows\": %llu}}",
+             "{\"tile\": %u, \"k\": %u, \"column_tiles\": %u, \"tile_rows\": %u, \"strip_entries\": %u, "
+             "\"long_row_threshold\": %u, \"long_rows\": %llu}",
              tile, k, (k + tile - 1) / tile, tile_rows(first), kCap, kLong, (unsigned long long)nlong);
-    const size_t len = strnlen(buf, buf_len);
-    if (len == 0 || buf[len - 1] != '}' || len + strlen(info) + 1 > buf_len)
-        return fail(SPAL_ERR_INVALID_ARGUMENT, "describe: buffer of %zu bytes too small", buf_len);
-    snprintf(buf + len - 1, buf_len - (len - 1), "%s", info);
-    return SPAL_OK;
+    return describe_append(buf, buf_len, "spmm", info);
 }
 
 }  // namespace spal
@@ -383,35 +360,35 @@ extern "C" {
 
 int spal_csr_spmm_f64(spal_csr_t a, uint64_t k, const double *x, uint64_t ldx, uint64_t x_rows, double *y, uint64_t ldy,
                       uint64_t y_rows) {
-    return csr_spmm_host<double>(a, k, x, ldx, x_rows, y, ldy, y_rows);
+    return spmm_host_entry<double>("spal_csr_spmm", a, k, x, ldx, x_rows, y, ldy, y_rows);
 }
 int spal_csr_spmm_f32(spal_csr_t a, uint64_t k, const float *x, uint64_t ldx, uint64_t x_rows, float *y, uint64_t ldy,
                       uint64_t y_rows) {
-    return csr_spmm_host<float>(a, k, x, ldx, x_rows, y, ldy, y_rows);
+    return spmm_host_entry<float>("spal_csr_spmm", a, k, x, ldx, x_rows, y, ldy, y_rows);
 }
 int spal_csr_spmm_dev_f64(spal_csr_t a, uint64_t k, const double *x_dev, uint64_t ldx, double *y_dev, uint64_t ldy,
                           void *stream) {
-    return csr_spmm_dev<double>(a, k, x_dev, ldx, y_dev, ldy, stream);
+    return spmm_dev_entry<double>("spal_csr_spmm_dev", a, k, x_dev, ldx, y_dev, ldy, stream);
 }
 int spal_csr_spmm_dev_f32(spal_csr_t a, uint64_t k, const float *x_dev, uint64_t ldx, float *y_dev, uint64_t ldy,
                           void *stream) {
-    return csr_spmm_dev<float>(a, k, x_dev, ldx, y_dev, ldy, stream);
+    return spmm_dev_entry<float>("spal_csr_spmm_dev", a, k, x_dev, ldx, y_dev, ldy, stream);
 }
 int spal_csc_spmm_f64(spal_csc_t a, uint64_t k, const double *x, uint64_t ldx, uint64_t x_rows, double *y, uint64_t ldy,
                       uint64_t y_rows) {
-    return csc_spmm_host<double>(a, k, x, ldx, x_rows, y, ldy, y_rows);
+    return spmm_host_entry<double>("spal_csc_spmm", a, k, x, ldx, x_rows, y, ldy, y_rows);
 }
 int spal_csc_spmm_f32(spal_csc_t a, uint64_t k, const float *x, uint64_t ldx, uint64_t x_rows, float *y, uint64_t ldy,
                       uint64_t y_rows) {
-    return csc_spmm_host<float>(a, k, x, ldx, x_rows, y, ldy, y_rows);
+    return spmm_host_entry<float>("spal_csc_spmm", a, k, x, ldx, x_rows, y, ldy, y_rows);
 }
 int spal_csc_spmm_dev_f64(spal_csc_t a, uint64_t k, const double *x_dev, uint64_t ldx, double *y_dev, uint64_t ldy,
                           void *stream) {
-    return csc_spmm_dev<double>(a, k, x_dev, ldx, y_dev, ldy, stream);
+    return spmm_dev_entry<double>("spal_csc_spmm_dev", a, k, x_dev, ldx, y_dev, ldy, stream);
 }
 int spal_csc_spmm_dev_f32(spal_csc_t a, uint64_t k, const float *x_dev, uint64_t ldx, float *y_dev, uint64_t ldy,
                           void *stream) {
-    return csc_spmm_dev<float>(a, k, x_dev, ldx, y_dev, ldy, stream);
+    return spmm_dev_entry<float>("spal_csc_spmm_dev", a, k, x_dev, ldx, y_dev, ldy, stream);
 }
 
 }  // extern "C"

@@ -21,18 +21,12 @@ __global__ __launch_bounds__(256) void expand_major(const uint32_t *__restrict__
 }
 
 template <typename T>
-static int transpose_t(uint64_t nmajor, uint64_t nminor, uint64_t nnz,
-                       const uint32_t *d_ptr, const uint32_t *d_ind, const T *d_val, hipStream_t st,
-                       uint32_t **out_ptr, uint32_t **out_ind, T **out_val, uint64_t *out_cap) {
-    const uint64_t cap = nnz + kStreamPad;  // the stream kernel's over-read margin
-    DevBuf optr, oind, oval, work, major;   // (work, major: scratch, freed on return -- behind the synchronise below)
-    SPAL_HIP_TRY(optr.alloc((nminor + 1) * 4));
-    SPAL_HIP_TRY(oind.alloc(cap * 4));
-    SPAL_HIP_TRY(oval.alloc(cap * sizeof(T)));
-    SPAL_HIP_TRY(hipMemsetAsync((char *)oind.p + nnz * 4, 0, kStreamPad * 4, st));
-    SPAL_HIP_TRY(hipMemsetAsync((char *)oval.p + nnz * sizeof(T), 0, kStreamPad * sizeof(T), st));
+static int transpose_t(uint64_t nmajor, uint64_t nminor, uint64_t nnz, const uint32_t *d_ptr, const uint32_t *d_ind,
+                       const T *d_val, hipStream_t st, OpArrays &out) {
+    DevBuf work, major;   // (scratch, freed on return -- behind the synchronise below)
+    SPAL_TRY(out.alloc(nminor, nnz, sizeof(T), st));
     if (nnz == 0) {
-        SPAL_HIP_TRY(hipMemsetAsync(optr.p, 0, (nminor + 1) * 4, st));
+        SPAL_HIP_TRY(hipMemsetAsync(out.ptr, 0, (nminor + 1) * 4, st));
     } else {
         const CooWorkspace ws = coo_workspace_layout(nnz, nminor, sizeof(T));
         SPAL_HIP_TRY(work.alloc(ws.bytes));
@@ -43,34 +37,19 @@ static int transpose_t(uint64_t nmajor, uint64_t nminor, uint64_t nnz,
         int cur = 0;
         SPAL_HIP_TRY(radix_sort_bits<T>(sb, nnz, 0, bits_for(nminor), cur, st, d_ind,
                                         major.as<uint32_t>(), d_val));
-        launch_row_starts(sb.key[cur], (uint32_t)nnz, (uint32_t)nminor, optr.as<uint32_t>(), st);
-        SPAL_HIP_TRY(hipMemcpyAsync(oind.p, sb.aux[cur], nnz * 4, hipMemcpyDeviceToDevice, st));
-        SPAL_HIP_TRY(hipMemcpyAsync(oval.p, sb.val[cur], nnz * sizeof(T), hipMemcpyDeviceToDevice, st));
+        launch_row_starts(sb.key[cur], (uint32_t)nnz, (uint32_t)nminor, out.ptr, st);
+        SPAL_HIP_TRY(hipMemcpyAsync(out.ind, sb.aux[cur], nnz * 4, hipMemcpyDeviceToDevice, st));
+        SPAL_HIP_TRY(hipMemcpyAsync(out.val, sb.val[cur], nnz * sizeof(T), hipMemcpyDeviceToDevice, st));
         SPAL_HIP_TRY(hipGetLastError());
     }
     SPAL_HIP_TRY(hipStreamSynchronize(st));
-    *out_ptr = (uint32_t *)optr.release();
-    *out_ind = (uint32_t *)oind.release();
-    *out_val = (T *)oval.release();
-    *out_cap = cap;
     return SPAL_OK;
 }
 
-int transpose_device(int device, int elem_size, uint64_t nmajor, uint64_t nminor, uint64_t nnz,
-                     const uint32_t *d_ptr, const uint32_t *d_ind, const void *d_val, hipStream_t st,
-                     uint32_t **out_ptr, uint32_t **out_ind, void **out_val, uint64_t *out_cap) {
-    if (elem_size == 8) {
-        double *v = nullptr;
-        SPAL_TRY(transpose_t<double>(nmajor, nminor, nnz, d_ptr, d_ind, (const double *)d_val, st,
-                                     out_ptr, out_ind, &v, out_cap));
-        *out_val = v;
-    } else {
-        float *v = nullptr;
-        SPAL_TRY(transpose_t<float>(nmajor, nminor, nnz, d_ptr, d_ind, (const float *)d_val, st,
-                                    out_ptr, out_ind, &v, out_cap));
-        *out_val = v;
-    }
-    return SPAL_OK;
+int transpose_device(int device, int elem_size, uint64_t nmajor, uint64_t nminor, uint64_t nnz, const uint32_t *d_ptr,
+                     const uint32_t *d_ind, const void *d_val, hipStream_t st, OpArrays &out) {
+    return elem_size == 8 ? transpose_t<double>(nmajor, nminor, nnz, d_ptr, d_ind, (const double *)d_val, st, out)
+                          : transpose_t<float>(nmajor, nminor, nnz, d_ptr, d_ind, (const float *)d_val, st, out);
 }
 
 }  // namespace spal

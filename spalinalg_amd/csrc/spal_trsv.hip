@@ -17,7 +17,7 @@
 // Maximal runs of levels at most "trsv_chain_rows" wide are one chain launch; every wider level is a level launch.  The
 // list is recorded once; a solve after that allocates nothing and synchronises nothing.
 // A long row is walked by its one thread, kBatch gathers in flight at a time, the subtractions in stored order.
-#include "spal_internal.hpp"
+#include "spal_ops.hpp"
 
 #include <chrono>
 
@@ -230,13 +230,6 @@ int solve_locked(const char *fn, spal_csr *a, int uplo, int unit_diag, const T *
 }
 
 template <typename T>
-int check_dtype(const char *fn, int elem_size) {
-    if (elem_size != (int)sizeof(T))
-        return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: handle holds %s values", fn, elem_size == 8 ? "f64" : "f32");
-    return SPAL_OK;
-}
-
-template <typename T>
 int solve_host(const char *fn, spal_csr *a, int uplo, int unit_diag, const T *b, uint64_t b_len, T *x, uint64_t x_len) {
     if (!b || !x) return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: null vector", fn);
     if (b_len != a->nrows || x_len != a->nrows)
@@ -252,59 +245,40 @@ int solve_host(const char *fn, spal_csr *a, int uplo, int unit_diag, const T *b,
     return SPAL_OK;
 }
 
-template <typename T>
-int csr_trsv_host(spal_csr *a, int uplo, int unit_diag, const T *b, uint64_t b_len, T *x, uint64_t x_len) {
-    const char *fn = "spal_csr_trsv";
+// The entry points, for either handle type: the solve runs on solve_handle(a), under its lock.
+template <typename T, typename H>
+int trsv_host(const char *fn, H *a, int uplo, int unit_diag, const T *b, uint64_t b_len, T *x, uint64_t x_len) {
     if (!a) return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: handle is NULL", fn);
     SPAL_TRY(check_dtype<T>(fn, a->elem_size));
     SPAL_TRY(check_flags(fn, uplo, unit_diag));
     DeviceGuard guard(a->device);
     if (guard.status != SPAL_OK) return guard.status;
-    return solve_host<T>(fn, a, uplo, unit_diag, b, b_len, x, x_len);
+    return solve_host<T>(fn, solve_handle(a), uplo, unit_diag, b, b_len, x, x_len);
 }
 
-template <typename T>
-int csr_trsv_dev(spal_csr *a, int uplo, int unit_diag, const T *b, T *x, void *stream) {
-    const char *fn = "spal_csr_trsv_dev";
+template <typename T, typename H>
+int trsv_dev(const char *fn, H *a, int uplo, int unit_diag, const T *b, T *x, void *stream) {
     if (!a) return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: handle is NULL", fn);
     SPAL_TRY(check_dtype<T>(fn, a->elem_size));
     SPAL_TRY(check_flags(fn, uplo, unit_diag));
     if (!b || !x) return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: null vector", fn);
     DeviceGuard guard(a->device);
     if (guard.status != SPAL_OK) return guard.status;
-    std::lock_guard<std::mutex> lock(a->mu);
-    return solve_locked<T>(fn, a, uplo, unit_diag, b, x, (hipStream_t)stream);
+    spal_csr *s = solve_handle(a);
+    std::lock_guard<std::mutex> lock(s->mu);
+    return solve_locked<T>(fn, s, uplo, unit_diag, b, x, (hipStream_t)stream);
 }
 
-int csr_trsv_analyse(const char *fn, spal_csr *a, int uplo, int unit_diag, void *stream) {
+template <typename H>
+int trsv_analyse(const char *fn, H *a, int uplo, int unit_diag, void *stream) {
+    if (!a) return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: handle is NULL", fn);
+    DeviceGuard guard(a->device);
+    if (guard.status != SPAL_OK) return guard.status;
     SPAL_TRY(check_flags(fn, uplo, unit_diag));
-    std::lock_guard<std::mutex> lock(a->mu);
+    spal_csr *s = solve_handle(a);
+    std::lock_guard<std::mutex> lock(s->mu);
     TrsvPlan *p = nullptr;
-    return plan_get(fn, a, uplo, unit_diag, (hipStream_t)stream, &p);
-}
-
-template <typename T>
-int csc_trsv_host(spal_csc *a, int uplo, int unit_diag, const T *b, uint64_t b_len, T *x, uint64_t x_len) {
-    const char *fn = "spal_csc_trsv";
-    if (!a) return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: handle is NULL", fn);
-    SPAL_TRY(check_dtype<T>(fn, a->elem_size));
-    SPAL_TRY(check_flags(fn, uplo, unit_diag));
-    DeviceGuard guard(a->device);
-    if (guard.status != SPAL_OK) return guard.status;
-    return solve_host<T>(fn, a->as_csr, uplo, unit_diag, b, b_len, x, x_len);
-}
-
-template <typename T>
-int csc_trsv_dev(spal_csc *a, int uplo, int unit_diag, const T *b, T *x, void *stream) {
-    const char *fn = "spal_csc_trsv_dev";
-    if (!a) return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: handle is NULL", fn);
-    SPAL_TRY(check_dtype<T>(fn, a->elem_size));
-    SPAL_TRY(check_flags(fn, uplo, unit_diag));
-    if (!b || !x) return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: null vector", fn);
-    DeviceGuard guard(a->device);
-    if (guard.status != SPAL_OK) return guard.status;
-    std::lock_guard<std::mutex> lock(a->as_csr->mu);
-    return solve_locked<T>(fn, a->as_csr, uplo, unit_diag, b, x, (hipStream_t)stream);
+    return plan_get(fn, s, uplo, unit_diag, (hipStream_t)stream, &p);
 }
 
 }  // namespace
@@ -341,7 +315,7 @@ int trsv_describe_append(char *buf, size_t buf_len, spal_csr *a) {
         std::lock_guard<std::mutex> lock(a->mu);
         if (!a->trsv[0] && !a->trsv[1]) return SPAL_OK;
         char part[384];
-        snprintf(part, sizeof part, ", \"trsv\": {\"analyses\": %d", a->trsv_analyses);
+        snprintf(part, sizeof part, "{\"analyses\": %d", a->trsv_analyses);
         info = part;
         for (int uplo = 0; uplo < 2; ++uplo) {
             const TrsvPlan *p = a->trsv[uplo];
@@ -354,13 +328,9 @@ int trsv_describe_append(char *buf, size_t buf_len, spal_csr *a) {
                      p->analysis_ms);
             info += part;
         }
-        info += "}}";
+        info += "}";
     }
-    const size_t len = strnlen(buf, buf_len);
-    if (len == 0 || buf[len - 1] != '}' || len + info.size() + 1 > buf_len)
-        return fail(SPAL_ERR_INVALID_ARGUMENT, "describe: buffer of %zu bytes too small", buf_len);
-    snprintf(buf + len - 1, buf_len - (len - 1), "%s", info.c_str());
-    return SPAL_OK;
+    return describe_append(buf, buf_len, "trsv", info);
 }
 
 }  // namespace spal
@@ -370,41 +340,35 @@ using namespace spal;
 extern "C" {
 
 int spal_csr_trsv_analyse(spal_csr_t a, int uplo, int unit_diag, void *stream) {
-    if (!a) return fail(SPAL_ERR_INVALID_ARGUMENT, "spal_csr_trsv_analyse: handle is NULL");
-    DeviceGuard guard(a->device);
-    if (guard.status != SPAL_OK) return guard.status;
-    return csr_trsv_analyse("spal_csr_trsv_analyse", a, uplo, unit_diag, stream);
+    return trsv_analyse("spal_csr_trsv_analyse", a, uplo, unit_diag, stream);
 }
 int spal_csr_trsv_f64(spal_csr_t a, int uplo, int unit_diag, const double *b, uint64_t b_len, double *x, uint64_t x_len) {
-    return csr_trsv_host<double>(a, uplo, unit_diag, b, b_len, x, x_len);
+    return trsv_host<double>("spal_csr_trsv", a, uplo, unit_diag, b, b_len, x, x_len);
 }
 int spal_csr_trsv_f32(spal_csr_t a, int uplo, int unit_diag, const float *b, uint64_t b_len, float *x, uint64_t x_len) {
-    return csr_trsv_host<float>(a, uplo, unit_diag, b, b_len, x, x_len);
+    return trsv_host<float>("spal_csr_trsv", a, uplo, unit_diag, b, b_len, x, x_len);
 }
 int spal_csr_trsv_dev_f64(spal_csr_t a, int uplo, int unit_diag, const double *b_dev, double *x_dev, void *stream) {
-    return csr_trsv_dev<double>(a, uplo, unit_diag, b_dev, x_dev, stream);
+    return trsv_dev<double>("spal_csr_trsv_dev", a, uplo, unit_diag, b_dev, x_dev, stream);
 }
 int spal_csr_trsv_dev_f32(spal_csr_t a, int uplo, int unit_diag, const float *b_dev, float *x_dev, void *stream) {
-    return csr_trsv_dev<float>(a, uplo, unit_diag, b_dev, x_dev, stream);
+    return trsv_dev<float>("spal_csr_trsv_dev", a, uplo, unit_diag, b_dev, x_dev, stream);
 }
 
 int spal_csc_trsv_analyse(spal_csc_t a, int uplo, int unit_diag, void *stream) {
-    if (!a) return fail(SPAL_ERR_INVALID_ARGUMENT, "spal_csc_trsv_analyse: handle is NULL");
-    DeviceGuard guard(a->device);
-    if (guard.status != SPAL_OK) return guard.status;
-    return csr_trsv_analyse("spal_csc_trsv_analyse", a->as_csr, uplo, unit_diag, stream);
+    return trsv_analyse("spal_csc_trsv_analyse", a, uplo, unit_diag, stream);
 }
 int spal_csc_trsv_f64(spal_csc_t a, int uplo, int unit_diag, const double *b, uint64_t b_len, double *x, uint64_t x_len) {
-    return csc_trsv_host<double>(a, uplo, unit_diag, b, b_len, x, x_len);
+    return trsv_host<double>("spal_csc_trsv", a, uplo, unit_diag, b, b_len, x, x_len);
 }
 int spal_csc_trsv_f32(spal_csc_t a, int uplo, int unit_diag, const float *b, uint64_t b_len, float *x, uint64_t x_len) {
-    return csc_trsv_host<float>(a, uplo, unit_diag, b, b_len, x, x_len);
+    return trsv_host<float>("spal_csc_trsv", a, uplo, unit_diag, b, b_len, x, x_len);
 }
 int spal_csc_trsv_dev_f64(spal_csc_t a, int uplo, int unit_diag, const double *b_dev, double *x_dev, void *stream) {
-    return csc_trsv_dev<double>(a, uplo, unit_diag, b_dev, x_dev, stream);
+    return trsv_dev<double>("spal_csc_trsv_dev", a, uplo, unit_diag, b_dev, x_dev, stream);
 }
 int spal_csc_trsv_dev_f32(spal_csc_t a, int uplo, int unit_diag, const float *b_dev, float *x_dev, void *stream) {
-    return csc_trsv_dev<float>(a, uplo, unit_diag, b_dev, x_dev, stream);
+    return trsv_dev<float>("spal_csc_trsv_dev", a, uplo, unit_diag, b_dev, x_dev, stream);
 }
 
 }  // extern "C"

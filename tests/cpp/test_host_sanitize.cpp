@@ -1,13 +1,16 @@
 // Host-only parts of libspal_hip (spal_host.cpp: the constructor invariants, the row
-// partitioner) and the bench input generators (spal_synth/spal_synth.cpp) under ASan +
+// partitioner, describe()'s append epilogue) and the bench input generators (spal_synth/spal_synth.cpp) under ASan +
 // UBSan, driven with edge-case and fuzzed inputs.  Built with g++ (no device code involved).
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <random>
+#include <string>
 #include <vector>
 
 #include "spal.h"
 #include "spal_synth.h"
+#include "../../spalinalg_amd/csrc/spal_internal.hpp"   // spal::describe_append
 
 static int failures = 0;
 #define CHECK(c) do { if (!(c)) { printf("FAIL %s:%d %s\n", __FILE__, __LINE__, #c); ++failures; } } while (0)
@@ -84,6 +87,34 @@ int main() {
         std::vector<float> x(12345);
         CHECK(spal_synth_vector_f32(x.size(), 3, x.data()) == 0);
         CHECK(spal_synth_vector_f64(0, 3, nullptr) == 0);
+    }
+    // describe_append: `, "<key>": <body>` before the closing brace, exact size bound, buf unchanged on failure
+    {
+        using spal::describe_append;
+        const std::string base = "{\"format\": \"csr\"}", body = "{\"tile\": 2048}";
+        const std::string expected = "{\"format\": \"csr\", \"spadd\": {\"tile\": 2048}}";
+        const char *too_small = "describe: buffer of";
+        char roomy[128];
+        strcpy(roomy, base.c_str());
+        CHECK(describe_append(roomy, sizeof roomy, "spadd", "") == SPAL_OK && roomy == base);            // empty body: no-op
+        char empty[8] = "";
+        CHECK(describe_append(empty, sizeof empty, "spadd", body) == SPAL_ERR_INVALID_ARGUMENT && empty[0] == 0);
+        CHECK(strstr(spal_last_error(), too_small) != nullptr);
+        char open_line[64] = "{\"format\": \"csr\"";                                                      // no closing brace
+        CHECK(describe_append(open_line, sizeof open_line, "spadd", body) == SPAL_ERR_INVALID_ARGUMENT);
+        CHECK(std::string(open_line) == "{\"format\": \"csr\"");
+        for (size_t len : {expected.size() + 1, expected.size()}) {   // heap blocks of the exact size: ASan sees an overrun
+            std::vector<char> heap(len);
+            memcpy(heap.data(), base.c_str(), base.size() + 1);
+            const int st = describe_append(heap.data(), heap.size(), "spadd", body);
+            if (len > expected.size()) CHECK(st == SPAL_OK && heap.data() == expected);
+            else CHECK(st == SPAL_ERR_INVALID_ARGUMENT && heap.data() == base && strstr(spal_last_error(), too_small) != nullptr);
+        }
+        CHECK(describe_append(roomy, sizeof roomy, "spadd", body) == SPAL_OK && roomy == expected);      // two in a row compose
+        CHECK(describe_append(roomy, sizeof roomy, "ilu0", "{\"levels\": 3}") == SPAL_OK);
+        CHECK(roomy == expected.substr(0, expected.size() - 1) + ", \"ilu0\": {\"levels\": 3}}");
+        char unterminated[4] = {'{', 'a', 'b', '}'};                                                      // no NUL inside buf_len
+        CHECK(describe_append(unterminated, sizeof unterminated, "k", "1") == SPAL_ERR_INVALID_ARGUMENT);
     }
     CHECK(spal_last_error() != nullptr && spal_version() != nullptr);
     printf("host sanitize: %d failure(s)\n", failures);

@@ -234,20 +234,21 @@ def test_zero_pivot_gives_the_reference_inf_and_nan(kind, dtype):
 # ---- refusals -------------------------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("kind", ["csr", "csc"])
-def test_refusals_leave_the_operand_usable_and_out_alone(kind):
+def test_refusals_leave_the_operand_usable_and_null_out(kind):
     make = csr if kind == "csr" else csc
     cls = sp.CsrMatrix if kind == "csr" else sp.CscMatrix
     fn = getattr(_ffi.lib(), f"spal_{kind}_ilu0")
     rect = cls(2, 3, [0, 1, 2] if kind == "csr" else [0, 1, 2, 2], [0, 1], np.array([1.0, 2.0])).device()
-    out = C.c_void_p(0x1234)
-    assert fn(rect._h, None, C.byref(out)) == _ffi.SPAL_ERR_INVALID_ARGUMENT and out.value == 0x1234
+    out = C.c_void_p(0x1234)     # (never dereferenced: a refused call nulls its out, as mul / add / sub / neg do)
+    assert fn(rect._h, None, C.byref(out)) == _ffi.SPAL_ERR_INVALID_ARGUMENT and out.value is None
     with pytest.raises(sp.Panic, match=r"not square \(2 x 3\)"):
         rect.ilu0()
     pattern = tr.drop_diagonal(tr.drop_diagonal(ir.full(900, 4, np.random.default_rng(18)), 700), 7)
     values, x = ir.fill(pattern, np.float64, np.random.default_rng(19))
     dev = make(pattern, values).device()
     y = dev.spmv(x)
-    assert fn(dev._h, None, C.byref(out)) == _ffi.SPAL_ERR_INVALID_ARGUMENT and out.value == 0x1234
+    out = C.c_void_p(0x1234)
+    assert fn(dev._h, None, C.byref(out)) == _ffi.SPAL_ERR_INVALID_ARGUMENT and out.value is None
     with pytest.raises(sp.Panic, match=f"spal_{kind}_ilu0: row 7 stores no diagonal entry"):
         dev.ilu0()
     assert fn(dev._h, None, None) == _ffi.SPAL_ERR_INVALID_ARGUMENT
