@@ -388,6 +388,106 @@ int spal_csc_trsv_dev_f32(spal_csc_t a, int uplo, int unit_diag, const float *b_
 int spal_csr_ilu0(spal_csr_t a, void *stream, spal_csr_t *out);
 int spal_csc_ilu0(spal_csc_t a, void *stream, spal_csc_t *out);
 
+/* ---- A x = b on the device: CG and BiCGStab, optionally preconditioned by an ILU(0) factor ------------
+ * Not in the reference.  As for the solve and the factorisation, the contract is a sequential text that the device
+ * reproduces bit for bit in f32 and f64; a Krylov loop can only keep that promise if its reductions have ONE order, so
+ * the dot product is defined first and everything below is built from it.
+ *
+ * dot(a, b, n), element type T:  p[i] = a[i] * b[i], each product rounded; the result is reduce(p).
+ * reduce(v), v of length m:  c = max(1, ceil(m / 1024)); v is padded with +0.0 to 1024 * c elements (the zeros ARE
+ *   added: a lone -0.0 gives +0.0, n = 0 gives +0.0); in every tile of 1024 consecutive elements, for h = 512, 256, ..,
+ *   1:  e[t] = e[t] + e[t + h] for t < h, and the tile's sum is e[0]; c == 1: that sum is the result, otherwise the
+ *   result is reduce(the c tile sums in order).  NaN propagates by IEEE.  The definition depends on n alone -- not on
+ *   a grid, a wave size or the number of launches.
+ * spal_dot_* restate it on the host (no device needed, like spal_trsv_levels); spal_dot_dev_* enqueue it on `stream`
+ * for device vectors and write the one result to out_dev: not synchronised (tile sums go through a scratch block of
+ * the runtime's stream-ordered allocator, taken and returned in stream order).
+ *
+ * The two loops.  All scalars are T.  thr = T(tol * tol) * bb with bb = dot(b, b) (tol is a double; tol * tol is formed
+ * in double and rounded to T once).  x holds x0 on entry and the result on exit.  M^-1 v with a factor handle m is
+ * trsv(m, lower, unit_diag = 1) followed by trsv(m, upper, unit_diag = 0); with m == NULL it is v itself.  Every
+ * product alpha * v[i] is rounded before the sum it enters (no FMA).
+ *   test (on rr):  rr <= thr: stop, reason 0;  else rr not finite: stop, reason 2;  else it == maxit: stop, reason 1.
+ *   Nothing is an error because of values: a breakdown (a zero denominator, an overflow) shows as reason 2.
+ *
+ *   SPAL_KRYLOV_CG
+ *     q = A x;  r[i] = b[i] - q[i];  rr = dot(r, r);  it = 0;  test
+ *     z = M^-1 r;  p = z;  rz = dot(r, z)
+ *     while not stopped:
+ *       q = A p;  alpha = rz / dot(p, q)
+ *       x[i] = x[i] + (alpha * p[i]);  r[i] = r[i] - (alpha * q[i]);  it += 1
+ *       rr = dot(r, r);  test
+ *       z = M^-1 r;  rz1 = dot(r, z);  beta = rz1 / rz;  rz = rz1;  p[i] = z[i] + (beta * p[i])
+ *
+ *   SPAL_KRYLOV_BICGSTAB
+ *     r = b - A x (as above);  rhat = r;  rho = alpha = omega = 1;  v = p = 0;  rr = dot(r, r);  it = 0;  test
+ *     while not stopped:
+ *       rho1 = dot(rhat, r);  beta = (rho1 / rho) * (alpha / omega);  rho = rho1
+ *       p[i] = r[i] + (beta * (p[i] - (omega * v[i])))
+ *       ph = M^-1 p;  v = A ph;  alpha = rho / dot(rhat, v)
+ *       s[i] = r[i] - (alpha * v[i]);  it += 1
+ *       ss = dot(s, s);  if ss <= thr (reason 0) or ss not finite (reason 2):
+ *                            x[i] = x[i] + (alpha * ph[i]);  r = s;  rr = ss;  stop      -- the half-step exit
+ *       sh = M^-1 s;  t = A sh;  omega = dot(t, s) / dot(t, t)
+ *       x[i] = (x[i] + (alpha * ph[i])) + (omega * sh[i]);  r[i] = s[i] - (omega * t[i])
+ *       rr = dot(r, r);  test
+ *   (The half-step exit is part of the contract: with M = A exactly -- a diagonal or triangular A and its own factor --
+ *   s is exactly zero and omega would be 0 / 0.)
+ *
+ * On the device the scalars live in a small block of device memory; the one-workgroup launch that finishes a dot also
+ * does the scalar arithmetic that follows it, and every vector update is fused with the first level of the dot that
+ * follows it -- neither changes a bit.  The host enqueues "krylov_check_every" iterations, then copies the status block
+ * to pinned memory and synchronises.  Once the device has stopped, every later vector or scalar kernel of the call
+ * reads the stop flag and writes nothing (products and solves still run, into work vectors), so x, iterations and
+ * residual_sq are the values AT the stop whatever the poll interval is.  The flag is written by an earlier launch on
+ * the same stream and only read: nothing waits on it, nothing spins.
+ * Option "krylov_check_every" (spal_csr_set_option / spal_csc_set_option on `a`, >= 1; 0 is refused): default 8 without
+ * a preconditioner and 1 with one.  The bits do not depend on it.
+ * Before the first iteration the call builds a's product plan and m's lower and upper solve plans if they do not exist
+ * yet (a first touch is fine; it synchronises) and takes its work vectors from the caching allocator; no handle lock is
+ * held across a product or a solve (each takes its own), so calls on one handle from several threads are safe.
+ * CSC handles multiply by their own SpMV route and solve on their CSR twin.  The _dev forms SYNCHRONISE `stream` (they
+ * poll) and cannot be captured into a graph.
+ * info: iterations, reason (0 converged, 1 maxit, 2 breakdown / not finite), residual_sq = rr and rhs_sq = bb (exact
+ * conversions of the T values), solve_ms = device time from the first to the last launch of the call.
+ * SPAL_ERR_INVALID_ARGUMENT: null a, b, x or info; wrong lengths (host forms); a or m not square; shapes, devices or
+ * element types of a and m that differ, an _f64 entry on an f32 handle or the reverse; a method outside the enum; tol
+ * negative or NaN; m with a row that stores no diagonal (the solve's own message); x_dev == b_dev.
+ * SPAL_ERR_UNSUPPORTED: a handle held as row blocks.  Nothing leaks on failure.
+ * describe() on `a` gains "krylov" after a solve: {method, preconditioned, iterations, reason, check_every, polls,
+ * solve_ms} of the last call.
+ * Not provided: capture into a graph, Jacobi, GMRES, several GPUs, a dot fused into the SpMV kernels. */
+enum { SPAL_KRYLOV_CG = 0, SPAL_KRYLOV_BICGSTAB = 1 };
+typedef struct spal_krylov_info {
+    uint64_t iterations;
+    int reason;
+    double residual_sq, rhs_sq, solve_ms;
+} spal_krylov_info;
+int spal_dot_f64(const double *a, const double *b, uint64_t n, double *out);      /* host only */
+int spal_dot_f32(const float *a, const float *b, uint64_t n, float *out);
+int spal_dot_dev_f64(int device, const double *a_dev, const double *b_dev, uint64_t n, double *out_dev,
+                     void *stream);                                               /* enqueued, not synchronised */
+int spal_dot_dev_f32(int device, const float *a_dev, const float *b_dev, uint64_t n, float *out_dev,
+                     void *stream);
+int spal_csr_krylov_f64(spal_csr_t a, int method, spal_csr_t m, const double *b, uint64_t b_len,
+                        double *x, uint64_t x_len, double tol, uint64_t maxit,
+                        spal_krylov_info *info);                                  /* host vectors; m NULL: none */
+int spal_csr_krylov_f32(spal_csr_t a, int method, spal_csr_t m, const float *b, uint64_t b_len,
+                        float *x, uint64_t x_len, double tol, uint64_t maxit, spal_krylov_info *info);
+int spal_csr_krylov_dev_f64(spal_csr_t a, int method, spal_csr_t m, const double *b_dev, double *x_dev,
+                            double tol, uint64_t maxit, void *stream,
+                            spal_krylov_info *info);                              /* synchronises */
+int spal_csr_krylov_dev_f32(spal_csr_t a, int method, spal_csr_t m, const float *b_dev, float *x_dev,
+                            double tol, uint64_t maxit, void *stream, spal_krylov_info *info);
+int spal_csc_krylov_f64(spal_csc_t a, int method, spal_csc_t m, const double *b, uint64_t b_len,
+                        double *x, uint64_t x_len, double tol, uint64_t maxit, spal_krylov_info *info);
+int spal_csc_krylov_f32(spal_csc_t a, int method, spal_csc_t m, const float *b, uint64_t b_len,
+                        float *x, uint64_t x_len, double tol, uint64_t maxit, spal_krylov_info *info);
+int spal_csc_krylov_dev_f64(spal_csc_t a, int method, spal_csc_t m, const double *b_dev, double *x_dev,
+                            double tol, uint64_t maxit, void *stream, spal_krylov_info *info);
+int spal_csc_krylov_dev_f32(spal_csc_t a, int method, spal_csc_t m, const float *b_dev, float *x_dev,
+                            double tol, uint64_t maxit, void *stream, spal_krylov_info *info);
+
 /* ---- CSR <-> CSC on the device ------------------------------------------------
  * Replace `impl From<&CscMatrix<T>> for CsrMatrix<T>` (src/csr/conv/csc.rs:4-52)
  * and `impl From<&CsrMatrix<T>> for CscMatrix<T>` (src/csc/conv/csr.rs:4-52),

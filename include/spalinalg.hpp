@@ -16,6 +16,8 @@
 //   a + b, a - b, -a          == impl Add / Sub / Neg for &CsrMatrix<T>  src/csr/ops/{add,sub,neg}.rs
 //   CsrMatrix<T>::from(coo)  == CsrMatrix::from(&coo)    src/csr/conv/coo.rs:3-116
 //   CscMatrix<T>, CooMatrix<T> likewise                  src/csc.rs, src/coo.rs
+//   a.solve(b, method, M, x0, tol, maxit), dot(a, b)     not in the reference: CG / BiCGStab and their dot product
+//                                                        (include/spal.h, spal_*_krylov_*, spal_dot_*)
 //
 // A failed `assert!` in the reference is a panic; here it is a
 // spalinalg::Panic exception (the Rust shim in rust_shim/ turns the same
@@ -63,11 +65,14 @@ template <> struct Abi<double> {
     static constexpr auto csr_spmv = spal_csr_spmv_f64;
     static constexpr auto csr_spmm = spal_csr_spmm_f64;
     static constexpr auto csr_trsv = spal_csr_trsv_f64;
+    static constexpr auto csr_krylov = spal_csr_krylov_f64;
+    static constexpr auto dot = spal_dot_f64;
     static constexpr auto csr_download = spal_csr_download_f64;
     static constexpr auto csc_create = spal_csc_create_f64;
     static constexpr auto csc_spmv = spal_csc_spmv_f64;
     static constexpr auto csc_spmm = spal_csc_spmm_f64;
     static constexpr auto csc_trsv = spal_csc_trsv_f64;
+    static constexpr auto csc_krylov = spal_csc_krylov_f64;
     static constexpr auto coo_to_csr = spal_coo_to_csr_f64;
     static constexpr auto coo_to_csc = spal_coo_to_csc_f64;
     static constexpr auto csc_download = spal_csc_download_f64;
@@ -77,11 +82,14 @@ template <> struct Abi<float> {
     static constexpr auto csr_spmv = spal_csr_spmv_f32;
     static constexpr auto csr_spmm = spal_csr_spmm_f32;
     static constexpr auto csr_trsv = spal_csr_trsv_f32;
+    static constexpr auto csr_krylov = spal_csr_krylov_f32;
+    static constexpr auto dot = spal_dot_f32;
     static constexpr auto csr_download = spal_csr_download_f32;
     static constexpr auto csc_create = spal_csc_create_f32;
     static constexpr auto csc_spmv = spal_csc_spmv_f32;
     static constexpr auto csc_spmm = spal_csc_spmm_f32;
     static constexpr auto csc_trsv = spal_csc_trsv_f32;
+    static constexpr auto csc_krylov = spal_csc_krylov_f32;
     static constexpr auto coo_to_csr = spal_coo_to_csr_f32;
     static constexpr auto coo_to_csc = spal_coo_to_csc_f32;
     static constexpr auto csc_download = spal_csc_download_f32;
@@ -101,6 +109,27 @@ struct CscDeleter { void operator()(spal_csc *h) const { spal_csc_destroy(h); } 
 
 template <typename T> class CooMatrix;
 template <typename T> class CscMatrix;
+
+// The Krylov solvers of include/spal.h (spal_*_krylov_*): the method, and what a solve returns beside x.
+enum class Method { Cg = SPAL_KRYLOV_CG, BiCgStab = SPAL_KRYLOV_BICGSTAB };
+template <typename T>
+struct Solution {
+    std::vector<T> x;
+    usize iterations;
+    int reason;   // 0 converged (dot(r, r) <= tol^2 dot(b, b)), 1 maxit reached, 2 breakdown / not finite
+    double residual_sq, rhs_sq, solve_ms;
+};
+
+// dot(a, b) by the library's definition: products rounded, then the fixed tree over tiles of 1024 (spal_dot_*, host only).
+template <typename T>
+T dot(const std::vector<T> &a, const std::vector<T> &b) {
+    if (a.size() != b.size())
+        throw Panic(SPAL_ERR_INVALID_ARGUMENT, "dot: a.len() = " + std::to_string(a.size()) + " but b.len() = " +
+                                                   std::to_string(b.size()));
+    T out = T(0);
+    detail::check(detail::Abi<T>::dot(a.data(), b.data(), a.size(), &out));
+    return out;
+}
 
 // ---------------------------------------------------------------------------
 // CsrMatrix<T>                                     reference src/csr.rs:66-72
@@ -207,6 +236,30 @@ class CsrMatrix {
         spal_csr_t h = nullptr;
         detail::check(spal_csr_ilu0(device_handle(), nullptr, &h));
         return adopt(h);
+    }
+
+    // x with A x = b by CG (A symmetric positive definite) or BiCGStab on the device, optionally preconditioned by
+    // M = ilu0() (nullptr: none), from x0 (empty: zeros); bit for bit the loops of include/spal.h (spal_csr_krylov_*).
+    // Panics when the matrix is not square or a length differs; a breakdown is no panic but reason 2.
+    Solution<T> solve(const std::vector<T> &b, Method method = Method::Cg, const CsrMatrix *M = nullptr,
+                      const std::vector<T> &x0 = {}, double tol = 1e-8, usize maxit = 1000) const {
+        if (nrows_ != ncols_)
+            throw Panic(SPAL_ERR_INVALID_ARGUMENT, "solve: the matrix is not square (" + std::to_string(nrows_) + " x " +
+                                                       std::to_string(ncols_) + ")");
+        if (b.size() != nrows_ || (!x0.empty() && x0.size() != nrows_))
+            throw Panic(SPAL_ERR_INVALID_ARGUMENT, "solve: b.len() = " + std::to_string(b.size()) + " and x0.len() = " +
+                                                       std::to_string(x0.size()) + " but the matrix has " +
+                                                       std::to_string(nrows_) + " rows");
+        Solution<T> s{x0.empty() ? std::vector<T>(nrows_, T(0)) : x0, 0, 0, 0.0, 0.0, 0.0};
+        spal_krylov_info info;
+        detail::check(detail::Abi<T>::csr_krylov(device_handle(), static_cast<int>(method), M ? M->device_handle() : nullptr,
+                                                  b.data(), b.size(), s.x.data(), s.x.size(), tol, maxit, &info));
+        s.iterations = info.iterations;
+        s.reason = info.reason;
+        s.residual_sq = info.residual_sq;
+        s.rhs_sq = info.rhs_sq;
+        s.solve_ms = info.solve_ms;
+        return s;
     }
 
     // CsrMatrix::from(&coo): assembled on the device, bit-identical to the reference.
@@ -336,6 +389,29 @@ class CscMatrix {
         spal_csc_t h = nullptr;
         detail::check(spal_csc_ilu0(device_handle(), nullptr, &h));
         return adopt(h);
+    }
+    // x with A x = b by CG (A symmetric positive definite) or BiCGStab on the device, optionally preconditioned by
+    // M = ilu0() (nullptr: none), from x0 (empty: zeros); bit for bit the loops of include/spal.h (spal_csc_krylov_*).
+    // Panics when the matrix is not square or a length differs; a breakdown is no panic but reason 2.
+    Solution<T> solve(const std::vector<T> &b, Method method = Method::Cg, const CscMatrix *M = nullptr,
+                      const std::vector<T> &x0 = {}, double tol = 1e-8, usize maxit = 1000) const {
+        if (nrows_ != ncols_)
+            throw Panic(SPAL_ERR_INVALID_ARGUMENT, "solve: the matrix is not square (" + std::to_string(nrows_) + " x " +
+                                                       std::to_string(ncols_) + ")");
+        if (b.size() != nrows_ || (!x0.empty() && x0.size() != nrows_))
+            throw Panic(SPAL_ERR_INVALID_ARGUMENT, "solve: b.len() = " + std::to_string(b.size()) + " and x0.len() = " +
+                                                       std::to_string(x0.size()) + " but the matrix has " +
+                                                       std::to_string(nrows_) + " rows");
+        Solution<T> s{x0.empty() ? std::vector<T>(nrows_, T(0)) : x0, 0, 0, 0.0, 0.0, 0.0};
+        spal_krylov_info info;
+        detail::check(detail::Abi<T>::csc_krylov(device_handle(), static_cast<int>(method), M ? M->device_handle() : nullptr,
+                                                  b.data(), b.size(), s.x.data(), s.x.size(), tol, maxit, &info));
+        s.iterations = info.iterations;
+        s.reason = info.reason;
+        s.residual_sq = info.residual_sq;
+        s.rhs_sq = info.rhs_sq;
+        s.solve_ms = info.solve_ms;
+        return s;
     }
     // CscMatrix::from(&csr)  (src/csc/conv/csr.rs:4-52) and CscMatrix::from(&coo)
     // (src/csc/conv/coo.rs:3-116), both on the device.

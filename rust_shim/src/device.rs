@@ -4,7 +4,7 @@
 use std::marker::PhantomData;
 use std::os::raw::{c_int, c_void};
 
-use super::{ffi, scalar::{HipScalar, HipSpmm, HipTrsv}};
+use super::{ffi, scalar::{HipKrylov, HipScalar, HipSpmm, HipTrsv}};
 use crate::{CooMatrix, CscMatrix, CsrMatrix};
 
 /// `CsrMatrix<T>` resident on a GPU (include/spal.h: spal_csr_t).
@@ -112,6 +112,17 @@ impl<T: HipScalar> DeviceCsr<T> {
         let mut x = vec![T::zero(); nrows];
         unsafe { ffi::check(T::csr_trsv(self.h, if lower { 0 } else { 1 }, unit_diagonal as c_int, b, &mut x)); }
         x
+    }
+
+    /// x with A x = b by CG (`ffi::SPAL_KRYLOV_CG`: A symmetric positive definite) or BiCGStab, optionally preconditioned by
+    /// `m = self.ilu0(..)`; `x` holds x0 on entry and the result on exit.  Bit for bit the loops of include/spal.h; a
+    /// breakdown is no panic but `reason == 2`.  Panics when the matrix is not square or a length differs.
+    pub fn solve(&self, method: c_int, m: Option<&DeviceCsr<T>>, b: &[T], x: &mut [T], tol: f64, maxit: u64) -> ffi::spal_krylov_info
+    where T: HipKrylov {
+        let mut info = ffi::spal_krylov_info::default();
+        let mh = m.map_or(std::ptr::null_mut(), |f| f.h);
+        unsafe { ffi::check(T::csr_krylov(self.h, method, mh, b, x, tol, maxit, &mut info)); }
+        info
     }
 
     /// `solve_triangular` on device pointers (`x_dev == b_dev` solves in place), enqueued on `stream` and not
@@ -276,6 +287,17 @@ impl<T: HipScalar> DeviceCsc<T> {
         let mut x = vec![T::zero(); nrows];
         unsafe { ffi::check(T::csc_trsv(self.h, if lower { 0 } else { 1 }, unit_diagonal as c_int, b, &mut x)); }
         x
+    }
+
+    /// x with A x = b by CG (`ffi::SPAL_KRYLOV_CG`: A symmetric positive definite) or BiCGStab, optionally preconditioned by
+    /// `m = self.ilu0(..)`; `x` holds x0 on entry and the result on exit.  Bit for bit the loops of include/spal.h; a
+    /// breakdown is no panic but `reason == 2`.  Panics when the matrix is not square or a length differs.
+    pub fn solve(&self, method: c_int, m: Option<&DeviceCsc<T>>, b: &[T], x: &mut [T], tol: f64, maxit: u64) -> ffi::spal_krylov_info
+    where T: HipKrylov {
+        let mut info = ffi::spal_krylov_info::default();
+        let mh = m.map_or(std::ptr::null_mut(), |f| f.h);
+        unsafe { ffi::check(T::csc_krylov(self.h, method, mh, b, x, tol, maxit, &mut info)); }
+        info
     }
 
     /// `solve_triangular` on device pointers (`x_dev == b_dev` solves in place), enqueued on `stream` and not

@@ -21,6 +21,12 @@ pub const SPAL_ERR_UNSUPPORTED: c_int = 5;
 pub const SPAL_ERR_NO_DEVICE: c_int = 6;
 pub const SPAL_ERR_INDEX_OUT_OF_BOUNDS: c_int = 7;
 
+pub const SPAL_KRYLOV_CG: c_int = 0;
+pub const SPAL_KRYLOV_BICGSTAB: c_int = 1;
+/// What spal_*_krylov_* report: reason 0 converged, 1 maxit reached, 2 breakdown / not finite.
+#[repr(C)] #[derive(Clone, Copy, Debug, Default)]
+pub struct spal_krylov_info { pub iterations: u64, pub reason: c_int, pub residual_sq: f64, pub rhs_sq: f64, pub solve_ms: f64 }
+
 #[link(name = "spal_hip")]
 extern "C" {
     pub fn spal_last_error() -> *const c_char;
@@ -80,6 +86,18 @@ extern "C" {
     pub fn spal_csc_trsv_dev_f32(a: *mut spal_csc, uplo: c_int, unit_diag: c_int, b_dev: *const f32, x_dev: *mut f32, stream: *mut c_void) -> c_int;
     pub fn spal_csr_ilu0(a: *mut spal_csr, stream: *mut c_void, out: *mut *mut spal_csr) -> c_int;
     pub fn spal_csc_ilu0(a: *mut spal_csc, stream: *mut c_void, out: *mut *mut spal_csc) -> c_int;
+    pub fn spal_dot_f64(a: *const f64, b: *const f64, n: u64, out: *mut f64) -> c_int;
+    pub fn spal_dot_f32(a: *const f32, b: *const f32, n: u64, out: *mut f32) -> c_int;
+    pub fn spal_dot_dev_f64(device: c_int, a_dev: *const f64, b_dev: *const f64, n: u64, out_dev: *mut f64, stream: *mut c_void) -> c_int;
+    pub fn spal_dot_dev_f32(device: c_int, a_dev: *const f32, b_dev: *const f32, n: u64, out_dev: *mut f32, stream: *mut c_void) -> c_int;
+    pub fn spal_csr_krylov_f64(a: *mut spal_csr, method: c_int, m: *mut spal_csr, b: *const f64, b_len: u64, x: *mut f64, x_len: u64, tol: f64, maxit: u64, info: *mut spal_krylov_info) -> c_int;
+    pub fn spal_csr_krylov_f32(a: *mut spal_csr, method: c_int, m: *mut spal_csr, b: *const f32, b_len: u64, x: *mut f32, x_len: u64, tol: f64, maxit: u64, info: *mut spal_krylov_info) -> c_int;
+    pub fn spal_csr_krylov_dev_f64(a: *mut spal_csr, method: c_int, m: *mut spal_csr, b_dev: *const f64, x_dev: *mut f64, tol: f64, maxit: u64, stream: *mut c_void, info: *mut spal_krylov_info) -> c_int;
+    pub fn spal_csr_krylov_dev_f32(a: *mut spal_csr, method: c_int, m: *mut spal_csr, b_dev: *const f32, x_dev: *mut f32, tol: f64, maxit: u64, stream: *mut c_void, info: *mut spal_krylov_info) -> c_int;
+    pub fn spal_csc_krylov_f64(a: *mut spal_csc, method: c_int, m: *mut spal_csc, b: *const f64, b_len: u64, x: *mut f64, x_len: u64, tol: f64, maxit: u64, info: *mut spal_krylov_info) -> c_int;
+    pub fn spal_csc_krylov_f32(a: *mut spal_csc, method: c_int, m: *mut spal_csc, b: *const f32, b_len: u64, x: *mut f32, x_len: u64, tol: f64, maxit: u64, info: *mut spal_krylov_info) -> c_int;
+    pub fn spal_csc_krylov_dev_f64(a: *mut spal_csc, method: c_int, m: *mut spal_csc, b_dev: *const f64, x_dev: *mut f64, tol: f64, maxit: u64, stream: *mut c_void, info: *mut spal_krylov_info) -> c_int;
+    pub fn spal_csc_krylov_dev_f32(a: *mut spal_csc, method: c_int, m: *mut spal_csc, b_dev: *const f32, x_dev: *mut f32, tol: f64, maxit: u64, stream: *mut c_void, info: *mut spal_krylov_info) -> c_int;
     pub fn spal_csc_to_csr(a: *mut spal_csc, out: *mut *mut spal_csr) -> c_int;
     pub fn spal_csr_to_csc(a: *mut spal_csr, out: *mut *mut spal_csc) -> c_int;
     pub fn spal_csr_mul(a: *mut spal_csr, b: *mut spal_csr, stream: *mut c_void, out: *mut *mut spal_csr) -> c_int;

@@ -135,3 +135,41 @@ macro_rules! impl_hip_trsv {
 }
 impl_hip_trsv!(f64, spal_csr_trsv_f64, spal_csr_trsv_dev_f64, spal_csc_trsv_f64, spal_csc_trsv_dev_f64);
 impl_hip_trsv!(f32, spal_csr_trsv_f32, spal_csr_trsv_dev_f32, spal_csc_trsv_f32, spal_csc_trsv_dev_f32);
+
+/// CG / BiCGStab and their dot product (the spal_*_krylov_* and spal_dot_* entry points): `method` is
+/// `ffi::SPAL_KRYLOV_CG` / `ffi::SPAL_KRYLOV_BICGSTAB`, `m` an ILU(0) factor handle or null.
+pub trait HipKrylov: Sized {
+    unsafe fn csr_krylov(a: *mut ffi::spal_csr, method: c_int, m: *mut ffi::spal_csr, b: &[Self], x: &mut [Self], tol: f64,
+                         maxit: u64, info: *mut ffi::spal_krylov_info) -> c_int;
+    unsafe fn csc_krylov(a: *mut ffi::spal_csc, method: c_int, m: *mut ffi::spal_csc, b: &[Self], x: &mut [Self], tol: f64,
+                         maxit: u64, info: *mut ffi::spal_krylov_info) -> c_int;
+    unsafe fn dot(a: &[Self], b: &[Self], out: *mut Self) -> c_int;
+}
+
+macro_rules! impl_hip_krylov {
+    ($t:ty, $csr_krylov:ident, $csc_krylov:ident, $dot:ident) => {
+        impl HipKrylov for $t {
+            unsafe fn csr_krylov(a: *mut ffi::spal_csr, method: c_int, m: *mut ffi::spal_csr, b: &[Self], x: &mut [Self],
+                                 tol: f64, maxit: u64, info: *mut ffi::spal_krylov_info) -> c_int {
+                ffi::$csr_krylov(a, method, m, b.as_ptr(), b.len() as u64, x.as_mut_ptr(), x.len() as u64, tol, maxit, info)
+            }
+            unsafe fn csc_krylov(a: *mut ffi::spal_csc, method: c_int, m: *mut ffi::spal_csc, b: &[Self], x: &mut [Self],
+                                 tol: f64, maxit: u64, info: *mut ffi::spal_krylov_info) -> c_int {
+                ffi::$csc_krylov(a, method, m, b.as_ptr(), b.len() as u64, x.as_mut_ptr(), x.len() as u64, tol, maxit, info)
+            }
+            unsafe fn dot(a: &[Self], b: &[Self], out: *mut Self) -> c_int {
+                ffi::$dot(a.as_ptr(), b.as_ptr(), a.len() as u64, out)
+            }
+        }
+    };
+}
+impl_hip_krylov!(f64, spal_csr_krylov_f64, spal_csc_krylov_f64, spal_dot_f64);
+impl_hip_krylov!(f32, spal_csr_krylov_f32, spal_csc_krylov_f32, spal_dot_f32);
+
+/// dot(a, b) by the library's definition (include/spal.h): products rounded, then the fixed tree over tiles of 1024.
+pub fn dot<T: HipKrylov + Default>(a: &[T], b: &[T]) -> T {
+    assert_eq!(a.len(), b.len());
+    let mut out = T::default();
+    unsafe { ffi::check(T::dot(a, b, &mut out)); }
+    out
+}

@@ -1,0 +1,700 @@
+// spal_krylov.hip -- the dot product, CG and BiCGStab on the device.  The contracts are written out in
+// include/spal.h: dot(a, b, n) = reduce(p), p[i] = a[i] * b[i] rounded; reduce pads with +0.0 to whole tiles of 1024,
+// halves every tile (h = 512 .. 1: e[t] = e[t] + e[t + h]) and, when there is more than one tile, reduces the tile sums
+// the same way.  The order depends on n alone, so every kernel here returns the bits of the sequential text.
+//
+// ONE TILE IS ONE TRIP OF A WORKGROUP OF 256.  Thread t holds elements t, t + 256, t + 512, t + 768: strides 512 and 256
+// are thread-local ((v0 + v2) + (v1 + v3)), strides 128 and 64 go through LDS, strides 32 .. 1 are __shfl_down inside
+// wave 0.  The first level writes one sum per tile to a scratch array; a launch of ONE workgroup (`finish`) walks the
+// upper levels, and its thread 0 then does the scalar arithmetic that follows the dot in the loop (alpha, beta, omega,
+// the test, the iteration count) in a small block of device memory.  Every vector update is fused with the first level
+// of the dot that follows it (`vec`): the same products, the same tile order, one pass less over the vectors.
+// ORDER BETWEEN LAUNCHES IS STREAM ORDER ALONE: no spinning, no ticket, nothing another workgroup waits on.
+//
+// FREEZE AFTER STOP.  The scalar block carries `done`.  It is written by a `finish` launch and read -- never waited
+// on -- by every later `vec` / `finish` launch of the call, which then returns before it writes: x, it and rr are the
+// values at the stop whatever the poll interval ("krylov_check_every") is.  Products and solves enqueued after the stop
+// still run, into work vectors nobody reads again.  BiCGStab's half-step exit needs one vector update AFTER the stop
+// was decided (x += alpha * ph): `half` is set with `done`, the next `vec` launch (V_BI_HALF) applies it, and the
+// scalar launch after that clears it.
+//
+// THE DRIVER HOLDS NO HANDLE LOCK ACROSS A PRODUCT OR A SOLVE: it calls the spal_*_spmv_dev_* / spal_*_trsv_dev_* entry
+// points, each of which takes what it needs itself (f5b9766: re-entering a handle's lock deadlocks).  Plans are built
+// before the first iteration; work vectors, the scratch and the scalar block come from the caching allocator per call,
+// so concurrent calls on one handle share nothing but the matrix.
+#include "spal_ops.hpp"
+
+#include <cmath>
+
+#pragma clang fp contract(off)
+
+namespace spal {
+namespace {
+
+constexpr uint64_t kTile = 1024;
+constexpr int kThreads = 256;
+constexpr unsigned kMaxGrid = 4096;   // first-level workgroups of a launch; each walks tiles blockIdx.x, + gridDim.x, ...
+
+// The scalars of one call, on the device; the host reads a copy in pinned memory when it polls.
+template <typename T>
+struct Scal {
+    T rr, bb, thr, rz, alpha, beta, omega, rho;
+    unsigned long long it;
+    unsigned done, reason, half, pad;
+};
+
+// The sum of one tile, valid in thread 0.  `lds` holds kThreads elements; ends with a barrier, so it can be reused.
+template <typename T>
+__device__ __forceinline__ T tile_sum(T v0, T v1, T v2, T v3, T *lds) {
+    const unsigned t = threadIdx.x;
+    T a = (v0 + v2) + (v1 + v3);                 // h = 512 (e[t], e[t + 256]), then h = 256
+    lds[t] = a;
+    __syncthreads();
+    if (t < 128) {
+        a = lds[t] + lds[t + 128];               // h = 128
+        if (t >= 64) lds[t] = a;                 // (its own slot: nobody else read it)
+    }
+    __syncthreads();
+    if (t < 64) {
+        a = a + lds[t + 64];                     // h = 64
+#pragma unroll
+        for (int h = 32; h >= 1; h >>= 1) a = a + __shfl_down(a, h, 64);
+    }
+    __syncthreads();
+    return a;
+}
+
+// ---- the first level, fused with the vector update in front of it ---------------------------------------------------
+enum VecOp {
+    V_DOT,      // d0 = a . b
+    V_DOT2,     // d0 = a . b, d1 = a . a
+    V_INIT,     // y = a - b;  d0 = y . y, d1 = a . a                                   (r = b - q;  rr, bb)
+    V_COPY_DOT, // y = b;  d0 = a . b                                                   (p = z;  rz)
+    V_CG_XR,    // x += alpha * a;  y -= alpha * b;  d0 = y . y                         (x, r;  rr)
+    V_CG_P,     // y = a + beta * y                                                     (p = z + beta p)
+    V_BI_P,     // y = a + beta * (y - omega * b)                                       (p = r + beta (p - omega v))
+    V_BI_S,     // y = a - alpha * b;  d0 = y . y                                       (s = r - alpha v;  ss)
+    V_BI_HALF,  // only when `half`:  x += alpha * a;  y = b                            (x += alpha ph;  r = s)
+    V_BI_XR,    // x = (x + alpha * a) + omega * b;  y = c - omega * d;  d0 = y . y      (x, r;  rr)
+};
+template <int OP> struct Dots { static constexpr int n = (OP == V_CG_P || OP == V_BI_P || OP == V_BI_HALF) ? 0 : (OP == V_DOT2 || OP == V_INIT) ? 2 : 1; };
+
+// Nothing is __restrict__: without a preconditioner z is r, ph is p and sh is s.
+template <typename T>
+struct VecArgs {
+    const T *a, *b, *c, *d;
+    T *x, *y;
+    const Scal<T> *s;   // nullptr: the stand-alone dot
+    T *part0, *part1;   // tile sums of d0 / d1
+    uint64_t n;
+};
+
+template <typename T, int OP>
+__device__ __forceinline__ void element(const VecArgs<T> &g, uint64_t i, T alpha, T beta, T omega, T &p0, T &p1) {
+    p0 = T(0);
+    p1 = T(0);
+    if (i >= g.n) return;   // the padding: +0.0, and it is added
+    if (OP == V_DOT) {
+        p0 = g.a[i] * g.b[i];
+    } else if (OP == V_DOT2) {
+        const T a = g.a[i];
+        p0 = a * g.b[i];
+        p1 = a * a;
+    } else if (OP == V_INIT) {
+        const T b = g.a[i];
+        const T r = b - g.b[i];
+        g.y[i] = r;
+        p0 = r * r;
+        p1 = b * b;
+    } else if (OP == V_COPY_DOT) {
+        const T z = g.b[i];
+        p0 = g.a[i] * z;
+        g.y[i] = z;
+    } else if (OP == V_CG_XR) {
+        g.x[i] = g.x[i] + alpha * g.a[i];
+        const T r = g.y[i] - alpha * g.b[i];
+        g.y[i] = r;
+        p0 = r * r;
+    } else if (OP == V_CG_P) {
+        g.y[i] = g.a[i] + beta * g.y[i];
+    } else if (OP == V_BI_P) {
+        g.y[i] = g.a[i] + beta * (g.y[i] - omega * g.b[i]);
+    } else if (OP == V_BI_S) {
+        const T s = g.a[i] - alpha * g.b[i];
+        g.y[i] = s;
+        p0 = s * s;
+    } else if (OP == V_BI_HALF) {
+        g.x[i] = g.x[i] + alpha * g.a[i];
+        g.y[i] = g.b[i];
+    } else if (OP == V_BI_XR) {
+        g.x[i] = (g.x[i] + alpha * g.a[i]) + omega * g.b[i];
+        const T r = g.c[i] - omega * g.d[i];
+        g.y[i] = r;
+        p0 = r * r;
+    }
+}
+
+template <typename T, int OP>
+__global__ __launch_bounds__(kThreads) void vec(VecArgs<T> g, uint64_t tiles) {
+    __shared__ T lds[2][kThreads];
+    T alpha = T(0), beta = T(0), omega = T(0);
+    if (g.s) {   // uniform: one word for the whole grid, written by an earlier launch
+        if (OP == V_BI_HALF ? g.s->half == 0 : g.s->done != 0) return;
+        alpha = g.s->alpha;
+        beta = g.s->beta;
+        omega = g.s->omega;
+    }
+    for (uint64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+        const uint64_t i = tile * kTile + threadIdx.x;
+        T p[4], q[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) element<T, OP>(g, i + (uint64_t)k * kThreads, alpha, beta, omega, p[k], q[k]);
+        if (Dots<OP>::n >= 1) {
+            const T s = tile_sum<T>(p[0], p[1], p[2], p[3], lds[0]);
+            if (threadIdx.x == 0) g.part0[tile] = s;
+        }
+        if (Dots<OP>::n >= 2) {
+            const T s = tile_sum<T>(q[0], q[1], q[2], q[3], lds[1]);
+            if (threadIdx.x == 0) g.part1[tile] = s;
+        }
+    }
+}
+
+// ---- the upper levels and the scalars, one workgroup ----------------------------------------------------------------
+// `part` holds the c1 sums of the first level, then room for every further level; returns reduce()'s result.  The
+// workgroup reads what it stored a level earlier: __syncthreads() orders that (workgroup scope), as in trsv_chain.
+template <typename T>
+__device__ T upper_levels(T *part, uint64_t c1, T *lds) {
+    T *in = part;
+    uint64_t m = c1;
+    while (m > 1) {
+        const uint64_t c = (m + kTile - 1) / kTile;
+        T *out = in + m;
+        for (uint64_t tile = 0; tile < c; ++tile) {
+            const uint64_t i = tile * kTile + threadIdx.x;
+            T v[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) v[k] = i + (uint64_t)k * kThreads < m ? in[i + (uint64_t)k * kThreads] : T(0);
+            const T s = tile_sum<T>(v[0], v[1], v[2], v[3], lds);
+            if (threadIdx.x == 0) out[tile] = s;
+        }
+        __syncthreads();
+        in = out;
+        m = c;
+    }
+    return in[0];
+}
+
+enum FinOp { F_STORE, F_INIT, F_RZ, F_ALPHA_CG, F_TEST_CG, F_BETA, F_RHO, F_ALPHA_BI, F_HALF, F_OMEGA, F_TEST_BI };
+
+template <typename T>
+struct FinArgs {
+    Scal<T> *s;
+    T *part0, *part1;
+    uint64_t c1;
+    T tol2;            // T(tol * tol)
+    uint64_t maxit;
+    T *out;            // F_STORE
+    int unpreconditioned;   // F_TEST_CG: z is r, so rz1 = rr and beta follows here
+};
+
+template <typename T>
+__device__ __forceinline__ void stop_test(Scal<T> *s, T rr, uint64_t maxit) {
+    s->rr = rr;
+    if (rr <= s->thr) {
+        s->done = 1;
+        s->reason = 0;
+    } else if (!isfinite(rr)) {
+        s->done = 1;
+        s->reason = 2;
+    } else if (s->it == maxit) {
+        s->done = 1;
+        s->reason = 1;
+    }
+}
+
+template <typename T, int OP>
+__global__ __launch_bounds__(kThreads) void finish(FinArgs<T> g) {
+    __shared__ T lds[kThreads];
+    Scal<T> *s = g.s;
+    if (OP != F_STORE) {
+        if (OP == F_OMEGA && threadIdx.x == 0) s->half = 0;   // the half step, if there was one, has been applied
+        if (s->done != 0) return;                             // uniform; this launch does not write `done` before here
+    }
+    const T d0 = upper_levels<T>(g.part0, g.c1, lds);
+    T d1 = T(0);
+    if (OP == F_INIT || OP == F_OMEGA) d1 = upper_levels<T>(g.part1, g.c1, lds);
+    if (threadIdx.x != 0) return;
+    if (OP == F_STORE) {
+        *g.out = d0;
+    } else if (OP == F_INIT) {
+        s->bb = d1;
+        s->thr = g.tol2 * d1;
+        s->it = 0;
+        s->rho = s->alpha = s->omega = T(1);
+        stop_test<T>(s, d0, g.maxit);
+    } else if (OP == F_RZ) {
+        s->rz = d0;
+    } else if (OP == F_ALPHA_CG) {
+        s->alpha = s->rz / d0;
+    } else if (OP == F_TEST_CG) {
+        s->it += 1;
+        stop_test<T>(s, d0, g.maxit);
+        if (g.unpreconditioned && !s->done) {
+            s->beta = d0 / s->rz;
+            s->rz = d0;
+        }
+    } else if (OP == F_BETA) {
+        s->beta = d0 / s->rz;
+        s->rz = d0;
+    } else if (OP == F_RHO) {
+        s->beta = (d0 / s->rho) * (s->alpha / s->omega);
+        s->rho = d0;
+    } else if (OP == F_ALPHA_BI) {
+        s->alpha = s->rho / d0;
+    } else if (OP == F_HALF) {
+        s->it += 1;
+        const bool small = d0 <= s->thr;
+        if (small || !isfinite(d0)) {
+            s->rr = d0;
+            s->reason = small ? 0 : 2;
+            s->half = 1;
+            s->done = 1;
+        }
+    } else if (OP == F_OMEGA) {
+        s->omega = d0 / d1;
+    } else if (OP == F_TEST_BI) {
+        stop_test<T>(s, d0, g.maxit);
+    }
+}
+
+// ---- host side of the launches --------------------------------------------------------------------------------------
+inline uint64_t tiles_of(uint64_t n) { return std::max<uint64_t>(1, (n + kTile - 1) / kTile); }
+// elements of the scratch of ONE dot over n elements: the first level's sums and every level above
+uint64_t scratch_elems(uint64_t n) {
+    uint64_t m = tiles_of(n), total = m;
+    while (m > 1) {
+        m = (m + kTile - 1) / kTile;
+        total += m;
+    }
+    return total;
+}
+
+template <typename T, int OP>
+hipError_t launch_vec(const VecArgs<T> &g, hipStream_t st) {
+    const uint64_t tiles = tiles_of(g.n);
+    hipLaunchKernelGGL((vec<T, OP>), dim3((unsigned)std::min<uint64_t>(tiles, kMaxGrid)), dim3(kThreads), 0, st, g, tiles);
+    return hipGetLastError();
+}
+template <typename T, int OP>
+hipError_t launch_finish(const FinArgs<T> &g, hipStream_t st) {
+    hipLaunchKernelGGL((finish<T, OP>), dim3(1), dim3(kThreads), 0, st, g);
+    return hipGetLastError();
+}
+
+// the definition on the host
+template <typename T>
+T reduce_host(std::vector<T> &v) {
+    for (;;) {
+        const uint64_t c = tiles_of(v.size());
+        v.resize(c * kTile, T(0));
+        std::vector<T> sums(c);
+        for (uint64_t tile = 0; tile < c; ++tile) {
+            T *e = v.data() + tile * kTile;
+            for (uint64_t h = kTile / 2; h >= 1; h /= 2)
+                for (uint64_t t = 0; t < h; ++t) e[t] = e[t] + e[t + h];
+            sums[tile] = e[0];
+        }
+        if (c == 1) return sums[0];
+        v.swap(sums);
+    }
+}
+
+template <typename T>
+int dot_host(const char *fn, const T *a, const T *b, uint64_t n, T *out) {
+    if (!out || (n && (!a || !b))) return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: null argument", fn);
+    std::vector<T> p(n);
+    for (uint64_t i = 0; i < n; ++i) p[i] = a[i] * b[i];
+    *out = reduce_host<T>(p);
+    return SPAL_OK;
+}
+
+template <typename T>
+int dot_dev(const char *fn, int device, const T *a, const T *b, uint64_t n, T *out, void *stream) {
+    if (!out || (n && (!a || !b))) return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: null argument", fn);
+    DeviceGuard guard(device);
+    if (guard.status != SPAL_OK) return guard.status;
+    const hipStream_t st = (hipStream_t)stream;
+    // stream-ordered scratch: returning a block to the caching allocator would wait for the device
+    void *part = nullptr;
+    SPAL_HIP_TRY(hipMallocAsync(&part, scratch_elems(n) * sizeof(T), st));
+    VecArgs<T> g = {};
+    g.a = a;
+    g.b = b;
+    g.n = n;
+    g.part0 = (T *)part;
+    hipError_t e = launch_vec<T, V_DOT>(g, st);
+    FinArgs<T> f = {};
+    f.part0 = (T *)part;
+    f.c1 = tiles_of(n);
+    f.out = out;
+    if (e == hipSuccess) e = launch_finish<T, F_STORE>(f, st);
+    const hipError_t e2 = hipFreeAsync(part, st);
+    if (e != hipSuccess) return fail(SPAL_ERR_HIP, "%s: launch failed: %s", fn, hipGetErrorString(e));
+    SPAL_HIP_TRY(e2);
+    return SPAL_OK;
+}
+
+// ---- the entry points the driver goes through, by handle and element type -------------------------------------------
+inline int mul_dev(spal_csr *a, const double *x, double *y, void *st) { return spal_csr_spmv_dev_f64(a, x, y, st); }
+inline int mul_dev(spal_csr *a, const float *x, float *y, void *st) { return spal_csr_spmv_dev_f32(a, x, y, st); }
+inline int mul_dev(spal_csc *a, const double *x, double *y, void *st) { return spal_csc_spmv_dev_f64(a, x, y, st); }
+inline int mul_dev(spal_csc *a, const float *x, float *y, void *st) { return spal_csc_spmv_dev_f32(a, x, y, st); }
+inline int solve_dev(spal_csr *m, int uplo, int unit, const double *b, double *x, void *st) { return spal_csr_trsv_dev_f64(m, uplo, unit, b, x, st); }
+inline int solve_dev(spal_csr *m, int uplo, int unit, const float *b, float *x, void *st) { return spal_csr_trsv_dev_f32(m, uplo, unit, b, x, st); }
+inline int solve_dev(spal_csc *m, int uplo, int unit, const double *b, double *x, void *st) { return spal_csc_trsv_dev_f64(m, uplo, unit, b, x, st); }
+inline int solve_dev(spal_csc *m, int uplo, int unit, const float *b, float *x, void *st) { return spal_csc_trsv_dev_f32(m, uplo, unit, b, x, st); }
+inline int analyse(spal_csr *m, int uplo, int unit, void *st) { return spal_csr_trsv_analyse(m, uplo, unit, st); }
+inline int analyse(spal_csc *m, int uplo, int unit, void *st) { return spal_csc_trsv_analyse(m, uplo, unit, st); }
+inline int product_plan(spal_csr *a) { return spal_csr_plan(a); }
+inline int product_plan(spal_csc *) { return SPAL_OK; }   // planned, twin included, by its constructor
+
+struct PinnedBuf {
+    void *p = nullptr;
+    PinnedBuf() = default;
+    PinnedBuf(const PinnedBuf &) = delete;
+    PinnedBuf &operator=(const PinnedBuf &) = delete;
+    ~PinnedBuf() { if (p) (void)hipHostFree(p); }
+};
+
+struct Record {
+    int method = 0, preconditioned = 0, reason = 0;
+    uint64_t iterations = 0, polls = 0;
+    int64_t check_every = 0;
+    double solve_ms = 0.0;
+};
+std::string info_json(const Record &r) {
+    char buf[320];
+    snprintf(buf, sizeof buf,
+             "{\"method\": \"%s\", \"preconditioned\": %d, \"iterations\": %llu, \"reason\": %d, \"check_every\": %lld, "
+             "\"polls\": %llu, \"solve_ms\": %.4f}",
+             r.method == SPAL_KRYLOV_CG ? "cg" : "bicgstab", r.preconditioned, (unsigned long long)r.iterations, r.reason,
+             (long long)r.check_every, (unsigned long long)r.polls, r.solve_ms);
+    return buf;
+}
+
+// What both loops share: the vectors, the scalar block, the scratch of two dots, and the launches by name.
+template <typename T, typename H>
+struct Run {
+    const char *fn;
+    H *a, *m;
+    hipStream_t st;
+    uint64_t n = 0, maxit = 0, c1 = 0;
+    T tol2 = T(0);
+    Scal<T> *s = nullptr;
+    T *part0 = nullptr, *part1 = nullptr;
+
+    int mul(const T *v, T *out) { return mul_dev(a, v, out, st); }
+    // out = M^-1 v (out != v); without a preconditioner the caller uses v itself
+    int prec(const T *v, T *out) {
+        SPAL_TRY(solve_dev(m, 0, 1, v, out, st));
+        return solve_dev(m, 1, 0, out, out, st);
+    }
+    template <int OP>
+    int v(const T *va, const T *vb, const T *vc, const T *vd, T *x, T *y) {
+        VecArgs<T> g = {va, vb, vc, vd, x, y, s, part0, part1, n};
+        const hipError_t e = launch_vec<T, OP>(g, st);
+        return e == hipSuccess ? SPAL_OK : fail(SPAL_ERR_HIP, "%s: launch failed: %s", fn, hipGetErrorString(e));
+    }
+    template <int OP>
+    int f(int unpreconditioned = 0) {
+        FinArgs<T> g = {s, part0, part1, c1, tol2, maxit, nullptr, unpreconditioned};
+        const hipError_t e = launch_finish<T, OP>(g, st);
+        return e == hipSuccess ? SPAL_OK : fail(SPAL_ERR_HIP, "%s: launch failed: %s", fn, hipGetErrorString(e));
+    }
+};
+
+template <typename T, typename H>
+int krylov_run(const char *fn, H *a, int method, H *m, const T *b, T *x, double tol, uint64_t maxit, hipStream_t st,
+               spal_krylov_info *info) {
+    const uint64_t n = a->nrows;
+    spal_csr *owner = solve_handle(a);   // whose lock guards a's option and its "krylov" string
+    int64_t check_every;
+    {
+        std::lock_guard<std::mutex> lock(owner->mu);
+        check_every = a->ops.krylov_check_every;
+    }
+    if (check_every == 0) check_every = m ? 1 : 8;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone)
+        return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: the call polls and synchronises: it cannot be captured into a graph", fn);
+
+    // plans first: nothing plans lazily once the iterations are being enqueued
+    SPAL_TRY(product_plan(a));
+    if (m) {
+        SPAL_TRY(analyse(m, 0, 1, st));
+        SPAL_TRY(analyse(m, 1, 0, st));   // a row without a diagonal: the solve's own message
+    }
+    // work vectors, scratch, scalars
+    const bool cg = method == SPAL_KRYLOV_CG;
+    const int nvec = cg ? (m ? 4 : 3) : (m ? 8 : 6);
+    DevBuf vecs, parts, scal;
+    PinnedBuf host;
+    EventSpans ev;
+    const uint64_t stride = (n + 63) & ~(uint64_t)63;   // every vector on a 256-byte boundary at least
+    SPAL_HIP_TRY(vecs.alloc((size_t)nvec * stride * sizeof(T)));
+    const uint64_t pe = scratch_elems(n);
+    SPAL_HIP_TRY(parts.alloc(2 * pe * sizeof(T)));
+    SPAL_HIP_TRY(scal.alloc(sizeof(Scal<T>)));
+    SPAL_HIP_TRY(hipHostMalloc(&host.p, sizeof(Scal<T>), hipHostMallocDefault));
+    SPAL_HIP_TRY(ev.create(1));
+    auto vec_at = [&](int k) { return vecs.as<T>() + (uint64_t)k * stride; };
+
+    Run<T, H> R;
+    R.fn = fn;
+    R.a = a;
+    R.m = m;
+    R.st = st;
+    R.n = n;
+    R.maxit = maxit;
+    R.c1 = tiles_of(n);
+    R.tol2 = (T)(tol * tol);
+    R.s = scal.as<Scal<T>>();
+    R.part0 = parts.as<T>();
+    R.part1 = parts.as<T>() + pe;
+
+    Scal<T> *h = (Scal<T> *)host.p;
+    uint64_t polls = 0;
+    auto poll = [&]() -> int {
+        SPAL_HIP_TRY(hipMemcpyAsync(h, R.s, sizeof(Scal<T>), hipMemcpyDeviceToHost, st));
+        SPAL_HIP_TRY(hipStreamSynchronize(st));
+        ++polls;
+        return SPAL_OK;
+    };
+
+    SPAL_HIP_TRY(hipEventRecord(ev.e[0], st));
+    SPAL_HIP_TRY(hipMemsetAsync(R.s, 0, sizeof(Scal<T>), st));
+    T *r = vec_at(0), *q = vec_at(1), *p = vec_at(2);
+    // r = b - A x;  rr, bb;  it = 0;  test
+    SPAL_TRY(R.mul(x, q));
+    SPAL_TRY((R.template v<V_INIT>(b, q, nullptr, nullptr, nullptr, r)));
+    SPAL_TRY((R.template f<F_INIT>()));
+    uint64_t enqueued = 0;
+    bool stopped = false;
+    if (cg) {
+        T *z = m ? vec_at(3) : r;
+        if (m) SPAL_TRY(R.prec(r, z));
+        SPAL_TRY((R.template v<V_COPY_DOT>(r, z, nullptr, nullptr, nullptr, p)));   // p = z;  rz
+        SPAL_TRY((R.template f<F_RZ>()));
+        while (enqueued < maxit && !stopped) {
+            const uint64_t batch = std::min<uint64_t>((uint64_t)check_every, maxit - enqueued);
+            for (uint64_t k = 0; k < batch; ++k) {
+                SPAL_TRY(R.mul(p, q));
+                SPAL_TRY((R.template v<V_DOT>(p, q, nullptr, nullptr, nullptr, nullptr)));
+                SPAL_TRY((R.template f<F_ALPHA_CG>()));
+                SPAL_TRY((R.template v<V_CG_XR>(p, q, nullptr, nullptr, x, r)));      // x, r;  rr
+                SPAL_TRY((R.template f<F_TEST_CG>(m ? 0 : 1)));                      // it, test (and beta when z is r)
+                if (m) {
+                    SPAL_TRY(R.prec(r, z));
+                    SPAL_TRY((R.template v<V_DOT>(r, z, nullptr, nullptr, nullptr, nullptr)));
+                    SPAL_TRY((R.template f<F_BETA>()));
+                }
+                SPAL_TRY((R.template v<V_CG_P>(z, nullptr, nullptr, nullptr, nullptr, p)));
+            }
+            enqueued += batch;
+            SPAL_TRY(poll());
+            stopped = h->done != 0;
+        }
+    } else {
+        T *rhat = vec_at(3), *vv = vec_at(4), *t = vec_at(5);
+        T *sv = q;   // q is free once r exists
+        T *ph = m ? vec_at(6) : p, *sh = m ? vec_at(7) : sv;
+        SPAL_HIP_TRY(hipMemcpyAsync(rhat, r, n * sizeof(T), hipMemcpyDeviceToDevice, st));
+        SPAL_HIP_TRY(hipMemsetAsync(vv, 0, n * sizeof(T), st));
+        SPAL_HIP_TRY(hipMemsetAsync(p, 0, n * sizeof(T), st));
+        while (enqueued < maxit && !stopped) {
+            const uint64_t batch = std::min<uint64_t>((uint64_t)check_every, maxit - enqueued);
+            for (uint64_t k = 0; k < batch; ++k) {
+                SPAL_TRY((R.template v<V_DOT>(rhat, r, nullptr, nullptr, nullptr, nullptr)));
+                SPAL_TRY((R.template f<F_RHO>()));
+                SPAL_TRY((R.template v<V_BI_P>(r, vv, nullptr, nullptr, nullptr, p)));
+                if (m) SPAL_TRY(R.prec(p, ph));
+                SPAL_TRY(R.mul(ph, vv));
+                SPAL_TRY((R.template v<V_DOT>(rhat, vv, nullptr, nullptr, nullptr, nullptr)));
+                SPAL_TRY((R.template f<F_ALPHA_BI>()));
+                SPAL_TRY((R.template v<V_BI_S>(r, vv, nullptr, nullptr, nullptr, sv)));   // s;  ss
+                SPAL_TRY((R.template f<F_HALF>()));                                       // it;  the half-step exit
+                SPAL_TRY((R.template v<V_BI_HALF>(ph, sv, nullptr, nullptr, x, r)));      // ... applied, if taken
+                if (m) SPAL_TRY(R.prec(sv, sh));
+                SPAL_TRY(R.mul(sh, t));
+                SPAL_TRY((R.template v<V_DOT2>(t, sv, nullptr, nullptr, nullptr, nullptr)));   // t . s, t . t
+                SPAL_TRY((R.template f<F_OMEGA>()));
+                SPAL_TRY((R.template v<V_BI_XR>(ph, sh, sv, t, x, r)));                   // x, r;  rr
+                SPAL_TRY((R.template f<F_TEST_BI>()));
+            }
+            enqueued += batch;
+            SPAL_TRY(poll());
+            stopped = h->done != 0;
+        }
+    }
+    if (!polls) SPAL_TRY(poll());   // maxit = 0: the test after r0 has decided
+    SPAL_HIP_TRY(hipEventRecord(ev.e[1], st));
+    SPAL_HIP_TRY(hipStreamSynchronize(st));
+    if (!h->done) return fail(SPAL_ERR_HIP, "%s: the device did not stop after %llu iterations", fn, (unsigned long long)maxit);
+    float ms = 0.f;
+    SPAL_HIP_TRY(ev.span(0, &ms));
+    info->iterations = h->it;
+    info->reason = (int)h->reason;
+    info->residual_sq = (double)h->rr;
+    info->rhs_sq = (double)h->bb;
+    info->solve_ms = (double)ms;
+    Record rec;
+    rec.method = method;
+    rec.preconditioned = m ? 1 : 0;
+    rec.reason = info->reason;
+    rec.iterations = info->iterations;
+    rec.polls = polls;
+    rec.check_every = check_every;
+    rec.solve_ms = info->solve_ms;
+    const std::string json = info_json(rec);
+    std::lock_guard<std::mutex> lock(owner->mu);
+    a->ops.krylov_info = json;
+    return SPAL_OK;
+}
+
+// every refusal that needs no device
+template <typename T, typename H>
+int krylov_check(const char *fn, H *a, int method, H *m, const T *b, T *x, double tol, spal_krylov_info *info) {
+    if (!a || !b || !x || !info) return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: null argument", fn);
+    SPAL_TRY(check_dtype<T>(fn, a->elem_size));
+    if (method != SPAL_KRYLOV_CG && method != SPAL_KRYLOV_BICGSTAB)
+        return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: method = %d must be 0 (CG) or 1 (BiCGStab)", fn, method);
+    if (!(tol >= 0.0)) return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: tol = %g must be >= 0", fn, tol);
+    if (a->nrows != a->ncols)
+        return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: the matrix is not square (%llu x %llu)", fn, (unsigned long long)a->nrows,
+                    (unsigned long long)a->ncols);
+    if (m) {
+        SPAL_TRY(check_same_device_and_dtype(fn, a, m));
+        if (m->nrows != a->nrows || m->ncols != a->ncols)
+            return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: the preconditioner is %llu x %llu but the matrix %llu x %llu", fn,
+                        (unsigned long long)m->nrows, (unsigned long long)m->ncols, (unsigned long long)a->nrows,
+                        (unsigned long long)a->ncols);
+    }
+    if (row_blocks(a) || (m && row_blocks(m))) return refuse_row_blocks(fn);
+    return SPAL_OK;
+}
+
+template <typename T, typename H>
+int krylov_dev(const char *fn, H *a, int method, H *m, const T *b, T *x, double tol, uint64_t maxit, void *stream,
+               spal_krylov_info *info) {
+    SPAL_TRY((krylov_check<T, H>(fn, a, method, m, b, x, tol, info)));
+    if (x == b) return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: x_dev == b_dev (b is read in every test of the residual)", fn);
+    DeviceGuard guard(a->device);
+    if (guard.status != SPAL_OK) return guard.status;
+    return krylov_run<T, H>(fn, a, method, m, b, x, tol, maxit, (hipStream_t)stream, info);
+}
+
+struct PooledStream {
+    hipStream_t s = nullptr;
+    PooledStream() = default;
+    PooledStream(const PooledStream &) = delete;
+    PooledStream &operator=(const PooledStream &) = delete;
+    ~PooledStream() { stream_release(s); }
+};
+
+template <typename T, typename H>
+int krylov_host(const char *fn, H *a, int method, H *m, const T *b, uint64_t b_len, T *x, uint64_t x_len, double tol,
+                uint64_t maxit, spal_krylov_info *info) {
+    SPAL_TRY((krylov_check<T, H>(fn, a, method, m, b, x, tol, info)));
+    if (b_len != a->nrows || x_len != a->nrows)
+        return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: b.len() = %llu and x.len() = %llu but the matrix has %llu rows", fn,
+                    (unsigned long long)b_len, (unsigned long long)x_len, (unsigned long long)a->nrows);
+    DeviceGuard guard(a->device);
+    if (guard.status != SPAL_OK) return guard.status;
+    const uint64_t n = a->nrows;
+    DevBuf db, dx;
+    PooledStream ps;   // a stream of the call's own: the handle's staging stream belongs to whoever holds its lock
+    SPAL_HIP_TRY(db.alloc(n * sizeof(T)));
+    SPAL_HIP_TRY(dx.alloc(n * sizeof(T)));
+    SPAL_HIP_TRY(stream_acquire(&ps.s));
+    SPAL_HIP_TRY(hipMemcpyAsync(db.p, b, n * sizeof(T), hipMemcpyHostToDevice, ps.s));
+    SPAL_HIP_TRY(hipMemcpyAsync(dx.p, x, n * sizeof(T), hipMemcpyHostToDevice, ps.s));
+    SPAL_TRY((krylov_run<T, H>(fn, a, method, m, db.as<T>(), dx.as<T>(), tol, maxit, ps.s, info)));
+    SPAL_HIP_TRY(hipMemcpyAsync(x, dx.p, n * sizeof(T), hipMemcpyDeviceToHost, ps.s));
+    SPAL_HIP_TRY(hipStreamSynchronize(ps.s));
+    return SPAL_OK;
+}
+
+}  // namespace
+
+int krylov_option(spal_csr *a, const char *key, int64_t value, OpState &s, int *status) {
+    if (strcmp(key, "krylov_check_every")) return 0;
+    if (value < 1) {
+        *status = fail(SPAL_ERR_INVALID_ARGUMENT, "krylov_check_every must be >= 1 (iterations enqueued between two polls of the stop flag)");
+        return 1;
+    }
+    std::lock_guard<std::mutex> lock(a->mu);
+    s.krylov_check_every = value;
+    *status = SPAL_OK;
+    return 1;
+}
+
+int krylov_describe_append(char *buf, size_t buf_len, const OpState &s, spal_csr *solve) {
+    if (!solve) return SPAL_OK;
+    std::string info;
+    {
+        std::lock_guard<std::mutex> lock(solve->mu);
+        info = s.krylov_info;
+    }
+    return describe_append(buf, buf_len, "krylov", info);
+}
+
+}  // namespace spal
+
+using namespace spal;
+
+extern "C" {
+
+int spal_dot_f64(const double *a, const double *b, uint64_t n, double *out) { return dot_host<double>("spal_dot", a, b, n, out); }
+int spal_dot_f32(const float *a, const float *b, uint64_t n, float *out) { return dot_host<float>("spal_dot", a, b, n, out); }
+int spal_dot_dev_f64(int device, const double *a_dev, const double *b_dev, uint64_t n, double *out_dev, void *stream) {
+    return dot_dev<double>("spal_dot_dev", device, a_dev, b_dev, n, out_dev, stream);
+}
+int spal_dot_dev_f32(int device, const float *a_dev, const float *b_dev, uint64_t n, float *out_dev, void *stream) {
+    return dot_dev<float>("spal_dot_dev", device, a_dev, b_dev, n, out_dev, stream);
+}
+
+int spal_csr_krylov_f64(spal_csr_t a, int method, spal_csr_t m, const double *b, uint64_t b_len, double *x, uint64_t x_len,
+                        double tol, uint64_t maxit, spal_krylov_info *info) {
+    return krylov_host<double, spal_csr>("spal_csr_krylov", a, method, m, b, b_len, x, x_len, tol, maxit, info);
+}
+int spal_csr_krylov_f32(spal_csr_t a, int method, spal_csr_t m, const float *b, uint64_t b_len, float *x, uint64_t x_len,
+                        double tol, uint64_t maxit, spal_krylov_info *info) {
+    return krylov_host<float, spal_csr>("spal_csr_krylov", a, method, m, b, b_len, x, x_len, tol, maxit, info);
+}
+int spal_csr_krylov_dev_f64(spal_csr_t a, int method, spal_csr_t m, const double *b_dev, double *x_dev, double tol,
+                            uint64_t maxit, void *stream, spal_krylov_info *info) {
+    return krylov_dev<double, spal_csr>("spal_csr_krylov_dev", a, method, m, b_dev, x_dev, tol, maxit, stream, info);
+}
+int spal_csr_krylov_dev_f32(spal_csr_t a, int method, spal_csr_t m, const float *b_dev, float *x_dev, double tol,
+                            uint64_t maxit, void *stream, spal_krylov_info *info) {
+    return krylov_dev<float, spal_csr>("spal_csr_krylov_dev", a, method, m, b_dev, x_dev, tol, maxit, stream, info);
+}
+int spal_csc_krylov_f64(spal_csc_t a, int method, spal_csc_t m, const double *b, uint64_t b_len, double *x, uint64_t x_len,
+                        double tol, uint64_t maxit, spal_krylov_info *info) {
+    return krylov_host<double, spal_csc>("spal_csc_krylov", a, method, m, b, b_len, x, x_len, tol, maxit, info);
+}
+int spal_csc_krylov_f32(spal_csc_t a, int method, spal_csc_t m, const float *b, uint64_t b_len, float *x, uint64_t x_len,
+                        double tol, uint64_t maxit, spal_krylov_info *info) {
+    return krylov_host<float, spal_csc>("spal_csc_krylov", a, method, m, b, b_len, x, x_len, tol, maxit, info);
+}
+int spal_csc_krylov_dev_f64(spal_csc_t a, int method, spal_csc_t m, const double *b_dev, double *x_dev, double tol,
+                            uint64_t maxit, void *stream, spal_krylov_info *info) {
+    return krylov_dev<double, spal_csc>("spal_csc_krylov_dev", a, method, m, b_dev, x_dev, tol, maxit, stream, info);
+}
+int spal_csc_krylov_dev_f32(spal_csc_t a, int method, spal_csc_t m, const float *b_dev, float *x_dev, double tol,
+                            uint64_t maxit, void *stream, spal_krylov_info *info) {
+    return krylov_dev<float, spal_csc>("spal_csc_krylov_dev", a, method, m, b_dev, x_dev, tol, maxit, stream, info);
+}
+
+}  // extern "C"

@@ -1,5 +1,5 @@
 // spal_ops.hpp -- the host layer the sparse operations share: spal_spgemm.hip, spal_spadd.hip,
-// spal_spmm.hip, spal_trsv.hip and spal_ilu.hip keep their kernels, their driver, their option's validation and their
+// spal_spmm.hip, spal_trsv.hip, spal_ilu.hip and spal_krylov.hip keep their kernels, their driver, their option's validation and their
 // info JSON; what surrounds a launch the same way in each of them is here, once.  (Not installed.)
 #pragma once
 
@@ -157,22 +157,26 @@ int spadd_option(const char *key, int64_t value, OpState &s, int *status);    //
 int spmm_option(const char *key, int64_t value, OpState &s, int *status);     // "spmm_tile"
 int trsv_option(spal_csr *a, const char *key, int64_t value, int *status);    // "trsv_chain_rows" (launch lists rebuilt)
 int ilu_option(spal_csr *a, const char *key, int64_t value, int *status);     // "ilu_wide_work"
+int krylov_option(spal_csr *a, const char *key, int64_t value, OpState &s, int *status);   // "krylov_check_every"
 inline int ops_set_option(OpState &s, spal_csr *solve, const char *key, int64_t value, int *status) {
     return spgemm_option(key, value, s, status) || spadd_option(key, value, s, status) ||
            spmm_option(key, value, s, status) || trsv_option(solve, key, value, status) ||
-           ilu_option(solve, key, value, status);
+           ilu_option(solve, key, value, status) || krylov_option(solve, key, value, s, status);
 }
 
 // (describe_append itself is host code: spal_host.cpp, declared in spal_internal.hpp)
 // the "spmm" / "trsv" objects of a handle an SpMM ran on / a triangle of which was analysed (spal_spmm.hip, spal_trsv.hip)
 int spmm_describe_append(char *buf, size_t buf_len, const spal_csr *a);
 int trsv_describe_append(char *buf, size_t buf_len, spal_csr *a);
+// the "krylov" object of a handle a solve ran with as A (spal_krylov.hip; the string is read under the solve handle's lock)
+int krylov_describe_append(char *buf, size_t buf_len, const OpState &s, spal_csr *solve);
 inline int ops_describe_append(char *buf, size_t buf_len, const OpState &s, spal_csr *solve) {
     SPAL_TRY(describe_append(buf, buf_len, "spgemm", s.spgemm_info));   // a product of spal_*_mul: how it was built
     SPAL_TRY(describe_append(buf, buf_len, "spadd", s.spadd_info));     // a result of spal_*_add / _sub / _neg
     SPAL_TRY(spmm_describe_append(buf, buf_len, solve));                // an SpMM ran on it
     SPAL_TRY(trsv_describe_append(buf, buf_len, solve));                // a triangle of it was analysed for a solve
-    return describe_append(buf, buf_len, "ilu0", s.ilu_info);           // a factor of spal_*_ilu0: how it was built
+    SPAL_TRY(describe_append(buf, buf_len, "ilu0", s.ilu_info));        // a factor of spal_*_ilu0: how it was built
+    return krylov_describe_append(buf, buf_len, s, solve);              // spal_*_krylov_* ran with it as A: the last call
 }
 
 }  // namespace spal

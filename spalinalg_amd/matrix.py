@@ -68,6 +68,55 @@ def _stream_ptr(stream) -> vp:
 
 
 # --------------------------------------------------------------------------
+# the dot product and the Krylov solvers' result (include/spal.h)
+# --------------------------------------------------------------------------
+class _KrylovInfoC(C.Structure):
+    """spal_krylov_info"""
+    _fields_ = [("iterations", C.c_uint64), ("reason", C.c_int), ("residual_sq", C.c_double),
+                ("rhs_sq", C.c_double), ("solve_ms", C.c_double)]
+
+
+class KrylovInfo(dict):
+    """What a solve reports: iterations, reason (0 converged, 1 maxit, 2 breakdown / not finite), residual_sq = the
+    recurrence's dot(r, r) and rhs_sq = dot(b, b) (exact conversions of the element type's values), solve_ms."""
+    __getattr__ = dict.__getitem__
+
+
+_KRYLOV_METHODS = {"cg": 0, "bicgstab": 1}
+
+
+def _krylov_method(method) -> int:
+    if isinstance(method, str):
+        if method.lower() not in _KRYLOV_METHODS:
+            raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT, f"method {method!r} must be 'cg' or 'bicgstab'")
+        return _KRYLOV_METHODS[method.lower()]
+    return int(method)
+
+
+def _krylov_info(c: _KrylovInfoC) -> KrylovInfo:
+    return KrylovInfo(iterations=int(c.iterations), reason=int(c.reason), residual_sq=float(c.residual_sq),
+                      rhs_sq=float(c.rhs_sq), solve_ms=float(c.solve_ms))
+
+
+def dot(a, b):
+    """dot(a, b) by the library's definition (include/spal.h): products rounded, then the fixed tree over tiles of
+    1024 -- on the host, no device needed (spal_dot_*).  A numpy scalar of the vectors' dtype (float32 / float64)."""
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    if a.dtype != b.dtype or a.dtype not in (np.float32, np.float64) or a.ndim != 1 or a.shape != b.shape:
+        raise TypeError("dot() takes two 1-D vectors of one length and dtype, float32 or float64")
+    out = np.empty(1, dtype=a.dtype)
+    check(getattr(_ffi.lib(), f"spal_dot_{_sfx(a.dtype)}")(_p(a), _p(b), u64(a.size), _p(out)))
+    return out[0]
+
+
+def dot_dev(dtype, a_ptr: int, b_ptr: int, n: int, out_ptr: int, device: int = 0, stream=None) -> None:
+    """The same dot for device vectors (spal_dot_dev_*): the one result is written to out_ptr; enqueued on `stream`,
+    not synchronised."""
+    check(getattr(_ffi.lib(), f"spal_dot_dev_{_sfx(np.dtype(dtype))}")(C.c_int(device), vp(a_ptr), vp(b_ptr), u64(n),
+                                                                     vp(out_ptr), _stream_ptr(stream)))
+
+
+# --------------------------------------------------------------------------
 # device handles
 # --------------------------------------------------------------------------
 class _DeviceMatrix:
@@ -210,6 +259,33 @@ class _DeviceMatrix:
         check(self._fn(f"trsv_dev_{_sfx(self.dtype)}")(self._h, C.c_int(0 if lower else 1),
                                                        C.c_int(1 if unit_diagonal else 0), vp(b_ptr), vp(x_ptr),
                                                        _stream_ptr(stream)))
+
+    def krylov(self, b, method="cg", M=None, x0=None, tol: float = 1e-8, maxit: int = 1000):
+        """Solves A x = b by CG ("cg") or BiCGStab ("bicgstab") on the device (spal_*_krylov_*), optionally
+        preconditioned by `M`, an ILU(0) factor handle of this class (M^-1 v = two solves on it).  Host vectors; returns
+        (x, KrylovInfo).  Bit for bit the loops written out in include/spal.h, whatever "krylov_check_every" is."""
+        b = np.ascontiguousarray(b)
+        if b.dtype not in (np.float32, np.float64):
+            b = b.astype(self.dtype)
+        if b.ndim != 1:
+            raise TypeError("krylov() takes one right-hand side, a 1-D vector")
+        x = np.zeros_like(b) if x0 is None else np.array(x0, dtype=b.dtype, order="C", copy=True)
+        if M is not None and type(M) is not type(self):
+            raise TypeError(f"M must be a {type(self).__name__} (the factor of a matrix of the same format)")
+        info = _KrylovInfoC()
+        check(self._fn(f"krylov_{_sfx(b.dtype)}")(self._h, C.c_int(_krylov_method(method)), M._h if M is not None else None,
+                                                  _p(b), u64(b.size), _p(x), u64(x.size), C.c_double(tol), u64(maxit),
+                                                  C.byref(info)))
+        return x, _krylov_info(info)
+
+    def krylov_dev(self, b_ptr: int, x_ptr: int, method="cg", M=None, tol: float = 1e-8, maxit: int = 1000,
+                   stream=None) -> KrylovInfo:
+        """Device pointers: x holds x0 on entry and the result on exit; the call polls, so it synchronises `stream`."""
+        info = _KrylovInfoC()
+        check(self._fn(f"krylov_dev_{_sfx(self.dtype)}")(self._h, C.c_int(_krylov_method(method)),
+                                                         M._h if M is not None else None, vp(b_ptr), vp(x_ptr),
+                                                         C.c_double(tol), u64(maxit), _stream_ptr(stream), C.byref(info)))
+        return _krylov_info(info)
 
     def alloc_vectors(self, stream=None):
         """Device pointers (x, y) of vectors owned by this handle and placed so that the stores of y do not collide
@@ -658,6 +734,23 @@ class _Compressed:
             raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT,
                         f"solve_triangular: b has shape {b.shape} but the matrix has {self._nrows} rows")
         return self.device(device).trsv(b, lower, unit_diagonal)
+
+    def solve(self, b, method="cg", M=None, x0=None, tol: float = 1e-8, maxit: int = 1000, device: int = 0):
+        """x with A x = b by CG (`method="cg"`: A symmetric positive definite) or BiCGStab ("bicgstab") on the device,
+        optionally preconditioned by `M = a.ilu0()`; returns (x, info) with info.iterations, info.reason (0 converged to
+        dot(r, r) <= tol^2 dot(b, b), 1 maxit reached, 2 breakdown), info.residual_sq, info.rhs_sq, info.solve_ms.
+        Bit for bit the loops of include/spal.h.  The reference has no solver; a Rust binding adds it as a
+        method of the matrix types."""
+        b = np.asarray(b)
+        if self._nrows != self._ncols:
+            raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT, f"solve: the matrix is not square ({self._nrows} x {self._ncols})")
+        if b.ndim != 1 or b.shape[0] != self._nrows:
+            raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT, f"solve: b has shape {b.shape} but the matrix has {self._nrows} rows")
+        if x0 is not None and np.shape(x0) != b.shape:
+            raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT, f"solve: x0 has shape {np.shape(x0)} but b {b.shape}")
+        if M is not None and type(M) is not type(self):
+            raise TypeError(f"M must be a {type(self).__name__}, e.g. self.ilu0()")
+        return self.device(device).krylov(b, method, None if M is None else M.device(device), x0, tol, maxit)
 
     def _mul_mat(self, other, device: int = 0):
         """`&self * &other` (src/csr/ops/mul.rs:5-59 / src/csc/ops/mul.rs:5-60) on the device; the result is downloaded

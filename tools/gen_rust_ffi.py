@@ -15,6 +15,7 @@ OUT = os.path.join(ROOT, "rust_shim", "src", "ffi.rs")
 
 SCALARS = {"int": "c_int", "uint64_t": "u64", "uint32_t": "u32", "int64_t": "i64", "size_t": "usize", "double": "f64",
            "float": "f32", "void": "c_void", "char": "c_char"}
+STRUCTS = {"spal_krylov_info": "spal_krylov_info"}   # plain structs passed by pointer, declared in render()
 HANDLES = {"spal_csr_t": "spal_csr", "spal_csc_t": "spal_csc", "spal_coo_t": "spal_coo", "spal_mg_t": "spal_mg",
            "spal_mg_csr_t": "spal_mg_csr"}
 
@@ -31,7 +32,7 @@ def rust_type(ctype: str) -> str:
     if b in HANDLES:
         inner, stars = HANDLES[b], stars + 1      # the handle typedefs are pointers themselves
     else:
-        inner = SCALARS[b]
+        inner = STRUCTS.get(b) or SCALARS[b]
     out = inner
     for level in range(stars):
         # only the innermost pointer of `const T *` is const; handles and out-parameters are *mut
@@ -76,6 +77,13 @@ def render(fns) -> str:
               'pub const SPAL_ERR_UNSUPPORTED: c_int = 5;',
               'pub const SPAL_ERR_NO_DEVICE: c_int = 6;',
               'pub const SPAL_ERR_INDEX_OUT_OF_BOUNDS: c_int = 7;',
+              '',
+              'pub const SPAL_KRYLOV_CG: c_int = 0;',
+              'pub const SPAL_KRYLOV_BICGSTAB: c_int = 1;',
+              '/// What spal_*_krylov_* report: reason 0 converged, 1 maxit reached, 2 breakdown / not finite.',
+              '#[repr(C)] #[derive(Clone, Copy, Debug, Default)]',
+              'pub struct spal_krylov_info { pub iterations: u64, pub reason: c_int, pub residual_sq: f64, pub rhs_sq: f64, '
+              'pub solve_ms: f64 }',
               '',
               '#[link(name = "spal_hip")]',
               'extern "C" {']
