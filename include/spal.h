@@ -358,6 +358,65 @@ int spal_csc_trsv_dev_f64(spal_csc_t a, int uplo, int unit_diag, const double *b
 int spal_csc_trsv_dev_f32(spal_csc_t a, int uplo, int unit_diag, const float *b_dev, float *x_dev,
                           void *stream);
 
+/* ---- Jacobi sweeps on a triangle: an approximate L x = b / U x = b in s SpMV-shaped passes -------------
+ * Not in the reference.  The exact solve above is a chain of levels ordered by the stream, and the chain is a property
+ * of the matrix (8028 levels per triangle on the banded 1M x 1M factor).  A preconditioner does not need
+ * the exact solve: sweep(A, uplo, unit_diag, s, b) -> x replaces it by s Jacobi passes x <- D^-1 (b - N x) on the chosen
+ * triangle (N: the triangle off the diagonal), every pass one launch in which all rows are independent.  It gives up
+ * exactness of the SOLVE, not of the arithmetic: the contract is again a sequential text that the device reproduces bit
+ * for bit in f32 and f64 (NaN by position), T the handle's element type:
+ *   d[i]  = the stored (i, i) entry                      (unit_diag = 1: not read)
+ *   x0[i] = b[i] / d[i]                                  (unit_diag = 1: b[i])
+ *   for t = 1 .. s, every row i independently of the others:
+ *       acc = b[i]
+ *       for each stored (i, j, v) of the chosen triangle off the diagonal, in ascending column:
+ *           acc = acc - (v * x(t-1)[j])      -- product rounded, then the difference: no FMA
+ *       xt[i] = acc / d[i]                                (unit_diag = 1: acc)
+ *   result: xs
+ * Triangle selection (`uplo` 0: entries with j < i, 1: j > i), IEEE division and the errors are the exact solve's:
+ * SPAL_ERR_INVALID_ARGUMENT for A not square, unit_diag = 0 and a row without a stored (i, i) (the message names the
+ * first such row), flags outside {0, 1}, null pointers, wrong lengths, an _f64 entry on an f32 handle or the reverse;
+ * SPAL_ERR_UNSUPPORTED for a handle held as row blocks.  A stored zero diagonal is not an error (inf / NaN, propagating).
+ * Entries of the other triangle are ignored and their values never enter the arithmetic (they may be NaN).
+ * Two consequences:
+ *   EQUALITY WITH THE EXACT SOLVE.  A row of level l (as spal_trsv_levels defines it) holds its final value from x_l on,
+ *   NaN positions included: by induction the rows it reads, of levels < l, are final in x(l-1), so pass l performs the
+ *   operations of the sequential substitution on the same inputs, and so does every later pass.  Hence for
+ *   s >= nlevels - 1 the result is bit for bit that of spal_*_trsv_*.
+ *   CLAMPING.  nlevels <= n, so an s greater than n - 1 is clamped to n - 1 without changing a bit: a call enqueues at
+ *   most n launches whatever `sweeps` is.
+ * s = 0 on A itself is the Jacobi preconditioner D^-1 b.
+ * Preparation: a sweep needs, per row, the position of its first entry with column >= row and whether that is the
+ * diagonal.  One small kernel builds this on the first sweep call of a handle (under the handle's lock; it synchronises
+ * `stream` once to read back the first row without a diagonal).  There is no host analysis and no solve plan: after
+ * sweep calls alone describe() shows no "trsv" object.  Every later call allocates no handle state and synchronises
+ * nothing: x0 is one launch, every pass one more, ordered by the stream alone -- no atomics, no flags, nothing waits on
+ * another workgroup, so a call cannot hang.  The host forms copy b up, sweep, copy x back and synchronise.  The _dev
+ * forms enqueue on `stream`; x_dev == b_dev is allowed (a row reads only its own b[i]); the passes ping-pong through
+ * scratch taken from and returned to the runtime's stream-ordered allocator in stream order (as spal_dot_dev_*): none
+ * for s = 0, one vector for s = 1, two beyond -- two calls on different streams never share scratch.
+ * CSC handles sweep on their CSR twin.  Calls on one handle serialise on its lock, from any number of threads.
+ * describe() gains "trsv_sweep": {prepared, prepare_ms, block_rows = rows of a workgroup, chunk_entries = entries it
+ * stages in LDS at a time, calls} once the handle is prepared.
+ * Option "trsv_sweeps" (spal_csr_set_option / spal_csc_set_option on a factor, >= -1; default -1): read by
+ * spal_*_krylov_* from its `m` only (below); the spal_*_trsv_* entry points ignore it and stay exact. */
+int spal_csr_trsv_sweep_f64(spal_csr_t a, int uplo, int unit_diag, uint64_t sweeps, const double *b, uint64_t b_len,
+                            double *x, uint64_t x_len);                          /* host vectors */
+int spal_csr_trsv_sweep_f32(spal_csr_t a, int uplo, int unit_diag, uint64_t sweeps, const float *b, uint64_t b_len,
+                            float *x, uint64_t x_len);
+int spal_csr_trsv_sweep_dev_f64(spal_csr_t a, int uplo, int unit_diag, uint64_t sweeps, const double *b_dev,
+                                double *x_dev, void *stream);                    /* enqueued, not synchronised */
+int spal_csr_trsv_sweep_dev_f32(spal_csr_t a, int uplo, int unit_diag, uint64_t sweeps, const float *b_dev,
+                                float *x_dev, void *stream);
+int spal_csc_trsv_sweep_f64(spal_csc_t a, int uplo, int unit_diag, uint64_t sweeps, const double *b, uint64_t b_len,
+                            double *x, uint64_t x_len);
+int spal_csc_trsv_sweep_f32(spal_csc_t a, int uplo, int unit_diag, uint64_t sweeps, const float *b, uint64_t b_len,
+                            float *x, uint64_t x_len);
+int spal_csc_trsv_sweep_dev_f64(spal_csc_t a, int uplo, int unit_diag, uint64_t sweeps, const double *b_dev,
+                                double *x_dev, void *stream);
+int spal_csc_trsv_sweep_dev_f32(spal_csc_t a, int uplo, int unit_diag, uint64_t sweeps, const float *b_dev,
+                                float *x_dev, void *stream);
+
 /* ---- ILU(0): the incomplete LU factorisation without fill, CSR and CSC ------------------
  * Not in the reference; the contract is this sequential loop, which the device reproduces bit for bit in f32 and f64
  * (NaN by position).  A is square and stored as the handle stores it, columns strictly ascending inside a row, and every
@@ -405,8 +464,12 @@ int spal_csc_ilu0(spal_csc_t a, void *stream, spal_csc_t *out);
  *
  * The two loops.  All scalars are T.  thr = T(tol * tol) * bb with bb = dot(b, b) (tol is a double; tol * tol is formed
  * in double and rounded to T once).  x holds x0 on entry and the result on exit.  M^-1 v with a factor handle m is
- * trsv(m, lower, unit_diag = 1) followed by trsv(m, upper, unit_diag = 0); with m == NULL it is v itself.  Every
- * product alpha * v[i] is rounded before the sum it enters (no FMA).
+ * trsv(m, lower, unit_diag = 1) followed by trsv(m, upper, unit_diag = 0); with m == NULL it is v itself.  When m's
+ * option "trsv_sweeps" is s >= 0, M^-1 v is instead sweep(m, lower, unit_diag = 1, s, v) followed by
+ * sweep(m, upper, unit_diag = 0, s, .) -- the sweeps defined above, wherever "M^-1" stands in the two loops; -1, the
+ * default, means the exact solves.  M = A with "trsv_sweeps" = 0 is the Jacobi preconditioner: the lower sweep with a
+ * unit diagonal copies v, the upper one divides by the stored diagonal.  Every product alpha * v[i] is rounded before
+ * the sum it enters (no FMA).
  *   test (on rr):  rr <= thr: stop, reason 0;  else rr not finite: stop, reason 2;  else it == maxit: stop, reason 1.
  *   Nothing is an error because of values: a breakdown (a zero denominator, an overflow) shows as reason 2.
  *
@@ -444,7 +507,9 @@ int spal_csc_ilu0(spal_csc_t a, void *stream, spal_csc_t *out);
  * Option "krylov_check_every" (spal_csr_set_option / spal_csc_set_option on `a`, >= 1; 0 is refused): default 8 without
  * a preconditioner and 1 with one.  The bits do not depend on it.
  * Before the first iteration the call builds a's product plan and m's lower and upper solve plans if they do not exist
- * yet (a first touch is fine; it synchronises) and takes its work vectors from the caching allocator; no handle lock is
+ * yet (a first touch is fine; it synchronises) -- with "trsv_sweeps" >= 0 it prepares m for sweeps instead and
+ * analyses no triangle -- and takes its work vectors from the caching allocator (two more for the sweeps' ping-pong,
+ * so no iteration allocates); no handle lock is
  * held across a product or a solve (each takes its own), so calls on one handle from several threads are safe.
  * CSC handles multiply by their own SpMV route and solve on their CSR twin.  The _dev forms SYNCHRONISE `stream` (they
  * poll) and cannot be captured into a graph.
@@ -455,8 +520,8 @@ int spal_csc_ilu0(spal_csc_t a, void *stream, spal_csc_t *out);
  * negative or NaN; m with a row that stores no diagonal (the solve's own message); x_dev == b_dev.
  * SPAL_ERR_UNSUPPORTED: a handle held as row blocks.  Nothing leaks on failure.
  * describe() on `a` gains "krylov" after a solve: {method, preconditioned, iterations, reason, check_every, polls,
- * solve_ms} of the last call.
- * Not provided: capture into a graph, Jacobi, GMRES, several GPUs, a dot fused into the SpMV kernels. */
+ * solve_ms, precond_sweeps = m's "trsv_sweeps" (-1 without m)} of the last call.
+ * Not provided: capture into a graph, GMRES, several GPUs, a dot fused into the SpMV kernels. */
 enum { SPAL_KRYLOV_CG = 0, SPAL_KRYLOV_BICGSTAB = 1 };
 typedef struct spal_krylov_info {
     uint64_t iterations;

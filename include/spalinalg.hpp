@@ -65,6 +65,7 @@ template <> struct Abi<double> {
     static constexpr auto csr_spmv = spal_csr_spmv_f64;
     static constexpr auto csr_spmm = spal_csr_spmm_f64;
     static constexpr auto csr_trsv = spal_csr_trsv_f64;
+    static constexpr auto csr_trsv_sweep = spal_csr_trsv_sweep_f64;
     static constexpr auto csr_krylov = spal_csr_krylov_f64;
     static constexpr auto dot = spal_dot_f64;
     static constexpr auto csr_download = spal_csr_download_f64;
@@ -72,6 +73,7 @@ template <> struct Abi<double> {
     static constexpr auto csc_spmv = spal_csc_spmv_f64;
     static constexpr auto csc_spmm = spal_csc_spmm_f64;
     static constexpr auto csc_trsv = spal_csc_trsv_f64;
+    static constexpr auto csc_trsv_sweep = spal_csc_trsv_sweep_f64;
     static constexpr auto csc_krylov = spal_csc_krylov_f64;
     static constexpr auto coo_to_csr = spal_coo_to_csr_f64;
     static constexpr auto coo_to_csc = spal_coo_to_csc_f64;
@@ -82,6 +84,7 @@ template <> struct Abi<float> {
     static constexpr auto csr_spmv = spal_csr_spmv_f32;
     static constexpr auto csr_spmm = spal_csr_spmm_f32;
     static constexpr auto csr_trsv = spal_csr_trsv_f32;
+    static constexpr auto csr_trsv_sweep = spal_csr_trsv_sweep_f32;
     static constexpr auto csr_krylov = spal_csr_krylov_f32;
     static constexpr auto dot = spal_dot_f32;
     static constexpr auto csr_download = spal_csr_download_f32;
@@ -89,6 +92,7 @@ template <> struct Abi<float> {
     static constexpr auto csc_spmv = spal_csc_spmv_f32;
     static constexpr auto csc_spmm = spal_csc_spmm_f32;
     static constexpr auto csc_trsv = spal_csc_trsv_f32;
+    static constexpr auto csc_trsv_sweep = spal_csc_trsv_sweep_f32;
     static constexpr auto csc_krylov = spal_csc_krylov_f32;
     static constexpr auto coo_to_csr = spal_coo_to_csr_f32;
     static constexpr auto coo_to_csc = spal_coo_to_csc_f32;
@@ -204,6 +208,22 @@ class CsrMatrix {
         std::vector<T> x(nrows_);
         detail::check(detail::Abi<T>::csr_trsv(device_handle(), lower ? 0 : 1, unit_diagonal ? 1 : 0, b.data(), b.size(),
                                                x.data(), x.size()));
+        return x;
+    }
+
+    // `sweeps` Jacobi passes on the chosen triangle instead of the substitution (spal_csr_trsv_sweep_*, the sequential
+    // text in include/spal.h, bit for bit): an approximate solve in launches whose rows are all independent; from
+    // sweeps = levels - 1 on it IS solve_triangular's result.  Panics as solve_triangular does.
+    std::vector<T> solve_triangular_sweeps(const std::vector<T> &b, bool lower, bool unit_diagonal, std::uint64_t sweeps) const {
+        if (nrows_ != ncols_)
+            throw Panic(SPAL_ERR_INVALID_ARGUMENT, "solve_triangular_sweeps: the matrix is not square (" +
+                                                       std::to_string(nrows_) + " x " + std::to_string(ncols_) + ")");
+        if (b.size() != nrows_)
+            throw Panic(SPAL_ERR_INVALID_ARGUMENT, "solve_triangular_sweeps: b.len() = " + std::to_string(b.size()) +
+                                                       " but the matrix has " + std::to_string(nrows_) + " rows");
+        std::vector<T> x(nrows_);
+        detail::check(detail::Abi<T>::csr_trsv_sweep(device_handle(), lower ? 0 : 1, unit_diagonal ? 1 : 0, sweeps, b.data(),
+                                                     b.size(), x.data(), x.size()));
         return x;
     }
 
@@ -365,6 +385,22 @@ class CscMatrix {
         std::vector<T> x(nrows_);
         detail::check(detail::Abi<T>::csc_trsv(device_handle(), lower ? 0 : 1, unit_diagonal ? 1 : 0, b.data(), b.size(),
                                                x.data(), x.size()));
+        return x;
+    }
+
+    // `sweeps` Jacobi passes on the chosen triangle instead of the substitution (spal_csc_trsv_sweep_*, the sequential
+    // text in include/spal.h, bit for bit): an approximate solve in launches whose rows are all independent; from
+    // sweeps = levels - 1 on it IS solve_triangular's result.  Panics as solve_triangular does.
+    std::vector<T> solve_triangular_sweeps(const std::vector<T> &b, bool lower, bool unit_diagonal, std::uint64_t sweeps) const {
+        if (nrows_ != ncols_)
+            throw Panic(SPAL_ERR_INVALID_ARGUMENT, "solve_triangular_sweeps: the matrix is not square (" +
+                                                       std::to_string(nrows_) + " x " + std::to_string(ncols_) + ")");
+        if (b.size() != nrows_)
+            throw Panic(SPAL_ERR_INVALID_ARGUMENT, "solve_triangular_sweeps: b.len() = " + std::to_string(b.size()) +
+                                                       " but the matrix has " + std::to_string(nrows_) + " rows");
+        std::vector<T> x(nrows_);
+        detail::check(detail::Abi<T>::csc_trsv_sweep(device_handle(), lower ? 0 : 1, unit_diagonal ? 1 : 0, sweeps, b.data(),
+                                                     b.size(), x.data(), x.size()));
         return x;
     }
     // C = A * B: `impl Mul for &CscMatrix<T>` (src/csc/ops/mul.rs:5-60) on the device, bit-identical.

@@ -117,6 +117,8 @@ impl<T: HipScalar> DeviceCsr<T> {
     /// x with A x = b by CG (`ffi::SPAL_KRYLOV_CG`: A symmetric positive definite) or BiCGStab, optionally preconditioned by
     /// `m = self.ilu0(..)`; `x` holds x0 on entry and the result on exit.  Bit for bit the loops of include/spal.h; a
     /// breakdown is no panic but `reason == 2`.  Panics when the matrix is not square or a length differs.
+    /// `m.set_option("trsv_sweeps", s)` with s >= 0 makes the call apply `m` by s Jacobi sweeps per triangle instead of
+    /// the two exact solves (`self` as `m` with s = 0: Jacobi).
     pub fn solve(&self, method: c_int, m: Option<&DeviceCsr<T>>, b: &[T], x: &mut [T], tol: f64, maxit: u64) -> ffi::spal_krylov_info
     where T: HipKrylov {
         let mut info = ffi::spal_krylov_info::default();
@@ -133,6 +135,28 @@ impl<T: HipScalar> DeviceCsr<T> {
     pub unsafe fn solve_triangular_dev(&self, lower: bool, unit_diagonal: bool, b_dev: *const T, x_dev: *mut T, stream: *mut c_void)
     where T: HipTrsv {
         ffi::check(T::csr_trsv_dev(self.h, if lower { 0 } else { 1 }, unit_diagonal as c_int, b_dev, x_dev, stream));
+    }
+
+    /// `sweeps` Jacobi passes `x <- D^-1 (b - N x)` on the chosen triangle instead of the substitution: an approximate
+    /// solve whose every pass is one launch of independent rows.  Bit for bit the sequential text of include/spal.h;
+    /// from `sweeps = levels - 1` on it is `solve_triangular`'s result.  No host analysis.  Panics as `solve_triangular`.
+    pub fn solve_triangular_sweeps(&self, b: &[T], lower: bool, unit_diagonal: bool, sweeps: u64) -> Vec<T> where T: HipTrsv {
+        let (nrows, _, _) = self.shape();
+        assert_eq!(nrows, b.len());
+        let mut x = vec![T::zero(); nrows];
+        unsafe { ffi::check(T::csr_trsv_sweep(self.h, if lower { 0 } else { 1 }, unit_diagonal as c_int, sweeps, b, &mut x)); }
+        x
+    }
+
+    /// `solve_triangular_sweeps` on device pointers (`x_dev == b_dev` is allowed), enqueued on `stream` and not
+    /// synchronised once the handle is prepared (the first sweep call prepares it); scratch comes and goes in stream order.
+    ///
+    /// # Safety
+    /// `b_dev` and `x_dev` must hold `nrows` elements each.
+    pub unsafe fn solve_triangular_sweeps_dev(&self, lower: bool, unit_diagonal: bool, sweeps: u64, b_dev: *const T, x_dev: *mut T,
+                                              stream: *mut c_void)
+    where T: HipTrsv {
+        ffi::check(T::csr_trsv_sweep_dev(self.h, if lower { 0 } else { 1 }, unit_diagonal as c_int, sweeps, b_dev, x_dev, stream));
     }
 
     /// Builds the solve plan of one triangle now (host level analysis; synchronises `stream`).
@@ -292,6 +316,8 @@ impl<T: HipScalar> DeviceCsc<T> {
     /// x with A x = b by CG (`ffi::SPAL_KRYLOV_CG`: A symmetric positive definite) or BiCGStab, optionally preconditioned by
     /// `m = self.ilu0(..)`; `x` holds x0 on entry and the result on exit.  Bit for bit the loops of include/spal.h; a
     /// breakdown is no panic but `reason == 2`.  Panics when the matrix is not square or a length differs.
+    /// `m.set_option("trsv_sweeps", s)` with s >= 0 makes the call apply `m` by s Jacobi sweeps per triangle instead of
+    /// the two exact solves (`self` as `m` with s = 0: Jacobi).
     pub fn solve(&self, method: c_int, m: Option<&DeviceCsc<T>>, b: &[T], x: &mut [T], tol: f64, maxit: u64) -> ffi::spal_krylov_info
     where T: HipKrylov {
         let mut info = ffi::spal_krylov_info::default();
@@ -308,6 +334,28 @@ impl<T: HipScalar> DeviceCsc<T> {
     pub unsafe fn solve_triangular_dev(&self, lower: bool, unit_diagonal: bool, b_dev: *const T, x_dev: *mut T, stream: *mut c_void)
     where T: HipTrsv {
         ffi::check(T::csc_trsv_dev(self.h, if lower { 0 } else { 1 }, unit_diagonal as c_int, b_dev, x_dev, stream));
+    }
+
+    /// `sweeps` Jacobi passes `x <- D^-1 (b - N x)` on the chosen triangle instead of the substitution: an approximate
+    /// solve whose every pass is one launch of independent rows.  Bit for bit the sequential text of include/spal.h;
+    /// from `sweeps = levels - 1` on it is `solve_triangular`'s result.  No host analysis.  Panics as `solve_triangular`.
+    pub fn solve_triangular_sweeps(&self, b: &[T], lower: bool, unit_diagonal: bool, sweeps: u64) -> Vec<T> where T: HipTrsv {
+        let (nrows, _, _) = self.shape();
+        assert_eq!(nrows, b.len());
+        let mut x = vec![T::zero(); nrows];
+        unsafe { ffi::check(T::csc_trsv_sweep(self.h, if lower { 0 } else { 1 }, unit_diagonal as c_int, sweeps, b, &mut x)); }
+        x
+    }
+
+    /// `solve_triangular_sweeps` on device pointers (`x_dev == b_dev` is allowed), enqueued on `stream` and not
+    /// synchronised once the handle is prepared (the first sweep call prepares it); scratch comes and goes in stream order.
+    ///
+    /// # Safety
+    /// `b_dev` and `x_dev` must hold `nrows` elements each.
+    pub unsafe fn solve_triangular_sweeps_dev(&self, lower: bool, unit_diagonal: bool, sweeps: u64, b_dev: *const T, x_dev: *mut T,
+                                              stream: *mut c_void)
+    where T: HipTrsv {
+        ffi::check(T::csc_trsv_sweep_dev(self.h, if lower { 0 } else { 1 }, unit_diagonal as c_int, sweeps, b_dev, x_dev, stream));
     }
 
     /// Builds the solve plan of one triangle now (host level analysis; synchronises `stream`).

@@ -113,10 +113,16 @@ pub trait HipTrsv: HipScalar {
     unsafe fn csr_trsv_dev(a: *mut ffi::spal_csr, uplo: c_int, unit_diag: c_int, b: *const Self, x: *mut Self, stream: *mut c_void) -> c_int;
     unsafe fn csc_trsv(a: *mut ffi::spal_csc, uplo: c_int, unit_diag: c_int, b: &[Self], x: &mut [Self]) -> c_int;
     unsafe fn csc_trsv_dev(a: *mut ffi::spal_csc, uplo: c_int, unit_diag: c_int, b: *const Self, x: *mut Self, stream: *mut c_void) -> c_int;
+    // `sweeps` Jacobi passes on the triangle instead of the substitution (the spal_*_trsv_sweep_* entry points)
+    unsafe fn csr_trsv_sweep(a: *mut ffi::spal_csr, uplo: c_int, unit_diag: c_int, sweeps: u64, b: &[Self], x: &mut [Self]) -> c_int;
+    unsafe fn csr_trsv_sweep_dev(a: *mut ffi::spal_csr, uplo: c_int, unit_diag: c_int, sweeps: u64, b: *const Self, x: *mut Self, stream: *mut c_void) -> c_int;
+    unsafe fn csc_trsv_sweep(a: *mut ffi::spal_csc, uplo: c_int, unit_diag: c_int, sweeps: u64, b: &[Self], x: &mut [Self]) -> c_int;
+    unsafe fn csc_trsv_sweep_dev(a: *mut ffi::spal_csc, uplo: c_int, unit_diag: c_int, sweeps: u64, b: *const Self, x: *mut Self, stream: *mut c_void) -> c_int;
 }
 
 macro_rules! impl_hip_trsv {
-    ($t:ty, $csr_trsv:ident, $csr_trsv_dev:ident, $csc_trsv:ident, $csc_trsv_dev:ident) => {
+    ($t:ty, $csr_trsv:ident, $csr_trsv_dev:ident, $csc_trsv:ident, $csc_trsv_dev:ident,
+     $csr_sweep:ident, $csr_sweep_dev:ident, $csc_sweep:ident, $csc_sweep_dev:ident) => {
         impl HipTrsv for $t {
             unsafe fn csr_trsv(a: *mut ffi::spal_csr, uplo: c_int, unit_diag: c_int, b: &[Self], x: &mut [Self]) -> c_int {
                 ffi::$csr_trsv(a, uplo, unit_diag, b.as_ptr(), b.len() as u64, x.as_mut_ptr(), x.len() as u64)
@@ -130,11 +136,25 @@ macro_rules! impl_hip_trsv {
             unsafe fn csc_trsv_dev(a: *mut ffi::spal_csc, uplo: c_int, unit_diag: c_int, b: *const Self, x: *mut Self, stream: *mut c_void) -> c_int {
                 ffi::$csc_trsv_dev(a, uplo, unit_diag, b, x, stream)
             }
+            unsafe fn csr_trsv_sweep(a: *mut ffi::spal_csr, uplo: c_int, unit_diag: c_int, sweeps: u64, b: &[Self], x: &mut [Self]) -> c_int {
+                ffi::$csr_sweep(a, uplo, unit_diag, sweeps, b.as_ptr(), b.len() as u64, x.as_mut_ptr(), x.len() as u64)
+            }
+            unsafe fn csr_trsv_sweep_dev(a: *mut ffi::spal_csr, uplo: c_int, unit_diag: c_int, sweeps: u64, b: *const Self, x: *mut Self, stream: *mut c_void) -> c_int {
+                ffi::$csr_sweep_dev(a, uplo, unit_diag, sweeps, b, x, stream)
+            }
+            unsafe fn csc_trsv_sweep(a: *mut ffi::spal_csc, uplo: c_int, unit_diag: c_int, sweeps: u64, b: &[Self], x: &mut [Self]) -> c_int {
+                ffi::$csc_sweep(a, uplo, unit_diag, sweeps, b.as_ptr(), b.len() as u64, x.as_mut_ptr(), x.len() as u64)
+            }
+            unsafe fn csc_trsv_sweep_dev(a: *mut ffi::spal_csc, uplo: c_int, unit_diag: c_int, sweeps: u64, b: *const Self, x: *mut Self, stream: *mut c_void) -> c_int {
+                ffi::$csc_sweep_dev(a, uplo, unit_diag, sweeps, b, x, stream)
+            }
         }
     };
 }
-impl_hip_trsv!(f64, spal_csr_trsv_f64, spal_csr_trsv_dev_f64, spal_csc_trsv_f64, spal_csc_trsv_dev_f64);
-impl_hip_trsv!(f32, spal_csr_trsv_f32, spal_csr_trsv_dev_f32, spal_csc_trsv_f32, spal_csc_trsv_dev_f32);
+impl_hip_trsv!(f64, spal_csr_trsv_f64, spal_csr_trsv_dev_f64, spal_csc_trsv_f64, spal_csc_trsv_dev_f64,
+               spal_csr_trsv_sweep_f64, spal_csr_trsv_sweep_dev_f64, spal_csc_trsv_sweep_f64, spal_csc_trsv_sweep_dev_f64);
+impl_hip_trsv!(f32, spal_csr_trsv_f32, spal_csr_trsv_dev_f32, spal_csc_trsv_f32, spal_csc_trsv_dev_f32,
+               spal_csr_trsv_sweep_f32, spal_csr_trsv_sweep_dev_f32, spal_csc_trsv_sweep_f32, spal_csc_trsv_sweep_dev_f32);
 
 /// CG / BiCGStab and their dot product (the spal_*_krylov_* and spal_dot_* entry points): `method` is
 /// `ffi::SPAL_KRYLOV_CG` / `ffi::SPAL_KRYLOV_BICGSTAB`, `m` an ILU(0) factor handle or null.

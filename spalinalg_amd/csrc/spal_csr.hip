@@ -312,6 +312,7 @@ void csr_free(spal_csr *a) {
     (void)dev_free(a->d_win_groups);
     cblock_free(a);
     trsv_free(a);
+    trsv_sweep_free(a);
     (void)dev_free(a->d_x);
     (void)dev_free(a->d_y);
     stream_release(a->stream);

@@ -359,6 +359,13 @@ struct spal_csr {
     int trsv_analyses = 0;         // plans built so far (describe)
     // ILU(0) (spal_ilu.hip); the option guarded by mu
     int64_t ilu_wide_work = spal::kIluWideWorkDefault;   // option "ilu_wide_work": rows with at least this much work take the wide form
+    // Jacobi sweeps on a triangle (spal_trsv_sweep.hip); guarded by mu
+    int64_t trsv_sweeps = -1;      // option "trsv_sweeps": how spal_*_krylov_* applies this handle as M (-1: exact solves)
+    uint2 *d_sweep_rows = nullptr; // nrows x {first entry with column >= row, that + 1 if it is the diagonal}, built by the first sweep
+    int sweep_prepared = 0;
+    uint64_t sweep_first_missing = 0;   // the first row without a stored diagonal, nrows when there is none
+    double sweep_prepare_ms = 0.0;      // launch + read back, host clock
+    uint64_t sweep_calls = 0;           // sweep calls enqueued so far (describe)
 };
 
 struct spal_csc {
@@ -464,6 +471,8 @@ int spmm_launch(spal_csr *a, int tile, uint64_t k, const void *x_dev, uint64_t l
                 hipStream_t stream);
 // implemented in spal_trsv.hip: frees a handle's solve plans (csr_free)
 void trsv_free(spal_csr *a);
+// implemented in spal_trsv_sweep.hip: frees a handle's sweep preparation (csr_free)
+void trsv_sweep_free(spal_csr *a);
 // implemented in spal_csr_slide.hip: the sliding-window kernel for a plan with plan.slide set
 hipError_t launch_slide(const spal_csr *a, const void *x, void *y, hipStream_t st);
 // ... its plan (for csr_plan_build): decides whether it can run the chosen stream plan and builds its step descriptors

@@ -19,8 +19,9 @@
 // scalar launch after that clears it.
 //
 // THE DRIVER HOLDS NO HANDLE LOCK ACROSS A PRODUCT OR A SOLVE: it calls the spal_*_spmv_dev_* / spal_*_trsv_dev_* entry
-// points, each of which takes what it needs itself (f5b9766: re-entering a handle's lock deadlocks).  Plans are built
-// before the first iteration; work vectors, the scratch and the scalar block come from the caching allocator per call,
+// points, each of which takes what it needs itself (f5b9766: re-entering a handle's lock deadlocks).  A factor whose
+// option "trsv_sweeps" is s >= 0 is applied by s Jacobi sweeps per triangle instead (trsv_sweep_enqueue),
+// through two more work vectors of the call.  Plans are built before the first iteration; work vectors, the scratch and the scalar block come from the caching allocator per call,
 // so concurrent calls on one handle share nothing but the matrix.
 #include "spal_ops.hpp"
 
@@ -369,17 +370,18 @@ struct PinnedBuf {
 
 struct Record {
     int method = 0, preconditioned = 0, reason = 0;
+    int64_t precond_sweeps = -1;
     uint64_t iterations = 0, polls = 0;
     int64_t check_every = 0;
     double solve_ms = 0.0;
 };
 std::string info_json(const Record &r) {
-    char buf[320];
+    char buf[384];
     snprintf(buf, sizeof buf,
              "{\"method\": \"%s\", \"preconditioned\": %d, \"iterations\": %llu, \"reason\": %d, \"check_every\": %lld, "
-             "\"polls\": %llu, \"solve_ms\": %.4f}",
+             "\"polls\": %llu, \"solve_ms\": %.4f, \"precond_sweeps\": %lld}",
              r.method == SPAL_KRYLOV_CG ? "cg" : "bicgstab", r.preconditioned, (unsigned long long)r.iterations, r.reason,
-             (long long)r.check_every, (unsigned long long)r.polls, r.solve_ms);
+             (long long)r.check_every, (unsigned long long)r.polls, r.solve_ms, (long long)r.precond_sweeps);
     return buf;
 }
 
@@ -393,10 +395,16 @@ struct Run {
     T tol2 = T(0);
     Scal<T> *s = nullptr;
     T *part0 = nullptr, *part1 = nullptr;
+    int64_t sweeps = -1;            // m's option "trsv_sweeps"
+    T *w0 = nullptr, *w1 = nullptr; // the sweeps' ping-pong vectors
 
     int mul(const T *v, T *out) { return mul_dev(a, v, out, st); }
     // out = M^-1 v (out != v); without a preconditioner the caller uses v itself
     int prec(const T *v, T *out) {
+        if (sweeps >= 0) {
+            SPAL_TRY(trsv_sweep_enqueue(fn, solve_handle(m), 0, 1, (uint64_t)sweeps, v, out, w0, w1, st));
+            return trsv_sweep_enqueue(fn, solve_handle(m), 1, 0, (uint64_t)sweeps, out, out, w0, w1, st);
+        }
         SPAL_TRY(solve_dev(m, 0, 1, v, out, st));
         return solve_dev(m, 1, 0, out, out, st);
     }
@@ -431,13 +439,17 @@ int krylov_run(const char *fn, H *a, int method, H *m, const T *b, T *x, double 
 
     // plans first: nothing plans lazily once the iterations are being enqueued
     SPAL_TRY(product_plan(a));
-    if (m) {
+    const int64_t sweeps = m ? trsv_sweeps_of(solve_handle(m)) : -1;
+    if (m && sweeps >= 0) {
+        SPAL_TRY(trsv_sweep_prepare(fn, solve_handle(m), 0, st));   // no analysis; a row without a diagonal: the solve's own message
+    } else if (m) {
         SPAL_TRY(analyse(m, 0, 1, st));
         SPAL_TRY(analyse(m, 1, 0, st));   // a row without a diagonal: the solve's own message
     }
     // work vectors, scratch, scalars
     const bool cg = method == SPAL_KRYLOV_CG;
-    const int nvec = cg ? (m ? 4 : 3) : (m ? 8 : 6);
+    const int nwork = cg ? (m ? 4 : 3) : (m ? 8 : 6);
+    const int nvec = nwork + (sweeps >= 0 ? 2 : 0);
     DevBuf vecs, parts, scal;
     PinnedBuf host;
     EventSpans ev;
@@ -462,6 +474,11 @@ int krylov_run(const char *fn, H *a, int method, H *m, const T *b, T *x, double 
     R.s = scal.as<Scal<T>>();
     R.part0 = parts.as<T>();
     R.part1 = parts.as<T>() + pe;
+    R.sweeps = sweeps;
+    if (sweeps >= 0) {
+        R.w0 = vec_at(nwork);
+        R.w1 = vec_at(nwork + 1);
+    }
 
     Scal<T> *h = (Scal<T> *)host.p;
     uint64_t polls = 0;
@@ -551,6 +568,7 @@ int krylov_run(const char *fn, H *a, int method, H *m, const T *b, T *x, double 
     Record rec;
     rec.method = method;
     rec.preconditioned = m ? 1 : 0;
+    rec.precond_sweeps = sweeps;
     rec.reason = info->reason;
     rec.iterations = info->iterations;
     rec.polls = polls;

@@ -1,5 +1,5 @@
 // spal_ops.hpp -- the host layer the sparse operations share: spal_spgemm.hip, spal_spadd.hip,
-// spal_spmm.hip, spal_trsv.hip, spal_ilu.hip and spal_krylov.hip keep their kernels, their driver, their option's validation and their
+// spal_spmm.hip, spal_trsv.hip, spal_trsv_sweep.hip, spal_ilu.hip and spal_krylov.hip keep their kernels, their driver, their option's validation and their
 // info JSON; what surrounds a launch the same way in each of them is here, once.  (Not installed.)
 #pragma once
 
@@ -81,6 +81,22 @@ int check_same_device_and_dtype(const char *fn, const H *a, const H *b) {
     return SPAL_OK;
 }
 
+// the exact solve's and the sweeps' flags, and what both refuse of a handle before they look at its entries
+inline int check_uplo_unit(const char *fn, int uplo, int unit_diag) {
+    if (uplo != 0 && uplo != 1) return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: uplo = %d must be 0 (lower) or 1 (upper)", fn, uplo);
+    if (unit_diag != 0 && unit_diag != 1)
+        return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: unit_diag = %d must be 0 or 1", fn, unit_diag);
+    return SPAL_OK;
+}
+inline int check_solvable(const char *fn, const spal_csr *a) {
+    if (!a->parts.empty())
+        return fail(SPAL_ERR_UNSUPPORTED, "%s: handles held as row blocks (more than 2^32 - 65537 entries) have no solve", fn);
+    if (a->nrows != a->ncols)
+        return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: the matrix is not square (%llu x %llu)", fn,
+                    (unsigned long long)a->nrows, (unsigned long long)a->ncols);
+    return SPAL_OK;
+}
+
 // ---- CSR and CSC through one body ----------------------------------------------------------------------------------
 // Either handle type's arrays as an operand: CSC's (colptr, rowind) are the CSR arrays of the transpose.
 struct Operand {
@@ -149,6 +165,16 @@ struct OpArrays {
 int transpose_device(int device, int elem_size, uint64_t nmajor, uint64_t nminor, uint64_t nnz, const uint32_t *d_ptr,
                      const uint32_t *d_ind, const void *d_val, hipStream_t st, OpArrays &out);
 
+// ---- Jacobi sweeps on a triangle, for callers that bring their own scratch (spal_trsv_sweep.hip) --------
+// Both take a->mu themselves.  prepare: builds the handle's sweep rows if it has none (synchronises `st`); refuses what
+// the exact solve refuses, a row without a diagonal unless unit_diag.  enqueue: x = sweep(a, uplo, unit_diag, sweeps, b)
+// on `st`, allocating and synchronising nothing on a prepared handle; b, x, w0, w1 are device vectors of a's element
+// type, w0 is written when sweeps >= 1 and w1 when sweeps >= 2, x may be b.
+int trsv_sweep_prepare(const char *fn, spal_csr *a, int unit_diag, hipStream_t st);
+int trsv_sweep_enqueue(const char *fn, spal_csr *a, int uplo, int unit_diag, uint64_t sweeps, const void *b, void *x,
+                       void *w0, void *w1, hipStream_t st);
+int64_t trsv_sweeps_of(spal_csr *a);   // the option "trsv_sweeps" of a solve handle, read under its lock
+
 // ---- per-operation state of a handle (spal_internal.hpp: OpState), set and described in one place -------------------
 // Each operation file implements its own: 1 = the key is this operation's and *status says how setting it went, 0 =
 // another key.  The solve's and ILU(0)'s options live on the solve handle, under its `mu`.
@@ -156,11 +182,13 @@ int spgemm_option(const char *key, int64_t value, OpState &s, int *status);   //
 int spadd_option(const char *key, int64_t value, OpState &s, int *status);    // "spadd_tile"
 int spmm_option(const char *key, int64_t value, OpState &s, int *status);     // "spmm_tile"
 int trsv_option(spal_csr *a, const char *key, int64_t value, int *status);    // "trsv_chain_rows" (launch lists rebuilt)
+int trsv_sweep_option(spal_csr *a, const char *key, int64_t value, int *status);   // "trsv_sweeps"
 int ilu_option(spal_csr *a, const char *key, int64_t value, int *status);     // "ilu_wide_work"
 int krylov_option(spal_csr *a, const char *key, int64_t value, OpState &s, int *status);   // "krylov_check_every"
 inline int ops_set_option(OpState &s, spal_csr *solve, const char *key, int64_t value, int *status) {
     return spgemm_option(key, value, s, status) || spadd_option(key, value, s, status) ||
            spmm_option(key, value, s, status) || trsv_option(solve, key, value, status) ||
+           trsv_sweep_option(solve, key, value, status) ||
            ilu_option(solve, key, value, status) || krylov_option(solve, key, value, s, status);
 }
 
@@ -168,6 +196,8 @@ inline int ops_set_option(OpState &s, spal_csr *solve, const char *key, int64_t 
 // the "spmm" / "trsv" objects of a handle an SpMM ran on / a triangle of which was analysed (spal_spmm.hip, spal_trsv.hip)
 int spmm_describe_append(char *buf, size_t buf_len, const spal_csr *a);
 int trsv_describe_append(char *buf, size_t buf_len, spal_csr *a);
+// the "trsv_sweep" object of a handle prepared for Jacobi sweeps (spal_trsv_sweep.hip)
+int trsv_sweep_describe_append(char *buf, size_t buf_len, spal_csr *a);
 // the "krylov" object of a handle a solve ran with as A (spal_krylov.hip; the string is read under the solve handle's lock)
 int krylov_describe_append(char *buf, size_t buf_len, const OpState &s, spal_csr *solve);
 inline int ops_describe_append(char *buf, size_t buf_len, const OpState &s, spal_csr *solve) {
@@ -175,6 +205,7 @@ inline int ops_describe_append(char *buf, size_t buf_len, const OpState &s, spal
     SPAL_TRY(describe_append(buf, buf_len, "spadd", s.spadd_info));     // a result of spal_*_add / _sub / _neg
     SPAL_TRY(spmm_describe_append(buf, buf_len, solve));                // an SpMM ran on it
     SPAL_TRY(trsv_describe_append(buf, buf_len, solve));                // a triangle of it was analysed for a solve
+    SPAL_TRY(trsv_sweep_describe_append(buf, buf_len, solve));          // it was prepared for sweeps on a triangle
     SPAL_TRY(describe_append(buf, buf_len, "ilu0", s.ilu_info));        // a factor of spal_*_ilu0: how it was built
     return krylov_describe_append(buf, buf_len, s, solve);              // spal_*_krylov_* ran with it as A: the last call
 }

@@ -199,20 +199,9 @@ int plan_build(spal_csr *a, int uplo, hipStream_t st) {
     return SPAL_OK;
 }
 
-int check_flags(const char *fn, int uplo, int unit_diag) {
-    if (uplo != 0 && uplo != 1) return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: uplo = %d must be 0 (lower) or 1 (upper)", fn, uplo);
-    if (unit_diag != 0 && unit_diag != 1)
-        return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: unit_diag = %d must be 0 or 1", fn, unit_diag);
-    return SPAL_OK;
-}
-
 // The plan of `uplo`, built now if this is the first use; a->mu is held.
 int plan_get(const char *fn, spal_csr *a, int uplo, int unit_diag, hipStream_t st, TrsvPlan **out) {
-    if (!a->parts.empty())
-        return fail(SPAL_ERR_UNSUPPORTED, "%s: handles held as row blocks (more than 2^32 - 65537 entries) have no solve", fn);
-    if (a->nrows != a->ncols)
-        return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: the matrix is not square (%llu x %llu)", fn,
-                    (unsigned long long)a->nrows, (unsigned long long)a->ncols);
+    SPAL_TRY(check_solvable(fn, a));
     if (!a->trsv[uplo]) SPAL_TRY(plan_build(a, uplo, st));
     TrsvPlan *p = a->trsv[uplo];
     if (!unit_diag && p->first_missing_diag < a->nrows) return trsv_missing_diag(fn, p->first_missing_diag);
@@ -250,7 +239,7 @@ template <typename T, typename H>
 int trsv_host(const char *fn, H *a, int uplo, int unit_diag, const T *b, uint64_t b_len, T *x, uint64_t x_len) {
     if (!a) return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: handle is NULL", fn);
     SPAL_TRY(check_dtype<T>(fn, a->elem_size));
-    SPAL_TRY(check_flags(fn, uplo, unit_diag));
+    SPAL_TRY(check_uplo_unit(fn, uplo, unit_diag));
     DeviceGuard guard(a->device);
     if (guard.status != SPAL_OK) return guard.status;
     return solve_host<T>(fn, solve_handle(a), uplo, unit_diag, b, b_len, x, x_len);
@@ -260,7 +249,7 @@ template <typename T, typename H>
 int trsv_dev(const char *fn, H *a, int uplo, int unit_diag, const T *b, T *x, void *stream) {
     if (!a) return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: handle is NULL", fn);
     SPAL_TRY(check_dtype<T>(fn, a->elem_size));
-    SPAL_TRY(check_flags(fn, uplo, unit_diag));
+    SPAL_TRY(check_uplo_unit(fn, uplo, unit_diag));
     if (!b || !x) return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: null vector", fn);
     DeviceGuard guard(a->device);
     if (guard.status != SPAL_OK) return guard.status;
@@ -274,7 +263,7 @@ int trsv_analyse(const char *fn, H *a, int uplo, int unit_diag, void *stream) {
     if (!a) return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: handle is NULL", fn);
     DeviceGuard guard(a->device);
     if (guard.status != SPAL_OK) return guard.status;
-    SPAL_TRY(check_flags(fn, uplo, unit_diag));
+    SPAL_TRY(check_uplo_unit(fn, uplo, unit_diag));
     spal_csr *s = solve_handle(a);
     std::lock_guard<std::mutex> lock(s->mu);
     TrsvPlan *p = nullptr;

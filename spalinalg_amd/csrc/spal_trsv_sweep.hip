@@ -1,0 +1,335 @@
+// spal_trsv_sweep.hip -- Jacobi sweeps on a triangle of a CSR handle: an approximate L x = b / U x = b whose
+// every pass is SpMV-shaped.  The contract (include/spal.h): x0[i] = b[i] / d[i]; for t = 1 .. s, every row on its own,
+// acc = b[i]; acc = acc - (v * x(t-1)[j]) over the row's entries of the chosen triangle off the diagonal in ascending
+// column, product and difference rounded separately; xt[i] = acc / d[i].  A row of level l performs from pass l on the
+// operations of the sequential substitution on the same inputs, so s >= levels - 1 gives the exact solve's bits.
+//
+// ONE PASS IS ONE LAUNCH; ORDER BETWEEN PASSES IS STREAM ORDER ALONE: no atomics, no flags, nothing waits on another
+// workgroup.  A workgroup owns kBlockRows consecutive rows and walks their contiguous entries [rowptr[r0], rowptr[r1])
+// in chunks of kChunk:
+//   * every thread streams values and columns along the entry stream (coalesced, load_stream), finds an entry's row by
+//     a binary search in the block's row pointers (LDS) and, for entries of the chosen triangle ONLY, gathers
+//     x(t-1)[col] and puts the rounded product into LDS at the entry's place.  Entries of the other triangle -- half of
+//     an ILU factor -- are streamed past: contiguous with the rest, never gathered for, never multiplied;
+//   * after a barrier the thread that owns a row subtracts the row's products of this chunk from its accumulator, in
+//     stored order.  The accumulator lives in a register across chunks: a row of any length works;
+//   * after the last chunk it divides and stores.
+// The products' LDS image is skewed by one element per 32 (slot): the row threads read at a stride of their row length,
+// and a length of 16 or 32 would otherwise put a half-wave on two banks (guide: LDS, bank = dword address mod 64 / 32).
+//
+// WHAT A HANDLE NEEDS is, per row, the position of its first entry with column >= row and whether that entry is the
+// diagonal: sweep_rows {dlo, dhi}, the lower triangle's entries are [rowptr[i], dlo), the upper's [dhi, rowptr[i + 1])
+// and the diagonal is stored, at dlo, exactly when dhi > dlo.  One kernel over the rows builds it (a binary search in the
+// row's ascending columns, an atomic min for the first row without a diagonal) on the first sweep call, under the
+// handle's lock.  No host analysis, no TrsvPlan.
+#include "spal_ops.hpp"
+
+#include "csr_kernels.hpp"
+
+#pragma clang fp contract(off)
+
+namespace spal {
+namespace {
+
+constexpr int kBlockRows = 256;        // rows of a workgroup = its threads
+constexpr uint32_t kChunk = 2048;      // entries of a chunk: 16.5 KiB of f64 products, so LDS never bounds residency
+constexpr int kPerThread = kChunk / kBlockRows;
+
+__host__ __device__ constexpr uint32_t slot(uint32_t e) { return e + (e >> 5); }
+
+// ---- preparation ----------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void sweep_prepare(uint32_t n, const uint32_t *__restrict__ rowptr,
+                                                     const uint32_t *__restrict__ colind, uint2 *__restrict__ rows,
+                                                     uint32_t *first_missing) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    uint32_t lo = rowptr[i];
+    const uint32_t end = rowptr[i + 1];
+    uint32_t hi = end;
+    while (lo < hi) {   // the first entry with column >= i
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (colind[mid] < (uint32_t)i) lo = mid + 1; else hi = mid;
+    }
+    const bool has = lo < end && colind[lo] == (uint32_t)i;
+    rows[i] = make_uint2(lo, lo + (has ? 1u : 0u));
+    if (!has) atomicMin(first_missing, (uint32_t)i);
+}
+
+// ---- s = 0: the diagonal scaling ------------------------------------------------------------------------------------
+template <typename T>
+__global__ __launch_bounds__(256) void sweep_scale(uint32_t n, const uint2 *__restrict__ rows, const T *__restrict__ values,
+                                                   const T *b, T *x, int unit_diag) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const T s = b[i];
+    x[i] = unit_diag ? s : s / values[rows[i].x];
+}
+
+// ---- one pass -------------------------------------------------------------------------------------------------------
+// b and xout may be the same array (row i reads b[i] before it stores xout[i], and nothing else of b); xin is neither.
+template <typename T, int UPLO>
+__global__ __launch_bounds__(kBlockRows) void sweep_pass(uint32_t n, const uint32_t *__restrict__ rowptr,
+                                                         const uint32_t *__restrict__ colind,
+                                                         const T *__restrict__ values, const uint2 *__restrict__ rows,
+                                                         const T *b, const T *__restrict__ xin, T *xout, int unit_diag) {
+    __shared__ uint32_t s_rp[kBlockRows + 1];
+    __shared__ T s_prod[slot(kChunk) + 1];
+    const uint32_t tid = threadIdx.x;
+    const uint64_t r0 = (uint64_t)blockIdx.x * kBlockRows;
+    const uint32_t nr = (uint32_t)min((uint64_t)kBlockRows, (uint64_t)n - r0);   // rows of this block, >= 1
+    // row pointers of the block; past its last row the end repeats, so the search never leaves the block
+    s_rp[tid] = rowptr[r0 + min(tid, nr)];
+    if (tid == 0) s_rp[kBlockRows] = rowptr[r0 + nr];
+    const bool mine = tid < nr;
+    const uint32_t row = (uint32_t)r0 + tid;
+    uint32_t p0 = 0, p1 = 0, dp = 0;
+    T acc = T(0);
+    if (mine) {
+        const uint2 rd = rows[row];
+        dp = rd.x;
+        if (UPLO == 0) {
+            p0 = rowptr[row];
+            p1 = rd.x;
+        } else {
+            p0 = rd.y;
+            p1 = rowptr[row + 1];
+        }
+        acc = b[row];
+    }
+    __syncthreads();
+    const uint32_t e0 = s_rp[0], e1 = s_rp[kBlockRows];
+    for (uint32_t c0 = e0; c0 < e1; c0 += kChunk) {
+        const uint32_t lim = min(e1 - c0, kChunk);   // entries of this chunk, >= 1
+        uint32_t col[kPerThread];
+        T val[kPerThread];
+#pragma unroll
+        for (int u = 0; u < kPerThread; ++u) {   // past the chunk's end its last entry's addresses repeat
+            const uint32_t q = c0 + min(tid + (uint32_t)u * kBlockRows, lim - 1);
+            col[u] = load_stream(colind + q);
+            val[u] = load_stream(values + q);
+        }
+#pragma unroll
+        for (int u = 0; u < kPerThread; ++u) {
+            const uint32_t k = tid + (uint32_t)u * kBlockRows;
+            if (k < lim) {
+                const uint32_t e = c0 + k;
+                uint32_t r = 0;   // the last row of the block with s_rp[r] <= e: the row that holds entry e
+#pragma unroll
+                for (uint32_t step = kBlockRows / 2; step >= 1; step >>= 1)
+                    if (s_rp[r + step] <= e) r += step;
+                const uint32_t grow = (uint32_t)r0 + r;
+                if (UPLO == 0 ? col[u] < grow : col[u] > grow) s_prod[slot(k)] = val[u] * xin[col[u]];
+            }
+        }
+        __syncthreads();
+        if (mine) {
+            const uint32_t a = max(p0, c0), z = min(p1, c0 + lim);   // (c0 + lim <= e1: no overflow)
+            for (uint32_t p = a; p < z; ++p) acc = acc - s_prod[slot(p - c0)];
+        }
+        __syncthreads();
+    }
+    if (mine) xout[row] = unit_diag ? acc : acc / values[dp];   // plain division: correctly rounded
+}
+
+// ---- host side ------------------------------------------------------------------------------------------------------
+// The refusals of the exact solve, in its order and words; builds sweep_rows on first use.  a->mu is held.
+int prepare_locked(const char *fn, spal_csr *a, int unit_diag, hipStream_t st) {
+    SPAL_TRY(check_solvable(fn, a));
+    if (!a->sweep_prepared) {
+        const auto t0 = std::chrono::steady_clock::now();
+        const uint32_t n = (uint32_t)a->nrows;
+        DevBuf rows, missing;
+        SPAL_HIP_TRY(rows.alloc((size_t)n * sizeof(uint2)));
+        SPAL_HIP_TRY(missing.alloc(sizeof(uint32_t)));
+        uint32_t first = n;
+        SPAL_HIP_TRY(hipMemcpyAsync(missing.p, &first, sizeof first, hipMemcpyHostToDevice, st));
+        if (n) {
+            hipLaunchKernelGGL(sweep_prepare, dim3(grid_of(n, 256)), dim3(256), 0, st, n, a->d_rowptr, a->d_colind,
+                               rows.as<uint2>(), missing.as<uint32_t>());
+            SPAL_HIP_TRY(hipGetLastError());
+        }
+        SPAL_HIP_TRY(hipMemcpyAsync(&first, missing.p, sizeof first, hipMemcpyDeviceToHost, st));
+        SPAL_HIP_TRY(hipStreamSynchronize(st));
+        a->d_sweep_rows = (uint2 *)rows.release();
+        a->sweep_first_missing = first;
+        a->sweep_prepare_ms = ms_since(t0);
+        a->sweep_prepared = 1;
+    }
+    if (!unit_diag && a->sweep_first_missing < a->nrows) return trsv_missing_diag(fn, a->sweep_first_missing);
+    return SPAL_OK;
+}
+
+// s beyond n - 1 changes no bit (every row is final from the pass of its level on, and levels <= n)
+inline uint64_t clamp_sweeps(const spal_csr *a, uint64_t sweeps) {
+    return std::min<uint64_t>(sweeps, a->nrows ? a->nrows - 1 : 0);
+}
+inline int scratch_vectors(uint64_t s) { return s == 0 ? 0 : s == 1 ? 1 : 2; }
+
+// The launches of one call on a prepared handle: x0 and s passes, ping-pong through w0 / w1, the last one into x.
+template <typename T>
+hipError_t enqueue_t(const spal_csr *a, int uplo, int unit_diag, uint64_t s, const T *b, T *x, T *w0, T *w1, hipStream_t st) {
+    const uint32_t n = (uint32_t)a->nrows;
+    if (!n) return hipSuccess;
+    const T *values = (const T *)a->d_values;
+    T *cur = s == 0 ? x : w0;
+    hipLaunchKernelGGL((sweep_scale<T>), dim3(grid_of(n, 256)), dim3(256), 0, st, n, a->d_sweep_rows, values, b, cur,
+                       unit_diag);
+    hipError_t e = hipGetLastError();
+    for (uint64_t t = 1; t <= s && e == hipSuccess; ++t) {
+        T *out = t == s ? x : (cur == w0 ? w1 : w0);
+        if (uplo)
+            hipLaunchKernelGGL((sweep_pass<T, 1>), dim3(grid_of(n, kBlockRows)), dim3(kBlockRows), 0, st, n, a->d_rowptr,
+                               a->d_colind, values, a->d_sweep_rows, b, cur, out, unit_diag);
+        else
+            hipLaunchKernelGGL((sweep_pass<T, 0>), dim3(grid_of(n, kBlockRows)), dim3(kBlockRows), 0, st, n, a->d_rowptr,
+                               a->d_colind, values, a->d_sweep_rows, b, cur, out, unit_diag);
+        e = hipGetLastError();
+        cur = out;
+    }
+    return e;
+}
+
+template <typename T>
+int enqueue_locked(const char *fn, spal_csr *a, int uplo, int unit_diag, uint64_t s, const T *b, T *x, T *w0, T *w1,
+                   hipStream_t st) {
+    const hipError_t e = enqueue_t<T>(a, uplo, unit_diag, s, b, x, w0, w1, st);
+    if (e != hipSuccess) return fail(SPAL_ERR_HIP, "%s: launch failed: %s", fn, hipGetErrorString(e));
+    ++a->sweep_calls;
+    return SPAL_OK;
+}
+
+template <typename T>
+int sweep_host_locked(const char *fn, spal_csr *a, int uplo, int unit_diag, uint64_t sweeps, const T *b, uint64_t b_len,
+                      T *x, uint64_t x_len) {
+    if (!b || !x) return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: null vector", fn);
+    if (b_len != a->nrows || x_len != a->nrows)
+        return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: b.len() = %llu and x.len() = %llu but the matrix has %llu rows", fn,
+                    (unsigned long long)b_len, (unsigned long long)x_len, (unsigned long long)a->nrows);
+    std::lock_guard<std::mutex> lock(a->mu);
+    SPAL_TRY(prepare_locked(fn, a, unit_diag, a->stream));
+    const uint64_t s = clamp_sweeps(a, sweeps), n = a->nrows;
+    const uint64_t stride = (n + 63) & ~(uint64_t)63;
+    DevBuf v;   // b / x, then the scratch vectors
+    SPAL_HIP_TRY(v.alloc((size_t)(1 + scratch_vectors(s)) * stride * sizeof(T)));
+    T *d = v.as<T>();
+    SPAL_HIP_TRY(hipMemcpyAsync(d, b, n * sizeof(T), hipMemcpyHostToDevice, a->stream));
+    SPAL_TRY(enqueue_locked<T>(fn, a, uplo, unit_diag, s, d, d, d + stride, d + 2 * stride, a->stream));
+    SPAL_HIP_TRY(hipMemcpyAsync(x, d, n * sizeof(T), hipMemcpyDeviceToHost, a->stream));
+    SPAL_HIP_TRY(hipStreamSynchronize(a->stream));
+    return SPAL_OK;
+}
+
+template <typename T, typename H>
+int sweep_host(const char *fn, H *a, int uplo, int unit_diag, uint64_t sweeps, const T *b, uint64_t b_len, T *x,
+               uint64_t x_len) {
+    SPAL_TRY(check_uplo_unit(fn, uplo, unit_diag));   // first: it needs no handle
+    if (!a) return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: handle is NULL", fn);
+    SPAL_TRY(check_dtype<T>(fn, a->elem_size));
+    DeviceGuard guard(a->device);
+    if (guard.status != SPAL_OK) return guard.status;
+    return sweep_host_locked<T>(fn, solve_handle(a), uplo, unit_diag, sweeps, b, b_len, x, x_len);
+}
+
+// The scratch is taken and returned in stream order (as spal_dot_dev_*): a block of the caching allocator would have to
+// wait for the device before it could be handed out again, and two calls on different streams never share one.
+template <typename T, typename H>
+int sweep_dev(const char *fn, H *a, int uplo, int unit_diag, uint64_t sweeps, const T *b, T *x, void *stream) {
+    SPAL_TRY(check_uplo_unit(fn, uplo, unit_diag));   // first: it needs no handle
+    if (!a) return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: handle is NULL", fn);
+    SPAL_TRY(check_dtype<T>(fn, a->elem_size));
+    if (!b || !x) return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: null vector", fn);
+    DeviceGuard guard(a->device);
+    if (guard.status != SPAL_OK) return guard.status;
+    const hipStream_t st = (hipStream_t)stream;
+    spal_csr *h = solve_handle(a);
+    std::lock_guard<std::mutex> lock(h->mu);
+    SPAL_TRY(prepare_locked(fn, h, unit_diag, st));
+    const uint64_t s = clamp_sweeps(h, sweeps);
+    const uint64_t stride = (h->nrows + 63) & ~(uint64_t)63;
+    const int nw = scratch_vectors(s);
+    void *w = nullptr;
+    if (nw) SPAL_HIP_TRY(hipMallocAsync(&w, (size_t)nw * stride * sizeof(T), st));
+    const int status = enqueue_locked<T>(fn, h, uplo, unit_diag, s, b, x, (T *)w, nw > 1 ? (T *)w + stride : nullptr, st);
+    if (nw) {
+        const hipError_t e = hipFreeAsync(w, st);
+        if (status == SPAL_OK) SPAL_HIP_TRY(e);
+    }
+    return status;
+}
+
+}  // namespace
+
+int trsv_sweep_prepare(const char *fn, spal_csr *a, int unit_diag, hipStream_t st) {
+    std::lock_guard<std::mutex> lock(a->mu);
+    return prepare_locked(fn, a, unit_diag, st);
+}
+
+int trsv_sweep_enqueue(const char *fn, spal_csr *a, int uplo, int unit_diag, uint64_t sweeps, const void *b, void *x,
+                       void *w0, void *w1, hipStream_t st) {
+    std::lock_guard<std::mutex> lock(a->mu);
+    SPAL_TRY(prepare_locked(fn, a, unit_diag, st));   // prepared by the caller: the refusals only
+    const uint64_t s = clamp_sweeps(a, sweeps);
+    return a->elem_size == 8
+               ? enqueue_locked<double>(fn, a, uplo, unit_diag, s, (const double *)b, (double *)x, (double *)w0, (double *)w1, st)
+               : enqueue_locked<float>(fn, a, uplo, unit_diag, s, (const float *)b, (float *)x, (float *)w0, (float *)w1, st);
+}
+
+int64_t trsv_sweeps_of(spal_csr *a) {
+    std::lock_guard<std::mutex> lock(a->mu);
+    return a->trsv_sweeps;
+}
+
+int trsv_sweep_option(spal_csr *a, const char *key, int64_t value, int *status) {
+    if (strcmp(key, "trsv_sweeps")) return 0;
+    if (value < -1) {
+        *status = fail(SPAL_ERR_INVALID_ARGUMENT,
+                       "trsv_sweeps must be >= -1 (-1: spal_*_krylov_* applies this factor by exact solves; s >= 0: by s Jacobi sweeps per triangle)");
+        return 1;
+    }
+    std::lock_guard<std::mutex> lock(a->mu);
+    a->trsv_sweeps = value;
+    *status = SPAL_OK;
+    return 1;
+}
+
+void trsv_sweep_free(spal_csr *a) {
+    (void)dev_free(a->d_sweep_rows);
+    a->d_sweep_rows = nullptr;
+    a->sweep_prepared = 0;
+}
+
+int trsv_sweep_describe_append(char *buf, size_t buf_len, spal_csr *a) {
+    if (!a) return SPAL_OK;
+    char info[256];
+    {
+        std::lock_guard<std::mutex> lock(a->mu);
+        if (!a->sweep_prepared) return SPAL_OK;
+        snprintf(info, sizeof info,
+                 "{\"prepared\": 1, \"prepare_ms\": %.3f, \"block_rows\": %d, \"chunk_entries\": %u, \"calls\": %llu}",
+                 a->sweep_prepare_ms, kBlockRows, kChunk, (unsigned long long)a->sweep_calls);
+    }
+    return describe_append(buf, buf_len, "trsv_sweep", info);
+}
+
+}  // namespace spal
+
+using namespace spal;
+
+extern "C" {
+
+#define SPAL_SWEEP_ENTRIES(kind, sfx, T)                                                                                   \
+    int spal_##kind##_trsv_sweep_##sfx(spal_##kind##_t a, int uplo, int unit_diag, uint64_t sweeps, const T *b,           \
+                                       uint64_t b_len, T *x, uint64_t x_len) {                                            \
+        return sweep_host<T>("spal_" #kind "_trsv_sweep", a, uplo, unit_diag, sweeps, b, b_len, x, x_len);                \
+    }                                                                                                                      \
+    int spal_##kind##_trsv_sweep_dev_##sfx(spal_##kind##_t a, int uplo, int unit_diag, uint64_t sweeps, const T *b_dev,   \
+                                           T *x_dev, void *stream) {                                                      \
+        return sweep_dev<T>("spal_" #kind "_trsv_sweep_dev", a, uplo, unit_diag, sweeps, b_dev, x_dev, stream);           \
+    }
+SPAL_SWEEP_ENTRIES(csr, f64, double)
+SPAL_SWEEP_ENTRIES(csr, f32, float)
+SPAL_SWEEP_ENTRIES(csc, f64, double)
+SPAL_SWEEP_ENTRIES(csc, f32, float)
+#undef SPAL_SWEEP_ENTRIES
+
+}  // extern "C"

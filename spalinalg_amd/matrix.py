@@ -260,9 +260,35 @@ class _DeviceMatrix:
                                                        C.c_int(1 if unit_diagonal else 0), vp(b_ptr), vp(x_ptr),
                                                        _stream_ptr(stream)))
 
+    def trsv_sweep(self, b, sweeps: int, lower: bool = True, unit_diagonal: bool = False) -> np.ndarray:
+        """`sweeps` Jacobi passes x <- D^-1 (b - N x) on the chosen triangle instead of the substitution
+        (spal_*_trsv_sweep_*): x0 = b / d, every pass one launch of independent rows; bit for bit the
+        sequential text in include/spal.h, and trsv()'s result from sweeps = levels - 1 on.  No host analysis.  Host
+        vector in, host vector out; a dtype other than the handle's is refused by the library."""
+        b = np.ascontiguousarray(b)
+        if b.dtype not in (np.float32, np.float64):
+            b = b.astype(self.dtype)
+        if b.ndim != 1:
+            raise TypeError("trsv_sweep() takes one right-hand side, a 1-D vector")
+        x = np.empty_like(b)
+        check(self._fn(f"trsv_sweep_{_sfx(b.dtype)}")(self._h, C.c_int(0 if lower else 1),
+                                                      C.c_int(1 if unit_diagonal else 0), u64(sweeps), _p(b), u64(b.size),
+                                                      _p(x), u64(x.size)))
+        return x
+
+    def trsv_sweep_dev(self, b_ptr: int, x_ptr: int, sweeps: int, lower: bool = True, unit_diagonal: bool = False,
+                       stream=None) -> None:
+        """Device pointers (x_ptr == b_ptr is allowed); enqueued on `stream`, not synchronised once the handle is
+        prepared (its first sweep call prepares it, which synchronises).  The passes' scratch is taken and returned in
+        stream order."""
+        check(self._fn(f"trsv_sweep_dev_{_sfx(self.dtype)}")(self._h, C.c_int(0 if lower else 1),
+                                                             C.c_int(1 if unit_diagonal else 0), u64(sweeps), vp(b_ptr),
+                                                             vp(x_ptr), _stream_ptr(stream)))
+
     def krylov(self, b, method="cg", M=None, x0=None, tol: float = 1e-8, maxit: int = 1000):
         """Solves A x = b by CG ("cg") or BiCGStab ("bicgstab") on the device (spal_*_krylov_*), optionally
-        preconditioned by `M`, an ILU(0) factor handle of this class (M^-1 v = two solves on it).  Host vectors; returns
+        preconditioned by `M`, an ILU(0) factor handle of this class (M^-1 v = two solves on it, or, when M's option
+        "trsv_sweeps" is s >= 0, s Jacobi sweeps per triangle).  Host vectors; returns
         (x, KrylovInfo).  Bit for bit the loops written out in include/spal.h, whatever "krylov_check_every" is."""
         b = np.ascontiguousarray(b)
         if b.dtype not in (np.float32, np.float64):
@@ -721,11 +747,14 @@ class _Compressed:
                         f"assertion failed: ncols == rhs.nrows (left: {self._ncols}, right: {X.shape[0]})")
         return self.device().spmm(X.astype(self.dtype, copy=False))
 
-    def solve_triangular(self, b, lower: bool = True, unit_diagonal: bool = False, device: int = 0) -> np.ndarray:
+    def solve_triangular(self, b, lower: bool = True, unit_diagonal: bool = False, device: int = 0,
+                         sweeps=None) -> np.ndarray:
         """x with L x = b (the lower triangle of self, `lower`) or U x = b; entries of the other triangle are ignored
         and `unit_diagonal` takes the diagonal as ones.  Forward / backward substitution on the device, bit for bit
         the sequential loop (spal_*_trsv_*).  The reference has no solve; a Rust binding adds it as a
-        method of the matrix types."""
+        method of the matrix types.
+        `sweeps` = None is that exact solve; an integer s >= 0 asks for s Jacobi passes on the triangle instead
+        (spal_*_trsv_sweep_*): approximate, every pass one launch, exact from s = levels - 1 on."""
         b = np.asarray(b)
         if self._nrows != self._ncols:
             raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT,
@@ -733,14 +762,20 @@ class _Compressed:
         if b.ndim != 1 or b.shape[0] != self._nrows:
             raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT,
                         f"solve_triangular: b has shape {b.shape} but the matrix has {self._nrows} rows")
+        if sweeps is not None:
+            return self.device(device).trsv_sweep(b, int(sweeps), lower, unit_diagonal)
         return self.device(device).trsv(b, lower, unit_diagonal)
 
-    def solve(self, b, method="cg", M=None, x0=None, tol: float = 1e-8, maxit: int = 1000, device: int = 0):
+    def solve(self, b, method="cg", M=None, x0=None, tol: float = 1e-8, maxit: int = 1000, device: int = 0,
+              precond_sweeps=None):
         """x with A x = b by CG (`method="cg"`: A symmetric positive definite) or BiCGStab ("bicgstab") on the device,
         optionally preconditioned by `M = a.ilu0()`; returns (x, info) with info.iterations, info.reason (0 converged to
         dot(r, r) <= tol^2 dot(b, b), 1 maxit reached, 2 breakdown), info.residual_sq, info.rhs_sq, info.solve_ms.
         Bit for bit the loops of include/spal.h.  The reference has no solver; a Rust binding adds it as a
-        method of the matrix types."""
+        method of the matrix types.
+        `precond_sweeps`, when given, SETS M's option "trsv_sweeps" before the call, and the option stays set on M's
+        device handle: s >= 0 applies M by s Jacobi sweeps per triangle instead of two exact solves (3 is a good
+        start; `M=self, precond_sweeps=0` is the Jacobi preconditioner), -1 restores the exact solves."""
         b = np.asarray(b)
         if self._nrows != self._ncols:
             raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT, f"solve: the matrix is not square ({self._nrows} x {self._ncols})")
@@ -750,6 +785,10 @@ class _Compressed:
             raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT, f"solve: x0 has shape {np.shape(x0)} but b {b.shape}")
         if M is not None and type(M) is not type(self):
             raise TypeError(f"M must be a {type(self).__name__}, e.g. self.ilu0()")
+        if precond_sweeps is not None:
+            if M is None:
+                raise TypeError("precond_sweeps needs M, the factor it is an option of")
+            M.device(device).set_option("trsv_sweeps", int(precond_sweeps))
         return self.device(device).krylov(b, method, None if M is None else M.device(device), x0, tol, maxit)
 
     def _mul_mat(self, other, device: int = 0):
