@@ -29,7 +29,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DTYPES = [np.float64, np.float32]
 TOL = {np.float64: 1e-10, np.float32: 1e-5}
 MAXIT = 200
-SIZES = [0, 1, 2, 1023, 1024, 1025, 1024 ** 2 - 1, 1024 ** 2, 1024 ** 2 + 1]
+G = 4096 * 1024      # the elements one trip of the first-level grid covers: 4096 workgroups (kMaxGrid), a tile of 1024 each
+# G: the last size of one trip; G + 1: workgroup 0 alone takes a second tile; 3 G - 1023: three tiles each, the last one
+# of a single element, and a second level of 12 tiles
+SIZES = [0, 1, 2, 1023, 1024, 1025, 1024 ** 2 - 1, 1024 ** 2, 1024 ** 2 + 1, G, G + 1, 3 * G - 1023]
 
 
 # ---- 1. the dot product ---------------------------------------------------------------------------------------------
@@ -151,6 +154,57 @@ def test_solve_is_the_reference_loop(name, method, kind, prec, dtype):
     d = a.device().describe()["krylov"]
     assert d["method"] == method and d["preconditioned"] == int(prec) and d["iterations"] == info.iterations
     assert d["reason"] == 0 and d["check_every"] == (1 if prec else 8) and d["polls"] >= 1 and d["solve_ms"] > 0
+
+
+# ---- 2b. the fused updates past one trip of the grid ------------------------------------------------------------------
+
+@functools.lru_cache(maxsize=None)
+def long_case(name, dtype):
+    """(pattern, values, b) of G + 1 rows, so that every first-level launch takes a second tile in workgroup 0:
+    "tridiagonal" is symmetric positive definite (krylov_ref.spd_fill), "diagonal" holds d in [0.5, 2).  Shared, read-only."""
+    n = G + 1
+    rng = np.random.default_rng(zlib.crc32(f"long/{name}".encode()))
+    if name == "tridiagonal":
+        cols = (np.repeat(np.arange(n, dtype=np.int64), 3).reshape(n, 3) + np.array([-1, 0, 1])).ravel()[1:-1]
+        rowptr = np.concatenate([[0, 2], 2 + 3 * np.arange(1, n - 1, dtype=np.int64), [3 * n - 2]]).astype(np.uint64)
+        pattern = (n, rowptr, cols.astype(np.uint64))
+        values, b = kr.spd_fill(pattern, dtype, rng)
+    else:
+        pattern = tr.diagonal(n)
+        values = rng.uniform(0.5, 2, size=n).astype(dtype)
+        b = rng.uniform(-1, 1, size=n).astype(dtype)
+    for a in (*pattern[1:], values, b):
+        a.setflags(write=False)
+    return pattern, values, b
+
+
+# (matrix, method, with M = a.ilu0(), maxit).  Between them the cases launch every VecOp with more tiles than workgroups:
+# V_INIT, V_COPY_DOT, V_DOT, V_CG_XR, V_CG_P by CG; V_BI_P, V_BI_S, V_DOT2, V_BI_XR by BiCGStab; V_BI_HALF where the
+# preconditioner is the matrix itself and BiCGStab leaves by the half step.
+LONG_CASES = [("tridiagonal", "cg", False, 3), ("tridiagonal", "bicgstab", False, 2), ("diagonal", "bicgstab", True, MAXIT),
+              ("diagonal", "cg", True, MAXIT)]
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=["f64", "f32"])
+@pytest.mark.parametrize("name,method,prec,maxit", LONG_CASES, ids=["cg", "bicgstab", "bicgstab-half-step", "cg-ilu0"])
+def test_fused_updates_past_one_trip_of_the_grid(name, method, prec, maxit, dtype):
+    pattern, values, b = long_case(name, dtype)
+    assert -(-pattern[0] // 1024) == 4096 + 1
+    tol = TOL[dtype]
+    a = make("csr", pattern, values)
+    f = hp = None
+    if prec:
+        f = a.ilu0()
+        tr.assert_same_bits(f.values(), values)      # the factor of a diagonal matrix is the matrix
+        # ... so the two solves of the host preconditioner are: nothing (the unit lower triangle), then one division
+        hp = lambda v: v / values                                                            # noqa: E731
+    ref = kr.METHODS[method](lambda v: a.device().spmv(v), hp, b, np.zeros_like(b), tol, maxit)
+    got = a.solve(b, method, M=f, tol=tol, maxit=maxit)
+    same_result(got, ref)
+    if prec and method == "bicgstab":
+        assert (got[1].reason, got[1].iterations) == (0, 1)     # the half-step exit: V_BI_HALF has applied x += alpha ph
+    if not prec:
+        assert (got[1].reason, got[1].iterations) == (1, maxit)
 
 
 # ---- 3. the pure-host reference --------------------------------------------------------------------------------------
