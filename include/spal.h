@@ -521,7 +521,8 @@ int spal_csc_ilu0(spal_csc_t a, void *stream, spal_csc_t *out);
  * SPAL_ERR_UNSUPPORTED: a handle held as row blocks.  Nothing leaks on failure.
  * describe() on `a` gains "krylov" after a solve: {method, preconditioned, iterations, reason, check_every, polls,
  * solve_ms, precond_sweeps = m's "trsv_sweeps" (-1 without m)} of the last call.
- * Not provided: capture into a graph, GMRES, several GPUs, a dot fused into the SpMV kernels. */
+ * Not provided: capture into a graph, several GPUs, a dot fused into the SpMV kernels.  GMRES has its own entry points
+ * (below). */
 enum { SPAL_KRYLOV_CG = 0, SPAL_KRYLOV_BICGSTAB = 1 };
 typedef struct spal_krylov_info {
     uint64_t iterations;
@@ -552,6 +553,76 @@ int spal_csc_krylov_dev_f64(spal_csc_t a, int method, spal_csc_t m, const double
                             double tol, uint64_t maxit, void *stream, spal_krylov_info *info);
 int spal_csc_krylov_dev_f32(spal_csc_t a, int method, spal_csc_t m, const float *b_dev, float *x_dev,
                             double tol, uint64_t maxit, void *stream, spal_krylov_info *info);
+
+/* ---- A x = b on the device: restarted GMRES(m), right-preconditioned ------------------------------------
+ * Not in the reference.  For matrices that are not symmetric, where BiCGStab can break down (on the cyclic shift with
+ * b = e0 it returns reason 2 after one iteration; GMRES solves that system in n steps).  The contract is again a
+ * sequential text the device reproduces bit for bit, f32 and f64.  All scalars are T.  dot, thr = T(tol * tol) * bb,
+ * M^-1 (two exact solves on m, or "trsv_sweeps" sweeps per triangle, or v itself when m == NULL) and the stop reasons
+ * are exactly those of the section above.  Every product is rounded before the sum or difference it enters (no FMA);
+ * sqrt and / are IEEE, correctly rounded.  m = restart.  The basis is orthogonalised by two passes of classical
+ * Gram-Schmidt (CGS2); H is the (m + 1) x m Hessenberg matrix after the rotations (cs, sn), g the rotated right-hand side.
+ *
+ *   bb = dot(b, b);  thr = T(tol * tol) * bb;  it = 0
+ *   cycle:
+ *     q = A x;  r[i] = b[i] - q[i];  rr = dot(r, r)
+ *     test on rr:  rr <= thr: stop 0;  else rr not finite: stop 2;  else it == maxit: stop 1      (residual_sq = rr)
+ *     beta = sqrt(rr);  v_0[i] = r[i] / beta;  g[0] = beta;  jj = 0
+ *     repeat:
+ *       j = jj;  z = M^-1 v_j;  w = A z
+ *       h[k] = dot(v_k, w)                      k = 0..j     (all from the same w)
+ *       w[i] = (..((w[i] - (h[0]*v_0[i])) - (h[1]*v_1[i])) ..) - (h[j]*v_j[i])
+ *       c[k] = dot(v_k, w)                      k = 0..j
+ *       w[i] = the same update with c;   h[k] = h[k] + c[k]
+ *       hn = sqrt(dot(w, w));  v_{j+1}[i] = w[i] / hn;  it += 1
+ *       for k = 0..j-1:  t = (cs[k]*h[k]) + (sn[k]*h[k+1]);  h[k+1] = (cs[k]*h[k+1]) - (sn[k]*h[k]);  h[k] = t     (h[j+1] = hn)
+ *       d = sqrt((h[j]*h[j]) + (hn*hn));  cs[j] = h[j]/d;  sn[j] = hn/d;  h[j] = d
+ *       g[j+1] = -(sn[j]*g[j]);  g[j] = cs[j]*g[j];  H[0..j, j] = h[0..j];  est = g[j+1]*g[j+1];  jj = j + 1
+ *       if est not finite:  stop 2, residual_sq = est, x is what it was at the start of this cycle
+ *       until est <= thr or it == maxit or jj == m
+ *     back substitution, column form:  for k = jj-1 .. 0:  y[k] = g[k] / H[k,k];  g[l] = g[l] - (H[l,k]*y[k]) for l < k
+ *     u[i] = (..((y[0]*v_0[i]) + (y[1]*v_1[i])) ..) + (y[jj-1]*v_{jj-1}[i]);   x[i] = x[i] + (M^-1 u)[i]
+ *     goto cycle
+ *
+ * Consequences.  (1) Reasons 0 and 1 are always decided on the TRUE residual, recomputed at the head of a cycle; est
+ * only ends a cycle.  (2) Every cycle performs at least one iteration, so maxit bounds the call.  (3) On a lucky
+ * breakdown (hn == 0 with h[j] != 0) v_{j+1} is a vector of NaN: it is written and never read, because sn[j] = 0 gives
+ * est = 0 and ends the cycle.  A zero matrix gives cs = 0 / 0: reason 2 at it = 1 with x untouched.
+ *
+ * On the device one kernel forms the first level of all j + 1 dot products of a pass from one read of w,
+ * one workgroup per k finishes them, one kernel applies all j + 1 updates from one read of w (the second one fused with
+ * the first level of dot(w, w)), and one workgroup does the step's scalar arithmetic in a block of device memory.
+ * "krylov_check_every" on `a` counts INNER iterations between two polls, with the defaults of the section above; the
+ * host also polls when its own count reaches restart, and after the head of a cycle that follows an early end.  Every
+ * kernel reads the block's flags (written by an earlier launch on the same stream: nothing waits, nothing spins) and
+ * returns before it writes once the call has stopped or, for the kernels of a step, once the cycle has ended; x,
+ * iterations, reason and residual_sq do not depend on the interval.  "trsv_sweeps" on m works as above.  The basis
+ * (restart + 1 vectors), w, q, with m also z and u, and two more vectors for sweeps come from the caching allocator in
+ * ONE block per call on 256-byte strides; no handle lock is held across a product or a solve.  The _dev forms
+ * SYNCHRONISE `stream` and cannot be captured into a graph.
+ * SPAL_ERR_INVALID_ARGUMENT: everything spal_*_krylov_* refuses (there is no method here), and restart == 0 or
+ * restart > 256 (one Hessenberg column element per thread of the 256-thread scalar workgroup).
+ * SPAL_ERR_UNSUPPORTED: a handle held as row blocks.  SPAL_ERR_OUT_OF_MEMORY: no room for the basis.  Nothing leaks.
+ * describe() on `a` gains "gmres" after a call: {restart, preconditioned, precond_sweeps, iterations, cycles, reason,
+ * check_every, polls, dot_batch = basis vectors per batch of the two kernels, basis_bytes = that one block, solve_ms};
+ * "krylov" is left to CG and BiCGStab.
+ * Not provided: capture into a graph, flexible GMRES, several GPUs, a multi-dot fused into the SpMV kernels. */
+int spal_csr_gmres_f64(spal_csr_t a, spal_csr_t m, const double *b, uint64_t b_len, double *x, uint64_t x_len,
+                       uint64_t restart, double tol, uint64_t maxit, spal_krylov_info *info);
+int spal_csr_gmres_f32(spal_csr_t a, spal_csr_t m, const float *b, uint64_t b_len, float *x, uint64_t x_len,
+                       uint64_t restart, double tol, uint64_t maxit, spal_krylov_info *info);
+int spal_csr_gmres_dev_f64(spal_csr_t a, spal_csr_t m, const double *b_dev, double *x_dev, uint64_t restart,
+                           double tol, uint64_t maxit, void *stream, spal_krylov_info *info);   /* synchronises */
+int spal_csr_gmres_dev_f32(spal_csr_t a, spal_csr_t m, const float *b_dev, float *x_dev, uint64_t restart,
+                           double tol, uint64_t maxit, void *stream, spal_krylov_info *info);
+int spal_csc_gmres_f64(spal_csc_t a, spal_csc_t m, const double *b, uint64_t b_len, double *x, uint64_t x_len,
+                       uint64_t restart, double tol, uint64_t maxit, spal_krylov_info *info);
+int spal_csc_gmres_f32(spal_csc_t a, spal_csc_t m, const float *b, uint64_t b_len, float *x, uint64_t x_len,
+                       uint64_t restart, double tol, uint64_t maxit, spal_krylov_info *info);
+int spal_csc_gmres_dev_f64(spal_csc_t a, spal_csc_t m, const double *b_dev, double *x_dev, uint64_t restart,
+                           double tol, uint64_t maxit, void *stream, spal_krylov_info *info);
+int spal_csc_gmres_dev_f32(spal_csc_t a, spal_csc_t m, const float *b_dev, float *x_dev, uint64_t restart,
+                           double tol, uint64_t maxit, void *stream, spal_krylov_info *info);
 
 /* ---- CSR <-> CSC on the device ------------------------------------------------
  * Replace `impl From<&CscMatrix<T>> for CsrMatrix<T>` (src/csr/conv/csc.rs:4-52)

@@ -18,6 +18,7 @@
 //   CscMatrix<T>, CooMatrix<T> likewise                  src/csc.rs, src/coo.rs
 //   a.solve(b, method, M, x0, tol, maxit), dot(a, b)     not in the reference: CG / BiCGStab and their dot product
 //                                                        (include/spal.h, spal_*_krylov_*, spal_dot_*)
+//   a.gmres(b, restart, M, x0, tol, maxit)               not in the reference: restarted GMRES (spal_*_gmres_*)
 //
 // A failed `assert!` in the reference is a panic; here it is a
 // spalinalg::Panic exception (the Rust shim in rust_shim/ turns the same
@@ -67,6 +68,7 @@ template <> struct Abi<double> {
     static constexpr auto csr_trsv = spal_csr_trsv_f64;
     static constexpr auto csr_trsv_sweep = spal_csr_trsv_sweep_f64;
     static constexpr auto csr_krylov = spal_csr_krylov_f64;
+    static constexpr auto csr_gmres = spal_csr_gmres_f64;
     static constexpr auto dot = spal_dot_f64;
     static constexpr auto csr_download = spal_csr_download_f64;
     static constexpr auto csc_create = spal_csc_create_f64;
@@ -75,6 +77,7 @@ template <> struct Abi<double> {
     static constexpr auto csc_trsv = spal_csc_trsv_f64;
     static constexpr auto csc_trsv_sweep = spal_csc_trsv_sweep_f64;
     static constexpr auto csc_krylov = spal_csc_krylov_f64;
+    static constexpr auto csc_gmres = spal_csc_gmres_f64;
     static constexpr auto coo_to_csr = spal_coo_to_csr_f64;
     static constexpr auto coo_to_csc = spal_coo_to_csc_f64;
     static constexpr auto csc_download = spal_csc_download_f64;
@@ -86,6 +89,7 @@ template <> struct Abi<float> {
     static constexpr auto csr_trsv = spal_csr_trsv_f32;
     static constexpr auto csr_trsv_sweep = spal_csr_trsv_sweep_f32;
     static constexpr auto csr_krylov = spal_csr_krylov_f32;
+    static constexpr auto csr_gmres = spal_csr_gmres_f32;
     static constexpr auto dot = spal_dot_f32;
     static constexpr auto csr_download = spal_csr_download_f32;
     static constexpr auto csc_create = spal_csc_create_f32;
@@ -94,6 +98,7 @@ template <> struct Abi<float> {
     static constexpr auto csc_trsv = spal_csc_trsv_f32;
     static constexpr auto csc_trsv_sweep = spal_csc_trsv_sweep_f32;
     static constexpr auto csc_krylov = spal_csc_krylov_f32;
+    static constexpr auto csc_gmres = spal_csc_gmres_f32;
     static constexpr auto coo_to_csr = spal_coo_to_csr_f32;
     static constexpr auto coo_to_csc = spal_coo_to_csc_f32;
     static constexpr auto csc_download = spal_csc_download_f32;
@@ -282,6 +287,32 @@ class CsrMatrix {
         return s;
     }
 
+    // x with A x = b by restarted GMRES(restart) on the device, for matrices that are not symmetric; right-preconditioned
+    // by M as solve() is; bit for bit the text of include/spal.h (spal_csr_gmres_*).  restart is 1 .. 256.  Reasons 0 and
+    // 1 are decided on the true residual.  Panics as solve() does, and on a restart outside its range.
+    Solution<T> gmres(const std::vector<T> &b, usize restart = 30, const CsrMatrix *M = nullptr,
+                      const std::vector<T> &x0 = {}, double tol = 1e-8, usize maxit = 1000) const {
+        if (nrows_ != ncols_)
+            throw Panic(SPAL_ERR_INVALID_ARGUMENT, "gmres: the matrix is not square (" + std::to_string(nrows_) + " x " +
+                                                       std::to_string(ncols_) + ")");
+        if (b.size() != nrows_ || (!x0.empty() && x0.size() != nrows_))
+            throw Panic(SPAL_ERR_INVALID_ARGUMENT, "gmres: b.len() = " + std::to_string(b.size()) + " and x0.len() = " +
+                                                       std::to_string(x0.size()) + " but the matrix has " +
+                                                       std::to_string(nrows_) + " rows");
+        if (restart == 0 || restart > 256)
+            throw Panic(SPAL_ERR_INVALID_ARGUMENT, "gmres: restart = " + std::to_string(restart) + " must be 1 .. 256");
+        Solution<T> s{x0.empty() ? std::vector<T>(nrows_, T(0)) : x0, 0, 0, 0.0, 0.0, 0.0};
+        spal_krylov_info info;
+        detail::check(detail::Abi<T>::csr_gmres(device_handle(), M ? M->device_handle() : nullptr, b.data(), b.size(),
+                                                 s.x.data(), s.x.size(), restart, tol, maxit, &info));
+        s.iterations = info.iterations;
+        s.reason = info.reason;
+        s.residual_sq = info.residual_sq;
+        s.rhs_sq = info.rhs_sq;
+        s.solve_ms = info.solve_ms;
+        return s;
+    }
+
     // CsrMatrix::from(&coo): assembled on the device, bit-identical to the reference.
     static CsrMatrix from(const CooMatrix<T> &coo, int device = 0);
     // CsrMatrix::from(&csc)  (src/csr/conv/csc.rs:4-52): device stable sort by row.
@@ -442,6 +473,32 @@ class CscMatrix {
         spal_krylov_info info;
         detail::check(detail::Abi<T>::csc_krylov(device_handle(), static_cast<int>(method), M ? M->device_handle() : nullptr,
                                                   b.data(), b.size(), s.x.data(), s.x.size(), tol, maxit, &info));
+        s.iterations = info.iterations;
+        s.reason = info.reason;
+        s.residual_sq = info.residual_sq;
+        s.rhs_sq = info.rhs_sq;
+        s.solve_ms = info.solve_ms;
+        return s;
+    }
+
+    // x with A x = b by restarted GMRES(restart) on the device, for matrices that are not symmetric; right-preconditioned
+    // by M as solve() is; bit for bit the text of include/spal.h (spal_csc_gmres_*).  restart is 1 .. 256.  Reasons 0 and
+    // 1 are decided on the true residual.  Panics as solve() does, and on a restart outside its range.
+    Solution<T> gmres(const std::vector<T> &b, usize restart = 30, const CscMatrix *M = nullptr,
+                      const std::vector<T> &x0 = {}, double tol = 1e-8, usize maxit = 1000) const {
+        if (nrows_ != ncols_)
+            throw Panic(SPAL_ERR_INVALID_ARGUMENT, "gmres: the matrix is not square (" + std::to_string(nrows_) + " x " +
+                                                       std::to_string(ncols_) + ")");
+        if (b.size() != nrows_ || (!x0.empty() && x0.size() != nrows_))
+            throw Panic(SPAL_ERR_INVALID_ARGUMENT, "gmres: b.len() = " + std::to_string(b.size()) + " and x0.len() = " +
+                                                       std::to_string(x0.size()) + " but the matrix has " +
+                                                       std::to_string(nrows_) + " rows");
+        if (restart == 0 || restart > 256)
+            throw Panic(SPAL_ERR_INVALID_ARGUMENT, "gmres: restart = " + std::to_string(restart) + " must be 1 .. 256");
+        Solution<T> s{x0.empty() ? std::vector<T>(nrows_, T(0)) : x0, 0, 0, 0.0, 0.0, 0.0};
+        spal_krylov_info info;
+        detail::check(detail::Abi<T>::csc_gmres(device_handle(), M ? M->device_handle() : nullptr, b.data(), b.size(),
+                                                 s.x.data(), s.x.size(), restart, tol, maxit, &info));
         s.iterations = info.iterations;
         s.reason = info.reason;
         s.residual_sq = info.residual_sq;

@@ -127,6 +127,16 @@ impl<T: HipScalar> DeviceCsr<T> {
         info
     }
 
+    /// x with A x = b by restarted GMRES(`restart`, 1 ..= 256), right-preconditioned by `m` as `solve` is; for matrices
+    /// that are not symmetric.  Bit for bit the text of include/spal.h; reasons 0 and 1 are decided on the true residual.
+    pub fn gmres(&self, m: Option<&DeviceCsr<T>>, b: &[T], x: &mut [T], restart: u64, tol: f64, maxit: u64) -> ffi::spal_krylov_info
+    where T: HipKrylov {
+        let mut info = ffi::spal_krylov_info::default();
+        let mh = m.map_or(std::ptr::null_mut(), |f| f.h);
+        unsafe { ffi::check(T::csr_gmres(self.h, mh, b, x, restart, tol, maxit, &mut info)); }
+        info
+    }
+
     /// `solve_triangular` on device pointers (`x_dev == b_dev` solves in place), enqueued on `stream` and not
     /// synchronised once the triangle has its plan (`trsv_analyse`, or the first solve, builds it).
     ///
@@ -323,6 +333,16 @@ impl<T: HipScalar> DeviceCsc<T> {
         let mut info = ffi::spal_krylov_info::default();
         let mh = m.map_or(std::ptr::null_mut(), |f| f.h);
         unsafe { ffi::check(T::csc_krylov(self.h, method, mh, b, x, tol, maxit, &mut info)); }
+        info
+    }
+
+    /// x with A x = b by restarted GMRES(`restart`, 1 ..= 256), right-preconditioned by `m` as `solve` is; for matrices
+    /// that are not symmetric.  Bit for bit the text of include/spal.h; reasons 0 and 1 are decided on the true residual.
+    pub fn gmres(&self, m: Option<&DeviceCsc<T>>, b: &[T], x: &mut [T], restart: u64, tol: f64, maxit: u64) -> ffi::spal_krylov_info
+    where T: HipKrylov {
+        let mut info = ffi::spal_krylov_info::default();
+        let mh = m.map_or(std::ptr::null_mut(), |f| f.h);
+        unsafe { ffi::check(T::csc_gmres(self.h, mh, b, x, restart, tol, maxit, &mut info)); }
         info
     }
 

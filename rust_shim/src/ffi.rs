@@ -106,6 +106,14 @@ extern "C" {
     pub fn spal_csc_krylov_f32(a: *mut spal_csc, method: c_int, m: *mut spal_csc, b: *const f32, b_len: u64, x: *mut f32, x_len: u64, tol: f64, maxit: u64, info: *mut spal_krylov_info) -> c_int;
     pub fn spal_csc_krylov_dev_f64(a: *mut spal_csc, method: c_int, m: *mut spal_csc, b_dev: *const f64, x_dev: *mut f64, tol: f64, maxit: u64, stream: *mut c_void, info: *mut spal_krylov_info) -> c_int;
     pub fn spal_csc_krylov_dev_f32(a: *mut spal_csc, method: c_int, m: *mut spal_csc, b_dev: *const f32, x_dev: *mut f32, tol: f64, maxit: u64, stream: *mut c_void, info: *mut spal_krylov_info) -> c_int;
+    pub fn spal_csr_gmres_f64(a: *mut spal_csr, m: *mut spal_csr, b: *const f64, b_len: u64, x: *mut f64, x_len: u64, restart: u64, tol: f64, maxit: u64, info: *mut spal_krylov_info) -> c_int;
+    pub fn spal_csr_gmres_f32(a: *mut spal_csr, m: *mut spal_csr, b: *const f32, b_len: u64, x: *mut f32, x_len: u64, restart: u64, tol: f64, maxit: u64, info: *mut spal_krylov_info) -> c_int;
+    pub fn spal_csr_gmres_dev_f64(a: *mut spal_csr, m: *mut spal_csr, b_dev: *const f64, x_dev: *mut f64, restart: u64, tol: f64, maxit: u64, stream: *mut c_void, info: *mut spal_krylov_info) -> c_int;
+    pub fn spal_csr_gmres_dev_f32(a: *mut spal_csr, m: *mut spal_csr, b_dev: *const f32, x_dev: *mut f32, restart: u64, tol: f64, maxit: u64, stream: *mut c_void, info: *mut spal_krylov_info) -> c_int;
+    pub fn spal_csc_gmres_f64(a: *mut spal_csc, m: *mut spal_csc, b: *const f64, b_len: u64, x: *mut f64, x_len: u64, restart: u64, tol: f64, maxit: u64, info: *mut spal_krylov_info) -> c_int;
+    pub fn spal_csc_gmres_f32(a: *mut spal_csc, m: *mut spal_csc, b: *const f32, b_len: u64, x: *mut f32, x_len: u64, restart: u64, tol: f64, maxit: u64, info: *mut spal_krylov_info) -> c_int;
+    pub fn spal_csc_gmres_dev_f64(a: *mut spal_csc, m: *mut spal_csc, b_dev: *const f64, x_dev: *mut f64, restart: u64, tol: f64, maxit: u64, stream: *mut c_void, info: *mut spal_krylov_info) -> c_int;
+    pub fn spal_csc_gmres_dev_f32(a: *mut spal_csc, m: *mut spal_csc, b_dev: *const f32, x_dev: *mut f32, restart: u64, tol: f64, maxit: u64, stream: *mut c_void, info: *mut spal_krylov_info) -> c_int;
     pub fn spal_csc_to_csr(a: *mut spal_csc, out: *mut *mut spal_csr) -> c_int;
     pub fn spal_csr_to_csc(a: *mut spal_csr, out: *mut *mut spal_csc) -> c_int;
     pub fn spal_csr_mul(a: *mut spal_csr, b: *mut spal_csr, stream: *mut c_void, out: *mut *mut spal_csr) -> c_int;

@@ -164,10 +164,15 @@ pub trait HipKrylov: Sized {
     unsafe fn csc_krylov(a: *mut ffi::spal_csc, method: c_int, m: *mut ffi::spal_csc, b: &[Self], x: &mut [Self], tol: f64,
                          maxit: u64, info: *mut ffi::spal_krylov_info) -> c_int;
     unsafe fn dot(a: &[Self], b: &[Self], out: *mut Self) -> c_int;
+    /// restarted GMRES (the spal_*_gmres_* entry points): `restart` is 1 ..= 256
+    unsafe fn csr_gmres(a: *mut ffi::spal_csr, m: *mut ffi::spal_csr, b: &[Self], x: &mut [Self], restart: u64, tol: f64,
+                        maxit: u64, info: *mut ffi::spal_krylov_info) -> c_int;
+    unsafe fn csc_gmres(a: *mut ffi::spal_csc, m: *mut ffi::spal_csc, b: &[Self], x: &mut [Self], restart: u64, tol: f64,
+                        maxit: u64, info: *mut ffi::spal_krylov_info) -> c_int;
 }
 
 macro_rules! impl_hip_krylov {
-    ($t:ty, $csr_krylov:ident, $csc_krylov:ident, $dot:ident) => {
+    ($t:ty, $csr_krylov:ident, $csc_krylov:ident, $dot:ident, $csr_gmres:ident, $csc_gmres:ident) => {
         impl HipKrylov for $t {
             unsafe fn csr_krylov(a: *mut ffi::spal_csr, method: c_int, m: *mut ffi::spal_csr, b: &[Self], x: &mut [Self],
                                  tol: f64, maxit: u64, info: *mut ffi::spal_krylov_info) -> c_int {
@@ -180,11 +185,19 @@ macro_rules! impl_hip_krylov {
             unsafe fn dot(a: &[Self], b: &[Self], out: *mut Self) -> c_int {
                 ffi::$dot(a.as_ptr(), b.as_ptr(), a.len() as u64, out)
             }
+            unsafe fn csr_gmres(a: *mut ffi::spal_csr, m: *mut ffi::spal_csr, b: &[Self], x: &mut [Self], restart: u64,
+                                tol: f64, maxit: u64, info: *mut ffi::spal_krylov_info) -> c_int {
+                ffi::$csr_gmres(a, m, b.as_ptr(), b.len() as u64, x.as_mut_ptr(), x.len() as u64, restart, tol, maxit, info)
+            }
+            unsafe fn csc_gmres(a: *mut ffi::spal_csc, m: *mut ffi::spal_csc, b: &[Self], x: &mut [Self], restart: u64,
+                                tol: f64, maxit: u64, info: *mut ffi::spal_krylov_info) -> c_int {
+                ffi::$csc_gmres(a, m, b.as_ptr(), b.len() as u64, x.as_mut_ptr(), x.len() as u64, restart, tol, maxit, info)
+            }
         }
     };
 }
-impl_hip_krylov!(f64, spal_csr_krylov_f64, spal_csc_krylov_f64, spal_dot_f64);
-impl_hip_krylov!(f32, spal_csr_krylov_f32, spal_csc_krylov_f32, spal_dot_f32);
+impl_hip_krylov!(f64, spal_csr_krylov_f64, spal_csc_krylov_f64, spal_dot_f64, spal_csr_gmres_f64, spal_csc_gmres_f64);
+impl_hip_krylov!(f32, spal_csr_krylov_f32, spal_csc_krylov_f32, spal_dot_f32, spal_csr_gmres_f32, spal_csc_gmres_f32);
 
 /// dot(a, b) by the library's definition (include/spal.h): products rounded, then the fixed tree over tiles of 1024.
 pub fn dot<T: HipKrylov + Default>(a: &[T], b: &[T]) -> T {

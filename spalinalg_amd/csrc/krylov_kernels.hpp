@@ -1,0 +1,175 @@
+// krylov_kernels.hpp -- what spal_krylov.hip (the dot product, CG, BiCGStab: DESIGN 3.14) and spal_gmres.hip (GMRES:
+// DESIGN 3.17) share: the tile sum and the upper levels of reduce(), the sizes of a dot's scratch, the entry points a
+// driver goes through by handle and element type, the preparation of the plans, M^-1, the refusals that need no device
+// and two scope guards.  The contracts are written out in include/spal.h.  (Not installed.)
+#pragma once
+
+#include "spal_ops.hpp"
+
+#include <cmath>
+
+#pragma clang fp contract(off)
+
+namespace spal {
+
+constexpr uint64_t kTile = 1024;
+constexpr int kThreads = 256;
+constexpr unsigned kMaxGrid = 4096;   // first-level workgroups of a launch; each walks tiles blockIdx.x, + gridDim.x, ...
+
+// The sum of one tile, valid in thread 0.  `lds` holds kThreads elements; ends with a barrier, so it can be reused.
+template <typename T>
+__device__ __forceinline__ T tile_sum(T v0, T v1, T v2, T v3, T *lds) {
+    const unsigned t = threadIdx.x;
+    T a = (v0 + v2) + (v1 + v3);                 // h = 512 (e[t], e[t + 256]), then h = 256
+    lds[t] = a;
+    __syncthreads();
+    if (t < 128) {
+        a = lds[t] + lds[t + 128];               // h = 128
+        if (t >= 64) lds[t] = a;                 // (its own slot: nobody else read it)
+    }
+    __syncthreads();
+    if (t < 64) {
+        a = a + lds[t + 64];                     // h = 64
+#pragma unroll
+        for (int h = 32; h >= 1; h >>= 1) a = a + __shfl_down(a, h, 64);
+    }
+    __syncthreads();
+    return a;
+}
+
+// `part` holds the c1 sums of the first level, then room for every further level; returns reduce()'s result.  The
+// workgroup reads what it stored a level earlier: __syncthreads() orders that (workgroup scope), as in trsv_chain.
+template <typename T>
+__device__ T upper_levels(T *part, uint64_t c1, T *lds) {
+    T *in = part;
+    uint64_t m = c1;
+    while (m > 1) {
+        const uint64_t c = (m + kTile - 1) / kTile;
+        T *out = in + m;
+        for (uint64_t tile = 0; tile < c; ++tile) {
+            const uint64_t i = tile * kTile + threadIdx.x;
+            T v[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) v[k] = i + (uint64_t)k * kThreads < m ? in[i + (uint64_t)k * kThreads] : T(0);
+            const T s = tile_sum<T>(v[0], v[1], v[2], v[3], lds);
+            if (threadIdx.x == 0) out[tile] = s;
+        }
+        __syncthreads();
+        in = out;
+        m = c;
+    }
+    return in[0];
+}
+
+inline uint64_t tiles_of(uint64_t n) { return std::max<uint64_t>(1, (n + kTile - 1) / kTile); }
+// elements of the scratch of ONE dot over n elements: the first level's sums and every level above
+inline uint64_t scratch_elems(uint64_t n) {
+    uint64_t m = tiles_of(n), total = m;
+    while (m > 1) {
+        m = (m + kTile - 1) / kTile;
+        total += m;
+    }
+    return total;
+}
+inline unsigned first_level_grid(uint64_t n) { return (unsigned)std::min<uint64_t>(tiles_of(n), kMaxGrid); }
+
+// ---- the entry points the driver goes through, by handle and element type -------------------------------------------
+inline int mul_dev(spal_csr *a, const double *x, double *y, void *st) { return spal_csr_spmv_dev_f64(a, x, y, st); }
+inline int mul_dev(spal_csr *a, const float *x, float *y, void *st) { return spal_csr_spmv_dev_f32(a, x, y, st); }
+inline int mul_dev(spal_csc *a, const double *x, double *y, void *st) { return spal_csc_spmv_dev_f64(a, x, y, st); }
+inline int mul_dev(spal_csc *a, const float *x, float *y, void *st) { return spal_csc_spmv_dev_f32(a, x, y, st); }
+inline int solve_dev(spal_csr *m, int uplo, int unit, const double *b, double *x, void *st) { return spal_csr_trsv_dev_f64(m, uplo, unit, b, x, st); }
+inline int solve_dev(spal_csr *m, int uplo, int unit, const float *b, float *x, void *st) { return spal_csr_trsv_dev_f32(m, uplo, unit, b, x, st); }
+inline int solve_dev(spal_csc *m, int uplo, int unit, const double *b, double *x, void *st) { return spal_csc_trsv_dev_f64(m, uplo, unit, b, x, st); }
+inline int solve_dev(spal_csc *m, int uplo, int unit, const float *b, float *x, void *st) { return spal_csc_trsv_dev_f32(m, uplo, unit, b, x, st); }
+inline int analyse(spal_csr *m, int uplo, int unit, void *st) { return spal_csr_trsv_analyse(m, uplo, unit, st); }
+inline int analyse(spal_csc *m, int uplo, int unit, void *st) { return spal_csc_trsv_analyse(m, uplo, unit, st); }
+inline int product_plan(spal_csr *a) { return spal_csr_plan(a); }
+inline int product_plan(spal_csc *) { return SPAL_OK; }   // planned, twin included, by its constructor
+
+struct PinnedBuf {
+    void *p = nullptr;
+    PinnedBuf() = default;
+    PinnedBuf(const PinnedBuf &) = delete;
+    PinnedBuf &operator=(const PinnedBuf &) = delete;
+    ~PinnedBuf() { if (p) (void)hipHostFree(p); }
+};
+
+struct PooledStream {
+    hipStream_t s = nullptr;
+    PooledStream() = default;
+    PooledStream(const PooledStream &) = delete;
+    PooledStream &operator=(const PooledStream &) = delete;
+    ~PooledStream() { stream_release(s); }
+};
+
+// a's option "krylov_check_every", 0 (unset) resolved to the default: 1 with a preconditioner, 8 without
+template <typename H>
+int64_t krylov_check_every_of(H *a, bool preconditioned) {
+    int64_t check_every;
+    {
+        std::lock_guard<std::mutex> lock(solve_handle(a)->mu);
+        check_every = a->ops.krylov_check_every;
+    }
+    return check_every ? check_every : (preconditioned ? 1 : 8);
+}
+
+inline int refuse_capture(const char *fn, hipStream_t st) {
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone)
+        return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: the call polls and synchronises: it cannot be captured into a graph", fn);
+    return SPAL_OK;
+}
+
+// Plans first: nothing plans lazily once the iterations are being enqueued.  *sweeps = m's option "trsv_sweeps", -1
+// without m.
+template <typename H>
+int krylov_prepare(const char *fn, H *a, H *m, hipStream_t st, int64_t *sweeps) {
+    SPAL_TRY(product_plan(a));
+    *sweeps = m ? trsv_sweeps_of(solve_handle(m)) : -1;
+    if (m && *sweeps >= 0) {
+        SPAL_TRY(trsv_sweep_prepare(fn, solve_handle(m), 0, st));   // no analysis; a row without a diagonal: the solve's own message
+    } else if (m) {
+        SPAL_TRY(analyse(m, 0, 1, st));
+        SPAL_TRY(analyse(m, 1, 0, st));   // a row without a diagonal: the solve's own message
+    }
+    return SPAL_OK;
+}
+
+// out = M^-1 v (out != v): two exact solves, or `sweeps` >= 0 Jacobi sweeps per triangle through w0 / w1
+template <typename T, typename H>
+int prec_dev(const char *fn, H *m, int64_t sweeps, const T *v, T *out, T *w0, T *w1, hipStream_t st) {
+    if (sweeps >= 0) {
+        SPAL_TRY(trsv_sweep_enqueue(fn, solve_handle(m), 0, 1, (uint64_t)sweeps, v, out, w0, w1, st));
+        return trsv_sweep_enqueue(fn, solve_handle(m), 1, 0, (uint64_t)sweeps, out, out, w0, w1, st);
+    }
+    SPAL_TRY(solve_dev(m, 0, 1, v, out, st));
+    return solve_dev(m, 1, 0, out, out, st);
+}
+
+// every refusal of a solver that needs no device and is not about its own parameters
+template <typename T, typename H>
+int krylov_check_operands(const char *fn, H *a, H *m, double tol) {
+    if (!(tol >= 0.0)) return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: tol = %g must be >= 0", fn, tol);
+    if (a->nrows != a->ncols)
+        return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: the matrix is not square (%llu x %llu)", fn, (unsigned long long)a->nrows,
+                    (unsigned long long)a->ncols);
+    if (m) {
+        SPAL_TRY(check_same_device_and_dtype(fn, a, m));
+        if (m->nrows != a->nrows || m->ncols != a->ncols)
+            return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: the preconditioner is %llu x %llu but the matrix %llu x %llu", fn,
+                        (unsigned long long)m->nrows, (unsigned long long)m->ncols, (unsigned long long)a->nrows,
+                        (unsigned long long)a->ncols);
+    }
+    if (row_blocks(a) || (m && row_blocks(m))) return refuse_row_blocks(fn);
+    return SPAL_OK;
+}
+
+inline int refuse_lengths(const char *fn, uint64_t b_len, uint64_t x_len, uint64_t nrows) {
+    if (b_len != nrows || x_len != nrows)
+        return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: b.len() = %llu and x.len() = %llu but the matrix has %llu rows", fn,
+                    (unsigned long long)b_len, (unsigned long long)x_len, (unsigned long long)nrows);
+    return SPAL_OK;
+}
+
+}  // namespace spal

@@ -3,6 +3,9 @@
 // halves every tile (h = 512 .. 1: e[t] = e[t] + e[t + h]) and, when there is more than one tile, reduces the tile sums
 // the same way.  The order depends on n alone, so every kernel here returns the bits of the sequential text.
 //
+// (tile_sum, upper_levels, the scratch sizes, the plan preparation, M^-1 and the shared refusals are in krylov_kernels.hpp,
+// which spal_gmres.hip includes too.)
+//
 // ONE TILE IS ONE TRIP OF A WORKGROUP OF 256.  Thread t holds elements t, t + 256, t + 512, t + 768: strides 512 and 256
 // are thread-local ((v0 + v2) + (v1 + v3)), strides 128 and 64 go through LDS, strides 32 .. 1 are __shfl_down inside
 // wave 0.  The first level writes one sum per tile to a scratch array; a launch of ONE workgroup (`finish`) walks the
@@ -23,18 +26,12 @@
 // option "trsv_sweeps" is s >= 0 is applied by s Jacobi sweeps per triangle instead (trsv_sweep_enqueue),
 // through two more work vectors of the call.  Plans are built before the first iteration; work vectors, the scratch and the scalar block come from the caching allocator per call,
 // so concurrent calls on one handle share nothing but the matrix.
-#include "spal_ops.hpp"
-
-#include <cmath>
+#include "krylov_kernels.hpp"
 
 #pragma clang fp contract(off)
 
 namespace spal {
 namespace {
-
-constexpr uint64_t kTile = 1024;
-constexpr int kThreads = 256;
-constexpr unsigned kMaxGrid = 4096;   // first-level workgroups of a launch; each walks tiles blockIdx.x, + gridDim.x, ...
 
 // The scalars of one call, on the device; the host reads a copy in pinned memory when it polls.
 template <typename T>
@@ -43,27 +40,6 @@ struct Scal {
     unsigned long long it;
     unsigned done, reason, half, pad;
 };
-
-// The sum of one tile, valid in thread 0.  `lds` holds kThreads elements; ends with a barrier, so it can be reused.
-template <typename T>
-__device__ __forceinline__ T tile_sum(T v0, T v1, T v2, T v3, T *lds) {
-    const unsigned t = threadIdx.x;
-    T a = (v0 + v2) + (v1 + v3);                 // h = 512 (e[t], e[t + 256]), then h = 256
-    lds[t] = a;
-    __syncthreads();
-    if (t < 128) {
-        a = lds[t] + lds[t + 128];               // h = 128
-        if (t >= 64) lds[t] = a;                 // (its own slot: nobody else read it)
-    }
-    __syncthreads();
-    if (t < 64) {
-        a = a + lds[t + 64];                     // h = 64
-#pragma unroll
-        for (int h = 32; h >= 1; h >>= 1) a = a + __shfl_down(a, h, 64);
-    }
-    __syncthreads();
-    return a;
-}
 
 // ---- the first level, fused with the vector update in front of it ---------------------------------------------------
 enum VecOp {
@@ -161,31 +137,7 @@ __global__ __launch_bounds__(kThreads) void vec(VecArgs<T> g, uint64_t tiles) {
     }
 }
 
-// ---- the upper levels and the scalars, one workgroup ----------------------------------------------------------------
-// `part` holds the c1 sums of the first level, then room for every further level; returns reduce()'s result.  The
-// workgroup reads what it stored a level earlier: __syncthreads() orders that (workgroup scope), as in trsv_chain.
-template <typename T>
-__device__ T upper_levels(T *part, uint64_t c1, T *lds) {
-    T *in = part;
-    uint64_t m = c1;
-    while (m > 1) {
-        const uint64_t c = (m + kTile - 1) / kTile;
-        T *out = in + m;
-        for (uint64_t tile = 0; tile < c; ++tile) {
-            const uint64_t i = tile * kTile + threadIdx.x;
-            T v[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) v[k] = i + (uint64_t)k * kThreads < m ? in[i + (uint64_t)k * kThreads] : T(0);
-            const T s = tile_sum<T>(v[0], v[1], v[2], v[3], lds);
-            if (threadIdx.x == 0) out[tile] = s;
-        }
-        __syncthreads();
-        in = out;
-        m = c;
-    }
-    return in[0];
-}
-
+// ---- the upper levels (upper_levels, krylov_kernels.hpp) and the scalars, one workgroup --------------------------------
 enum FinOp { F_STORE, F_INIT, F_RZ, F_ALPHA_CG, F_TEST_CG, F_BETA, F_RHO, F_ALPHA_BI, F_HALF, F_OMEGA, F_TEST_BI };
 
 template <typename T>
@@ -270,21 +222,10 @@ __global__ __launch_bounds__(kThreads) void finish(FinArgs<T> g) {
 }
 
 // ---- host side of the launches --------------------------------------------------------------------------------------
-inline uint64_t tiles_of(uint64_t n) { return std::max<uint64_t>(1, (n + kTile - 1) / kTile); }
-// elements of the scratch of ONE dot over n elements: the first level's sums and every level above
-uint64_t scratch_elems(uint64_t n) {
-    uint64_t m = tiles_of(n), total = m;
-    while (m > 1) {
-        m = (m + kTile - 1) / kTile;
-        total += m;
-    }
-    return total;
-}
-
 template <typename T, int OP>
 hipError_t launch_vec(const VecArgs<T> &g, hipStream_t st) {
     const uint64_t tiles = tiles_of(g.n);
-    hipLaunchKernelGGL((vec<T, OP>), dim3((unsigned)std::min<uint64_t>(tiles, kMaxGrid)), dim3(kThreads), 0, st, g, tiles);
+    hipLaunchKernelGGL((vec<T, OP>), dim3(first_level_grid(g.n)), dim3(kThreads), 0, st, g, tiles);
     return hipGetLastError();
 }
 template <typename T, int OP>
@@ -346,28 +287,6 @@ int dot_dev(const char *fn, int device, const T *a, const T *b, uint64_t n, T *o
     return SPAL_OK;
 }
 
-// ---- the entry points the driver goes through, by handle and element type -------------------------------------------
-inline int mul_dev(spal_csr *a, const double *x, double *y, void *st) { return spal_csr_spmv_dev_f64(a, x, y, st); }
-inline int mul_dev(spal_csr *a, const float *x, float *y, void *st) { return spal_csr_spmv_dev_f32(a, x, y, st); }
-inline int mul_dev(spal_csc *a, const double *x, double *y, void *st) { return spal_csc_spmv_dev_f64(a, x, y, st); }
-inline int mul_dev(spal_csc *a, const float *x, float *y, void *st) { return spal_csc_spmv_dev_f32(a, x, y, st); }
-inline int solve_dev(spal_csr *m, int uplo, int unit, const double *b, double *x, void *st) { return spal_csr_trsv_dev_f64(m, uplo, unit, b, x, st); }
-inline int solve_dev(spal_csr *m, int uplo, int unit, const float *b, float *x, void *st) { return spal_csr_trsv_dev_f32(m, uplo, unit, b, x, st); }
-inline int solve_dev(spal_csc *m, int uplo, int unit, const double *b, double *x, void *st) { return spal_csc_trsv_dev_f64(m, uplo, unit, b, x, st); }
-inline int solve_dev(spal_csc *m, int uplo, int unit, const float *b, float *x, void *st) { return spal_csc_trsv_dev_f32(m, uplo, unit, b, x, st); }
-inline int analyse(spal_csr *m, int uplo, int unit, void *st) { return spal_csr_trsv_analyse(m, uplo, unit, st); }
-inline int analyse(spal_csc *m, int uplo, int unit, void *st) { return spal_csc_trsv_analyse(m, uplo, unit, st); }
-inline int product_plan(spal_csr *a) { return spal_csr_plan(a); }
-inline int product_plan(spal_csc *) { return SPAL_OK; }   // planned, twin included, by its constructor
-
-struct PinnedBuf {
-    void *p = nullptr;
-    PinnedBuf() = default;
-    PinnedBuf(const PinnedBuf &) = delete;
-    PinnedBuf &operator=(const PinnedBuf &) = delete;
-    ~PinnedBuf() { if (p) (void)hipHostFree(p); }
-};
-
 struct Record {
     int method = 0, preconditioned = 0, reason = 0;
     int64_t precond_sweeps = -1;
@@ -400,14 +319,7 @@ struct Run {
 
     int mul(const T *v, T *out) { return mul_dev(a, v, out, st); }
     // out = M^-1 v (out != v); without a preconditioner the caller uses v itself
-    int prec(const T *v, T *out) {
-        if (sweeps >= 0) {
-            SPAL_TRY(trsv_sweep_enqueue(fn, solve_handle(m), 0, 1, (uint64_t)sweeps, v, out, w0, w1, st));
-            return trsv_sweep_enqueue(fn, solve_handle(m), 1, 0, (uint64_t)sweeps, out, out, w0, w1, st);
-        }
-        SPAL_TRY(solve_dev(m, 0, 1, v, out, st));
-        return solve_dev(m, 1, 0, out, out, st);
-    }
+    int prec(const T *v, T *out) { return prec_dev<T, H>(fn, m, sweeps, v, out, w0, w1, st); }
     template <int OP>
     int v(const T *va, const T *vb, const T *vc, const T *vd, T *x, T *y) {
         VecArgs<T> g = {va, vb, vc, vd, x, y, s, part0, part1, n};
@@ -427,25 +339,10 @@ int krylov_run(const char *fn, H *a, int method, H *m, const T *b, T *x, double 
                spal_krylov_info *info) {
     const uint64_t n = a->nrows;
     spal_csr *owner = solve_handle(a);   // whose lock guards a's option and its "krylov" string
-    int64_t check_every;
-    {
-        std::lock_guard<std::mutex> lock(owner->mu);
-        check_every = a->ops.krylov_check_every;
-    }
-    if (check_every == 0) check_every = m ? 1 : 8;
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone)
-        return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: the call polls and synchronises: it cannot be captured into a graph", fn);
-
-    // plans first: nothing plans lazily once the iterations are being enqueued
-    SPAL_TRY(product_plan(a));
-    const int64_t sweeps = m ? trsv_sweeps_of(solve_handle(m)) : -1;
-    if (m && sweeps >= 0) {
-        SPAL_TRY(trsv_sweep_prepare(fn, solve_handle(m), 0, st));   // no analysis; a row without a diagonal: the solve's own message
-    } else if (m) {
-        SPAL_TRY(analyse(m, 0, 1, st));
-        SPAL_TRY(analyse(m, 1, 0, st));   // a row without a diagonal: the solve's own message
-    }
+    const int64_t check_every = krylov_check_every_of(a, m != nullptr);
+    SPAL_TRY(refuse_capture(fn, st));
+    int64_t sweeps = -1;
+    SPAL_TRY(krylov_prepare(fn, a, m, st, &sweeps));
     // work vectors, scratch, scalars
     const bool cg = method == SPAL_KRYLOV_CG;
     const int nwork = cg ? (m ? 4 : 3) : (m ? 8 : 6);
@@ -587,19 +484,7 @@ int krylov_check(const char *fn, H *a, int method, H *m, const T *b, T *x, doubl
     SPAL_TRY(check_dtype<T>(fn, a->elem_size));
     if (method != SPAL_KRYLOV_CG && method != SPAL_KRYLOV_BICGSTAB)
         return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: method = %d must be 0 (CG) or 1 (BiCGStab)", fn, method);
-    if (!(tol >= 0.0)) return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: tol = %g must be >= 0", fn, tol);
-    if (a->nrows != a->ncols)
-        return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: the matrix is not square (%llu x %llu)", fn, (unsigned long long)a->nrows,
-                    (unsigned long long)a->ncols);
-    if (m) {
-        SPAL_TRY(check_same_device_and_dtype(fn, a, m));
-        if (m->nrows != a->nrows || m->ncols != a->ncols)
-            return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: the preconditioner is %llu x %llu but the matrix %llu x %llu", fn,
-                        (unsigned long long)m->nrows, (unsigned long long)m->ncols, (unsigned long long)a->nrows,
-                        (unsigned long long)a->ncols);
-    }
-    if (row_blocks(a) || (m && row_blocks(m))) return refuse_row_blocks(fn);
-    return SPAL_OK;
+    return krylov_check_operands<T, H>(fn, a, m, tol);
 }
 
 template <typename T, typename H>
@@ -612,21 +497,11 @@ int krylov_dev(const char *fn, H *a, int method, H *m, const T *b, T *x, double 
     return krylov_run<T, H>(fn, a, method, m, b, x, tol, maxit, (hipStream_t)stream, info);
 }
 
-struct PooledStream {
-    hipStream_t s = nullptr;
-    PooledStream() = default;
-    PooledStream(const PooledStream &) = delete;
-    PooledStream &operator=(const PooledStream &) = delete;
-    ~PooledStream() { stream_release(s); }
-};
-
 template <typename T, typename H>
 int krylov_host(const char *fn, H *a, int method, H *m, const T *b, uint64_t b_len, T *x, uint64_t x_len, double tol,
                 uint64_t maxit, spal_krylov_info *info) {
     SPAL_TRY((krylov_check<T, H>(fn, a, method, m, b, x, tol, info)));
-    if (b_len != a->nrows || x_len != a->nrows)
-        return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: b.len() = %llu and x.len() = %llu but the matrix has %llu rows", fn,
-                    (unsigned long long)b_len, (unsigned long long)x_len, (unsigned long long)a->nrows);
+    SPAL_TRY(refuse_lengths(fn, b_len, x_len, a->nrows));
     DeviceGuard guard(a->device);
     if (guard.status != SPAL_OK) return guard.status;
     const uint64_t n = a->nrows;

@@ -1,5 +1,5 @@
 // spal_ops.hpp -- the host layer the sparse operations share: spal_spgemm.hip, spal_spadd.hip,
-// spal_spmm.hip, spal_trsv.hip, spal_trsv_sweep.hip, spal_ilu.hip and spal_krylov.hip keep their kernels, their driver, their option's validation and their
+// spal_spmm.hip, spal_trsv.hip, spal_trsv_sweep.hip, spal_ilu.hip, spal_krylov.hip and spal_gmres.hip keep their kernels, their driver, their option's validation and their
 // info JSON; what surrounds a launch the same way in each of them is here, once.  (Not installed.)
 #pragma once
 
@@ -200,6 +200,8 @@ int trsv_describe_append(char *buf, size_t buf_len, spal_csr *a);
 int trsv_sweep_describe_append(char *buf, size_t buf_len, spal_csr *a);
 // the "krylov" object of a handle a solve ran with as A (spal_krylov.hip; the string is read under the solve handle's lock)
 int krylov_describe_append(char *buf, size_t buf_len, const OpState &s, spal_csr *solve);
+// the "gmres" object of a handle spal_*_gmres_* ran with as A (spal_gmres.hip; read under the same lock)
+int gmres_describe_append(char *buf, size_t buf_len, const OpState &s, spal_csr *solve);
 inline int ops_describe_append(char *buf, size_t buf_len, const OpState &s, spal_csr *solve) {
     SPAL_TRY(describe_append(buf, buf_len, "spgemm", s.spgemm_info));   // a product of spal_*_mul: how it was built
     SPAL_TRY(describe_append(buf, buf_len, "spadd", s.spadd_info));     // a result of spal_*_add / _sub / _neg
@@ -207,7 +209,8 @@ inline int ops_describe_append(char *buf, size_t buf_len, const OpState &s, spal
     SPAL_TRY(trsv_describe_append(buf, buf_len, solve));                // a triangle of it was analysed for a solve
     SPAL_TRY(trsv_sweep_describe_append(buf, buf_len, solve));          // it was prepared for sweeps on a triangle
     SPAL_TRY(describe_append(buf, buf_len, "ilu0", s.ilu_info));        // a factor of spal_*_ilu0: how it was built
-    return krylov_describe_append(buf, buf_len, s, solve);              // spal_*_krylov_* ran with it as A: the last call
+    SPAL_TRY(krylov_describe_append(buf, buf_len, s, solve));           // spal_*_krylov_* ran with it as A: the last call
+    return gmres_describe_append(buf, buf_len, s, solve);               // spal_*_gmres_* ran with it as A: the last call
 }
 
 }  // namespace spal

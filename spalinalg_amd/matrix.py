@@ -313,6 +313,33 @@ class _DeviceMatrix:
                                                          C.c_double(tol), u64(maxit), _stream_ptr(stream), C.byref(info)))
         return _krylov_info(info)
 
+    def gmres(self, b, M=None, x0=None, restart: int = 30, tol: float = 1e-8, maxit: int = 1000):
+        """Solves A x = b by restarted GMRES(restart) on the device (spal_*_gmres_*), right-preconditioned
+        by `M` as krylov() is (an ILU(0) factor handle of this class: two solves, or "trsv_sweeps" sweeps per triangle).
+        Host vectors; returns (x, KrylovInfo).  Bit for bit the text written out in include/spal.h, whatever
+        "krylov_check_every" is."""
+        b = np.ascontiguousarray(b)
+        if b.dtype not in (np.float32, np.float64):
+            b = b.astype(self.dtype)
+        if b.ndim != 1:
+            raise TypeError("gmres() takes one right-hand side, a 1-D vector")
+        x = np.zeros_like(b) if x0 is None else np.array(x0, dtype=b.dtype, order="C", copy=True)
+        if M is not None and type(M) is not type(self):
+            raise TypeError(f"M must be a {type(self).__name__} (the factor of a matrix of the same format)")
+        info = _KrylovInfoC()
+        check(self._fn(f"gmres_{_sfx(b.dtype)}")(self._h, M._h if M is not None else None, _p(b), u64(b.size), _p(x),
+                                                 u64(x.size), u64(restart), C.c_double(tol), u64(maxit), C.byref(info)))
+        return x, _krylov_info(info)
+
+    def gmres_dev(self, b_ptr: int, x_ptr: int, M=None, restart: int = 30, tol: float = 1e-8, maxit: int = 1000,
+                  stream=None) -> KrylovInfo:
+        """Device pointers: x holds x0 on entry and the result on exit; the call polls, so it synchronises `stream`."""
+        info = _KrylovInfoC()
+        check(self._fn(f"gmres_dev_{_sfx(self.dtype)}")(self._h, M._h if M is not None else None, vp(b_ptr), vp(x_ptr),
+                                                        u64(restart), C.c_double(tol), u64(maxit), _stream_ptr(stream),
+                                                        C.byref(info)))
+        return _krylov_info(info)
+
     def alloc_vectors(self, stream=None):
         """Device pointers (x, y) of vectors owned by this handle and placed so that the stores of y do not collide
         with the matrix stream (spal_csr_alloc_vectors: a walk over the device's memory, setup time).  CSR handles."""
@@ -790,6 +817,31 @@ class _Compressed:
                 raise TypeError("precond_sweeps needs M, the factor it is an option of")
             M.device(device).set_option("trsv_sweeps", int(precond_sweeps))
         return self.device(device).krylov(b, method, None if M is None else M.device(device), x0, tol, maxit)
+
+    def gmres(self, b, M=None, x0=None, restart: int = 30, tol: float = 1e-8, maxit: int = 1000, device: int = 0,
+              precond_sweeps=None):
+        """x with A x = b by restarted GMRES(restart) on the device, for matrices that are not symmetric (BiCGStab, the
+        other solver for them, can break down); right-preconditioned by `M = a.ilu0()`, with `precond_sweeps` as in
+        solve().  Returns (x, info) as solve() does: reasons 0 and 1 are decided on the true residual, recomputed at
+        the head of every cycle.  restart is 1 .. 256; the call holds restart + 1 basis vectors on the device.  Bit for
+        bit the text of include/spal.h."""
+        b = np.asarray(b)
+        if self._nrows != self._ncols:
+            raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT, f"gmres: the matrix is not square ({self._nrows} x {self._ncols})")
+        if b.ndim != 1 or b.shape[0] != self._nrows:
+            raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT, f"gmres: b has shape {b.shape} but the matrix has {self._nrows} rows")
+        if x0 is not None and np.shape(x0) != b.shape:
+            raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT, f"gmres: x0 has shape {np.shape(x0)} but b {b.shape}")
+        if not 1 <= int(restart) <= 256:
+            raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT, f"gmres: restart = {int(restart)} must be 1 .. 256 (one Hessenberg "
+                        "column element per thread of the scalar workgroup)")
+        if M is not None and type(M) is not type(self):
+            raise TypeError(f"M must be a {type(self).__name__}, e.g. self.ilu0()")
+        if precond_sweeps is not None:
+            if M is None:
+                raise TypeError("precond_sweeps needs M, the factor it is an option of")
+            M.device(device).set_option("trsv_sweeps", int(precond_sweeps))
+        return self.device(device).gmres(b, None if M is None else M.device(device), x0, int(restart), tol, maxit)
 
     def _mul_mat(self, other, device: int = 0):
         """`&self * &other` (src/csr/ops/mul.rs:5-59 / src/csc/ops/mul.rs:5-60) on the device; the result is downloaded
