@@ -624,6 +624,71 @@ int spal_csc_gmres_dev_f64(spal_csc_t a, spal_csc_t m, const double *b_dev, doub
 int spal_csc_gmres_dev_f32(spal_csc_t a, spal_csc_t m, const float *b_dev, float *x_dev, uint64_t restart,
                            double tol, uint64_t maxit, void *stream, spal_krylov_info *info);
 
+/* ---- multicolour reordering: greedy colouring and B = P A P^T -------------------------------------------
+ * Not in the reference.  An exact triangular solve costs one launch step per level; numbering the rows
+ * colour by colour leaves both triangles of P A P^T with at most as many levels as there are colours.
+ * The contract is again a sequential text the device reproduces exactly.
+ *
+ *   Graph.     A is square with n rows; the vertices are the rows.  i ~ j iff i != j and (i, j) or (j, i) is stored.
+ *              Values play no part: a stored zero is an edge.
+ *   Priority.  key(i) = mix32((i + seed) mod 2^32), in 32-bit arithmetic
+ *                  x ^= x >> 16;  x *= 0x7feb352d;  x ^= x >> 15;  x *= 0x846ca68b;  x ^= x >> 16
+ *              a bijection of the 32-bit words: keys are distinct for n < 2^32, no tie-break is needed.
+ *              mix32(0) = 0, mix32(1) = 1753845952, mix32(2) = 3507691905, mix32(3) = 1408362973.
+ *   Colouring. Visit the vertices by DESCENDING key; a vertex takes the smallest colour >= 0 that no neighbour
+ *              visited before it has.  ncolours = the largest colour + 1 (0 for n = 0).
+ *   Ordering.  perm maps new -> old and lists the rows by (colour, old row) ascending: a stable counting sort.
+ *   Symmetric permutation.  B = P A P^T:  B[i'][j'] = A[perm[i']][perm[j']], columns ascending inside a row, the values
+ *              A's bits, moved and never recomputed (f32 and f64 bit-identical, NaN payloads included).  B stores
+ *              (i', i') exactly where A stores (perm[i'], perm[i']): ILU(0)'s precondition carries over.
+ *
+ * Host, no device: spal_colour_greedy is the text on uint64 arrays (it builds the transposed adjacency itself),
+ * spal_perm_from_colours the ordering.  Both refuse null pointers, a rowptr that does not ascend from 0 and a column
+ * >= n (SPAL_ERR_INVALID_ARGUMENT; a colour >= n likewise).
+ *
+ * Device (spal_colour.hip).  spal_*_colour returns the text's colours by Jones-Plassmann rounds: a row is READY in
+ * round r when every neighbour (of A's row or of A^T's row) with a HIGHER key was coloured in a round before r, and
+ * then takes the smallest colour absent among those higher-key neighbours; lower-key neighbours are ignored even when
+ * coloured.  Every round is one launch over the rows still uncoloured; order between rounds is stream order alone (no
+ * flags, no spins, no grid sync); the host polls a device counter of uncoloured rows after a batch of rounds.
+ * *rounds = the longest path of descending keys, counted in vertices (at most n; 0 for n = 0).  colour_host may be NULL.
+ * spal_*_permute builds B for ANY permutation perm_host[n] (new -> old) as a new, independent handle of a's type: a
+ * relabel-and-gather kernel, then two stable transposes put the columns back in order.  spal_*_multicolour runs
+ * colour -> order -> permute with only the poll block crossing to the host.  The result keeps perm on the device:
+ * spal_*_ordering downloads it (ncolours = 0 for a handle made by spal_*_permute; a handle without an ordering is
+ * refused), spal_*_permute_vec_* moves a vector between the orders:
+ *   direction 0:  y[i'] = x[perm[i']]   (into the handle's order)      direction 1:  y[perm[i']] = x[i']   (back)
+ * The _dev forms are enqueued on `stream` and not synchronised; colour, permute and multicolour synchronise it.
+ * SPAL_ERR_INVALID_ARGUMENT: null arguments; a matrix that is not square; perm that is not a permutation of 0 .. n-1
+ * (the message names the first offending position) or n != nrows; direction outside {0, 1}; x == y; vectors of the
+ * wrong length or element type.  SPAL_ERR_UNSUPPORTED: a handle held as row blocks.  Nothing leaks on failure.
+ * describe() of a handle with an ordering gains "ordering": {colours, rounds, seed, colour_ms, permute_ms}.
+ * Not provided: applying a permuted factor inside spal_*_krylov_* / _gmres_* (solve the permuted system instead:
+ * p = multicolour(a), f = ilu0(p), x = from_order(solve(p, to_order(b), f))). */
+int spal_colour_greedy(uint64_t n, const uint64_t *rowptr, const uint64_t *colind, uint64_t seed, uint64_t *colour,
+                       uint64_t *ncolours);                                       /* host only */
+int spal_perm_from_colours(uint64_t n, const uint64_t *colour, uint64_t *perm);  /* host only */
+int spal_csr_colour(spal_csr_t a, uint64_t seed, void *stream, uint64_t *colour_host, uint64_t *ncolours,
+                    uint64_t *rounds);
+int spal_csc_colour(spal_csc_t a, uint64_t seed, void *stream, uint64_t *colour_host, uint64_t *ncolours,
+                    uint64_t *rounds);
+int spal_csr_permute(spal_csr_t a, const uint64_t *perm_host, uint64_t n, void *stream, spal_csr_t *out);
+int spal_csc_permute(spal_csc_t a, const uint64_t *perm_host, uint64_t n, void *stream, spal_csc_t *out);
+int spal_csr_multicolour(spal_csr_t a, uint64_t seed, void *stream, spal_csr_t *out, uint64_t *ncolours);
+int spal_csc_multicolour(spal_csc_t a, uint64_t seed, void *stream, spal_csc_t *out, uint64_t *ncolours);
+int spal_csr_ordering(spal_csr_t a, uint64_t *perm_host, uint64_t *ncolours);
+int spal_csc_ordering(spal_csc_t a, uint64_t *perm_host, uint64_t *ncolours);
+int spal_csr_permute_vec_f64(spal_csr_t a, const double *x, uint64_t x_len, double *y, uint64_t y_len,
+                             int direction);                                      /* host vectors */
+int spal_csr_permute_vec_f32(spal_csr_t a, const float *x, uint64_t x_len, float *y, uint64_t y_len, int direction);
+int spal_csr_permute_vec_dev_f64(spal_csr_t a, const double *x_dev, double *y_dev, int direction, void *stream);
+int spal_csr_permute_vec_dev_f32(spal_csr_t a, const float *x_dev, float *y_dev, int direction, void *stream);
+int spal_csc_permute_vec_f64(spal_csc_t a, const double *x, uint64_t x_len, double *y, uint64_t y_len,
+                             int direction);
+int spal_csc_permute_vec_f32(spal_csc_t a, const float *x, uint64_t x_len, float *y, uint64_t y_len, int direction);
+int spal_csc_permute_vec_dev_f64(spal_csc_t a, const double *x_dev, double *y_dev, int direction, void *stream);
+int spal_csc_permute_vec_dev_f32(spal_csc_t a, const float *x_dev, float *y_dev, int direction, void *stream);
+
 /* ---- CSR <-> CSC on the device ------------------------------------------------
  * Replace `impl From<&CscMatrix<T>> for CsrMatrix<T>` (src/csr/conv/csc.rs:4-52)
  * and `impl From<&CsrMatrix<T>> for CscMatrix<T>` (src/csc/conv/csr.rs:4-52),

@@ -19,6 +19,10 @@
 //   a.solve(b, method, M, x0, tol, maxit), dot(a, b)     not in the reference: CG / BiCGStab and their dot product
 //                                                        (include/spal.h, spal_*_krylov_*, spal_dot_*)
 //   a.gmres(b, restart, M, x0, tol, maxit)               not in the reference: restarted GMRES (spal_*_gmres_*)
+//   a.colour(seed), a.permute(perm), a.multicolour(seed), p.ordering(), p.to_order(v), p.from_order(v),
+//   colour_greedy(n, rowptr, colind, seed), perm_from_colours(colours)
+//                                                        not in the reference: the multicolour ordering
+//                                                        (spal_*_colour, _permute, _multicolour, spal_colour_greedy)
 //
 // A failed `assert!` in the reference is a panic; here it is a
 // spalinalg::Panic exception (the Rust shim in rust_shim/ turns the same
@@ -69,6 +73,7 @@ template <> struct Abi<double> {
     static constexpr auto csr_trsv_sweep = spal_csr_trsv_sweep_f64;
     static constexpr auto csr_krylov = spal_csr_krylov_f64;
     static constexpr auto csr_gmres = spal_csr_gmres_f64;
+    static constexpr auto csr_permute_vec = spal_csr_permute_vec_f64;
     static constexpr auto dot = spal_dot_f64;
     static constexpr auto csr_download = spal_csr_download_f64;
     static constexpr auto csc_create = spal_csc_create_f64;
@@ -78,6 +83,7 @@ template <> struct Abi<double> {
     static constexpr auto csc_trsv_sweep = spal_csc_trsv_sweep_f64;
     static constexpr auto csc_krylov = spal_csc_krylov_f64;
     static constexpr auto csc_gmres = spal_csc_gmres_f64;
+    static constexpr auto csc_permute_vec = spal_csc_permute_vec_f64;
     static constexpr auto coo_to_csr = spal_coo_to_csr_f64;
     static constexpr auto coo_to_csc = spal_coo_to_csc_f64;
     static constexpr auto csc_download = spal_csc_download_f64;
@@ -90,6 +96,7 @@ template <> struct Abi<float> {
     static constexpr auto csr_trsv_sweep = spal_csr_trsv_sweep_f32;
     static constexpr auto csr_krylov = spal_csr_krylov_f32;
     static constexpr auto csr_gmres = spal_csr_gmres_f32;
+    static constexpr auto csr_permute_vec = spal_csr_permute_vec_f32;
     static constexpr auto dot = spal_dot_f32;
     static constexpr auto csr_download = spal_csr_download_f32;
     static constexpr auto csc_create = spal_csc_create_f32;
@@ -99,6 +106,7 @@ template <> struct Abi<float> {
     static constexpr auto csc_trsv_sweep = spal_csc_trsv_sweep_f32;
     static constexpr auto csc_krylov = spal_csc_krylov_f32;
     static constexpr auto csc_gmres = spal_csc_gmres_f32;
+    static constexpr auto csc_permute_vec = spal_csc_permute_vec_f32;
     static constexpr auto coo_to_csr = spal_coo_to_csr_f32;
     static constexpr auto coo_to_csc = spal_coo_to_csc_f32;
     static constexpr auto csc_download = spal_csc_download_f32;
@@ -138,6 +146,35 @@ T dot(const std::vector<T> &a, const std::vector<T> &b) {
     T out = T(0);
     detail::check(detail::Abi<T>::dot(a.data(), b.data(), a.size(), &out));
     return out;
+}
+
+// The multicolour ordering of include/spal.h: what colour() returns, and what ordering() reads back from a
+// matrix made by permute() or multicolour().
+struct Colouring {
+    std::vector<usize> colours;
+    usize ncolours, rounds;   // rounds: Jones-Plassmann rounds = the longest path of descending keys, in vertices
+};
+struct Ordering {
+    std::vector<usize> perm;  // new -> old
+    usize ncolours;           // 0: the permutation was the caller's
+};
+// The text itself on host arrays, no device (spal_colour_greedy, spal_perm_from_colours): colours by descending
+// key(i) = mix32(i + seed), and the rows listed by (colour, row).
+inline Colouring colour_greedy(usize n, const std::vector<usize> &rowptr, const std::vector<usize> &colind, usize seed = 0) {
+    if (rowptr.size() != n + 1)
+        throw Panic(SPAL_ERR_INVALID_ARGUMENT, "colour_greedy: rowptr.len() = " + std::to_string(rowptr.size()) +
+                                                   " but n + 1 = " + std::to_string(n + 1));
+    if (colind.size() < rowptr[n])
+        throw Panic(SPAL_ERR_INVALID_ARGUMENT, "colour_greedy: colind.len() = " + std::to_string(colind.size()) +
+                                                   " but rowptr[n] = " + std::to_string(rowptr[n]));
+    Colouring c{std::vector<usize>(n), 0, 0};
+    detail::check(spal_colour_greedy(n, rowptr.data(), colind.data(), seed, c.colours.data(), &c.ncolours));
+    return c;
+}
+inline std::vector<usize> perm_from_colours(const std::vector<usize> &colours) {
+    std::vector<usize> perm(colours.size());
+    detail::check(spal_perm_from_colours(colours.size(), colours.data(), perm.data()));
+    return perm;
 }
 
 // ---------------------------------------------------------------------------
@@ -263,6 +300,39 @@ class CsrMatrix {
         return adopt(h);
     }
 
+    // The multicolour ordering (include/spal.h).  colour(): the greedy colouring of the graph of A + A^T by
+    // hashed priority, exactly the sequential text, by rounds on the device.  permute(perm): B = P A P^T with
+    // B[i'][j'] = A[perm[i']][perm[j']], values moved.  multicolour(): the rows numbered colour by colour, so that both
+    // triangles (and those of ilu0()) have at most ncolours levels.  The results keep their permutation: ordering()
+    // reads it back, to_order(v) = v[perm] and from_order() its inverse move a vector between the two numberings:
+    //   auto p = a.multicolour(); auto f = p.ilu0();
+    //   auto x = p.from_order(p.solve(p.to_order(b), Method::BiCgStab, &f).x);
+    // Panic when the matrix is not square, perm is no permutation, or (ordering, to_order, from_order) the matrix is no
+    // result of permute() / multicolour().
+    Colouring colour(usize seed = 0) const {
+        Colouring c{std::vector<usize>(nrows_), 0, 0};
+        detail::check(spal_csr_colour(device_handle(), seed, nullptr, c.colours.data(), &c.ncolours, &c.rounds));
+        return c;
+    }
+    CsrMatrix permute(const std::vector<usize> &perm) const {
+        spal_csr_t h = nullptr;
+        detail::check(spal_csr_permute(device_handle(), perm.data(), perm.size(), nullptr, &h));
+        return adopt(h);
+    }
+    CsrMatrix multicolour(usize seed = 0) const {
+        spal_csr_t h = nullptr;
+        usize ncolours = 0;
+        detail::check(spal_csr_multicolour(device_handle(), seed, nullptr, &h, &ncolours));
+        return adopt(h);
+    }
+    Ordering ordering() const {
+        Ordering o{std::vector<usize>(nrows_), 0};
+        detail::check(spal_csr_ordering(device_handle(), o.perm.data(), &o.ncolours));
+        return o;
+    }
+    std::vector<T> to_order(const std::vector<T> &v) const { return permute_vec(v, 0); }
+    std::vector<T> from_order(const std::vector<T> &v) const { return permute_vec(v, 1); }
+
     // x with A x = b by CG (A symmetric positive definite) or BiCGStab on the device, optionally preconditioned by
     // M = ilu0() (nullptr: none), from x0 (empty: zeros); bit for bit the loops of include/spal.h (spal_csr_krylov_*).
     // Panics when the matrix is not square or a length differs; a breakdown is no panic but reason 2.
@@ -330,6 +400,11 @@ class CsrMatrix {
         spal_csr_t h = nullptr;
         detail::check(op(device_handle(), rhs.device_handle(), nullptr, &h));
         return adopt(h);
+    }
+    std::vector<T> permute_vec(const std::vector<T> &v, int direction) const {
+        std::vector<T> y(v.size());
+        detail::check(detail::Abi<T>::csr_permute_vec(device_handle(), v.data(), v.size(), y.data(), y.size(), direction));
+        return y;
     }
     static CsrMatrix adopt(spal_csr_t h) {   // downloads h into a host matrix that also owns h
         std::unique_ptr<spal_csr, detail::CsrDeleter> guard(h);
@@ -457,6 +532,39 @@ class CscMatrix {
         detail::check(spal_csc_ilu0(device_handle(), nullptr, &h));
         return adopt(h);
     }
+
+    // The multicolour ordering (include/spal.h).  colour(): the greedy colouring of the graph of A + A^T by
+    // hashed priority, exactly the sequential text, by rounds on the device.  permute(perm): B = P A P^T with
+    // B[i'][j'] = A[perm[i']][perm[j']], values moved.  multicolour(): the rows numbered colour by colour, so that both
+    // triangles (and those of ilu0()) have at most ncolours levels.  The results keep their permutation: ordering()
+    // reads it back, to_order(v) = v[perm] and from_order() its inverse move a vector between the two numberings:
+    //   auto p = a.multicolour(); auto f = p.ilu0();
+    //   auto x = p.from_order(p.solve(p.to_order(b), Method::BiCgStab, &f).x);
+    // Panic when the matrix is not square, perm is no permutation, or (ordering, to_order, from_order) the matrix is no
+    // result of permute() / multicolour().
+    Colouring colour(usize seed = 0) const {
+        Colouring c{std::vector<usize>(nrows_), 0, 0};
+        detail::check(spal_csc_colour(device_handle(), seed, nullptr, c.colours.data(), &c.ncolours, &c.rounds));
+        return c;
+    }
+    CscMatrix permute(const std::vector<usize> &perm) const {
+        spal_csc_t h = nullptr;
+        detail::check(spal_csc_permute(device_handle(), perm.data(), perm.size(), nullptr, &h));
+        return adopt(h);
+    }
+    CscMatrix multicolour(usize seed = 0) const {
+        spal_csc_t h = nullptr;
+        usize ncolours = 0;
+        detail::check(spal_csc_multicolour(device_handle(), seed, nullptr, &h, &ncolours));
+        return adopt(h);
+    }
+    Ordering ordering() const {
+        Ordering o{std::vector<usize>(nrows_), 0};
+        detail::check(spal_csc_ordering(device_handle(), o.perm.data(), &o.ncolours));
+        return o;
+    }
+    std::vector<T> to_order(const std::vector<T> &v) const { return permute_vec(v, 0); }
+    std::vector<T> from_order(const std::vector<T> &v) const { return permute_vec(v, 1); }
     // x with A x = b by CG (A symmetric positive definite) or BiCGStab on the device, optionally preconditioned by
     // M = ilu0() (nullptr: none), from x0 (empty: zeros); bit for bit the loops of include/spal.h (spal_csc_krylov_*).
     // Panics when the matrix is not square or a length differs; a breakdown is no panic but reason 2.
@@ -527,6 +635,11 @@ class CscMatrix {
         spal_csc_t h = nullptr;
         detail::check(op(device_handle(), rhs.device_handle(), nullptr, &h));
         return adopt(h);
+    }
+    std::vector<T> permute_vec(const std::vector<T> &v, int direction) const {
+        std::vector<T> y(v.size());
+        detail::check(detail::Abi<T>::csc_permute_vec(device_handle(), v.data(), v.size(), y.data(), y.size(), direction));
+        return y;
     }
     static CscMatrix adopt(spal_csc_t h) {
         std::unique_ptr<spal_csc, detail::CscDeleter> guard(h);

@@ -254,6 +254,55 @@ impl<T: HipScalar> DeviceCsr<T> {
         unsafe { ffi::check(ffi::spal_csr_ilu0(self.h, stream, &mut out)); }
         DeviceCsr::from_raw(out)
     }
+
+    /// The greedy colouring of the graph of A + A^T by hashed priority (include/spal.h): exactly the
+    /// sequential text, by Jones-Plassmann rounds on the device.  Returns `(colours, ncolours, rounds)`.
+    pub fn colour(&self, seed: u64, stream: *mut c_void) -> (Vec<usize>, usize, usize) {
+        let (nrows, _, _) = self.shape();
+        let mut colours = vec![0u64; nrows];
+        let (mut nc, mut rounds) = (0u64, 0u64);
+        unsafe { ffi::check(ffi::spal_csr_colour(self.h, seed, stream, colours.as_mut_ptr(), &mut nc, &mut rounds)); }
+        (colours.into_iter().map(|c| c as usize).collect(), nc as usize, rounds as usize)
+    }
+
+    /// `B = P A P^T`, `B[i'][j'] = A[perm[i']][perm[j']]`, for any permutation `perm` (new -> old); values are moved.
+    /// The result keeps `perm` (`ordering`, `permute_vec_dev`).  Panics when `perm` is no permutation of `0..nrows`.
+    pub fn permute(&self, perm: &[usize], stream: *mut c_void) -> DeviceCsr<T> {
+        let p: Vec<u64> = perm.iter().map(|&i| i as u64).collect();
+        let mut out = std::ptr::null_mut();
+        unsafe { ffi::check(ffi::spal_csr_permute(self.h, p.as_ptr(), p.len() as u64, stream, &mut out)); }
+        DeviceCsr::from_raw(out)
+    }
+
+    /// colour -> order by (colour, row) -> permute on the device: both triangles of the result, and of its `ilu0`,
+    /// have at most `ordering().1` levels.
+    pub fn multicolour(&self, seed: u64, stream: *mut c_void) -> DeviceCsr<T> {
+        let mut out = std::ptr::null_mut();
+        let mut nc = 0u64;
+        unsafe { ffi::check(ffi::spal_csr_multicolour(self.h, seed, stream, &mut out, &mut nc)); }
+        DeviceCsr::from_raw(out)
+    }
+
+    /// `(perm, ncolours)` of a handle made by `permute` (`ncolours == 0`) or `multicolour`; panics on any other handle.
+    pub fn ordering(&self) -> (Vec<usize>, usize) {
+        let (nrows, _, _) = self.shape();
+        let mut perm = vec![0u64; nrows];
+        let mut nc = 0u64;
+        unsafe { ffi::check(ffi::spal_csr_ordering(self.h, perm.as_mut_ptr(), &mut nc)); }
+        (perm.into_iter().map(|i| i as usize).collect(), nc as usize)
+    }
+
+    /// `y[i'] = x[perm[i']]` (into this handle's order), or with `back` `y[perm[i']] = x[i']`; enqueued on `stream`.
+    ///
+    /// # Safety
+    /// `x_dev` and `y_dev` must hold `nrows` elements each and must not be the same vector.
+    pub unsafe fn permute_vec_dev(&self, x_dev: *const T, y_dev: *mut T, back: bool, stream: *mut c_void) {
+        if std::mem::size_of::<T>() == 8 {
+            ffi::check(ffi::spal_csr_permute_vec_dev_f64(self.h, x_dev as *const f64, y_dev as *mut f64, back as c_int, stream));
+        } else {
+            ffi::check(ffi::spal_csr_permute_vec_dev_f32(self.h, x_dev as *const f32, y_dev as *mut f32, back as c_int, stream));
+        }
+    }
 }
 
 impl<T: HipScalar> DeviceCsc<T> {
@@ -432,6 +481,55 @@ impl<T: HipScalar> DeviceCsc<T> {
         let mut out = std::ptr::null_mut();
         unsafe { ffi::check(ffi::spal_csc_ilu0(self.h, stream, &mut out)); }
         DeviceCsc { h: out, _t: PhantomData }
+    }
+
+    /// The greedy colouring of the graph of A + A^T by hashed priority (include/spal.h): exactly the
+    /// sequential text, by Jones-Plassmann rounds on the device.  Returns `(colours, ncolours, rounds)`.
+    pub fn colour(&self, seed: u64, stream: *mut c_void) -> (Vec<usize>, usize, usize) {
+        let (nrows, _, _) = self.shape();
+        let mut colours = vec![0u64; nrows];
+        let (mut nc, mut rounds) = (0u64, 0u64);
+        unsafe { ffi::check(ffi::spal_csc_colour(self.h, seed, stream, colours.as_mut_ptr(), &mut nc, &mut rounds)); }
+        (colours.into_iter().map(|c| c as usize).collect(), nc as usize, rounds as usize)
+    }
+
+    /// `B = P A P^T`, `B[i'][j'] = A[perm[i']][perm[j']]`, for any permutation `perm` (new -> old); values are moved.
+    /// The result keeps `perm` (`ordering`, `permute_vec_dev`).  Panics when `perm` is no permutation of `0..nrows`.
+    pub fn permute(&self, perm: &[usize], stream: *mut c_void) -> DeviceCsc<T> {
+        let p: Vec<u64> = perm.iter().map(|&i| i as u64).collect();
+        let mut out = std::ptr::null_mut();
+        unsafe { ffi::check(ffi::spal_csc_permute(self.h, p.as_ptr(), p.len() as u64, stream, &mut out)); }
+        DeviceCsc { h: out, _t: PhantomData }
+    }
+
+    /// colour -> order by (colour, row) -> permute on the device: both triangles of the result, and of its `ilu0`,
+    /// have at most `ordering().1` levels.
+    pub fn multicolour(&self, seed: u64, stream: *mut c_void) -> DeviceCsc<T> {
+        let mut out = std::ptr::null_mut();
+        let mut nc = 0u64;
+        unsafe { ffi::check(ffi::spal_csc_multicolour(self.h, seed, stream, &mut out, &mut nc)); }
+        DeviceCsc { h: out, _t: PhantomData }
+    }
+
+    /// `(perm, ncolours)` of a handle made by `permute` (`ncolours == 0`) or `multicolour`; panics on any other handle.
+    pub fn ordering(&self) -> (Vec<usize>, usize) {
+        let (nrows, _, _) = self.shape();
+        let mut perm = vec![0u64; nrows];
+        let mut nc = 0u64;
+        unsafe { ffi::check(ffi::spal_csc_ordering(self.h, perm.as_mut_ptr(), &mut nc)); }
+        (perm.into_iter().map(|i| i as usize).collect(), nc as usize)
+    }
+
+    /// `y[i'] = x[perm[i']]` (into this handle's order), or with `back` `y[perm[i']] = x[i']`; enqueued on `stream`.
+    ///
+    /// # Safety
+    /// `x_dev` and `y_dev` must hold `nrows` elements each and must not be the same vector.
+    pub unsafe fn permute_vec_dev(&self, x_dev: *const T, y_dev: *mut T, back: bool, stream: *mut c_void) {
+        if std::mem::size_of::<T>() == 8 {
+            ffi::check(ffi::spal_csc_permute_vec_dev_f64(self.h, x_dev as *const f64, y_dev as *mut f64, back as c_int, stream));
+        } else {
+            ffi::check(ffi::spal_csc_permute_vec_dev_f32(self.h, x_dev as *const f32, y_dev as *mut f32, back as c_int, stream));
+        }
     }
 }
 

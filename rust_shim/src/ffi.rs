@@ -114,6 +114,24 @@ extern "C" {
     pub fn spal_csc_gmres_f32(a: *mut spal_csc, m: *mut spal_csc, b: *const f32, b_len: u64, x: *mut f32, x_len: u64, restart: u64, tol: f64, maxit: u64, info: *mut spal_krylov_info) -> c_int;
     pub fn spal_csc_gmres_dev_f64(a: *mut spal_csc, m: *mut spal_csc, b_dev: *const f64, x_dev: *mut f64, restart: u64, tol: f64, maxit: u64, stream: *mut c_void, info: *mut spal_krylov_info) -> c_int;
     pub fn spal_csc_gmres_dev_f32(a: *mut spal_csc, m: *mut spal_csc, b_dev: *const f32, x_dev: *mut f32, restart: u64, tol: f64, maxit: u64, stream: *mut c_void, info: *mut spal_krylov_info) -> c_int;
+    pub fn spal_colour_greedy(n: u64, rowptr: *const u64, colind: *const u64, seed: u64, colour: *mut u64, ncolours: *mut u64) -> c_int;
+    pub fn spal_perm_from_colours(n: u64, colour: *const u64, perm: *mut u64) -> c_int;
+    pub fn spal_csr_colour(a: *mut spal_csr, seed: u64, stream: *mut c_void, colour_host: *mut u64, ncolours: *mut u64, rounds: *mut u64) -> c_int;
+    pub fn spal_csc_colour(a: *mut spal_csc, seed: u64, stream: *mut c_void, colour_host: *mut u64, ncolours: *mut u64, rounds: *mut u64) -> c_int;
+    pub fn spal_csr_permute(a: *mut spal_csr, perm_host: *const u64, n: u64, stream: *mut c_void, out: *mut *mut spal_csr) -> c_int;
+    pub fn spal_csc_permute(a: *mut spal_csc, perm_host: *const u64, n: u64, stream: *mut c_void, out: *mut *mut spal_csc) -> c_int;
+    pub fn spal_csr_multicolour(a: *mut spal_csr, seed: u64, stream: *mut c_void, out: *mut *mut spal_csr, ncolours: *mut u64) -> c_int;
+    pub fn spal_csc_multicolour(a: *mut spal_csc, seed: u64, stream: *mut c_void, out: *mut *mut spal_csc, ncolours: *mut u64) -> c_int;
+    pub fn spal_csr_ordering(a: *mut spal_csr, perm_host: *mut u64, ncolours: *mut u64) -> c_int;
+    pub fn spal_csc_ordering(a: *mut spal_csc, perm_host: *mut u64, ncolours: *mut u64) -> c_int;
+    pub fn spal_csr_permute_vec_f64(a: *mut spal_csr, x: *const f64, x_len: u64, y: *mut f64, y_len: u64, direction: c_int) -> c_int;
+    pub fn spal_csr_permute_vec_f32(a: *mut spal_csr, x: *const f32, x_len: u64, y: *mut f32, y_len: u64, direction: c_int) -> c_int;
+    pub fn spal_csr_permute_vec_dev_f64(a: *mut spal_csr, x_dev: *const f64, y_dev: *mut f64, direction: c_int, stream: *mut c_void) -> c_int;
+    pub fn spal_csr_permute_vec_dev_f32(a: *mut spal_csr, x_dev: *const f32, y_dev: *mut f32, direction: c_int, stream: *mut c_void) -> c_int;
+    pub fn spal_csc_permute_vec_f64(a: *mut spal_csc, x: *const f64, x_len: u64, y: *mut f64, y_len: u64, direction: c_int) -> c_int;
+    pub fn spal_csc_permute_vec_f32(a: *mut spal_csc, x: *const f32, x_len: u64, y: *mut f32, y_len: u64, direction: c_int) -> c_int;
+    pub fn spal_csc_permute_vec_dev_f64(a: *mut spal_csc, x_dev: *const f64, y_dev: *mut f64, direction: c_int, stream: *mut c_void) -> c_int;
+    pub fn spal_csc_permute_vec_dev_f32(a: *mut spal_csc, x_dev: *const f32, y_dev: *mut f32, direction: c_int, stream: *mut c_void) -> c_int;
     pub fn spal_csc_to_csr(a: *mut spal_csc, out: *mut *mut spal_csr) -> c_int;
     pub fn spal_csr_to_csc(a: *mut spal_csr, out: *mut *mut spal_csc) -> c_int;
     pub fn spal_csr_mul(a: *mut spal_csr, b: *mut spal_csr, stream: *mut c_void, out: *mut *mut spal_csr) -> c_int;

@@ -59,6 +59,7 @@ static void csc_free(spal_csc *a) {
     (void)dev_free(a->d_prev_hi);
     (void)dev_free(a->d_flags);
     csc_rowtiles_free(a);
+    ordering_free(a->ops);
     if (a->ev_last) (void)hipEventDestroy(a->ev_last);
     if (a->h_gave_up) (void)hipHostFree(a->h_gave_up);
     (void)dev_free(a->d_x);

@@ -313,6 +313,7 @@ void csr_free(spal_csr *a) {
     cblock_free(a);
     trsv_free(a);
     trsv_sweep_free(a);
+    ordering_free(a->ops);
     (void)dev_free(a->d_x);
     (void)dev_free(a->d_y);
     stream_release(a->stream);

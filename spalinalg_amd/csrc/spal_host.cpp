@@ -171,6 +171,23 @@ int trsv_missing_diag(const char *fn, uint64_t row) {
                 (unsigned long long)row);
 }
 
+// ---------------------------------------------------------------------------
+// Multicolour ordering: what spal_colour_greedy checks of its arrays before it reads through them.
+// ---------------------------------------------------------------------------
+static int colour_check_pattern(const char *fn, uint64_t n, const uint64_t *rowptr, const uint64_t *colind) {
+    if (rowptr[0] != 0) return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: rowptr[0] = %llu, not 0", fn, (unsigned long long)rowptr[0]);
+    for (uint64_t i = 0; i < n; ++i)
+        if (rowptr[i] > rowptr[i + 1])
+            return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: rowptr is not sorted (rowptr[%llu] > rowptr[%llu])", fn,
+                        (unsigned long long)i, (unsigned long long)(i + 1));
+    if (!colind && rowptr[n]) return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: null array", fn);
+    for (uint64_t p = 0; p < rowptr[n]; ++p)
+        if (colind[p] >= n)
+            return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: the matrix is not square (entry %llu stores column %llu, n = %llu)", fn,
+                        (unsigned long long)p, (unsigned long long)colind[p], (unsigned long long)n);
+    return SPAL_OK;
+}
+
 }  // namespace spal
 
 using namespace spal;
@@ -241,6 +258,59 @@ int spal_trsv_levels(uint64_t n, const uint64_t *rowptr, const uint64_t *colind,
     uint64_t missing = n;
     SPAL_TRY((trsv_levels_impl<uint64_t, uint64_t>(n, rowptr, colind, uplo, level_of, nlevels, &missing, nullptr)));
     if (!unit_diag && missing < n) return trsv_missing_diag("spal_trsv_levels", missing);
+    return SPAL_OK;
+}
+
+// The text of include/spal.h as it reads: vertices by descending key, the smallest colour no visited neighbour has.
+int spal_colour_greedy(uint64_t n, const uint64_t *rowptr, const uint64_t *colind, uint64_t seed, uint64_t *colour,
+                       uint64_t *ncolours) {
+    const char *fn = "spal_colour_greedy";
+    if (!rowptr || !ncolours || (!colour && n)) return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: null array", fn);
+    SPAL_TRY(colour_check_pattern(fn, n, rowptr, colind));
+    const uint64_t nnz = rowptr[n];
+    // the rows of A^T: a counting sort of the entries by column
+    std::vector<uint64_t> tptr(n + 1, 0), tind(nnz);
+    for (uint64_t p = 0; p < nnz; ++p) ++tptr[colind[p] + 1];
+    for (uint64_t j = 0; j < n; ++j) tptr[j + 1] += tptr[j];
+    {
+        std::vector<uint64_t> next(tptr.begin(), tptr.end() - 1);
+        for (uint64_t i = 0; i < n; ++i)
+            for (uint64_t p = rowptr[i]; p < rowptr[i + 1]; ++p) tind[next[colind[p]]++] = i;
+    }
+    std::vector<std::pair<uint32_t, uint64_t>> order(n);   // (key, vertex); keys are distinct
+    for (uint64_t i = 0; i < n; ++i) order[i] = {colour_mix32((uint32_t)(i + seed)), i};
+    std::sort(order.begin(), order.end(), [](const auto &a, const auto &b) { return a.first > b.first; });
+    const uint64_t none = ~0ull;
+    std::fill(colour, colour + n, none);
+    std::vector<uint64_t> taken(n, none);   // taken[c] == v: a visited neighbour of v has colour c
+    uint64_t top = 0;
+    for (const auto &kv : order) {
+        const uint64_t v = kv.second;
+        for (uint64_t p = rowptr[v]; p < rowptr[v + 1]; ++p)
+            if (colind[p] != v && colour[colind[p]] != none) taken[colour[colind[p]]] = v;
+        for (uint64_t p = tptr[v]; p < tptr[v + 1]; ++p)
+            if (tind[p] != v && colour[tind[p]] != none) taken[colour[tind[p]]] = v;
+        uint64_t c = 0;
+        while (taken[c] == v) ++c;   // at most deg(v) colours are taken and deg(v) < n: c < n
+        colour[v] = c;
+        top = std::max(top, c + 1);
+    }
+    *ncolours = top;
+    return SPAL_OK;
+}
+
+int spal_perm_from_colours(uint64_t n, const uint64_t *colour, uint64_t *perm) {
+    const char *fn = "spal_perm_from_colours";
+    if ((!colour || !perm) && n) return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: null array", fn);
+    std::vector<uint64_t> start(n + 1, 0);
+    for (uint64_t i = 0; i < n; ++i) {
+        if (colour[i] >= n)
+            return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: colour[%llu] = %llu is not below n = %llu", fn, (unsigned long long)i,
+                        (unsigned long long)colour[i], (unsigned long long)n);
+        ++start[colour[i] + 1];
+    }
+    for (uint64_t c = 0; c < n; ++c) start[c + 1] += start[c];
+    for (uint64_t i = 0; i < n; ++i) perm[start[colour[i]]++] = i;   // rows ascending inside a colour: stable
     return SPAL_OK;
 }
 

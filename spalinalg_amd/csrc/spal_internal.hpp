@@ -274,7 +274,23 @@ struct OpState {
     int64_t krylov_check_every = 0; // option "krylov_check_every": iterations between two polls, 0 = default (spal_krylov.hip)
     std::string krylov_info;       // "krylov": the last spal_*_krylov_* call with this handle as A (guarded by the solve handle's mu)
     std::string gmres_info;        // "gmres": the last spal_*_gmres_* call with this handle as A (the same lock; spal_gmres.hip)
+    // a result of spal_*_permute / _multicolour (spal_colour.hip): written once, before the handle is
+    // returned, and only read afterwards
+    uint32_t *d_perm = nullptr;    // nrows: new -> old; freed by ordering_free (csr_free, csc_free)
+    uint64_t ordering_colours = 0; // 0: the permutation was the caller's
+    std::string ordering_info;     // "ordering"
 };
+void ordering_free(OpState &s);    // spal_colour.hip
+
+// The priority of a row in the multicolour ordering (include/spal.h): a bijection of the 32-bit words.
+__host__ __device__ inline uint32_t colour_mix32(uint32_t x) {
+    x ^= x >> 16;
+    x *= 0x7feb352du;
+    x ^= x >> 15;
+    x *= 0x846ca68bu;
+    x ^= x >> 16;
+    return x;
+}
 }  // namespace spal
 
 // The opaque handle types of spal.h.

@@ -1,5 +1,5 @@
 // spal_ops.hpp -- the host layer the sparse operations share: spal_spgemm.hip, spal_spadd.hip,
-// spal_spmm.hip, spal_trsv.hip, spal_trsv_sweep.hip, spal_ilu.hip, spal_krylov.hip and spal_gmres.hip keep their kernels, their driver, their option's validation and their
+// spal_spmm.hip, spal_trsv.hip, spal_trsv_sweep.hip, spal_ilu.hip, spal_krylov.hip, spal_gmres.hip and spal_colour.hip keep their kernels, their driver, their option's validation and their
 // info JSON; what surrounds a launch the same way in each of them is here, once.  (Not installed.)
 #pragma once
 
@@ -210,7 +210,8 @@ inline int ops_describe_append(char *buf, size_t buf_len, const OpState &s, spal
     SPAL_TRY(trsv_sweep_describe_append(buf, buf_len, solve));          // it was prepared for sweeps on a triangle
     SPAL_TRY(describe_append(buf, buf_len, "ilu0", s.ilu_info));        // a factor of spal_*_ilu0: how it was built
     SPAL_TRY(krylov_describe_append(buf, buf_len, s, solve));           // spal_*_krylov_* ran with it as A: the last call
-    return gmres_describe_append(buf, buf_len, s, solve);               // spal_*_gmres_* ran with it as A: the last call
+    SPAL_TRY(gmres_describe_append(buf, buf_len, s, solve));            // spal_*_gmres_* ran with it as A: the last call
+    return describe_append(buf, buf_len, "ordering", s.ordering_info);  // a result of spal_*_permute / _multicolour
 }
 
 }  // namespace spal

@@ -340,6 +340,53 @@ class _DeviceMatrix:
                                                         C.byref(info)))
         return _krylov_info(info)
 
+    def colour(self, seed: int = 0, stream=None):
+        """The greedy colouring of this square matrix's graph by hashed priority (spal_*_colour): exactly
+        the sequential text of include/spal.h, by Jones-Plassmann rounds on the device.  Returns (colours as a uint64
+        array, ncolours, rounds); synchronises `stream`."""
+        n = self.shape()[0]
+        colours = np.empty(n, dtype=np.uint64)
+        nc, rounds = u64(), u64()
+        check(self._fn("colour")(self._h, u64(seed), _stream_ptr(stream), _p(colours), C.byref(nc), C.byref(rounds)))
+        return colours, nc.value, rounds.value
+
+    def permute(self, perm, stream=None):
+        """B = P A P^T as a new handle of this class, B[i'][j'] = A[perm[i']][perm[j']] for any permutation `perm`
+        (new -> old); values are moved, never recomputed.  The result keeps `perm` (ordering(), permute_vec())."""
+        perm = _idx(perm)
+        out = vp()
+        check(self._fn("permute")(self._h, _p(perm), u64(perm.size), _stream_ptr(stream), C.byref(out)))
+        return type(self)(out, self.dtype, self.device)
+
+    def multicolour(self, seed: int = 0, stream=None):
+        """colour -> order by (colour, row) -> permute, on the device (spal_*_multicolour): a new handle of this class
+        whose two triangles have at most ncolours levels each; ordering() returns its perm and ncolours."""
+        out, nc = vp(), u64()
+        check(self._fn("multicolour")(self._h, u64(seed), _stream_ptr(stream), C.byref(out), C.byref(nc)))
+        return type(self)(out, self.dtype, self.device)
+
+    def ordering(self):
+        """(perm, ncolours) of a handle made by permute() (ncolours = 0) or multicolour(); any other handle is refused."""
+        perm = np.empty(self.shape()[0], dtype=np.uint64)
+        nc = u64()
+        check(self._fn("ordering")(self._h, _p(perm), C.byref(nc)))
+        return perm, nc.value
+
+    def permute_vec(self, x, back: bool = False) -> np.ndarray:
+        """Host vectors: x[perm] (into this handle's order), or with `back` the inverse, y[perm] = x."""
+        x = np.ascontiguousarray(x)
+        if x.dtype not in (np.float32, np.float64):
+            x = x.astype(self.dtype)
+        y = np.empty_like(x)
+        check(self._fn(f"permute_vec_{_sfx(x.dtype)}")(self._h, _p(x), u64(x.size), _p(y), u64(y.size),
+                                                       C.c_int(1 if back else 0)))
+        return y
+
+    def permute_vec_dev(self, x_ptr: int, y_ptr: int, back: bool = False, stream=None) -> None:
+        """Device pointers, x_ptr != y_ptr; enqueued on `stream`, not synchronised."""
+        check(self._fn(f"permute_vec_dev_{_sfx(self.dtype)}")(self._h, vp(x_ptr), vp(y_ptr), C.c_int(1 if back else 0),
+                                                           _stream_ptr(stream)))
+
     def alloc_vectors(self, stream=None):
         """Device pointers (x, y) of vectors owned by this handle and placed so that the stores of y do not collide
         with the matrix stream (spal_csr_alloc_vectors: a walk over the device's memory, setup time).  CSR handles."""
@@ -910,6 +957,58 @@ class _Compressed:
             z = f.solve_triangular(y, lower=False)                         # U z = y
         """
         return self._adopt_result(self.device(device).ilu0(), device)
+
+    def _square(self, what: str) -> None:
+        if self._nrows != self._ncols:
+            raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT, f"{what}: the matrix is not square ({self._nrows} x {self._ncols})")
+
+    def colour(self, seed: int = 0, device: int = 0):
+        """(colours, ncolours): the greedy colouring of the graph of A + A^T by hashed priority, as written out in
+        include/spal.h, computed on the device (spal_*_colour)."""
+        self._square("colour")
+        colours, ncolours, _ = self.device(device).colour(seed)
+        return colours, ncolours
+
+    def _adopt_ordered(self, dev, device: int):
+        out = self._adopt_result(dev, device)
+        out.perm, out.ncolours = dev.ordering()
+        return out
+
+    def permute(self, perm, device: int = 0):
+        """P A P^T for any permutation `perm` (new -> old): a matrix of the same class, its values A's bits.  The result
+        keeps its device handle and has `perm`, `ncolours` = 0, to_order() and from_order()."""
+        self._square("permute")
+        return self._adopt_ordered(self.device(device).permute(perm), device)
+
+    def multicolour(self, seed: int = 0, device: int = 0):
+        """The matrix in multicolour order: rows numbered colour by colour, so that both triangles -- and those of its
+        ILU(0) factor -- have at most `ncolours` levels and an exact triangular solve is a few wide launches.  A matrix
+        of the same class that keeps its device handle, with `perm` (new -> old), `ncolours`, to_order(), from_order()::
+
+            p = a.multicolour(); f = p.ilu0()
+            xp, info = p.solve(p.to_order(b), method="bicgstab", M=f); x = p.from_order(xp)
+
+        ILU(0) in this order is usually a weaker preconditioner than in the natural one (more iterations), and the
+        permuted matrix has lost its band."""
+        self._square("multicolour")
+        return self._adopt_ordered(self.device(device).multicolour(seed), device)
+
+    def _perm(self) -> np.ndarray:
+        perm = getattr(self, "perm", None)
+        if perm is None:
+            raise TypeError("this matrix has no ordering: it is no result of permute() or multicolour()")
+        return perm.astype(np.int64)
+
+    def to_order(self, v) -> np.ndarray:
+        """v[perm]: a vector of the original numbering in this matrix's order."""
+        return np.asarray(v)[self._perm()]
+
+    def from_order(self, vp_) -> np.ndarray:
+        """The inverse of to_order()."""
+        vp_ = np.asarray(vp_)
+        out = np.empty_like(vp_)
+        out[self._perm()] = vp_
+        return out
 
 
 class CsrMatrix(_Compressed):
