@@ -447,6 +447,54 @@ int spal_csc_trsv_sweep_dev_f32(spal_csc_t a, int uplo, int unit_diag, uint64_t 
 int spal_csr_ilu0(spal_csr_t a, void *stream, spal_csr_t *out);
 int spal_csc_ilu0(spal_csc_t a, void *stream, spal_csc_t *out);
 
+/* ---- ILU(0) by row sweeps: the factor in s SpMV-shaped passes, no analysis ------------------
+ * Not in the reference.  The fine-grained ILU idea (Chow and Patel) in the form that is the factorisation's twin of
+ * spal_*_trsv_sweep_*: again a sequential text that the device reproduces bit for bit in f32 and f64 (NaN by position).
+ * A is as for ILU(0): square, columns ascending inside a row, every row stores (i, i).  T is the handle's element type.
+ *   F0 = A's values
+ *   for t = 1 .. s, every row i independently of the others:
+ *       row i of Ft starts as a copy of row i of A
+ *       for each stored (i, k) with k < i, in ascending k, at position p:
+ *           w = Ft[p] / F(t-1)[diag(k)]                    -- IEEE division
+ *           Ft[p] = w
+ *           for each stored (k, j) with j > k, in ascending j, value u = F(t-1)[(k, j)]:
+ *               if (i, j) is stored, at position q:  Ft[q] = Ft[q] - (w * u)   -- product rounded, then the difference: no FMA
+ *   result: Fs   (s = 0: A's values on A's structure)
+ * This is the body of ILU(0)'s loop for row i with every read of ANOTHER row taken from the previous pass; the row's own
+ * running values are this pass's.  Three consequences:
+ *   EQUALITY WITH ILU(0).  A row of level l of the lower triangle (as spal_trsv_levels defines it) holds its final bits
+ *   from F_l on, NaN positions included: level-0 rows have no entry below the diagonal, so they are A's rows in every
+ *   pass; by induction the rows k that a level-l row reads are final in F(l-1), so pass l performs the sequential loop's
+ *   operations on the same inputs, and so does every later pass.  Hence for s >= nlevels - 1 the result is bit for bit
+ *   that of spal_*_ilu0.
+ *   CLAMPING.  nlevels <= n, so an s greater than n - 1 is clamped to n - 1 without changing a bit: a call enqueues at
+ *   most n - 1 passes whatever `sweeps` is.
+ *   APPROXIMATION.  A smaller s gives up exactness of the factor, not of the arithmetic: the result is still this text's,
+ *   bit for bit, and it is a preconditioner in its own right (DESIGN 3.19 has the measured iteration counts).
+ * The result has the shape of spal_*_ilu0's: a new, independent handle of a's structure and element type, L strictly
+ * below the diagonal (unit diagonal implied) and U on and above it, with a lazy product plan.  The errors and their
+ * messages are spal_*_ilu0's; *out is not written and nothing leaks.  `a` is only read; the call synchronises `stream`
+ * once, at its end.
+ * NO HOST ANALYSIS, NO SOLVE PLAN.  The diagonals' positions come from the preparation spal_*_trsv_sweep_* builds per
+ * handle (one kernel, on first use, under the handle's lock; it names the first row without a diagonal): a's describe()
+ * shows "analyses" unchanged and no "trsv" object it did not have.  The factor receives no solve plan: it is meant to be
+ * applied by sweeps ("trsv_sweeps", spal_*_trsv_sweep_*); an exact solve on it analyses as usual.
+ * One pass is one launch (one more, before the first, classifies the rows); order between passes is stream order alone:
+ * no atomics on values, no flags, nothing waits on another workgroup.  The passes ping-pong between the result's values
+ * and one scratch array from the runtime's stream-ordered allocator, the parity chosen so that the last pass lands in
+ * the result: s = 0 is a copy, s = 1 needs no scratch, pass 1 reads A's array as F0.  Concurrent calls on one handle
+ * share nothing but the preparation.
+ * A workgroup owns block_rows consecutive rows and stages their entries in LDS when they number at most stage_entries
+ * (else those rows run in place in the pass's output); a row is factorised by one thread or, from "ilu_wide_work"
+ * updates to look for (the option of spal_*_ilu0, read from a), by one wave, staged in LDS up to wide_stage_entries
+ * entries and in place beyond.  The bits depend on none of this.  CSC handles factorise their CSR twin and return the
+ * factor as CSC.
+ * describe() on the result gains "ilu0_sweep": {sweeps = passes run (after clamping), requested, launches = passes,
+ * block_rows, stage_entries, wide_stage_entries, rows_row_form, rows_wide_form, wide_work, kernel_ms = device time,
+ * call_ms}; it has no "ilu0" object. */
+int spal_csr_ilu0_sweep(spal_csr_t a, uint64_t sweeps, void *stream, spal_csr_t *out);
+int spal_csc_ilu0_sweep(spal_csc_t a, uint64_t sweeps, void *stream, spal_csc_t *out);
+
 /* ---- A x = b on the device: CG and BiCGStab, optionally preconditioned by an ILU(0) factor ------------
  * Not in the reference.  As for the solve and the factorisation, the contract is a sequential text that the device
  * reproduces bit for bit in f32 and f64; a Krylov loop can only keep that promise if its reductions have ONE order, so

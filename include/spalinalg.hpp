@@ -299,6 +299,17 @@ class CsrMatrix {
         detail::check(spal_csr_ilu0(device_handle(), nullptr, &h));
         return adopt(h);
     }
+    // ILU(0) by `sweeps` row sweeps (spal_csr_ilu0_sweep, include/spal.h): every pass factorises every row on its own
+    // against the previous pass's factor -- no analysis, one SpMV-shaped launch per pass, bit for bit the sequential
+    // text, and ilu0()'s bits from sweeps = levels - 1 on.  Meant to be applied by sweeps too (option "trsv_sweeps").
+    CsrMatrix ilu0(uint64_t sweeps) const {
+        if (nrows_ != ncols_)   // before any device call
+            throw Panic(SPAL_ERR_INVALID_ARGUMENT, "ilu0: the matrix is not square (" + std::to_string(nrows_) + " x " +
+                                                       std::to_string(ncols_) + ")");
+        spal_csr_t h = nullptr;
+        detail::check(spal_csr_ilu0_sweep(device_handle(), sweeps, nullptr, &h));
+        return adopt(h);
+    }
 
     // The multicolour ordering (include/spal.h).  colour(): the greedy colouring of the graph of A + A^T by
     // hashed priority, exactly the sequential text, by rounds on the device.  permute(perm): B = P A P^T with
@@ -530,6 +541,15 @@ class CscMatrix {
     CscMatrix ilu0() const {
         spal_csc_t h = nullptr;
         detail::check(spal_csc_ilu0(device_handle(), nullptr, &h));
+        return adopt(h);
+    }
+    // ILU(0) by `sweeps` row sweeps (spal_csc_ilu0_sweep): as CsrMatrix::ilu0(sweeps), returned by columns.
+    CscMatrix ilu0(uint64_t sweeps) const {
+        if (nrows_ != ncols_)   // before any device call
+            throw Panic(SPAL_ERR_INVALID_ARGUMENT, "ilu0: the matrix is not square (" + std::to_string(nrows_) + " x " +
+                                                       std::to_string(ncols_) + ")");
+        spal_csc_t h = nullptr;
+        detail::check(spal_csc_ilu0_sweep(device_handle(), sweeps, nullptr, &h));
         return adopt(h);
     }
 

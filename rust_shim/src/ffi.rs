@@ -94,6 +94,8 @@ extern "C" {
     pub fn spal_csc_trsv_sweep_dev_f32(a: *mut spal_csc, uplo: c_int, unit_diag: c_int, sweeps: u64, b_dev: *const f32, x_dev: *mut f32, stream: *mut c_void) -> c_int;
     pub fn spal_csr_ilu0(a: *mut spal_csr, stream: *mut c_void, out: *mut *mut spal_csr) -> c_int;
     pub fn spal_csc_ilu0(a: *mut spal_csc, stream: *mut c_void, out: *mut *mut spal_csc) -> c_int;
+    pub fn spal_csr_ilu0_sweep(a: *mut spal_csr, sweeps: u64, stream: *mut c_void, out: *mut *mut spal_csr) -> c_int;
+    pub fn spal_csc_ilu0_sweep(a: *mut spal_csc, sweeps: u64, stream: *mut c_void, out: *mut *mut spal_csc) -> c_int;
     pub fn spal_dot_f64(a: *const f64, b: *const f64, n: u64, out: *mut f64) -> c_int;
     pub fn spal_dot_f32(a: *const f32, b: *const f32, n: u64, out: *mut f32) -> c_int;
     pub fn spal_dot_dev_f64(device: c_int, a_dev: *const f64, b_dev: *const f64, n: u64, out_dev: *mut f64, stream: *mut c_void) -> c_int;

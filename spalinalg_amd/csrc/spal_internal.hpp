@@ -271,6 +271,7 @@ struct OpState {
     std::string spgemm_info;       // "spgemm": a product of spal_*_mul
     std::string spadd_info;        // "spadd": a result of spal_*_add / _sub / _neg
     std::string ilu_info;          // "ilu0": a factor of spal_*_ilu0
+    std::string ilu_sweep_info;    // "ilu0_sweep": a factor of spal_*_ilu0_sweep (spal_ilu_sweep.hip)
     int64_t krylov_check_every = 0; // option "krylov_check_every": iterations between two polls, 0 = default (spal_krylov.hip)
     std::string krylov_info;       // "krylov": the last spal_*_krylov_* call with this handle as A (guarded by the solve handle's mu)
     std::string gmres_info;        // "gmres": the last spal_*_gmres_* call with this handle as A (the same lock; spal_gmres.hip)

@@ -1,5 +1,5 @@
 // spal_ops.hpp -- the host layer the sparse operations share: spal_spgemm.hip, spal_spadd.hip,
-// spal_spmm.hip, spal_trsv.hip, spal_trsv_sweep.hip, spal_ilu.hip, spal_krylov.hip, spal_gmres.hip and spal_colour.hip keep their kernels, their driver, their option's validation and their
+// spal_spmm.hip, spal_trsv.hip, spal_trsv_sweep.hip, spal_ilu.hip, spal_ilu_sweep.hip, spal_krylov.hip, spal_gmres.hip and spal_colour.hip keep their kernels, their driver, their option's validation and their
 // info JSON; what surrounds a launch the same way in each of them is here, once.  (Not installed.)
 #pragma once
 
@@ -167,7 +167,8 @@ int transpose_device(int device, int elem_size, uint64_t nmajor, uint64_t nminor
 
 // ---- Jacobi sweeps on a triangle, for callers that bring their own scratch (spal_trsv_sweep.hip) --------
 // Both take a->mu themselves.  prepare: builds the handle's sweep rows if it has none (synchronises `st`); refuses what
-// the exact solve refuses, a row without a diagonal unless unit_diag.  enqueue: x = sweep(a, uplo, unit_diag, sweeps, b)
+// the exact solve refuses, a row without a diagonal unless unit_diag.  Afterwards a->d_sweep_rows is there until the
+// handle is freed and never changes: spal_ilu_sweep.hip reads the diagonals' positions from it without the lock.  enqueue: x = sweep(a, uplo, unit_diag, sweeps, b)
 // on `st`, allocating and synchronising nothing on a prepared handle; b, x, w0, w1 are device vectors of a's element
 // type, w0 is written when sweeps >= 1 and w1 when sweeps >= 2, x may be b.
 int trsv_sweep_prepare(const char *fn, spal_csr *a, int unit_diag, hipStream_t st);
@@ -209,6 +210,7 @@ inline int ops_describe_append(char *buf, size_t buf_len, const OpState &s, spal
     SPAL_TRY(trsv_describe_append(buf, buf_len, solve));                // a triangle of it was analysed for a solve
     SPAL_TRY(trsv_sweep_describe_append(buf, buf_len, solve));          // it was prepared for sweeps on a triangle
     SPAL_TRY(describe_append(buf, buf_len, "ilu0", s.ilu_info));        // a factor of spal_*_ilu0: how it was built
+    SPAL_TRY(describe_append(buf, buf_len, "ilu0_sweep", s.ilu_sweep_info));   // ... of spal_*_ilu0_sweep
     SPAL_TRY(krylov_describe_append(buf, buf_len, s, solve));           // spal_*_krylov_* ran with it as A: the last call
     SPAL_TRY(gmres_describe_append(buf, buf_len, s, solve));            // spal_*_gmres_* ran with it as A: the last call
     return describe_append(buf, buf_len, "ordering", s.ordering_info);  // a result of spal_*_permute / _multicolour

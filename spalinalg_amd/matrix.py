@@ -456,6 +456,15 @@ class _DeviceMatrix:
         return out
 
 
+def _sweep_count(sweeps) -> int:
+    """ilu0(sweeps=...): an integer >= 0 (bool is not one), at most what the ABI's uint64_t holds."""
+    if isinstance(sweeps, bool) or not isinstance(sweeps, (int, np.integer)):
+        raise TypeError(f"sweeps must be None or an integer >= 0, not {type(sweeps).__name__}")
+    if sweeps < 0:
+        raise ValueError(f"sweeps must be >= 0, not {sweeps}")
+    return min(int(sweeps), 2 ** 64 - 1)
+
+
 class DeviceCsr(_DeviceMatrix):
     _kind = "csr"
 
@@ -502,7 +511,7 @@ class DeviceCsr(_DeviceMatrix):
         check(_ffi.lib().spal_csr_neg(self._h, _stream_ptr(stream), C.byref(out)))
         return DeviceCsr(out, self.dtype, self.device)
 
-    def ilu0(self, stream=None) -> "DeviceCsr":
+    def ilu0(self, stream=None, sweeps=None) -> "DeviceCsr":
         """The ILU(0) factor of this square matrix as a new handle of the same structure (spal_csr_ilu0):
         L strictly below the diagonal, its unit diagonal implied, U on and above it; bit for bit the sequential loop.
         Synchronises `stream`.  Applying the preconditioner is two solves on the result::
@@ -511,9 +520,17 @@ class DeviceCsr(_DeviceMatrix):
             z = f.trsv(f.trsv(r, lower=True, unit_diagonal=True), lower=False)      # z = U^-1 L^-1 r
 
         The result already has its lower solve plan (a copy of self's); options "ilu_wide_work" and
-        "trsv_chain_rows" are read from self."""
+        "trsv_chain_rows" are read from self.
+
+        `sweeps` = None is that exact call; an integer s >= 0 builds the factor by s row sweeps instead
+        (spal_csr_ilu0_sweep): every pass factorises every row on its own against the previous pass's
+        factor -- no analysis, no solve plan, one SpMV-shaped launch per pass, bit for bit its sequential text and the
+        exact factor's bits from s = levels - 1 on.  Apply it by sweeps as well (trsv_sweep, `precond_sweeps`)."""
         out = vp()
-        check(_ffi.lib().spal_csr_ilu0(self._h, _stream_ptr(stream), C.byref(out)))
+        if sweeps is None:
+            check(_ffi.lib().spal_csr_ilu0(self._h, _stream_ptr(stream), C.byref(out)))
+        else:
+            check(_ffi.lib().spal_csr_ilu0_sweep(self._h, u64(_sweep_count(sweeps)), _stream_ptr(stream), C.byref(out)))
         return DeviceCsr(out, self.dtype, self.device)
 
 
@@ -564,11 +581,14 @@ class DeviceCsc(_DeviceMatrix):
         check(_ffi.lib().spal_csc_neg(self._h, _stream_ptr(stream), C.byref(out)))
         return DeviceCsc(out, self.dtype, self.device)
 
-    def ilu0(self, stream=None) -> "DeviceCsc":
-        """The ILU(0) factor as a new CSC handle (spal_csc_ilu0: the CSR twin is factorised, the factor returned by
-        columns); see DeviceCsr.ilu0 for the contract and the two-solve application."""
+    def ilu0(self, stream=None, sweeps=None) -> "DeviceCsc":
+        """The ILU(0) factor as a new CSC handle (spal_csc_ilu0, or spal_csc_ilu0_sweep when `sweeps` is given: the CSR
+        twin is factorised, the factor returned by columns); see DeviceCsr.ilu0 for the contract and the application."""
         out = vp()
-        check(_ffi.lib().spal_csc_ilu0(self._h, _stream_ptr(stream), C.byref(out)))
+        if sweeps is None:
+            check(_ffi.lib().spal_csc_ilu0(self._h, _stream_ptr(stream), C.byref(out)))
+        else:
+            check(_ffi.lib().spal_csc_ilu0_sweep(self._h, u64(_sweep_count(sweeps)), _stream_ptr(stream), C.byref(out)))
         return DeviceCsc(out, self.dtype, self.device)
 
 
@@ -946,7 +966,7 @@ class _Compressed:
         """`-&self` (src/csr/ops/neg.rs:5-17 / src/csc/ops/neg.rs:5-17) on the device."""
         return self._adopt_result(self.device().neg(), 0)
 
-    def ilu0(self, device: int = 0):
+    def ilu0(self, device: int = 0, sweeps=None):
         """The ILU(0) factor of this square matrix, a matrix of the same class and structure (spal_*_ilu0, DESIGN
         3.12): L strictly below the diagonal with its unit diagonal implied, U on and above it, bit for bit the
         sequential loop without fill.  Every row must store its diagonal.  The result is downloaded and keeps its
@@ -955,8 +975,18 @@ class _Compressed:
             f = a.ilu0()
             y = f.solve_triangular(r, lower=True, unit_diagonal=True)      # L y = r
             z = f.solve_triangular(y, lower=False)                         # U z = y
+
+        `sweeps` = None is that exact factorisation, which analyses the matrix and walks its levels; an integer
+        s >= 0 builds the factor by s row sweeps instead (spal_*_ilu0_sweep): no analysis, one
+        SpMV-shaped launch per pass, the exact factor's bits from s = levels - 1 on and a preconditioner well before.
+        Such a factor has no solve plan and is meant to be applied by sweeps, SpMV-shaped from start to finish::
+
+            f = a.ilu0(sweeps=3)
+            x, info = a.solve(b, M=f, precond_sweeps=3)
         """
-        return self._adopt_result(self.device(device).ilu0(), device)
+        if sweeps is not None:
+            sweeps = _sweep_count(sweeps)              # refused before anything is uploaded
+        return self._adopt_result(self.device(device).ilu0(sweeps=sweeps), device)
 
     def _square(self, what: str) -> None:
         if self._nrows != self._ncols:
