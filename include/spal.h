@@ -683,6 +683,8 @@ int spal_csc_gmres_dev_f32(spal_csc_t a, spal_csc_t m, const float *b_dev, float
  *                  x ^= x >> 16;  x *= 0x7feb352d;  x ^= x >> 15;  x *= 0x846ca68b;  x ^= x >> 16
  *              a bijection of the 32-bit words: keys are distinct for n < 2^32, no tie-break is needed.
  *              mix32(0) = 0, mix32(1) = 1753845952, mix32(2) = 3507691905, mix32(3) = 1408362973.
+ *              `seed` is a uint64_t of which only seed mod 2^32 enters the keys: seed 2^32 + 7 colours as seed 7 does
+ *              (host and device alike); describe()["ordering"]["seed"] reports the value as it was given.
  *   Colouring. Visit the vertices by DESCENDING key; a vertex takes the smallest colour >= 0 that no neighbour
  *              visited before it has.  ncolours = the largest colour + 1 (0 for n = 0).
  *   Ordering.  perm maps new -> old and lists the rows by (colour, old row) ascending: a stable counting sort.

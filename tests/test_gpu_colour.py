@@ -7,6 +7,7 @@ thousands of neighbours, a chain of 3000 rounds (every batch size between two po
 than one workgroup, and 4096 * 1024 + 1 rows."""
 import ctypes as C
 import functools
+import threading
 
 import numpy as np
 import pytest
@@ -16,6 +17,7 @@ from spalinalg_amd import _ffi
 from tests import colour_ref as cr
 from tests import ilu_ref as ir
 from tests import krylov_ref as kr
+from tests import ordering_cases as oc
 from tests import trsv_ref as tr
 
 pytestmark = pytest.mark.gpu
@@ -96,6 +98,24 @@ def test_chain_of_3000_rounds(kind):
     ref7, nc7, rounds7 = cr.greedy(pattern, 7)
     colours, nc, rounds = a.device().colour(7)
     assert (nc, rounds) == (nc7, rounds7) and rounds7 < 100 and np.array_equal(colours, ref7)
+
+
+@pytest.mark.parametrize("kind", KINDS)
+@pytest.mark.parametrize("rounds", oc.CHAIN_ROUNDS)
+def test_chain_at_batch_boundaries(rounds, kind):
+    """The host enqueues batches of 8, 16, 32, 64, ... rounds between two polls.  A chain of exactly 8, 24, 56 or 120
+    rounds ends with a batch: the last poll reads the count a round past the end would start with.  One round more,
+    and a whole batch runs for one row."""
+    pattern = oc.chain(rounds)
+    ref, ref_nc, ref_rounds = cr.greedy(pattern, 0)
+    assert (ref_nc, ref_rounds) == (2, rounds)
+    a = make(kind, pattern, np.ones(pattern[2].size, dtype=np.float32))
+    colours, nc, got = a.device().colour(0)
+    assert (nc, got) == (2, rounds)
+    assert np.array_equal(colours, ref)
+    m = a.multicolour(0)                                  # ... and the whole call on the same boundary
+    assert m.ncolours == 2 and np.array_equal(m.perm, cr.perm_from_colours(ref))
+    assert m.device().describe()["ordering"]["rounds"] == rounds
 
 
 def test_one_row_past_one_grid_trip():
@@ -197,6 +217,42 @@ def test_multicolour_is_colour_then_order_then_permute(name, kind):
         n, rp, ci = want_pattern
         assert plans["lower"]["levels"] == tr.levels(n, rp, ci, lower=True)[1]
     assert "ordering" not in a.device().describe()        # the operand is left as it was
+
+
+@pytest.mark.parametrize("kind", KINDS)
+def test_two_threads_multicolour_one_fresh_handle(kind):
+    """Two callers, one handle nothing has been called on yet: both results are the text.  A hang fails the test at the
+    joins."""
+    pattern = cr.patterns_cached()["sym_banded"]
+    values, _ = tr.fill(pattern, np.float64, np.random.default_rng(41))
+    ref, ref_nc, ref_rounds = cr.reference("sym_banded", 7)
+    perm = cr.perm_from_colours(ref)
+    want_pattern, want_values = cr.permute(pattern, values, perm)
+    dev = make(kind, pattern, values).device()
+    results, errors = [None, None], []
+    gate = threading.Barrier(2)
+
+    def work(i):
+        try:
+            gate.wait(timeout=30)
+            out = dev.multicolour(7)
+            results[i] = (out.download(), out.ordering(), out.describe()["ordering"])
+        except Exception as e:          # reported below, from the main thread
+            errors.append(e)
+
+    threads = [threading.Thread(target=work, args=(i,), daemon=True) for i in range(2)]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join(timeout=60)
+    assert not any(t.is_alive() for t in threads), "a thread did not return from multicolour"
+    assert not errors, errors
+    eptr, eind, eval_ = expected_arrays(kind, want_pattern, want_values)
+    for (ptr, ind, val), (got_perm, got_nc), info in results:
+        assert np.array_equal(ptr, eptr) and np.array_equal(ind, eind) and np.array_equal(bits(val), bits(eval_))
+        assert got_nc == ref_nc and np.array_equal(got_perm, perm)
+        assert (info["colours"], info["rounds"], info["seed"]) == (ref_nc, ref_rounds, 7)
+    assert "ordering" not in dev.describe()
 
 
 # ---- 4. vectors ------------------------------------------------------------------------------------------------------
@@ -322,3 +378,28 @@ def test_refusals(kind):
     rounds = u64()
     assert getattr(lib, f"spal_{kind}_colour")(dev._h, u64(0), None, None, C.byref(nc), C.byref(rounds)) == _ffi.SPAL_OK
     assert (nc.value, rounds.value) == (3, cr.HAND_ROUNDS)
+
+
+def test_row_block_handle_is_refused(monkeypatch):
+    """A CSR handle held as row blocks (more entries than one set of 32-bit offsets addresses; the limit lowered for the
+    test) has no ordering calls: refused by name (SPAL_ERR_UNSUPPORTED) before anything is launched."""
+    monkeypatch.setenv("SPAL_CSR_PART_ENTRIES", "4000")
+    pattern = cr.patterns_cached()["sym_bidiagonal"]
+    n = pattern[0]
+    a = sp.CsrMatrix(n, n, pattern[1], pattern[2], np.ones(pattern[2].size))
+    dev = a.device()
+    d = dev.describe()
+    assert d["kernel"] == "row_blocks" and d["parts"] >= 3, d
+    refused = r"spal_csr_{}: an operand of more than 2\^32 - 65537 entries \(row blocks\)"
+    with pytest.raises(sp.SpalError, match=refused.format("colour")):
+        dev.colour(0)
+    with pytest.raises(sp.SpalError, match=refused.format("permute")):
+        dev.permute(np.arange(n, dtype=np.uint64))
+    with pytest.raises(sp.SpalError, match=refused.format("multicolour")):
+        dev.multicolour(0)
+    with pytest.raises(sp.SpalError, match=refused.format("colour")):
+        a.colour()
+    with pytest.raises(sp.SpalError, match=refused.format("multicolour")):
+        a.multicolour()
+    x = np.arange(n, dtype=np.float64)
+    assert np.array_equal(dev.spmv(x), np.convolve(x, [1, 1, 1], mode="same"))      # the handle is as it was
