@@ -417,6 +417,72 @@ int spal_csc_trsv_sweep_dev_f64(spal_csc_t a, int uplo, int unit_diag, uint64_t 
 int spal_csc_trsv_sweep_dev_f32(spal_csc_t a, int uplo, int unit_diag, uint64_t sweeps, const float *b_dev,
                                 float *x_dev, void *stream);
 
+/* ---- triangular solves for a block of k right-hand sides, exact and by sweeps, CSR and CSC -------------
+ * Not in the reference.  B and X are n x k, dense and ROW-MAJOR: element (i, j) at [i * ld + j], ld >= k -- the layout
+ * of spal_*_spmm_*; offsets i * ld are 64-bit.  One call solves all k columns on the launches of ONE single-vector call.
+ *   EXACT (spal_*_trsm_*).  Column j of X is, bit for bit in f32 and f64 with NaN by position, what spal_*_trsv_*
+ *   returns for column j of B: the sequential text above, applied per column.
+ *   SWEEPS (spal_*_trsm_sweep_*).  Column j of X is, bit for bit, what spal_*_trsv_sweep_* returns for column j of B with
+ *   the same `sweeps`.  From sweeps >= nlevels - 1 on these are the exact block solve's bits; an s > n - 1 is clamped to
+ *   n - 1, so a call enqueues at most n launches.
+ * INDEPENDENCE OF THE GEOMETRY.  A column's sum is never split and never meets another column's: the bits do not depend
+ * on k, ldb, ldx, the column tile or "trsv_chain_rows".  A NaN or inf in one column of B never reaches another column.
+ * PADDING.  X[i, 0..k) is overwritten for every row; the padding X[i, k..ldx) is not touched; the padding of B is never
+ * read.  IN PLACE: x == b is allowed when ldx == ldb (element (i, j) is read before it is stored, and nothing else of B
+ * is read); otherwise the two blocks must not overlap.
+ * WIDTH.  k is not limited: a block wider than the column tile is covered inside each launch.  The exact solve enqueues
+ * exactly the plan's recorded launches ("launches" of describe()["trsv"]) whatever k is, a sweep call exactly 1 + s;
+ * column panels are never looped on the host.  Order between workgroups comes from the stream alone -- no flags, no
+ * spins, no atomics, no grid syncs -- so a call cannot hang.
+ * SPAL_ERR_INVALID_ARGUMENT before any device work: null handle or pointers; k == 0; ldb < k or ldx < k; x == b with
+ * ldx != ldb; the host forms: b_rows != nrows or x_rows != nrows; uplo or unit_diag outside {0, 1}; an _f64 entry on an
+ * f32 handle or the reverse; a matrix that is not square; unit_diag = 0 and a row without a stored (i, i) (the message
+ * names the first such row).  SPAL_ERR_UNSUPPORTED: a handle held as row blocks.
+ * THE PLAN IS THE VECTOR SOLVE'S.  The first exact solve of a triangle -- of a vector or of a block -- builds the
+ * triangle's plan, which synchronises `stream`; every later call, of either kind, allocates nothing and synchronises
+ * nothing, and "analyses" of describe()["trsv"] stays 1.  The sweep forms use the handle's sweep preparation, built by
+ * the first sweep call of either kind (no host analysis, no plan); their ping-pong scratch is n * k elements per buffer
+ * -- none for s = 0, one buffer for s = 1, two beyond -- taken from and returned to the runtime's stream-ordered
+ * allocator in stream order, as the single-vector form does it.  The host forms copy B up packed, solve in place, copy
+ * the k columns of X back and synchronise.  CSC handles run on their CSR twin.  Calls on one handle serialise on its
+ * lock, as the vector solves do.
+ * Option "trsm_tile" (spal_csr_set_option / spal_csc_set_option): the column tile KT -- a wave is 64 / KT rows x KT
+ * columns of X.  0 = automatic (the narrowest tile that holds k, at most 32), else one of 1, 2, 4, 8, 16, 32; anything
+ * else SPAL_ERR_INVALID_ARGUMENT.  After the first block call describe() carries a "trsm" object: {tile, k,
+ * column_tiles, launches} of the last call, and calls / sweep_calls, the exact and the sweep calls so far. */
+int spal_csr_trsm_f64(spal_csr_t a, int uplo, int unit_diag, uint64_t k, const double *b, uint64_t ldb,
+                      uint64_t b_rows, double *x, uint64_t ldx, uint64_t x_rows);
+int spal_csr_trsm_dev_f64(spal_csr_t a, int uplo, int unit_diag, uint64_t k, const double *b_dev, uint64_t ldb,
+                          double *x_dev, uint64_t ldx, void *stream);
+int spal_csr_trsm_sweep_f64(spal_csr_t a, int uplo, int unit_diag, uint64_t sweeps, uint64_t k, const double *b,
+                            uint64_t ldb, uint64_t b_rows, double *x, uint64_t ldx, uint64_t x_rows);
+int spal_csr_trsm_sweep_dev_f64(spal_csr_t a, int uplo, int unit_diag, uint64_t sweeps, uint64_t k,
+                                const double *b_dev, uint64_t ldb, double *x_dev, uint64_t ldx, void *stream);
+int spal_csr_trsm_f32(spal_csr_t a, int uplo, int unit_diag, uint64_t k, const float *b, uint64_t ldb,
+                      uint64_t b_rows, float *x, uint64_t ldx, uint64_t x_rows);
+int spal_csr_trsm_dev_f32(spal_csr_t a, int uplo, int unit_diag, uint64_t k, const float *b_dev, uint64_t ldb,
+                          float *x_dev, uint64_t ldx, void *stream);
+int spal_csr_trsm_sweep_f32(spal_csr_t a, int uplo, int unit_diag, uint64_t sweeps, uint64_t k, const float *b,
+                            uint64_t ldb, uint64_t b_rows, float *x, uint64_t ldx, uint64_t x_rows);
+int spal_csr_trsm_sweep_dev_f32(spal_csr_t a, int uplo, int unit_diag, uint64_t sweeps, uint64_t k,
+                                const float *b_dev, uint64_t ldb, float *x_dev, uint64_t ldx, void *stream);
+int spal_csc_trsm_f64(spal_csc_t a, int uplo, int unit_diag, uint64_t k, const double *b, uint64_t ldb,
+                      uint64_t b_rows, double *x, uint64_t ldx, uint64_t x_rows);
+int spal_csc_trsm_dev_f64(spal_csc_t a, int uplo, int unit_diag, uint64_t k, const double *b_dev, uint64_t ldb,
+                          double *x_dev, uint64_t ldx, void *stream);
+int spal_csc_trsm_sweep_f64(spal_csc_t a, int uplo, int unit_diag, uint64_t sweeps, uint64_t k, const double *b,
+                            uint64_t ldb, uint64_t b_rows, double *x, uint64_t ldx, uint64_t x_rows);
+int spal_csc_trsm_sweep_dev_f64(spal_csc_t a, int uplo, int unit_diag, uint64_t sweeps, uint64_t k,
+                                const double *b_dev, uint64_t ldb, double *x_dev, uint64_t ldx, void *stream);
+int spal_csc_trsm_f32(spal_csc_t a, int uplo, int unit_diag, uint64_t k, const float *b, uint64_t ldb,
+                      uint64_t b_rows, float *x, uint64_t ldx, uint64_t x_rows);
+int spal_csc_trsm_dev_f32(spal_csc_t a, int uplo, int unit_diag, uint64_t k, const float *b_dev, uint64_t ldb,
+                          float *x_dev, uint64_t ldx, void *stream);
+int spal_csc_trsm_sweep_f32(spal_csc_t a, int uplo, int unit_diag, uint64_t sweeps, uint64_t k, const float *b,
+                            uint64_t ldb, uint64_t b_rows, float *x, uint64_t ldx, uint64_t x_rows);
+int spal_csc_trsm_sweep_dev_f32(spal_csc_t a, int uplo, int unit_diag, uint64_t sweeps, uint64_t k,
+                                const float *b_dev, uint64_t ldb, float *x_dev, uint64_t ldx, void *stream);
+
 /* ---- ILU(0): the incomplete LU factorisation without fill, CSR and CSC ------------------
  * Not in the reference; the contract is this sequential loop, which the device reproduces bit for bit in f32 and f64
  * (NaN by position).  A is square and stored as the handle stores it, columns strictly ascending inside a row, and every

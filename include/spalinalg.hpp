@@ -71,6 +71,8 @@ template <> struct Abi<double> {
     static constexpr auto csr_spmm = spal_csr_spmm_f64;
     static constexpr auto csr_trsv = spal_csr_trsv_f64;
     static constexpr auto csr_trsv_sweep = spal_csr_trsv_sweep_f64;
+    static constexpr auto csr_trsm = spal_csr_trsm_f64;
+    static constexpr auto csr_trsm_sweep = spal_csr_trsm_sweep_f64;
     static constexpr auto csr_krylov = spal_csr_krylov_f64;
     static constexpr auto csr_gmres = spal_csr_gmres_f64;
     static constexpr auto csr_permute_vec = spal_csr_permute_vec_f64;
@@ -81,6 +83,8 @@ template <> struct Abi<double> {
     static constexpr auto csc_spmm = spal_csc_spmm_f64;
     static constexpr auto csc_trsv = spal_csc_trsv_f64;
     static constexpr auto csc_trsv_sweep = spal_csc_trsv_sweep_f64;
+    static constexpr auto csc_trsm = spal_csc_trsm_f64;
+    static constexpr auto csc_trsm_sweep = spal_csc_trsm_sweep_f64;
     static constexpr auto csc_krylov = spal_csc_krylov_f64;
     static constexpr auto csc_gmres = spal_csc_gmres_f64;
     static constexpr auto csc_permute_vec = spal_csc_permute_vec_f64;
@@ -94,6 +98,8 @@ template <> struct Abi<float> {
     static constexpr auto csr_spmm = spal_csr_spmm_f32;
     static constexpr auto csr_trsv = spal_csr_trsv_f32;
     static constexpr auto csr_trsv_sweep = spal_csr_trsv_sweep_f32;
+    static constexpr auto csr_trsm = spal_csr_trsm_f32;
+    static constexpr auto csr_trsm_sweep = spal_csr_trsm_sweep_f32;
     static constexpr auto csr_krylov = spal_csr_krylov_f32;
     static constexpr auto csr_gmres = spal_csr_gmres_f32;
     static constexpr auto csr_permute_vec = spal_csr_permute_vec_f32;
@@ -104,6 +110,8 @@ template <> struct Abi<float> {
     static constexpr auto csc_spmm = spal_csc_spmm_f32;
     static constexpr auto csc_trsv = spal_csc_trsv_f32;
     static constexpr auto csc_trsv_sweep = spal_csc_trsv_sweep_f32;
+    static constexpr auto csc_trsm = spal_csc_trsm_f32;
+    static constexpr auto csc_trsm_sweep = spal_csc_trsm_sweep_f32;
     static constexpr auto csc_krylov = spal_csc_krylov_f32;
     static constexpr auto csc_gmres = spal_csc_gmres_f32;
     static constexpr auto csc_permute_vec = spal_csc_permute_vec_f32;
@@ -266,6 +274,40 @@ class CsrMatrix {
         std::vector<T> x(nrows_);
         detail::check(detail::Abi<T>::csr_trsv_sweep(device_handle(), lower ? 0 : 1, unit_diagonal ? 1 : 0, sweeps, b.data(),
                                                      b.size(), x.data(), x.size()));
+        return x;
+    }
+
+    // the host-side refusals of the block solves, before any device call
+    void check_block(const char *who, std::size_t len, usize k) const {
+        if (nrows_ != ncols_)
+            throw Panic(SPAL_ERR_INVALID_ARGUMENT, std::string(who) + ": the matrix is not square (" +
+                                                       std::to_string(nrows_) + " x " + std::to_string(ncols_) + ")");
+        if (k == 0) throw Panic(SPAL_ERR_INVALID_ARGUMENT, std::string(who) + ": k = 0 (B and X need at least one column)");
+        if (len % k != 0 || len / k != nrows_)
+            throw Panic(SPAL_ERR_INVALID_ARGUMENT, std::string(who) + ": B.len() = " + std::to_string(len) + " is not " +
+                                                       std::to_string(nrows_) + " rows of k = " + std::to_string(k));
+    }
+
+    // X with L X = B / U X = B for a ROW-MAJOR block of k right-hand sides (B.size() == nrows * k, element (i, j) at
+    // i * k + j): column j of the result is bit for bit solve_triangular's result for column j of B, and all k columns
+    // share one solve's launches (spal_csr_trsm_*).  Panics as solve_triangular does, and when k == 0 or B has another
+    // number of rows than the matrix.
+    std::vector<T> solve_triangular_block(const std::vector<T> &B, usize k, bool lower = true, bool unit_diagonal = false) const {
+        check_block("solve_triangular_block", B.size(), k);
+        std::vector<T> x(nrows_ * k);
+        detail::check(detail::Abi<T>::csr_trsm(device_handle(), lower ? 0 : 1, unit_diagonal ? 1 : 0, k, B.data(), k,
+                                               nrows_, x.data(), k, nrows_));
+        return x;
+    }
+
+    // ... and by `sweeps` Jacobi passes per column (spal_csr_trsm_sweep_*): column j is solve_triangular_sweeps' result
+    // for column j of B; a pass stages the matrix once for all k columns.
+    std::vector<T> solve_triangular_block_sweeps(const std::vector<T> &B, usize k, bool lower, bool unit_diagonal,
+                                                 std::uint64_t sweeps) const {
+        check_block("solve_triangular_block_sweeps", B.size(), k);
+        std::vector<T> x(nrows_ * k);
+        detail::check(detail::Abi<T>::csr_trsm_sweep(device_handle(), lower ? 0 : 1, unit_diagonal ? 1 : 0, sweeps, k,
+                                                     B.data(), k, nrows_, x.data(), k, nrows_));
         return x;
     }
 
@@ -518,6 +560,40 @@ class CscMatrix {
         std::vector<T> x(nrows_);
         detail::check(detail::Abi<T>::csc_trsv_sweep(device_handle(), lower ? 0 : 1, unit_diagonal ? 1 : 0, sweeps, b.data(),
                                                      b.size(), x.data(), x.size()));
+        return x;
+    }
+
+    // the host-side refusals of the block solves, before any device call
+    void check_block(const char *who, std::size_t len, usize k) const {
+        if (nrows_ != ncols_)
+            throw Panic(SPAL_ERR_INVALID_ARGUMENT, std::string(who) + ": the matrix is not square (" +
+                                                       std::to_string(nrows_) + " x " + std::to_string(ncols_) + ")");
+        if (k == 0) throw Panic(SPAL_ERR_INVALID_ARGUMENT, std::string(who) + ": k = 0 (B and X need at least one column)");
+        if (len % k != 0 || len / k != nrows_)
+            throw Panic(SPAL_ERR_INVALID_ARGUMENT, std::string(who) + ": B.len() = " + std::to_string(len) + " is not " +
+                                                       std::to_string(nrows_) + " rows of k = " + std::to_string(k));
+    }
+
+    // X with L X = B / U X = B for a ROW-MAJOR block of k right-hand sides (B.size() == nrows * k, element (i, j) at
+    // i * k + j): column j of the result is bit for bit solve_triangular's result for column j of B, and all k columns
+    // share one solve's launches (spal_csc_trsm_*).  Panics as solve_triangular does, and when k == 0 or B has another
+    // number of rows than the matrix.
+    std::vector<T> solve_triangular_block(const std::vector<T> &B, usize k, bool lower = true, bool unit_diagonal = false) const {
+        check_block("solve_triangular_block", B.size(), k);
+        std::vector<T> x(nrows_ * k);
+        detail::check(detail::Abi<T>::csc_trsm(device_handle(), lower ? 0 : 1, unit_diagonal ? 1 : 0, k, B.data(), k,
+                                               nrows_, x.data(), k, nrows_));
+        return x;
+    }
+
+    // ... and by `sweeps` Jacobi passes per column (spal_csc_trsm_sweep_*): column j is solve_triangular_sweeps' result
+    // for column j of B; a pass stages the matrix once for all k columns.
+    std::vector<T> solve_triangular_block_sweeps(const std::vector<T> &B, usize k, bool lower, bool unit_diagonal,
+                                                 std::uint64_t sweeps) const {
+        check_block("solve_triangular_block_sweeps", B.size(), k);
+        std::vector<T> x(nrows_ * k);
+        detail::check(detail::Abi<T>::csc_trsm_sweep(device_handle(), lower ? 0 : 1, unit_diagonal ? 1 : 0, sweeps, k,
+                                                     B.data(), k, nrows_, x.data(), k, nrows_));
         return x;
     }
     // C = A * B: `impl Mul for &CscMatrix<T>` (src/csc/ops/mul.rs:5-60) on the device, bit-identical.

@@ -92,6 +92,22 @@ extern "C" {
     pub fn spal_csc_trsv_sweep_f32(a: *mut spal_csc, uplo: c_int, unit_diag: c_int, sweeps: u64, b: *const f32, b_len: u64, x: *mut f32, x_len: u64) -> c_int;
     pub fn spal_csc_trsv_sweep_dev_f64(a: *mut spal_csc, uplo: c_int, unit_diag: c_int, sweeps: u64, b_dev: *const f64, x_dev: *mut f64, stream: *mut c_void) -> c_int;
     pub fn spal_csc_trsv_sweep_dev_f32(a: *mut spal_csc, uplo: c_int, unit_diag: c_int, sweeps: u64, b_dev: *const f32, x_dev: *mut f32, stream: *mut c_void) -> c_int;
+    pub fn spal_csr_trsm_f64(a: *mut spal_csr, uplo: c_int, unit_diag: c_int, k: u64, b: *const f64, ldb: u64, b_rows: u64, x: *mut f64, ldx: u64, x_rows: u64) -> c_int;
+    pub fn spal_csr_trsm_dev_f64(a: *mut spal_csr, uplo: c_int, unit_diag: c_int, k: u64, b_dev: *const f64, ldb: u64, x_dev: *mut f64, ldx: u64, stream: *mut c_void) -> c_int;
+    pub fn spal_csr_trsm_sweep_f64(a: *mut spal_csr, uplo: c_int, unit_diag: c_int, sweeps: u64, k: u64, b: *const f64, ldb: u64, b_rows: u64, x: *mut f64, ldx: u64, x_rows: u64) -> c_int;
+    pub fn spal_csr_trsm_sweep_dev_f64(a: *mut spal_csr, uplo: c_int, unit_diag: c_int, sweeps: u64, k: u64, b_dev: *const f64, ldb: u64, x_dev: *mut f64, ldx: u64, stream: *mut c_void) -> c_int;
+    pub fn spal_csr_trsm_f32(a: *mut spal_csr, uplo: c_int, unit_diag: c_int, k: u64, b: *const f32, ldb: u64, b_rows: u64, x: *mut f32, ldx: u64, x_rows: u64) -> c_int;
+    pub fn spal_csr_trsm_dev_f32(a: *mut spal_csr, uplo: c_int, unit_diag: c_int, k: u64, b_dev: *const f32, ldb: u64, x_dev: *mut f32, ldx: u64, stream: *mut c_void) -> c_int;
+    pub fn spal_csr_trsm_sweep_f32(a: *mut spal_csr, uplo: c_int, unit_diag: c_int, sweeps: u64, k: u64, b: *const f32, ldb: u64, b_rows: u64, x: *mut f32, ldx: u64, x_rows: u64) -> c_int;
+    pub fn spal_csr_trsm_sweep_dev_f32(a: *mut spal_csr, uplo: c_int, unit_diag: c_int, sweeps: u64, k: u64, b_dev: *const f32, ldb: u64, x_dev: *mut f32, ldx: u64, stream: *mut c_void) -> c_int;
+    pub fn spal_csc_trsm_f64(a: *mut spal_csc, uplo: c_int, unit_diag: c_int, k: u64, b: *const f64, ldb: u64, b_rows: u64, x: *mut f64, ldx: u64, x_rows: u64) -> c_int;
+    pub fn spal_csc_trsm_dev_f64(a: *mut spal_csc, uplo: c_int, unit_diag: c_int, k: u64, b_dev: *const f64, ldb: u64, x_dev: *mut f64, ldx: u64, stream: *mut c_void) -> c_int;
+    pub fn spal_csc_trsm_sweep_f64(a: *mut spal_csc, uplo: c_int, unit_diag: c_int, sweeps: u64, k: u64, b: *const f64, ldb: u64, b_rows: u64, x: *mut f64, ldx: u64, x_rows: u64) -> c_int;
+    pub fn spal_csc_trsm_sweep_dev_f64(a: *mut spal_csc, uplo: c_int, unit_diag: c_int, sweeps: u64, k: u64, b_dev: *const f64, ldb: u64, x_dev: *mut f64, ldx: u64, stream: *mut c_void) -> c_int;
+    pub fn spal_csc_trsm_f32(a: *mut spal_csc, uplo: c_int, unit_diag: c_int, k: u64, b: *const f32, ldb: u64, b_rows: u64, x: *mut f32, ldx: u64, x_rows: u64) -> c_int;
+    pub fn spal_csc_trsm_dev_f32(a: *mut spal_csc, uplo: c_int, unit_diag: c_int, k: u64, b_dev: *const f32, ldb: u64, x_dev: *mut f32, ldx: u64, stream: *mut c_void) -> c_int;
+    pub fn spal_csc_trsm_sweep_f32(a: *mut spal_csc, uplo: c_int, unit_diag: c_int, sweeps: u64, k: u64, b: *const f32, ldb: u64, b_rows: u64, x: *mut f32, ldx: u64, x_rows: u64) -> c_int;
+    pub fn spal_csc_trsm_sweep_dev_f32(a: *mut spal_csc, uplo: c_int, unit_diag: c_int, sweeps: u64, k: u64, b_dev: *const f32, ldb: u64, x_dev: *mut f32, ldx: u64, stream: *mut c_void) -> c_int;
     pub fn spal_csr_ilu0(a: *mut spal_csr, stream: *mut c_void, out: *mut *mut spal_csr) -> c_int;
     pub fn spal_csc_ilu0(a: *mut spal_csc, stream: *mut c_void, out: *mut *mut spal_csc) -> c_int;
     pub fn spal_csr_ilu0_sweep(a: *mut spal_csr, sweeps: u64, stream: *mut c_void, out: *mut *mut spal_csr) -> c_int;

@@ -384,6 +384,11 @@ struct spal_csr {
     uint64_t sweep_first_missing = 0;   // the first row without a stored diagonal, nrows when there is none
     double sweep_prepare_ms = 0.0;      // launch + read back, host clock
     uint64_t sweep_calls = 0;           // sweep calls enqueued so far (describe)
+    // Solves for a block of right-hand sides (spal_trsm.hip); guarded by mu
+    int trsm_tile = 0;                  // option "trsm_tile": column tile, 0 = automatic
+    uint32_t trsm_last_tile = 0, trsm_last_k = 0;   // of the last block call (describe)
+    uint64_t trsm_last_launches = 0;    // launches the last block call enqueued
+    uint64_t trsm_calls = 0, trsm_sweep_calls = 0;   // block calls enqueued so far, exact and sweeps
 };
 
 struct spal_csc {

@@ -1,0 +1,561 @@
+// spal_trsm.hip -- triangular solves for a block of k right-hand sides, exact and by Jacobi sweeps.  B and X
+// are n x k, dense and row-major (element (i, j) at [i * ld + j], ld >= k): the layout of SpMM.  Column j of X is, bit for
+// bit, what spal_*_trsv_* / spal_*_trsv_sweep_* return for column j of B: the same sequential texts (include/spal.h),
+// applied per column.  A column's sum is never split and never meets another column's, so the bits depend neither on k,
+// the leading dimensions or the column tile, nor on "trsv_chain_rows".
+//
+// THE EXACT SOLVE RIDES ON THE VECTOR SOLVE'S PLAN.  The TrsvPlan of the triangle (spal_trsv.hip, reached through
+// trsv_plan_get) gives the rows by level and the recorded launches; a block solve enqueues exactly those launches, whatever
+// k is.  One thread owns one (row, column j) pair: the lane-group layout is SpMM's, a wave is 64 / KT rows x KT columns,
+// the KT lanes of a group read the same colind[q] and values[q] and gather the contiguous segment
+// X[col * ldx + j0 .. j0 + KT).
+//   * trsm_level: one launch = one wide level; the column tiles j0 = 0, KT, 2 KT, ... are looped inside the thread.
+//   * trsm_chain: one launch = a run of narrow levels walked by ONE workgroup of 1024 threads with a __syncthreads()
+//     between levels.  Its 1024 / KT lane groups take the (row, column tile) items of a level in turn, so a level of one
+//     row and three column tiles keeps three groups busy; more items than groups are looped over.  While a level is being
+//     summed the head of the group's first item of the next level (row, bounds, B[row, j]) is already in flight.
+// VISIBILITY, as in trsv_chain: level l + 1 gathers what the same workgroup stored in level l.  The waves of a workgroup
+// share a CU and its L1, the barrier orders the stores before the loads at workgroup scope, and x is neither __restrict__
+// nor read by streaming / non-temporal loads in these two kernels, so no load is moved or served from a stale copy.
+//
+// A SWEEP PASS STAGES THE MATRIX ONCE FOR ALL k COLUMNS.  trsm_sweep_pass: a workgroup owns a tile of R consecutive rows
+// (R as in spal_spmm.hip), loads the tile's whole entry range -- columns and values -- coalesced into LDS once, and every
+// (row, column) thread then walks its row's entries of the chosen triangle only, [rowptr[i], dlo) or [dhi, rowptr[i + 1])
+// of the handle's sweep_rows, in stored order from LDS.  A tile whose entries exceed the strip walks from global memory.
+// The single-vector pass keeps a product per entry in LDS; with k columns that image would be k times as large, so here
+// the products stay in registers.  trsm_sweep_scale is the s = 0 step X = D^-1 B.
+//
+// ORDER BETWEEN WORKGROUPS COMES FROM THE STREAM ALONE: no flags, no spins, no atomics, no grid syncs.  A call cannot hang.
+#include "spal_ops.hpp"
+
+#include <type_traits>
+
+#pragma clang fp contract(off)
+
+namespace spal {
+namespace {
+
+constexpr int kLevelThreads = 256;
+constexpr int kChainThreads = 1024;
+constexpr int kPassThreads = 256;
+constexpr uint32_t kCap = 2048;          // entries of a tile's LDS strip (sweep pass)
+constexpr uint32_t kTileRowsMax = 256;   // rows of a tile, at most
+constexpr uint32_t kBatch = 8;           // gathers of x in flight per thread
+constexpr int kTiles[] = {1, 2, 4, 8, 16, 32};   // the instantiated column tiles
+
+// What a row needs that depends neither on x nor on the column.
+struct RowHead {
+    uint32_t row, p0, p1, dp;   // off-diagonal entries [p0, p1) of the triangle; dp: where the diagonal is, if stored
+};
+
+template <int UPLO>
+__device__ __forceinline__ RowHead trsm_head(uint2 rd, const uint32_t *__restrict__ rowptr,
+                                             const uint32_t *__restrict__ colind) {
+    RowHead h;
+    h.row = rd.x;
+    h.dp = rd.y;
+    if (UPLO == 0) {
+        h.p0 = rowptr[rd.x];
+        h.p1 = rd.y;
+    } else {
+        h.p1 = rowptr[rd.x + 1];
+        h.p0 = rd.y + ((rd.y < h.p1 && colind[rd.y] == rd.x) ? 1u : 0u);
+    }
+    return h;
+}
+
+// One (row, column) pair: s - the row's entries [p0, p1) of `col` / `val` (global arrays or an LDS strip) times column
+// xj of the block, in stored order, one product then one difference; kBatch gathers in flight, past the row's end the
+// last entry's addresses repeat and their products are dropped.
+template <typename T>
+__device__ __forceinline__ T trsm_sub(T s, const uint32_t *col, const T *val, uint32_t p0, uint32_t p1, const T *xj,
+                                      uint64_t ldx) {
+    for (uint32_t p = p0; p < p1; p += kBatch) {
+        T xv[kBatch], v[kBatch];
+#pragma unroll
+        for (uint32_t u = 0; u < kBatch; ++u) {
+            const uint32_t q = min(p + u, p1 - 1);
+            xv[u] = xj[(uint64_t)col[q] * ldx];
+            v[u] = val[q];
+        }
+#pragma unroll
+        for (uint32_t u = 0; u < kBatch; ++u)
+            if (p + u < p1) s = s - v[u] * xv[u];
+    }
+    return s;
+}
+
+// B and X may be the same block (same leading dimension): pair (i, j) reads B[i, j] before it stores X[i, j], and
+// nothing else of B.
+template <typename T>
+__device__ __forceinline__ void trsm_pair(const RowHead &h, T rhs, uint32_t jc, const uint32_t *__restrict__ colind,
+                                          const T *__restrict__ values, T *X, uint64_t ldx, int unit_diag) {
+    const T s = trsm_sub<T>(rhs, colind, values, h.p0, h.p1, X + jc, ldx);
+    X[(uint64_t)h.row * ldx + jc] = unit_diag ? s : s / values[h.dp];   // plain division: correctly rounded
+}
+
+template <typename T, int UPLO, int KT>
+__global__ __launch_bounds__(kLevelThreads) void trsm_level(const uint2 *__restrict__ rows, uint32_t k0, uint32_t k1,
+                                                            const uint32_t *__restrict__ rowptr,
+                                                            const uint32_t *__restrict__ colind,
+                                                            const T *__restrict__ values, uint32_t k, const T *B,
+                                                            uint64_t ldb, T *X, uint64_t ldx, int unit_diag) {
+    constexpr uint32_t G = kLevelThreads / KT;
+    const uint32_t g = threadIdx.x / KT, j = threadIdx.x % KT;
+    const uint64_t at = (uint64_t)k0 + (uint64_t)blockIdx.x * G + g;
+    if (at >= k1) return;
+    const RowHead h = trsm_head<UPLO>(rows[at], rowptr, colind);
+    for (uint32_t jc = j; jc < k; jc += KT)   // column tiles of the block, the last one partial
+        trsm_pair<T>(h, B[(uint64_t)h.row * ldb + jc], jc, colind, values, X, ldx, unit_diag);
+}
+
+// An item of a level: (row, column tile), and this lane's column in it.
+template <typename T>
+struct Item {
+    RowHead h;
+    uint32_t jc;
+    bool live;
+    T rhs;
+};
+
+// item `it` of the level whose rows are rows[a0 .. a1): row a0 + it / ct, column tile it % ct (ct tiles cover k)
+template <typename T, int UPLO, int KT>
+__device__ __forceinline__ Item<T> trsm_item(const uint2 *__restrict__ rows, uint32_t a0, uint32_t a1, uint64_t it,
+                                             uint32_t ct, uint32_t k, uint32_t j, const uint32_t *__restrict__ rowptr,
+                                             const uint32_t *__restrict__ colind, const T *B, uint64_t ldb) {
+    Item<T> m = {};
+    if (it >= (uint64_t)(a1 - a0) * ct) return m;
+    const uint32_t r = (it >> 32) ? (uint32_t)(it / ct) : (uint32_t)it / ct;   // the 64-bit division is the rare one
+    m.jc = (uint32_t)(it - (uint64_t)r * ct) * KT + j;
+    if (m.jc >= k) return m;
+    m.live = true;
+    m.h = trsm_head<UPLO>(rows[a0 + r], rowptr, colind);
+    m.rhs = B[(uint64_t)m.h.row * ldb + m.jc];
+    return m;
+}
+
+template <typename T, int UPLO, int KT>
+__global__ __launch_bounds__(kChainThreads) void trsm_chain(const uint2 *__restrict__ rows,
+                                                            const uint32_t *__restrict__ level_ptr, uint32_t l0,
+                                                            uint32_t l1, const uint32_t *__restrict__ rowptr,
+                                                            const uint32_t *__restrict__ colind,
+                                                            const T *__restrict__ values, uint32_t k, uint32_t ct,
+                                                            const T *B, uint64_t ldb, T *X, uint64_t ldx,
+                                                            int unit_diag) {
+    constexpr uint32_t G = kChainThreads / KT;
+    const uint32_t g = threadIdx.x / KT, j = threadIdx.x % KT;
+    uint32_t a0 = level_ptr[l0], a1 = level_ptr[l0 + 1];
+    Item<T> cur = trsm_item<T, UPLO, KT>(rows, a0, a1, g, ct, k, j, rowptr, colind, B, ldb);
+    for (uint32_t l = l0; l < l1; ++l) {
+        const bool more = l + 1 < l1;
+        const uint32_t a2 = more ? level_ptr[l + 2] : a1;
+        Item<T> nxt = {};
+        if (more) nxt = trsm_item<T, UPLO, KT>(rows, a1, a2, g, ct, k, j, rowptr, colind, B, ldb);
+        if (cur.live) trsm_pair<T>(cur.h, cur.rhs, cur.jc, colind, values, X, ldx, unit_diag);
+        const uint64_t items = (uint64_t)(a1 - a0) * ct;
+        for (uint64_t it = (uint64_t)g + G; it < items; it += G) {
+            const Item<T> m = trsm_item<T, UPLO, KT>(rows, a0, a1, it, ct, k, j, rowptr, colind, B, ldb);
+            if (m.live) trsm_pair<T>(m.h, m.rhs, m.jc, colind, values, X, ldx, unit_diag);
+        }
+        __syncthreads();   // level l's X is stored and visible to the workgroup before level l + 1 gathers it
+        cur = nxt;
+        a0 = a1;
+        a1 = a2;
+    }
+}
+
+// ---- sweeps ---------------------------------------------------------------------------------------------------------
+// s = 0: X = D^-1 B, an element per thread (grid-stride: n * k may exceed what one grid trip covers)
+template <typename T>
+__global__ __launch_bounds__(256) void trsm_sweep_scale(uint64_t n, uint32_t k, const uint2 *__restrict__ srows,
+                                                        const T *__restrict__ values, const T *B, uint64_t ldb, T *X,
+                                                        uint64_t ldx, int unit_diag) {
+    const uint64_t total = n * k, step = (uint64_t)gridDim.x * 256;
+    for (uint64_t e = (uint64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += step) {
+        const uint64_t i = e / k;
+        const uint32_t j = (uint32_t)(e - i * k);
+        const T s = B[i * ldb + j];
+        X[i * ldx + j] = unit_diag ? s : s / values[srows[i].x];
+    }
+}
+
+// The lane groups' walk over the tile's rows; `col` / `val` are indexed by (entry - base).  B and Xout may be the same
+// block (pair (i, j) reads B[i, j] before it stores Xout[i, j]); Xin is neither.
+template <typename T, int UPLO, int KT>
+__device__ __forceinline__ void trsm_sweep_walk(const uint32_t *s_rp, const uint32_t *col, const T *val, uint32_t base,
+                                                uint32_t r0, uint32_t nr, uint32_t k, const uint2 *__restrict__ srows,
+                                                const T *__restrict__ values, const T *B, uint64_t ldb,
+                                                const T *__restrict__ Xin, uint64_t ldin, T *Xout, uint64_t ldout,
+                                                int unit_diag) {
+    constexpr uint32_t G = kPassThreads / KT;
+    const uint32_t g = threadIdx.x / KT, j = threadIdx.x % KT;
+    for (uint32_t lr = g; lr < nr; lr += G) {
+        const uint32_t row = r0 + lr;
+        const uint2 rd = srows[row];   // {dlo, dhi}
+        const uint32_t p0 = (UPLO == 0 ? s_rp[lr] : rd.y) - base, p1 = (UPLO == 0 ? rd.x : s_rp[lr + 1]) - base;
+        for (uint32_t jc = j; jc < k; jc += KT) {   // column tiles of the block, the last one partial
+            const T acc = trsm_sub<T>(B[(uint64_t)row * ldb + jc], col, val, p0, p1, Xin + jc, ldin);
+            Xout[(uint64_t)row * ldout + jc] = unit_diag ? acc : acc / values[rd.x];   // plain division
+        }
+    }
+}
+
+template <typename T, int UPLO, int KT>
+__global__ __launch_bounds__(kPassThreads) void trsm_sweep_pass(const uint32_t *__restrict__ rowptr,
+                                                                const uint32_t *__restrict__ colind,
+                                                                const T *__restrict__ values,
+                                                                const uint2 *__restrict__ srows, uint32_t nrows,
+                                                                uint32_t R, uint32_t k, const T *B, uint64_t ldb,
+                                                                const T *__restrict__ Xin, uint64_t ldin, T *Xout,
+                                                                uint64_t ldout, int unit_diag) {
+    __shared__ uint32_t s_rp[kTileRowsMax + 1];
+    __shared__ uint32_t s_col[kCap];
+    __shared__ T s_val[kCap];
+    const uint32_t tid = threadIdx.x;
+    const uint32_t r0 = blockIdx.x * R;   // the grid is ceil(nrows / R): r0 < nrows
+    const uint32_t nr = min(R, nrows - r0);
+    for (uint32_t i = tid; i <= nr; i += kPassThreads) s_rp[i] = rowptr[r0 + i];
+    __syncthreads();
+    const uint32_t e0 = s_rp[0], n = s_rp[nr] - e0;
+    const bool staged = n <= kCap;   // uniform over the workgroup
+    if (staged) {   // the tile's entries, coalesced, all loads issued before the first LDS store
+        constexpr int U = kCap / kPassThreads;
+        uint32_t c[U] = {};
+        T v[U] = {};
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const uint32_t i = tid + u * kPassThreads;
+            if (i < n) { c[u] = colind[e0 + i]; v[u] = values[e0 + i]; }
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const uint32_t i = tid + u * kPassThreads;
+            if (i < n) { s_col[i] = c[u]; s_val[i] = v[u]; }
+        }
+    }
+    __syncthreads();
+    if (staged)
+        trsm_sweep_walk<T, UPLO, KT>(s_rp, s_col, s_val, e0, r0, nr, k, srows, values, B, ldb, Xin, ldin, Xout, ldout,
+                                     unit_diag);
+    else
+        trsm_sweep_walk<T, UPLO, KT>(s_rp, colind, values, 0u, r0, nr, k, srows, values, B, ldb, Xin, ldin, Xout,
+                                     ldout, unit_diag);
+}
+
+// ---- host side ------------------------------------------------------------------------------------------------------
+bool tile_instantiated(int64_t t) {
+    for (int v : kTiles)
+        if (t == v) return true;
+    return false;
+}
+
+// automatic column tile: the narrowest instantiated tile that holds k
+int auto_tile(uint64_t k) {
+    int t = 1;
+    while (t < 32 && (uint64_t)t < k) t *= 2;
+    return t;
+}
+
+// rows of a sweep tile: the largest power of two whose entries fit the strip with a tenth to spare (as SpMM's)
+uint32_t tile_rows(const spal_csr *a) {
+    const double mean = a->nrows ? (double)a->nnz / (double)a->nrows : 0.0;
+    uint32_t R = kTileRowsMax;
+    while (R > 8 && (double)R * mean * 1.1 > (double)kCap) R /= 2;
+    return R;
+}
+
+template <typename T>
+struct Block {   // the two blocks of a call
+    const T *b;
+    uint64_t ldb;
+    T *x;
+    uint64_t ldx;
+    uint32_t k;
+};
+
+// The plan's recorded launches, each for all k columns.
+template <typename T, int UPLO, int KT>
+hipError_t run_list_t(const spal_csr *a, const TrsvPlan *p, int unit_diag, const Block<T> &m, hipStream_t st) {
+    const T *values = (const T *)a->d_values;
+    constexpr uint32_t G = kLevelThreads / KT;
+    const uint32_t ct = (m.k + KT - 1) / KT;
+    for (const TrsvLaunch &ln : p->launches) {
+        if (ln.chain) {
+            hipLaunchKernelGGL((trsm_chain<T, UPLO, KT>), dim3(1), dim3(kChainThreads), 0, st, p->d_rows,
+                               p->d_level_ptr, ln.level0, ln.level1, a->d_rowptr, a->d_colind, values, m.k, ct, m.b,
+                               m.ldb, m.x, m.ldx, unit_diag);
+        } else {
+            const uint32_t k0 = p->level_ptr[ln.level0], k1 = p->level_ptr[ln.level1];
+            hipLaunchKernelGGL((trsm_level<T, UPLO, KT>), dim3(grid_of(k1 - k0, G)), dim3(kLevelThreads), 0, st,
+                               p->d_rows, k0, k1, a->d_rowptr, a->d_colind, values, m.k, m.b, m.ldb, m.x, m.ldx,
+                               unit_diag);
+        }
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+// x0 and s passes, ping-pong through w0 / w1 (packed, leading dimension k), the last one into X.
+template <typename T, int UPLO, int KT>
+hipError_t run_sweeps_t(const spal_csr *a, int unit_diag, uint64_t s, const Block<T> &m, T *w0, T *w1, hipStream_t st) {
+    const uint32_t n = (uint32_t)a->nrows;
+    const T *values = (const T *)a->d_values;
+    T *cur = s == 0 ? m.x : w0;
+    uint64_t ldcur = s == 0 ? m.ldx : m.k;
+    const uint64_t blocks = ((uint64_t)n * m.k + 255) / 256;
+    hipLaunchKernelGGL((trsm_sweep_scale<T>), dim3((unsigned)std::min<uint64_t>(blocks, 1u << 20)), dim3(256), 0, st,
+                       (uint64_t)n, m.k, a->d_sweep_rows, values, m.b, m.ldb, cur, ldcur, unit_diag);
+    hipError_t e = hipGetLastError();
+    const uint32_t R = tile_rows(a);
+    for (uint64_t t = 1; t <= s && e == hipSuccess; ++t) {
+        T *out = t == s ? m.x : (cur == w0 ? w1 : w0);
+        const uint64_t ldout = t == s ? m.ldx : m.k;
+        hipLaunchKernelGGL((trsm_sweep_pass<T, UPLO, KT>), dim3(grid_of(n, R)), dim3(kPassThreads), 0, st, a->d_rowptr,
+                           a->d_colind, values, a->d_sweep_rows, n, R, m.k, m.b, m.ldb, cur, ldcur, out, ldout,
+                           unit_diag);
+        e = hipGetLastError();
+        cur = out;
+        ldcur = ldout;
+    }
+    return e;
+}
+
+// f(std::integral_constant<int, UPLO>, std::integral_constant<int, KT>) for the run-time pair
+template <typename F>
+hipError_t with_uplo_tile(int uplo, int tile, F &&f) {
+#define SPAL_TRSM_CASE(KT)                                                                                             \
+    case KT:                                                                                                           \
+        return uplo ? f(std::integral_constant<int, 1>(), std::integral_constant<int, KT>())                           \
+                    : f(std::integral_constant<int, 0>(), std::integral_constant<int, KT>());
+    switch (tile) {
+        SPAL_TRSM_CASE(1)
+        SPAL_TRSM_CASE(2)
+        SPAL_TRSM_CASE(4)
+        SPAL_TRSM_CASE(8)
+        SPAL_TRSM_CASE(16)
+    default:
+        SPAL_TRSM_CASE(32)
+    }
+#undef SPAL_TRSM_CASE
+}
+
+void note_call(spal_csr *a, int tile, uint32_t k, uint64_t launches, bool sweep) {   // a->mu is held
+    a->trsm_last_tile = (uint32_t)tile;
+    a->trsm_last_k = k;
+    a->trsm_last_launches = launches;
+    ++(sweep ? a->trsm_sweep_calls : a->trsm_calls);
+}
+
+// The exact block solve on a->mu's holder: the plan (built now if this triangle has none), then its launches.
+template <typename T>
+int solve_locked(const char *fn, spal_csr *a, int uplo, int unit_diag, const Block<T> &m, hipStream_t st) {
+    TrsvPlan *p = nullptr;
+    SPAL_TRY(trsv_plan_get(fn, a, uplo, unit_diag, st, &p));
+    const int tile = a->trsm_tile ? a->trsm_tile : auto_tile(m.k);
+    const hipError_t e = with_uplo_tile(uplo, tile, [&](auto U, auto K) {
+        return run_list_t<T, decltype(U)::value, decltype(K)::value>(a, p, unit_diag, m, st);
+    });
+    if (e != hipSuccess) return fail(SPAL_ERR_HIP, "%s: launch failed: %s", fn, hipGetErrorString(e));
+    note_call(a, tile, m.k, p->launches.size(), false);
+    return SPAL_OK;
+}
+
+// s beyond n - 1 changes no bit (every row is final from the pass of its level on, and levels <= n)
+inline uint64_t clamp_sweeps(const spal_csr *a, uint64_t sweeps) {
+    return std::min<uint64_t>(sweeps, a->nrows ? a->nrows - 1 : 0);
+}
+inline int scratch_blocks(uint64_t s) { return s == 0 ? 0 : s == 1 ? 1 : 2; }
+// elements between two scratch blocks: n * k, rounded up to 64 so that every block starts aligned
+inline uint64_t scratch_stride(const spal_csr *a, uint64_t k) { return (a->nrows * k + 63) & ~(uint64_t)63; }
+
+// The sweeps on a prepared handle, a->mu held: 1 + s launches.
+template <typename T>
+int sweep_locked(const char *fn, spal_csr *a, int uplo, int unit_diag, uint64_t s, const Block<T> &m, T *w0, T *w1,
+                 hipStream_t st) {
+    const int tile = a->trsm_tile ? a->trsm_tile : auto_tile(m.k);
+    if (a->nrows) {
+        const hipError_t e = with_uplo_tile(uplo, tile, [&](auto U, auto K) {
+            return run_sweeps_t<T, decltype(U)::value, decltype(K)::value>(a, unit_diag, s, m, w0, w1, st);
+        });
+        if (e != hipSuccess) return fail(SPAL_ERR_HIP, "%s: launch failed: %s", fn, hipGetErrorString(e));
+    }
+    note_call(a, tile, m.k, a->nrows ? 1 + s : 0, true);
+    return SPAL_OK;
+}
+
+// ---- checks, before any device work ---------------------------------------------------------------------------------
+template <typename T, typename H>
+int check_block(const char *fn, const H *a, int uplo, int unit_diag, uint64_t k, const T *b, uint64_t ldb, const T *x,
+                uint64_t ldx) {
+    if (!a) return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: handle is NULL", fn);
+    SPAL_TRY(check_dtype<T>(fn, a->elem_size));
+    SPAL_TRY(check_uplo_unit(fn, uplo, unit_diag));
+    if (!b || !x) return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: null block of vectors", fn);
+    if (k == 0) return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: k = 0 (B and X need at least one column)", fn);
+    if (k > 0xffffffffull) return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: k = %llu does not fit 32 bits", fn, (unsigned long long)k);
+    if (ldb < k)
+        return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: ldb = %llu is less than k = %llu", fn, (unsigned long long)ldb,
+                    (unsigned long long)k);
+    if (ldx < k)
+        return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: ldx = %llu is less than k = %llu", fn, (unsigned long long)ldx,
+                    (unsigned long long)k);
+    if (b == x && ldb != ldx)
+        return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: in place (x == b) needs ldx == ldb, got ldb = %llu and ldx = %llu", fn,
+                    (unsigned long long)ldb, (unsigned long long)ldx);
+    return SPAL_OK;
+}
+
+int check_rows(const char *fn, const spal_csr *a, uint64_t b_rows, uint64_t x_rows) {
+    if (b_rows != a->nrows || x_rows != a->nrows)
+        return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: B has %llu rows and X has %llu rows but the matrix has %llu rows", fn,
+                    (unsigned long long)b_rows, (unsigned long long)x_rows, (unsigned long long)a->nrows);
+    return check_solvable(fn, a);
+}
+
+// ---- the entry points, for either handle type: the work runs on solve_handle(a), under its lock -----------------------
+// host blocks: B packed to ld = k on the way up, solved in place, X's k columns copied back into the caller's rows
+// (padding untouched); `extra` scratch blocks behind it for the sweeps
+template <typename T, typename F>
+int host_form(spal_csr *a, uint64_t k, const T *b, uint64_t ldb, T *x, uint64_t ldx, int extra, F &&run) {
+    const size_t row = (size_t)k * sizeof(T);
+    const uint64_t stride = scratch_stride(a, k);
+    DevBuf d;
+    SPAL_HIP_TRY(d.alloc((size_t)(1 + extra) * stride * sizeof(T)));
+    if (a->nrows)
+        SPAL_HIP_TRY(hipMemcpy2DAsync(d.p, row, b, (size_t)ldb * sizeof(T), row, a->nrows, hipMemcpyHostToDevice, a->stream));
+    T *p = d.as<T>();
+    SPAL_TRY(run(Block<T>{p, k, p, k, (uint32_t)k}, p + stride, p + 2 * stride));
+    if (a->nrows)
+        SPAL_HIP_TRY(hipMemcpy2DAsync(x, (size_t)ldx * sizeof(T), d.p, row, row, a->nrows, hipMemcpyDeviceToHost, a->stream));
+    SPAL_HIP_TRY(hipStreamSynchronize(a->stream));
+    return SPAL_OK;
+}
+
+template <typename T, typename H>
+int trsm_host(const char *fn, H *h, int uplo, int unit_diag, uint64_t k, const T *b, uint64_t ldb, uint64_t b_rows, T *x,
+              uint64_t ldx, uint64_t x_rows) {
+    SPAL_TRY(check_block<T>(fn, h, uplo, unit_diag, k, b, ldb, x, ldx));
+    spal_csr *a = solve_handle(h);
+    SPAL_TRY(check_rows(fn, a, b_rows, x_rows));
+    DeviceGuard guard(h->device);
+    if (guard.status != SPAL_OK) return guard.status;
+    std::lock_guard<std::mutex> lock(a->mu);
+    return host_form<T>(a, k, b, ldb, x, ldx, 0, [&](const Block<T> &m, T *, T *) {
+        return solve_locked<T>(fn, a, uplo, unit_diag, m, a->stream);
+    });
+}
+
+template <typename T, typename H>
+int trsm_dev(const char *fn, H *h, int uplo, int unit_diag, uint64_t k, const T *b, uint64_t ldb, T *x, uint64_t ldx,
+             void *stream) {
+    SPAL_TRY(check_block<T>(fn, h, uplo, unit_diag, k, b, ldb, x, ldx));
+    DeviceGuard guard(h->device);
+    if (guard.status != SPAL_OK) return guard.status;
+    spal_csr *a = solve_handle(h);
+    std::lock_guard<std::mutex> lock(a->mu);
+    return solve_locked<T>(fn, a, uplo, unit_diag, Block<T>{b, ldb, x, ldx, (uint32_t)k}, (hipStream_t)stream);
+}
+
+template <typename T, typename H>
+int trsm_sweep_host(const char *fn, H *h, int uplo, int unit_diag, uint64_t sweeps, uint64_t k, const T *b, uint64_t ldb,
+                    uint64_t b_rows, T *x, uint64_t ldx, uint64_t x_rows) {
+    SPAL_TRY(check_block<T>(fn, h, uplo, unit_diag, k, b, ldb, x, ldx));
+    spal_csr *a = solve_handle(h);
+    SPAL_TRY(check_rows(fn, a, b_rows, x_rows));
+    DeviceGuard guard(h->device);
+    if (guard.status != SPAL_OK) return guard.status;
+    SPAL_TRY(trsv_sweep_prepare(fn, a, unit_diag, a->stream));   // takes the lock itself
+    std::lock_guard<std::mutex> lock(a->mu);
+    const uint64_t s = clamp_sweeps(a, sweeps);
+    return host_form<T>(a, k, b, ldb, x, ldx, scratch_blocks(s), [&](const Block<T> &m, T *w0, T *w1) {
+        return sweep_locked<T>(fn, a, uplo, unit_diag, s, m, w0, w1, a->stream);
+    });
+}
+
+// The scratch is taken and returned in stream order, as the single-vector form does it (spal_trsv_sweep.hip).
+template <typename T, typename H>
+int trsm_sweep_dev(const char *fn, H *h, int uplo, int unit_diag, uint64_t sweeps, uint64_t k, const T *b, uint64_t ldb,
+                   T *x, uint64_t ldx, void *stream) {
+    SPAL_TRY(check_block<T>(fn, h, uplo, unit_diag, k, b, ldb, x, ldx));
+    DeviceGuard guard(h->device);
+    if (guard.status != SPAL_OK) return guard.status;
+    const hipStream_t st = (hipStream_t)stream;
+    spal_csr *a = solve_handle(h);
+    SPAL_TRY(trsv_sweep_prepare(fn, a, unit_diag, st));   // takes the lock itself
+    std::lock_guard<std::mutex> lock(a->mu);
+    const uint64_t s = clamp_sweeps(a, sweeps);
+    const uint64_t stride = scratch_stride(a, k);
+    const int nw = a->nrows ? scratch_blocks(s) : 0;
+    void *w = nullptr;
+    if (nw) SPAL_HIP_TRY(hipMallocAsync(&w, (size_t)nw * stride * sizeof(T), st));
+    const int status = sweep_locked<T>(fn, a, uplo, unit_diag, s, Block<T>{b, ldb, x, ldx, (uint32_t)k}, (T *)w,
+                                       nw > 1 ? (T *)w + stride : nullptr, st);
+    if (nw) {
+        const hipError_t e = hipFreeAsync(w, st);
+        if (status == SPAL_OK) SPAL_HIP_TRY(e);
+    }
+    return status;
+}
+
+}  // namespace
+
+int trsm_option(spal_csr *a, const char *key, int64_t value, int *status) {
+    if (strcmp(key, "trsm_tile")) return 0;
+    if (value != 0 && !tile_instantiated(value)) {
+        *status = fail(SPAL_ERR_INVALID_ARGUMENT, "trsm_tile must be 0 (automatic) or one of 1, 2, 4, 8, 16, 32");
+        return 1;
+    }
+    std::lock_guard<std::mutex> lock(a->mu);
+    a->trsm_tile = (int)value;
+    *status = SPAL_OK;
+    return 1;
+}
+
+int trsm_describe_append(char *buf, size_t buf_len, spal_csr *a) {
+    if (!a) return SPAL_OK;
+    char info[256];
+    {
+        std::lock_guard<std::mutex> lock(a->mu);
+        if (!a->trsm_calls && !a->trsm_sweep_calls) return SPAL_OK;
+        const uint32_t tile = a->trsm_last_tile, k = a->trsm_last_k;
+        snprintf(info, sizeof info,
+                 "{\"tile\": %u, \"k\": %u, \"column_tiles\": %u, \"launches\": %llu, \"calls\": %llu, \"sweep_calls\": %llu}",
+                 tile, k, (k + tile - 1) / tile, (unsigned long long)a->trsm_last_launches,
+                 (unsigned long long)a->trsm_calls, (unsigned long long)a->trsm_sweep_calls);
+    }
+    return describe_append(buf, buf_len, "trsm", info);
+}
+
+}  // namespace spal
+
+using namespace spal;
+
+extern "C" {
+
+#define SPAL_TRSM_ENTRIES(kind, sfx, T)                                                                                    \
+    int spal_##kind##_trsm_##sfx(spal_##kind##_t a, int uplo, int unit_diag, uint64_t k, const T *b, uint64_t ldb,        \
+                                 uint64_t b_rows, T *x, uint64_t ldx, uint64_t x_rows) {                                  \
+        return trsm_host<T>("spal_" #kind "_trsm", a, uplo, unit_diag, k, b, ldb, b_rows, x, ldx, x_rows);                \
+    }                                                                                                                      \
+    int spal_##kind##_trsm_dev_##sfx(spal_##kind##_t a, int uplo, int unit_diag, uint64_t k, const T *b_dev,              \
+                                     uint64_t ldb, T *x_dev, uint64_t ldx, void *stream) {                                \
+        return trsm_dev<T>("spal_" #kind "_trsm_dev", a, uplo, unit_diag, k, b_dev, ldb, x_dev, ldx, stream);             \
+    }                                                                                                                      \
+    int spal_##kind##_trsm_sweep_##sfx(spal_##kind##_t a, int uplo, int unit_diag, uint64_t sweeps, uint64_t k,           \
+                                       const T *b, uint64_t ldb, uint64_t b_rows, T *x, uint64_t ldx, uint64_t x_rows) {  \
+        return trsm_sweep_host<T>("spal_" #kind "_trsm_sweep", a, uplo, unit_diag, sweeps, k, b, ldb, b_rows, x, ldx,     \
+                                  x_rows);                                                                                 \
+    }                                                                                                                      \
+    int spal_##kind##_trsm_sweep_dev_##sfx(spal_##kind##_t a, int uplo, int unit_diag, uint64_t sweeps, uint64_t k,       \
+                                           const T *b_dev, uint64_t ldb, T *x_dev, uint64_t ldx, void *stream) {          \
+        return trsm_sweep_dev<T>("spal_" #kind "_trsm_sweep_dev", a, uplo, unit_diag, sweeps, k, b_dev, ldb, x_dev, ldx,  \
+                                 stream);                                                                                  \
+    }
+SPAL_TRSM_ENTRIES(csr, f64, double)
+SPAL_TRSM_ENTRIES(csr, f32, float)
+SPAL_TRSM_ENTRIES(csc, f64, double)
+SPAL_TRSM_ENTRIES(csc, f32, float)
+#undef SPAL_TRSM_ENTRIES
+
+}  // extern "C"

@@ -285,6 +285,108 @@ class _DeviceMatrix:
                                                              C.c_int(1 if unit_diagonal else 0), u64(sweeps), vp(b_ptr),
                                                              vp(x_ptr), _stream_ptr(stream)))
 
+    def _block(self, B, who):
+        B = np.asarray(B)
+        if B.dtype not in (np.float32, np.float64):
+            B = B.astype(self.dtype)
+        if B.ndim != 2:
+            raise TypeError(f"{who}() takes a 2-D block of right-hand sides, shape (nrows, k)")
+        return np.ascontiguousarray(B)
+
+    def trsm(self, B, lower: bool = True, unit_diagonal: bool = False) -> np.ndarray:
+        """Solves L X = B (lower) or U X = B for a host block B of shape (n, k): every column is, bit for bit, what
+        trsv() returns for it, and all k ride on the launches of one vector solve (spal_*_trsm_*).  Host
+        block in, host block out; a dtype other than the handle's is refused by the library."""
+        B = self._block(B, "trsm")
+        n, k = B.shape
+        X = np.empty_like(B)
+        check(self._fn(f"trsm_{_sfx(B.dtype)}")(self._h, C.c_int(0 if lower else 1), C.c_int(1 if unit_diagonal else 0),
+                                                u64(k), _p(B), u64(k), u64(n), _p(X), u64(k), u64(n)))
+        return X
+
+    def trsm_dev(self, k: int, b_ptr: int, ldb: int, x_ptr: int, ldx: int, lower: bool = True,
+                 unit_diagonal: bool = False, stream=None) -> None:
+        """Device pointers of row-major blocks (element (i, j) at i * ld + j; x_ptr == b_ptr with ldx == ldb solves in
+        place); enqueued on `stream`, not synchronised once the triangle has its plan -- the one trsv() uses."""
+        check(self._fn(f"trsm_dev_{_sfx(self.dtype)}")(self._h, C.c_int(0 if lower else 1),
+                                                       C.c_int(1 if unit_diagonal else 0), u64(k), vp(b_ptr), u64(ldb),
+                                                       vp(x_ptr), u64(ldx), _stream_ptr(stream)))
+
+    def trsm_sweep(self, B, sweeps: int, lower: bool = True, unit_diagonal: bool = False) -> np.ndarray:
+        """`sweeps` Jacobi passes on the chosen triangle for a host block B of shape (n, k): every column is, bit for
+        bit, what trsv_sweep() returns for it; a pass stages the matrix once for all k columns (spal_*_trsm_sweep_*,
+        DESIGN 3.20).  Host block in, host block out."""
+        B = self._block(B, "trsm_sweep")
+        n, k = B.shape
+        X = np.empty_like(B)
+        check(self._fn(f"trsm_sweep_{_sfx(B.dtype)}")(self._h, C.c_int(0 if lower else 1),
+                                                      C.c_int(1 if unit_diagonal else 0), u64(sweeps), u64(k), _p(B),
+                                                      u64(k), u64(n), _p(X), u64(k), u64(n)))
+        return X
+
+    def trsm_sweep_dev(self, k: int, b_ptr: int, ldb: int, x_ptr: int, ldx: int, sweeps: int, lower: bool = True,
+                       unit_diagonal: bool = False, stream=None) -> None:
+        """Device pointers of row-major blocks (x_ptr == b_ptr with ldx == ldb is allowed); enqueued on `stream`, not
+        synchronised once the handle is prepared.  The passes' scratch is taken and returned in stream order."""
+        check(self._fn(f"trsm_sweep_dev_{_sfx(self.dtype)}")(self._h, C.c_int(0 if lower else 1),
+                                                             C.c_int(1 if unit_diagonal else 0), u64(sweeps), u64(k),
+                                                             vp(b_ptr), u64(ldb), vp(x_ptr), u64(ldx),
+                                                             _stream_ptr(stream)))
+
+    def trsm_torch(self, B, out=None, lower: bool = True, unit_diagonal: bool = False, sweeps=None):
+        """B: (n, k) torch tensor on this handle's device with unit stride in its last dimension -- stride(0) is passed
+        as the leading dimension, so a column slice B[:, 2:6] of a wider tensor needs no copy; the same holds for `out`.
+        `out is B` solves in place; `sweeps` = None is the exact solve, an integer that many Jacobi passes.  Runs on
+        torch's current stream."""
+        import torch
+        n = self.shape()[0]
+        tdt = torch.float64 if self.dtype == np.float64 else torch.float32
+
+        def rows_ok(t):   # 2-D, unit stride inside a row, rows ld >= k apart
+            return (t.dim() == 2 and t.shape[0] == n and t.shape[1] >= 1 and t.stride(1) == 1
+                    and (t.stride(0) >= t.shape[1] or t.shape[0] <= 1))
+
+        def span(t):      # [first byte, one past the last byte) the kernels may touch
+            m = (t.shape[0] - 1) * t.stride(0) + t.shape[1] if t.shape[0] else 0
+            return t.data_ptr(), t.data_ptr() + m * t.element_size()
+
+        if B.dtype != tdt or not B.is_cuda or B.dim() != 2:
+            raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT, f"B must be a 2-D {tdt} device tensor of shape (n = {n}, k)")
+        if B.shape[0] != n:
+            raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT, f"B has {B.shape[0]} rows but the matrix has {n} rows")
+        if not rows_ok(B):
+            raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT, "B needs k >= 1 columns, unit stride in its last dimension and "
+                                                        "stride(0) >= k")
+        if B.device.index != self.device:
+            raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT,
+                        f"B lives on cuda:{B.device.index} but the matrix on cuda:{self.device}")
+        k = B.shape[1]
+        if out is None:
+            out = torch.empty((n, k), dtype=tdt, device=B.device)
+        elif out is not B:
+            if out.dtype != tdt or not out.is_cuda or not rows_ok(out) or out.shape[1] != k:
+                raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT,
+                            f"out must be a {tdt} device tensor of shape (n = {n}, k = {k}) with unit stride in its last "
+                            "dimension")
+            if out.device != B.device:
+                raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT, "out and B live on different devices")
+            (b0, b1), (x0, x1) = span(B), span(out)
+            same = x0 == b0 and out.stride(0) == B.stride(0)            # the same block: in place
+            if x0 < b1 and b0 < x1 and not same:
+                # the spans meet: fine only for disjoint column ranges of one wider row-major buffer (same leading dimension)
+                ld, shift = B.stride(0), abs(x0 - b0) // B.element_size() % max(B.stride(0), 1)
+                if not (out.stride(0) == ld and k <= shift <= ld - k):
+                    raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT, "out overlaps B (in place needs out is B)")
+        ldb, ldx = max(B.stride(0), k), max(out.stride(0), k)
+        if out is B:
+            ldx = ldb
+        st = torch.cuda.current_stream(B.device)
+        if sweeps is None:
+            self.trsm_dev(k, B.data_ptr(), ldb, out.data_ptr(), ldx, lower, unit_diagonal, st)
+        else:
+            self.trsm_sweep_dev(k, B.data_ptr(), ldb, out.data_ptr(), ldx, int(sweeps), lower, unit_diagonal, st)
+        return out
+
     def krylov(self, b, method="cg", M=None, x0=None, tol: float = 1e-8, maxit: int = 1000):
         """Solves A x = b by CG ("cg") or BiCGStab ("bicgstab") on the device (spal_*_krylov_*), optionally
         preconditioned by `M`, an ILU(0) factor handle of this class (M^-1 v = two solves on it, or, when M's option
@@ -848,7 +950,8 @@ class _Compressed:
         the sequential loop (spal_*_trsv_*).  The reference has no solve; a Rust binding adds it as a
         method of the matrix types.
         `sweeps` = None is that exact solve; an integer s >= 0 asks for s Jacobi passes on the triangle instead
-        (spal_*_trsv_sweep_*): approximate, every pass one launch, exact from s = levels - 1 on."""
+        (spal_*_trsv_sweep_*): approximate, every pass one launch, exact from s = levels - 1 on.
+        A block of right-hand sides goes to solve_triangular_block."""
         b = np.asarray(b)
         if self._nrows != self._ncols:
             raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT,
@@ -859,6 +962,25 @@ class _Compressed:
         if sweeps is not None:
             return self.device(device).trsv_sweep(b, int(sweeps), lower, unit_diagonal)
         return self.device(device).trsv(b, lower, unit_diagonal)
+
+    def solve_triangular_block(self, B, lower: bool = True, unit_diagonal: bool = False, device: int = 0,
+                               sweeps=None) -> np.ndarray:
+        """X with L X = B / U X = B for a block of right-hand sides B of shape (n, k): column j of the result is bit for
+        bit solve_triangular's result for B[:, j], and the k columns share one solve's launches (spal_*_trsm_*,
+        DESIGN 3.20).  `sweeps` = None is the exact solve, an integer s >= 0 that many Jacobi passes per column
+        (spal_*_trsm_sweep_*).  solve_triangular itself keeps taking one 1-D right-hand side and refusing everything
+        else.  A matrix that is not square, a B that is not 2-D or has another first dimension than n is refused before
+        any device copy is made."""
+        B = np.asarray(B)
+        if self._nrows != self._ncols:
+            raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT,
+                        f"solve_triangular_block: the matrix is not square ({self._nrows} x {self._ncols})")
+        if B.ndim != 2 or B.shape[0] != self._nrows:
+            raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT,
+                        f"solve_triangular_block: B has shape {B.shape} but the matrix has {self._nrows} rows")
+        if sweeps is not None:
+            return self.device(device).trsm_sweep(B, int(sweeps), lower, unit_diagonal)
+        return self.device(device).trsm(B, lower, unit_diagonal)
 
     def solve(self, b, method="cg", M=None, x0=None, tol: float = 1e-8, maxit: int = 1000, device: int = 0,
               precond_sweeps=None):
