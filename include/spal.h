@@ -101,6 +101,17 @@ int spal_csr_destroy(spal_csr_t a);
 /* nrows()/ncols()/nnz() (src/csr.rs:200-222, :287-289); elem_size 4 or 8. */
 int spal_csr_shape(spal_csr_t a, uint64_t *nrows, uint64_t *ncols,
                    uint64_t *nnz, int *elem_size);
+/* What a product returns (CSR and CSC, SpMV and SpMM; DESIGN 3.2d has the table per path).
+ * NaN and +-inf -- in x or stored in the matrix -- reach exactly the rows that reference them, on every path; a stored
+ * zero is an entry like any other (0 * inf is the reference's NaN); the sign and payload of a NaN are not promised.
+ * The paths that keep the reference's order of additions -- the stream, sliding-window, column-panel and column-blocked
+ * kernels, the block-window kernel's rows of at most 32 entries, the short part of the row split where its plan streams
+ * it, CSC handles on their default route, SpMM, the row shards -- return the reference's BITS: the first product of a
+ * row is assigned (src/csr/ops/mul.rs:34), so a row whose products are all -0.0 gives -0.0; subnormals are not flushed;
+ * rows without stored entries give +0.0.  The tree-summed and atomic paths -- vector kernel, overflow kernel, listed
+ * rows of the row split, the block-window kernel's longer rows, the CSC scatter routes ("kernel" = 1) -- agree with
+ * the reference to 1e-10 (f64) / 1e-4 (f32), normwise and against sum |a||x|; they accumulate from +0.0 and may return
+ * +0.0 where the reference returns -0.0; they keep subnormals too (the f32 atomic adds do not flush them on gfx950). */
 /* Host convenience: H2D x, kernel, D2H y.  x_len must equal ncols and y_len
  * nrows (mirrors assert_eq! at src/csr/ops/mul.rs:9).  y is fully
  * overwritten; rows without stored entries give 0.0. */

@@ -347,7 +347,9 @@ __global__ __launch_bounds__(kBwThreads) void csr_spmv_blockwin(const uint32_t *
                 const uint32_t rs = s_rp[i], re = s_rp[i + 1];
                 const uint32_t a = max(rs, ps), b = min(re, pe);
                 if (a >= b || re - rs > kBwShort) continue;         // empty, ended where the pass begins, or listed
-                T acc = rs < ps ? s_carry[parity ^ 1u] : T(0);      // a cut row goes on where the last pass stopped
+                // a cut row goes on where the last pass stopped; a row that begins here starts from -0.0, the identity of IEEE
+                // addition (-0.0 + p == p bit for bit, p = -0.0 included): its first product is ASSIGNED, as in the reference
+                T acc = rs < ps ? s_carry[parity ^ 1u] : T(-0.0);
                 const uint32_t jb = b - ps;
                 uint32_t j = a - ps;
                 for (; j + 4u <= jb; j += 4u) {   // (eight requested at once and added under predicates: 7.4 -> 9.4 us per block)

@@ -3,12 +3,16 @@
 //   ./test_mirror gpu    -- the reference's known-answer vectors on the device
 // Reads like the reference's own #[test]s (src/csr.rs:466-511,
 // src/csr/conv/coo.rs:128-145, src/csc/ops/mul.rs:67-95).
+#include <cmath>
+#include <cstdint>
 #include <cstdio>
 #include <cstring>
 #include <functional>
+#include <limits>
 #include <string>
 #include <vector>
 
+#include "blockwin_rows.hpp"
 #include "spalinalg.hpp"
 
 using namespace spalinalg;
@@ -53,6 +57,38 @@ static void host_tests() {
     CHECK(panics([] { CooMatrix<double>::with_triplets(2, 2, {0}, {0, 1}, {1.0}); }));
 }
 
+// The block-window kernel's one-thread row sums (blockwin_rows.hpp) against the reference's loop (src/csr/ops/mul.rs:31-38:
+// the first product assigned, the others added), compared on the bit patterns: five rows in passes of four entries, so that
+// boundaries cut rows 1 and 3.
+template <typename T>
+static void blockwin_rows_tests() {
+    const T inf = std::numeric_limits<T>::infinity(), den = std::numeric_limits<T>::denorm_min();
+    // row 0: one product -0.0 | row 1 (cut after three entries): all -0.0 | row 2: empty | row 3 (cut after three): -0.0 three
+    // times, then 2.5 | row 4: (+0.0) + (-0.0) | row 5 (cut): inf - inf | row 6: one subnormal product
+    const std::vector<uint64_t> rp{0, 1, 5, 5, 9, 11, 13, 14};
+    const std::vector<uint64_t> ci{0, 0, 1, 2, 3, 0, 1, 2, 3, 0, 1, 3, 4, 3};
+    const std::vector<T> va{T(-1), T(-2), T(-0.0), T(-3), T(-0.0), T(-0.0), T(-7), T(-1), T(2.5), T(4), T(-0.0), inf, -inf, den};
+    const std::vector<T> xs{T(0), T(0), T(0), T(1), T(1)};
+    const uint64_t n = rp.size() - 1;
+    std::vector<T> ref(n, T(0)), got(n, T(77)), old(n, T(77));
+    for (uint64_t i = 0; i < n; ++i)
+        for (uint64_t e = rp[i]; e < rp[i + 1]; ++e) {
+            volatile T prod = va[e] * xs[ci[e]];
+            ref[i] = e == rp[i] ? T(prod) : T(ref[i] + prod);
+        }
+    bw_thread_rows_blocks<T>(n, rp.data(), ci.data(), va.data(), xs.data(), n, 4, T(-0.0), got.data());
+    bw_thread_rows_blocks<T>(n, rp.data(), ci.data(), va.data(), xs.data(), n, 4, T(0), old.data());
+    for (uint64_t i = 0; i < n; ++i) {
+        const bool both_nan = ref[i] != ref[i] && got[i] != got[i];
+        CHECK(both_nan || std::memcmp(&ref[i], &got[i], sizeof(T)) == 0);
+    }
+    CHECK(std::signbit(ref[0]) && std::signbit(ref[1]) && !std::signbit(ref[2]) && !std::signbit(ref[4]));
+    CHECK(ref[3] == T(2.5) && ref[5] != ref[5] && ref[6] == den);
+    // seeded with +0.0 the rows of -0.0 alone lose their sign -- and only they differ
+    for (uint64_t i = 0; i < n; ++i)
+        CHECK((std::memcmp(&old[i], &got[i], sizeof(T)) != 0) == (i == 0 || i == 1));
+}
+
 static void gpu_tests() {
     // src/csr/conv/coo.rs:128-145
     CooMatrix<double> coo(2, 3);
@@ -89,6 +125,8 @@ static void gpu_tests() {
 int main(int argc, char **argv) {
     const std::string mode = argc > 1 ? argv[1] : "host";
     host_tests();
+    blockwin_rows_tests<double>();
+    blockwin_rows_tests<float>();
     if (mode == "gpu") {
         try { gpu_tests(); } catch (const std::exception &e) { printf("FAIL exception: %s\n", e.what()); ++failures; }
     } else {
