@@ -701,6 +701,77 @@ int spal_csc_krylov_dev_f64(spal_csc_t a, int method, spal_csc_t m, const double
 int spal_csc_krylov_dev_f32(spal_csc_t a, int method, spal_csc_t m, const float *b_dev, float *x_dev,
                             double tol, uint64_t maxit, void *stream, spal_krylov_info *info);
 
+/* ---- A X = B on the device: CG and BiCGStab for a block of k right-hand sides --------------------------
+ * Not in the reference.  ONE call runs k INDEPENDENT iterations in lockstep on shared launches: one pass over the
+ * matrix per product and one walk of the factor's launches per solve serve all k columns.  It is not the block-Krylov
+ * method with a shared search space: every column keeps its own sequential text, so the contract above carries over.
+ * LAYOUT.  B and X are n x k, dense and ROW-MAJOR: element (i, j) at [i * ld + j], ld >= k -- the layout of
+ * spal_*_spmm_* and spal_*_trsm_*; offsets i * ld are 64-bit.  X holds X0 on entry and the result on exit.
+ * COLUMN j IS THE LOOP ABOVE.  Column j follows SPAL_KRYLOV_CG / SPAL_KRYLOV_BICGSTAB as written above, applied to
+ * B[:, j] and X[:, j], with its own bb, thr, scalars, it, stop test, reason and residual_sq.  dot is the dot above
+ * (tiles of 1024 rows) applied to the column.  A v is the value spal_*_spmm_* defines (ascending columns, the first
+ * product assigned, no FMA: the reference's bits).  M^-1 v is column j of spal_*_trsm_*(lower, unit_diag = 1) followed
+ * by spal_*_trsm_*(upper, unit_diag = 0); with m's option "trsv_sweeps" = s >= 0 it is column j of the two
+ * spal_*_trsm_sweep_* calls with s sweeps; with m == NULL it is v.  Hence for every column x, iterations, reason,
+ * residual_sq and rhs_sq are, bit for bit in f32 and f64, what the text gives -- and, on a handle whose SpMV runs a
+ * sequential-order kernel, what spal_*_krylov_* returns for that column.  solve_ms is the call's device time, the same
+ * in all k records.
+ * WHAT THE BITS DO NOT DEPEND ON: k, ldb, ldx, the column tile, "krylov_check_every", what the other columns hold.  A
+ * NaN, an inf or a breakdown in one column never reaches another.
+ * FREEZE, PER COLUMN.  Once column j has stopped, no kernel writes its x, r, p, scalars or it again; BiCGStab's
+ * half-step update is applied to exactly the columns that asked for it; the other columns go on.  The call ends when
+ * every column has stopped, so maxit bounds it.  Products and solves keep running on all k columns, into work blocks:
+ * the work on finished columns is wasted and accepted -- the active columns are not compacted.
+ * PADDING.  X[i, k..ldx) is never written and B[i, k..ldb) is never read.  X and B must not overlap.
+ * SPAL_ERR_INVALID_ARGUMENT before any device work: everything spal_*_krylov_* refuses (null a, b, x or info -- info
+ * points to k records --, a or m not square, shapes, devices or element types of a and m that differ, an _f64 entry on
+ * an f32 handle or the reverse, a method outside the enum, tol negative or NaN); k == 0; ldb < k or ldx < k; the host
+ * forms: b_rows != nrows or x_rows != nrows; x_dev == b_dev.  SPAL_ERR_UNSUPPORTED: a handle held as row blocks.
+ * SPAL_ERR_OUT_OF_MEMORY: no room for the work blocks; nothing leaks.  The messages begin "spal_csr_krylov_block:" /
+ * "spal_csc_krylov_block:".
+ * The _dev forms SYNCHRONISE `stream` (they poll) and are refused on a capturing stream.  Before the first iteration
+ * the call builds what spal_*_krylov_* builds (a's product plan; m's two solve plans, or its sweep preparation), takes
+ * ALL its work blocks (3 / 4 for CG without / with m, 6 / 8 for BiCGStab, n x k each), the dots' scratch and the k
+ * scalar records from the caching allocator in one go, and grows the stream's sweep scratch to n x k per buffer: no
+ * iteration allocates, and nothing synchronises except the polls, which copy the k scalar records to pinned memory and
+ * count the stopped columns.  No handle lock is held across a product or a solve, so calls on one handle from several
+ * threads are safe.  Order between launches comes from the stream alone -- no flags waited on, no spins, no float
+ * atomics, no grid syncs -- so a call cannot hang.  CSC handles multiply through their CSR twin, as SpMM does, and
+ * solve on it.  The host forms copy B and X0 up packed, iterate, and copy the k columns of X back.
+ * Options on `a`: "krylov_check_every" as above, same defaults and meaning.  "krylov_tile": the column tile KT of the
+ * fused vector kernels -- a workgroup covers 1024 rows x KT columns, a wave reads 64 / KT rows x KT columns.  0 =
+ * automatic (the narrowest tile that holds k, at most 32), else one of 1, 2, 4, 8, 16, 32; anything else
+ * SPAL_ERR_INVALID_ARGUMENT.  A block wider than the tile is covered inside each launch.
+ * describe() on `a` gains "krylov_block" after a call: {method, k, preconditioned, precond_sweeps, tile,
+ * iterations_min, iterations_max, converged (columns that ended with reason 0), check_every, polls, solve_ms} of the
+ * last call; "krylov" stays with the vector calls.
+ * Not provided: GMRES on a block (the next step), compaction of finished columns, a true block-Krylov method (shared
+ * search space), capture into a graph, several GPUs. */
+int spal_csr_krylov_block_f64(spal_csr_t a, int method, spal_csr_t m, uint64_t k, const double *b, uint64_t ldb,
+                              uint64_t b_rows, double *x, uint64_t ldx, uint64_t x_rows, double tol, uint64_t maxit,
+                              spal_krylov_info *info);                            /* host blocks; info: k records */
+int spal_csr_krylov_block_f32(spal_csr_t a, int method, spal_csr_t m, uint64_t k, const float *b, uint64_t ldb,
+                              uint64_t b_rows, float *x, uint64_t ldx, uint64_t x_rows, double tol, uint64_t maxit,
+                              spal_krylov_info *info);
+int spal_csr_krylov_block_dev_f64(spal_csr_t a, int method, spal_csr_t m, uint64_t k, const double *b_dev,
+                                  uint64_t ldb, double *x_dev, uint64_t ldx, double tol, uint64_t maxit, void *stream,
+                                  spal_krylov_info *info);                        /* synchronises; info on the host */
+int spal_csr_krylov_block_dev_f32(spal_csr_t a, int method, spal_csr_t m, uint64_t k, const float *b_dev,
+                                  uint64_t ldb, float *x_dev, uint64_t ldx, double tol, uint64_t maxit, void *stream,
+                                  spal_krylov_info *info);
+int spal_csc_krylov_block_f64(spal_csc_t a, int method, spal_csc_t m, uint64_t k, const double *b, uint64_t ldb,
+                              uint64_t b_rows, double *x, uint64_t ldx, uint64_t x_rows, double tol, uint64_t maxit,
+                              spal_krylov_info *info);
+int spal_csc_krylov_block_f32(spal_csc_t a, int method, spal_csc_t m, uint64_t k, const float *b, uint64_t ldb,
+                              uint64_t b_rows, float *x, uint64_t ldx, uint64_t x_rows, double tol, uint64_t maxit,
+                              spal_krylov_info *info);
+int spal_csc_krylov_block_dev_f64(spal_csc_t a, int method, spal_csc_t m, uint64_t k, const double *b_dev,
+                                  uint64_t ldb, double *x_dev, uint64_t ldx, double tol, uint64_t maxit, void *stream,
+                                  spal_krylov_info *info);
+int spal_csc_krylov_block_dev_f32(spal_csc_t a, int method, spal_csc_t m, uint64_t k, const float *b_dev,
+                                  uint64_t ldb, float *x_dev, uint64_t ldx, double tol, uint64_t maxit, void *stream,
+                                  spal_krylov_info *info);
+
 /* ---- A x = b on the device: restarted GMRES(m), right-preconditioned ------------------------------------
  * Not in the reference.  For matrices that are not symmetric, where BiCGStab can break down (on the cyclic shift with
  * b = e0 it returns reason 2 after one iteration; GMRES solves that system in n steps).  The contract is again a

@@ -17,7 +17,7 @@
 //   CsrMatrix<T>::from(coo)  == CsrMatrix::from(&coo)    src/csr/conv/coo.rs:3-116
 //   CscMatrix<T>, CooMatrix<T> likewise                  src/csc.rs, src/coo.rs
 //   a.solve(b, method, M, x0, tol, maxit), dot(a, b)     not in the reference: CG / BiCGStab and their dot product
-//                                                        (include/spal.h, spal_*_krylov_*, spal_dot_*)
+//                                                        (include/spal.h, spal_*_krylov_*, spal_*_krylov_block_*, spal_dot_*)
 //   a.gmres(b, restart, M, x0, tol, maxit)               not in the reference: restarted GMRES (spal_*_gmres_*)
 //   a.colour(seed), a.permute(perm), a.multicolour(seed), p.ordering(), p.to_order(v), p.from_order(v),
 //   colour_greedy(n, rowptr, colind, seed), perm_from_colours(colours)
@@ -74,6 +74,7 @@ template <> struct Abi<double> {
     static constexpr auto csr_trsm = spal_csr_trsm_f64;
     static constexpr auto csr_trsm_sweep = spal_csr_trsm_sweep_f64;
     static constexpr auto csr_krylov = spal_csr_krylov_f64;
+    static constexpr auto csr_krylov_block = spal_csr_krylov_block_f64;
     static constexpr auto csr_gmres = spal_csr_gmres_f64;
     static constexpr auto csr_permute_vec = spal_csr_permute_vec_f64;
     static constexpr auto dot = spal_dot_f64;
@@ -86,6 +87,7 @@ template <> struct Abi<double> {
     static constexpr auto csc_trsm = spal_csc_trsm_f64;
     static constexpr auto csc_trsm_sweep = spal_csc_trsm_sweep_f64;
     static constexpr auto csc_krylov = spal_csc_krylov_f64;
+    static constexpr auto csc_krylov_block = spal_csc_krylov_block_f64;
     static constexpr auto csc_gmres = spal_csc_gmres_f64;
     static constexpr auto csc_permute_vec = spal_csc_permute_vec_f64;
     static constexpr auto coo_to_csr = spal_coo_to_csr_f64;
@@ -101,6 +103,7 @@ template <> struct Abi<float> {
     static constexpr auto csr_trsm = spal_csr_trsm_f32;
     static constexpr auto csr_trsm_sweep = spal_csr_trsm_sweep_f32;
     static constexpr auto csr_krylov = spal_csr_krylov_f32;
+    static constexpr auto csr_krylov_block = spal_csr_krylov_block_f32;
     static constexpr auto csr_gmres = spal_csr_gmres_f32;
     static constexpr auto csr_permute_vec = spal_csr_permute_vec_f32;
     static constexpr auto dot = spal_dot_f32;
@@ -113,6 +116,7 @@ template <> struct Abi<float> {
     static constexpr auto csc_trsm = spal_csc_trsm_f32;
     static constexpr auto csc_trsm_sweep = spal_csc_trsm_sweep_f32;
     static constexpr auto csc_krylov = spal_csc_krylov_f32;
+    static constexpr auto csc_krylov_block = spal_csc_krylov_block_f32;
     static constexpr auto csc_gmres = spal_csc_gmres_f32;
     static constexpr auto csc_permute_vec = spal_csc_permute_vec_f32;
     static constexpr auto coo_to_csr = spal_coo_to_csr_f32;
@@ -143,6 +147,18 @@ struct Solution {
     usize iterations;
     int reason;   // 0 converged (dot(r, r) <= tol^2 dot(b, b)), 1 maxit reached, 2 breakdown / not finite
     double residual_sq, rhs_sq, solve_ms;
+};
+
+// What solve_block returns: X row-major (element (i, j) at i * k + j) and one record per column, as Solution holds one.
+struct ColumnResult {
+    usize iterations;
+    int reason;
+    double residual_sq, rhs_sq, solve_ms;   // solve_ms: the call's time, the same in every column
+};
+template <typename T>
+struct BlockSolution {
+    std::vector<T> x;
+    std::vector<ColumnResult> columns;
 };
 
 // dot(a, b) by the library's definition: products rounded, then the fixed tree over tiles of 1024 (spal_dot_*, host only).
@@ -407,6 +423,27 @@ class CsrMatrix {
         s.residual_sq = info.residual_sq;
         s.rhs_sq = info.rhs_sq;
         s.solve_ms = info.solve_ms;
+        return s;
+    }
+
+    // X with A X = B for a ROW-MAJOR block of k right-hand sides (B.size() == nrows * k): k independent CG / BiCGStab
+    // iterations in lockstep on shared launches (spal_csr_krylov_block_*, include/spal.h).  Column j of the result and
+    // columns[j] are bit for bit solve()'s loop on column j of B, whatever k and the other columns are; a column that has
+    // stopped is frozen while the others run on.  X0 empty: zeros.  Panics as solve() does, and when k == 0 or B / X0
+    // are not nrows x k.
+    BlockSolution<T> solve_block(const std::vector<T> &B, usize k, Method method = Method::Cg, const CsrMatrix *M = nullptr,
+                                 const std::vector<T> &X0 = {}, double tol = 1e-8, usize maxit = 1000) const {
+        check_block("solve_block", B.size(), k);
+        if (!X0.empty() && X0.size() != B.size())
+            throw Panic(SPAL_ERR_INVALID_ARGUMENT, "solve_block: X0.len() = " + std::to_string(X0.size()) +
+                                                       " but B.len() = " + std::to_string(B.size()));
+        BlockSolution<T> s{X0.empty() ? std::vector<T>(B.size(), T(0)) : X0, {}};
+        std::vector<spal_krylov_info> info(k);
+        detail::check(detail::Abi<T>::csr_krylov_block(device_handle(), static_cast<int>(method),
+                                                        M ? M->device_handle() : nullptr, k, B.data(), k, nrows_,
+                                                        s.x.data(), k, nrows_, tol, maxit, info.data()));
+        for (const spal_krylov_info &c : info)
+            s.columns.push_back(ColumnResult{c.iterations, c.reason, c.residual_sq, c.rhs_sq, c.solve_ms});
         return s;
     }
 
@@ -682,6 +719,27 @@ class CscMatrix {
         s.residual_sq = info.residual_sq;
         s.rhs_sq = info.rhs_sq;
         s.solve_ms = info.solve_ms;
+        return s;
+    }
+
+    // X with A X = B for a ROW-MAJOR block of k right-hand sides (B.size() == nrows * k): k independent CG / BiCGStab
+    // iterations in lockstep on shared launches (spal_csc_krylov_block_*, include/spal.h).  Column j of the result and
+    // columns[j] are bit for bit solve()'s loop on column j of B, whatever k and the other columns are; a column that has
+    // stopped is frozen while the others run on.  X0 empty: zeros.  Panics as solve() does, and when k == 0 or B / X0
+    // are not nrows x k.
+    BlockSolution<T> solve_block(const std::vector<T> &B, usize k, Method method = Method::Cg, const CscMatrix *M = nullptr,
+                                 const std::vector<T> &X0 = {}, double tol = 1e-8, usize maxit = 1000) const {
+        check_block("solve_block", B.size(), k);
+        if (!X0.empty() && X0.size() != B.size())
+            throw Panic(SPAL_ERR_INVALID_ARGUMENT, "solve_block: X0.len() = " + std::to_string(X0.size()) +
+                                                       " but B.len() = " + std::to_string(B.size()));
+        BlockSolution<T> s{X0.empty() ? std::vector<T>(B.size(), T(0)) : X0, {}};
+        std::vector<spal_krylov_info> info(k);
+        detail::check(detail::Abi<T>::csc_krylov_block(device_handle(), static_cast<int>(method),
+                                                        M ? M->device_handle() : nullptr, k, B.data(), k, nrows_,
+                                                        s.x.data(), k, nrows_, tol, maxit, info.data()));
+        for (const spal_krylov_info &c : info)
+            s.columns.push_back(ColumnResult{c.iterations, c.reason, c.residual_sq, c.rhs_sq, c.solve_ms});
         return s;
     }
 

@@ -127,6 +127,21 @@ impl<T: HipScalar> DeviceCsr<T> {
         info
     }
 
+    /// X with A X = B for a row-major block of `k` right-hand sides (`b` and `x` hold nrows * k elements, element (i, j)
+    /// at i * k + j; `x` holds X0 on entry): k independent CG / BiCGStab iterations in lockstep on shared launches
+    /// (spal_csr_krylov_block_*).  Column j and record j are bit for bit `solve`'s loop on column j, whatever k and the
+    /// other columns are; a column that has stopped is frozen while the others run on.  Panics as `solve` does, and when
+    /// k == 0 or a block is not nrows x k.
+    pub fn solve_block(&self, method: c_int, m: Option<&DeviceCsr<T>>, k: usize, b: &[T], x: &mut [T], tol: f64, maxit: u64)
+        -> Vec<ffi::spal_krylov_info>
+    where T: HipKrylov {
+        assert!(k > 0 && b.len() % k == 0 && x.len() == b.len());
+        let mut info = vec![ffi::spal_krylov_info::default(); k];
+        let mh = m.map_or(std::ptr::null_mut(), |f| f.h);
+        unsafe { ffi::check(T::csr_krylov_block(self.h, method, mh, k as u64, b, x, tol, maxit, info.as_mut_ptr())); }
+        info
+    }
+
     /// x with A x = b by restarted GMRES(`restart`, 1 ..= 256), right-preconditioned by `m` as `solve` is; for matrices
     /// that are not symmetric.  Bit for bit the text of include/spal.h; reasons 0 and 1 are decided on the true residual.
     pub fn gmres(&self, m: Option<&DeviceCsr<T>>, b: &[T], x: &mut [T], restart: u64, tol: f64, maxit: u64) -> ffi::spal_krylov_info
@@ -382,6 +397,21 @@ impl<T: HipScalar> DeviceCsc<T> {
         let mut info = ffi::spal_krylov_info::default();
         let mh = m.map_or(std::ptr::null_mut(), |f| f.h);
         unsafe { ffi::check(T::csc_krylov(self.h, method, mh, b, x, tol, maxit, &mut info)); }
+        info
+    }
+
+    /// X with A X = B for a row-major block of `k` right-hand sides (`b` and `x` hold nrows * k elements, element (i, j)
+    /// at i * k + j; `x` holds X0 on entry): k independent CG / BiCGStab iterations in lockstep on shared launches
+    /// (spal_csc_krylov_block_*).  Column j and record j are bit for bit `solve`'s loop on column j, whatever k and the
+    /// other columns are; a column that has stopped is frozen while the others run on.  Panics as `solve` does, and when
+    /// k == 0 or a block is not nrows x k.
+    pub fn solve_block(&self, method: c_int, m: Option<&DeviceCsc<T>>, k: usize, b: &[T], x: &mut [T], tol: f64, maxit: u64)
+        -> Vec<ffi::spal_krylov_info>
+    where T: HipKrylov {
+        assert!(k > 0 && b.len() % k == 0 && x.len() == b.len());
+        let mut info = vec![ffi::spal_krylov_info::default(); k];
+        let mh = m.map_or(std::ptr::null_mut(), |f| f.h);
+        unsafe { ffi::check(T::csc_krylov_block(self.h, method, mh, k as u64, b, x, tol, maxit, info.as_mut_ptr())); }
         info
     }
 

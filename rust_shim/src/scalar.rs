@@ -164,6 +164,12 @@ pub trait HipKrylov: Sized {
     unsafe fn csc_krylov(a: *mut ffi::spal_csc, method: c_int, m: *mut ffi::spal_csc, b: &[Self], x: &mut [Self], tol: f64,
                          maxit: u64, info: *mut ffi::spal_krylov_info) -> c_int;
     unsafe fn dot(a: &[Self], b: &[Self], out: *mut Self) -> c_int;
+    /// the same two loops on a row-major block of k right-hand sides (the spal_*_krylov_block_* entry points): `b` and
+    /// `x` hold nrows * k elements, element (i, j) at i * k + j; `info` points to k records
+    unsafe fn csr_krylov_block(a: *mut ffi::spal_csr, method: c_int, m: *mut ffi::spal_csr, k: u64, b: &[Self], x: &mut [Self],
+                               tol: f64, maxit: u64, info: *mut ffi::spal_krylov_info) -> c_int;
+    unsafe fn csc_krylov_block(a: *mut ffi::spal_csc, method: c_int, m: *mut ffi::spal_csc, k: u64, b: &[Self], x: &mut [Self],
+                               tol: f64, maxit: u64, info: *mut ffi::spal_krylov_info) -> c_int;
     /// restarted GMRES (the spal_*_gmres_* entry points): `restart` is 1 ..= 256
     unsafe fn csr_gmres(a: *mut ffi::spal_csr, m: *mut ffi::spal_csr, b: &[Self], x: &mut [Self], restart: u64, tol: f64,
                         maxit: u64, info: *mut ffi::spal_krylov_info) -> c_int;
@@ -172,8 +178,19 @@ pub trait HipKrylov: Sized {
 }
 
 macro_rules! impl_hip_krylov {
-    ($t:ty, $csr_krylov:ident, $csc_krylov:ident, $dot:ident, $csr_gmres:ident, $csc_gmres:ident) => {
+    ($t:ty, $csr_krylov:ident, $csc_krylov:ident, $dot:ident, $csr_gmres:ident, $csc_gmres:ident, $csr_block:ident,
+     $csc_block:ident) => {
         impl HipKrylov for $t {
+            unsafe fn csr_krylov_block(a: *mut ffi::spal_csr, method: c_int, m: *mut ffi::spal_csr, k: u64, b: &[Self],
+                                       x: &mut [Self], tol: f64, maxit: u64, info: *mut ffi::spal_krylov_info) -> c_int {
+                let (br, xr) = (if k > 0 { b.len() as u64 / k } else { 0 }, if k > 0 { x.len() as u64 / k } else { 0 });
+                ffi::$csr_block(a, method, m, k, b.as_ptr(), k, br, x.as_mut_ptr(), k, xr, tol, maxit, info)
+            }
+            unsafe fn csc_krylov_block(a: *mut ffi::spal_csc, method: c_int, m: *mut ffi::spal_csc, k: u64, b: &[Self],
+                                       x: &mut [Self], tol: f64, maxit: u64, info: *mut ffi::spal_krylov_info) -> c_int {
+                let (br, xr) = (if k > 0 { b.len() as u64 / k } else { 0 }, if k > 0 { x.len() as u64 / k } else { 0 });
+                ffi::$csc_block(a, method, m, k, b.as_ptr(), k, br, x.as_mut_ptr(), k, xr, tol, maxit, info)
+            }
             unsafe fn csr_krylov(a: *mut ffi::spal_csr, method: c_int, m: *mut ffi::spal_csr, b: &[Self], x: &mut [Self],
                                  tol: f64, maxit: u64, info: *mut ffi::spal_krylov_info) -> c_int {
                 ffi::$csr_krylov(a, method, m, b.as_ptr(), b.len() as u64, x.as_mut_ptr(), x.len() as u64, tol, maxit, info)
@@ -196,8 +213,10 @@ macro_rules! impl_hip_krylov {
         }
     };
 }
-impl_hip_krylov!(f64, spal_csr_krylov_f64, spal_csc_krylov_f64, spal_dot_f64, spal_csr_gmres_f64, spal_csc_gmres_f64);
-impl_hip_krylov!(f32, spal_csr_krylov_f32, spal_csc_krylov_f32, spal_dot_f32, spal_csr_gmres_f32, spal_csc_gmres_f32);
+impl_hip_krylov!(f64, spal_csr_krylov_f64, spal_csc_krylov_f64, spal_dot_f64, spal_csr_gmres_f64, spal_csc_gmres_f64,
+                 spal_csr_krylov_block_f64, spal_csc_krylov_block_f64);
+impl_hip_krylov!(f32, spal_csr_krylov_f32, spal_csc_krylov_f32, spal_dot_f32, spal_csr_gmres_f32, spal_csc_gmres_f32,
+                 spal_csr_krylov_block_f32, spal_csc_krylov_block_f32);
 
 /// dot(a, b) by the library's definition (include/spal.h): products rounded, then the fixed tree over tiles of 1024.
 pub fn dot<T: HipKrylov + Default>(a: &[T], b: &[T]) -> T {

@@ -1,7 +1,9 @@
-// krylov_kernels.hpp -- what spal_krylov.hip (the dot product, CG, BiCGStab: DESIGN 3.14) and spal_gmres.hip (GMRES:
-// DESIGN 3.17) share: the tile sum and the upper levels of reduce(), the sizes of a dot's scratch, the entry points a
-// driver goes through by handle and element type, the preparation of the plans, M^-1, the refusals that need no device
-// and two scope guards.  The contracts are written out in include/spal.h.  (Not installed.)
+// krylov_kernels.hpp -- what spal_krylov.hip (the dot product, CG, BiCGStab: DESIGN 3.14), spal_krylov_block.hip (the
+// same two loops on a block of right-hand sides: DESIGN 3.22) and spal_gmres.hip (GMRES: DESIGN 3.17) share: the tile
+// sum and the upper levels of reduce(), the scalar block, the fused vector updates and the scalar steps of CG and
+// BiCGStab, the sizes of a dot's scratch, the entry points a driver goes through by handle and element type, the
+// preparation of the plans, M^-1, the refusals that need no device and two scope guards.  The contracts are written
+// out in include/spal.h.  (Not installed.)
 #pragma once
 
 #include "spal_ops.hpp"
@@ -59,6 +61,155 @@ __device__ T upper_levels(T *part, uint64_t c1, T *lds) {
         m = c;
     }
     return in[0];
+}
+
+// ---- what the vector loops (spal_krylov.hip) and the block loops (spal_krylov_block.hip) share on the device ----------
+// The scalars of one call -- of one column of a block call --, on the device; the host reads a copy in pinned memory
+// when it polls.
+template <typename T>
+struct Scal {
+    T rr, bb, thr, rz, alpha, beta, omega, rho;
+    unsigned long long it;
+    unsigned done, reason, half, pad;
+};
+
+// ---- the first level, fused with the vector update in front of it ---------------------------------------------------
+enum VecOp {
+    V_DOT,      // d0 = a . b
+    V_DOT2,     // d0 = a . b, d1 = a . a
+    V_INIT,     // y = a - b;  d0 = y . y, d1 = a . a                                   (r = b - q;  rr, bb)
+    V_COPY_DOT, // y = b;  d0 = a . b                                                   (p = z;  rz)
+    V_CG_XR,    // x += alpha * a;  y -= alpha * b;  d0 = y . y                         (x, r;  rr)
+    V_CG_P,     // y = a + beta * y                                                     (p = z + beta p)
+    V_BI_P,     // y = a + beta * (y - omega * b)                                       (p = r + beta (p - omega v))
+    V_BI_S,     // y = a - alpha * b;  d0 = y . y                                       (s = r - alpha v;  ss)
+    V_BI_HALF,  // only when `half`:  x += alpha * a;  y = b                            (x += alpha ph;  r = s)
+    V_BI_XR,    // x = (x + alpha * a) + omega * b;  y = c - omega * d;  d0 = y . y      (x, r;  rr)
+};
+template <int OP> struct Dots { static constexpr int n = (OP == V_CG_P || OP == V_BI_P || OP == V_BI_HALF) ? 0 : (OP == V_DOT2 || OP == V_INIT) ? 2 : 1; };
+
+// What update OP reads and writes of an element, and its arithmetic on the values alone: x and y come in as loaded (or
+// as anything, where OP does not read them) and go out as what OP stores.  p0 / p1: the element's products for d0 / d1.
+template <int OP> struct Reads {
+    static constexpr bool c = OP == V_BI_XR, d = OP == V_BI_XR;
+    static constexpr bool x = OP == V_CG_XR || OP == V_BI_HALF || OP == V_BI_XR;
+    static constexpr bool y = OP == V_CG_XR || OP == V_CG_P || OP == V_BI_P;
+    static constexpr bool b = OP != V_CG_P;   // every OP reads a
+};
+template <int OP> struct Writes {
+    static constexpr bool x = Reads<OP>::x;
+    static constexpr bool y = OP != V_DOT && OP != V_DOT2;
+};
+template <typename T, int OP>
+__device__ __forceinline__ void vec_value(T a, T b, T c, T d, T &x, T &y, T alpha, T beta, T omega, T &p0, T &p1) {
+    if (OP == V_DOT) {
+        p0 = a * b;
+    } else if (OP == V_DOT2) {
+        p0 = a * b;
+        p1 = a * a;
+    } else if (OP == V_INIT) {
+        y = a - b;
+        p0 = y * y;
+        p1 = a * a;
+    } else if (OP == V_COPY_DOT) {
+        p0 = a * b;
+        y = b;
+    } else if (OP == V_CG_XR) {
+        x = x + alpha * a;
+        y = y - alpha * b;
+        p0 = y * y;
+    } else if (OP == V_CG_P) {
+        y = a + beta * y;
+    } else if (OP == V_BI_P) {
+        y = a + beta * (y - omega * b);
+    } else if (OP == V_BI_S) {
+        y = a - alpha * b;
+        p0 = y * y;
+    } else if (OP == V_BI_HALF) {
+        x = x + alpha * a;
+        y = b;
+    } else if (OP == V_BI_XR) {
+        x = (x + alpha * a) + omega * b;
+        y = c - omega * d;
+        p0 = y * y;
+    }
+}
+
+// One element of update OP through memory: every pointer is AT the element (of a vector, or of a column of a row-major
+// block), and the ones OP does not name are never dereferenced.  Nothing is __restrict__, and nothing needs to be: two
+// operands are either the same array (z is r, ph is p, sh is s -- all of them only read) or disjoint, and an element's
+// update touches that element's index alone, so loading everything before the first store changes nothing.
+template <typename T, int OP>
+__device__ __forceinline__ void vec_update(const T *a, const T *b, const T *c, const T *d, T *x, T *y, T alpha, T beta,
+                                           T omega, T &p0, T &p1) {
+    const T av = *a, bv = Reads<OP>::b ? *b : T(0), cv = Reads<OP>::c ? *c : T(0), dv = Reads<OP>::d ? *d : T(0);
+    T xv = Reads<OP>::x ? *x : T(0), yv = Reads<OP>::y ? *y : T(0);
+    vec_value<T, OP>(av, bv, cv, dv, xv, yv, alpha, beta, omega, p0, p1);
+    if (Writes<OP>::x) *x = xv;
+    if (Writes<OP>::y) *y = yv;
+}
+
+// ---- the scalar step that follows a dot: thread 0 of the launch that walked the upper levels --------------------------
+enum FinOp { F_STORE, F_INIT, F_RZ, F_ALPHA_CG, F_TEST_CG, F_BETA, F_RHO, F_ALPHA_BI, F_HALF, F_OMEGA, F_TEST_BI };
+
+template <typename T>
+__device__ __forceinline__ void stop_test(Scal<T> *s, T rr, uint64_t maxit) {
+    s->rr = rr;
+    if (rr <= s->thr) {
+        s->done = 1;
+        s->reason = 0;
+    } else if (!isfinite(rr)) {
+        s->done = 1;
+        s->reason = 2;
+    } else if (s->it == maxit) {
+        s->done = 1;
+        s->reason = 1;
+    }
+}
+
+// d0 / d1: the dots the launch finished; tol2 = T(tol * tol); unpreconditioned (F_TEST_CG): z is r, so rz1 = rr and beta
+// follows here
+template <typename T, int OP>
+__device__ __forceinline__ void scalar_step(Scal<T> *s, T d0, T d1, T tol2, uint64_t maxit, int unpreconditioned) {
+    if (OP == F_INIT) {
+        s->bb = d1;
+        s->thr = tol2 * d1;
+        s->it = 0;
+        s->rho = s->alpha = s->omega = T(1);
+        stop_test<T>(s, d0, maxit);
+    } else if (OP == F_RZ) {
+        s->rz = d0;
+    } else if (OP == F_ALPHA_CG) {
+        s->alpha = s->rz / d0;
+    } else if (OP == F_TEST_CG) {
+        s->it += 1;
+        stop_test<T>(s, d0, maxit);
+        if (unpreconditioned && !s->done) {
+            s->beta = d0 / s->rz;
+            s->rz = d0;
+        }
+    } else if (OP == F_BETA) {
+        s->beta = d0 / s->rz;
+        s->rz = d0;
+    } else if (OP == F_RHO) {
+        s->beta = (d0 / s->rho) * (s->alpha / s->omega);
+        s->rho = d0;
+    } else if (OP == F_ALPHA_BI) {
+        s->alpha = s->rho / d0;
+    } else if (OP == F_HALF) {
+        s->it += 1;
+        const bool small = d0 <= s->thr;
+        if (small || !isfinite(d0)) {
+            s->rr = d0;
+            s->reason = small ? 0 : 2;
+            s->half = 1;
+            s->done = 1;
+        }
+    } else if (OP == F_OMEGA) {
+        s->omega = d0 / d1;
+    } else if (OP == F_TEST_BI) {
+        stop_test<T>(s, d0, maxit);
+    }
 }
 
 inline uint64_t tiles_of(uint64_t n) { return std::max<uint64_t>(1, (n + kTile - 1) / kTile); }

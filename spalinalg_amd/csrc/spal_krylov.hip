@@ -4,7 +4,8 @@
 // the same way.  The order depends on n alone, so every kernel here returns the bits of the sequential text.
 //
 // (tile_sum, upper_levels, the scratch sizes, the plan preparation, M^-1 and the shared refusals are in krylov_kernels.hpp,
-// which spal_gmres.hip includes too.)
+// which spal_gmres.hip includes too; so are the scalar block Scal, the fused updates VecOp / vec_update and the scalar
+// steps FinOp / scalar_step, which spal_krylov_block.hip runs per column of a block of right-hand sides.)
 //
 // ONE TILE IS ONE TRIP OF A WORKGROUP OF 256.  Thread t holds elements t, t + 256, t + 512, t + 768: strides 512 and 256
 // are thread-local ((v0 + v2) + (v1 + v3)), strides 128 and 64 go through LDS, strides 32 .. 1 are __shfl_down inside
@@ -33,29 +34,6 @@
 namespace spal {
 namespace {
 
-// The scalars of one call, on the device; the host reads a copy in pinned memory when it polls.
-template <typename T>
-struct Scal {
-    T rr, bb, thr, rz, alpha, beta, omega, rho;
-    unsigned long long it;
-    unsigned done, reason, half, pad;
-};
-
-// ---- the first level, fused with the vector update in front of it ---------------------------------------------------
-enum VecOp {
-    V_DOT,      // d0 = a . b
-    V_DOT2,     // d0 = a . b, d1 = a . a
-    V_INIT,     // y = a - b;  d0 = y . y, d1 = a . a                                   (r = b - q;  rr, bb)
-    V_COPY_DOT, // y = b;  d0 = a . b                                                   (p = z;  rz)
-    V_CG_XR,    // x += alpha * a;  y -= alpha * b;  d0 = y . y                         (x, r;  rr)
-    V_CG_P,     // y = a + beta * y                                                     (p = z + beta p)
-    V_BI_P,     // y = a + beta * (y - omega * b)                                       (p = r + beta (p - omega v))
-    V_BI_S,     // y = a - alpha * b;  d0 = y . y                                       (s = r - alpha v;  ss)
-    V_BI_HALF,  // only when `half`:  x += alpha * a;  y = b                            (x += alpha ph;  r = s)
-    V_BI_XR,    // x = (x + alpha * a) + omega * b;  y = c - omega * d;  d0 = y . y      (x, r;  rr)
-};
-template <int OP> struct Dots { static constexpr int n = (OP == V_CG_P || OP == V_BI_P || OP == V_BI_HALF) ? 0 : (OP == V_DOT2 || OP == V_INIT) ? 2 : 1; };
-
 // Nothing is __restrict__: without a preconditioner z is r, ph is p and sh is s.
 template <typename T>
 struct VecArgs {
@@ -71,44 +49,7 @@ __device__ __forceinline__ void element(const VecArgs<T> &g, uint64_t i, T alpha
     p0 = T(0);
     p1 = T(0);
     if (i >= g.n) return;   // the padding: +0.0, and it is added
-    if (OP == V_DOT) {
-        p0 = g.a[i] * g.b[i];
-    } else if (OP == V_DOT2) {
-        const T a = g.a[i];
-        p0 = a * g.b[i];
-        p1 = a * a;
-    } else if (OP == V_INIT) {
-        const T b = g.a[i];
-        const T r = b - g.b[i];
-        g.y[i] = r;
-        p0 = r * r;
-        p1 = b * b;
-    } else if (OP == V_COPY_DOT) {
-        const T z = g.b[i];
-        p0 = g.a[i] * z;
-        g.y[i] = z;
-    } else if (OP == V_CG_XR) {
-        g.x[i] = g.x[i] + alpha * g.a[i];
-        const T r = g.y[i] - alpha * g.b[i];
-        g.y[i] = r;
-        p0 = r * r;
-    } else if (OP == V_CG_P) {
-        g.y[i] = g.a[i] + beta * g.y[i];
-    } else if (OP == V_BI_P) {
-        g.y[i] = g.a[i] + beta * (g.y[i] - omega * g.b[i]);
-    } else if (OP == V_BI_S) {
-        const T s = g.a[i] - alpha * g.b[i];
-        g.y[i] = s;
-        p0 = s * s;
-    } else if (OP == V_BI_HALF) {
-        g.x[i] = g.x[i] + alpha * g.a[i];
-        g.y[i] = g.b[i];
-    } else if (OP == V_BI_XR) {
-        g.x[i] = (g.x[i] + alpha * g.a[i]) + omega * g.b[i];
-        const T r = g.c[i] - omega * g.d[i];
-        g.y[i] = r;
-        p0 = r * r;
-    }
+    vec_update<T, OP>(g.a + i, g.b + i, g.c + i, g.d + i, g.x + i, g.y + i, alpha, beta, omega, p0, p1);
 }
 
 template <typename T, int OP>
@@ -138,8 +79,6 @@ __global__ __launch_bounds__(kThreads) void vec(VecArgs<T> g, uint64_t tiles) {
 }
 
 // ---- the upper levels (upper_levels, krylov_kernels.hpp) and the scalars, one workgroup --------------------------------
-enum FinOp { F_STORE, F_INIT, F_RZ, F_ALPHA_CG, F_TEST_CG, F_BETA, F_RHO, F_ALPHA_BI, F_HALF, F_OMEGA, F_TEST_BI };
-
 template <typename T>
 struct FinArgs {
     Scal<T> *s;
@@ -150,21 +89,6 @@ struct FinArgs {
     T *out;            // F_STORE
     int unpreconditioned;   // F_TEST_CG: z is r, so rz1 = rr and beta follows here
 };
-
-template <typename T>
-__device__ __forceinline__ void stop_test(Scal<T> *s, T rr, uint64_t maxit) {
-    s->rr = rr;
-    if (rr <= s->thr) {
-        s->done = 1;
-        s->reason = 0;
-    } else if (!isfinite(rr)) {
-        s->done = 1;
-        s->reason = 2;
-    } else if (s->it == maxit) {
-        s->done = 1;
-        s->reason = 1;
-    }
-}
 
 template <typename T, int OP>
 __global__ __launch_bounds__(kThreads) void finish(FinArgs<T> g) {
@@ -178,47 +102,10 @@ __global__ __launch_bounds__(kThreads) void finish(FinArgs<T> g) {
     T d1 = T(0);
     if (OP == F_INIT || OP == F_OMEGA) d1 = upper_levels<T>(g.part1, g.c1, lds);
     if (threadIdx.x != 0) return;
-    if (OP == F_STORE) {
+    if (OP == F_STORE)
         *g.out = d0;
-    } else if (OP == F_INIT) {
-        s->bb = d1;
-        s->thr = g.tol2 * d1;
-        s->it = 0;
-        s->rho = s->alpha = s->omega = T(1);
-        stop_test<T>(s, d0, g.maxit);
-    } else if (OP == F_RZ) {
-        s->rz = d0;
-    } else if (OP == F_ALPHA_CG) {
-        s->alpha = s->rz / d0;
-    } else if (OP == F_TEST_CG) {
-        s->it += 1;
-        stop_test<T>(s, d0, g.maxit);
-        if (g.unpreconditioned && !s->done) {
-            s->beta = d0 / s->rz;
-            s->rz = d0;
-        }
-    } else if (OP == F_BETA) {
-        s->beta = d0 / s->rz;
-        s->rz = d0;
-    } else if (OP == F_RHO) {
-        s->beta = (d0 / s->rho) * (s->alpha / s->omega);
-        s->rho = d0;
-    } else if (OP == F_ALPHA_BI) {
-        s->alpha = s->rho / d0;
-    } else if (OP == F_HALF) {
-        s->it += 1;
-        const bool small = d0 <= s->thr;
-        if (small || !isfinite(d0)) {
-            s->rr = d0;
-            s->reason = small ? 0 : 2;
-            s->half = 1;
-            s->done = 1;
-        }
-    } else if (OP == F_OMEGA) {
-        s->omega = d0 / d1;
-    } else if (OP == F_TEST_BI) {
-        stop_test<T>(s, d0, g.maxit);
-    }
+    else
+        scalar_step<T, OP>(s, d0, d1, g.tol2, g.maxit, g.unpreconditioned);
 }
 
 // ---- host side of the launches --------------------------------------------------------------------------------------

@@ -415,6 +415,35 @@ class _DeviceMatrix:
                                                          C.c_double(tol), u64(maxit), _stream_ptr(stream), C.byref(info)))
         return _krylov_info(info)
 
+    def krylov_block(self, B, method="cg", M=None, X0=None, tol: float = 1e-8, maxit: int = 1000):
+        """Solves A X = B for a host block B of shape (n, k) by CG or BiCGStab: k independent iterations in lockstep on
+        shared launches (spal_*_krylov_block_*).  Column j is, bit for bit, the loop of include/spal.h on
+        B[:, j] with SpMM's products and the block solves as M^-1; a column that has stopped is frozen while the others
+        run on.  Returns (X, [KrylovInfo] * k)."""
+        B = self._block(B, "krylov_block")
+        n, k = B.shape
+        X = np.zeros_like(B) if X0 is None else np.array(X0, dtype=B.dtype, order="C", copy=True)
+        if X.shape != B.shape:
+            raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT, f"krylov_block: X0 has shape {X.shape} but B {B.shape}")
+        if M is not None and type(M) is not type(self):
+            raise TypeError(f"M must be a {type(self).__name__} (the factor of a matrix of the same format)")
+        infos = (_KrylovInfoC * max(k, 1))()
+        check(self._fn(f"krylov_block_{_sfx(B.dtype)}")(self._h, C.c_int(_krylov_method(method)),
+                                                        M._h if M is not None else None, u64(k), _p(B), u64(k), u64(n),
+                                                        _p(X), u64(k), u64(n), C.c_double(tol), u64(maxit), infos))
+        return X, [_krylov_info(c) for c in infos[:k]]
+
+    def krylov_block_dev(self, k: int, b_ptr: int, ldb: int, x_ptr: int, ldx: int, method="cg", M=None,
+                         tol: float = 1e-8, maxit: int = 1000, stream=None):
+        """Device pointers of row-major blocks (element (i, j) at i * ld + j): X holds X0 on entry and the result on
+        exit; the call polls, so it synchronises `stream`.  Returns the k KrylovInfo records."""
+        infos = (_KrylovInfoC * max(int(k), 1))()
+        check(self._fn(f"krylov_block_dev_{_sfx(self.dtype)}")(self._h, C.c_int(_krylov_method(method)),
+                                                               M._h if M is not None else None, u64(k), vp(b_ptr),
+                                                               u64(ldb), vp(x_ptr), u64(ldx), C.c_double(tol), u64(maxit),
+                                                               _stream_ptr(stream), infos))
+        return [_krylov_info(c) for c in infos[:int(k)]]
+
     def gmres(self, b, M=None, x0=None, restart: int = 30, tol: float = 1e-8, maxit: int = 1000):
         """Solves A x = b by restarted GMRES(restart) on the device (spal_*_gmres_*), right-preconditioned
         by `M` as krylov() is (an ILU(0) factor handle of this class: two solves, or "trsv_sweeps" sweeps per triangle).
@@ -1006,6 +1035,32 @@ class _Compressed:
                 raise TypeError("precond_sweeps needs M, the factor it is an option of")
             M.device(device).set_option("trsv_sweeps", int(precond_sweeps))
         return self.device(device).krylov(b, method, None if M is None else M.device(device), x0, tol, maxit)
+
+    def solve_block(self, B, method="cg", M=None, X0=None, tol: float = 1e-8, maxit: int = 1000, device: int = 0,
+                    precond_sweeps=None):
+        """X with A X = B for a block of right-hand sides B of shape (n, k): k independent CG / BiCGStab iterations run
+        in lockstep, one pass over the matrix per product and one walk of M's launches per solve for all k columns
+        (spal_*_krylov_block_*, DESIGN 3.22).  Returns (X, infos), infos a list of k records as solve() returns one;
+        column j of X and infos[j] are bit for bit the loop of include/spal.h on B[:, j], whatever k, the other
+        columns or the options are.  `M` and `precond_sweeps` as in solve(), which keeps taking one 1-D right-hand
+        side.  A matrix that is not square, a B that is not 2-D or has another first dimension than n and an X0 of
+        another shape than B are refused before any device copy is made."""
+        B = np.asarray(B)
+        if self._nrows != self._ncols:
+            raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT,
+                        f"solve_block: the matrix is not square ({self._nrows} x {self._ncols})")
+        if B.ndim != 2 or B.shape[0] != self._nrows:
+            raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT,
+                        f"solve_block: B has shape {B.shape} but the matrix has {self._nrows} rows")
+        if X0 is not None and np.shape(X0) != B.shape:
+            raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT, f"solve_block: X0 has shape {np.shape(X0)} but B {B.shape}")
+        if M is not None and type(M) is not type(self):
+            raise TypeError(f"M must be a {type(self).__name__}, e.g. self.ilu0()")
+        if precond_sweeps is not None:
+            if M is None:
+                raise TypeError("precond_sweeps needs M, the factor it is an option of")
+            M.device(device).set_option("trsv_sweeps", int(precond_sweeps))
+        return self.device(device).krylov_block(B, method, None if M is None else M.device(device), X0, tol, maxit)
 
     def gmres(self, b, M=None, x0=None, restart: int = 30, tol: float = 1e-8, maxit: int = 1000, device: int = 0,
               precond_sweeps=None):
