@@ -745,8 +745,8 @@ int spal_csc_krylov_dev_f32(spal_csc_t a, int method, spal_csc_t m, const float 
  * describe() on `a` gains "krylov_block" after a call: {method, k, preconditioned, precond_sweeps, tile,
  * iterations_min, iterations_max, converged (columns that ended with reason 0), check_every, polls, solve_ms} of the
  * last call; "krylov" stays with the vector calls.
- * Not provided: GMRES on a block (the next step), compaction of finished columns, a true block-Krylov method (shared
- * search space), capture into a graph, several GPUs. */
+ * Not provided: compaction of finished columns, a true block-Krylov method (shared search space), capture into a
+ * graph, several GPUs.  GMRES on a block has its own entry points below. */
 int spal_csr_krylov_block_f64(spal_csr_t a, int method, spal_csr_t m, uint64_t k, const double *b, uint64_t ldb,
                               uint64_t b_rows, double *x, uint64_t ldx, uint64_t x_rows, double tol, uint64_t maxit,
                               spal_krylov_info *info);                            /* host blocks; info: k records */
@@ -841,6 +841,78 @@ int spal_csc_gmres_dev_f64(spal_csc_t a, spal_csc_t m, const double *b_dev, doub
                            double tol, uint64_t maxit, void *stream, spal_krylov_info *info);
 int spal_csc_gmres_dev_f32(spal_csc_t a, spal_csc_t m, const float *b_dev, float *x_dev, uint64_t restart,
                            double tol, uint64_t maxit, void *stream, spal_krylov_info *info);
+
+/* ---- A X = B on the device: restarted GMRES(m) for a block of k right-hand sides --------------------------
+ * Not in the reference.  ONE call runs k INDEPENDENT restarted GMRES iterations in lockstep on shared launches: one pass
+ * over the matrix per product and one walk of the factor's launches per solve serve all k columns.  It is not block
+ * GMRES with a shared Krylov space: every column keeps the sequential text above.
+ * LAYOUT.  B and X are n x k, dense and ROW-MAJOR: element (i, j) at [i * ld + j], ld >= k, offsets i * ld 64-bit.  X
+ * holds X0 on entry and the result on exit.
+ * COLUMN j IS THE GMRES TEXT, as written above, applied to B[:, j] and X[:, j], with its own bb, thr, it, jj, h, c, cs,
+ * sn, g, H, y, stop test, reason and residual_sq.  dot is the header's dot on the column.  A v is the value
+ * spal_*_spmm_* defines.  M^-1 v is column j of spal_*_trsm_*(lower, unit_diag = 1) followed by spal_*_trsm_*(upper,
+ * unit_diag = 0); with m's option "trsv_sweeps" = s >= 0 it is column j of the two spal_*_trsm_sweep_* calls; with
+ * m == NULL it is v.  Hence x, iterations, reason, residual_sq and rhs_sq of every column are, bit for bit in f32 and
+ * f64, what the text gives for that column -- and, on a handle whose SpMV sums rows in sequence, what spal_*_gmres_*
+ * returns for it.  solve_ms is the call's device time, the same in all k records.
+ * CYCLES ARE COMMON TO THE BLOCK.  All columns that have not stopped begin a cycle together.  Inside the cycle a
+ * column takes inner steps until its own text ends its cycle (est <= thr, it == maxit or jj == restart); after that it
+ * idles -- no kernel writes anything of it -- until every column still running has ended its cycle.  Then the back
+ * substitution, the update of x and the head of the next cycle run for all of them together.  Idling changes no bit of
+ * a column's text.  A column that stops is frozen for the rest of the call; the call ends when all k columns have
+ * stopped, and every common cycle advances every running column by at least one iteration, so maxit bounds it.
+ * Products and solves keep running on all k columns, into work blocks: the steps spent on idle and frozen columns are
+ * wasted and accepted -- the columns are not compacted.
+ * WHAT THE BITS DO NOT DEPEND ON: k, ldb, ldx, the column tile, "krylov_check_every", the batch of basis blocks, what
+ * the other columns hold.  A NaN, an inf, a breakdown or a lucky breakdown in one column never reaches another; on a
+ * lucky breakdown v_{j+1} of that column is NaN and is never read.
+ * PADDING.  X[i, k..ldx) is never written and B[i, k..ldb) is never read.  X and B must not overlap.
+ * SPAL_ERR_INVALID_ARGUMENT before any device work: everything spal_*_gmres_* refuses, restart == 0 and restart > 256
+ * included (info points to k records); k == 0; ldb < k or ldx < k; the host forms: b_rows != nrows or x_rows != nrows;
+ * x_dev == b_dev.  SPAL_ERR_UNSUPPORTED: a handle held as row blocks.  SPAL_ERR_OUT_OF_MEMORY: no room for the basis
+ * (the message names the number of blocks, n, k and the bytes); nothing leaks.  The messages begin
+ * "spal_csr_gmres_block:" / "spal_csc_gmres_block:".
+ * The _dev forms SYNCHRONISE `stream` (they poll) and are refused on a capturing stream.  Before the first step the
+ * call builds what spal_*_gmres_* builds, takes the basis (restart + 1 blocks of n x k), w, q and with m also z and u
+ * in ONE block on 256-byte strides with packed leading dimension k -- so the products and solves take v_j and w
+ * directly --, the dots' scratch and the k scalar records, and grows the stream's sweep scratch to n x k per buffer:
+ * no iteration allocates.  The host polls every "krylov_check_every" inner steps, when its count reaches restart (or
+ * the steps that bring the column with the fewest iterations to maxit), and after a head that follows an early end; a
+ * poll copies the k heads of the scalar records to pinned memory and decides "all stopped" and "every running column
+ * has ended its cycle".  No handle lock is held across a product or a solve.  Order between launches comes from the
+ * stream alone -- no flags waited on, no spins, no float atomics, no grid syncs.  CSC handles multiply and solve on
+ * their CSR twin.  The host forms copy B and X0 up packed, iterate, and copy the k columns of X back.
+ * Options on `a`: "krylov_check_every" and "krylov_tile", with the meaning and defaults they have above.
+ * describe() on `a` gains "gmres_block" after a call: {restart, k, preconditioned, precond_sweeps, tile,
+ * iterations_min, iterations_max, cycles (common cycles), steps (inner steps the host enqueued: steps * k - the sum of
+ * the iterations is the idle and wasted work), converged (columns that ended with reason 0), check_every, polls,
+ * dot_batch (basis blocks per batch), basis_bytes, solve_ms}; "gmres" and "krylov_block" stay with their own calls.
+ * Not provided: compaction of finished or idle columns, per-column cycles out of step, a shared search space, flexible
+ * GMRES, capture into a graph, several GPUs. */
+int spal_csr_gmres_block_f64(spal_csr_t a, spal_csr_t m, uint64_t k, const double *b, uint64_t ldb, uint64_t b_rows,
+                             double *x, uint64_t ldx, uint64_t x_rows, uint64_t restart, double tol, uint64_t maxit,
+                             spal_krylov_info *info);
+int spal_csr_gmres_block_f32(spal_csr_t a, spal_csr_t m, uint64_t k, const float *b, uint64_t ldb, uint64_t b_rows,
+                             float *x, uint64_t ldx, uint64_t x_rows, uint64_t restart, double tol, uint64_t maxit,
+                             spal_krylov_info *info);
+int spal_csr_gmres_block_dev_f64(spal_csr_t a, spal_csr_t m, uint64_t k, const double *b_dev, uint64_t ldb,
+                                 double *x_dev, uint64_t ldx, uint64_t restart, double tol, uint64_t maxit, void *stream,
+                                 spal_krylov_info *info);
+int spal_csr_gmres_block_dev_f32(spal_csr_t a, spal_csr_t m, uint64_t k, const float *b_dev, uint64_t ldb,
+                                 float *x_dev, uint64_t ldx, uint64_t restart, double tol, uint64_t maxit, void *stream,
+                                 spal_krylov_info *info);
+int spal_csc_gmres_block_f64(spal_csc_t a, spal_csc_t m, uint64_t k, const double *b, uint64_t ldb, uint64_t b_rows,
+                             double *x, uint64_t ldx, uint64_t x_rows, uint64_t restart, double tol, uint64_t maxit,
+                             spal_krylov_info *info);
+int spal_csc_gmres_block_f32(spal_csc_t a, spal_csc_t m, uint64_t k, const float *b, uint64_t ldb, uint64_t b_rows,
+                             float *x, uint64_t ldx, uint64_t x_rows, uint64_t restart, double tol, uint64_t maxit,
+                             spal_krylov_info *info);
+int spal_csc_gmres_block_dev_f64(spal_csc_t a, spal_csc_t m, uint64_t k, const double *b_dev, uint64_t ldb,
+                                 double *x_dev, uint64_t ldx, uint64_t restart, double tol, uint64_t maxit, void *stream,
+                                 spal_krylov_info *info);
+int spal_csc_gmres_block_dev_f32(spal_csc_t a, spal_csc_t m, uint64_t k, const float *b_dev, uint64_t ldb,
+                                 float *x_dev, uint64_t ldx, uint64_t restart, double tol, uint64_t maxit, void *stream,
+                                 spal_krylov_info *info);
 
 /* ---- multicolour reordering: greedy colouring and B = P A P^T -------------------------------------------
  * Not in the reference.  An exact triangular solve costs one launch step per level; numbering the rows

@@ -19,6 +19,7 @@
 //   a.solve(b, method, M, x0, tol, maxit), dot(a, b)     not in the reference: CG / BiCGStab and their dot product
 //                                                        (include/spal.h, spal_*_krylov_*, spal_*_krylov_block_*, spal_dot_*)
 //   a.gmres(b, restart, M, x0, tol, maxit)               not in the reference: restarted GMRES (spal_*_gmres_*)
+//   a.gmres_block(B, k, restart, M, X0, tol, maxit)      not in the reference: GMRES on k right-hand sides (spal_*_gmres_block_*)
 //   a.colour(seed), a.permute(perm), a.multicolour(seed), p.ordering(), p.to_order(v), p.from_order(v),
 //   colour_greedy(n, rowptr, colind, seed), perm_from_colours(colours)
 //                                                        not in the reference: the multicolour ordering
@@ -76,6 +77,7 @@ template <> struct Abi<double> {
     static constexpr auto csr_krylov = spal_csr_krylov_f64;
     static constexpr auto csr_krylov_block = spal_csr_krylov_block_f64;
     static constexpr auto csr_gmres = spal_csr_gmres_f64;
+    static constexpr auto csr_gmres_block = spal_csr_gmres_block_f64;
     static constexpr auto csr_permute_vec = spal_csr_permute_vec_f64;
     static constexpr auto dot = spal_dot_f64;
     static constexpr auto csr_download = spal_csr_download_f64;
@@ -89,6 +91,7 @@ template <> struct Abi<double> {
     static constexpr auto csc_krylov = spal_csc_krylov_f64;
     static constexpr auto csc_krylov_block = spal_csc_krylov_block_f64;
     static constexpr auto csc_gmres = spal_csc_gmres_f64;
+    static constexpr auto csc_gmres_block = spal_csc_gmres_block_f64;
     static constexpr auto csc_permute_vec = spal_csc_permute_vec_f64;
     static constexpr auto coo_to_csr = spal_coo_to_csr_f64;
     static constexpr auto coo_to_csc = spal_coo_to_csc_f64;
@@ -105,6 +108,7 @@ template <> struct Abi<float> {
     static constexpr auto csr_krylov = spal_csr_krylov_f32;
     static constexpr auto csr_krylov_block = spal_csr_krylov_block_f32;
     static constexpr auto csr_gmres = spal_csr_gmres_f32;
+    static constexpr auto csr_gmres_block = spal_csr_gmres_block_f32;
     static constexpr auto csr_permute_vec = spal_csr_permute_vec_f32;
     static constexpr auto dot = spal_dot_f32;
     static constexpr auto csr_download = spal_csr_download_f32;
@@ -118,6 +122,7 @@ template <> struct Abi<float> {
     static constexpr auto csc_krylov = spal_csc_krylov_f32;
     static constexpr auto csc_krylov_block = spal_csc_krylov_block_f32;
     static constexpr auto csc_gmres = spal_csc_gmres_f32;
+    static constexpr auto csc_gmres_block = spal_csc_gmres_block_f32;
     static constexpr auto csc_permute_vec = spal_csc_permute_vec_f32;
     static constexpr auto coo_to_csr = spal_coo_to_csr_f32;
     static constexpr auto coo_to_csc = spal_coo_to_csc_f32;
@@ -473,6 +478,27 @@ class CsrMatrix {
         return s;
     }
 
+    // X with A X = B for a ROW-MAJOR block of k right-hand sides by restarted GMRES(restart): k independent iterations in
+    // lockstep on shared launches, with cycles common to the block (spal_csr_gmres_block_*, include/spal.h).  Column j
+    // of the result and columns[j] are bit for bit gmres()'s text on column j of B, whatever k and the other columns are.
+    // X0 empty: zeros.  Panics as gmres() does, and when k == 0 or B / X0 are not nrows x k.
+    BlockSolution<T> gmres_block(const std::vector<T> &B, usize k, usize restart = 30, const CsrMatrix *M = nullptr,
+                                 const std::vector<T> &X0 = {}, double tol = 1e-8, usize maxit = 1000) const {
+        check_block("gmres_block", B.size(), k);
+        if (!X0.empty() && X0.size() != B.size())
+            throw Panic(SPAL_ERR_INVALID_ARGUMENT, "gmres_block: X0.len() = " + std::to_string(X0.size()) +
+                                                       " but B.len() = " + std::to_string(B.size()));
+        if (restart == 0 || restart > 256)
+            throw Panic(SPAL_ERR_INVALID_ARGUMENT, "gmres_block: restart = " + std::to_string(restart) + " must be 1 .. 256");
+        BlockSolution<T> s{X0.empty() ? std::vector<T>(B.size(), T(0)) : X0, {}};
+        std::vector<spal_krylov_info> info(k);
+        detail::check(detail::Abi<T>::csr_gmres_block(device_handle(), M ? M->device_handle() : nullptr, k, B.data(), k,
+                                                       nrows_, s.x.data(), k, nrows_, restart, tol, maxit, info.data()));
+        for (const spal_krylov_info &c : info)
+            s.columns.push_back(ColumnResult{c.iterations, c.reason, c.residual_sq, c.rhs_sq, c.solve_ms});
+        return s;
+    }
+
     // CsrMatrix::from(&coo): assembled on the device, bit-identical to the reference.
     static CsrMatrix from(const CooMatrix<T> &coo, int device = 0);
     // CsrMatrix::from(&csc)  (src/csr/conv/csc.rs:4-52): device stable sort by row.
@@ -766,6 +792,27 @@ class CscMatrix {
         s.residual_sq = info.residual_sq;
         s.rhs_sq = info.rhs_sq;
         s.solve_ms = info.solve_ms;
+        return s;
+    }
+
+    // X with A X = B for a ROW-MAJOR block of k right-hand sides by restarted GMRES(restart): k independent iterations in
+    // lockstep on shared launches, with cycles common to the block (spal_csc_gmres_block_*, include/spal.h).  Column j
+    // of the result and columns[j] are bit for bit gmres()'s text on column j of B, whatever k and the other columns are.
+    // X0 empty: zeros.  Panics as gmres() does, and when k == 0 or B / X0 are not nrows x k.
+    BlockSolution<T> gmres_block(const std::vector<T> &B, usize k, usize restart = 30, const CscMatrix *M = nullptr,
+                                 const std::vector<T> &X0 = {}, double tol = 1e-8, usize maxit = 1000) const {
+        check_block("gmres_block", B.size(), k);
+        if (!X0.empty() && X0.size() != B.size())
+            throw Panic(SPAL_ERR_INVALID_ARGUMENT, "gmres_block: X0.len() = " + std::to_string(X0.size()) +
+                                                       " but B.len() = " + std::to_string(B.size()));
+        if (restart == 0 || restart > 256)
+            throw Panic(SPAL_ERR_INVALID_ARGUMENT, "gmres_block: restart = " + std::to_string(restart) + " must be 1 .. 256");
+        BlockSolution<T> s{X0.empty() ? std::vector<T>(B.size(), T(0)) : X0, {}};
+        std::vector<spal_krylov_info> info(k);
+        detail::check(detail::Abi<T>::csc_gmres_block(device_handle(), M ? M->device_handle() : nullptr, k, B.data(), k,
+                                                       nrows_, s.x.data(), k, nrows_, restart, tol, maxit, info.data()));
+        for (const spal_krylov_info &c : info)
+            s.columns.push_back(ColumnResult{c.iterations, c.reason, c.residual_sq, c.rhs_sq, c.solve_ms});
         return s;
     }
     // CscMatrix::from(&csr)  (src/csc/conv/csr.rs:4-52) and CscMatrix::from(&coo)

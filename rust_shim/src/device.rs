@@ -152,6 +152,21 @@ impl<T: HipScalar> DeviceCsr<T> {
         info
     }
 
+    /// X with A X = B for a row-major block of `k` right-hand sides by restarted GMRES(`restart`): k independent
+    /// iterations in lockstep on shared launches, with cycles common to the block (spal_csr_gmres_block_*).  `b` and `x`
+    /// hold nrows * k elements, element (i, j) at i * k + j; `x` holds X0 on entry.  Column j and record j are bit for
+    /// bit `gmres`'s text on column j, whatever k and the other columns are.  Panics as `gmres` does, and when k == 0 or a
+    /// block is not nrows x k.
+    pub fn gmres_block(&self, m: Option<&DeviceCsr<T>>, k: usize, b: &[T], x: &mut [T], restart: u64, tol: f64, maxit: u64)
+        -> Vec<ffi::spal_krylov_info>
+    where T: HipKrylov {
+        assert!(k > 0 && b.len() % k == 0 && x.len() == b.len());
+        let mut info = vec![ffi::spal_krylov_info::default(); k];
+        let mh = m.map_or(std::ptr::null_mut(), |f| f.h);
+        unsafe { ffi::check(T::csr_gmres_block(self.h, mh, k as u64, b, x, restart, tol, maxit, info.as_mut_ptr())); }
+        info
+    }
+
     /// `solve_triangular` on device pointers (`x_dev == b_dev` solves in place), enqueued on `stream` and not
     /// synchronised once the triangle has its plan (`trsv_analyse`, or the first solve, builds it).
     ///
@@ -422,6 +437,21 @@ impl<T: HipScalar> DeviceCsc<T> {
         let mut info = ffi::spal_krylov_info::default();
         let mh = m.map_or(std::ptr::null_mut(), |f| f.h);
         unsafe { ffi::check(T::csc_gmres(self.h, mh, b, x, restart, tol, maxit, &mut info)); }
+        info
+    }
+
+    /// X with A X = B for a row-major block of `k` right-hand sides by restarted GMRES(`restart`): k independent
+    /// iterations in lockstep on shared launches, with cycles common to the block (spal_csc_gmres_block_*).  `b` and `x`
+    /// hold nrows * k elements, element (i, j) at i * k + j; `x` holds X0 on entry.  Column j and record j are bit for
+    /// bit `gmres`'s text on column j, whatever k and the other columns are.  Panics as `gmres` does, and when k == 0 or a
+    /// block is not nrows x k.
+    pub fn gmres_block(&self, m: Option<&DeviceCsc<T>>, k: usize, b: &[T], x: &mut [T], restart: u64, tol: f64, maxit: u64)
+        -> Vec<ffi::spal_krylov_info>
+    where T: HipKrylov {
+        assert!(k > 0 && b.len() % k == 0 && x.len() == b.len());
+        let mut info = vec![ffi::spal_krylov_info::default(); k];
+        let mh = m.map_or(std::ptr::null_mut(), |f| f.h);
+        unsafe { ffi::check(T::csc_gmres_block(self.h, mh, k as u64, b, x, restart, tol, maxit, info.as_mut_ptr())); }
         info
     }
 

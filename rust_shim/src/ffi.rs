@@ -140,6 +140,14 @@ extern "C" {
     pub fn spal_csc_gmres_f32(a: *mut spal_csc, m: *mut spal_csc, b: *const f32, b_len: u64, x: *mut f32, x_len: u64, restart: u64, tol: f64, maxit: u64, info: *mut spal_krylov_info) -> c_int;
     pub fn spal_csc_gmres_dev_f64(a: *mut spal_csc, m: *mut spal_csc, b_dev: *const f64, x_dev: *mut f64, restart: u64, tol: f64, maxit: u64, stream: *mut c_void, info: *mut spal_krylov_info) -> c_int;
     pub fn spal_csc_gmres_dev_f32(a: *mut spal_csc, m: *mut spal_csc, b_dev: *const f32, x_dev: *mut f32, restart: u64, tol: f64, maxit: u64, stream: *mut c_void, info: *mut spal_krylov_info) -> c_int;
+    pub fn spal_csr_gmres_block_f64(a: *mut spal_csr, m: *mut spal_csr, k: u64, b: *const f64, ldb: u64, b_rows: u64, x: *mut f64, ldx: u64, x_rows: u64, restart: u64, tol: f64, maxit: u64, info: *mut spal_krylov_info) -> c_int;
+    pub fn spal_csr_gmres_block_f32(a: *mut spal_csr, m: *mut spal_csr, k: u64, b: *const f32, ldb: u64, b_rows: u64, x: *mut f32, ldx: u64, x_rows: u64, restart: u64, tol: f64, maxit: u64, info: *mut spal_krylov_info) -> c_int;
+    pub fn spal_csr_gmres_block_dev_f64(a: *mut spal_csr, m: *mut spal_csr, k: u64, b_dev: *const f64, ldb: u64, x_dev: *mut f64, ldx: u64, restart: u64, tol: f64, maxit: u64, stream: *mut c_void, info: *mut spal_krylov_info) -> c_int;
+    pub fn spal_csr_gmres_block_dev_f32(a: *mut spal_csr, m: *mut spal_csr, k: u64, b_dev: *const f32, ldb: u64, x_dev: *mut f32, ldx: u64, restart: u64, tol: f64, maxit: u64, stream: *mut c_void, info: *mut spal_krylov_info) -> c_int;
+    pub fn spal_csc_gmres_block_f64(a: *mut spal_csc, m: *mut spal_csc, k: u64, b: *const f64, ldb: u64, b_rows: u64, x: *mut f64, ldx: u64, x_rows: u64, restart: u64, tol: f64, maxit: u64, info: *mut spal_krylov_info) -> c_int;
+    pub fn spal_csc_gmres_block_f32(a: *mut spal_csc, m: *mut spal_csc, k: u64, b: *const f32, ldb: u64, b_rows: u64, x: *mut f32, ldx: u64, x_rows: u64, restart: u64, tol: f64, maxit: u64, info: *mut spal_krylov_info) -> c_int;
+    pub fn spal_csc_gmres_block_dev_f64(a: *mut spal_csc, m: *mut spal_csc, k: u64, b_dev: *const f64, ldb: u64, x_dev: *mut f64, ldx: u64, restart: u64, tol: f64, maxit: u64, stream: *mut c_void, info: *mut spal_krylov_info) -> c_int;
+    pub fn spal_csc_gmres_block_dev_f32(a: *mut spal_csc, m: *mut spal_csc, k: u64, b_dev: *const f32, ldb: u64, x_dev: *mut f32, ldx: u64, restart: u64, tol: f64, maxit: u64, stream: *mut c_void, info: *mut spal_krylov_info) -> c_int;
     pub fn spal_colour_greedy(n: u64, rowptr: *const u64, colind: *const u64, seed: u64, colour: *mut u64, ncolours: *mut u64) -> c_int;
     pub fn spal_perm_from_colours(n: u64, colour: *const u64, perm: *mut u64) -> c_int;
     pub fn spal_csr_colour(a: *mut spal_csr, seed: u64, stream: *mut c_void, colour_host: *mut u64, ncolours: *mut u64, rounds: *mut u64) -> c_int;

@@ -175,12 +175,28 @@ pub trait HipKrylov: Sized {
                         maxit: u64, info: *mut ffi::spal_krylov_info) -> c_int;
     unsafe fn csc_gmres(a: *mut ffi::spal_csc, m: *mut ffi::spal_csc, b: &[Self], x: &mut [Self], restart: u64, tol: f64,
                         maxit: u64, info: *mut ffi::spal_krylov_info) -> c_int;
+    /// GMRES on a row-major block of k right-hand sides (the spal_*_gmres_block_* entry points): `b` and `x` hold
+    /// nrows * k elements, element (i, j) at i * k + j; `info` points to k records
+    unsafe fn csr_gmres_block(a: *mut ffi::spal_csr, m: *mut ffi::spal_csr, k: u64, b: &[Self], x: &mut [Self], restart: u64,
+                              tol: f64, maxit: u64, info: *mut ffi::spal_krylov_info) -> c_int;
+    unsafe fn csc_gmres_block(a: *mut ffi::spal_csc, m: *mut ffi::spal_csc, k: u64, b: &[Self], x: &mut [Self], restart: u64,
+                              tol: f64, maxit: u64, info: *mut ffi::spal_krylov_info) -> c_int;
 }
 
 macro_rules! impl_hip_krylov {
     ($t:ty, $csr_krylov:ident, $csc_krylov:ident, $dot:ident, $csr_gmres:ident, $csc_gmres:ident, $csr_block:ident,
-     $csc_block:ident) => {
+     $csc_block:ident, $csr_gmres_block:ident, $csc_gmres_block:ident) => {
         impl HipKrylov for $t {
+            unsafe fn csr_gmres_block(a: *mut ffi::spal_csr, m: *mut ffi::spal_csr, k: u64, b: &[Self], x: &mut [Self],
+                                      restart: u64, tol: f64, maxit: u64, info: *mut ffi::spal_krylov_info) -> c_int {
+                let (br, xr) = (if k > 0 { b.len() as u64 / k } else { 0 }, if k > 0 { x.len() as u64 / k } else { 0 });
+                ffi::$csr_gmres_block(a, m, k, b.as_ptr(), k, br, x.as_mut_ptr(), k, xr, restart, tol, maxit, info)
+            }
+            unsafe fn csc_gmres_block(a: *mut ffi::spal_csc, m: *mut ffi::spal_csc, k: u64, b: &[Self], x: &mut [Self],
+                                      restart: u64, tol: f64, maxit: u64, info: *mut ffi::spal_krylov_info) -> c_int {
+                let (br, xr) = (if k > 0 { b.len() as u64 / k } else { 0 }, if k > 0 { x.len() as u64 / k } else { 0 });
+                ffi::$csc_gmres_block(a, m, k, b.as_ptr(), k, br, x.as_mut_ptr(), k, xr, restart, tol, maxit, info)
+            }
             unsafe fn csr_krylov_block(a: *mut ffi::spal_csr, method: c_int, m: *mut ffi::spal_csr, k: u64, b: &[Self],
                                        x: &mut [Self], tol: f64, maxit: u64, info: *mut ffi::spal_krylov_info) -> c_int {
                 let (br, xr) = (if k > 0 { b.len() as u64 / k } else { 0 }, if k > 0 { x.len() as u64 / k } else { 0 });
@@ -214,9 +230,11 @@ macro_rules! impl_hip_krylov {
     };
 }
 impl_hip_krylov!(f64, spal_csr_krylov_f64, spal_csc_krylov_f64, spal_dot_f64, spal_csr_gmres_f64, spal_csc_gmres_f64,
-                 spal_csr_krylov_block_f64, spal_csc_krylov_block_f64);
+                 spal_csr_krylov_block_f64, spal_csc_krylov_block_f64, spal_csr_gmres_block_f64,
+                 spal_csc_gmres_block_f64);
 impl_hip_krylov!(f32, spal_csr_krylov_f32, spal_csc_krylov_f32, spal_dot_f32, spal_csr_gmres_f32, spal_csc_gmres_f32,
-                 spal_csr_krylov_block_f32, spal_csc_krylov_block_f32);
+                 spal_csr_krylov_block_f32, spal_csc_krylov_block_f32, spal_csr_gmres_block_f32,
+                 spal_csc_gmres_block_f32);
 
 /// dot(a, b) by the library's definition (include/spal.h): products rounded, then the fixed tree over tiles of 1024.
 pub fn dot<T: HipKrylov + Default>(a: &[T], b: &[T]) -> T {

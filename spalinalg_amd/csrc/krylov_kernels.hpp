@@ -1,14 +1,16 @@
 // krylov_kernels.hpp -- what spal_krylov.hip (the dot product, CG, BiCGStab: DESIGN 3.14), spal_krylov_block.hip (the
-// same two loops on a block of right-hand sides: DESIGN 3.22) and spal_gmres.hip (GMRES: DESIGN 3.17) share: the tile
-// sum and the upper levels of reduce(), the scalar block, the fused vector updates and the scalar steps of CG and
-// BiCGStab, the sizes of a dot's scratch, the entry points a driver goes through by handle and element type, the
-// preparation of the plans, M^-1, the refusals that need no device and two scope guards.  The contracts are written
-// out in include/spal.h.  (Not installed.)
+// same two loops on a block of right-hand sides: DESIGN 3.22), spal_gmres.hip (GMRES: DESIGN 3.17) and
+// spal_gmres_block.hip (GMRES on a block: DESIGN 3.23) share: the tile sum and the upper levels of reduce(), the scalar
+// block, the fused vector updates and the scalar steps of CG and BiCGStab, the sizes of a dot's scratch, the entry
+// points a driver goes through by handle and element type, the preparation of the plans, M^-1, the refusals that need no
+// device, two scope guards, and for the block drivers the column tiles, column_tree and the routes to SpMM and trsm.
+// The contracts are written out in include/spal.h.  (Not installed.)
 #pragma once
 
 #include "spal_ops.hpp"
 
 #include <cmath>
+#include <limits>
 
 #pragma clang fp contract(off)
 
@@ -314,6 +316,85 @@ inline int refuse_lengths(const char *fn, uint64_t b_len, uint64_t x_len, uint64
         return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: b.len() = %llu and x.len() = %llu but the matrix has %llu rows", fn,
                     (unsigned long long)b_len, (unsigned long long)x_len, (unsigned long long)nrows);
     return SPAL_OK;
+}
+
+// ---- what the block drivers (spal_krylov_block.hip, spal_gmres_block.hip) share --------------------------------------
+constexpr unsigned kBlockMaxGrid = 1024;   // first-level workgroups along the rows; each walks tiles blockIdx.x, + gridDim.x, ...
+constexpr unsigned kColumnGrid = 64;       // ... and along the column tiles (blockIdx.y)
+constexpr unsigned kFinishGrid = 65535;    // finish workgroups; each walks columns blockIdx.x, + gridDim.x, ...
+constexpr int kTiles[] = {1, 2, 4, 8, 16, 32};   // the instantiated column tiles
+
+// A block operand: the pointer and its leading dimension.  Nothing is __restrict__: without a preconditioner z is r, ph
+// is p and sh is s.
+template <typename T>
+struct Mat {
+    T *p;
+    uint64_t ld;
+};
+
+// The h < G levels of a column's tile: `a` is the sum over the thread's own rows; valid in threads 0 .. KT - 1.  `lds`
+// holds kThreads elements; ends with a barrier, so it can be reused.
+template <typename T, int KT>
+__device__ __forceinline__ T column_tree(T a, T *lds) {
+    const unsigned t = threadIdx.x;
+    lds[t] = a;
+    __syncthreads();
+    if (t < 128) {
+        a = lds[t] + lds[t + 128];               // h = 128 / KT
+        if (t >= 64) lds[t] = a;                 // (its own slot: nobody else read it)
+    }
+    __syncthreads();
+    if (t < 64) {
+        a = a + lds[t + 64];                     // h = 64 / KT
+#pragma unroll
+        for (int h = 32; h >= KT; h >>= 1) a = a + __shfl_down(a, h, 64);
+    }
+    __syncthreads();
+    return a;
+}
+
+inline bool tile_instantiated(int64_t t) {
+    for (int v : kTiles)
+        if (t == v) return true;
+    return false;
+}
+
+// automatic column tile: the narrowest instantiated tile that holds k
+inline int auto_tile(uint64_t k) {
+    int t = 1;
+    while (t < 32 && (uint64_t)t < k) t *= 2;
+    return t;
+}
+
+// the entry points a block driver goes through, by handle and element type
+#define SPAL_KB_ROUTES(kind, sfx, T)                                                                                   \
+    inline int mul_block(spal_##kind *a, uint64_t k, const T *x, uint64_t ldx, T *y, uint64_t ldy, void *st) {         \
+        return spal_##kind##_spmm_dev_##sfx(a, k, x, ldx, y, ldy, st);                                                 \
+    }                                                                                                                  \
+    inline int solve_block(spal_##kind *m, int uplo, int unit, uint64_t k, const T *b, uint64_t ldb, T *x,             \
+                           uint64_t ldx, void *st) {                                                                   \
+        return spal_##kind##_trsm_dev_##sfx(m, uplo, unit, k, b, ldb, x, ldx, st);                                     \
+    }                                                                                                                  \
+    inline int sweep_block(spal_##kind *m, int uplo, int unit, uint64_t s, uint64_t k, const T *b, uint64_t ldb, T *x, \
+                           uint64_t ldx, void *st) {                                                                   \
+        return spal_##kind##_trsm_sweep_dev_##sfx(m, uplo, unit, s, k, b, ldb, x, ldx, st);                            \
+    }
+SPAL_KB_ROUTES(csr, f64, double)
+SPAL_KB_ROUTES(csr, f32, float)
+SPAL_KB_ROUTES(csc, f64, double)
+SPAL_KB_ROUTES(csc, f32, float)
+#undef SPAL_KB_ROUTES
+
+// a * b * c * d, or false when it does not fit half of size_t
+inline bool bytes_of(uint64_t a, uint64_t b, uint64_t c, uint64_t d, size_t *out) {
+    unsigned __int128 v = (unsigned __int128)a * b;
+    if (v > std::numeric_limits<size_t>::max()) return false;
+    v *= c;
+    if (v > std::numeric_limits<size_t>::max()) return false;
+    v *= d;
+    if (v > std::numeric_limits<size_t>::max() / 2) return false;
+    *out = (size_t)v;
+    return true;
 }
 
 }  // namespace spal

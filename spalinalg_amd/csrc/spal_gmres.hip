@@ -21,7 +21,7 @@
 // and the call has not; after `done` every kernel returns before it writes.  Products and solves enqueued past a stop
 // still run, into work vectors nobody reads again.  So x, it, reason and rr do not depend on "krylov_check_every".
 // ORDER BETWEEN LAUNCHES IS STREAM ORDER ALONE.  The driver holds no handle lock across a product or a solve.
-#include "krylov_kernels.hpp"
+#include "gmres_kernels.hpp"
 
 #pragma clang fp contract(off)
 
@@ -29,28 +29,8 @@ namespace spal {
 namespace {
 
 constexpr int kDotBatch = 8;          // basis vectors per batch of mdot / mupdate / combine ("dot_batch")
-constexpr uint64_t kMaxRestart = 256; // one Hessenberg column element per thread of the scalar workgroup
 
-// What the host polls.
-template <typename T>
-struct GHead {
-    T rr, bb, thr, beta, hn, est;
-    unsigned long long it, cycles;
-    unsigned done, reason, cyc_end, jj;
-};
-
-// The scalar block by its parts (all device pointers into one allocation).
-template <typename T>
-struct GBlock {
-    GHead<T> *s;
-    T *h, *c;      // restart + 1 each: the current column, the second pass's corrections
-    T *cs, *sn;    // restart each
-    T *g;          // restart + 1
-    T *y;          // restart
-    T *H;          // (restart + 1) x restart, column k at H + k * (restart + 1)
-    unsigned m;    // restart
-};
-inline size_t block_elems(uint64_t m) { return (size_t)(3 * (m + 1) + 3 * m + (m + 1) * m); }
+// (GHead, GBlock, block_elems and the three scalar steps are in gmres_kernels.hpp, shared with spal_gmres_block.hip.)
 
 // The basis and one of its passes.
 template <typename T>
@@ -58,11 +38,6 @@ struct Basis {
     const T *v;        // v_k at v + k * stride
     uint64_t stride, n, tiles;
 };
-
-template <typename T>
-__device__ __forceinline__ bool at_step(const GHead<T> *s, unsigned j) {
-    return s->done == 0 && s->cyc_end == 0 && s->jj == j;   // uniform: written by an earlier launch
-}
 
 // thread t's four elements of a tile; the padding is +0.0
 template <typename T>
@@ -136,27 +111,7 @@ __global__ __launch_bounds__(kThreads) void cycle_start(GBlock<T> B, T *part0, T
     if (s->done != 0) return;
     const T rr = upper_levels<T>(part0, c1, lds);
     const T bb = upper_levels<T>(part1, c1, lds);
-    if (threadIdx.x != 0) return;
-    s->bb = bb;
-    s->thr = tol2 * bb;
-    s->rr = rr;
-    if (rr <= s->thr) {
-        s->done = 1;
-        s->reason = 0;
-    } else if (!isfinite(rr)) {
-        s->done = 1;
-        s->reason = 2;
-    } else if (s->it == maxit) {
-        s->done = 1;
-        s->reason = 1;
-    } else {
-        const T beta = sqrt(rr);
-        s->beta = beta;
-        B.g[0] = beta;
-        s->jj = 0;
-        s->cyc_end = 0;
-        s->cycles += 1;
-    }
+    if (threadIdx.x == 0) cycle_start_scalars<T>(B, rr, bb, tol2, maxit);
 }
 
 // dst = src / beta (step < 0: v_0, in place) or dst = src / hn (v_{step + 1} = w / hn, after step's scalars)
@@ -256,60 +211,16 @@ __global__ __launch_bounds__(kThreads) void step_scalars(GBlock<T> B, unsigned j
     GHead<T> *s = B.s;
     if (!at_step(s, j)) return;
     const T ww = upper_levels<T>(part0, c1, lds);
-    const unsigned t = threadIdx.x;
-    T *h = B.h;
-    if (t <= j) h[t] = h[t] + B.c[t];
-    __syncthreads();
-    if (t == 0) {
-        const T hn = sqrt(ww);
-        s->hn = hn;
-        s->it += 1;
-        for (unsigned k = 0; k < j; ++k) {
-            const T tmp = (B.cs[k] * h[k]) + (B.sn[k] * h[k + 1]);
-            h[k + 1] = (B.cs[k] * h[k + 1]) - (B.sn[k] * h[k]);
-            h[k] = tmp;
-        }
-        const T d = sqrt((h[j] * h[j]) + (hn * hn));
-        const T cs = h[j] / d, sn = hn / d;
-        B.cs[j] = cs;
-        B.sn[j] = sn;
-        h[j] = d;
-        const T gj = B.g[j];
-        const T g1 = -(sn * gj);
-        B.g[j + 1] = g1;
-        B.g[j] = cs * gj;
-        const T est = g1 * g1;
-        s->est = est;
-        s->jj = j + 1;
-        if (!isfinite(est)) {
-            s->rr = est;
-            s->done = 1;
-            s->reason = 2;
-        } else if (est <= s->thr || s->it == maxit || j + 1 == B.m) {
-            s->cyc_end = 1;
-        }
-    }
-    __syncthreads();
-    if (t <= j) B.H[(uint64_t)j * (B.m + 1) + t] = h[t];
+    step_scalars_body<T>(B, j, ww, maxit);
 }
 
 // ---- the end of a cycle ---------------------------------------------------------------------------------------------
-template <typename T>
-__device__ __forceinline__ bool at_cycle_end(const GHead<T> *s) { return s->done == 0 && s->cyc_end != 0; }
-
 // column form: thread l owns g[l];  for k = jj - 1 .. 0:  y[k] = g[k] / H[k, k];  g[l] -= H[l, k] * y[k] for l < k
 template <typename T>
 __global__ __launch_bounds__(kThreads) void back_substitute(GBlock<T> B) {
     __shared__ T y[kThreads];
     if (!at_cycle_end(B.s)) return;
-    const unsigned jj = B.s->jj, t = threadIdx.x, ld = B.m + 1;
-    T gl = t < jj ? B.g[t] : T(0);
-    for (unsigned k = jj; k-- > 0;) {
-        if (t == k) y[k] = gl / B.H[(uint64_t)k * ld + k];
-        __syncthreads();
-        if (t < k) gl = gl - (B.H[(uint64_t)k * ld + t] * y[k]);
-    }
-    if (t < jj) B.y[t] = y[t];
+    back_substitute_body<T>(B, y);
 }
 
 // u[i] = (..((y[0] * v_0[i]) + (y[1] * v_1[i])) ..) + (y[jj - 1] * v_{jj-1}[i]);  ADD: out[i] = out[i] + u[i], else out = u
@@ -495,25 +406,7 @@ int gmres_run(const char *fn, H *a, H *m, const T *b, T *x, uint64_t restart, do
         R.w0 = R.v_at(next++);
         R.w1 = R.v_at(next++);
     }
-    {
-        GBlock<T> &B = R.B;
-        B.s = scal.as<GHead<T>>();
-        B.m = (unsigned)restart;
-        T *p = reinterpret_cast<T *>(reinterpret_cast<char *>(scal.p) + sizeof(GHead<T>));
-        B.h = p;
-        p += restart + 1;
-        B.c = p;
-        p += restart + 1;
-        B.cs = p;
-        p += restart;
-        B.sn = p;
-        p += restart;
-        B.g = p;
-        p += restart + 1;
-        B.y = p;
-        p += restart;
-        B.H = p;
-    }
+    R.B = block_parts<T>(scal.as<GHead<T>>(), reinterpret_cast<T *>(reinterpret_cast<char *>(scal.p) + sizeof(GHead<T>)), restart);
 
     GHead<T> *h = (GHead<T> *)host.p;
     uint64_t polls = 0;

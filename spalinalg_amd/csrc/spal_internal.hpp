@@ -314,8 +314,9 @@ struct OpState {
     int64_t krylov_check_every = 0; // option "krylov_check_every": iterations between two polls, 0 = default (spal_krylov.hip)
     std::string krylov_info;       // "krylov": the last spal_*_krylov_* call with this handle as A (guarded by the solve handle's mu)
     std::string gmres_info;        // "gmres": the last spal_*_gmres_* call with this handle as A (the same lock; spal_gmres.hip)
-    int krylov_tile = 0;           // option "krylov_tile": column tile of the block Krylov vector kernels, 0 = automatic (spal_krylov_block.hip)
+    int krylov_tile = 0;           // option "krylov_tile": column tile of the block Krylov vector kernels, 0 = automatic (spal_krylov_block.hip, spal_gmres_block.hip)
     std::string krylov_block_info; // "krylov_block": the last spal_*_krylov_block_* call with this handle as A (the same lock)
+    std::string gmres_block_info;  // "gmres_block": the last spal_*_gmres_block_* call with this handle as A (the same lock)
     // a result of spal_*_permute / _multicolour (spal_colour.hip): written once, before the handle is
     // returned, and only read afterwards
     uint32_t *d_perm = nullptr;    // nrows: new -> old; freed by ordering_free (csr_free, csc_free)

@@ -7,7 +7,8 @@
 // search space is shared, so every column keeps its sequential text and its bits.
 //
 // (tile_sum, upper_levels, the scalar block Scal, the ten fused updates and the scalar steps are in krylov_kernels.hpp,
-// shared with spal_krylov.hip: the arithmetic of a column is the vector call's, by construction.)
+// shared with spal_krylov.hip: the arithmetic of a column is the vector call's, by construction.  Mat, column_tree, the
+// column tiles and the routes to SpMM and trsm are there too, shared with spal_gmres_block.hip.)
 //
 // THE FIRST LEVEL.  A workgroup of 256 covers a tile of 1024 rows x KT columns of the blocks.  Thread t is column
 // t % KT of the tile and row group g = t / KT of G = 256 / KT; it owns rows g, g + G, g + 2G, ... of the tile, L = 4 KT
@@ -38,26 +39,12 @@
 // too, so no iteration allocates and nothing synchronises but the polls.
 #include "krylov_kernels.hpp"
 
-#include <limits>
 #include <type_traits>
 
 #pragma clang fp contract(off)
 
 namespace spal {
 namespace {
-
-constexpr unsigned kBlockMaxGrid = 1024;   // first-level workgroups along the rows; each walks tiles blockIdx.x, + gridDim.x, ...
-constexpr unsigned kColumnGrid = 64;       // ... and along the column tiles (blockIdx.y)
-constexpr unsigned kFinishGrid = 65535;    // finish workgroups; each walks columns blockIdx.x, + gridDim.x, ...
-constexpr int kTiles[] = {1, 2, 4, 8, 16, 32};   // the instantiated column tiles
-
-// A block operand: the pointer and its leading dimension.  Nothing is __restrict__: without a preconditioner z is r, ph
-// is p and sh is s.
-template <typename T>
-struct Mat {
-    T *p;
-    uint64_t ld;
-};
 
 template <typename T>
 struct BlockVecArgs {
@@ -68,27 +55,6 @@ struct BlockVecArgs {
     uint64_t n, pe;
     uint32_t k;
 };
-
-// The h < G levels of a column's tile: `a` is the sum over the thread's own rows; valid in threads 0 .. KT - 1.  `lds`
-// holds kThreads elements; ends with a barrier, so it can be reused.
-template <typename T, int KT>
-__device__ __forceinline__ T column_tree(T a, T *lds) {
-    const unsigned t = threadIdx.x;
-    lds[t] = a;
-    __syncthreads();
-    if (t < 128) {
-        a = lds[t] + lds[t + 128];               // h = 128 / KT
-        if (t >= 64) lds[t] = a;                 // (its own slot: nobody else read it)
-    }
-    __syncthreads();
-    if (t < 64) {
-        a = a + lds[t + 64];                     // h = 64 / KT
-#pragma unroll
-        for (int h = 32; h >= KT; h >>= 1) a = a + __shfl_down(a, h, 64);
-    }
-    __syncthreads();
-    return a;
-}
 
 template <typename T, int OP, int KT>
 __global__ __launch_bounds__(kThreads) void vec_block(BlockVecArgs<T> g, uint64_t tiles) {
@@ -217,20 +183,7 @@ __global__ __launch_bounds__(kThreads) void finish_block(BlockFinArgs<T> g) {
     }
 }
 
-// ---- host side of the launches --------------------------------------------------------------------------------------
-bool tile_instantiated(int64_t t) {
-    for (int v : kTiles)
-        if (t == v) return true;
-    return false;
-}
-
-// automatic column tile: the narrowest instantiated tile that holds k
-int auto_tile(uint64_t k) {
-    int t = 1;
-    while (t < 32 && (uint64_t)t < k) t *= 2;
-    return t;
-}
-
+// ---- host side of the launches (the tiles, auto_tile, the routes and bytes_of are in krylov_kernels.hpp) ---------------
 template <typename T, int OP>
 hipError_t launch_vec_block(const BlockVecArgs<T> &g, int tile, hipStream_t st) {
     const uint64_t tiles = tiles_of(g.n);
@@ -258,25 +211,6 @@ hipError_t launch_finish_block(const BlockFinArgs<T> &g, hipStream_t st) {
     hipLaunchKernelGGL((finish_block<T, OP>), dim3(std::min<unsigned>(g.k, kFinishGrid)), dim3(kThreads), 0, st, g);
     return hipGetLastError();
 }
-
-// ---- the entry points the driver goes through, by handle and element type -------------------------------------------
-#define SPAL_KB_ROUTES(kind, sfx, T)                                                                                   \
-    inline int mul_block(spal_##kind *a, uint64_t k, const T *x, uint64_t ldx, T *y, uint64_t ldy, void *st) {         \
-        return spal_##kind##_spmm_dev_##sfx(a, k, x, ldx, y, ldy, st);                                                 \
-    }                                                                                                                  \
-    inline int solve_block(spal_##kind *m, int uplo, int unit, uint64_t k, const T *b, uint64_t ldb, T *x,             \
-                           uint64_t ldx, void *st) {                                                                   \
-        return spal_##kind##_trsm_dev_##sfx(m, uplo, unit, k, b, ldb, x, ldx, st);                                     \
-    }                                                                                                                  \
-    inline int sweep_block(spal_##kind *m, int uplo, int unit, uint64_t s, uint64_t k, const T *b, uint64_t ldb, T *x, \
-                           uint64_t ldx, void *st) {                                                                   \
-        return spal_##kind##_trsm_sweep_dev_##sfx(m, uplo, unit, s, k, b, ldb, x, ldx, st);                            \
-    }
-SPAL_KB_ROUTES(csr, f64, double)
-SPAL_KB_ROUTES(csr, f32, float)
-SPAL_KB_ROUTES(csc, f64, double)
-SPAL_KB_ROUTES(csc, f32, float)
-#undef SPAL_KB_ROUTES
 
 struct Record {
     int method = 0, preconditioned = 0, tile = 0;
@@ -334,18 +268,6 @@ struct Run {
         return e == hipSuccess ? SPAL_OK : fail(SPAL_ERR_HIP, "%s: launch failed: %s", fn, hipGetErrorString(e));
     }
 };
-
-// a * b * c * d, or false when it does not fit half of size_t
-inline bool bytes_of(uint64_t a, uint64_t b, uint64_t c, uint64_t d, size_t *out) {
-    unsigned __int128 v = (unsigned __int128)a * b;
-    if (v > std::numeric_limits<size_t>::max()) return false;
-    v *= c;
-    if (v > std::numeric_limits<size_t>::max()) return false;
-    v *= d;
-    if (v > std::numeric_limits<size_t>::max() / 2) return false;
-    *out = (size_t)v;
-    return true;
-}
 
 template <typename T, typename H>
 int block_run(const char *fn, H *a, int method, H *m, uint32_t k, const T *b, uint64_t ldb, T *x, uint64_t ldx,

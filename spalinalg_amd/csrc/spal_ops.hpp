@@ -1,5 +1,5 @@
 // spal_ops.hpp -- the host layer the sparse operations share: spal_spgemm.hip, spal_spadd.hip,
-// spal_spmm.hip, spal_trsv.hip, spal_trsv_sweep.hip, spal_trsm.hip, spal_ilu.hip, spal_ilu_sweep.hip, spal_krylov.hip, spal_krylov_block.hip, spal_gmres.hip and spal_colour.hip keep their kernels, their driver, their option's validation and their
+// spal_spmm.hip, spal_trsv.hip, spal_trsv_sweep.hip, spal_trsm.hip, spal_ilu.hip, spal_ilu_sweep.hip, spal_krylov.hip, spal_krylov_block.hip, spal_gmres.hip, spal_gmres_block.hip and spal_colour.hip keep their kernels, their driver, their option's validation and their
 // info JSON; what surrounds a launch the same way in each of them is here, once.  (Not installed.)
 #pragma once
 
@@ -210,6 +210,8 @@ int krylov_describe_append(char *buf, size_t buf_len, const OpState &s, spal_csr
 int krylov_block_describe_append(char *buf, size_t buf_len, const OpState &s, spal_csr *solve);
 // the "gmres" object of a handle spal_*_gmres_* ran with as A (spal_gmres.hip; read under the same lock)
 int gmres_describe_append(char *buf, size_t buf_len, const OpState &s, spal_csr *solve);
+// the "gmres_block" object of a handle spal_*_gmres_block_* ran with as A (spal_gmres_block.hip; the same lock)
+int gmres_block_describe_append(char *buf, size_t buf_len, const OpState &s, spal_csr *solve);
 inline int ops_describe_append(char *buf, size_t buf_len, const OpState &s, spal_csr *solve) {
     SPAL_TRY(describe_append(buf, buf_len, "spgemm", s.spgemm_info));   // a product of spal_*_mul: how it was built
     SPAL_TRY(describe_append(buf, buf_len, "spadd", s.spadd_info));     // a result of spal_*_add / _sub / _neg
@@ -222,6 +224,7 @@ inline int ops_describe_append(char *buf, size_t buf_len, const OpState &s, spal
     SPAL_TRY(krylov_describe_append(buf, buf_len, s, solve));           // spal_*_krylov_* ran with it as A: the last call
     SPAL_TRY(krylov_block_describe_append(buf, buf_len, s, solve));     // spal_*_krylov_block_* ran with it as A: the last call
     SPAL_TRY(gmres_describe_append(buf, buf_len, s, solve));            // spal_*_gmres_* ran with it as A: the last call
+    SPAL_TRY(gmres_block_describe_append(buf, buf_len, s, solve));      // spal_*_gmres_block_* ran with it as A: the last call
     return describe_append(buf, buf_len, "ordering", s.ordering_info);  // a result of spal_*_permute / _multicolour
 }
 

@@ -471,6 +471,35 @@ class _DeviceMatrix:
                                                         C.byref(info)))
         return _krylov_info(info)
 
+    def gmres_block(self, B, M=None, X0=None, restart: int = 30, tol: float = 1e-8, maxit: int = 1000):
+        """Solves A X = B for a host block B of shape (n, k) by restarted GMRES(restart): k independent iterations in
+        lockstep on shared launches, with cycles common to the block (spal_*_gmres_block_*).  Column j is,
+        bit for bit, the GMRES text of include/spal.h on B[:, j] with SpMM's products and the block solves as M^-1; a
+        column whose cycle has ended idles until the others' have, one that has stopped is frozen.  Returns
+        (X, [KrylovInfo] * k)."""
+        B = self._block(B, "gmres_block")
+        n, k = B.shape
+        X = np.zeros_like(B) if X0 is None else np.array(X0, dtype=B.dtype, order="C", copy=True)
+        if X.shape != B.shape:
+            raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT, f"gmres_block: X0 has shape {X.shape} but B {B.shape}")
+        if M is not None and type(M) is not type(self):
+            raise TypeError(f"M must be a {type(self).__name__} (the factor of a matrix of the same format)")
+        infos = (_KrylovInfoC * max(k, 1))()
+        check(self._fn(f"gmres_block_{_sfx(B.dtype)}")(self._h, M._h if M is not None else None, u64(k), _p(B), u64(k),
+                                                       u64(n), _p(X), u64(k), u64(n), u64(restart), C.c_double(tol),
+                                                       u64(maxit), infos))
+        return X, [_krylov_info(c) for c in infos[:k]]
+
+    def gmres_block_dev(self, k: int, b_ptr: int, ldb: int, x_ptr: int, ldx: int, M=None, restart: int = 30,
+                        tol: float = 1e-8, maxit: int = 1000, stream=None):
+        """Device pointers of row-major blocks (element (i, j) at i * ld + j): X holds X0 on entry and the result on
+        exit; the call polls, so it synchronises `stream`.  Returns the k KrylovInfo records."""
+        infos = (_KrylovInfoC * max(int(k), 1))()
+        check(self._fn(f"gmres_block_dev_{_sfx(self.dtype)}")(self._h, M._h if M is not None else None, u64(k),
+                                                              vp(b_ptr), u64(ldb), vp(x_ptr), u64(ldx), u64(restart),
+                                                              C.c_double(tol), u64(maxit), _stream_ptr(stream), infos))
+        return [_krylov_info(c) for c in infos[:int(k)]]
+
     def colour(self, seed: int = 0, stream=None):
         """The greedy colouring of this square matrix's graph by hashed priority (spal_*_colour): exactly
         the sequential text of include/spal.h, by Jones-Plassmann rounds on the device.  Returns (colours as a uint64
@@ -1086,6 +1115,35 @@ class _Compressed:
                 raise TypeError("precond_sweeps needs M, the factor it is an option of")
             M.device(device).set_option("trsv_sweeps", int(precond_sweeps))
         return self.device(device).gmres(b, None if M is None else M.device(device), x0, int(restart), tol, maxit)
+
+    def gmres_block(self, B, M=None, X0=None, restart: int = 30, tol: float = 1e-8, maxit: int = 1000, device: int = 0,
+                    precond_sweeps=None):
+        """X with A X = B for a block of right-hand sides B of shape (n, k) by restarted GMRES(restart): k independent
+        iterations in lockstep, one pass over the matrix per product and one walk of M's launches per solve for all k
+        columns; cycles are common to the block (spal_*_gmres_block_*).  Returns (X, infos) like
+        solve_block(); column j of X and infos[j] are bit for bit the GMRES text of include/spal.h on B[:, j], whatever
+        k, the other columns or the options are.  `M`, `restart` and `precond_sweeps` as in gmres().  A matrix that is
+        not square, a B that is not 2-D or has another first dimension than n, an X0 of another shape than B and a
+        restart outside 1 .. 256 are refused before any device copy is made."""
+        B = np.asarray(B)
+        if self._nrows != self._ncols:
+            raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT,
+                        f"gmres_block: the matrix is not square ({self._nrows} x {self._ncols})")
+        if B.ndim != 2 or B.shape[0] != self._nrows:
+            raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT,
+                        f"gmres_block: B has shape {B.shape} but the matrix has {self._nrows} rows")
+        if X0 is not None and np.shape(X0) != B.shape:
+            raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT, f"gmres_block: X0 has shape {np.shape(X0)} but B {B.shape}")
+        if not 1 <= int(restart) <= 256:
+            raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT, f"gmres_block: restart = {int(restart)} must be 1 .. 256 (one "
+                        "Hessenberg column element per thread of the scalar workgroup)")
+        if M is not None and type(M) is not type(self):
+            raise TypeError(f"M must be a {type(self).__name__}, e.g. self.ilu0()")
+        if precond_sweeps is not None:
+            if M is None:
+                raise TypeError("precond_sweeps needs M, the factor it is an option of")
+            M.device(device).set_option("trsv_sweeps", int(precond_sweeps))
+        return self.device(device).gmres_block(B, None if M is None else M.device(device), X0, int(restart), tol, maxit)
 
     def _mul_mat(self, other, device: int = 0):
         """`&self * &other` (src/csr/ops/mul.rs:5-59 / src/csc/ops/mul.rs:5-60) on the device; the result is downloaded
