@@ -47,6 +47,7 @@ typedef struct spal_csc *spal_csc_t; /* mirrors CscMatrix<T>, src/csc.rs:66-72 *
 typedef struct spal_coo *spal_coo_t; /* mirrors CooMatrix<T>, src/coo.rs:53-57 (SoA on device) */
 typedef struct spal_mg *spal_mg_t;          /* the GPUs of one node + their RCCL communicators */
 typedef struct spal_mg_csr *spal_mg_csr_t;  /* a CsrMatrix partitioned by rows over them */
+typedef struct spal_amg *spal_amg_t;        /* an aggregation multigrid hierarchy (below) */
 
 /* ---- library ---------------------------------------------------------- */
 const char *spal_last_error(void);   /* thread-local, never NULL */
@@ -980,6 +981,119 @@ int spal_csc_permute_vec_f64(spal_csc_t a, const double *x, uint64_t x_len, doub
 int spal_csc_permute_vec_f32(spal_csc_t a, const float *x, uint64_t x_len, float *y, uint64_t y_len, int direction);
 int spal_csc_permute_vec_dev_f64(spal_csc_t a, const double *x_dev, double *y_dev, int direction, void *stream);
 int spal_csc_permute_vec_dev_f32(spal_csc_t a, const float *x_dev, float *y_dev, int direction, void *stream);
+
+/* ---- aggregation AMG: a multigrid cycle as the preconditioner of CG and BiCGStab -----------------------
+ * Not in the reference.  Unsmoothed aggregation: the coarse operators are built with the colouring's hashed priority
+ * and the COO -> CSR assembly, every step of the cycle is SpMV-shaped.  The contract is again a
+ * sequential text the device reproduces bit for bit, in f32 and f64; T is the handle's element type.
+ *
+ *   Graph.      As for the colouring: A is square with n rows; i ~ j iff i != j and (i, j) or (j, i) is stored.  Values
+ *               play no part.  deg(i) = the number of distinct such j (an entry stored in both directions counts once).
+ *   Priority.   prio(i) = (min(deg(i), 2^31 - 1) << 32) | mix32((i + seed) mod 2^32), a 64-bit integer; mix32 is the
+ *               colouring's.  Distinct for n < 2^32.  The degree comes first on purpose: with the key alone, high-key
+ *               roots turn into hubs whose leaves stay singleton aggregates level after level and the coarsening stalls.
+ *   Roots.      Visit the vertices by DESCENDING priority; a vertex becomes a root iff no neighbour is a root already.
+ *               The roots are a maximal independent set: every other vertex has a root among its neighbours.
+ *   Aggregates. Roots are numbered by ascending row; agg[i] = the number of i's root, where the root of a vertex that
+ *               is not one is its neighbouring root of highest priority.  nagg = the number of roots (0 for n = 0); an
+ *               isolated vertex is an aggregate of one.
+ *               The path 0-1-...-7 with seed 0: roots {0, 2, 4, 6}, agg = [0,1,1,2,2,2,3,3].  The 3 x 3 five-point grid
+ *               with seed 0: agg = [0,2,1,2,2,2,3,2,4], nagg = 5.  A star stored in one direction only: one aggregate.
+ *   Coarse matrix.  A_{l+1} = what the COO -> CSR text (below) makes of the triplets (agg[i], agg[j], v) listed in
+ *               A_l's storage order, rows ascending, columns ascending: stable order by (row, col), duplicates summed
+ *               left to right in insertion order, results equal to zero dropped.
+ *   Hierarchy.  A_0 = A.  Level l + 1 is built while ALL of: n_l > coarse_rows;  l + 1 < max_levels;  nagg < n_l;
+ *               every row of A_{l+1} stores its diagonal.  Otherwise level l is the coarsest; L = the number of levels.
+ *   Cycle.      w_l[i] = T(omega) / d_l[i], d_l[i] the stored (i, i) entry (IEEE division; a stored zero is no error,
+ *               it propagates).
+ *                 rowsum(A, x, i):  acc = +0.0;  for each stored (i, j, v) in ascending column, diagonal included:
+ *                                   acc = acc + (v * x[j])          (the product rounded: no FMA)
+ *                 smooth0(l, b):    x[i] = w_l[i] * b[i]
+ *                 smooth(l, b, x):  x'[i] = x[i] + (w_l[i] * (b[i] - rowsum(A_l, x, i)))     (every row from the OLD x)
+ *               cycle(l, b) -> x:
+ *                 x = smooth0(l, b), then s - 1 times smooth;  s = nu for l < L - 1, coarse_sweeps for l = L - 1
+ *                 if l == L - 1: return x
+ *                 gamma times:
+ *                     r[i]  = b[i] - rowsum(A_l, x, i)
+ *                     bc[I] = acc = +0.0;  for the members i of aggregate I in ascending i: acc = acc + r[i]
+ *                     e     = cycle(l + 1, bc)
+ *                     x[i]  = x[i] + (T(alpha) * e[agg[i]])
+ *                 nu times smooth
+ *                 return x
+ *               With L = 1 the cycle is coarse_sweeps damped Jacobi sweeps.  The operator is linear and fixed; for a
+ *               symmetric A it is symmetric (equal pre- and post-smoothing, Jacobi; gamma = 2 squares the correction),
+ *               so CG may use it.  NaN goes by position.
+ *   Krylov.     spal_*_krylov_amg_* are the two loops of spal_*_krylov_* (above), unchanged, with M^-1 v = cycle(0, v).
+ *
+ * Parameters (spal_amg_default_params: {0, 16, 64, 2, 16, 1, 2.0 / 3.0, 1.0}): gamma 1 = V cycle, 2 = W cycle.  Refused
+ * with SPAL_ERR_INVALID_ARGUMENT and a message that names the field: max_levels outside 1 .. 32, nu outside 1 .. 16,
+ * coarse_sweeps outside 1 .. 1024, gamma outside {1, 2}, omega or alpha not finite or <= 0.
+ *
+ * Host, no device: spal_amg_aggregate is the aggregation text on uint64 arrays (it builds the transposed adjacency
+ * itself and refuses what spal_colour_greedy refuses).
+ *
+ * Device (spal_amg.hip).  Setup builds level after level, ordered by the stream alone (no flags, no spins, no grid
+ * sync): degrees by a merge of A's and A^T's rows, the roots by rounds (a vertex decides once every higher-priority
+ * neighbour has decided, and becomes a non-root as soon as one of them is a root; the host polls a counter of undecided
+ * vertices after a batch of rounds, as the colouring does), the join, the numbering by a scan, the member lists by a
+ * stable counting sort, the relabelled triplets through the COO assembly on the device, w_l.  Setup synchronises
+ * `stream`.  The hierarchy holds its OWN copy of level 0's CSR arrays (of a CSC handle: its CSR twin's) and outlives
+ * `a`.  Every work vector of every level is allocated at setup: an apply allocates nothing.
+ * spal_amg_apply_* take host vectors; spal_amg_apply_dev_* are enqueued on `stream` and not synchronised (x_dev ==
+ * b_dev is refused; a capturing stream is refused in this version).  Applies on one handle serialise on its lock; a
+ * call on another stream than the previous call's first makes that stream wait on an event the handle keeps (no host
+ * wait).  The smoother is ONE kernel per sweep (matrix + x + b + w read, x' written to a ping-pong vector); rows of any
+ * length keep the text's order of additions while the products of a long row are formed by a whole wave.
+ * Option "amg_tail_rows" (spal_amg_set_option; default 1024, values above 4096 are clamped to it, 0 = off): all
+ * levels from the first with n_l <= amg_tail_rows down to the coarsest run as ONE single-workgroup launch per visit of
+ * that level, with workgroup barriers between the steps.  The bits do not depend on it.
+ * spal_amg_describe: {dtype, levels, rows[], nnz[], aggregates[], rounds[], setup_ms[], stopped_by ("coarse_rows",
+ * "max_levels", "no_coarsening" or "diagonal"), tail_rows, tail_from_level (= levels when no level runs in the tail),
+ * applies, params}.  spal_amg_level_csr returns an independent handle holding A_level; spal_amg_aggregates the agg[]
+ * of a level that has a coarser one (len = its rows).
+ * spal_*_krylov_amg_*: the arguments of spal_*_krylov_* with `g` where `m` stands; g is not NULL and matches `a` in
+ * rows, device and element type (it need not come from `a` itself).  Default "krylov_check_every" is 1, as with a
+ * factor; describe()["krylov"] of such a call additionally carries "precond": "amg".
+ * SPAL_ERR_INVALID_ARGUMENT: null arguments, wrong lengths, an _f64 entry on an f32 handle or the reverse, a matrix
+ * that is not square, a level-0 row without a stored diagonal (the message names the first such row), a level out of
+ * range.  SPAL_ERR_UNSUPPORTED: a handle held as row blocks.  Nothing leaks on failure.
+ * Not provided: smoothed aggregation, a strength-of-connection threshold, K-cycles, graph capture of the cycle, AMG
+ * inside spal_*_gmres_* and the block solvers, several GPUs, changing cycle parameters after setup, re-setup on new
+ * values with the old aggregates. */
+typedef struct spal_amg_params {
+    uint64_t seed, max_levels, coarse_rows, nu, coarse_sweeps, gamma;
+    double omega, alpha;
+} spal_amg_params;
+int spal_amg_default_params(spal_amg_params *params);
+int spal_amg_aggregate(uint64_t n, const uint64_t *rowptr, const uint64_t *colind, uint64_t seed, uint64_t *agg,
+                       uint64_t *nagg);                                           /* host only */
+int spal_csr_amg_setup(spal_csr_t a, const spal_amg_params *params, void *stream, spal_amg_t *out);
+int spal_csc_amg_setup(spal_csc_t a, const spal_amg_params *params, void *stream, spal_amg_t *out);
+int spal_amg_destroy(spal_amg_t g);                                               /* NULL is fine */
+int spal_amg_describe(spal_amg_t g, char *buf, size_t buf_len);
+int spal_amg_set_option(spal_amg_t g, const char *key, int64_t value);
+int spal_amg_level_csr(spal_amg_t g, uint64_t level, spal_csr_t *copy);
+int spal_amg_aggregates(spal_amg_t g, uint64_t level, uint64_t *agg_host, uint64_t len);
+int spal_amg_apply_f64(spal_amg_t g, const double *b, uint64_t b_len, double *x, uint64_t x_len);
+int spal_amg_apply_f32(spal_amg_t g, const float *b, uint64_t b_len, float *x, uint64_t x_len);
+int spal_amg_apply_dev_f64(spal_amg_t g, const double *b_dev, double *x_dev, void *stream);
+int spal_amg_apply_dev_f32(spal_amg_t g, const float *b_dev, float *x_dev, void *stream);
+int spal_csr_krylov_amg_f64(spal_csr_t a, int method, spal_amg_t g, const double *b, uint64_t b_len, double *x,
+                            uint64_t x_len, double tol, uint64_t maxit, spal_krylov_info *info);
+int spal_csr_krylov_amg_f32(spal_csr_t a, int method, spal_amg_t g, const float *b, uint64_t b_len, float *x,
+                            uint64_t x_len, double tol, uint64_t maxit, spal_krylov_info *info);
+int spal_csr_krylov_amg_dev_f64(spal_csr_t a, int method, spal_amg_t g, const double *b_dev, double *x_dev, double tol,
+                                uint64_t maxit, void *stream, spal_krylov_info *info);
+int spal_csr_krylov_amg_dev_f32(spal_csr_t a, int method, spal_amg_t g, const float *b_dev, float *x_dev, double tol,
+                                uint64_t maxit, void *stream, spal_krylov_info *info);
+int spal_csc_krylov_amg_f64(spal_csc_t a, int method, spal_amg_t g, const double *b, uint64_t b_len, double *x,
+                            uint64_t x_len, double tol, uint64_t maxit, spal_krylov_info *info);
+int spal_csc_krylov_amg_f32(spal_csc_t a, int method, spal_amg_t g, const float *b, uint64_t b_len, float *x,
+                            uint64_t x_len, double tol, uint64_t maxit, spal_krylov_info *info);
+int spal_csc_krylov_amg_dev_f64(spal_csc_t a, int method, spal_amg_t g, const double *b_dev, double *x_dev, double tol,
+                                uint64_t maxit, void *stream, spal_krylov_info *info);
+int spal_csc_krylov_amg_dev_f32(spal_csc_t a, int method, spal_amg_t g, const float *b_dev, float *x_dev, double tol,
+                                uint64_t maxit, void *stream, spal_krylov_info *info);
 
 /* ---- CSR <-> CSC on the device ------------------------------------------------
  * Replace `impl From<&CscMatrix<T>> for CsrMatrix<T>` (src/csr/conv/csc.rs:4-52)

@@ -11,6 +11,7 @@ use std::os::raw::{c_char, c_int, c_void};
 #[repr(C)] pub struct spal_coo { _private: [u8; 0] }
 #[repr(C)] pub struct spal_mg { _private: [u8; 0] }
 #[repr(C)] pub struct spal_mg_csr { _private: [u8; 0] }
+#[repr(C)] pub struct spal_amg { _private: [u8; 0] }
 
 pub const SPAL_OK: c_int = 0;
 pub const SPAL_ERR_INVALID_ARGUMENT: c_int = 1;
@@ -26,6 +27,9 @@ pub const SPAL_KRYLOV_BICGSTAB: c_int = 1;
 /// What spal_*_krylov_* report: reason 0 converged, 1 maxit reached, 2 breakdown / not finite.
 #[repr(C)] #[derive(Clone, Copy, Debug, Default)]
 pub struct spal_krylov_info { pub iterations: u64, pub reason: c_int, pub residual_sq: f64, pub rhs_sq: f64, pub solve_ms: f64 }
+/// The parameters of spal_*_amg_setup; spal_amg_default_params fills in {0, 16, 64, 2, 16, 1, 2/3, 1}.
+#[repr(C)] #[derive(Clone, Copy, Debug, Default)]
+pub struct spal_amg_params { pub seed: u64, pub max_levels: u64, pub coarse_rows: u64, pub nu: u64, pub coarse_sweeps: u64, pub gamma: u64, pub omega: f64, pub alpha: f64 }
 
 #[link(name = "spal_hip")]
 extern "C" {
@@ -166,6 +170,27 @@ extern "C" {
     pub fn spal_csc_permute_vec_f32(a: *mut spal_csc, x: *const f32, x_len: u64, y: *mut f32, y_len: u64, direction: c_int) -> c_int;
     pub fn spal_csc_permute_vec_dev_f64(a: *mut spal_csc, x_dev: *const f64, y_dev: *mut f64, direction: c_int, stream: *mut c_void) -> c_int;
     pub fn spal_csc_permute_vec_dev_f32(a: *mut spal_csc, x_dev: *const f32, y_dev: *mut f32, direction: c_int, stream: *mut c_void) -> c_int;
+    pub fn spal_amg_default_params(params: *mut spal_amg_params) -> c_int;
+    pub fn spal_amg_aggregate(n: u64, rowptr: *const u64, colind: *const u64, seed: u64, agg: *mut u64, nagg: *mut u64) -> c_int;
+    pub fn spal_csr_amg_setup(a: *mut spal_csr, params: *const spal_amg_params, stream: *mut c_void, out: *mut *mut spal_amg) -> c_int;
+    pub fn spal_csc_amg_setup(a: *mut spal_csc, params: *const spal_amg_params, stream: *mut c_void, out: *mut *mut spal_amg) -> c_int;
+    pub fn spal_amg_destroy(g: *mut spal_amg) -> c_int;
+    pub fn spal_amg_describe(g: *mut spal_amg, buf: *mut c_char, buf_len: usize) -> c_int;
+    pub fn spal_amg_set_option(g: *mut spal_amg, key: *const c_char, value: i64) -> c_int;
+    pub fn spal_amg_level_csr(g: *mut spal_amg, level: u64, copy: *mut *mut spal_csr) -> c_int;
+    pub fn spal_amg_aggregates(g: *mut spal_amg, level: u64, agg_host: *mut u64, len: u64) -> c_int;
+    pub fn spal_amg_apply_f64(g: *mut spal_amg, b: *const f64, b_len: u64, x: *mut f64, x_len: u64) -> c_int;
+    pub fn spal_amg_apply_f32(g: *mut spal_amg, b: *const f32, b_len: u64, x: *mut f32, x_len: u64) -> c_int;
+    pub fn spal_amg_apply_dev_f64(g: *mut spal_amg, b_dev: *const f64, x_dev: *mut f64, stream: *mut c_void) -> c_int;
+    pub fn spal_amg_apply_dev_f32(g: *mut spal_amg, b_dev: *const f32, x_dev: *mut f32, stream: *mut c_void) -> c_int;
+    pub fn spal_csr_krylov_amg_f64(a: *mut spal_csr, method: c_int, g: *mut spal_amg, b: *const f64, b_len: u64, x: *mut f64, x_len: u64, tol: f64, maxit: u64, info: *mut spal_krylov_info) -> c_int;
+    pub fn spal_csr_krylov_amg_f32(a: *mut spal_csr, method: c_int, g: *mut spal_amg, b: *const f32, b_len: u64, x: *mut f32, x_len: u64, tol: f64, maxit: u64, info: *mut spal_krylov_info) -> c_int;
+    pub fn spal_csr_krylov_amg_dev_f64(a: *mut spal_csr, method: c_int, g: *mut spal_amg, b_dev: *const f64, x_dev: *mut f64, tol: f64, maxit: u64, stream: *mut c_void, info: *mut spal_krylov_info) -> c_int;
+    pub fn spal_csr_krylov_amg_dev_f32(a: *mut spal_csr, method: c_int, g: *mut spal_amg, b_dev: *const f32, x_dev: *mut f32, tol: f64, maxit: u64, stream: *mut c_void, info: *mut spal_krylov_info) -> c_int;
+    pub fn spal_csc_krylov_amg_f64(a: *mut spal_csc, method: c_int, g: *mut spal_amg, b: *const f64, b_len: u64, x: *mut f64, x_len: u64, tol: f64, maxit: u64, info: *mut spal_krylov_info) -> c_int;
+    pub fn spal_csc_krylov_amg_f32(a: *mut spal_csc, method: c_int, g: *mut spal_amg, b: *const f32, b_len: u64, x: *mut f32, x_len: u64, tol: f64, maxit: u64, info: *mut spal_krylov_info) -> c_int;
+    pub fn spal_csc_krylov_amg_dev_f64(a: *mut spal_csc, method: c_int, g: *mut spal_amg, b_dev: *const f64, x_dev: *mut f64, tol: f64, maxit: u64, stream: *mut c_void, info: *mut spal_krylov_info) -> c_int;
+    pub fn spal_csc_krylov_amg_dev_f32(a: *mut spal_csc, method: c_int, g: *mut spal_amg, b_dev: *const f32, x_dev: *mut f32, tol: f64, maxit: u64, stream: *mut c_void, info: *mut spal_krylov_info) -> c_int;
     pub fn spal_csc_to_csr(a: *mut spal_csc, out: *mut *mut spal_csr) -> c_int;
     pub fn spal_csr_to_csc(a: *mut spal_csr, out: *mut *mut spal_csc) -> c_int;
     pub fn spal_csr_mul(a: *mut spal_csr, b: *mut spal_csr, stream: *mut c_void, out: *mut *mut spal_csr) -> c_int;

@@ -6,8 +6,9 @@ Host-side mirror of the reference's public types (`CsrMatrix`, `CscMatrix`,
 CPU fallback.
 """
 from ._ffi import Panic, SpalError, cache_trim, device_count  # noqa: F401
-from .matrix import (CooMatrix, CscMatrix, CsrMatrix, DeviceCoo, DeviceCsr, DeviceCsc, KrylovInfo, MultiGpuCsr,  # noqa: F401
-                     dot, dot_dev)
+from .matrix import (Amg, CooMatrix, CscMatrix, CsrMatrix, DeviceCoo, DeviceCsr, DeviceCsc, KrylovInfo, MultiGpuCsr,  # noqa: F401
+                     amg_aggregate, dot, dot_dev)
 
 __all__ = ["CsrMatrix", "CscMatrix", "CooMatrix", "DeviceCsr", "DeviceCsc", "DeviceCoo", "MultiGpuCsr", "Panic",
-           "SpalError", "device_count", "cache_trim", "dot", "dot_dev", "KrylovInfo"]
+           "SpalError", "device_count", "cache_trim", "dot", "dot_dev", "KrylovInfo", "Amg",
+           "amg_aggregate"]

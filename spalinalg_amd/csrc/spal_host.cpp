@@ -299,6 +299,78 @@ int spal_colour_greedy(uint64_t n, const uint64_t *rowptr, const uint64_t *colin
     return SPAL_OK;
 }
 
+int spal_amg_default_params(spal_amg_params *params) {
+    if (!params) return fail(SPAL_ERR_INVALID_ARGUMENT, "spal_amg_default_params: null argument");
+    *params = spal_amg_params{0, 16, 64, 2, 16, 1, 2.0 / 3.0, 1.0};
+    return SPAL_OK;
+}
+
+// The aggregation text of include/spal.h as it reads: degrees, vertices by descending priority, roots,
+// the join, the numbering.
+int spal_amg_aggregate(uint64_t n, const uint64_t *rowptr, const uint64_t *colind, uint64_t seed, uint64_t *agg,
+                       uint64_t *nagg) {
+    const char *fn = "spal_amg_aggregate";
+    if (!rowptr || !nagg || (!agg && n)) return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: null array", fn);
+    SPAL_TRY(colour_check_pattern(fn, n, rowptr, colind));
+    const uint64_t nnz = rowptr[n];
+    // the rows of A^T: a counting sort of the entries by column (rows ascending inside a column)
+    std::vector<uint64_t> tptr(n + 1, 0), tind(nnz);
+    for (uint64_t p = 0; p < nnz; ++p) ++tptr[colind[p] + 1];
+    for (uint64_t j = 0; j < n; ++j) tptr[j + 1] += tptr[j];
+    {
+        std::vector<uint64_t> next(tptr.begin(), tptr.end() - 1);
+        for (uint64_t i = 0; i < n; ++i)
+            for (uint64_t p = rowptr[i]; p < rowptr[i + 1]; ++p) tind[next[colind[p]]++] = i;
+    }
+    // the neighbours of every vertex, each once (the rows of a pattern need not be in order here)
+    std::vector<uint64_t> nptr(n + 1, 0), nbr;
+    nbr.reserve(2 * nnz);
+    std::vector<uint64_t> row;
+    for (uint64_t i = 0; i < n; ++i) {
+        row.assign(colind + rowptr[i], colind + rowptr[i + 1]);
+        row.insert(row.end(), tind.begin() + tptr[i], tind.begin() + tptr[i + 1]);
+        std::sort(row.begin(), row.end());
+        row.erase(std::unique(row.begin(), row.end()), row.end());
+        for (uint64_t j : row)
+            if (j != i) nbr.push_back(j);
+        nptr[i + 1] = nbr.size();
+    }
+    std::vector<uint64_t> prio(n);
+    for (uint64_t i = 0; i < n; ++i) {
+        const uint64_t deg = std::min<uint64_t>(nptr[i + 1] - nptr[i], 0x7fffffffull);
+        prio[i] = deg << 32 | colour_mix32((uint32_t)(i + seed));
+    }
+    std::vector<uint64_t> order(n);
+    for (uint64_t i = 0; i < n; ++i) order[i] = i;
+    std::sort(order.begin(), order.end(), [&](uint64_t a, uint64_t b) { return prio[a] > prio[b]; });
+    std::vector<char> root(n, 0);
+    for (const uint64_t v : order) {
+        bool free = true;
+        for (uint64_t p = nptr[v]; p < nptr[v + 1] && free; ++p) free = !root[nbr[p]];
+        root[v] = free ? 1 : 0;
+    }
+    std::vector<uint64_t> number(n, 0);
+    uint64_t count = 0;
+    for (uint64_t i = 0; i < n; ++i)
+        if (root[i]) number[i] = count++;
+    for (uint64_t i = 0; i < n; ++i) {
+        uint64_t r = i;
+        if (!root[i]) {
+            bool any = false;
+            for (uint64_t p = nptr[i]; p < nptr[i + 1]; ++p) {
+                const uint64_t j = nbr[p];
+                if (root[j] && (!any || prio[j] > prio[r])) {
+                    r = j;
+                    any = true;
+                }
+            }
+        }
+        agg[i] = number[r];
+    }
+    *nagg = count;
+    return SPAL_OK;
+}
+
 int spal_perm_from_colours(uint64_t n, const uint64_t *colour, uint64_t *perm) {
     const char *fn = "spal_perm_from_colours";
     if ((!colour || !perm) && n) return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: null array", fn);

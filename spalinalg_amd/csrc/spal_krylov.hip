@@ -25,7 +25,9 @@
 // THE DRIVER HOLDS NO HANDLE LOCK ACROSS A PRODUCT OR A SOLVE: it calls the spal_*_spmv_dev_* / spal_*_trsv_dev_* entry
 // points, each of which takes what it needs itself (f5b9766: re-entering a handle's lock deadlocks).  A factor whose
 // option "trsv_sweeps" is s >= 0 is applied by s Jacobi sweeps per triangle instead (trsv_sweep_enqueue),
-// through two more work vectors of the call.  Plans are built before the first iteration; work vectors, the scratch and the scalar block come from the caching allocator per call,
+// through two more work vectors of the call.  The spal_*_krylov_amg_* entry points run the same two loops with an AMG
+// hierarchy `g` in m's place: M^-1 v is one multigrid cycle (amg_apply_enqueue, spal_amg.hip), enqueued into
+// the hierarchy's own work vectors under its own lock.  Plans are built before the first iteration; work vectors, the scratch and the scalar block come from the caching allocator per call,
 // so concurrent calls on one handle share nothing but the matrix.
 #include "krylov_kernels.hpp"
 
@@ -173,7 +175,7 @@ int dot_dev(const char *fn, int device, const T *a, const T *b, uint64_t n, T *o
 }
 
 struct Record {
-    int method = 0, preconditioned = 0, reason = 0;
+    int method = 0, preconditioned = 0, reason = 0, amg = 0;
     int64_t precond_sweeps = -1;
     uint64_t iterations = 0, polls = 0;
     int64_t check_every = 0;
@@ -183,9 +185,10 @@ std::string info_json(const Record &r) {
     char buf[384];
     snprintf(buf, sizeof buf,
              "{\"method\": \"%s\", \"preconditioned\": %d, \"iterations\": %llu, \"reason\": %d, \"check_every\": %lld, "
-             "\"polls\": %llu, \"solve_ms\": %.4f, \"precond_sweeps\": %lld}",
+             "\"polls\": %llu, \"solve_ms\": %.4f, \"precond_sweeps\": %lld%s}",
              r.method == SPAL_KRYLOV_CG ? "cg" : "bicgstab", r.preconditioned, (unsigned long long)r.iterations, r.reason,
-             (long long)r.check_every, (unsigned long long)r.polls, r.solve_ms, (long long)r.precond_sweeps);
+             (long long)r.check_every, (unsigned long long)r.polls, r.solve_ms, (long long)r.precond_sweeps,
+             r.amg ? ", \"precond\": \"amg\"" : "");   // (the objects written without a hierarchy do not change)
     return buf;
 }
 
@@ -194,6 +197,7 @@ template <typename T, typename H>
 struct Run {
     const char *fn;
     H *a, *m;
+    spal_amg *g = nullptr;   // the other kind of preconditioner: an AMG hierarchy (spal_amg.hip); m is NULL then
     hipStream_t st;
     uint64_t n = 0, maxit = 0, c1 = 0;
     T tol2 = T(0);
@@ -204,7 +208,9 @@ struct Run {
 
     int mul(const T *v, T *out) { return mul_dev(a, v, out, st); }
     // out = M^-1 v (out != v); without a preconditioner the caller uses v itself
-    int prec(const T *v, T *out) { return prec_dev<T, H>(fn, m, sweeps, v, out, w0, w1, st); }
+    int prec(const T *v, T *out) {
+        return g ? amg_apply_enqueue(fn, g, v, out, st) : prec_dev<T, H>(fn, m, sweeps, v, out, w0, w1, st);
+    }
     template <int OP>
     int v(const T *va, const T *vb, const T *vc, const T *vd, T *x, T *y) {
         VecArgs<T> g = {va, vb, vc, vd, x, y, s, part0, part1, n};
@@ -220,17 +226,18 @@ struct Run {
 };
 
 template <typename T, typename H>
-int krylov_run(const char *fn, H *a, int method, H *m, const T *b, T *x, double tol, uint64_t maxit, hipStream_t st,
-               spal_krylov_info *info) {
+int krylov_run(const char *fn, H *a, int method, H *m, spal_amg *g, const T *b, T *x, double tol, uint64_t maxit,
+               hipStream_t st, spal_krylov_info *info) {
     const uint64_t n = a->nrows;
     spal_csr *owner = solve_handle(a);   // whose lock guards a's option and its "krylov" string
-    const int64_t check_every = krylov_check_every_of(a, m != nullptr);
+    const bool pre = m || g;   // M^-1 is there: z, ph and sh are vectors of their own
+    const int64_t check_every = krylov_check_every_of(a, pre);
     SPAL_TRY(refuse_capture(fn, st, "the call polls and synchronises"));
     int64_t sweeps = -1;
     SPAL_TRY(krylov_prepare(fn, a, m, st, &sweeps));
     // work vectors, scratch, scalars
     const bool cg = method == SPAL_KRYLOV_CG;
-    const int nwork = cg ? (m ? 4 : 3) : (m ? 8 : 6);
+    const int nwork = cg ? (pre ? 4 : 3) : (pre ? 8 : 6);
     const int nvec = nwork + (sweeps >= 0 ? 2 : 0);
     DevBuf vecs, parts, scal;
     PinnedBuf host;
@@ -248,6 +255,7 @@ int krylov_run(const char *fn, H *a, int method, H *m, const T *b, T *x, double 
     R.fn = fn;
     R.a = a;
     R.m = m;
+    R.g = g;
     R.st = st;
     R.n = n;
     R.maxit = maxit;
@@ -281,8 +289,8 @@ int krylov_run(const char *fn, H *a, int method, H *m, const T *b, T *x, double 
     uint64_t enqueued = 0;
     bool stopped = false;
     if (cg) {
-        T *z = m ? vec_at(3) : r;
-        if (m) SPAL_TRY(R.prec(r, z));
+        T *z = pre ? vec_at(3) : r;
+        if (pre) SPAL_TRY(R.prec(r, z));
         SPAL_TRY((R.template v<V_COPY_DOT>(r, z, nullptr, nullptr, nullptr, p)));   // p = z;  rz
         SPAL_TRY((R.template f<F_RZ>()));
         while (enqueued < maxit && !stopped) {
@@ -292,8 +300,8 @@ int krylov_run(const char *fn, H *a, int method, H *m, const T *b, T *x, double 
                 SPAL_TRY((R.template v<V_DOT>(p, q, nullptr, nullptr, nullptr, nullptr)));
                 SPAL_TRY((R.template f<F_ALPHA_CG>()));
                 SPAL_TRY((R.template v<V_CG_XR>(p, q, nullptr, nullptr, x, r)));      // x, r;  rr
-                SPAL_TRY((R.template f<F_TEST_CG>(m ? 0 : 1)));                      // it, test (and beta when z is r)
-                if (m) {
+                SPAL_TRY((R.template f<F_TEST_CG>(pre ? 0 : 1)));                    // it, test (and beta when z is r)
+                if (pre) {
                     SPAL_TRY(R.prec(r, z));
                     SPAL_TRY((R.template v<V_DOT>(r, z, nullptr, nullptr, nullptr, nullptr)));
                     SPAL_TRY((R.template f<F_BETA>()));
@@ -307,7 +315,7 @@ int krylov_run(const char *fn, H *a, int method, H *m, const T *b, T *x, double 
     } else {
         T *rhat = vec_at(3), *vv = vec_at(4), *t = vec_at(5);
         T *sv = q;   // q is free once r exists
-        T *ph = m ? vec_at(6) : p, *sh = m ? vec_at(7) : sv;
+        T *ph = pre ? vec_at(6) : p, *sh = pre ? vec_at(7) : sv;
         SPAL_HIP_TRY(hipMemcpyAsync(rhat, r, n * sizeof(T), hipMemcpyDeviceToDevice, st));
         SPAL_HIP_TRY(hipMemsetAsync(vv, 0, n * sizeof(T), st));
         SPAL_HIP_TRY(hipMemsetAsync(p, 0, n * sizeof(T), st));
@@ -317,14 +325,14 @@ int krylov_run(const char *fn, H *a, int method, H *m, const T *b, T *x, double 
                 SPAL_TRY((R.template v<V_DOT>(rhat, r, nullptr, nullptr, nullptr, nullptr)));
                 SPAL_TRY((R.template f<F_RHO>()));
                 SPAL_TRY((R.template v<V_BI_P>(r, vv, nullptr, nullptr, nullptr, p)));
-                if (m) SPAL_TRY(R.prec(p, ph));
+                if (pre) SPAL_TRY(R.prec(p, ph));
                 SPAL_TRY(R.mul(ph, vv));
                 SPAL_TRY((R.template v<V_DOT>(rhat, vv, nullptr, nullptr, nullptr, nullptr)));
                 SPAL_TRY((R.template f<F_ALPHA_BI>()));
                 SPAL_TRY((R.template v<V_BI_S>(r, vv, nullptr, nullptr, nullptr, sv)));   // s;  ss
                 SPAL_TRY((R.template f<F_HALF>()));                                       // it;  the half-step exit
                 SPAL_TRY((R.template v<V_BI_HALF>(ph, sv, nullptr, nullptr, x, r)));      // ... applied, if taken
-                if (m) SPAL_TRY(R.prec(sv, sh));
+                if (pre) SPAL_TRY(R.prec(sv, sh));
                 SPAL_TRY(R.mul(sh, t));
                 SPAL_TRY((R.template v<V_DOT2>(t, sv, nullptr, nullptr, nullptr, nullptr)));   // t . s, t . t
                 SPAL_TRY((R.template f<F_OMEGA>()));
@@ -349,7 +357,8 @@ int krylov_run(const char *fn, H *a, int method, H *m, const T *b, T *x, double 
     info->solve_ms = (double)ms;
     Record rec;
     rec.method = method;
-    rec.preconditioned = m ? 1 : 0;
+    rec.preconditioned = pre ? 1 : 0;
+    rec.amg = g ? 1 : 0;
     rec.precond_sweeps = sweeps;
     rec.reason = info->reason;
     rec.iterations = info->iterations;
@@ -363,29 +372,32 @@ int krylov_run(const char *fn, H *a, int method, H *m, const T *b, T *x, double 
 }
 
 // every refusal that needs no device
+// (amg: the call takes a hierarchy `g` where m stands, and g is not NULL)
 template <typename T, typename H>
-int krylov_check(const char *fn, H *a, int method, H *m, const T *b, T *x, double tol, spal_krylov_info *info) {
-    if (!a || !b || !x || !info) return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: null argument", fn);
+int krylov_check(const char *fn, H *a, int method, H *m, const T *b, T *x, double tol, spal_krylov_info *info,
+                 bool amg = false, spal_amg *g = nullptr) {
+    if (!a || !b || !x || !info || (amg && !g)) return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: null argument", fn);
     SPAL_TRY(check_dtype<T>(fn, a->elem_size));
     if (method != SPAL_KRYLOV_CG && method != SPAL_KRYLOV_BICGSTAB)
         return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: method = %d must be 0 (CG) or 1 (BiCGStab)", fn, method);
-    return krylov_check_operands<T, H>(fn, a, m, tol);
+    SPAL_TRY((krylov_check_operands<T, H>(fn, a, m, tol)));
+    return amg ? amg_check_match(fn, g, a->nrows, a->device, a->elem_size) : SPAL_OK;
 }
 
 template <typename T, typename H>
 int krylov_dev(const char *fn, H *a, int method, H *m, const T *b, T *x, double tol, uint64_t maxit, void *stream,
-               spal_krylov_info *info) {
-    SPAL_TRY((krylov_check<T, H>(fn, a, method, m, b, x, tol, info)));
+               spal_krylov_info *info, bool amg = false, spal_amg *g = nullptr) {
+    SPAL_TRY((krylov_check<T, H>(fn, a, method, m, b, x, tol, info, amg, g)));
     if (x == b) return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: x_dev == b_dev (b is read in every test of the residual)", fn);
     DeviceGuard guard(a->device);
     if (guard.status != SPAL_OK) return guard.status;
-    return krylov_run<T, H>(fn, a, method, m, b, x, tol, maxit, (hipStream_t)stream, info);
+    return krylov_run<T, H>(fn, a, method, m, g, b, x, tol, maxit, (hipStream_t)stream, info);
 }
 
 template <typename T, typename H>
 int krylov_host(const char *fn, H *a, int method, H *m, const T *b, uint64_t b_len, T *x, uint64_t x_len, double tol,
-                uint64_t maxit, spal_krylov_info *info) {
-    SPAL_TRY((krylov_check<T, H>(fn, a, method, m, b, x, tol, info)));
+                uint64_t maxit, spal_krylov_info *info, bool amg = false, spal_amg *g = nullptr) {
+    SPAL_TRY((krylov_check<T, H>(fn, a, method, m, b, x, tol, info, amg, g)));
     SPAL_TRY(refuse_lengths(fn, b_len, x_len, a->nrows));
     DeviceGuard guard(a->device);
     if (guard.status != SPAL_OK) return guard.status;
@@ -397,7 +409,7 @@ int krylov_host(const char *fn, H *a, int method, H *m, const T *b, uint64_t b_l
     SPAL_HIP_TRY(stream_acquire(&ps.s));
     SPAL_HIP_TRY(hipMemcpyAsync(db.p, b, n * sizeof(T), hipMemcpyHostToDevice, ps.s));
     SPAL_HIP_TRY(hipMemcpyAsync(dx.p, x, n * sizeof(T), hipMemcpyHostToDevice, ps.s));
-    SPAL_TRY((krylov_run<T, H>(fn, a, method, m, db.as<T>(), dx.as<T>(), tol, maxit, ps.s, info)));
+    SPAL_TRY((krylov_run<T, H>(fn, a, method, m, g, db.as<T>(), dx.as<T>(), tol, maxit, ps.s, info)));
     SPAL_HIP_TRY(hipMemcpyAsync(x, dx.p, n * sizeof(T), hipMemcpyDeviceToHost, ps.s));
     SPAL_HIP_TRY(hipStreamSynchronize(ps.s));
     return SPAL_OK;
@@ -473,6 +485,40 @@ int spal_csc_krylov_dev_f64(spal_csc_t a, int method, spal_csc_t m, const double
 int spal_csc_krylov_dev_f32(spal_csc_t a, int method, spal_csc_t m, const float *b_dev, float *x_dev, double tol,
                             uint64_t maxit, void *stream, spal_krylov_info *info) {
     return krylov_dev<float, spal_csc>("spal_csc_krylov_dev", a, method, m, b_dev, x_dev, tol, maxit, stream, info);
+}
+
+// the same loops with M^-1 v = cycle(0, v) of an AMG hierarchy (spal_amg.hip)
+int spal_csr_krylov_amg_f64(spal_csr_t a, int method, spal_amg_t g, const double *b, uint64_t b_len, double *x, uint64_t x_len,
+                            double tol, uint64_t maxit, spal_krylov_info *info) {
+    return krylov_host<double, spal_csr>("spal_csr_krylov_amg", a, method, nullptr, b, b_len, x, x_len, tol, maxit, info, true, g);
+}
+int spal_csr_krylov_amg_dev_f64(spal_csr_t a, int method, spal_amg_t g, const double *b_dev, double *x_dev, double tol,
+                                uint64_t maxit, void *stream, spal_krylov_info *info) {
+    return krylov_dev<double, spal_csr>("spal_csr_krylov_amg_dev", a, method, nullptr, b_dev, x_dev, tol, maxit, stream, info, true, g);
+}
+int spal_csr_krylov_amg_f32(spal_csr_t a, int method, spal_amg_t g, const float *b, uint64_t b_len, float *x, uint64_t x_len,
+                            double tol, uint64_t maxit, spal_krylov_info *info) {
+    return krylov_host<float, spal_csr>("spal_csr_krylov_amg", a, method, nullptr, b, b_len, x, x_len, tol, maxit, info, true, g);
+}
+int spal_csr_krylov_amg_dev_f32(spal_csr_t a, int method, spal_amg_t g, const float *b_dev, float *x_dev, double tol,
+                                uint64_t maxit, void *stream, spal_krylov_info *info) {
+    return krylov_dev<float, spal_csr>("spal_csr_krylov_amg_dev", a, method, nullptr, b_dev, x_dev, tol, maxit, stream, info, true, g);
+}
+int spal_csc_krylov_amg_f64(spal_csc_t a, int method, spal_amg_t g, const double *b, uint64_t b_len, double *x, uint64_t x_len,
+                            double tol, uint64_t maxit, spal_krylov_info *info) {
+    return krylov_host<double, spal_csc>("spal_csc_krylov_amg", a, method, nullptr, b, b_len, x, x_len, tol, maxit, info, true, g);
+}
+int spal_csc_krylov_amg_dev_f64(spal_csc_t a, int method, spal_amg_t g, const double *b_dev, double *x_dev, double tol,
+                                uint64_t maxit, void *stream, spal_krylov_info *info) {
+    return krylov_dev<double, spal_csc>("spal_csc_krylov_amg_dev", a, method, nullptr, b_dev, x_dev, tol, maxit, stream, info, true, g);
+}
+int spal_csc_krylov_amg_f32(spal_csc_t a, int method, spal_amg_t g, const float *b, uint64_t b_len, float *x, uint64_t x_len,
+                            double tol, uint64_t maxit, spal_krylov_info *info) {
+    return krylov_host<float, spal_csc>("spal_csc_krylov_amg", a, method, nullptr, b, b_len, x, x_len, tol, maxit, info, true, g);
+}
+int spal_csc_krylov_amg_dev_f32(spal_csc_t a, int method, spal_amg_t g, const float *b_dev, float *x_dev, double tol,
+                                uint64_t maxit, void *stream, spal_krylov_info *info) {
+    return krylov_dev<float, spal_csc>("spal_csc_krylov_amg_dev", a, method, nullptr, b_dev, x_dev, tol, maxit, stream, info, true, g);
 }
 
 }  // extern "C"

@@ -1,5 +1,5 @@
 // spal_ops.hpp -- the host layer the sparse operations share: spal_spgemm.hip, spal_spadd.hip,
-// spal_spmm.hip, spal_trsv.hip, spal_trsv_sweep.hip, spal_trsm.hip, spal_ilu.hip, spal_ilu_sweep.hip, spal_krylov.hip, spal_krylov_block.hip, spal_gmres.hip, spal_gmres_block.hip and spal_colour.hip keep their kernels, their driver, their option's validation and their
+// spal_spmm.hip, spal_trsv.hip, spal_trsv_sweep.hip, spal_trsm.hip, spal_ilu.hip, spal_ilu_sweep.hip, spal_krylov.hip, spal_krylov_block.hip, spal_gmres.hip, spal_gmres_block.hip, spal_colour.hip and spal_amg.hip keep their kernels, their driver, their option's validation and their
 // info JSON; what surrounds a launch the same way in each of them is here, once.  (Not installed.)
 #pragma once
 
@@ -175,6 +175,12 @@ int trsv_sweep_prepare(const char *fn, spal_csr *a, int unit_diag, hipStream_t s
 int trsv_sweep_enqueue(const char *fn, spal_csr *a, int uplo, int unit_diag, uint64_t sweeps, const void *b, void *x,
                        void *w0, void *w1, hipStream_t st);
 int64_t trsv_sweeps_of(spal_csr *a);   // the option "trsv_sweeps" of a solve handle, read under its lock
+
+// ---- the AMG hierarchy as a preconditioner (spal_amg.hip), for spal_krylov.hip -----------------------------
+// match: g is there and agrees with a matrix of `nrows` rows in rows, device and element type.  enqueue: x = cycle(0, b)
+// on `st` (x != b, device vectors of g's element type); takes g's lock, allocates and synchronises nothing.
+int amg_check_match(const char *fn, const spal_amg *g, uint64_t nrows, int device, int elem_size);
+int amg_apply_enqueue(const char *fn, spal_amg *g, const void *b, void *x, hipStream_t st);
 
 // ---- per-operation state of a handle (spal_internal.hpp: OpState), set and described in one place -------------------
 // Each operation file implements its own: 1 = the key is this operation's and *status says how setting it went, 0 =

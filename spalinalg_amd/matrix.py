@@ -117,6 +117,115 @@ def dot_dev(dtype, a_ptr: int, b_ptr: int, n: int, out_ptr: int, device: int = 0
 
 
 # --------------------------------------------------------------------------
+# aggregation AMG (include/spal.h)
+# --------------------------------------------------------------------------
+class _AmgParamsC(C.Structure):
+    """spal_amg_params"""
+    _fields_ = [("seed", C.c_uint64), ("max_levels", C.c_uint64), ("coarse_rows", C.c_uint64), ("nu", C.c_uint64),
+                ("coarse_sweeps", C.c_uint64), ("gamma", C.c_uint64), ("omega", C.c_double), ("alpha", C.c_double)]
+
+
+def _amg_params(seed, max_levels, coarse_rows, nu, coarse_sweeps, cycle, omega, alpha) -> _AmgParamsC:
+    if not isinstance(cycle, str) or cycle.lower() not in ("v", "w"):
+        raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT, f"amg: cycle {cycle!r} must be 'v' or 'w'")
+    for name, v in (("seed", seed), ("max_levels", max_levels), ("coarse_rows", coarse_rows), ("nu", nu),
+                    ("coarse_sweeps", coarse_sweeps)):
+        if int(v) < 0:
+            raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT, f"amg: {name} = {int(v)} is negative")
+    return _AmgParamsC(int(seed), int(max_levels), int(coarse_rows), int(nu), int(coarse_sweeps),
+                       1 if cycle.lower() == "v" else 2, float(omega), float(alpha))
+
+
+def amg_aggregate(rowptr, colind, seed: int = 0):
+    """(agg, nagg): the aggregation text of include/spal.h on the pattern (rowptr, colind) of a square matrix, on the
+    host (spal_amg_aggregate): no device needed."""
+    rowptr, colind = _idx(rowptr), _idx(colind)
+    if rowptr.size < 1:
+        raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT, "amg_aggregate: rowptr is empty")
+    n = rowptr.size - 1
+    agg = np.empty(n, dtype=np.uint64)
+    nagg = u64()
+    check(_ffi.lib().spal_amg_aggregate(u64(n), _p(rowptr), _p(colind), u64(seed), _p(agg), C.byref(nagg)))
+    return agg, nagg.value
+
+
+class Amg:
+    """An aggregation multigrid hierarchy on the device (spal_*_amg_setup): apply(b) is one cycle, bit for bit the text
+    of include/spal.h; `a.solve(b, M=g)` preconditions CG / BiCGStab with it.  It holds its own copy of the matrix and
+    outlives the matrix it was built from."""
+
+    def __init__(self, handle, dtype, device: int, nrows: int):
+        self._h = handle
+        self.dtype = np.dtype(dtype)
+        self.device = device
+        self._nrows = int(nrows)
+
+    def close(self):
+        if self._h is not None:
+            _ffi.lib().spal_amg_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def nrows(self) -> int:
+        return self._nrows
+
+    def describe(self) -> dict:
+        buf = C.create_string_buffer(16384)
+        check(_ffi.lib().spal_amg_describe(self._h, buf, C.c_size_t(len(buf))))
+        return json.loads(buf.value.decode())
+
+    def set_option(self, key: str, value: int) -> None:
+        check(_ffi.lib().spal_amg_set_option(self._h, key.encode(), C.c_int64(value)))
+
+    def apply(self, b) -> np.ndarray:
+        """x = cycle(0, b) for a host vector of the hierarchy's dtype."""
+        b = np.ascontiguousarray(b)
+        if b.dtype not in (np.float32, np.float64):
+            b = b.astype(self.dtype)
+        if b.ndim != 1:
+            raise TypeError("apply() takes one 1-D vector")
+        x = np.empty_like(b)
+        check(getattr(_ffi.lib(), f"spal_amg_apply_{_sfx(b.dtype)}")(self._h, _p(b), u64(b.size), _p(x), u64(x.size)))
+        return x
+
+    def apply_dev(self, b_ptr: int, x_ptr: int, stream=None, dtype=None) -> None:
+        """Device pointers (x != b): enqueued on `stream`, not synchronised."""
+        dt = self.dtype if dtype is None else np.dtype(dtype)
+        check(getattr(_ffi.lib(), f"spal_amg_apply_dev_{_sfx(dt)}")(self._h, vp(b_ptr), vp(x_ptr), _stream_ptr(stream)))
+
+    def level(self, l: int) -> "CsrMatrix":
+        """A_l as a CsrMatrix (an independent copy, downloaded; it keeps its device handle)."""
+        out = vp()
+        check(_ffi.lib().spal_amg_level_csr(self._h, u64(l), C.byref(out)))
+        dev = DeviceCsr(out, self.dtype, self.device)
+        n = dev.shape()[0]
+        ptr, ind, val = dev.download()
+        m = CsrMatrix._trusted(n, n, ptr, ind, val)
+        m._dev[self.device] = dev
+        return m
+
+    def aggregates(self, l: int) -> np.ndarray:
+        """agg[] of level l, which must have a coarser level."""
+        rows = self.describe()["rows"]
+        if not 0 <= int(l) < len(rows):
+            raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT, f"aggregates: level = {l} but the hierarchy has {len(rows)}")
+        agg = np.empty(rows[int(l)], dtype=np.uint64)
+        check(_ffi.lib().spal_amg_aggregates(self._h, u64(l), _p(agg), u64(agg.size)))
+        return agg
+
+
+def _refuse_amg(M, what: str) -> None:
+    if isinstance(M, Amg):
+        raise TypeError(f"{what} takes an ILU(0) factor as M, not an Amg: an AMG hierarchy preconditions solve() "
+                        "(method 'cg' or 'bicgstab') only")
+
+
+# --------------------------------------------------------------------------
 # device handles
 # --------------------------------------------------------------------------
 class _DeviceMatrix:
@@ -398,9 +507,14 @@ class _DeviceMatrix:
         if b.ndim != 1:
             raise TypeError("krylov() takes one right-hand side, a 1-D vector")
         x = np.zeros_like(b) if x0 is None else np.array(x0, dtype=b.dtype, order="C", copy=True)
+        info = _KrylovInfoC()
+        if isinstance(M, Amg):   # the same loops with M^-1 v = one multigrid cycle (spal_*_krylov_amg_*)
+            check(self._fn(f"krylov_amg_{_sfx(b.dtype)}")(self._h, C.c_int(_krylov_method(method)), M._h, _p(b),
+                                                          u64(b.size), _p(x), u64(x.size), C.c_double(tol), u64(maxit),
+                                                          C.byref(info)))
+            return x, _krylov_info(info)
         if M is not None and type(M) is not type(self):
             raise TypeError(f"M must be a {type(self).__name__} (the factor of a matrix of the same format)")
-        info = _KrylovInfoC()
         check(self._fn(f"krylov_{_sfx(b.dtype)}")(self._h, C.c_int(_krylov_method(method)), M._h if M is not None else None,
                                                   _p(b), u64(b.size), _p(x), u64(x.size), C.c_double(tol), u64(maxit),
                                                   C.byref(info)))
@@ -410,6 +524,11 @@ class _DeviceMatrix:
                    stream=None) -> KrylovInfo:
         """Device pointers: x holds x0 on entry and the result on exit; the call polls, so it synchronises `stream`."""
         info = _KrylovInfoC()
+        if isinstance(M, Amg):
+            check(self._fn(f"krylov_amg_dev_{_sfx(self.dtype)}")(self._h, C.c_int(_krylov_method(method)), M._h,
+                                                                 vp(b_ptr), vp(x_ptr), C.c_double(tol), u64(maxit),
+                                                                 _stream_ptr(stream), C.byref(info)))
+            return _krylov_info(info)
         check(self._fn(f"krylov_dev_{_sfx(self.dtype)}")(self._h, C.c_int(_krylov_method(method)),
                                                          M._h if M is not None else None, vp(b_ptr), vp(x_ptr),
                                                          C.c_double(tol), u64(maxit), _stream_ptr(stream), C.byref(info)))
@@ -420,6 +539,7 @@ class _DeviceMatrix:
         shared launches (spal_*_krylov_block_*).  Column j is, bit for bit, the loop of include/spal.h on
         B[:, j] with SpMM's products and the block solves as M^-1; a column that has stopped is frozen while the others
         run on.  Returns (X, [KrylovInfo] * k)."""
+        _refuse_amg(M, "krylov_block()")
         B = self._block(B, "krylov_block")
         n, k = B.shape
         X = np.zeros_like(B) if X0 is None else np.array(X0, dtype=B.dtype, order="C", copy=True)
@@ -449,6 +569,7 @@ class _DeviceMatrix:
         by `M` as krylov() is (an ILU(0) factor handle of this class: two solves, or "trsv_sweeps" sweeps per triangle).
         Host vectors; returns (x, KrylovInfo).  Bit for bit the text written out in include/spal.h, whatever
         "krylov_check_every" is."""
+        _refuse_amg(M, "gmres()")
         b = np.ascontiguousarray(b)
         if b.dtype not in (np.float32, np.float64):
             b = b.astype(self.dtype)
@@ -477,6 +598,7 @@ class _DeviceMatrix:
         bit for bit, the GMRES text of include/spal.h on B[:, j] with SpMM's products and the block solves as M^-1; a
         column whose cycle has ended idles until the others' have, one that has stopped is frozen.  Returns
         (X, [KrylovInfo] * k)."""
+        _refuse_amg(M, "gmres_block()")
         B = self._block(B, "gmres_block")
         n, k = B.shape
         X = np.zeros_like(B) if X0 is None else np.array(X0, dtype=B.dtype, order="C", copy=True)
@@ -499,6 +621,15 @@ class _DeviceMatrix:
                                                               vp(b_ptr), u64(ldb), vp(x_ptr), u64(ldx), u64(restart),
                                                               C.c_double(tol), u64(maxit), _stream_ptr(stream), infos))
         return [_krylov_info(c) for c in infos[:int(k)]]
+
+    def amg(self, seed: int = 0, max_levels: int = 16, coarse_rows: int = 64, nu: int = 2, coarse_sweeps: int = 16,
+            cycle: str = "v", omega: float = 2.0 / 3.0, alpha: float = 1.0, stream=None) -> Amg:
+        """The aggregation AMG hierarchy of this square matrix (spal_*_amg_setup): an Amg, built on the
+        device level after level; synchronises `stream`."""
+        params = _amg_params(seed, max_levels, coarse_rows, nu, coarse_sweeps, cycle, omega, alpha)
+        out = vp()
+        check(self._fn("amg_setup")(self._h, C.byref(params), _stream_ptr(stream), C.byref(out)))
+        return Amg(out, self.dtype, self.device, self.shape()[0])
 
     def colour(self, seed: int = 0, stream=None):
         """The greedy colouring of this square matrix's graph by hashed priority (spal_*_colour): exactly
@@ -1057,6 +1188,10 @@ class _Compressed:
             raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT, f"solve: b has shape {b.shape} but the matrix has {self._nrows} rows")
         if x0 is not None and np.shape(x0) != b.shape:
             raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT, f"solve: x0 has shape {np.shape(x0)} but b {b.shape}")
+        if isinstance(M, Amg):   # M^-1 v = one multigrid cycle: `M = a.amg()`
+            if precond_sweeps is not None:
+                raise TypeError("precond_sweeps is an option of an ILU(0) factor: an Amg has no triangular sweeps")
+            return self.device(device).krylov(b, method, M, x0, tol, maxit)
         if M is not None and type(M) is not type(self):
             raise TypeError(f"M must be a {type(self).__name__}, e.g. self.ilu0()")
         if precond_sweeps is not None:
@@ -1074,6 +1209,7 @@ class _Compressed:
         columns or the options are.  `M` and `precond_sweeps` as in solve(), which keeps taking one 1-D right-hand
         side.  A matrix that is not square, a B that is not 2-D or has another first dimension than n and an X0 of
         another shape than B are refused before any device copy is made."""
+        _refuse_amg(M, "solve_block()")
         B = np.asarray(B)
         if self._nrows != self._ncols:
             raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT,
@@ -1098,6 +1234,7 @@ class _Compressed:
         solve().  Returns (x, info) as solve() does: reasons 0 and 1 are decided on the true residual, recomputed at
         the head of every cycle.  restart is 1 .. 256; the call holds restart + 1 basis vectors on the device.  Bit for
         bit the text of include/spal.h."""
+        _refuse_amg(M, "gmres()")
         b = np.asarray(b)
         if self._nrows != self._ncols:
             raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT, f"gmres: the matrix is not square ({self._nrows} x {self._ncols})")
@@ -1125,6 +1262,7 @@ class _Compressed:
         k, the other columns or the options are.  `M`, `restart` and `precond_sweeps` as in gmres().  A matrix that is
         not square, a B that is not 2-D or has another first dimension than n, an X0 of another shape than B and a
         restart outside 1 .. 256 are refused before any device copy is made."""
+        _refuse_amg(M, "gmres_block()")
         B = np.asarray(B)
         if self._nrows != self._ncols:
             raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT,
@@ -1222,6 +1360,21 @@ class _Compressed:
         if sweeps is not None:
             sweeps = _sweep_count(sweeps)              # refused before anything is uploaded
         return self._adopt_result(self.device(device).ilu0(sweeps=sweeps), device)
+
+    def amg(self, seed: int = 0, max_levels: int = 16, coarse_rows: int = 64, nu: int = 2, coarse_sweeps: int = 16,
+            cycle: str = "v", omega: float = 2.0 / 3.0, alpha: float = 1.0, device: int = 0) -> Amg:
+        """The aggregation AMG hierarchy of this square matrix, an :class:`Amg` (spal_*_amg_setup):
+        unsmoothed aggregation by hashed priority with the degree first, Galerkin coarse matrices through the COO
+        assembly, a V (`cycle="v"`) or W cycle with `nu` damped Jacobi sweeps (weight `omega`) before and after,
+        `coarse_sweeps` on the coarsest level, the coarse correction scaled by `alpha`.  Every row must store its
+        diagonal.  Its iteration counts grow slowly with the problem size where ILU(0)'s and Jacobi's do not::
+
+            g = a.amg(cycle="w", alpha=1.5)
+            x, info = a.solve(b, M=g)
+        """
+        self._square("amg")
+        _amg_params(seed, max_levels, coarse_rows, nu, coarse_sweeps, cycle, omega, alpha)   # refused before any upload
+        return self.device(device).amg(seed, max_levels, coarse_rows, nu, coarse_sweeps, cycle, omega, alpha)
 
     def _square(self, what: str) -> None:
         if self._nrows != self._ncols:

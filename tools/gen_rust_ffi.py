@@ -15,9 +15,9 @@ OUT = os.path.join(ROOT, "rust_shim", "src", "ffi.rs")
 
 SCALARS = {"int": "c_int", "uint64_t": "u64", "uint32_t": "u32", "int64_t": "i64", "size_t": "usize", "double": "f64",
            "float": "f32", "void": "c_void", "char": "c_char"}
-STRUCTS = {"spal_krylov_info": "spal_krylov_info"}   # plain structs passed by pointer, declared in render()
+STRUCTS = {"spal_krylov_info": "spal_krylov_info", "spal_amg_params": "spal_amg_params"}   # plain structs passed by pointer, declared in render()
 HANDLES = {"spal_csr_t": "spal_csr", "spal_csc_t": "spal_csc", "spal_coo_t": "spal_coo", "spal_mg_t": "spal_mg",
-           "spal_mg_csr_t": "spal_mg_csr"}
+           "spal_mg_csr_t": "spal_mg_csr", "spal_amg_t": "spal_amg"}
 
 
 def rust_type(ctype: str) -> str:
@@ -84,6 +84,10 @@ def render(fns) -> str:
               '#[repr(C)] #[derive(Clone, Copy, Debug, Default)]',
               'pub struct spal_krylov_info { pub iterations: u64, pub reason: c_int, pub residual_sq: f64, pub rhs_sq: f64, '
               'pub solve_ms: f64 }',
+              '/// The parameters of spal_*_amg_setup; spal_amg_default_params fills in {0, 16, 64, 2, 16, 1, 2/3, 1}.',
+              '#[repr(C)] #[derive(Clone, Copy, Debug, Default)]',
+              'pub struct spal_amg_params { pub seed: u64, pub max_levels: u64, pub coarse_rows: u64, pub nu: u64, '
+              'pub coarse_sweeps: u64, pub gamma: u64, pub omega: f64, pub alpha: f64 }',
               '',
               '#[link(name = "spal_hip")]',
               'extern "C" {']
