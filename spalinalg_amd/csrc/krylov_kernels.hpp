@@ -1,12 +1,16 @@
 // krylov_kernels.hpp -- what spal_krylov.hip (the dot product, CG, BiCGStab: DESIGN 3.14), spal_krylov_block.hip (the
 // same two loops on a block of right-hand sides: DESIGN 3.22), spal_gmres.hip (GMRES: DESIGN 3.17) and
 // spal_gmres_block.hip (GMRES on a block: DESIGN 3.23) share: the tile sum and the upper levels of reduce(), the scalar
-// block, the fused vector updates and the scalar steps of CG and BiCGStab, the sizes of a dot's scratch, the entry
-// points a driver goes through by handle and element type, the preparation of the plans, M^-1, the refusals that need no
-// device, two scope guards, and for the block drivers the column tiles, column_tree and the routes to SpMM and trsm.
+// block, the fused vector updates and the scalar steps of CG and BiCGStab (their names, and the two loops that enqueue
+// them, are in krylov_loops.hpp), the sizes of a dot's scratch, the entry points a driver goes through by handle and
+// element type, the preparation of the plans, M^-1, the refusals that need no device, and the frame of a call: the
+// launch-and-check macro, SolveFrame (pinned heads, polls, device time), the locked store of a describe string and the
+// staging of host vectors.  For the block drivers: the column tiles and their dispatch macro, column_tree, the routes
+// to SpMM and trsm, M^-1 on a block, the refusals of k / ldb / ldx, the sweep scratch and the staging of host blocks.
 // The contracts are written out in include/spal.h.  (Not installed.)
 #pragma once
 
+#include "krylov_loops.hpp"
 #include "spal_ops.hpp"
 
 #include <cmath>
@@ -75,19 +79,7 @@ struct Scal {
     unsigned done, reason, half, pad;
 };
 
-// ---- the first level, fused with the vector update in front of it ---------------------------------------------------
-enum VecOp {
-    V_DOT,      // d0 = a . b
-    V_DOT2,     // d0 = a . b, d1 = a . a
-    V_INIT,     // y = a - b;  d0 = y . y, d1 = a . a                                   (r = b - q;  rr, bb)
-    V_COPY_DOT, // y = b;  d0 = a . b                                                   (p = z;  rz)
-    V_CG_XR,    // x += alpha * a;  y -= alpha * b;  d0 = y . y                         (x, r;  rr)
-    V_CG_P,     // y = a + beta * y                                                     (p = z + beta p)
-    V_BI_P,     // y = a + beta * (y - omega * b)                                       (p = r + beta (p - omega v))
-    V_BI_S,     // y = a - alpha * b;  d0 = y . y                                       (s = r - alpha v;  ss)
-    V_BI_HALF,  // only when `half`:  x += alpha * a;  y = b                            (x += alpha ph;  r = s)
-    V_BI_XR,    // x = (x + alpha * a) + omega * b;  y = c - omega * d;  d0 = y . y      (x, r;  rr)
-};
+// (the updates by name, VecOp, and the scalar steps by name, FinOp: krylov_loops.hpp)
 template <int OP> struct Dots { static constexpr int n = (OP == V_CG_P || OP == V_BI_P || OP == V_BI_HALF) ? 0 : (OP == V_DOT2 || OP == V_INIT) ? 2 : 1; };
 
 // What update OP reads and writes of an element, and its arithmetic on the values alone: x and y come in as loaded (or
@@ -152,8 +144,6 @@ __device__ __forceinline__ void vec_update(const T *a, const T *b, const T *c, c
 }
 
 // ---- the scalar step that follows a dot: thread 0 of the launch that walked the upper levels --------------------------
-enum FinOp { F_STORE, F_INIT, F_RZ, F_ALPHA_CG, F_TEST_CG, F_BETA, F_RHO, F_ALPHA_BI, F_HALF, F_OMEGA, F_TEST_BI };
-
 template <typename T>
 __device__ __forceinline__ void stop_test(Scal<T> *s, T rr, uint64_t maxit) {
     s->rr = rr;
@@ -240,13 +230,84 @@ inline int analyse(spal_csc *m, int uplo, int unit, void *st) { return spal_csc_
 inline int product_plan(spal_csr *a) { return spal_csr_plan(a); }
 inline int product_plan(spal_csc *) { return SPAL_OK; }   // planned, twin included, by its constructor
 
-struct PinnedBuf {
-    void *p = nullptr;
-    PinnedBuf() = default;
-    PinnedBuf(const PinnedBuf &) = delete;
-    PinnedBuf &operator=(const PinnedBuf &) = delete;
-    ~PinnedBuf() { if (p) (void)hipHostFree(p); }
+// ---- the frame of a solver call, the same in all four drivers ---------------------------------------------------------
+// The helpers of this layer live in the four driver files alone: the library does not export them.
+#define KRYLOV_LOCAL __attribute__((visibility("hidden")))
+
+// Launch and check: `fn` and `st` are the caller's, and so is the `return`.
+#define KRYLOV_LAUNCH(kernel, grid, ...)                                                                       \
+    do {                                                                                                       \
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(kThreads), 0, st, __VA_ARGS__);                             \
+        const hipError_t le_ = hipGetLastError();                                                              \
+        if (le_ != hipSuccess) return fail(SPAL_ERR_HIP, "%s: launch failed: %s", fn, hipGetErrorString(le_)); \
+    } while (0)
+
+// The `count` heads of a call (Scal or GHead: what the host polls) in pinned memory, the call's device time and its
+// polls.  create() comes after the call's device allocations; begin .. end is the span that "solve_ms" reports.
+template <typename Head>
+struct KRYLOV_LOCAL SolveFrame {
+    hipStream_t st = nullptr;
+    const Head *dev = nullptr;
+    Head *h = nullptr;
+    size_t count = 0;
+    uint64_t polls = 0;
+    EventSpans ev;
+    SolveFrame() = default;
+    SolveFrame(const SolveFrame &) = delete;
+    SolveFrame &operator=(const SolveFrame &) = delete;
+    ~SolveFrame() { if (h) (void)hipHostFree(h); }
+
+    int create(hipStream_t stream, size_t heads) {
+        st = stream;
+        count = heads;
+        SPAL_HIP_TRY(hipHostMalloc((void **)&h, count * sizeof(Head), hipHostMallocDefault));
+        SPAL_HIP_TRY(ev.create(1));
+        return SPAL_OK;
+    }
+    // the heads are the first bytes of the scalars
+    int begin(void *dev_scalars, size_t bytes_to_zero) {
+        dev = (const Head *)dev_scalars;
+        SPAL_HIP_TRY(hipEventRecord(ev.e[0], st));
+        SPAL_HIP_TRY(hipMemsetAsync(dev_scalars, 0, bytes_to_zero, st));
+        return SPAL_OK;
+    }
+    int poll() {
+        SPAL_HIP_TRY(hipMemcpyAsync(h, dev, count * sizeof(Head), hipMemcpyDeviceToHost, st));
+        SPAL_HIP_TRY(hipStreamSynchronize(st));
+        ++polls;
+        return SPAL_OK;
+    }
+    int end(float *ms) {
+        SPAL_HIP_TRY(hipEventRecord(ev.e[1], st));
+        SPAL_HIP_TRY(hipStreamSynchronize(st));
+        SPAL_HIP_TRY(ev.span(0, ms));
+        return SPAL_OK;
+    }
+    void fill(spal_krylov_info *info, size_t j, float ms) const {
+        info->iterations = h[j].it;
+        info->reason = (int)h[j].reason;
+        info->residual_sq = (double)h[j].rr;
+        info->rhs_sq = (double)h[j].bb;
+        info->solve_ms = (double)ms;
+    }
 };
+
+// A call's describe string (OpState::krylov_info, ...) is stored and read under the lock of a's solve handle.
+template <typename H>
+KRYLOV_LOCAL void store_info(H *a, std::string OpState::*which, const std::string &json) {
+    std::lock_guard<std::mutex> lock(solve_handle(a)->mu);
+    a->ops.*which = json;
+}
+KRYLOV_LOCAL inline int info_describe_append(char *buf, size_t buf_len, const OpState &s, spal_csr *solve, const char *key,
+                                std::string OpState::*which) {
+    if (!solve) return SPAL_OK;
+    std::string info;
+    {
+        std::lock_guard<std::mutex> lock(solve->mu);
+        info = s.*which;
+    }
+    return describe_append(buf, buf_len, key, info);
+}
 
 struct PooledStream {
     hipStream_t s = nullptr;
@@ -311,10 +372,25 @@ int krylov_check_operands(const char *fn, H *a, H *m, double tol) {
     return SPAL_OK;
 }
 
-inline int refuse_lengths(const char *fn, uint64_t b_len, uint64_t x_len, uint64_t nrows) {
-    if (b_len != nrows || x_len != nrows)
+// A solve on host vectors, after the caller's own refusals: b and x0 go up, run(b_dev, x_dev, stream) solves, x comes back.
+template <typename T, typename H, typename Solve>
+KRYLOV_LOCAL int with_host_vectors(const char *fn, H *a, const T *b, uint64_t b_len, T *x, uint64_t x_len, Solve run) {
+    const uint64_t n = a->nrows;
+    if (b_len != n || x_len != n)
         return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: b.len() = %llu and x.len() = %llu but the matrix has %llu rows", fn,
-                    (unsigned long long)b_len, (unsigned long long)x_len, (unsigned long long)nrows);
+                    (unsigned long long)b_len, (unsigned long long)x_len, (unsigned long long)n);
+    DeviceGuard guard(a->device);
+    if (guard.status != SPAL_OK) return guard.status;
+    DevBuf db, dx;
+    PooledStream ps;   // a stream of the call's own: the handle's staging stream belongs to whoever holds its lock
+    SPAL_HIP_TRY(db.alloc(n * sizeof(T)));
+    SPAL_HIP_TRY(dx.alloc(n * sizeof(T)));
+    SPAL_HIP_TRY(stream_acquire(&ps.s));
+    SPAL_HIP_TRY(hipMemcpyAsync(db.p, b, n * sizeof(T), hipMemcpyHostToDevice, ps.s));
+    SPAL_HIP_TRY(hipMemcpyAsync(dx.p, x, n * sizeof(T), hipMemcpyHostToDevice, ps.s));
+    SPAL_TRY(run((const T *)db.p, dx.as<T>(), ps.s));
+    SPAL_HIP_TRY(hipMemcpyAsync(x, dx.p, n * sizeof(T), hipMemcpyDeviceToHost, ps.s));
+    SPAL_HIP_TRY(hipStreamSynchronize(ps.s));
     return SPAL_OK;
 }
 
@@ -395,6 +471,92 @@ inline bool bytes_of(uint64_t a, uint64_t b, uint64_t c, uint64_t d, size_t *out
     if (v > std::numeric_limits<size_t>::max() / 2) return false;
     *out = (size_t)v;
     return true;
+}
+
+// out = M^-1 v for packed blocks of k columns (out != v): two exact block solves, or `sweeps` >= 0 sweeps per triangle
+template <typename T, typename H>
+KRYLOV_LOCAL int prec_block(H *m, int64_t sweeps, uint32_t k, const T *v, T *out, hipStream_t st) {
+    if (sweeps >= 0) {
+        SPAL_TRY(sweep_block(m, 0, 1, (uint64_t)sweeps, k, v, k, out, k, st));
+        return sweep_block(m, 1, 0, (uint64_t)sweeps, k, out, k, out, k, st);
+    }
+    SPAL_TRY(solve_block(m, 0, 1, k, v, k, out, k, st));
+    return solve_block(m, 1, 0, k, out, k, out, k, st);
+}
+
+// what a block call refuses of k, ldb and ldx: it needs nothing of the handles
+KRYLOV_LOCAL inline int check_block_geometry(const char *who, uint64_t k, uint64_t ldb, uint64_t ldx) {
+    if (k == 0) return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: k = 0 (B and X need at least one column)", who);
+    if (k > 0xffffffffull) return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: k = %llu does not fit 32 bits", who, (unsigned long long)k);
+    if (ldb < k)
+        return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: ldb = %llu is less than k = %llu", who, (unsigned long long)ldb,
+                    (unsigned long long)k);
+    if (ldx < k)
+        return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: ldx = %llu is less than k = %llu", who, (unsigned long long)ldx,
+                    (unsigned long long)k);
+    return SPAL_OK;
+}
+
+// a's option "krylov_tile", 0 (automatic) resolved for k columns
+template <typename H>
+KRYLOV_LOCAL int column_tile_of(H *a, uint64_t k) {
+    int tile;
+    {
+        std::lock_guard<std::mutex> lock(solve_handle(a)->mu);
+        tile = a->ops.krylov_tile;
+    }
+    return tile ? tile : auto_tile(k);
+}
+
+// Runs `launch`, in which KT_ is the instantiated column tile that equals `tile`.
+#define KRYLOV_BY_TILE(tile, launch)                  \
+    switch (tile) {                                   \
+    case 1: { constexpr int KT_ = 1; launch; } break;   \
+    case 2: { constexpr int KT_ = 2; launch; } break;   \
+    case 4: { constexpr int KT_ = 4; launch; } break;   \
+    case 8: { constexpr int KT_ = 8; launch; } break;   \
+    case 16: { constexpr int KT_ = 16; launch; } break; \
+    default: { constexpr int KT_ = 32; launch; } break; \
+    }
+
+// From here on the stream's sweep scratch holds `bytes` (n x k per ping-pong block): the sweeps of M^-1 take it from there,
+// so no iteration allocates.
+template <typename H>
+KRYLOV_LOCAL int grow_sweep_scratch(const char *fn, hipStream_t st, H *m, int64_t sweeps, uint64_t n, size_t bytes) {
+    if (!m || sweeps < 1 || !n) return SPAL_OK;
+    StreamWork grow;
+    return grow.take(fn, st, bytes);
+}
+
+// A block solve on host blocks, after the caller's own refusals: B and X0 go up packed (leading dimension k),
+// run(b_dev, x_dev, stream) solves, the k columns of X come back into the caller's rows.
+template <typename T, typename H, typename Solve>
+KRYLOV_LOCAL int with_host_block(const char *who, H *a, uint64_t k, const T *b, uint64_t ldb, uint64_t b_rows, T *x, uint64_t ldx,
+                    uint64_t x_rows, Solve run) {
+    const uint64_t n = a->nrows;
+    if (b_rows != n || x_rows != n)
+        return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: B has %llu rows and X has %llu rows but the matrix has %llu rows", who,
+                    (unsigned long long)b_rows, (unsigned long long)x_rows, (unsigned long long)n);
+    DeviceGuard guard(a->device);
+    if (guard.status != SPAL_OK) return guard.status;
+    size_t bytes = 0;
+    if (!bytes_of(n, k, sizeof(T), 1, &bytes))
+        return fail(SPAL_ERR_OUT_OF_MEMORY, "%s: no room for blocks of %llu x %llu", who, (unsigned long long)n,
+                    (unsigned long long)k);
+    const size_t row = (size_t)k * sizeof(T);
+    DevBuf db, dx;
+    PooledStream ps;   // a stream of the call's own: the handle's staging stream belongs to whoever holds its lock
+    SPAL_HIP_TRY(db.alloc(bytes));
+    SPAL_HIP_TRY(dx.alloc(bytes));
+    SPAL_HIP_TRY(stream_acquire(&ps.s));
+    if (n) {
+        SPAL_HIP_TRY(hipMemcpy2DAsync(db.p, row, b, (size_t)ldb * sizeof(T), row, n, hipMemcpyHostToDevice, ps.s));
+        SPAL_HIP_TRY(hipMemcpy2DAsync(dx.p, row, x, (size_t)ldx * sizeof(T), row, n, hipMemcpyHostToDevice, ps.s));
+    }
+    SPAL_TRY(run((const T *)db.p, dx.as<T>(), ps.s));
+    if (n) SPAL_HIP_TRY(hipMemcpy2DAsync(x, (size_t)ldx * sizeof(T), dx.p, row, row, n, hipMemcpyDeviceToHost, ps.s));
+    SPAL_HIP_TRY(hipStreamSynchronize(ps.s));
+    return SPAL_OK;
 }
 
 }  // namespace spal

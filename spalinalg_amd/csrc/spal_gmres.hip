@@ -21,6 +21,9 @@
 // and the call has not; after `done` every kernel returns before it writes.  Products and solves enqueued past a stop
 // still run, into work vectors nobody reads again.  So x, it, reason and rr do not depend on "krylov_check_every".
 // ORDER BETWEEN LAUNCHES IS STREAM ORDER ALONE.  The driver holds no handle lock across a product or a solve.
+//
+// (The frame of the call -- KRYLOV_LAUNCH, SolveFrame with the pinned head, the polls and the device time, store_info,
+// with_host_vectors -- is krylov_kernels.hpp's, shared with CG and BiCGStab; the cycle loop in gmres_run is this file's.)
 #include "gmres_kernels.hpp"
 
 #pragma clang fp contract(off)
@@ -278,13 +281,6 @@ std::string info_json(const Record &r) {
     return buf;
 }
 
-#define GMRES_LAUNCH(kernel, grid, ...)                                                                     \
-    do {                                                                                                    \
-        hipLaunchKernelGGL(kernel, dim3(grid), dim3(kThreads), 0, st, __VA_ARGS__);                          \
-        const hipError_t le_ = hipGetLastError();                                                           \
-        if (le_ != hipSuccess) return fail(SPAL_ERR_HIP, "%s: launch failed: %s", fn, hipGetErrorString(le_)); \
-    } while (0)
-
 template <typename T, typename H>
 struct Run {
     const char *fn;
@@ -306,9 +302,9 @@ struct Run {
     // q = A x;  r, rr, bb;  the test;  beta, v_0
     int head() {
         SPAL_TRY(mul_dev(a, x, q, st));
-        GMRES_LAUNCH((residual<T>), grid, B.s, b, q, v_at(0), part, part + pe, n, V.tiles);
-        GMRES_LAUNCH((cycle_start<T>), 1, B, part, part + pe, c1, tol2, maxit);
-        GMRES_LAUNCH((scale<T>), grid, B.s, v_at(0), v_at(0), -1, n);
+        KRYLOV_LAUNCH((residual<T>), grid, B.s, b, q, v_at(0), part, part + pe, n, V.tiles);
+        KRYLOV_LAUNCH((cycle_start<T>), 1, B, part, part + pe, c1, tol2, maxit);
+        KRYLOV_LAUNCH((scale<T>), grid, B.s, v_at(0), v_at(0), -1, n);
         return SPAL_OK;
     }
     // step j of a cycle
@@ -319,26 +315,26 @@ struct Run {
             zj = z;
         }
         SPAL_TRY(mul_dev(a, zj, w, st));
-        GMRES_LAUNCH((mdot<T>), grid, B.s, V, j, w, part, pe);
-        GMRES_LAUNCH((mfinish<T>), j + 1, B.s, j, part, pe, c1, B.h);
-        GMRES_LAUNCH((mupdate<T, false>), grid, B.s, V, j, B.h, w, part);
-        GMRES_LAUNCH((mdot<T>), grid, B.s, V, j, w, part, pe);
-        GMRES_LAUNCH((mfinish<T>), j + 1, B.s, j, part, pe, c1, B.c);
-        GMRES_LAUNCH((mupdate<T, true>), grid, B.s, V, j, B.c, w, part);
-        GMRES_LAUNCH((step_scalars<T>), 1, B, j, part, c1, maxit);
-        GMRES_LAUNCH((scale<T>), grid, B.s, w, v_at(j + 1), (int)j, n);
+        KRYLOV_LAUNCH((mdot<T>), grid, B.s, V, j, w, part, pe);
+        KRYLOV_LAUNCH((mfinish<T>), j + 1, B.s, j, part, pe, c1, B.h);
+        KRYLOV_LAUNCH((mupdate<T, false>), grid, B.s, V, j, B.h, w, part);
+        KRYLOV_LAUNCH((mdot<T>), grid, B.s, V, j, w, part, pe);
+        KRYLOV_LAUNCH((mfinish<T>), j + 1, B.s, j, part, pe, c1, B.c);
+        KRYLOV_LAUNCH((mupdate<T, true>), grid, B.s, V, j, B.c, w, part);
+        KRYLOV_LAUNCH((step_scalars<T>), 1, B, j, part, c1, maxit);
+        KRYLOV_LAUNCH((scale<T>), grid, B.s, w, v_at(j + 1), (int)j, n);
         return SPAL_OK;
     }
     // y;  u = V y;  x += M^-1 u
     int cycle_end() {
-        GMRES_LAUNCH((back_substitute<T>), 1, B);
+        KRYLOV_LAUNCH((back_substitute<T>), 1, B);
         if (!m) {
-            GMRES_LAUNCH((combine<T, true>), grid, B, V, x);
+            KRYLOV_LAUNCH((combine<T, true>), grid, B, V, x);
             return SPAL_OK;
         }
-        GMRES_LAUNCH((combine<T, false>), grid, B, V, u);
+        KRYLOV_LAUNCH((combine<T, false>), grid, B, V, u);
         SPAL_TRY(prec(u, z));
-        GMRES_LAUNCH((add_to_x<T>), grid, B.s, z, x, n);
+        KRYLOV_LAUNCH((add_to_x<T>), grid, B.s, z, x, n);
         return SPAL_OK;
     }
 };
@@ -347,7 +343,6 @@ template <typename T, typename H>
 int gmres_run(const char *fn, H *a, H *m, const T *b, T *x, uint64_t restart, double tol, uint64_t maxit, hipStream_t st,
               spal_krylov_info *info) {
     const uint64_t n = a->nrows;
-    spal_csr *owner = solve_handle(a);   // whose lock guards a's option and its "gmres" string
     const int64_t check_every = krylov_check_every_of(a, m != nullptr);
     SPAL_TRY(refuse_capture(fn, st, "the call polls and synchronises"));
     int64_t sweeps = -1;
@@ -358,8 +353,7 @@ int gmres_run(const char *fn, H *a, H *m, const T *b, T *x, uint64_t restart, do
     const uint64_t stride = (n + 63) & ~(uint64_t)63;   // every vector on a 256-byte boundary at least
     const uint64_t basis_bytes = nvec * stride * sizeof(T);
     DevBuf vecs, parts, scal;
-    PinnedBuf host;
-    EventSpans ev;
+    SolveFrame<GHead<T>> F;
     {
         const hipError_t e = vecs.alloc((size_t)basis_bytes);
         if (e == hipErrorOutOfMemory)
@@ -371,8 +365,7 @@ int gmres_run(const char *fn, H *a, H *m, const T *b, T *x, uint64_t restart, do
     SPAL_HIP_TRY(parts.alloc(std::max<uint64_t>(restart, 2) * pe * sizeof(T)));
     const size_t scal_bytes = sizeof(GHead<T>) + block_elems(restart) * sizeof(T);
     SPAL_HIP_TRY(scal.alloc(scal_bytes));
-    SPAL_HIP_TRY(hipHostMalloc(&host.p, sizeof(GHead<T>), hipHostMallocDefault));
-    SPAL_HIP_TRY(ev.create(1));
+    SPAL_TRY(F.create(st, 1));
 
     Run<T, H> R;
     R.fn = fn;
@@ -408,22 +401,13 @@ int gmres_run(const char *fn, H *a, H *m, const T *b, T *x, uint64_t restart, do
     }
     R.B = block_parts<T>(scal.as<GHead<T>>(), reinterpret_cast<T *>(reinterpret_cast<char *>(scal.p) + sizeof(GHead<T>)), restart);
 
-    GHead<T> *h = (GHead<T> *)host.p;
-    uint64_t polls = 0;
-    auto poll = [&]() -> int {
-        SPAL_HIP_TRY(hipMemcpyAsync(h, R.B.s, sizeof(GHead<T>), hipMemcpyDeviceToHost, st));
-        SPAL_HIP_TRY(hipStreamSynchronize(st));
-        ++polls;
-        return SPAL_OK;
-    };
-
-    SPAL_HIP_TRY(hipEventRecord(ev.e[0], st));
-    SPAL_HIP_TRY(hipMemsetAsync(scal.p, 0, scal_bytes, st));
+    const GHead<T> *h = F.h;
+    SPAL_TRY(F.begin(scal.p, scal_bytes));
     SPAL_TRY(R.head());
     uint64_t total = 0;      // inner iterations enqueued; the device's `it` as long as it has not frozen
     bool stopped = false;
     if (maxit == 0) {        // the test after r0 has decided
-        SPAL_TRY(poll());
+        SPAL_TRY(F.poll());
         stopped = true;
     }
     while (!stopped) {
@@ -435,7 +419,7 @@ int gmres_run(const char *fn, H *a, H *m, const T *b, T *x, uint64_t restart, do
             ++total;
             ++since;
             if (since == (uint64_t)check_every || j == restart || total == maxit) {
-                SPAL_TRY(poll());
+                SPAL_TRY(F.poll());
                 since = 0;
                 stopped = h->done != 0;
                 ended = h->cyc_end != 0;
@@ -449,20 +433,14 @@ int gmres_run(const char *fn, H *a, H *m, const T *b, T *x, uint64_t restart, do
         SPAL_TRY(R.cycle_end());
         SPAL_TRY(R.head());
         if (early || total == maxit) {   // est <= thr or maxit: the test at the head stops the call, or very likely does
-            SPAL_TRY(poll());
+            SPAL_TRY(F.poll());
             stopped = h->done != 0;
         }
     }
-    SPAL_HIP_TRY(hipEventRecord(ev.e[1], st));
-    SPAL_HIP_TRY(hipStreamSynchronize(st));
-    if (!h->done) return fail(SPAL_ERR_HIP, "%s: the device did not stop after %llu iterations", fn, (unsigned long long)maxit);
     float ms = 0.f;
-    SPAL_HIP_TRY(ev.span(0, &ms));
-    info->iterations = h->it;
-    info->reason = (int)h->reason;
-    info->residual_sq = (double)h->rr;
-    info->rhs_sq = (double)h->bb;
-    info->solve_ms = (double)ms;
+    SPAL_TRY(F.end(&ms));
+    if (!h->done) return fail(SPAL_ERR_HIP, "%s: the device did not stop after %llu iterations", fn, (unsigned long long)maxit);
+    F.fill(info, 0, ms);
     Record rec;
     rec.restart = restart;
     rec.preconditioned = m ? 1 : 0;
@@ -471,12 +449,10 @@ int gmres_run(const char *fn, H *a, H *m, const T *b, T *x, uint64_t restart, do
     rec.cycles = h->cycles;
     rec.reason = info->reason;
     rec.check_every = check_every;
-    rec.polls = polls;
+    rec.polls = F.polls;
     rec.basis_bytes = basis_bytes;
     rec.solve_ms = info->solve_ms;
-    const std::string json = info_json(rec);
-    std::lock_guard<std::mutex> lock(owner->mu);
-    a->ops.gmres_info = json;
+    store_info(a, &OpState::gmres_info, info_json(rec));
     return SPAL_OK;
 }
 
@@ -506,33 +482,15 @@ template <typename T, typename H>
 int gmres_host(const char *fn, H *a, H *m, const T *b, uint64_t b_len, T *x, uint64_t x_len, uint64_t restart, double tol,
                uint64_t maxit, spal_krylov_info *info) {
     SPAL_TRY((gmres_check<T, H>(fn, a, m, b, x, restart, tol, info)));
-    SPAL_TRY(refuse_lengths(fn, b_len, x_len, a->nrows));
-    DeviceGuard guard(a->device);
-    if (guard.status != SPAL_OK) return guard.status;
-    const uint64_t n = a->nrows;
-    DevBuf db, dx;
-    PooledStream ps;   // a stream of the call's own: the handle's staging stream belongs to whoever holds its lock
-    SPAL_HIP_TRY(db.alloc(n * sizeof(T)));
-    SPAL_HIP_TRY(dx.alloc(n * sizeof(T)));
-    SPAL_HIP_TRY(stream_acquire(&ps.s));
-    SPAL_HIP_TRY(hipMemcpyAsync(db.p, b, n * sizeof(T), hipMemcpyHostToDevice, ps.s));
-    SPAL_HIP_TRY(hipMemcpyAsync(dx.p, x, n * sizeof(T), hipMemcpyHostToDevice, ps.s));
-    SPAL_TRY((gmres_run<T, H>(fn, a, m, db.as<T>(), dx.as<T>(), restart, tol, maxit, ps.s, info)));
-    SPAL_HIP_TRY(hipMemcpyAsync(x, dx.p, n * sizeof(T), hipMemcpyDeviceToHost, ps.s));
-    SPAL_HIP_TRY(hipStreamSynchronize(ps.s));
-    return SPAL_OK;
+    return with_host_vectors(fn, a, b, b_len, x, x_len, [&](const T *b_dev, T *x_dev, hipStream_t st) {
+        return gmres_run<T, H>(fn, a, m, b_dev, x_dev, restart, tol, maxit, st, info);
+    });
 }
 
 }  // namespace
 
 int gmres_describe_append(char *buf, size_t buf_len, const OpState &s, spal_csr *solve) {
-    if (!solve) return SPAL_OK;
-    std::string info;
-    {
-        std::lock_guard<std::mutex> lock(solve->mu);
-        info = s.gmres_info;
-    }
-    return describe_append(buf, buf_len, "gmres", info);
+    return info_describe_append(buf, buf_len, s, solve, "gmres", &OpState::gmres_info);
 }
 
 }  // namespace spal
@@ -541,37 +499,23 @@ using namespace spal;
 
 extern "C" {
 
-int spal_csr_gmres_f64(spal_csr_t a, spal_csr_t m, const double *b, uint64_t b_len, double *x, uint64_t x_len,
-                       uint64_t restart, double tol, uint64_t maxit, spal_krylov_info *info) {
-    return gmres_host<double, spal_csr>("spal_csr_gmres", a, m, b, b_len, x, x_len, restart, tol, maxit, info);
-}
-int spal_csr_gmres_f32(spal_csr_t a, spal_csr_t m, const float *b, uint64_t b_len, float *x, uint64_t x_len,
-                       uint64_t restart, double tol, uint64_t maxit, spal_krylov_info *info) {
-    return gmres_host<float, spal_csr>("spal_csr_gmres", a, m, b, b_len, x, x_len, restart, tol, maxit, info);
-}
-int spal_csr_gmres_dev_f64(spal_csr_t a, spal_csr_t m, const double *b_dev, double *x_dev, uint64_t restart, double tol,
-                           uint64_t maxit, void *stream, spal_krylov_info *info) {
-    return gmres_dev<double, spal_csr>("spal_csr_gmres_dev", a, m, b_dev, x_dev, restart, tol, maxit, stream, info);
-}
-int spal_csr_gmres_dev_f32(spal_csr_t a, spal_csr_t m, const float *b_dev, float *x_dev, uint64_t restart, double tol,
-                           uint64_t maxit, void *stream, spal_krylov_info *info) {
-    return gmres_dev<float, spal_csr>("spal_csr_gmres_dev", a, m, b_dev, x_dev, restart, tol, maxit, stream, info);
-}
-int spal_csc_gmres_f64(spal_csc_t a, spal_csc_t m, const double *b, uint64_t b_len, double *x, uint64_t x_len,
-                       uint64_t restart, double tol, uint64_t maxit, spal_krylov_info *info) {
-    return gmres_host<double, spal_csc>("spal_csc_gmres", a, m, b, b_len, x, x_len, restart, tol, maxit, info);
-}
-int spal_csc_gmres_f32(spal_csc_t a, spal_csc_t m, const float *b, uint64_t b_len, float *x, uint64_t x_len,
-                       uint64_t restart, double tol, uint64_t maxit, spal_krylov_info *info) {
-    return gmres_host<float, spal_csc>("spal_csc_gmres", a, m, b, b_len, x, x_len, restart, tol, maxit, info);
-}
-int spal_csc_gmres_dev_f64(spal_csc_t a, spal_csc_t m, const double *b_dev, double *x_dev, uint64_t restart, double tol,
-                           uint64_t maxit, void *stream, spal_krylov_info *info) {
-    return gmres_dev<double, spal_csc>("spal_csc_gmres_dev", a, m, b_dev, x_dev, restart, tol, maxit, stream, info);
-}
-int spal_csc_gmres_dev_f32(spal_csc_t a, spal_csc_t m, const float *b_dev, float *x_dev, uint64_t restart, double tol,
-                           uint64_t maxit, void *stream, spal_krylov_info *info) {
-    return gmres_dev<float, spal_csc>("spal_csc_gmres_dev", a, m, b_dev, x_dev, restart, tol, maxit, stream, info);
-}
+#define SPAL_GMRES_ENTRIES(kind, sfx, T)                                                                               \
+    int spal_##kind##_gmres_##sfx(spal_##kind##_t a, spal_##kind##_t m, const T *b, uint64_t b_len, T *x,              \
+                                  uint64_t x_len, uint64_t restart, double tol, uint64_t maxit,                        \
+                                  spal_krylov_info *info) {                                                            \
+        return gmres_host<T, spal_##kind>("spal_" #kind "_gmres", a, m, b, b_len, x, x_len, restart, tol, maxit,       \
+                                          info);                                                                       \
+    }                                                                                                                  \
+    int spal_##kind##_gmres_dev_##sfx(spal_##kind##_t a, spal_##kind##_t m, const T *b_dev, T *x_dev,                  \
+                                      uint64_t restart, double tol, uint64_t maxit, void *stream,                      \
+                                      spal_krylov_info *info) {                                                        \
+        return gmres_dev<T, spal_##kind>("spal_" #kind "_gmres_dev", a, m, b_dev, x_dev, restart, tol, maxit, stream,  \
+                                         info);                                                                        \
+    }
+SPAL_GMRES_ENTRIES(csr, f64, double)
+SPAL_GMRES_ENTRIES(csr, f32, float)
+SPAL_GMRES_ENTRIES(csc, f64, double)
+SPAL_GMRES_ENTRIES(csc, f32, float)
+#undef SPAL_GMRES_ENTRIES
 
 }  // extern "C"

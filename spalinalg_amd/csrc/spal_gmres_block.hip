@@ -31,6 +31,10 @@
 // ORDER BETWEEN LAUNCHES IS STREAM ORDER ALONE: no flags waited on, no spins, no float atomics, no grid syncs.  The
 // driver holds no handle lock across a product or a solve; every block, the dot scratch and the scalars are taken and
 // the stream's sweep scratch is grown before the first step, so no iteration allocates.
+//
+// (The host layer of a block call -- KRYLOV_BY_TILE, KRYLOV_LAUNCH, prec_block, check_block_geometry, column_tile_of,
+// grow_sweep_scratch, with_host_block -- and the frame -- SolveFrame over the k heads, store_info -- are
+// krylov_kernels.hpp's, shared with spal_krylov_block.hip; the cycle loop in gmres_block_run is this file's.)
 #include "gmres_kernels.hpp"
 
 #pragma clang fp contract(off)
@@ -432,30 +436,8 @@ std::string info_json(const Record &r) {
     return buf;
 }
 
-// a kernel of the tile geometry, by column tile (MODE: mupdate_block's DOT, combine_block's ADD; 0 in the others)
-#define GB_TILES(kernel, MODE, ...)                                                                                    \
-    do {                                                                                                               \
-        switch (tile) {                                                                                                \
-        case 1: hipLaunchKernelGGL((kernel<T, 1, MODE>), tgrid, dim3(kThreads), 0, st, __VA_ARGS__); break;            \
-        case 2: hipLaunchKernelGGL((kernel<T, 2, MODE>), tgrid, dim3(kThreads), 0, st, __VA_ARGS__); break;            \
-        case 4: hipLaunchKernelGGL((kernel<T, 4, MODE>), tgrid, dim3(kThreads), 0, st, __VA_ARGS__); break;            \
-        case 8: hipLaunchKernelGGL((kernel<T, 8, MODE>), tgrid, dim3(kThreads), 0, st, __VA_ARGS__); break;            \
-        case 16: hipLaunchKernelGGL((kernel<T, 16, MODE>), tgrid, dim3(kThreads), 0, st, __VA_ARGS__); break;          \
-        default: hipLaunchKernelGGL((kernel<T, 32, MODE>), tgrid, dim3(kThreads), 0, st, __VA_ARGS__); break;          \
-        }                                                                                                              \
-        GB_LAUNCHED();                                                                                                 \
-    } while (0)
-#define GB_LAUNCH(kernel, grid, ...)                                                                                   \
-    do {                                                                                                               \
-        hipLaunchKernelGGL(kernel, grid, dim3(kThreads), 0, st, __VA_ARGS__);                                          \
-        GB_LAUNCHED();                                                                                                 \
-    } while (0)
-#define GB_LAUNCHED()                                                                                                  \
-    do {                                                                                                               \
-        const hipError_t le_ = hipGetLastError();                                                                      \
-        if (le_ != hipSuccess) return fail(SPAL_ERR_HIP, "%s: launch failed: %s", fn, hipGetErrorString(le_));         \
-    } while (0)
-
+// (KRYLOV_BY_TILE names the column tile KT_; the third template argument is mupdate_block's DOT, combine_block's ADD, 0 in
+// the others)
 template <typename T, typename H>
 struct Run {
     const char *fn;
@@ -476,21 +458,14 @@ struct Run {
     T *v_at(uint64_t i) const { return basis + i * V.stride; }
     int mul(const T *v, uint64_t ld, T *out) { return mul_block(a, k, v, ld, out, k, st); }
     // out = M^-1 v (out != v, both packed)
-    int prec(const T *v, T *out) {
-        if (sweeps >= 0) {
-            SPAL_TRY(sweep_block(m, 0, 1, (uint64_t)sweeps, k, v, k, out, k, st));
-            return sweep_block(m, 1, 0, (uint64_t)sweeps, k, out, k, out, k, st);
-        }
-        SPAL_TRY(solve_block(m, 0, 1, k, v, k, out, k, st));
-        return solve_block(m, 1, 0, k, out, k, out, k, st);
-    }
+    int prec(const T *v, T *out) { return prec_block<T, H>(m, sweeps, k, v, out, st); }
 
     // q = A x;  r, rr, bb;  the test;  beta, v_0
     int head() {
         SPAL_TRY(mul(X.p, X.ld, q));
-        GB_TILES(residual_block, 0, S, B, q, v_at(0), part, part + pe * k, n, tiles, pe);
-        GB_LAUNCH((cycle_start_block<T>), cgrid, S, part, part + pe * k, pe, c1, tol2, maxit);
-        GB_TILES(scale_block, 0, S, v_at(0), v_at(0), -1, n, tiles);
+        KRYLOV_BY_TILE(tile, KRYLOV_LAUNCH((residual_block<T, KT_, 0>), tgrid, S, B, q, v_at(0), part, part + pe * k, n, tiles, pe));
+        KRYLOV_LAUNCH((cycle_start_block<T>), cgrid, S, part, part + pe * k, pe, c1, tol2, maxit);
+        KRYLOV_BY_TILE(tile, KRYLOV_LAUNCH((scale_block<T, KT_, 0>), tgrid, S, v_at(0), v_at(0), -1, n, tiles));
         return SPAL_OK;
     }
     // step j of a cycle, for the columns that are there
@@ -502,26 +477,26 @@ struct Run {
         }
         SPAL_TRY(mul(zj, k, w));
         const dim3 fgrid(j + 1, std::min<unsigned>(k, kFinishGrid));
-        GB_TILES(mdot_block, 0, S, V, j, w, part, pe);
-        GB_LAUNCH((mfinish_block<T>), fgrid, S, j, part, pe, c1, 0);
-        GB_TILES(mupdate_block, 0, S, V, j, 0, w, part, pe);
-        GB_TILES(mdot_block, 0, S, V, j, w, part, pe);
-        GB_LAUNCH((mfinish_block<T>), fgrid, S, j, part, pe, c1, 1);
-        GB_TILES(mupdate_block, 1, S, V, j, 1, w, part, pe);
-        GB_LAUNCH((step_scalars_block<T>), cgrid, S, j, part, pe, c1, maxit);
-        GB_TILES(scale_block, 0, S, w, v_at(j + 1), (int)j, n, tiles);
+        KRYLOV_BY_TILE(tile, KRYLOV_LAUNCH((mdot_block<T, KT_, 0>), tgrid, S, V, j, w, part, pe));
+        KRYLOV_LAUNCH((mfinish_block<T>), fgrid, S, j, part, pe, c1, 0);
+        KRYLOV_BY_TILE(tile, KRYLOV_LAUNCH((mupdate_block<T, KT_, 0>), tgrid, S, V, j, 0, w, part, pe));
+        KRYLOV_BY_TILE(tile, KRYLOV_LAUNCH((mdot_block<T, KT_, 0>), tgrid, S, V, j, w, part, pe));
+        KRYLOV_LAUNCH((mfinish_block<T>), fgrid, S, j, part, pe, c1, 1);
+        KRYLOV_BY_TILE(tile, KRYLOV_LAUNCH((mupdate_block<T, KT_, 1>), tgrid, S, V, j, 1, w, part, pe));
+        KRYLOV_LAUNCH((step_scalars_block<T>), cgrid, S, j, part, pe, c1, maxit);
+        KRYLOV_BY_TILE(tile, KRYLOV_LAUNCH((scale_block<T, KT_, 0>), tgrid, S, w, v_at(j + 1), (int)j, n, tiles));
         return SPAL_OK;
     }
     // y;  u = V y;  x += M^-1 u, for the columns whose cycle has ended
     int cycle_end() {
-        GB_LAUNCH((back_substitute_block<T>), cgrid, S);
+        KRYLOV_LAUNCH((back_substitute_block<T>), cgrid, S);
         if (!m) {
-            GB_TILES(combine_block, 1, S, V, X);
+            KRYLOV_BY_TILE(tile, KRYLOV_LAUNCH((combine_block<T, KT_, 1>), tgrid, S, V, X));
             return SPAL_OK;
         }
-        GB_TILES(combine_block, 0, S, V, (Mat<T>{u, (uint64_t)k}));
+        KRYLOV_BY_TILE(tile, KRYLOV_LAUNCH((combine_block<T, KT_, 0>), tgrid, S, V, (Mat<T>{u, (uint64_t)k})));
         SPAL_TRY(prec(u, z));
-        GB_TILES(add_to_x_block, 0, S, z, X, n, tiles);
+        KRYLOV_BY_TILE(tile, KRYLOV_LAUNCH((add_to_x_block<T, KT_, 0>), tgrid, S, z, X, n, tiles));
         return SPAL_OK;
     }
 };
@@ -552,14 +527,8 @@ template <typename T, typename H>
 int gmres_block_run(const char *fn, H *a, H *m, uint32_t k, const T *b, uint64_t ldb, T *x, uint64_t ldx, uint64_t restart,
                     double tol, uint64_t maxit, hipStream_t st, spal_krylov_info *info) {
     const uint64_t n = a->nrows;
-    spal_csr *owner = solve_handle(a);   // whose lock guards a's options and its "gmres_block" string
     const int64_t check_every = krylov_check_every_of(a, m != nullptr);
-    int tile;
-    {
-        std::lock_guard<std::mutex> lock(owner->mu);
-        tile = a->ops.krylov_tile;
-    }
-    if (!tile) tile = auto_tile(k);
+    const int tile = column_tile_of(a, k);
     SPAL_TRY(refuse_capture(fn, st, "the call polls and synchronises"));
     int64_t sweeps = -1;
     SPAL_TRY(krylov_prepare(fn, a, m, st, &sweeps));
@@ -577,8 +546,7 @@ int gmres_block_run(const char *fn, H *a, H *m, uint32_t k, const T *b, uint64_t
         return fail(SPAL_ERR_OUT_OF_MEMORY, "%s: no room for %llu blocks of %llu x %u", fn, (unsigned long long)nblk,
                     (unsigned long long)n, k);
     DevBuf blocks, parts, scal;
-    PinnedBuf host;
-    EventSpans ev;
+    SolveFrame<GHead<T>> F;
     {
         const hipError_t e = blocks.alloc(basis_bytes);
         if (e == hipErrorOutOfMemory)
@@ -590,12 +558,8 @@ int gmres_block_run(const char *fn, H *a, H *m, uint32_t k, const T *b, uint64_t
     const size_t head_bytes = (size_t)k * sizeof(GHead<T>);
     const size_t scal_bytes = head_bytes + (size_t)k * be * sizeof(T);
     SPAL_HIP_TRY(scal.alloc(scal_bytes));
-    SPAL_HIP_TRY(hipHostMalloc(&host.p, head_bytes, hipHostMallocDefault));
-    SPAL_HIP_TRY(ev.create(1));
-    if (m && sweeps >= 1 && n) {   // the stream's sweep scratch holds n x k per ping-pong block from here on
-        StreamWork grow;
-        SPAL_TRY(grow.take(fn, st, sweep_bytes));
-    }
+    SPAL_TRY(F.create(st, k));
+    SPAL_TRY(grow_sweep_scratch(fn, st, m, sweeps, n, sweep_bytes));
 
     Run<T, H> R;
     R.fn = fn;
@@ -634,19 +598,16 @@ int gmres_block_run(const char *fn, H *a, H *m, uint32_t k, const T *b, uint64_t
     R.S.m = (unsigned)restart;
     R.S.k = k;
 
-    GHead<T> *h = (GHead<T> *)host.p;
-    uint64_t polls = 0, steps = 0;
+    const GHead<T> *h = F.h;
+    uint64_t steps = 0;
     Polled P;
     auto poll = [&]() -> int {   // the k heads to pinned memory
-        SPAL_HIP_TRY(hipMemcpyAsync(h, R.S.heads, head_bytes, hipMemcpyDeviceToHost, st));
-        SPAL_HIP_TRY(hipStreamSynchronize(st));
-        ++polls;
+        SPAL_TRY(F.poll());
         P = poll_heads<T>(h, k, restart, maxit);
         return SPAL_OK;
     };
 
-    SPAL_HIP_TRY(hipEventRecord(ev.e[0], st));
-    SPAL_HIP_TRY(hipMemsetAsync(scal.p, 0, scal_bytes, st));
+    SPAL_TRY(F.begin(scal.p, scal_bytes));
     SPAL_TRY(R.head());
     if (maxit == 0) SPAL_TRY(poll());   // the test after r0 has decided every column
     // P.min_it: no column that runs has fewer iterations (0 before the first poll), so after maxit - min_it steps of a
@@ -675,21 +636,15 @@ int gmres_block_run(const char *fn, H *a, H *m, uint32_t k, const T *b, uint64_t
         SPAL_TRY(R.head());
         if (early) SPAL_TRY(poll());   // est <= thr or maxit in some column: the test at the head stops it, or very likely does
     }
-    SPAL_HIP_TRY(hipEventRecord(ev.e[1], st));
-    SPAL_HIP_TRY(hipStreamSynchronize(st));
+    float ms = 0.f;
+    SPAL_TRY(F.end(&ms));
     if (P.stopped < k)
         return fail(SPAL_ERR_HIP, "%s: %llu of %u columns did not stop after %llu iterations", fn,
                     (unsigned long long)(k - P.stopped), k, (unsigned long long)maxit);
-    float ms = 0.f;
-    SPAL_HIP_TRY(ev.span(0, &ms));
     Record rec;
     rec.iterations_min = h[0].it;
     for (uint32_t j = 0; j < k; ++j) {
-        info[j].iterations = h[j].it;
-        info[j].reason = (int)h[j].reason;
-        info[j].residual_sq = (double)h[j].rr;
-        info[j].rhs_sq = (double)h[j].bb;
-        info[j].solve_ms = (double)ms;
+        F.fill(info + j, j, ms);
         rec.iterations_min = std::min<uint64_t>(rec.iterations_min, h[j].it);
         rec.iterations_max = std::max<uint64_t>(rec.iterations_max, h[j].it);
         rec.cycles = std::max<uint64_t>(rec.cycles, h[j].cycles);
@@ -702,12 +657,10 @@ int gmres_block_run(const char *fn, H *a, H *m, uint32_t k, const T *b, uint64_t
     rec.tile = tile;
     rec.steps = steps;
     rec.check_every = check_every;
-    rec.polls = polls;
+    rec.polls = F.polls;
     rec.basis_bytes = basis_bytes;
     rec.solve_ms = (double)ms;
-    const std::string json = info_json(rec);
-    std::lock_guard<std::mutex> lock(owner->mu);
-    a->ops.gmres_block_info = json;
+    store_info(a, &OpState::gmres_block_info, info_json(rec));
     return SPAL_OK;
 }
 
@@ -721,14 +674,7 @@ int gmres_block_check(const char *who, H *a, H *m, uint64_t k, const T *b, uint6
         return fail(SPAL_ERR_INVALID_ARGUMENT,
                     "%s: restart = %llu must be 1 .. %llu (one Hessenberg column element per thread of the scalar workgroup)", who,
                     (unsigned long long)restart, (unsigned long long)kMaxRestart);
-    if (k == 0) return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: k = 0 (B and X need at least one column)", who);
-    if (k > 0xffffffffull) return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: k = %llu does not fit 32 bits", who, (unsigned long long)k);
-    if (ldb < k)
-        return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: ldb = %llu is less than k = %llu", who, (unsigned long long)ldb,
-                    (unsigned long long)k);
-    if (ldx < k)
-        return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: ldx = %llu is less than k = %llu", who, (unsigned long long)ldx,
-                    (unsigned long long)k);
+    SPAL_TRY(check_block_geometry(who, k, ldb, ldx));
     SPAL_TRY(check_dtype<T>(who, a->elem_size));
     return krylov_check_operands<T, H>(who, a, m, tol);
 }
@@ -743,47 +689,19 @@ int gmres_block_dev(const char *who, H *a, H *m, uint64_t k, const T *b, uint64_
     return gmres_block_run<T, H>(who, a, m, (uint32_t)k, b, ldb, x, ldx, restart, tol, maxit, (hipStream_t)stream, info);
 }
 
-// host blocks: B and X0 go up packed (leading dimension k), the k columns of X come back into the caller's rows
 template <typename T, typename H>
 int gmres_block_host(const char *who, H *a, H *m, uint64_t k, const T *b, uint64_t ldb, uint64_t b_rows, T *x, uint64_t ldx,
                      uint64_t x_rows, uint64_t restart, double tol, uint64_t maxit, spal_krylov_info *info) {
     SPAL_TRY((gmres_block_check<T, H>(who, a, m, k, b, ldb, x, ldx, restart, tol, info)));
-    if (b_rows != a->nrows || x_rows != a->nrows)
-        return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: B has %llu rows and X has %llu rows but the matrix has %llu rows", who,
-                    (unsigned long long)b_rows, (unsigned long long)x_rows, (unsigned long long)a->nrows);
-    DeviceGuard guard(a->device);
-    if (guard.status != SPAL_OK) return guard.status;
-    const uint64_t n = a->nrows;
-    size_t bytes = 0;
-    if (!bytes_of(n, k, sizeof(T), 1, &bytes))
-        return fail(SPAL_ERR_OUT_OF_MEMORY, "%s: no room for blocks of %llu x %llu", who, (unsigned long long)n,
-                    (unsigned long long)k);
-    const size_t row = (size_t)k * sizeof(T);
-    DevBuf db, dx;
-    PooledStream ps;   // a stream of the call's own: the handle's staging stream belongs to whoever holds its lock
-    SPAL_HIP_TRY(db.alloc(bytes));
-    SPAL_HIP_TRY(dx.alloc(bytes));
-    SPAL_HIP_TRY(stream_acquire(&ps.s));
-    if (n) {
-        SPAL_HIP_TRY(hipMemcpy2DAsync(db.p, row, b, (size_t)ldb * sizeof(T), row, n, hipMemcpyHostToDevice, ps.s));
-        SPAL_HIP_TRY(hipMemcpy2DAsync(dx.p, row, x, (size_t)ldx * sizeof(T), row, n, hipMemcpyHostToDevice, ps.s));
-    }
-    SPAL_TRY((gmres_block_run<T, H>(who, a, m, (uint32_t)k, db.as<T>(), k, dx.as<T>(), k, restart, tol, maxit, ps.s, info)));
-    if (n) SPAL_HIP_TRY(hipMemcpy2DAsync(x, (size_t)ldx * sizeof(T), dx.p, row, row, n, hipMemcpyDeviceToHost, ps.s));
-    SPAL_HIP_TRY(hipStreamSynchronize(ps.s));
-    return SPAL_OK;
+    return with_host_block(who, a, k, b, ldb, b_rows, x, ldx, x_rows, [&](const T *b_dev, T *x_dev, hipStream_t st) {
+        return gmres_block_run<T, H>(who, a, m, (uint32_t)k, b_dev, k, x_dev, k, restart, tol, maxit, st, info);
+    });
 }
 
 }  // namespace
 
 int gmres_block_describe_append(char *buf, size_t buf_len, const OpState &s, spal_csr *solve) {
-    if (!solve) return SPAL_OK;
-    std::string info;
-    {
-        std::lock_guard<std::mutex> lock(solve->mu);
-        info = s.gmres_block_info;
-    }
-    return describe_append(buf, buf_len, "gmres_block", info);
+    return info_describe_append(buf, buf_len, s, solve, "gmres_block", &OpState::gmres_block_info);
 }
 
 }  // namespace spal

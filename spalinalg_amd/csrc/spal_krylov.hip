@@ -4,8 +4,11 @@
 // the same way.  The order depends on n alone, so every kernel here returns the bits of the sequential text.
 //
 // (tile_sum, upper_levels, the scratch sizes, the plan preparation, M^-1 and the shared refusals are in krylov_kernels.hpp,
-// which spal_gmres.hip includes too; so are the scalar block Scal, the fused updates VecOp / vec_update and the scalar
-// steps FinOp / scalar_step, which spal_krylov_block.hip runs per column of a block of right-hand sides.)
+// which spal_gmres.hip includes too; so are the scalar block Scal, the fused updates vec_update and the scalar steps
+// scalar_step, which spal_krylov_block.hip runs per column of a block of right-hand sides, and the frame of a call:
+// KRYLOV_LAUNCH, SolveFrame, store_info, with_host_vectors.  The two loops themselves -- which launch follows which, and
+// when the host polls -- are in krylov_loops.hpp with the names VecOp / FinOp, once for this file and the block file:
+// `Run` below is the driver type they are instantiated on.)
 //
 // ONE TILE IS ONE TRIP OF A WORKGROUP OF 256.  Thread t holds elements t, t + 256, t + 512, t + 768: strides 512 and 256
 // are thread-local ((v0 + v2) + (v1 + v3)), strides 128 and 64 go through LDS, strides 32 .. 1 are __shfl_down inside
@@ -26,9 +29,10 @@
 // points, each of which takes what it needs itself (f5b9766: re-entering a handle's lock deadlocks).  A factor whose
 // option "trsv_sweeps" is s >= 0 is applied by s Jacobi sweeps per triangle instead (trsv_sweep_enqueue),
 // through two more work vectors of the call.  The spal_*_krylov_amg_* entry points run the same two loops with an AMG
-// hierarchy `g` in m's place: M^-1 v is one multigrid cycle (amg_apply_enqueue, spal_amg.hip), enqueued into
-// the hierarchy's own work vectors under its own lock.  Plans are built before the first iteration; work vectors, the scratch and the scalar block come from the caching allocator per call,
-// so concurrent calls on one handle share nothing but the matrix.
+// hierarchy `g` in m's place (Precond): M^-1 v is one multigrid cycle (amg_apply_enqueue, spal_amg.hip),
+// enqueued into the hierarchy's own work vectors under its own lock.  Plans are built before the first iteration; work
+// vectors, the scratch and the scalar block come from the caching allocator per call, so concurrent calls on one handle
+// share nothing but the matrix.
 #include "krylov_kernels.hpp"
 
 #pragma clang fp contract(off)
@@ -112,15 +116,15 @@ __global__ __launch_bounds__(kThreads) void finish(FinArgs<T> g) {
 
 // ---- host side of the launches --------------------------------------------------------------------------------------
 template <typename T, int OP>
-hipError_t launch_vec(const VecArgs<T> &g, hipStream_t st) {
+int launch_vec(const char *fn, const VecArgs<T> &g, hipStream_t st) {
     const uint64_t tiles = tiles_of(g.n);
-    hipLaunchKernelGGL((vec<T, OP>), dim3(first_level_grid(g.n)), dim3(kThreads), 0, st, g, tiles);
-    return hipGetLastError();
+    KRYLOV_LAUNCH((vec<T, OP>), first_level_grid(g.n), g, tiles);
+    return SPAL_OK;
 }
 template <typename T, int OP>
-hipError_t launch_finish(const FinArgs<T> &g, hipStream_t st) {
-    hipLaunchKernelGGL((finish<T, OP>), dim3(1), dim3(kThreads), 0, st, g);
-    return hipGetLastError();
+int launch_finish(const char *fn, const FinArgs<T> &g, hipStream_t st) {
+    KRYLOV_LAUNCH((finish<T, OP>), 1, g);
+    return SPAL_OK;
 }
 
 // the definition on the host
@@ -164,14 +168,12 @@ int dot_dev(const char *fn, int device, const T *a, const T *b, uint64_t n, T *o
     g.b = b;
     g.n = n;
     g.part0 = work.as<T>();
-    hipError_t e = launch_vec<T, V_DOT>(g, st);
+    SPAL_TRY((launch_vec<T, V_DOT>(fn, g, st)));
     FinArgs<T> f = {};
     f.part0 = work.as<T>();
     f.c1 = tiles_of(n);
     f.out = out;
-    if (e == hipSuccess) e = launch_finish<T, F_STORE>(f, st);
-    if (e != hipSuccess) return fail(SPAL_ERR_HIP, "%s: launch failed: %s", fn, hipGetErrorString(e));
-    return SPAL_OK;
+    return launch_finish<T, F_STORE>(fn, f, st);
 }
 
 struct Record {
@@ -192,227 +194,161 @@ std::string info_json(const Record &r) {
     return buf;
 }
 
-// What both loops share: the vectors, the scalar block, the scratch of two dots, and the launches by name.
+// The preconditioner of a call: an ILU(0) factor m, an AMG hierarchy g (spal_amg.hip), or neither.  Never both.
+template <typename H>
+struct Precond {
+    H *m;
+    spal_amg *g;
+    explicit operator bool() const { return m || g; }   // M^-1 is there: z, ph and sh are vectors of their own
+};
+
+// The driver the loops of krylov_loops.hpp run on: an operand is a device vector; the scalar block, the scratch of two
+// dots, and the launches by name.
 template <typename T, typename H>
 struct Run {
     const char *fn;
-    H *a, *m;
-    spal_amg *g = nullptr;   // the other kind of preconditioner: an AMG hierarchy (spal_amg.hip); m is NULL then
+    H *a;
+    Precond<H> pc;
     hipStream_t st;
-    uint64_t n = 0, maxit = 0, c1 = 0;
+    uint64_t n = 0, maxit = 0, c1 = 0, stride = 0;
     T tol2 = T(0);
     Scal<T> *s = nullptr;
     T *part0 = nullptr, *part1 = nullptr;
     int64_t sweeps = -1;            // m's option "trsv_sweeps"
+    T *vecs = nullptr;              // work vector i at vecs + i * stride
     T *w0 = nullptr, *w1 = nullptr; // the sweeps' ping-pong vectors
+    const T *b = nullptr;
+    T *x = nullptr;
+    SolveFrame<Scal<T>> frame;
+    bool stopped = false;
 
+    static T *null() { return nullptr; }
+    const T *B() const { return b; }
+    T *X() const { return x; }
+    T *work(int i) const { return vecs + (uint64_t)i * stride; }
+    bool preconditioned() const { return (bool)pc; }
     int mul(const T *v, T *out) { return mul_dev(a, v, out, st); }
-    // out = M^-1 v (out != v); without a preconditioner the caller uses v itself
+    // out = M^-1 v (out != v); without a preconditioner the loops use v itself
     int prec(const T *v, T *out) {
-        return g ? amg_apply_enqueue(fn, g, v, out, st) : prec_dev<T, H>(fn, m, sweeps, v, out, w0, w1, st);
+        return pc.g ? amg_apply_enqueue(fn, pc.g, v, out, st) : prec_dev<T, H>(fn, pc.m, sweeps, v, out, w0, w1, st);
     }
     template <int OP>
-    int v(const T *va, const T *vb, const T *vc, const T *vd, T *x, T *y) {
-        VecArgs<T> g = {va, vb, vc, vd, x, y, s, part0, part1, n};
-        const hipError_t e = launch_vec<T, OP>(g, st);
-        return e == hipSuccess ? SPAL_OK : fail(SPAL_ERR_HIP, "%s: launch failed: %s", fn, hipGetErrorString(e));
+    int v(const T *va, const T *vb, const T *vc, const T *vd, T *vx, T *vy) {
+        return launch_vec<T, OP>(fn, VecArgs<T>{va, vb, vc, vd, vx, vy, s, part0, part1, n}, st);
     }
     template <int OP>
     int f(int unpreconditioned = 0) {
-        FinArgs<T> g = {s, part0, part1, c1, tol2, maxit, nullptr, unpreconditioned};
-        const hipError_t e = launch_finish<T, OP>(g, st);
-        return e == hipSuccess ? SPAL_OK : fail(SPAL_ERR_HIP, "%s: launch failed: %s", fn, hipGetErrorString(e));
+        return launch_finish<T, OP>(fn, FinArgs<T>{s, part0, part1, c1, tol2, maxit, nullptr, unpreconditioned}, st);
     }
+    int copy(T *dst, const T *src) {
+        SPAL_HIP_TRY(hipMemcpyAsync(dst, src, n * sizeof(T), hipMemcpyDeviceToDevice, st));
+        return SPAL_OK;
+    }
+    int zero(T *dst) {
+        SPAL_HIP_TRY(hipMemsetAsync(dst, 0, n * sizeof(T), st));
+        return SPAL_OK;
+    }
+    int poll() {
+        SPAL_TRY(frame.poll());
+        stopped = frame.h->done != 0;
+        return SPAL_OK;
+    }
+    bool all_stopped() const { return stopped; }
+    uint64_t polls() const { return frame.polls; }
 };
 
 template <typename T, typename H>
-int krylov_run(const char *fn, H *a, int method, H *m, spal_amg *g, const T *b, T *x, double tol, uint64_t maxit,
+int krylov_run(const char *fn, H *a, int method, Precond<H> pc, const T *b, T *x, double tol, uint64_t maxit,
                hipStream_t st, spal_krylov_info *info) {
     const uint64_t n = a->nrows;
-    spal_csr *owner = solve_handle(a);   // whose lock guards a's option and its "krylov" string
-    const bool pre = m || g;   // M^-1 is there: z, ph and sh are vectors of their own
+    const bool pre = (bool)pc;
     const int64_t check_every = krylov_check_every_of(a, pre);
     SPAL_TRY(refuse_capture(fn, st, "the call polls and synchronises"));
     int64_t sweeps = -1;
-    SPAL_TRY(krylov_prepare(fn, a, m, st, &sweeps));
+    SPAL_TRY(krylov_prepare(fn, a, pc.m, st, &sweeps));
     // work vectors, scratch, scalars
     const bool cg = method == SPAL_KRYLOV_CG;
     const int nwork = cg ? (pre ? 4 : 3) : (pre ? 8 : 6);
     const int nvec = nwork + (sweeps >= 0 ? 2 : 0);
     DevBuf vecs, parts, scal;
-    PinnedBuf host;
-    EventSpans ev;
     const uint64_t stride = (n + 63) & ~(uint64_t)63;   // every vector on a 256-byte boundary at least
     SPAL_HIP_TRY(vecs.alloc((size_t)nvec * stride * sizeof(T)));
     const uint64_t pe = scratch_elems(n);
     SPAL_HIP_TRY(parts.alloc(2 * pe * sizeof(T)));
     SPAL_HIP_TRY(scal.alloc(sizeof(Scal<T>)));
-    SPAL_HIP_TRY(hipHostMalloc(&host.p, sizeof(Scal<T>), hipHostMallocDefault));
-    SPAL_HIP_TRY(ev.create(1));
-    auto vec_at = [&](int k) { return vecs.as<T>() + (uint64_t)k * stride; };
 
     Run<T, H> R;
+    SPAL_TRY(R.frame.create(st, 1));
     R.fn = fn;
     R.a = a;
-    R.m = m;
-    R.g = g;
+    R.pc = pc;
     R.st = st;
     R.n = n;
     R.maxit = maxit;
     R.c1 = tiles_of(n);
+    R.stride = stride;
     R.tol2 = (T)(tol * tol);
     R.s = scal.as<Scal<T>>();
     R.part0 = parts.as<T>();
     R.part1 = parts.as<T>() + pe;
     R.sweeps = sweeps;
+    R.vecs = vecs.as<T>();
     if (sweeps >= 0) {
-        R.w0 = vec_at(nwork);
-        R.w1 = vec_at(nwork + 1);
+        R.w0 = R.work(nwork);
+        R.w1 = R.work(nwork + 1);
     }
+    R.b = b;
+    R.x = x;
 
-    Scal<T> *h = (Scal<T> *)host.p;
-    uint64_t polls = 0;
-    auto poll = [&]() -> int {
-        SPAL_HIP_TRY(hipMemcpyAsync(h, R.s, sizeof(Scal<T>), hipMemcpyDeviceToHost, st));
-        SPAL_HIP_TRY(hipStreamSynchronize(st));
-        ++polls;
-        return SPAL_OK;
-    };
-
-    SPAL_HIP_TRY(hipEventRecord(ev.e[0], st));
-    SPAL_HIP_TRY(hipMemsetAsync(R.s, 0, sizeof(Scal<T>), st));
-    T *r = vec_at(0), *q = vec_at(1), *p = vec_at(2);
-    // r = b - A x;  rr, bb;  it = 0;  test
-    SPAL_TRY(R.mul(x, q));
-    SPAL_TRY((R.template v<V_INIT>(b, q, nullptr, nullptr, nullptr, r)));
-    SPAL_TRY((R.template f<F_INIT>()));
-    uint64_t enqueued = 0;
-    bool stopped = false;
-    if (cg) {
-        T *z = pre ? vec_at(3) : r;
-        if (pre) SPAL_TRY(R.prec(r, z));
-        SPAL_TRY((R.template v<V_COPY_DOT>(r, z, nullptr, nullptr, nullptr, p)));   // p = z;  rz
-        SPAL_TRY((R.template f<F_RZ>()));
-        while (enqueued < maxit && !stopped) {
-            const uint64_t batch = std::min<uint64_t>((uint64_t)check_every, maxit - enqueued);
-            for (uint64_t k = 0; k < batch; ++k) {
-                SPAL_TRY(R.mul(p, q));
-                SPAL_TRY((R.template v<V_DOT>(p, q, nullptr, nullptr, nullptr, nullptr)));
-                SPAL_TRY((R.template f<F_ALPHA_CG>()));
-                SPAL_TRY((R.template v<V_CG_XR>(p, q, nullptr, nullptr, x, r)));      // x, r;  rr
-                SPAL_TRY((R.template f<F_TEST_CG>(pre ? 0 : 1)));                    // it, test (and beta when z is r)
-                if (pre) {
-                    SPAL_TRY(R.prec(r, z));
-                    SPAL_TRY((R.template v<V_DOT>(r, z, nullptr, nullptr, nullptr, nullptr)));
-                    SPAL_TRY((R.template f<F_BETA>()));
-                }
-                SPAL_TRY((R.template v<V_CG_P>(z, nullptr, nullptr, nullptr, nullptr, p)));
-            }
-            enqueued += batch;
-            SPAL_TRY(poll());
-            stopped = h->done != 0;
-        }
-    } else {
-        T *rhat = vec_at(3), *vv = vec_at(4), *t = vec_at(5);
-        T *sv = q;   // q is free once r exists
-        T *ph = pre ? vec_at(6) : p, *sh = pre ? vec_at(7) : sv;
-        SPAL_HIP_TRY(hipMemcpyAsync(rhat, r, n * sizeof(T), hipMemcpyDeviceToDevice, st));
-        SPAL_HIP_TRY(hipMemsetAsync(vv, 0, n * sizeof(T), st));
-        SPAL_HIP_TRY(hipMemsetAsync(p, 0, n * sizeof(T), st));
-        while (enqueued < maxit && !stopped) {
-            const uint64_t batch = std::min<uint64_t>((uint64_t)check_every, maxit - enqueued);
-            for (uint64_t k = 0; k < batch; ++k) {
-                SPAL_TRY((R.template v<V_DOT>(rhat, r, nullptr, nullptr, nullptr, nullptr)));
-                SPAL_TRY((R.template f<F_RHO>()));
-                SPAL_TRY((R.template v<V_BI_P>(r, vv, nullptr, nullptr, nullptr, p)));
-                if (pre) SPAL_TRY(R.prec(p, ph));
-                SPAL_TRY(R.mul(ph, vv));
-                SPAL_TRY((R.template v<V_DOT>(rhat, vv, nullptr, nullptr, nullptr, nullptr)));
-                SPAL_TRY((R.template f<F_ALPHA_BI>()));
-                SPAL_TRY((R.template v<V_BI_S>(r, vv, nullptr, nullptr, nullptr, sv)));   // s;  ss
-                SPAL_TRY((R.template f<F_HALF>()));                                       // it;  the half-step exit
-                SPAL_TRY((R.template v<V_BI_HALF>(ph, sv, nullptr, nullptr, x, r)));      // ... applied, if taken
-                if (pre) SPAL_TRY(R.prec(sv, sh));
-                SPAL_TRY(R.mul(sh, t));
-                SPAL_TRY((R.template v<V_DOT2>(t, sv, nullptr, nullptr, nullptr, nullptr)));   // t . s, t . t
-                SPAL_TRY((R.template f<F_OMEGA>()));
-                SPAL_TRY((R.template v<V_BI_XR>(ph, sh, sv, t, x, r)));                   // x, r;  rr
-                SPAL_TRY((R.template f<F_TEST_BI>()));
-            }
-            enqueued += batch;
-            SPAL_TRY(poll());
-            stopped = h->done != 0;
-        }
-    }
-    if (!polls) SPAL_TRY(poll());   // maxit = 0: the test after r0 has decided
-    SPAL_HIP_TRY(hipEventRecord(ev.e[1], st));
-    SPAL_HIP_TRY(hipStreamSynchronize(st));
-    if (!h->done) return fail(SPAL_ERR_HIP, "%s: the device did not stop after %llu iterations", fn, (unsigned long long)maxit);
+    SPAL_TRY(R.frame.begin(R.s, sizeof(Scal<T>)));
+    SPAL_TRY(krylov_start(R));
+    SPAL_TRY(cg ? cg_loop(R, maxit, (uint64_t)check_every) : bicgstab_loop(R, maxit, (uint64_t)check_every));
     float ms = 0.f;
-    SPAL_HIP_TRY(ev.span(0, &ms));
-    info->iterations = h->it;
-    info->reason = (int)h->reason;
-    info->residual_sq = (double)h->rr;
-    info->rhs_sq = (double)h->bb;
-    info->solve_ms = (double)ms;
+    SPAL_TRY(R.frame.end(&ms));
+    if (!R.stopped) return fail(SPAL_ERR_HIP, "%s: the device did not stop after %llu iterations", fn, (unsigned long long)maxit);
+    R.frame.fill(info, 0, ms);
     Record rec;
     rec.method = method;
     rec.preconditioned = pre ? 1 : 0;
-    rec.amg = g ? 1 : 0;
+    rec.amg = pc.g ? 1 : 0;
     rec.precond_sweeps = sweeps;
     rec.reason = info->reason;
     rec.iterations = info->iterations;
-    rec.polls = polls;
+    rec.polls = R.frame.polls;
     rec.check_every = check_every;
     rec.solve_ms = info->solve_ms;
-    const std::string json = info_json(rec);
-    std::lock_guard<std::mutex> lock(owner->mu);
-    a->ops.krylov_info = json;
+    store_info(a, &OpState::krylov_info, info_json(rec));
     return SPAL_OK;
 }
 
-// every refusal that needs no device
-// (amg: the call takes a hierarchy `g` where m stands, and g is not NULL)
+// every refusal that needs no device (a hierarchy has to agree with a in rows, device and element type)
 template <typename T, typename H>
-int krylov_check(const char *fn, H *a, int method, H *m, const T *b, T *x, double tol, spal_krylov_info *info,
-                 bool amg = false, spal_amg *g = nullptr) {
-    if (!a || !b || !x || !info || (amg && !g)) return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: null argument", fn);
+int krylov_check(const char *fn, H *a, int method, Precond<H> pc, const T *b, T *x, double tol, spal_krylov_info *info) {
+    if (!a || !b || !x || !info) return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: null argument", fn);
     SPAL_TRY(check_dtype<T>(fn, a->elem_size));
     if (method != SPAL_KRYLOV_CG && method != SPAL_KRYLOV_BICGSTAB)
         return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: method = %d must be 0 (CG) or 1 (BiCGStab)", fn, method);
-    SPAL_TRY((krylov_check_operands<T, H>(fn, a, m, tol)));
-    return amg ? amg_check_match(fn, g, a->nrows, a->device, a->elem_size) : SPAL_OK;
+    SPAL_TRY((krylov_check_operands<T, H>(fn, a, pc.m, tol)));
+    return pc.g ? amg_check_match(fn, pc.g, a->nrows, a->device, a->elem_size) : SPAL_OK;
 }
 
 template <typename T, typename H>
-int krylov_dev(const char *fn, H *a, int method, H *m, const T *b, T *x, double tol, uint64_t maxit, void *stream,
-               spal_krylov_info *info, bool amg = false, spal_amg *g = nullptr) {
-    SPAL_TRY((krylov_check<T, H>(fn, a, method, m, b, x, tol, info, amg, g)));
+int krylov_dev(const char *fn, H *a, int method, Precond<H> pc, const T *b, T *x, double tol, uint64_t maxit, void *stream,
+               spal_krylov_info *info) {
+    SPAL_TRY((krylov_check<T, H>(fn, a, method, pc, b, x, tol, info)));
     if (x == b) return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: x_dev == b_dev (b is read in every test of the residual)", fn);
     DeviceGuard guard(a->device);
     if (guard.status != SPAL_OK) return guard.status;
-    return krylov_run<T, H>(fn, a, method, m, g, b, x, tol, maxit, (hipStream_t)stream, info);
+    return krylov_run<T, H>(fn, a, method, pc, b, x, tol, maxit, (hipStream_t)stream, info);
 }
 
 template <typename T, typename H>
-int krylov_host(const char *fn, H *a, int method, H *m, const T *b, uint64_t b_len, T *x, uint64_t x_len, double tol,
-                uint64_t maxit, spal_krylov_info *info, bool amg = false, spal_amg *g = nullptr) {
-    SPAL_TRY((krylov_check<T, H>(fn, a, method, m, b, x, tol, info, amg, g)));
-    SPAL_TRY(refuse_lengths(fn, b_len, x_len, a->nrows));
-    DeviceGuard guard(a->device);
-    if (guard.status != SPAL_OK) return guard.status;
-    const uint64_t n = a->nrows;
-    DevBuf db, dx;
-    PooledStream ps;   // a stream of the call's own: the handle's staging stream belongs to whoever holds its lock
-    SPAL_HIP_TRY(db.alloc(n * sizeof(T)));
-    SPAL_HIP_TRY(dx.alloc(n * sizeof(T)));
-    SPAL_HIP_TRY(stream_acquire(&ps.s));
-    SPAL_HIP_TRY(hipMemcpyAsync(db.p, b, n * sizeof(T), hipMemcpyHostToDevice, ps.s));
-    SPAL_HIP_TRY(hipMemcpyAsync(dx.p, x, n * sizeof(T), hipMemcpyHostToDevice, ps.s));
-    SPAL_TRY((krylov_run<T, H>(fn, a, method, m, g, db.as<T>(), dx.as<T>(), tol, maxit, ps.s, info)));
-    SPAL_HIP_TRY(hipMemcpyAsync(x, dx.p, n * sizeof(T), hipMemcpyDeviceToHost, ps.s));
-    SPAL_HIP_TRY(hipStreamSynchronize(ps.s));
-    return SPAL_OK;
+int krylov_host(const char *fn, H *a, int method, Precond<H> pc, const T *b, uint64_t b_len, T *x, uint64_t x_len, double tol,
+                uint64_t maxit, spal_krylov_info *info) {
+    SPAL_TRY((krylov_check<T, H>(fn, a, method, pc, b, x, tol, info)));
+    return with_host_vectors(fn, a, b, b_len, x, x_len, [&](const T *b_dev, T *x_dev, hipStream_t st) {
+        return krylov_run<T, H>(fn, a, method, pc, b_dev, x_dev, tol, maxit, st, info);
+    });
 }
 
 }  // namespace
@@ -430,13 +366,7 @@ int krylov_option(spal_csr *a, const char *key, int64_t value, OpState &s, int *
 }
 
 int krylov_describe_append(char *buf, size_t buf_len, const OpState &s, spal_csr *solve) {
-    if (!solve) return SPAL_OK;
-    std::string info;
-    {
-        std::lock_guard<std::mutex> lock(solve->mu);
-        info = s.krylov_info;
-    }
-    return describe_append(buf, buf_len, "krylov", info);
+    return info_describe_append(buf, buf_len, s, solve, "krylov", &OpState::krylov_info);
 }
 
 }  // namespace spal
@@ -454,71 +384,29 @@ int spal_dot_dev_f32(int device, const float *a_dev, const float *b_dev, uint64_
     return dot_dev<float>("spal_dot_dev", device, a_dev, b_dev, n, out_dev, stream);
 }
 
-int spal_csr_krylov_f64(spal_csr_t a, int method, spal_csr_t m, const double *b, uint64_t b_len, double *x, uint64_t x_len,
-                        double tol, uint64_t maxit, spal_krylov_info *info) {
-    return krylov_host<double, spal_csr>("spal_csr_krylov", a, method, m, b, b_len, x, x_len, tol, maxit, info);
-}
-int spal_csr_krylov_f32(spal_csr_t a, int method, spal_csr_t m, const float *b, uint64_t b_len, float *x, uint64_t x_len,
-                        double tol, uint64_t maxit, spal_krylov_info *info) {
-    return krylov_host<float, spal_csr>("spal_csr_krylov", a, method, m, b, b_len, x, x_len, tol, maxit, info);
-}
-int spal_csr_krylov_dev_f64(spal_csr_t a, int method, spal_csr_t m, const double *b_dev, double *x_dev, double tol,
-                            uint64_t maxit, void *stream, spal_krylov_info *info) {
-    return krylov_dev<double, spal_csr>("spal_csr_krylov_dev", a, method, m, b_dev, x_dev, tol, maxit, stream, info);
-}
-int spal_csr_krylov_dev_f32(spal_csr_t a, int method, spal_csr_t m, const float *b_dev, float *x_dev, double tol,
-                            uint64_t maxit, void *stream, spal_krylov_info *info) {
-    return krylov_dev<float, spal_csr>("spal_csr_krylov_dev", a, method, m, b_dev, x_dev, tol, maxit, stream, info);
-}
-int spal_csc_krylov_f64(spal_csc_t a, int method, spal_csc_t m, const double *b, uint64_t b_len, double *x, uint64_t x_len,
-                        double tol, uint64_t maxit, spal_krylov_info *info) {
-    return krylov_host<double, spal_csc>("spal_csc_krylov", a, method, m, b, b_len, x, x_len, tol, maxit, info);
-}
-int spal_csc_krylov_f32(spal_csc_t a, int method, spal_csc_t m, const float *b, uint64_t b_len, float *x, uint64_t x_len,
-                        double tol, uint64_t maxit, spal_krylov_info *info) {
-    return krylov_host<float, spal_csc>("spal_csc_krylov", a, method, m, b, b_len, x, x_len, tol, maxit, info);
-}
-int spal_csc_krylov_dev_f64(spal_csc_t a, int method, spal_csc_t m, const double *b_dev, double *x_dev, double tol,
-                            uint64_t maxit, void *stream, spal_krylov_info *info) {
-    return krylov_dev<double, spal_csc>("spal_csc_krylov_dev", a, method, m, b_dev, x_dev, tol, maxit, stream, info);
-}
-int spal_csc_krylov_dev_f32(spal_csc_t a, int method, spal_csc_t m, const float *b_dev, float *x_dev, double tol,
-                            uint64_t maxit, void *stream, spal_krylov_info *info) {
-    return krylov_dev<float, spal_csc>("spal_csc_krylov_dev", a, method, m, b_dev, x_dev, tol, maxit, stream, info);
-}
-
-// the same loops with M^-1 v = cycle(0, v) of an AMG hierarchy (spal_amg.hip)
-int spal_csr_krylov_amg_f64(spal_csr_t a, int method, spal_amg_t g, const double *b, uint64_t b_len, double *x, uint64_t x_len,
-                            double tol, uint64_t maxit, spal_krylov_info *info) {
-    return krylov_host<double, spal_csr>("spal_csr_krylov_amg", a, method, nullptr, b, b_len, x, x_len, tol, maxit, info, true, g);
-}
-int spal_csr_krylov_amg_dev_f64(spal_csr_t a, int method, spal_amg_t g, const double *b_dev, double *x_dev, double tol,
-                                uint64_t maxit, void *stream, spal_krylov_info *info) {
-    return krylov_dev<double, spal_csr>("spal_csr_krylov_amg_dev", a, method, nullptr, b_dev, x_dev, tol, maxit, stream, info, true, g);
-}
-int spal_csr_krylov_amg_f32(spal_csr_t a, int method, spal_amg_t g, const float *b, uint64_t b_len, float *x, uint64_t x_len,
-                            double tol, uint64_t maxit, spal_krylov_info *info) {
-    return krylov_host<float, spal_csr>("spal_csr_krylov_amg", a, method, nullptr, b, b_len, x, x_len, tol, maxit, info, true, g);
-}
-int spal_csr_krylov_amg_dev_f32(spal_csr_t a, int method, spal_amg_t g, const float *b_dev, float *x_dev, double tol,
-                                uint64_t maxit, void *stream, spal_krylov_info *info) {
-    return krylov_dev<float, spal_csr>("spal_csr_krylov_amg_dev", a, method, nullptr, b_dev, x_dev, tol, maxit, stream, info, true, g);
-}
-int spal_csc_krylov_amg_f64(spal_csc_t a, int method, spal_amg_t g, const double *b, uint64_t b_len, double *x, uint64_t x_len,
-                            double tol, uint64_t maxit, spal_krylov_info *info) {
-    return krylov_host<double, spal_csc>("spal_csc_krylov_amg", a, method, nullptr, b, b_len, x, x_len, tol, maxit, info, true, g);
-}
-int spal_csc_krylov_amg_dev_f64(spal_csc_t a, int method, spal_amg_t g, const double *b_dev, double *x_dev, double tol,
-                                uint64_t maxit, void *stream, spal_krylov_info *info) {
-    return krylov_dev<double, spal_csc>("spal_csc_krylov_amg_dev", a, method, nullptr, b_dev, x_dev, tol, maxit, stream, info, true, g);
-}
-int spal_csc_krylov_amg_f32(spal_csc_t a, int method, spal_amg_t g, const float *b, uint64_t b_len, float *x, uint64_t x_len,
-                            double tol, uint64_t maxit, spal_krylov_info *info) {
-    return krylov_host<float, spal_csc>("spal_csc_krylov_amg", a, method, nullptr, b, b_len, x, x_len, tol, maxit, info, true, g);
-}
-int spal_csc_krylov_amg_dev_f32(spal_csc_t a, int method, spal_amg_t g, const float *b_dev, float *x_dev, double tol,
-                                uint64_t maxit, void *stream, spal_krylov_info *info) {
-    return krylov_dev<float, spal_csc>("spal_csc_krylov_amg_dev", a, method, nullptr, b_dev, x_dev, tol, maxit, stream, info, true, g);
-}
+// name = krylov: m is an ILU(0) factor or NULL.  name = krylov_amg: the same loops with M^-1 v = cycle(0, v) of an AMG
+// hierarchy m (spal_amg.hip), which is not optional.
+#define SPAL_KRYLOV_ENTRIES(kind, name, sfx, T, M, NEEDS_M, PRECOND)                                                   \
+    int spal_##kind##_##name##_##sfx(spal_##kind##_t a, int method, M m, const T *b, uint64_t b_len, T *x,             \
+                                     uint64_t x_len, double tol, uint64_t maxit, spal_krylov_info *info) {             \
+        const char *fn = "spal_" #kind "_" #name;                                                                      \
+        if (NEEDS_M && !m) return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: null argument", fn);                            \
+        return krylov_host<T, spal_##kind>(fn, a, method, PRECOND, b, b_len, x, x_len, tol, maxit, info);              \
+    }                                                                                                                  \
+    int spal_##kind##_##name##_dev_##sfx(spal_##kind##_t a, int method, M m, const T *b_dev, T *x_dev, double tol,     \
+                                         uint64_t maxit, void *stream, spal_krylov_info *info) {                       \
+        const char *fn = "spal_" #kind "_" #name "_dev";                                                               \
+        if (NEEDS_M && !m) return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: null argument", fn);                            \
+        return krylov_dev<T, spal_##kind>(fn, a, method, PRECOND, b_dev, x_dev, tol, maxit, stream, info);             \
+    }
+#define SPAL_KRYLOV_KINDS(kind, sfx, T)                                                                                \
+    SPAL_KRYLOV_ENTRIES(kind, krylov, sfx, T, spal_##kind##_t, false, (Precond<spal_##kind>{m, nullptr}))              \
+    SPAL_KRYLOV_ENTRIES(kind, krylov_amg, sfx, T, spal_amg_t, true, (Precond<spal_##kind>{nullptr, m}))
+SPAL_KRYLOV_KINDS(csr, f64, double)
+SPAL_KRYLOV_KINDS(csr, f32, float)
+SPAL_KRYLOV_KINDS(csc, f64, double)
+SPAL_KRYLOV_KINDS(csc, f32, float)
+#undef SPAL_KRYLOV_KINDS
+#undef SPAL_KRYLOV_ENTRIES
 
 }  // extern "C"

@@ -7,8 +7,11 @@
 // search space is shared, so every column keeps its sequential text and its bits.
 //
 // (tile_sum, upper_levels, the scalar block Scal, the ten fused updates and the scalar steps are in krylov_kernels.hpp,
-// shared with spal_krylov.hip: the arithmetic of a column is the vector call's, by construction.  Mat, column_tree, the
-// column tiles and the routes to SpMM and trsm are there too, shared with spal_gmres_block.hip.)
+// shared with spal_krylov.hip: the arithmetic of a column is the vector call's, by construction.  So is the sequence of
+// launches: the two loops are krylov_loops.hpp's, instantiated here on a `Run` whose operands are blocks.  Mat,
+// column_tree, the column tiles and their dispatch (KRYLOV_BY_TILE), the routes to SpMM and trsm, M^-1 on a block, the
+// refusals of k / ldb / ldx, the sweep scratch and the staging of host blocks are in krylov_kernels.hpp too, shared with
+// spal_gmres_block.hip; the frame of a call -- KRYLOV_LAUNCH, SolveFrame, store_info -- with all four drivers.)
 //
 // THE FIRST LEVEL.  A workgroup of 256 covers a tile of 1024 rows x KT columns of the blocks.  Thread t is column
 // t % KT of the tile and row group g = t / KT of G = 256 / KT; it owns rows g, g + G, g + 2G, ... of the tile, L = 4 KT
@@ -183,33 +186,20 @@ __global__ __launch_bounds__(kThreads) void finish_block(BlockFinArgs<T> g) {
     }
 }
 
-// ---- host side of the launches (the tiles, auto_tile, the routes and bytes_of are in krylov_kernels.hpp) ---------------
+// ---- host side of the launches (the tiles and their dispatch, the routes and bytes_of are in krylov_kernels.hpp) -------
 template <typename T, int OP>
-hipError_t launch_vec_block(const BlockVecArgs<T> &g, int tile, hipStream_t st) {
+int launch_vec_block(const char *fn, const BlockVecArgs<T> &g, int tile, hipStream_t st) {
     const uint64_t tiles = tiles_of(g.n);
     const unsigned gx = (unsigned)std::min<uint64_t>(tiles, kBlockMaxGrid);
     const unsigned gy = std::min<unsigned>(grid_of(g.k, (unsigned)tile), kColumnGrid);
-#define SPAL_KB_CASE(KT)                                                                                               \
-    case KT:                                                                                                           \
-        hipLaunchKernelGGL((vec_block<T, OP, KT>), dim3(gx, gy), dim3(kThreads), 0, st, g, tiles);                    \
-        break;
-    switch (tile) {
-        SPAL_KB_CASE(1)
-        SPAL_KB_CASE(2)
-        SPAL_KB_CASE(4)
-        SPAL_KB_CASE(8)
-        SPAL_KB_CASE(16)
-    default:
-        SPAL_KB_CASE(32)
-    }
-#undef SPAL_KB_CASE
-    return hipGetLastError();
+    KRYLOV_BY_TILE(tile, KRYLOV_LAUNCH((vec_block<T, OP, KT_>), dim3(gx, gy), g, tiles));
+    return SPAL_OK;
 }
 
 template <typename T, int OP>
-hipError_t launch_finish_block(const BlockFinArgs<T> &g, hipStream_t st) {
-    hipLaunchKernelGGL((finish_block<T, OP>), dim3(std::min<unsigned>(g.k, kFinishGrid)), dim3(kThreads), 0, st, g);
-    return hipGetLastError();
+int launch_finish_block(const char *fn, const BlockFinArgs<T> &g, hipStream_t st) {
+    KRYLOV_LAUNCH((finish_block<T, OP>), std::min<unsigned>(g.k, kFinishGrid), g);
+    return SPAL_OK;
 }
 
 struct Record {
@@ -230,57 +220,67 @@ std::string info_json(const Record &r) {
     return buf;
 }
 
-// What both loops share: the blocks, the scalar records, the scratch of two dots per column, and the launches by name.
-// A work block is packed (leading dimension k).
+// The driver the loops of krylov_loops.hpp run on: an operand is a block and its leading dimension; the scalar records,
+// the scratch of two dots per column, and the launches by name.  A work block is packed (leading dimension k).
 template <typename T, typename H>
 struct Run {
     const char *fn;
     H *a, *m;
     hipStream_t st;
-    uint64_t n = 0, maxit = 0, c1 = 0, pe = 0;
+    uint64_t n = 0, maxit = 0, c1 = 0, pe = 0, stride = 0;
     uint32_t k = 0;
     int tile = 1;
     T tol2 = T(0);
     Scal<T> *s = nullptr;
     T *part0 = nullptr, *part1 = nullptr;
     int64_t sweeps = -1;   // m's option "trsv_sweeps"
+    T *blocks = nullptr;   // work block i at blocks + i * stride
+    Mat<const T> b;
+    Mat<T> x;
+    SolveFrame<Scal<T>> frame;
+    uint64_t stopped = 0;   // columns the last poll found stopped
 
-    int mul(Mat<const T> v, T *out) { return mul_block(a, k, v.p, v.ld, out, k, st); }
-    // out = M^-1 v (out != v, both packed); without a preconditioner the caller uses v itself
-    int prec(const T *v, T *out) {
-        if (sweeps >= 0) {
-            SPAL_TRY(sweep_block(m, 0, 1, (uint64_t)sweeps, k, v, k, out, k, st));
-            return sweep_block(m, 1, 0, (uint64_t)sweeps, k, out, k, out, k, st);
-        }
-        SPAL_TRY(solve_block(m, 0, 1, k, v, k, out, k, st));
-        return solve_block(m, 1, 0, k, out, k, out, k, st);
-    }
-    template <int OP>
-    int v(Mat<const T> va, Mat<const T> vb, Mat<const T> vc, Mat<const T> vd, Mat<T> x, Mat<T> y) {
-        BlockVecArgs<T> g = {va, vb, vc, vd, x, y, s, part0, part1, n, pe, k};
-        const hipError_t e = launch_vec_block<T, OP>(g, tile, st);
-        return e == hipSuccess ? SPAL_OK : fail(SPAL_ERR_HIP, "%s: launch failed: %s", fn, hipGetErrorString(e));
+    static Mat<T> null() { return {nullptr, 0}; }
+    Mat<const T> B() const { return b; }
+    Mat<T> X() const { return x; }
+    Mat<T> work(int i) const { return {blocks + (uint64_t)i * stride, (uint64_t)k}; }
+    bool preconditioned() const { return m != nullptr; }
+    int mul(Mat<T> v, Mat<T> out) { return mul_block(a, k, v.p, v.ld, out.p, out.ld, st); }
+    // out = M^-1 v (out != v, both packed); without a preconditioner the loops use v itself
+    int prec(Mat<T> v, Mat<T> out) { return prec_block<T, H>(m, sweeps, k, v.p, out.p, st); }
+    template <int OP, typename A>   // A: T, or const T where the operand is B
+    int v(Mat<A> va, Mat<T> vb, Mat<T> vc, Mat<T> vd, Mat<T> vx, Mat<T> vy) {
+        return launch_vec_block<T, OP>(
+            fn, BlockVecArgs<T>{{va.p, va.ld}, {vb.p, vb.ld}, {vc.p, vc.ld}, {vd.p, vd.ld}, vx, vy, s, part0, part1, n, pe, k}, tile, st);
     }
     template <int OP>
     int f(int unpreconditioned = 0) {
-        BlockFinArgs<T> g = {s, part0, part1, c1, pe, k, tol2, maxit, unpreconditioned};
-        const hipError_t e = launch_finish_block<T, OP>(g, st);
-        return e == hipSuccess ? SPAL_OK : fail(SPAL_ERR_HIP, "%s: launch failed: %s", fn, hipGetErrorString(e));
+        return launch_finish_block<T, OP>(fn, BlockFinArgs<T>{s, part0, part1, c1, pe, k, tol2, maxit, unpreconditioned}, st);
     }
+    int copy(Mat<T> dst, Mat<T> src) {
+        SPAL_HIP_TRY(hipMemcpyAsync(dst.p, src.p, (size_t)(n * k) * sizeof(T), hipMemcpyDeviceToDevice, st));
+        return SPAL_OK;
+    }
+    int zero(Mat<T> dst) {
+        SPAL_HIP_TRY(hipMemsetAsync(dst.p, 0, (size_t)(n * k) * sizeof(T), st));
+        return SPAL_OK;
+    }
+    int poll() {   // the k records to pinned memory; how many columns have stopped
+        SPAL_TRY(frame.poll());
+        stopped = 0;
+        for (uint32_t j = 0; j < k; ++j) stopped += frame.h[j].done != 0;
+        return SPAL_OK;
+    }
+    bool all_stopped() const { return stopped == k; }
+    uint64_t polls() const { return frame.polls; }
 };
 
 template <typename T, typename H>
 int block_run(const char *fn, H *a, int method, H *m, uint32_t k, const T *b, uint64_t ldb, T *x, uint64_t ldx,
               double tol, uint64_t maxit, hipStream_t st, spal_krylov_info *info) {
     const uint64_t n = a->nrows;
-    spal_csr *owner = solve_handle(a);   // whose lock guards a's options and its "krylov_block" string
     const int64_t check_every = krylov_check_every_of(a, m != nullptr);
-    int tile;
-    {
-        std::lock_guard<std::mutex> lock(owner->mu);
-        tile = a->ops.krylov_tile;
-    }
-    if (!tile) tile = auto_tile(k);
+    const int tile = column_tile_of(a, k);
     SPAL_TRY(refuse_capture(fn, st, "the call polls and synchronises"));
     int64_t sweeps = -1;
     SPAL_TRY(krylov_prepare(fn, a, m, st, &sweeps));
@@ -296,26 +296,13 @@ int block_run(const char *fn, H *a, int method, H *m, uint32_t k, const T *b, ui
         !bytes_of(stride, 2, sizeof(T), 1, &sweep_bytes))
         return fail(SPAL_ERR_OUT_OF_MEMORY, "%s: no room for work blocks of %llu x %u", fn, (unsigned long long)n, k);
     DevBuf blocks, parts, scal;
-    PinnedBuf host;
-    EventSpans ev;
     SPAL_HIP_TRY(blocks.alloc(work_bytes));
     SPAL_HIP_TRY(parts.alloc(part_bytes));
     SPAL_HIP_TRY(scal.alloc((size_t)k * sizeof(Scal<T>)));
-    SPAL_HIP_TRY(hipHostMalloc(&host.p, (size_t)k * sizeof(Scal<T>), hipHostMallocDefault));
-    SPAL_HIP_TRY(ev.create(1));
-    if (m && sweeps >= 1 && n) {   // the stream's sweep scratch holds n x k per ping-pong block from here on
-        StreamWork grow;
-        SPAL_TRY(grow.take(fn, st, sweep_bytes));
-    }
-    auto block_at = [&](int i) { return blocks.as<T>() + (uint64_t)i * stride; };
-    auto Out = [&](T *p) { return Mat<T>{p, (uint64_t)k}; };
-    auto In = [&](const T *p) { return Mat<const T>{p, (uint64_t)k}; };
-    const Mat<const T> none = {nullptr, 0};
-    const Mat<T> nonew = {nullptr, 0};
-    const Mat<const T> B = {b, ldb};
-    const Mat<T> X = {x, ldx};
 
     Run<T, H> R;
+    SPAL_TRY(R.frame.create(st, k));
+    SPAL_TRY(grow_sweep_scratch(fn, st, m, sweeps, n, sweep_bytes));
     R.fn = fn;
     R.a = a;
     R.m = m;
@@ -324,6 +311,7 @@ int block_run(const char *fn, H *a, int method, H *m, uint32_t k, const T *b, ui
     R.maxit = maxit;
     R.c1 = tiles_of(n);
     R.pe = pe;
+    R.stride = stride;
     R.k = k;
     R.tile = tile;
     R.tol2 = (T)(tol * tol);
@@ -331,130 +319,47 @@ int block_run(const char *fn, H *a, int method, H *m, uint32_t k, const T *b, ui
     R.part0 = parts.as<T>();
     R.part1 = parts.as<T>() + pe * k;
     R.sweeps = sweeps;
+    R.blocks = blocks.as<T>();
+    R.b = {b, ldb};
+    R.x = {x, ldx};
 
-    Scal<T> *h = (Scal<T> *)host.p;
-    uint64_t polls = 0, stopped = 0;
-    auto poll = [&]() -> int {   // the k records to pinned memory; how many columns have stopped
-        SPAL_HIP_TRY(hipMemcpyAsync(h, R.s, (size_t)k * sizeof(Scal<T>), hipMemcpyDeviceToHost, st));
-        SPAL_HIP_TRY(hipStreamSynchronize(st));
-        ++polls;
-        stopped = 0;
-        for (uint32_t j = 0; j < k; ++j) stopped += h[j].done != 0;
-        return SPAL_OK;
-    };
-
-    SPAL_HIP_TRY(hipEventRecord(ev.e[0], st));
-    SPAL_HIP_TRY(hipMemsetAsync(R.s, 0, (size_t)k * sizeof(Scal<T>), st));
-    T *r = block_at(0), *q = block_at(1), *p = block_at(2);
-    // r = b - A x;  rr, bb;  it = 0;  test
-    SPAL_TRY(R.mul(Mat<const T>{x, ldx}, q));
-    SPAL_TRY((R.template v<V_INIT>(B, In(q), none, none, nonew, Out(r))));
-    SPAL_TRY((R.template f<F_INIT>()));
-    uint64_t enqueued = 0;
-    if (cg) {
-        T *z = m ? block_at(3) : r;
-        if (m) SPAL_TRY(R.prec(r, z));
-        SPAL_TRY((R.template v<V_COPY_DOT>(In(r), In(z), none, none, nonew, Out(p))));   // p = z;  rz
-        SPAL_TRY((R.template f<F_RZ>()));
-        while (enqueued < maxit && stopped < k) {
-            const uint64_t batch = std::min<uint64_t>((uint64_t)check_every, maxit - enqueued);
-            for (uint64_t i = 0; i < batch; ++i) {
-                SPAL_TRY(R.mul(In(p), q));
-                SPAL_TRY((R.template v<V_DOT>(In(p), In(q), none, none, nonew, nonew)));
-                SPAL_TRY((R.template f<F_ALPHA_CG>()));
-                SPAL_TRY((R.template v<V_CG_XR>(In(p), In(q), none, none, X, Out(r))));   // x, r;  rr
-                SPAL_TRY((R.template f<F_TEST_CG>(m ? 0 : 1)));                           // it, test (and beta when z is r)
-                if (m) {
-                    SPAL_TRY(R.prec(r, z));
-                    SPAL_TRY((R.template v<V_DOT>(In(r), In(z), none, none, nonew, nonew)));
-                    SPAL_TRY((R.template f<F_BETA>()));
-                }
-                SPAL_TRY((R.template v<V_CG_P>(In(z), none, none, none, nonew, Out(p))));
-            }
-            enqueued += batch;
-            SPAL_TRY(poll());
-        }
-    } else {
-        T *rhat = block_at(3), *vv = block_at(4), *t = block_at(5);
-        T *sv = q;   // q is free once r exists
-        T *ph = m ? block_at(6) : p, *sh = m ? block_at(7) : sv;
-        SPAL_HIP_TRY(hipMemcpyAsync(rhat, r, (size_t)(n * k) * sizeof(T), hipMemcpyDeviceToDevice, st));
-        SPAL_HIP_TRY(hipMemsetAsync(vv, 0, (size_t)(n * k) * sizeof(T), st));
-        SPAL_HIP_TRY(hipMemsetAsync(p, 0, (size_t)(n * k) * sizeof(T), st));
-        while (enqueued < maxit && stopped < k) {
-            const uint64_t batch = std::min<uint64_t>((uint64_t)check_every, maxit - enqueued);
-            for (uint64_t i = 0; i < batch; ++i) {
-                SPAL_TRY((R.template v<V_DOT>(In(rhat), In(r), none, none, nonew, nonew)));
-                SPAL_TRY((R.template f<F_RHO>()));
-                SPAL_TRY((R.template v<V_BI_P>(In(r), In(vv), none, none, nonew, Out(p))));
-                if (m) SPAL_TRY(R.prec(p, ph));
-                SPAL_TRY(R.mul(In(ph), vv));
-                SPAL_TRY((R.template v<V_DOT>(In(rhat), In(vv), none, none, nonew, nonew)));
-                SPAL_TRY((R.template f<F_ALPHA_BI>()));
-                SPAL_TRY((R.template v<V_BI_S>(In(r), In(vv), none, none, nonew, Out(sv))));   // s;  ss
-                SPAL_TRY((R.template f<F_HALF>()));                                            // it;  the half-step exit
-                SPAL_TRY((R.template v<V_BI_HALF>(In(ph), In(sv), none, none, X, Out(r))));    // ... applied, where taken
-                if (m) SPAL_TRY(R.prec(sv, sh));
-                SPAL_TRY(R.mul(In(sh), t));
-                SPAL_TRY((R.template v<V_DOT2>(In(t), In(sv), none, none, nonew, nonew)));     // t . s, t . t
-                SPAL_TRY((R.template f<F_OMEGA>()));
-                SPAL_TRY((R.template v<V_BI_XR>(In(ph), In(sh), In(sv), In(t), X, Out(r))));   // x, r;  rr
-                SPAL_TRY((R.template f<F_TEST_BI>()));
-            }
-            enqueued += batch;
-            SPAL_TRY(poll());
-        }
-    }
-    if (!polls) SPAL_TRY(poll());   // maxit = 0: the test after r0 has decided
-    SPAL_HIP_TRY(hipEventRecord(ev.e[1], st));
-    SPAL_HIP_TRY(hipStreamSynchronize(st));
-    if (stopped < k)
-        return fail(SPAL_ERR_HIP, "%s: %llu of %u columns did not stop after %llu iterations", fn,
-                    (unsigned long long)(k - stopped), k, (unsigned long long)maxit);
+    SPAL_TRY(R.frame.begin(R.s, (size_t)k * sizeof(Scal<T>)));
+    SPAL_TRY(krylov_start(R));
+    SPAL_TRY(cg ? cg_loop(R, maxit, (uint64_t)check_every) : bicgstab_loop(R, maxit, (uint64_t)check_every));
     float ms = 0.f;
-    SPAL_HIP_TRY(ev.span(0, &ms));
+    SPAL_TRY(R.frame.end(&ms));
+    if (R.stopped < k)
+        return fail(SPAL_ERR_HIP, "%s: %llu of %u columns did not stop after %llu iterations", fn,
+                    (unsigned long long)(k - R.stopped), k, (unsigned long long)maxit);
     Record rec;
-    rec.iterations_min = h[0].it;
+    rec.iterations_min = R.frame.h[0].it;
     for (uint32_t j = 0; j < k; ++j) {
-        info[j].iterations = h[j].it;
-        info[j].reason = (int)h[j].reason;
-        info[j].residual_sq = (double)h[j].rr;
-        info[j].rhs_sq = (double)h[j].bb;
-        info[j].solve_ms = (double)ms;
-        rec.iterations_min = std::min<uint64_t>(rec.iterations_min, h[j].it);
-        rec.iterations_max = std::max<uint64_t>(rec.iterations_max, h[j].it);
-        rec.converged += h[j].reason == 0;
+        R.frame.fill(info + j, j, ms);
+        rec.iterations_min = std::min<uint64_t>(rec.iterations_min, info[j].iterations);
+        rec.iterations_max = std::max<uint64_t>(rec.iterations_max, info[j].iterations);
+        rec.converged += info[j].reason == 0;
     }
     rec.method = method;
     rec.k = k;
     rec.preconditioned = m ? 1 : 0;
     rec.precond_sweeps = sweeps;
     rec.tile = tile;
-    rec.polls = polls;
+    rec.polls = R.frame.polls;
     rec.check_every = check_every;
     rec.solve_ms = (double)ms;
-    const std::string json = info_json(rec);
-    std::lock_guard<std::mutex> lock(owner->mu);
-    a->ops.krylov_block_info = json;
+    store_info(a, &OpState::krylov_block_info, info_json(rec));
     return SPAL_OK;
 }
 
-// Every refusal that needs no device; `who` begins the messages ("spal_csr_krylov_block").  The block's geometry and the
-// method come first: they need nothing of the handles.
+// Every refusal that needs no device; `who` begins the messages ("spal_csr_krylov_block").  The method and the block's
+// geometry come first: they need nothing of the handles.
 template <typename T, typename H>
 int block_check(const char *who, H *a, int method, H *m, uint64_t k, const T *b, uint64_t ldb, T *x, uint64_t ldx,
                 double tol, spal_krylov_info *info) {
     if (!a || !b || !x || !info) return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: null argument", who);
     if (method != SPAL_KRYLOV_CG && method != SPAL_KRYLOV_BICGSTAB)
         return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: method = %d must be 0 (CG) or 1 (BiCGStab)", who, method);
-    if (k == 0) return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: k = 0 (B and X need at least one column)", who);
-    if (k > 0xffffffffull) return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: k = %llu does not fit 32 bits", who, (unsigned long long)k);
-    if (ldb < k)
-        return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: ldb = %llu is less than k = %llu", who, (unsigned long long)ldb,
-                    (unsigned long long)k);
-    if (ldx < k)
-        return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: ldx = %llu is less than k = %llu", who, (unsigned long long)ldx,
-                    (unsigned long long)k);
+    SPAL_TRY(check_block_geometry(who, k, ldb, ldx));
     SPAL_TRY(check_dtype<T>(who, a->elem_size));
     return krylov_check_operands<T, H>(who, a, m, tol);
 }
@@ -469,35 +374,13 @@ int block_dev(const char *who, H *a, int method, H *m, uint64_t k, const T *b, u
     return block_run<T, H>(who, a, method, m, (uint32_t)k, b, ldb, x, ldx, tol, maxit, (hipStream_t)stream, info);
 }
 
-// host blocks: B and X0 go up packed (leading dimension k), the k columns of X come back into the caller's rows
 template <typename T, typename H>
 int block_host(const char *who, H *a, int method, H *m, uint64_t k, const T *b, uint64_t ldb, uint64_t b_rows, T *x,
                uint64_t ldx, uint64_t x_rows, double tol, uint64_t maxit, spal_krylov_info *info) {
     SPAL_TRY((block_check<T, H>(who, a, method, m, k, b, ldb, x, ldx, tol, info)));
-    if (b_rows != a->nrows || x_rows != a->nrows)
-        return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: B has %llu rows and X has %llu rows but the matrix has %llu rows", who,
-                    (unsigned long long)b_rows, (unsigned long long)x_rows, (unsigned long long)a->nrows);
-    DeviceGuard guard(a->device);
-    if (guard.status != SPAL_OK) return guard.status;
-    const uint64_t n = a->nrows;
-    size_t bytes = 0;
-    if (!bytes_of(n, k, sizeof(T), 1, &bytes))
-        return fail(SPAL_ERR_OUT_OF_MEMORY, "%s: no room for blocks of %llu x %llu", who, (unsigned long long)n,
-                    (unsigned long long)k);
-    const size_t row = (size_t)k * sizeof(T);
-    DevBuf db, dx;
-    PooledStream ps;   // a stream of the call's own: the handle's staging stream belongs to whoever holds its lock
-    SPAL_HIP_TRY(db.alloc(bytes));
-    SPAL_HIP_TRY(dx.alloc(bytes));
-    SPAL_HIP_TRY(stream_acquire(&ps.s));
-    if (n) {
-        SPAL_HIP_TRY(hipMemcpy2DAsync(db.p, row, b, (size_t)ldb * sizeof(T), row, n, hipMemcpyHostToDevice, ps.s));
-        SPAL_HIP_TRY(hipMemcpy2DAsync(dx.p, row, x, (size_t)ldx * sizeof(T), row, n, hipMemcpyHostToDevice, ps.s));
-    }
-    SPAL_TRY((block_run<T, H>(who, a, method, m, (uint32_t)k, db.as<T>(), k, dx.as<T>(), k, tol, maxit, ps.s, info)));
-    if (n) SPAL_HIP_TRY(hipMemcpy2DAsync(x, (size_t)ldx * sizeof(T), dx.p, row, row, n, hipMemcpyDeviceToHost, ps.s));
-    SPAL_HIP_TRY(hipStreamSynchronize(ps.s));
-    return SPAL_OK;
+    return with_host_block(who, a, k, b, ldb, b_rows, x, ldx, x_rows, [&](const T *b_dev, T *x_dev, hipStream_t st) {
+        return block_run<T, H>(who, a, method, m, (uint32_t)k, b_dev, k, x_dev, k, tol, maxit, st, info);
+    });
 }
 
 }  // namespace
@@ -515,13 +398,7 @@ int krylov_block_option(spal_csr *a, const char *key, int64_t value, OpState &s,
 }
 
 int krylov_block_describe_append(char *buf, size_t buf_len, const OpState &s, spal_csr *solve) {
-    if (!solve) return SPAL_OK;
-    std::string info;
-    {
-        std::lock_guard<std::mutex> lock(solve->mu);
-        info = s.krylov_block_info;
-    }
-    return describe_append(buf, buf_len, "krylov_block", info);
+    return info_describe_append(buf, buf_len, s, solve, "krylov_block", &OpState::krylov_block_info);
 }
 
 }  // namespace spal
