@@ -144,7 +144,10 @@ int spal_csr_download_f32(spal_csr_t a, uint64_t *rowptr, uint64_t *colind,
  * longer row go to the overflow kernel; default 128), "skew" (-1 auto, 0, 1:
  * skewed LDS product strips), "slide" (-1 auto / 0: the sliding-window kernel
  * and its ring-addressed x window for band-like plans), "slide_on" (0 / 1:
- * launch it), "uniform_rows" (0 / 1: super-tiles whose rows all have one length
+ * launch it), "rowrec" (-1 auto / 0 / 1: rows of one even length in [12, 16]
+ * under the sliding kernel stream one 20- or 24-byte record per row instead of
+ * the row's 16-bit columns), "rowrec_on" (0 / 1: launch that form),
+ * "uniform_rows" (0 / 1: super-tiles whose rows all have one length
  * do not read rowptr), "prefetch" (1 / 2 tiles of loads ahead), "place_tries"
  * (autotune), "split_tiles" (1 default / 0: the sliding kernel computes tiles
  * above 1024 entries whose halves fit in two passes instead of leaving them to

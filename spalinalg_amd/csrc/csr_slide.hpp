@@ -23,6 +23,7 @@
 // launch: the kernels of csr_kernels.hpp read the same ring-encoded col16).  Everything else keeps those kernels.
 #pragma once
 #include "csr_kernels.hpp"
+#include "csr_rowrec.hpp"
 
 namespace spal {
 
@@ -80,8 +81,10 @@ __device__ __forceinline__ SlideNew slide_new_pages(uint32_t fa, uint32_t na, ui
     return r;
 }
 
-// One tile's loads, exactly S + S (+ 2) of them whatever the tile holds.
-template <typename T, int RPT, int S, bool UNI>
+// One tile's loads, exactly S + S (+ 2) of them whatever the tile holds.  REC != 0 (the row-record form, csr_rowrec.hpp:
+// every row of the matrix holds REC entries, 64 rows per tile, S = REC / 2): `col16` is the record array and the tile
+// issues rowrec_dwords(REC) record loads -- first, the decode starts on them -- and its S value loads.
+template <typename T, int RPT, int S, bool UNI, int REC = 0>
 __device__ __forceinline__ void slide_tile_load(StreamTile<T> &t, const uint32_t *__restrict__ rowptr,
                                                 const uint16_t *__restrict__ col16, const T *__restrict__ vals,
                                                 uint32_t row0, uint32_t nrows, uint32_t b, uint32_t e, uint32_t lane,
@@ -93,11 +96,12 @@ __device__ __forceinline__ void slide_tile_load(StreamTile<T> &t, const uint32_t
     t.steps = (e - t.start + 127u) >> 7;          // <= S by the plan
     const uint32_t e0 = t.start + lane * 2;
     const uint32_t jmax = max(t.steps, 1u) - 1u;  // steps past the tile's last re-read it (an L2 hit, no new bytes)
+    if constexpr (REC != 0) rowrec_tile_load<T, REC>(t, reinterpret_cast<const uint32_t *>(col16), row0 / 64u, lane);
 #pragma unroll
     for (int j = 0; j < S; ++j) {
         const uint32_t at = e0 + min((uint32_t)j, jmax) * 128u;
         t.v[j] = __builtin_nontemporal_load(reinterpret_cast<const pair_t *>(vals + at));
-        t.c[j] = __builtin_nontemporal_load(reinterpret_cast<const uint32_t *>(col16 + at));
+        if constexpr (REC == 0) t.c[j] = __builtin_nontemporal_load(reinterpret_cast<const uint32_t *>(col16 + at));
     }
     if constexpr (UNI) {     // every row of the matrix's streamed tiles holds ulen - 1 entries: rowptr is not read
         const uint32_t len = ulen - 1u, nrt = rlast - min(row0, rlast);
@@ -109,13 +113,14 @@ __device__ __forceinline__ void slide_tile_load(StreamTile<T> &t, const uint32_t
     }
 }
 
-template <typename T, int RPT, int S, bool UNI, int PF>
+template <typename T, int RPT, int S, bool UNI, int PF, int REC = 0>
 __global__ __launch_bounds__(kStreamBlock, 2) void csr_spmv_slide(
     const uint32_t *__restrict__ rowptr, const uint16_t *__restrict__ col16, const T *__restrict__ vals,
     const T *__restrict__ x, T *__restrict__ y, const uint2 *__restrict__ sdesc, uint32_t nrows, uint32_t ncols,
     uint32_t nsteps, uint32_t per_xcd, uint32_t chunk, uint32_t NP, uint32_t ulen, uint32_t flags) {
     static_assert(PF == 1 || PF == 2, "one or two tiles of loads ahead");
     static_assert(S >= 1 && S <= kStreamSteps, "a tile holds at most kStreamSteps steps");
+    static_assert(REC == 0 || (UNI && RPT == 64 && rowrec_length_ok(REC) && S == REC / 2), "row records: uniform rows, a row per lane");
     using vec_t = typename SlideVec<T>::type;
     extern __shared__ __attribute__((aligned(16))) unsigned char spal_smem[];
     constexpr uint32_t V = 16 / sizeof(T), VP = kPageCols / V;
@@ -181,7 +186,7 @@ __global__ __launch_bounds__(kStreamBlock, 2) void csr_spmv_slide(
     uint2 dn = sdesc[gi(1u)];
 #pragma unroll
     for (int q = 0; q < PF; ++q)
-        slide_tile_load<T, RPT, S, UNI>(t[q], rowptr, col16, vals, tile_row((uint32_t)q), nrows, tb[q], te[q], lane, ulen);
+        slide_tile_load<T, RPT, S, UNI, REC>(t[q], rowptr, col16, vals, tile_row((uint32_t)q), nrows, tb[q], te[q], lane, ulen);
     // the first window, whole: kSlideFirstBatch vectors per thread requested back to back (12: the 24 pages of an f64 window
     // in ONE round trip; four at a time made it three, and a shard-sized launch is only 7.6 steps per workgroup long)
     {
@@ -224,7 +229,7 @@ __global__ __launch_bounds__(kStreamBlock, 2) void csr_spmv_slide(
             nv[k] = slide_load_vec<T>(x, mine ? new_page(j) : 0u, mine ? j % VP : 0u, last_vec);
         }
         // the tile PF steps ahead
-        slide_tile_load<T, RPT, S, UNI>(t[KN], rowptr, col16, vals, tile_row(i + PF), nrows, tb[KN], te[KN], lane, ulen);
+        slide_tile_load<T, RPT, S, UNI, REC>(t[KN], rowptr, col16, vals, tile_row(i + PF), nrows, tb[KN], te[KN], lane, ulen);
         // ... and the entry range of the one after it (slot K is free: step i's loads went out PF steps ago)
         tb[K] = tile_b(i + PF + 1u);
         te[K] = tile_e(i + PF + 1u);
@@ -239,8 +244,9 @@ __global__ __launch_bounds__(kStreamBlock, 2) void csr_spmv_slide(
         } else
 #endif
         if (r0 < nrows && !((skip >> wave) & 1u)) {
+            if constexpr (REC != 0) rowrec_expand<T, REC>(t[K], reinterpret_cast<uint32_t *>(prod), NP * kPageCols, lane);
             stream_compute<T, RPT, false>(t[K], xw, wmax, prod, y, r0, nrows, lane, nt_store, flags);
-        } else if (r0 < nrows && ((d.y >> (20u + wave)) & 1u)) {
+        } else if (REC == 0 && r0 < nrows && ((d.y >> (20u + wave)) & 1u)) {   // (a record plan has no such tile)
             // More than the strip's 1024 entries, but each half of the rows fits (the plan checked): two passes
             // through the strip, rows [r0, rm) then [rm, re) -- same loads, products and left-to-right sums as any
             // tile, so these rows stay bit-identical too.  The slot's registers hold the tile's first 1024 entries,

@@ -298,6 +298,7 @@ void csr_free(spal_csr *a) {
     (void)dev_free(a->d_desc);
     if (a->col16_placed) place_free(a->device, a->d_col16);
     else (void)dev_free(a->d_col16);
+    rowrec_free(a);
     (void)dev_free(a->d_pages);
     (void)dev_free(a->d_ovtiles);
     (void)dev_free(a->d_sdesc);
@@ -640,6 +641,11 @@ static const PlanIntOption kPlanIntOptions[] = {
     // sliding kernel: tiles above 1024 entries whose two halves fit the strip are computed in two passes (1,
     // default) or left to the overflow kernel like every other skipped tile (0)
     {"split_tiles", &CsrPlan::split_tiles_on, 0, 1, nullptr, "split_tiles must be 0 or 1"},
+    // sliding kernel, rows of one even length in [12, 16]: one Elias-Fano record per row instead of its col16
+    // (csr_rowrec.hpp): -1 = where the plan qualifies (default), 0 = never, 1 = as -1; "rowrec_on" 0 keeps the records
+    // but streams col16 on the same plan (A/B, as "slide_on")
+    {"rowrec", &CsrPlan::rowrec_user, -1, 1, nullptr, "rowrec must be -1 (auto), 0 or 1"},
+    {"rowrec_on", &CsrPlan::rowrec_on, 0, 1, nullptr, "rowrec_on must be 0 or 1"},
     // autotune: blocks of 1 GiB the 16-bit columns are tried in (0 = leave them where they are)
     {"place_tries", &CsrPlan::place_tries, 0, 16, nullptr, "place_tries must be in [0, 16]"},
     // stream kernel: super-tiles whose rows all have one length do not read rowptr (default 1)
@@ -864,6 +870,22 @@ static int csr_describe_plan(spal_csr_t a, char *buf, size_t buf_len) {
              p.kernel == 2 ? p.nonlocal_row_fraction : 0.0, (p.cblock && p.cblock_on) ? 1 : 0, p.cblock_pending, p.cblock ? p.cblock_rows : 0, !p.cblock ? "" : p.cblock_form ? "rows" : "entry", p.cblock ? (double)p.cblock_run : 0.0,
              p.cblock ? (1ull << p.cblock_shift) : 0ull, p.cblock ? p.cblock_nbc : 0, p.cblock ? p.cblock_nrb : 0u,
              (double)a->cblock_us[0], (double)a->cblock_us[1], a->cblock_failed);
+    // row records (csr_rowrec.hpp), where the plan has the sliding kernel they ride on: built, launched, their size, the
+    // widest row they hold under this plan's ring, the autotune's {col16, records} per launch.  (Plans without it say nothing:
+    // a caller's buffer that held the line of a small matrix still does.)
+    if (p.kernel == 2 && p.slide) {
+        const bool rr = p.rowrec && a->d_rowrec;
+        const int rr_len = p.slide_uniform - 1;
+        SPAL_TRY(describe_append(buf, buf_len, "rowrec", rr ? "1" : "0"));
+        SPAL_TRY(describe_append(buf, buf_len, "rowrec_on", (rr && p.rowrec_on && p.slide_on && p.slide_fill_ok) ? "1" : "0"));
+        SPAL_TRY(describe_append(buf, buf_len, "rowrec_bytes_per_row", std::to_string(rr ? 4 * rowrec_dwords(p.rowrec) : 0)));
+        SPAL_TRY(describe_append(buf, buf_len, "rowrec_max_span",
+                                 std::to_string(rowrec_length_ok(rr_len) ? rowrec_max_span(rr_len, (uint32_t)p.ring_pages * kPageCols) : 0u)));
+        SPAL_TRY(describe_append(buf, buf_len, "rowrec_failed", std::to_string(p.rowrec_failed)));
+        char us[64];
+        snprintf(us, sizeof(us), "[%.1f, %.1f]", (double)a->rowrec_us[0], (double)a->rowrec_us[1]);
+        SPAL_TRY(describe_append(buf, buf_len, "rowrec_us", us));
+    }
     return SPAL_OK;
 }
 int spal_csr_describe(spal_csr_t a, char *buf, size_t buf_len) {

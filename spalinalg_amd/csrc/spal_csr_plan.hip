@@ -536,6 +536,7 @@ int csr_plan_build(spal_csr *a) {
     p.stream_row_fraction = 0.0;
     p.vec_col16 = 0;
     p.slide = 0;
+    p.rowrec = 0;
     p.ring_pages = 0;
     if (a->nnz == 0) {
         cblock_free(a);
@@ -667,6 +668,8 @@ int csr_plan_build(spal_csr *a) {
                                        a->d_colind, a->d_ptiles, a->d_pwin, a->d_col16, (uint32_t)a->nrows, R);
                 SPAL_HIP_TRY(hipGetLastError());
             }
+            // uniform short rows under the sliding kernel: one record per row instead of its col16 (csr_rowrec.hpp)
+            SPAL_TRY(rowrec_plan(a));
             if (best_over) {   // the tiles the stream kernels skip: listed for csr_spmv_overflow
                 uint32_t *d_list = nullptr;   // [count][first rows]
                 const uint32_t pieces = (uint32_t)std::max(1, best_rpt / 64) * best_over;   // (at most)
@@ -708,6 +711,7 @@ int csr_plan_build(spal_csr *a) {
         }
     }
     cblock_free(a);
+    rowrec_free(a);
 
     // ---- vector kernel
     p.kernel = 1;

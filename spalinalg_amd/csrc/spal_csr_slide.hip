@@ -6,7 +6,7 @@
 
 namespace spal {
 
-template <typename T, int RPT, int S, bool UNI>
+template <typename T, int RPT, int S, bool UNI, int REC = 0>
 static hipError_t launch_slide_inst(const spal_csr *a, const void *x, void *y, hipStream_t st) {
     constexpr int PF = 2;
     const CsrPlan &p = a->plan;
@@ -22,7 +22,9 @@ static hipError_t launch_slide_inst(const spal_csr *a, const void *x, void *y, h
     const uint32_t chunk = p.slide_run > 0 ? std::min<uint32_t>((uint32_t)p.slide_run, one_run) : one_run;
     const bool even = p.slide_run <= 0 && p.slide_even;        // one run per workgroup: the steps split evenly (csr_slide.hpp)
     const uint32_t used = even ? std::min(slots, per_xcd) : std::min(slots, (per_xcd + chunk - 1u) / chunk);
-    auto kern = csr_spmv_slide<T, RPT, S, UNI, PF>;
+    auto kern = csr_spmv_slide<T, RPT, S, UNI, PF, REC>;
+    // (the record form streams the records where the others stream col16)
+    const uint16_t *cols = REC != 0 ? reinterpret_cast<const uint16_t *>(a->d_rowrec) : a->d_col16;
     static std::atomic<uint64_t> configured{0};
     const uint64_t bit = 1ull << (a->device & 63);
     if (lds > 48 * 1024 && !(configured.load(std::memory_order_relaxed) & bit)) {
@@ -30,7 +32,7 @@ static hipError_t launch_slide_inst(const spal_csr *a, const void *x, void *y, h
         if (e != hipSuccess) return e;
         configured.fetch_or(bit, std::memory_order_relaxed);
     }
-    hipLaunchKernelGGL(kern, dim3(used * 8u), dim3(kStreamBlock), lds, st, a->d_rowptr, a->d_col16,
+    hipLaunchKernelGGL(kern, dim3(used * 8u), dim3(kStreamBlock), lds, st, a->d_rowptr, cols,
                        (const T *)a->d_values, (const T *)x, (T *)y, a->d_sdesc, (uint32_t)a->nrows, (uint32_t)a->ncols,
                        p.slide_steps, per_xcd, chunk, (uint32_t)p.ring_pages, (uint32_t)p.slide_uniform,
                        (uint32_t)(p.nt_store ? 1 : 0) | (uint32_t)p.diag | ((UNI && p.all_rows_uniform && p.arith_bounds) ? 4u : 0u) | (even ? 8u : 0u));
@@ -69,7 +71,19 @@ static hipError_t launch_slide_rpt(const spal_csr *a, const void *x, void *y, hi
     }
 }
 
+// the row-record form (csr_rowrec.hpp): a kernel of its own per row length, no branch in the others
+template <typename T>
+static hipError_t launch_slide_rowrec(const spal_csr *a, const void *x, void *y, hipStream_t st) {
+    switch (a->plan.rowrec) {
+        case 12: return launch_slide_inst<T, 64, 6, true, 12>(a, x, y, st);
+        case 14: return launch_slide_inst<T, 64, 7, true, 14>(a, x, y, st);
+        case 16: return launch_slide_inst<T, 64, 8, true, 16>(a, x, y, st);
+        default: return hipErrorInvalidValue;
+    }
+}
+
 hipError_t launch_slide(const spal_csr *a, const void *x, void *y, hipStream_t st) {
+    if (rowrec_runs(a)) return a->elem_size == 8 ? launch_slide_rowrec<double>(a, x, y, st) : launch_slide_rowrec<float>(a, x, y, st);
     return a->elem_size == 8 ? launch_slide_rpt<double>(a, x, y, st) : launch_slide_rpt<float>(a, x, y, st);
 }
 
@@ -262,6 +276,107 @@ int slide_plan(spal_csr *a, uint32_t rpt, const std::vector<uint4> &desc,
     // add up
     p.all_rows_uniform = (p.slide_uniform && left_over.empty() && n_split == 0 &&
                           (uint64_t)a->nrows * (uint64_t)(ulen - 1u) == a->nnz) ? 1 : 0;
+    return SPAL_OK;
+}
+
+// ---- row records (csr_rowrec.hpp) ---------------------------------------------------------------------------
+// One thread per row of the 4 * slide_steps tiles: the record of a row of the matrix out of colind (every row holds L
+// entries: row r's are colind[r * L ...]), the pad record for a row past the last.  flag[0]: a row is not ascending or
+// not encodable (it keeps the pad record; the plan drops the records).
+template <int L>
+__global__ __launch_bounds__(256) void rowrec_build(const uint32_t *__restrict__ colind, uint32_t nrows, uint32_t rows_padded,
+                                                    uint32_t R, uint32_t *__restrict__ rec, uint32_t *__restrict__ flag) {
+    constexpr int NR = rowrec_dwords(L);
+    const uint32_t r = blockIdx.x * 256u + threadIdx.x;
+    if (r >= rows_padded) return;
+    uint32_t w[kRowrecMaxDwords];
+    rowrec_pad<L>(w);
+    if (r < nrows) {
+        uint32_t cols[L];
+#pragma unroll
+        for (int k = 0; k < L; ++k) cols[k] = colind[(size_t)r * L + k];
+        if (!rowrec_encode<L>(cols, R, w)) atomicOr(&flag[0], 1u);
+    }
+    uint32_t *at = rec + (size_t)(r / 64u) * (NR * 64u) + r % 64u;
+#pragma unroll
+    for (int q = 0; q < NR; ++q) at[q * 64] = w[q];
+}
+
+// ... and every record decoded again and held against the row's col16.  flag[1]: one differs.
+template <int L>
+__global__ __launch_bounds__(256) void rowrec_verify(const uint32_t *__restrict__ rec, const uint16_t *__restrict__ col16,
+                                                     uint32_t nrows, uint32_t R, uint32_t *__restrict__ flag) {
+    constexpr int NR = rowrec_dwords(L);
+    const uint32_t r = blockIdx.x * 256u + threadIdx.x;
+    if (r >= nrows) return;
+    uint32_t w[kRowrecMaxDwords] = {0u, 0u, 0u, 0u, 0u, 0u}, pos[L];
+    const uint32_t *at = rec + (size_t)(r / 64u) * (NR * 64u) + r % 64u;
+#pragma unroll
+    for (int q = 0; q < NR; ++q) w[q] = at[q * 64];
+    rowrec_decode<L>(w, R, pos);
+    bool same = true;
+#pragma unroll
+    for (int k = 0; k < L; ++k) same = same && pos[k] == (uint32_t)col16[(size_t)r * L + k];
+    if (!same) atomicOr(&flag[1], 1u);
+}
+
+void rowrec_free(spal_csr *a) {
+    if (a->rowrec_placed) place_free(a->device, a->d_rowrec);
+    else (void)dev_free(a->d_rowrec);
+    a->d_rowrec = nullptr;
+    a->rowrec_bytes = 0;
+    a->rowrec_placed = 0;
+}
+
+// Builds the records where the plan qualifies: the sliding kernel, every row of the matrix L entries long with
+// arithmetic tile bounds, 64-row tiles, L even in [12, 16], every row encodable.  Called once col16 is encoded, on the
+// handle's stream.  An allocation of the right size is kept over a re-plan (it may be a placed piece).
+int rowrec_plan(spal_csr *a) {
+    CsrPlan &p = a->plan;
+    p.rowrec = 0;
+    p.rowrec_failed = 0;
+    const int L = p.slide_uniform - 1;
+    if (p.rowrec_user == 0 || !p.slide || !p.all_rows_uniform || !p.arith_bounds || p.rows_per_tile != 64 ||
+        p.tiles_per_wave != 4 || !rowrec_length_ok(L) || p.slide_S != L / 2 || !a->d_col16) {
+        rowrec_free(a);
+        return SPAL_OK;
+    }
+    const uint32_t R = (uint32_t)p.ring_pages * kPageCols;
+    const uint32_t rows_padded = p.slide_steps * 256u;
+    const size_t bytes = (size_t)p.slide_steps * 4u * (size_t)rowrec_dwords(L) * 64u * sizeof(uint32_t);
+    if (a->d_rowrec && a->rowrec_bytes != bytes) rowrec_free(a);
+    if (!a->d_rowrec) {
+        if (dev_alloc((void **)&a->d_rowrec, bytes) != hipSuccess) {   // no room: col16 serves
+            (void)hipGetLastError();
+            a->d_rowrec = nullptr;
+            return SPAL_OK;
+        }
+        a->rowrec_bytes = bytes;
+    }
+    DevBuf d_flag;
+    SPAL_HIP_TRY(d_flag.alloc(2 * sizeof(uint32_t)));
+    SPAL_HIP_TRY(hipMemsetAsync(d_flag.p, 0, 2 * sizeof(uint32_t), a->stream));
+    const dim3 gb((rows_padded + 255u) / 256u), gv((uint32_t)((a->nrows + 255) / 256));
+    auto run = [&](auto len) {
+        constexpr int LL = decltype(len)::value;
+        hipLaunchKernelGGL(rowrec_build<LL>, gb, dim3(256), 0, a->stream, a->d_colind, (uint32_t)a->nrows, rows_padded, R,
+                           a->d_rowrec, d_flag.as<uint32_t>());
+        hipLaunchKernelGGL(rowrec_verify<LL>, gv, dim3(256), 0, a->stream, a->d_rowrec, a->d_col16, (uint32_t)a->nrows, R,
+                           d_flag.as<uint32_t>());
+    };
+    if (L == 12) run(std::integral_constant<int, 12>{});
+    else if (L == 14) run(std::integral_constant<int, 14>{});
+    else run(std::integral_constant<int, 16>{});
+    SPAL_HIP_TRY(hipGetLastError());
+    uint32_t flag[2] = {0u, 0u};
+    SPAL_HIP_TRY(hipMemcpyAsync(flag, d_flag.p, sizeof(flag), hipMemcpyDeviceToHost, a->stream));
+    SPAL_HIP_TRY(hipStreamSynchronize(a->stream));
+    if (flag[0] || flag[1]) {
+        rowrec_free(a);
+        p.rowrec_failed = (!flag[0] && flag[1]) ? 1 : 0;
+        return SPAL_OK;
+    }
+    p.rowrec = L;
     return SPAL_OK;
 }
 

@@ -9,7 +9,8 @@ namespace spal {
 // work: it synchronises `stream`.
 //  1. form: one super-tile per workgroup, or the walking form -- the sliding-window kernel when the plan has
 //     it (bands), else the persistent form -- each with plain or non-temporal y stores;
-//  2. placement of the 16-bit columns relative to the values (two streams out of one class of region of the device's
+//  1b. where the plan built row records (csr_rowrec.hpp) and the sliding kernel was kept: records against col16;
+//  2. placement of the column array the kept form streams (the records, or the 16-bit columns) relative to the values (two streams out of one class of region of the device's
 //     memory disturb each other): the columns are tried in up to `place_tries` blocks of 1 GiB taken one
 //     after the other from the device's memory; the fastest place is kept.
 template <typename T>
@@ -90,6 +91,18 @@ static int csr_autotune(spal_csr_t a, const T *x_dev, T *y_dev, void *stream, in
     else p.persistent = best & 1;
     p.user_persistent = true;   // measured: a later re-plan keeps it
     p.nt_store = (best >> 1) & 1;
+    // ---- 1b. row records (csr_rowrec.hpp) against col16 on the kept form: 5 % fewer bytes per f64 row of 14 entries for a
+    // decode per lane; kept where that wins by 1 % (the results are bit-identical)
+    a->rowrec_us[0] = a->rowrec_us[1] = 0.f;
+    if (rc == SPAL_OK && walking_is_slide && p.slide_on && p.rowrec && a->d_rowrec) {
+        float ms[2] = {0.f, 0.f};
+        for (int round = 0; round < 2 && rc == SPAL_OK; ++round)
+            for (int on = 0; on < 2 && rc == SPAL_OK; ++on) { p.rowrec_on = on; timed(iters, &ms[on]); }
+        if (rc == SPAL_OK) {
+            a->rowrec_us[0] = ms[0] * 1e3f; a->rowrec_us[1] = ms[1] * 1e3f;
+            p.rowrec_on = ms[1] <= 0.99f * ms[0] ? 1 : 0;
+        }
+    }
     // ---- 2. where the 16-bit columns lie relative to the values (two streams out of one class of region
     // disturb each other, +12 us at config 3; out of two classes they do not): the columns are copied into blocks of
     // 1 GiB taken one after the other from the device's memory, the kernel is timed on each, the fastest place is kept
@@ -99,13 +112,17 @@ static int csr_autotune(spal_csr_t a, const T *x_dev, T *y_dev, void *stream, in
     // two, no hipMalloc here), the columns become a PIECE of the one that wins by 1 % and more.
     int tries = p.place_tries;
     if (const char *e = getenv("SPAL_PLACE_TRIES")) tries = atoi(e);
-    const size_t cbytes = a->d_col16 ? (size_t)a->cap_entries * sizeof(uint16_t) : 0;
-    if (rc == SPAL_OK && tries > 0 && cbytes >= ((size_t)64 << 20) && !a->col16_placed) {
+    // (the column array the kept form streams: the row records, or col16)
+    const bool recs = rowrec_runs(a) && walking_is_slide && p.slide_on;
+    void **const slot = recs ? (void **)&a->d_rowrec : (void **)&a->d_col16;
+    int *const placed = recs ? &a->rowrec_placed : &a->col16_placed;
+    const size_t cbytes = recs ? a->rowrec_bytes : a->d_col16 ? (size_t)a->cap_entries * sizeof(uint16_t) : 0;
+    if (rc == SPAL_OK && tries > 0 && cbytes >= ((size_t)64 << 20) && !*placed) {
         const int n = std::max(4, iters / 4);
         float cur_ms = 0.f;
         timed(n, &cur_ms);
         a->place_us[0] = cur_ms * 1e3f;
-        uint16_t *const original = a->d_col16;
+        void *const original = *slot;
         std::vector<void *> cand;
         std::vector<float> ms_of;
         const int kept = place_block_count(a->device);
@@ -114,7 +131,7 @@ static int csr_autotune(spal_csr_t a, const T *x_dev, T *y_dev, void *stream, in
             if (!b) continue;
             hipError_t e = hipMemcpyAsync(b, original, cbytes, hipMemcpyDeviceToDevice, st);
             if (e != hipSuccess) { place_free(a->device, b); rc = fail(SPAL_ERR_HIP, "spal_csr_autotune: %s", hipGetErrorString(e)); break; }
-            a->d_col16 = (uint16_t *)b;
+            *slot = b;
             float ms = 0.f;
             timed(n, &ms);
             cand.push_back(b); ms_of.push_back(ms);
@@ -124,10 +141,10 @@ static int csr_autotune(spal_csr_t a, const T *x_dev, T *y_dev, void *stream, in
         for (size_t k = 0; k < ms_of.size(); ++k)
             if (ms_of[k] < 0.99f * cur_ms && (best < 0 || ms_of[k] < ms_of[(size_t)best])) best = (int)k;
         (void)hipStreamSynchronize(st);
-        a->d_col16 = best >= 0 ? (uint16_t *)cand[(size_t)best] : original;
+        *slot = best >= 0 ? cand[(size_t)best] : original;
         for (size_t k = 0; k < cand.size(); ++k)
             if ((int)k != best) place_free(a->device, cand[k]);
-        if (best >= 0) { (void)dev_free(original); a->col16_placed = 1; }
+        if (best >= 0) { (void)dev_free(original); *placed = 1; }
         a->place_us[1] = (best >= 0 ? ms_of[(size_t)best] : cur_ms) * 1e3f;
     }
     return rc;

@@ -250,6 +250,11 @@ struct CsrPlan {
     int slide_fill_ok = 1;   // the sliding kernel's tiles are full enough for its fixed count of loads per tile (csr_slide plan)
     int slide_fill_user = -1; // -1 = by the tiles' average fill, 1 = "slide_on" was asked for by name
     int slide_even = 1;      // option "slide_even": one run per workgroup -> the XCD's steps split evenly over all its workgroups
+    // row records (csr_rowrec.hpp): the sliding kernel streams one Elias-Fano record per row instead of the row's col16
+    int rowrec_user = -1;    // option "rowrec": -1 auto (where the plan qualifies), 0 never, 1 as -1
+    int rowrec_on = 1;       // option "rowrec_on": launch the record form (0: the same plan streams col16 -- A/B, autotune)
+    int rowrec = 0;          // the records are built and verified against col16; = the rows' length (12, 14 or 16)
+    int rowrec_failed = 0;   // a built record did not decode to its row's col16 (cannot be): the records were dropped
     int blockwin = -1;       // option "blockwin": -1 = timed against the row split where that is built, 0 never, 1 whenever the windows fit (tests)
     int row_split = -1;      // option "row_split": -1 = when long rows keep a tenth of the 64-row tiles from streaming, 0 never, 1 always (tests)
     int split_threshold = 128;   // option "row_split_threshold": rows above it are "long"
@@ -390,6 +395,10 @@ struct spal_csr {
     int walk_probes = 0;               // places timed (new blocks + the process's retained ones)
     int walk_max = 8;                  // option "walk_blocks": blocks of 1 GiB a walk may hold at once = how far it reaches
     int col16_placed = 0;              // d_col16 is a piece of a placement block (place_free, not dev_free)
+    uint32_t *d_rowrec = nullptr;      // row records (csr_rowrec.hpp): [4 * slide_steps tiles][NR][64] dwords; col16 stays beside them
+    size_t rowrec_bytes = 0;
+    int rowrec_placed = 0;             // d_rowrec is a piece of a placement block
+    float rowrec_us[2] = {0.f, 0.f};   // autotune: per launch {col16, row records} on the kept form
     std::mutex mu_cb;
     // autotune: microseconds per launch of {plain, persistent} x {plain, non-temporal y stores}
     float tuned_us[4] = {0.f, 0.f, 0.f, 0.f};
@@ -542,6 +551,10 @@ void trsv_sweep_free(spal_csr *a);
 hipError_t launch_slide(const spal_csr *a, const void *x, void *y, hipStream_t st);
 // ... its plan (for csr_plan_build): decides whether it can run the chosen stream plan and builds its step descriptors
 int slide_plan(spal_csr *a, uint32_t rpt, const std::vector<uint4> &desc, const std::vector<uint32_t> &skip, uint32_t super_pages);
+// ... the row records of a plan that qualifies (after col16 is encoded: they are verified against it), and their release
+int rowrec_plan(spal_csr *a);
+void rowrec_free(spal_csr *a);
+inline bool rowrec_runs(const spal_csr *a) { return a->plan.rowrec && a->plan.rowrec_on && a->d_rowrec; }
 // ... and the column-panel kernel over a->d_ptiles
 hipError_t launch_panel(const spal_csr *a, const void *x, void *y, hipStream_t st);
 // The CSC scatter route over column tiles.  Implemented in spal_csc_plan.hip: windows, modes, hand-off eligibility, then
