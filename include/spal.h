@@ -147,6 +147,11 @@ int spal_csr_download_f32(spal_csr_t a, uint64_t *rowptr, uint64_t *colind,
  * launch it), "rowrec" (-1 auto / 0 / 1: rows of one even length in [12, 16]
  * under the sliding kernel stream one 20- or 24-byte record per row instead of
  * the row's 16-bit columns), "rowrec_on" (0 / 1: launch that form),
+ * "valpack" (-1 auto / 0 / 1: an f64 handle with row records whose values are
+ * all k * 2^e for one e, k inside 53 bits for rows of 12 and 54 bits for rows of
+ * 14 or 16 entries, no NaN, Inf or -0.0, streams one fixed-point block of 80 /
+ * 96 / 112 bytes per row instead of the row's values; the values stay resident
+ * beside the blocks), "valpack_on" (0 / 1: launch that form),
  * "uniform_rows" (0 / 1: super-tiles whose rows all have one length
  * do not read rowptr), "prefetch" (1 / 2 tiles of loads ahead), "place_tries"
  * (autotune), "split_tiles" (1 default / 0: the sliding kernel computes tiles
@@ -204,7 +209,13 @@ int spal_csr_alloc_vectors(spal_csr_t a, void **x_dev, void **y_dev, void *strea
  * "slide", "ring_pages", "uniform_row_fraction", "nt_store", "autotune_us"
  * (one workgroup per super-tile, walking form, each then with non-temporal y
  * stores), "placement_us" (before / after placing the 16-bit columns),
- * "vectors_walk_us" (fastest / slowest block of spal_csr_alloc_vectors). */
+ * "vectors_walk_us" (fastest / slowest block of spal_csr_alloc_vectors).
+ * Plans with the sliding kernel add "rowrec", "rowrec_on",
+ * "rowrec_bytes_per_row", "rowrec_max_span", "rowrec_failed", "rowrec_us" (the
+ * autotune's {16-bit columns, records} per launch), and f64 handles among them
+ * "valpack", "valpack_on", "valpack_bits" (of the widest k, sign included),
+ * "valpack_exp" (e), "valpack_bytes_per_row", "valpack_failed", "valpack_us"
+ * (the autotune's {values, packed values}), "valpack_build_ms". */
 int spal_csr_describe(spal_csr_t a, char *buf, size_t buf_len);
 
 /* ---- CSC: y = A * x (atomic scatter) --------------------------------------

@@ -24,6 +24,7 @@
 #pragma once
 #include "csr_kernels.hpp"
 #include "csr_rowrec.hpp"
+#include "csr_valpack.hpp"
 
 namespace spal {
 
@@ -84,13 +85,21 @@ __device__ __forceinline__ SlideNew slide_new_pages(uint32_t fa, uint32_t na, ui
 // One tile's loads, exactly S + S (+ 2) of them whatever the tile holds.  REC != 0 (the row-record form, csr_rowrec.hpp:
 // every row of the matrix holds REC entries, 64 rows per tile, S = REC / 2): `col16` is the record array and the tile
 // issues rowrec_dwords(REC) record loads -- first, the decode starts on them -- and its S value loads.
-template <typename T, int RPT, int S, bool UNI, int REC = 0>
+// VPK != 0 (the packed-value form of the record form, csr_valpack.hpp: f64, VPK = REC, S = REC / 2 - 1): `vals` is the
+// array of row blocks and the tile issues the record loads and its S block loads of 16 bytes; a lane then holds its
+// whole row and needs no bounds.
+template <typename T, int RPT, int S, bool UNI, int REC = 0, int VPK = 0>
 __device__ __forceinline__ void slide_tile_load(StreamTile<T> &t, const uint32_t *__restrict__ rowptr,
                                                 const uint16_t *__restrict__ col16, const T *__restrict__ vals,
                                                 uint32_t row0, uint32_t nrows, uint32_t b, uint32_t e, uint32_t lane,
                                                 uint32_t ulen) {
     using pair_t = typename Pair<T>::type;
     static_assert(RPT <= 64, "a row per lane");
+    if constexpr (VPK != 0) {
+        rowrec_tile_load<T, REC>(t, reinterpret_cast<const uint32_t *>(col16), row0 / 64u, lane);
+        valpack_tile_load<VPK>(t, reinterpret_cast<const valpack_chunk_t *>(vals), row0 / 64u, lane);
+        return;
+    }
     const uint32_t rlast = min(row0 + (uint32_t)RPT, nrows);
     t.start = b & ~1u;
     t.steps = (e - t.start + 127u) >> 7;          // <= S by the plan
@@ -113,14 +122,20 @@ __device__ __forceinline__ void slide_tile_load(StreamTile<T> &t, const uint32_t
     }
 }
 
-template <typename T, int RPT, int S, bool UNI, int PF, int REC = 0>
-__global__ __launch_bounds__(kStreamBlock, 2) void csr_spmv_slide(
+// The walk every form of the sliding kernel shares: the runs of steps, the ring window, the tiles in flight.  The
+// __global__ functions below are its forms: csr_spmv_slide (col16, or row records with REC != 0) and
+// csr_spmv_slide_valpack (row records and packed values, VPK = REC: `vals` is the array of row blocks, `vscale` the
+// quantum 2^e).
+template <typename T, int RPT, int S, bool UNI, int PF, int REC, int VPK>
+__device__ __forceinline__ void slide_walk(
     const uint32_t *__restrict__ rowptr, const uint16_t *__restrict__ col16, const T *__restrict__ vals,
     const T *__restrict__ x, T *__restrict__ y, const uint2 *__restrict__ sdesc, uint32_t nrows, uint32_t ncols,
-    uint32_t nsteps, uint32_t per_xcd, uint32_t chunk, uint32_t NP, uint32_t ulen, uint32_t flags) {
+    uint32_t nsteps, uint32_t per_xcd, uint32_t chunk, uint32_t NP, uint32_t ulen, uint32_t flags, double vscale) {
     static_assert(PF == 1 || PF == 2, "one or two tiles of loads ahead");
     static_assert(S >= 1 && S <= kStreamSteps, "a tile holds at most kStreamSteps steps");
-    static_assert(REC == 0 || (UNI && RPT == 64 && rowrec_length_ok(REC) && S == REC / 2), "row records: uniform rows, a row per lane");
+    static_assert(REC == 0 || (UNI && RPT == 64 && rowrec_length_ok(REC) && S == (VPK ? valpack_chunks(REC) : REC / 2)),
+                  "row records: uniform rows, a row per lane");
+    static_assert(VPK == 0 || (VPK == REC && sizeof(T) == 8 && valpack_length_ok(VPK)), "packed values: f64 rows with records");
     using vec_t = typename SlideVec<T>::type;
     extern __shared__ __attribute__((aligned(16))) unsigned char spal_smem[];
     constexpr uint32_t V = 16 / sizeof(T), VP = kPageCols / V;
@@ -186,7 +201,7 @@ __global__ __launch_bounds__(kStreamBlock, 2) void csr_spmv_slide(
     uint2 dn = sdesc[gi(1u)];
 #pragma unroll
     for (int q = 0; q < PF; ++q)
-        slide_tile_load<T, RPT, S, UNI, REC>(t[q], rowptr, col16, vals, tile_row((uint32_t)q), nrows, tb[q], te[q], lane, ulen);
+        slide_tile_load<T, RPT, S, UNI, REC, VPK>(t[q], rowptr, col16, vals, tile_row((uint32_t)q), nrows, tb[q], te[q], lane, ulen);
     // the first window, whole: kSlideFirstBatch vectors per thread requested back to back (12: the 24 pages of an f64 window
     // in ONE round trip; four at a time made it three, and a shard-sized launch is only 7.6 steps per workgroup long)
     {
@@ -229,7 +244,7 @@ __global__ __launch_bounds__(kStreamBlock, 2) void csr_spmv_slide(
             nv[k] = slide_load_vec<T>(x, mine ? new_page(j) : 0u, mine ? j % VP : 0u, last_vec);
         }
         // the tile PF steps ahead
-        slide_tile_load<T, RPT, S, UNI, REC>(t[KN], rowptr, col16, vals, tile_row(i + PF), nrows, tb[KN], te[KN], lane, ulen);
+        slide_tile_load<T, RPT, S, UNI, REC, VPK>(t[KN], rowptr, col16, vals, tile_row(i + PF), nrows, tb[KN], te[KN], lane, ulen);
         // ... and the entry range of the one after it (slot K is free: step i's loads went out PF steps ago)
         tb[K] = tile_b(i + PF + 1u);
         te[K] = tile_e(i + PF + 1u);
@@ -244,8 +259,12 @@ __global__ __launch_bounds__(kStreamBlock, 2) void csr_spmv_slide(
         } else
 #endif
         if (r0 < nrows && !((skip >> wave) & 1u)) {
-            if constexpr (REC != 0) rowrec_expand<T, REC>(t[K], reinterpret_cast<uint32_t *>(prod), NP * kPageCols, lane);
-            stream_compute<T, RPT, false>(t[K], xw, wmax, prod, y, r0, nrows, lane, nt_store, flags);
+            if constexpr (VPK != 0) {
+                valpack_row_compute<VPK>(t[K], xw, wmax, NP * kPageCols, vscale, y, r0, nrows, lane, nt_store);
+            } else {
+                if constexpr (REC != 0) rowrec_expand<T, REC>(t[K], reinterpret_cast<uint32_t *>(prod), NP * kPageCols, lane);
+                stream_compute<T, RPT, false>(t[K], xw, wmax, prod, y, r0, nrows, lane, nt_store, flags);
+            }
         } else if (REC == 0 && r0 < nrows && ((d.y >> (20u + wave)) & 1u)) {   // (a record plan has no such tile)
             // More than the strip's 1024 entries, but each half of the rows fits (the plan checked): two passes
             // through the strip, rows [r0, rm) then [rm, re) -- same loads, products and left-to-right sums as any
@@ -295,6 +314,27 @@ __global__ __launch_bounds__(kStreamBlock, 2) void csr_spmv_slide(
         if constexpr (NB > 2)
             if (i + 2u < nk) step(i + 2u, std::integral_constant<int, 2>{});
     }
+}
+
+template <typename T, int RPT, int S, bool UNI, int PF, int REC = 0>
+__global__ __launch_bounds__(kStreamBlock, 2) void csr_spmv_slide(
+    const uint32_t *__restrict__ rowptr, const uint16_t *__restrict__ col16, const T *__restrict__ vals,
+    const T *__restrict__ x, T *__restrict__ y, const uint2 *__restrict__ sdesc, uint32_t nrows, uint32_t ncols,
+    uint32_t nsteps, uint32_t per_xcd, uint32_t chunk, uint32_t NP, uint32_t ulen, uint32_t flags) {
+    slide_walk<T, RPT, S, UNI, PF, REC, 0>(rowptr, col16, vals, x, y, sdesc, nrows, ncols, nsteps, per_xcd, chunk, NP, ulen,
+                                           flags, 0.0);
+}
+
+// The packed-value form (csr_valpack.hpp): every row of the matrix holds L f64 entries; `rec` are the row records,
+// `blocks` the row blocks of fixed-point values with quantum `vscale`.  A kernel of its own, no branch in the others.
+template <int L, int PF>
+__global__ __launch_bounds__(kStreamBlock, 2) void csr_spmv_slide_valpack(
+    const uint32_t *__restrict__ rec, const valpack_chunk_t *__restrict__ blocks, double vscale,
+    const double *__restrict__ x, double *__restrict__ y, const uint2 *__restrict__ sdesc, uint32_t nrows, uint32_t ncols,
+    uint32_t nsteps, uint32_t per_xcd, uint32_t chunk, uint32_t NP, uint32_t flags) {
+    slide_walk<double, 64, valpack_chunks(L), true, PF, L, L>(nullptr, reinterpret_cast<const uint16_t *>(rec),
+                                                              reinterpret_cast<const double *>(blocks), x, y, sdesc, nrows,
+                                                              ncols, nsteps, per_xcd, chunk, NP, (uint32_t)L + 1u, flags, vscale);
 }
 
 }  // namespace spal

@@ -299,6 +299,7 @@ void csr_free(spal_csr *a) {
     if (a->col16_placed) place_free(a->device, a->d_col16);
     else (void)dev_free(a->d_col16);
     rowrec_free(a);
+    valpack_free(a);
     (void)dev_free(a->d_pages);
     (void)dev_free(a->d_ovtiles);
     (void)dev_free(a->d_sdesc);
@@ -646,6 +647,11 @@ static const PlanIntOption kPlanIntOptions[] = {
     // but streams col16 on the same plan (A/B, as "slide_on")
     {"rowrec", &CsrPlan::rowrec_user, -1, 1, nullptr, "rowrec must be -1 (auto), 0 or 1"},
     {"rowrec_on", &CsrPlan::rowrec_on, 0, 1, nullptr, "rowrec_on must be 0 or 1"},
+    // record form, f64 values that are all multiples of one power of two: one fixed-point block per row instead of its values
+    // (csr_valpack.hpp): -1 = where the plan qualifies (default), 0 = never, 1 = as -1; "valpack_on" 0 keeps the blocks but
+    // streams the values on the same plan (A/B, as "rowrec_on")
+    {"valpack", &CsrPlan::valpack_user, -1, 1, nullptr, "valpack must be -1 (auto), 0 or 1"},
+    {"valpack_on", &CsrPlan::valpack_on, 0, 1, nullptr, "valpack_on must be 0 or 1"},
     // autotune: blocks of 1 GiB the 16-bit columns are tried in (0 = leave them where they are)
     {"place_tries", &CsrPlan::place_tries, 0, 16, nullptr, "place_tries must be in [0, 16]"},
     // stream kernel: super-tiles whose rows all have one length do not read rowptr (default 1)
@@ -885,6 +891,22 @@ static int csr_describe_plan(spal_csr_t a, char *buf, size_t buf_len) {
         char us[64];
         snprintf(us, sizeof(us), "[%.1f, %.1f]", (double)a->rowrec_us[0], (double)a->rowrec_us[1]);
         SPAL_TRY(describe_append(buf, buf_len, "rowrec_us", us));
+        // packed values (csr_valpack.hpp), f64 handles only: built, launched, the bits of the widest k and the quantum's
+        // exponent, the block's size, the autotune's {values, packed} per launch, what the scan, builder and verify pass took
+        if (a->elem_size == 8) {
+            const bool vp = rr && p.valpack && a->d_valpack;
+            SPAL_TRY(describe_append(buf, buf_len, "valpack", vp ? "1" : "0"));
+            SPAL_TRY(describe_append(buf, buf_len, "valpack_on",
+                                     (vp && p.valpack_on && p.rowrec_on && p.slide_on && p.slide_fill_ok) ? "1" : "0"));
+            SPAL_TRY(describe_append(buf, buf_len, "valpack_bits", std::to_string(vp ? p.valpack_bits : 0)));
+            SPAL_TRY(describe_append(buf, buf_len, "valpack_exp", std::to_string(vp ? p.valpack_exp : 0)));
+            SPAL_TRY(describe_append(buf, buf_len, "valpack_bytes_per_row", std::to_string(vp ? 4 * valpack_dwords(p.valpack) : 0)));
+            SPAL_TRY(describe_append(buf, buf_len, "valpack_failed", std::to_string(p.valpack_failed)));
+            snprintf(us, sizeof(us), "[%.1f, %.1f]", (double)a->valpack_us[0], (double)a->valpack_us[1]);
+            SPAL_TRY(describe_append(buf, buf_len, "valpack_us", us));
+            snprintf(us, sizeof(us), "%.3f", (double)a->valpack_build_ms);
+            SPAL_TRY(describe_append(buf, buf_len, "valpack_build_ms", us));
+        }
     }
     return SPAL_OK;
 }

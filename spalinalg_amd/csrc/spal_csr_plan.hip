@@ -537,6 +537,7 @@ int csr_plan_build(spal_csr *a) {
     p.vec_col16 = 0;
     p.slide = 0;
     p.rowrec = 0;
+    p.valpack = 0;
     p.ring_pages = 0;
     if (a->nnz == 0) {
         cblock_free(a);
@@ -670,6 +671,8 @@ int csr_plan_build(spal_csr *a) {
             }
             // uniform short rows under the sliding kernel: one record per row instead of its col16 (csr_rowrec.hpp)
             SPAL_TRY(rowrec_plan(a));
+            // ... and f64 values that share a quantum: one fixed-point block per row instead of its values (csr_valpack.hpp)
+            SPAL_TRY(valpack_plan(a));
             if (best_over) {   // the tiles the stream kernels skip: listed for csr_spmv_overflow
                 uint32_t *d_list = nullptr;   // [count][first rows]
                 const uint32_t pieces = (uint32_t)std::max(1, best_rpt / 64) * best_over;   // (at most)
@@ -712,6 +715,7 @@ int csr_plan_build(spal_csr *a) {
     }
     cblock_free(a);
     rowrec_free(a);
+    valpack_free(a);
 
     // ---- vector kernel
     p.kernel = 1;

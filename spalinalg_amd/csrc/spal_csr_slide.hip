@@ -1,27 +1,41 @@
 // spal_csr_slide.hip -- instantiations, launch and plan of the sliding-window CSR kernel (csr_slide.hpp); a
 // translation unit of its own so that the build compiles it beside spal_csr.hip.
+#include <chrono>
+
 #include "csr_panel.hpp"
 #include "csr_slide.hpp"
 #include "spal_internal.hpp"
 
 namespace spal {
 
+// LDS, grid and runs of a launch of the sliding kernel, whatever its form
+struct SlideGrid { size_t lds; uint32_t per_xcd, chunk, used; bool even; };
+static SlideGrid slide_grid(const spal_csr *a, size_t elem) {
+    const CsrPlan &p = a->plan;
+    SlideGrid g;
+    g.lds = ((size_t)kStreamWaves * stream_strip<false>() + (size_t)p.ring_pages * kPageCols) * elem;
+    // as many workgroups as the device holds at once (160 KB of LDS per CU decide), each a contiguous chunk of
+    // its XCD's run of steps
+    const int per_cu = (int)std::min<size_t>(8, std::max<size_t>(1, (160 * 1024) / (g.lds + 512)));
+    const uint32_t grid = p.persistent_blocks > 0 ? (uint32_t)p.persistent_blocks : 256u * (uint32_t)per_cu;
+    g.per_xcd = (p.slide_steps + 7u) / 8u;
+    const uint32_t slots = std::max(1u, grid / 8u);
+    // steps per run: one run per workgroup, or what the plan says ("slide_run": shorter runs dealt round-robin)
+    const uint32_t one_run = (g.per_xcd + slots - 1u) / slots;
+    g.chunk = p.slide_run > 0 ? std::min<uint32_t>((uint32_t)p.slide_run, one_run) : one_run;
+    g.even = p.slide_run <= 0 && p.slide_even;        // one run per workgroup: the steps split evenly (csr_slide.hpp)
+    g.used = g.even ? std::min(slots, g.per_xcd) : std::min(slots, (g.per_xcd + g.chunk - 1u) / g.chunk);
+    return g;
+}
+
 template <typename T, int RPT, int S, bool UNI, int REC = 0>
 static hipError_t launch_slide_inst(const spal_csr *a, const void *x, void *y, hipStream_t st) {
     constexpr int PF = 2;
     const CsrPlan &p = a->plan;
-    const size_t lds = ((size_t)kStreamWaves * stream_strip<false>() + (size_t)p.ring_pages * kPageCols) * sizeof(T);
-    // as many workgroups as the device holds at once (160 KB of LDS per CU decide), each a contiguous chunk of
-    // its XCD's run of steps
-    const int per_cu = (int)std::min<size_t>(8, std::max<size_t>(1, (160 * 1024) / (lds + 512)));
-    const uint32_t grid = p.persistent_blocks > 0 ? (uint32_t)p.persistent_blocks : 256u * (uint32_t)per_cu;
-    const uint32_t per_xcd = (p.slide_steps + 7u) / 8u;
-    const uint32_t slots = std::max(1u, grid / 8u);
-    // steps per run: one run per workgroup, or what the plan says ("slide_run": shorter runs dealt round-robin)
-    const uint32_t one_run = (per_xcd + slots - 1u) / slots;
-    const uint32_t chunk = p.slide_run > 0 ? std::min<uint32_t>((uint32_t)p.slide_run, one_run) : one_run;
-    const bool even = p.slide_run <= 0 && p.slide_even;        // one run per workgroup: the steps split evenly (csr_slide.hpp)
-    const uint32_t used = even ? std::min(slots, per_xcd) : std::min(slots, (per_xcd + chunk - 1u) / chunk);
+    const SlideGrid g = slide_grid(a, sizeof(T));
+    const size_t lds = g.lds;
+    const uint32_t per_xcd = g.per_xcd, chunk = g.chunk, used = g.used;
+    const bool even = g.even;
     auto kern = csr_spmv_slide<T, RPT, S, UNI, PF, REC>;
     // (the record form streams the records where the others stream col16)
     const uint16_t *cols = REC != 0 ? reinterpret_cast<const uint16_t *>(a->d_rowrec) : a->d_col16;
@@ -82,7 +96,39 @@ static hipError_t launch_slide_rowrec(const spal_csr *a, const void *x, void *y,
     }
 }
 
+// the packed-value form (csr_valpack.hpp): the record form's grid and runs, the row blocks in place of the values
+template <int L>
+static hipError_t launch_slide_valpack_inst(const spal_csr *a, const void *x, void *y, hipStream_t st) {
+    constexpr int PF = 2;
+    const CsrPlan &p = a->plan;
+    const SlideGrid g = slide_grid(a, sizeof(double));
+    auto kern = csr_spmv_slide_valpack<L, PF>;
+    static std::atomic<uint64_t> configured{0};
+    const uint64_t bit = 1ull << (a->device & 63);
+    if (g.lds > 48 * 1024 && !(configured.load(std::memory_order_relaxed) & bit)) {
+        hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        if (e != hipSuccess) return e;
+        configured.fetch_or(bit, std::memory_order_relaxed);
+    }
+    // (flag 4: the tiles' bounds are arithmetic -- the plan packs under no other -- and rowptr is not passed)
+    hipLaunchKernelGGL(kern, dim3(g.used * 8u), dim3(kStreamBlock), g.lds, st, (const uint32_t *)a->d_rowrec,
+                       (const valpack_chunk_t *)a->d_valpack, valpack_scale(p.valpack_exp), (const double *)x, (double *)y,
+                       a->d_sdesc, (uint32_t)a->nrows, (uint32_t)a->ncols, p.slide_steps, g.per_xcd, g.chunk,
+                       (uint32_t)p.ring_pages, (uint32_t)(p.nt_store ? 1 : 0) | (uint32_t)p.diag | 4u | (g.even ? 8u : 0u));
+    return hipGetLastError();
+}
+
+static hipError_t launch_slide_valpack(const spal_csr *a, const void *x, void *y, hipStream_t st) {
+    switch (a->plan.valpack) {
+        case 12: return launch_slide_valpack_inst<12>(a, x, y, st);
+        case 14: return launch_slide_valpack_inst<14>(a, x, y, st);
+        case 16: return launch_slide_valpack_inst<16>(a, x, y, st);
+        default: return hipErrorInvalidValue;
+    }
+}
+
 hipError_t launch_slide(const spal_csr *a, const void *x, void *y, hipStream_t st) {
+    if (valpack_runs(a)) return launch_slide_valpack(a, x, y, st);
     if (rowrec_runs(a)) return a->elem_size == 8 ? launch_slide_rowrec<double>(a, x, y, st) : launch_slide_rowrec<float>(a, x, y, st);
     return a->elem_size == 8 ? launch_slide_rpt<double>(a, x, y, st) : launch_slide_rpt<float>(a, x, y, st);
 }
@@ -318,6 +364,175 @@ __global__ __launch_bounds__(256) void rowrec_verify(const uint32_t *__restrict_
 #pragma unroll
     for (int k = 0; k < L; ++k) same = same && pos[k] == (uint32_t)col16[(size_t)r * L + k];
     if (!same) atomicOr(&flag[1], 1u);
+}
+
+// ---- packed values (csr_valpack.hpp) ------------------------------------------------------------------------
+// One pass over the stored values: out[0] = the smallest exponent of a lowest set mantissa bit over the non-zero
+// values, biased by 2048 (0xffffffff: there is none), out[1] = a value is NaN, Inf or -0.0, out[2 ... 3] = the largest
+// |value| as its bit pattern.
+__global__ __launch_bounds__(256) void valpack_scan(const double *__restrict__ vals, uint64_t n, uint32_t *__restrict__ out) {
+    uint32_t emin = 0xffffffffu, bad = 0u;
+    uint64_t amax = 0ull;
+    for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256u) {
+        const uint64_t bits = valpack_bits_of(vals[i]);
+        if (bits == 0ull) continue;
+        uint64_t mant = 0;
+        int ex = 0;
+        if (!valpack_split(bits, &mant, &ex)) { bad = 1u; continue; }
+        emin = min(emin, (uint32_t)(ex + __builtin_ctzll(mant) + 2048));
+        const uint64_t mag = bits & ~(1ull << 63);
+        amax = mag > amax ? mag : amax;
+    }
+    for (int o = 32; o > 0; o >>= 1) {   // (64-bit patterns travel and compare as integers, in two halves)
+        emin = min(emin, (uint32_t)__shfl_xor((int)emin, o));
+        bad |= (uint32_t)__shfl_xor((int)bad, o);
+        const uint64_t other = (uint64_t)(uint32_t)__shfl_xor((int)(uint32_t)amax, o) |
+                               ((uint64_t)(uint32_t)__shfl_xor((int)(uint32_t)(amax >> 32), o) << 32);
+        amax = other > amax ? other : amax;
+    }
+    if ((threadIdx.x & 63u) == 0u) {
+        if (emin != 0xffffffffu) atomicMin(&out[0], emin);
+        if (bad) atomicOr(&out[1], 1u);
+        if (amax) atomicMax(reinterpret_cast<unsigned long long *>(out + 2), (unsigned long long)amax);
+    }
+}
+
+// One thread per row of the 4 * slide_steps tiles: the block of a row of the matrix out of its L values, a block of
+// zeros for a row past the last.  flag[0]: a value is not encodable (the plan drops the array).
+template <int L>
+__global__ __launch_bounds__(256) void valpack_build(const double *__restrict__ vals, uint32_t nrows, uint32_t rows_padded,
+                                                     int e, valpack_chunk_t *__restrict__ blocks, uint32_t *__restrict__ flag) {
+    constexpr int NQ = valpack_chunks(L);
+    const uint32_t r = blockIdx.x * 256u + threadIdx.x;
+    if (r >= rows_padded) return;
+    uint32_t w[4 * NQ];
+#pragma unroll
+    for (int q = 0; q < 4 * NQ; ++q) w[q] = 0u;
+    if (r < nrows) {
+        double v[L];
+#pragma unroll
+        for (int k = 0; k < L; ++k) v[k] = vals[(size_t)r * L + k];
+        if (!valpack_encode<L>(v, e, w)) atomicOr(&flag[0], 1u);
+    }
+    valpack_chunk_t *at = blocks + (size_t)(r / 64u) * (NQ * 64u) + r % 64u;
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+        valpack_chunk_t c = {w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3]};
+        at[q * 64] = c;
+    }
+}
+
+// ... and every block decoded again and held against the row's values, bit for bit.  flag[1]: one differs.
+template <int L>
+__global__ __launch_bounds__(256) void valpack_verify(const valpack_chunk_t *__restrict__ blocks, const double *__restrict__ vals,
+                                                      uint32_t nrows, double scale, uint32_t *__restrict__ flag) {
+    constexpr int NQ = valpack_chunks(L);
+    const uint32_t r = blockIdx.x * 256u + threadIdx.x;
+    if (r >= nrows) return;
+    uint32_t w[4 * NQ];
+    double v[L];
+    const valpack_chunk_t *at = blocks + (size_t)(r / 64u) * (NQ * 64u) + r % 64u;
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+        const valpack_chunk_t c = at[q * 64];
+        w[4 * q] = c.x; w[4 * q + 1] = c.y; w[4 * q + 2] = c.z; w[4 * q + 3] = c.w;
+    }
+    valpack_decode<L>(w, scale, v);
+    bool same = true;
+#pragma unroll
+    for (int k = 0; k < L; ++k) same = same && valpack_bits_of(v[k]) == valpack_bits_of(vals[(size_t)r * L + k]);
+    if (!same) atomicOr(&flag[1], 1u);
+}
+
+void valpack_free(spal_csr *a) {
+    (void)dev_free(a->d_valpack);
+    a->d_valpack = nullptr;
+    a->valpack_bytes = 0;
+}
+
+// Builds the row blocks where the plan has row records, the handle holds f64 and every value is k * 2^e with k inside
+// the width for the rows' length.  Called after rowrec_plan, on the handle's stream.  The plain values stay resident:
+// every other kernel, the download and the sparse operations read them.  An allocation of the right size is kept over
+// a re-plan.
+int valpack_plan(spal_csr *a) {
+    CsrPlan &p = a->plan;
+    p.valpack = 0;
+    p.valpack_failed = 0;
+    p.valpack_bits = 0;
+    p.valpack_exp = 0;
+    a->valpack_build_ms = 0.f;
+    const int L = p.rowrec;
+    if (p.valpack_user == 0 || a->elem_size != 8 || !p.rowrec || !a->d_rowrec || !valpack_length_ok(L)) {
+        valpack_free(a);
+        return SPAL_OK;
+    }
+    const auto t0 = std::chrono::steady_clock::now();
+    // 1. the quantum and the range
+    DevBuf d_out;
+    SPAL_HIP_TRY(d_out.alloc(6 * sizeof(uint32_t)));   // scan: {emin, bad, amax lo, amax hi}; build / verify: flag[0 ... 1]
+    const uint32_t init[6] = {0xffffffffu, 0u, 0u, 0u, 0u, 0u};
+    SPAL_HIP_TRY(hipMemcpyAsync(d_out.p, init, sizeof(init), hipMemcpyHostToDevice, a->stream));
+    const uint32_t scan_blocks = (uint32_t)std::min<uint64_t>(4096, (a->nnz + 255) / 256);
+    hipLaunchKernelGGL(valpack_scan, dim3(scan_blocks), dim3(256), 0, a->stream, (const double *)a->d_values, (uint64_t)a->nnz,
+                       d_out.as<uint32_t>());
+    SPAL_HIP_TRY(hipGetLastError());
+    uint32_t out[6] = {0u, 0u, 0u, 0u, 0u, 0u};
+    SPAL_HIP_TRY(hipMemcpyAsync(out, d_out.p, sizeof(out), hipMemcpyDeviceToHost, a->stream));
+    SPAL_HIP_TRY(hipStreamSynchronize(a->stream));   // (`init` was read)
+    const int e = out[0] == 0xffffffffu ? 0 : (int)out[0] - 2048;   // (stored zeros only: any quantum)
+    const uint64_t amax = (uint64_t)out[2] | ((uint64_t)out[3] << 32);
+    int bits = 1;   // of the widest k, sign included: 1 + the bits of the largest |k| (a negative power of two may need one fewer)
+    if (amax) {
+        uint64_t mant = 0;
+        int ex = 0;
+        (void)valpack_split(amax, &mant, &ex);
+        bits = 1 + (ex + 64 - __builtin_clzll(mant)) - e;
+    }
+    p.valpack_bits = bits;
+    p.valpack_exp = e;
+    const int W = valpack_width(L);
+    // (W + 1 bits: only -2^(W - 1) fits; the builder, which looks at every value, decides)
+    if (out[1] || !valpack_exp_ok(e) || bits > W + 1) {
+        valpack_free(a);
+        return SPAL_OK;
+    }
+    // 2. the array
+    const uint32_t rows_padded = p.slide_steps * 256u;
+    const size_t bytes = (size_t)p.slide_steps * 4u * (size_t)valpack_chunks(L) * 64u * sizeof(valpack_chunk_t);
+    if (a->d_valpack && a->valpack_bytes != bytes) valpack_free(a);
+    if (!a->d_valpack) {
+        if (dev_alloc((void **)&a->d_valpack, bytes) != hipSuccess) {   // no room: the plain values serve
+            (void)hipGetLastError();
+            a->d_valpack = nullptr;
+            return SPAL_OK;
+        }
+        a->valpack_bytes = bytes;
+    }
+    uint32_t *d_flag = d_out.as<uint32_t>() + 4;
+    const dim3 gb((rows_padded + 255u) / 256u), gv((uint32_t)((a->nrows + 255) / 256));
+    auto run = [&](auto len) {
+        constexpr int LL = decltype(len)::value;
+        hipLaunchKernelGGL(valpack_build<LL>, gb, dim3(256), 0, a->stream, (const double *)a->d_values, (uint32_t)a->nrows,
+                           rows_padded, e, (valpack_chunk_t *)a->d_valpack, d_flag);
+        // 3. every block decoded and compared
+        hipLaunchKernelGGL(valpack_verify<LL>, gv, dim3(256), 0, a->stream, (const valpack_chunk_t *)a->d_valpack,
+                           (const double *)a->d_values, (uint32_t)a->nrows, valpack_scale(e), d_flag);
+    };
+    if (L == 12) run(std::integral_constant<int, 12>{});
+    else if (L == 14) run(std::integral_constant<int, 14>{});
+    else run(std::integral_constant<int, 16>{});
+    SPAL_HIP_TRY(hipGetLastError());
+    uint32_t flag[2] = {0u, 0u};
+    SPAL_HIP_TRY(hipMemcpyAsync(flag, d_flag, sizeof(flag), hipMemcpyDeviceToHost, a->stream));
+    SPAL_HIP_TRY(hipStreamSynchronize(a->stream));
+    a->valpack_build_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (flag[0] || flag[1]) {   // 4. not encodable after all, or (cannot be) a block that does not decode to its row
+        valpack_free(a);
+        p.valpack_failed = (!flag[0] && flag[1]) ? 1 : 0;
+        return SPAL_OK;
+    }
+    p.valpack = L;
+    return SPAL_OK;
 }
 
 void rowrec_free(spal_csr *a) {

@@ -10,6 +10,7 @@ namespace spal {
 //  1. form: one super-tile per workgroup, or the walking form -- the sliding-window kernel when the plan has
 //     it (bands), else the persistent form -- each with plain or non-temporal y stores;
 //  1b. where the plan built row records (csr_rowrec.hpp) and the sliding kernel was kept: records against col16;
+//  1c. where the plan packed the values (csr_valpack.hpp) and the record form was kept: packed values against the values;
 //  2. placement of the column array the kept form streams (the records, or the 16-bit columns) relative to the values (two streams out of one class of region of the device's
 //     memory disturb each other): the columns are tried in up to `place_tries` blocks of 1 GiB taken one
 //     after the other from the device's memory; the fastest place is kept.
@@ -94,13 +95,37 @@ static int csr_autotune(spal_csr_t a, const T *x_dev, T *y_dev, void *stream, in
     // ---- 1b. row records (csr_rowrec.hpp) against col16 on the kept form: 5 % fewer bytes per f64 row of 14 entries for a
     // decode per lane; kept where that wins by 1 % (the results are bit-identical)
     a->rowrec_us[0] = a->rowrec_us[1] = 0.f;
+    const bool packed = p.valpack && a->d_valpack;
     if (rc == SPAL_OK && walking_is_slide && p.slide_on && p.rowrec && a->d_rowrec) {
         float ms[2] = {0.f, 0.f};
+        const int vp = p.valpack_on;
+        p.valpack_on = 0;   // (the records on their own: the packed values are stage 1c's)
         for (int round = 0; round < 2 && rc == SPAL_OK; ++round)
             for (int on = 0; on < 2 && rc == SPAL_OK; ++on) { p.rowrec_on = on; timed(iters, &ms[on]); }
+        p.valpack_on = vp;
         if (rc == SPAL_OK) {
             a->rowrec_us[0] = ms[0] * 1e3f; a->rowrec_us[1] = ms[1] * 1e3f;
             p.rowrec_on = ms[1] <= 0.99f * ms[0] ? 1 : 0;
+        }
+    }
+    // ---- 1c. packed values (csr_valpack.hpp) against the values on the record form: 96 instead of 112 B per f64 row of 14
+    // entries for a fixed-point decode per lane; kept where that wins by 1 % (the results are bit-identical)
+    a->valpack_us[0] = a->valpack_us[1] = 0.f;
+    // (the packed form rides on the records: it is timed with them against whatever stage 1b kept, and brings them along)
+    if (rc == SPAL_OK && walking_is_slide && p.slide_on && p.rowrec && a->d_rowrec && packed) {
+        float ms[2] = {0.f, 0.f};
+        const int rr = p.rowrec_on;
+        for (int round = 0; round < 2 && rc == SPAL_OK; ++round)
+            for (int on = 0; on < 2 && rc == SPAL_OK; ++on) {
+                p.valpack_on = on;
+                p.rowrec_on = on ? 1 : rr;
+                timed(iters, &ms[on]);
+            }
+        p.valpack_on = 0;
+        p.rowrec_on = rr;
+        if (rc == SPAL_OK) {
+            a->valpack_us[0] = ms[0] * 1e3f; a->valpack_us[1] = ms[1] * 1e3f;
+            if (ms[1] <= 0.99f * ms[0]) p.valpack_on = p.rowrec_on = 1;
         }
     }
     // ---- 2. where the 16-bit columns lie relative to the values (two streams out of one class of region

@@ -255,6 +255,13 @@ struct CsrPlan {
     int rowrec_on = 1;       // option "rowrec_on": launch the record form (0: the same plan streams col16 -- A/B, autotune)
     int rowrec = 0;          // the records are built and verified against col16; = the rows' length (12, 14 or 16)
     int rowrec_failed = 0;   // a built record did not decode to its row's col16 (cannot be): the records were dropped
+    // packed values (csr_valpack.hpp): the record form streams fixed-point row blocks instead of the f64 values
+    int valpack_user = -1;   // option "valpack": -1 auto (where the plan has records and the values share a quantum), 0 never, 1 as -1
+    int valpack_on = 1;      // option "valpack_on": launch the packed form (0: the same plan streams the values -- A/B, autotune)
+    int valpack = 0;         // the row blocks are built and verified against the values; = the rows' length (12, 14 or 16)
+    int valpack_failed = 0;  // a built block did not decode to its row's values (cannot be): the array was dropped
+    int valpack_bits = 0;    // bits of the widest k, sign included
+    int valpack_exp = 0;     // e of the quantum 2^e
     int blockwin = -1;       // option "blockwin": -1 = timed against the row split where that is built, 0 never, 1 whenever the windows fit (tests)
     int row_split = -1;      // option "row_split": -1 = when long rows keep a tenth of the 64-row tiles from streaming, 0 never, 1 always (tests)
     int split_threshold = 128;   // option "row_split_threshold": rows above it are "long"
@@ -399,6 +406,10 @@ struct spal_csr {
     size_t rowrec_bytes = 0;
     int rowrec_placed = 0;             // d_rowrec is a piece of a placement block
     float rowrec_us[2] = {0.f, 0.f};   // autotune: per launch {col16, row records} on the kept form
+    void *d_valpack = nullptr;         // packed values (csr_valpack.hpp): [4 * slide_steps tiles][NQ][64] chunks of 16 B; the values stay beside them
+    size_t valpack_bytes = 0;
+    float valpack_us[2] = {0.f, 0.f};  // autotune: per launch {values, packed values} on the kept form
+    float valpack_build_ms = 0.f;      // the scan, the builder and the verify pass of the last plan
     std::mutex mu_cb;
     // autotune: microseconds per launch of {plain, persistent} x {plain, non-temporal y stores}
     float tuned_us[4] = {0.f, 0.f, 0.f, 0.f};
@@ -555,6 +566,10 @@ int slide_plan(spal_csr *a, uint32_t rpt, const std::vector<uint4> &desc, const 
 int rowrec_plan(spal_csr *a);
 void rowrec_free(spal_csr *a);
 inline bool rowrec_runs(const spal_csr *a) { return a->plan.rowrec && a->plan.rowrec_on && a->d_rowrec; }
+// ... and the packed values of a plan with records (after rowrec_plan), their release
+int valpack_plan(spal_csr *a);
+void valpack_free(spal_csr *a);
+inline bool valpack_runs(const spal_csr *a) { return rowrec_runs(a) && a->plan.valpack && a->plan.valpack_on && a->d_valpack; }
 // ... and the column-panel kernel over a->d_ptiles
 hipError_t launch_panel(const spal_csr *a, const void *x, void *y, hipStream_t st);
 // The CSC scatter route over column tiles.  Implemented in spal_csc_plan.hip: windows, modes, hand-off eligibility, then
