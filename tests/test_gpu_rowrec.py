@@ -1,12 +1,17 @@
 """Row records under the sliding kernel (csr_rowrec.hpp): one Elias-Fano record per row of 12, 14 or 16 entries instead of
 the row's 16-bit window positions.  The decode delivers exactly the positions col16 would have, per lane, and the
 products and sums are the sliding kernel's own: every result here is compared bit for bit (np.array_equal) with the CPU
-oracle, and with the same handle's result under "rowrec_on" 0."""
+oracle, and with the same handle's result under "rowrec_on" 0 -- and, on the f64 handles, whose values pack
+(csr_valpack.hpp), under "valpack_on" 0 and 1: test_gpu_slide_forms.run_forms forces each form in turn.  The structures are
+those of tests/slide_cases.py."""
 import numpy as np
 import pytest
 
 import spalinalg_amd as sp
 import spal_synth as synth
+from tests import slide_cases as cases
+from tests.slide_cases import hand_built      # (the builders live there now)
+from tests.test_gpu_slide_forms import ALL, TWO, run_forms
 
 pytestmark = pytest.mark.gpu
 DTYPES = [np.float64, np.float32]
@@ -18,27 +23,17 @@ def bits(y):
 
 
 def both_forms(dev, x, y_ref):
-    """The product with the records and with col16 on the same handle; both are the oracle's bits."""
+    """The product with the records and with col16 on the same handle -- and, the values of an f64 handle here being
+    draws of m * 2^-52, with packed values: every form is reached (run_forms asserts it) and gives the oracle's bits."""
     dev.set_option("rowrec_on", 1)
     d = dev.describe()
     assert d["slide"] == 1 and d["rowrec"] == 1 and d["rowrec_on"] == 1 and d["rowrec_failed"] == 0, d
-    y1 = dev.spmv(x)
-    dev.set_option("rowrec_on", 0)
-    assert dev.describe()["rowrec_on"] == 0
-    y0 = dev.spmv(x)
-    dev.set_option("rowrec_on", 1)
+    out = run_forms(dev, x, ALL if d["dtype"] == "f64" else TWO, y_ref)
+    y0, y1 = out["col16"], out["records"]
+    assert dev.describe()["rowrec_on"] == 1
     assert np.array_equal(y0, y_ref)
     assert np.array_equal(y1, y_ref)
     assert np.array_equal(bits(y1), bits(y0))
-
-
-def uniform_rows(n, nc, cols_of_row, L=14):
-    ci = np.empty((n, L), dtype=np.uint64)
-    for r in range(n):
-        c = np.asarray(cols_of_row(r), dtype=np.uint64)
-        assert c.size == L and np.all(np.diff(c.astype(np.int64)) > 0) and c[-1] < nc, (r, c)
-        ci[r] = c
-    return np.arange(n + 1, dtype=np.uint64) * L, ci.reshape(-1)
 
 
 def values(rng, size, dtype):
@@ -94,30 +89,13 @@ def test_small_matrices(oracle, n, dtype):
     both_forms(dev, x, oracle.csr_spmv(rp, ci, va, x))
 
 
-def hand_built(n, wide_row, wide_span):
-    """n x n, 14 per row.  Most rows hold consecutive columns around the diagonal (the first and the last rows clamped
-    to the matrix); every 97th row spreads over 600 columns with low bytes 255 / 0 / 1 around a page boundary (whatever
-    the ring's size, one of them starts within 256 positions of its end and wraps); every 97th + 5 row holds all its
-    columns in the page of the diagonal; row `wide_row` spans `wide_span` columns."""
-    def cols(r):
-        if r == wide_row:
-            return [r + k for k in range(13)] + [r + wide_span]
-        if r % 97 == 0 and r + 600 < n:
-            return [r + k for k in (0, 3, 50, 255, 256, 257, 300, 301, 400, 511, 512, 513, 599, 600)]
-        if r % 97 == 5 and (r // 256) * 256 + 256 <= n:
-            p = (r // 256) * 256
-            return [p + k for k in (0, 1, 17, 30, 31, 64, 100, 127, 128, 200, 201, 250, 254, 255)]
-        c0 = min(max(r - 7, 0), n - 14)
-        return [c0 + k for k in range(14)]
-    return uniform_rows(n, n, cols)
-
-
 @pytest.mark.parametrize("dtype", DTYPES)
 def test_hand_built_rows(oracle, dtype):
     rng = np.random.default_rng(14)
     n = 40_000 + 37
     # the widest row a record of 14 columns holds: 39 - 12 = 27 whole pages and a low byte
     top = 27 * 256 + 255
+    assert top == cases.max_span(14)
     for span, on in ((top, 1), (top + 1, 0)):
         rp, ci = hand_built(n, 20_000, span)
         va, x = values(rng, ci.size, dtype), values(rng, n, dtype)
@@ -132,6 +110,7 @@ def test_hand_built_rows(oracle, dtype):
             R = d["ring_pages"] * 256
             wraps = [r for r in range(0, n - 600, 97) if r % R >= R - 256]
             assert wraps, d                       # a row whose positions wrap the ring
+            assert set(wraps) <= set(cases.wrapping_rows(ci, 14, R).tolist())
             both_forms(dev, x, y_ref)
         else:
             assert np.array_equal(dev.spmv(x), y_ref)
@@ -143,12 +122,7 @@ def test_jumps_between_steps(oracle, dtype):
     pages on both sides, disjoint windows, synchronous page loads; ncols odd (x ends inside a 16-byte vector)"""
     rng = np.random.default_rng(5)
     n, nc = 40_000, 50_001
-    starts = [0, 30_000, 2_000, 45_000, 44_000, 10_000, 49_000 - 2048, 0]
-
-    def cols(r):
-        base = min(starts[(r // 2048) % len(starts)] + (r % 2048), nc - 2050)
-        return np.sort(rng.choice(2049, size=14, replace=False)) + base
-    rp, ci = uniform_rows(n, nc, cols)
+    rp, ci = cases.block_jumps(rng, n, nc, 14)
     va, x = values(rng, ci.size, dtype), values(rng, nc, dtype)
     y_ref = oracle.csr_spmv(rp, ci, va, x)
     dev = sp.CsrMatrix(n, nc, rp, ci, va).device()
@@ -170,7 +144,7 @@ def test_ineligible_rows_keep_col16(oracle):
 
 def test_unaligned_x_falls_back(bands):
     """x off a 16-byte boundary: the one-super-tile kernels run on col16, which stays resident beside the records"""
-    torch = pytest.importorskip("torch")
+    import torch
     n, rp, ci, va, x, y_ref = bands[(14, np.dtype(np.float64))]
     dev = sp.CsrMatrix(n, n, rp, ci, va).device()
     assert dev.describe()["rowrec_on"] == 1

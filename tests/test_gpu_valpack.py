@@ -8,6 +8,7 @@ import pytest
 
 import spalinalg_amd as sp
 import spal_synth as synth
+from tests.test_gpu_slide_forms import ALL, TWO, run_forms
 
 pytestmark = pytest.mark.gpu
 W = 4096
@@ -22,17 +23,10 @@ def all_forms(dev, x, y_ref, packed=True):
     d = dev.describe()
     assert d["slide"] == 1 and d["rowrec"] == 1 and d["rowrec_on"] == 1, d
     assert d["valpack"] == (1 if packed else 0) and d["valpack_on"] == d["valpack"] and d["valpack_failed"] == 0, d
-    y2 = dev.spmv(x)
-    dev.set_option("valpack_on", 0)
-    assert dev.describe()["valpack_on"] == 0
-    y1 = dev.spmv(x)
-    dev.set_option("rowrec_on", 0)
+    out = run_forms(dev, x, ALL if packed else TWO, y_ref)      # every form reached, none beyond those named
     d = dev.describe()
-    assert d["rowrec_on"] == 0 and d["valpack_on"] == 0, d
-    y0 = dev.spmv(x)
-    dev.set_option("rowrec_on", 1)
-    dev.set_option("valpack_on", 1)
-    for y in (y2, y1, y0):
+    assert d["rowrec_on"] == 1 and d["valpack_on"] == d["valpack"], d
+    for y in out.values():
         assert np.array_equal(bits(y), bits(y_ref))
 
 
