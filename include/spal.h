@@ -929,6 +929,121 @@ int spal_csc_gmres_block_dev_f32(spal_csc_t a, spal_csc_t m, uint64_t k, const f
                                  float *x_dev, uint64_t ldx, uint64_t restart, double tol, uint64_t maxit, void *stream,
                                  spal_krylov_info *info);
 
+/* ---- eigsh: the k largest or smallest eigenpairs of a symmetric matrix on the device ----------------------
+ * Not in the reference.  Thick-restart Lanczos with full orthogonalisation.  A is taken to be symmetric;
+ * as with CG, that is not checked.  The contract is again a sequential text the device reproduces bit for bit, f32 and
+ * f64.  The vectors and the scalars of a step are T; the projected problem is solved in double for both element types.
+ * dot is the dot above; every product is rounded before the sum or difference it enters (no FMA); sqrt and / are IEEE.
+ * m = ncv.  A step is the GMRES step above without the rotations and without M:
+ *
+ *   step(j):  w = A v_j
+ *             h[t] = dot(v_t, w)                     t = 0..j     (all from the same w)
+ *             w[i] = (..((w[i] - (h[0]*v_0[i])) - (h[1]*v_1[i])) ..) - (h[j]*v_j[i])
+ *             c[t] = dot(v_t, w)                     t = 0..j
+ *             w[i] = the same update with c;   h[t] = h[t] + c[t]
+ *             hn = sqrt(dot(w, w));  v_{j+1}[i] = w[i] / hn;  products += 1
+ *             S[t, j] = S[j, t] = double(h[t])       t = 0..j     (exact conversions; no tridiagonal structure is assumed)
+ *
+ *   v0 given by the caller, or v0[i] = T((mix32((i + seed) mod 2^32) >> 8) + 1) / T(2^24)  (exact in f32; mix32 is the
+ *   colouring's, below);   v_0[i] = v0[i] / sqrt(dot(v0, v0))
+ *   S = 0 (m x m doubles);  keep = 0;  restarts = products = 0
+ *   phase:
+ *     for j = keep .. m-1:  step(j);  jj = j + 1;  if hn is not finite: stop 2;  if hn == 0: leave the loop (exhausted)
+ *     if any S[r, q], r, q < jj, is not finite: stop 2
+ *     (theta, Y) = jacobi(S[0..jj, 0..jj]), ordered: descending theta for which = LA, ascending for SA, ties by position
+ *     res[i] = |double(hn) * Y[jj-1, i]|;   nk = min(k, jj)
+ *     converged = the number of leading i < nk with res[i] <= tol * max_t |theta_t|
+ *     if exhausted:  stop 0 if jj >= k, else stop 3        (the pairs of the jj x jj problem are final: res = 0)
+ *     if converged == k: stop 0;   if restarts == maxit: stop 1
+ *     keep = min(k + (m - k) / 2, m - 1)                    (integer division)
+ *     new v_c[i] = (..((T(Y[0,c]) * v_0[i]) + (T(Y[1,c]) * v_1[i])) ..) + (T(Y[m-1,c]) * v_{m-1}[i])    c = 0..keep-1
+ *     new v_keep = the old v_m;   S = diag(theta_0 .. theta_{keep-1});   restarts += 1;   goto phase
+ *   stop 0, 1, 3:  theta[i] = T(theta_i), resid[i] = T(res[i]) for i < nk;  X[:, c] = the sum above over t < jj for c < nk.
+ *                  theta[nk..k), resid[nk..k) and X[:, nk..k) are not written (reason 3 alone has nk < k; converged = nk).
+ *   stop 2:        theta, resid and X are not written;  converged = 0.
+ *
+ *   jacobi(S), m x m, on doubles with + - * / sqrt alone:  Y = I;  at most 64 sweeps;  a sweep visits p = 0..m-2,
+ *   q = p+1..m-1 in that order:
+ *       a = S[p,q];  if a == 0: next
+ *       if |S[p,p]| + |a| == |S[p,p]| and |S[q,q]| + |a| == |S[q,q]|:  S[p,q] = S[q,p] = 0;  next
+ *       th = (0.5 * (S[q,q] - S[p,p])) / a;  t = 1 / (|th| + sqrt((th*th) + 1));  if th < 0: t = -t
+ *       c = 1 / sqrt((t*t) + 1);  s = t * c
+ *       S[p,p] = S[p,p] - (t*a);  S[q,q] = S[q,q] + (t*a);  S[p,q] = S[q,p] = 0
+ *       for r != p, q:  (x, y) = (S[r,p], S[r,q]);  S[r,p] = S[p,r] = (c*x) - (s*y);  S[r,q] = S[q,r] = (s*x) + (c*y)
+ *       for every r:    (x, y) = (Y[r,p], Y[r,q]);  Y[r,p] = (c*x) - (s*y);           Y[r,q] = (s*x) + (c*y)
+ *   and stops after the first sweep that rotated nothing.  theta_i = S[i,i], its vector column i of Y.
+ *   spal_eigsh_jacobi runs exactly this on the host (s: m x m by rows, symmetric and finite, 1 <= m <= 256; theta: m;
+ *   y: m x m by rows; sweeps may be NULL): the pairs are NOT ordered by it.  It is a DIAGNOSTIC AID -- it lets a test or a
+ *   binding compare its own restatement of the text with the library's bits without a device -- and no dense
+ *   eigensolver to build on: O(m^3) per sweep, one thread.
+ *
+ * Consequences.  (1) Because every step orthogonalises against the whole basis, the arrow entries S[t, keep], t < keep,
+ * of the phase after a restart fall out of the same dots: there is no separate formula for them.  (2) res[i] is the
+ * residual norm of pair i in exact arithmetic.  (3) The Ritz vectors are sums of rounded products: their norm is 1 only
+ * up to rounding.  (4) MULTIPLE EIGENVALUES: a single-vector Lanczos iteration sees one direction of an eigenspace, so an
+ * eigenvalue of multiplicity > 1 is returned ONCE (until rounding brings in a second copy, much later); the pairs
+ * returned are then not the k extreme eigenvalues counted with multiplicity.  (5) A start vector orthogonal to a wanted
+ * eigenvector misses it the same way; v0 = e_0 on a diagonal matrix exhausts the space at jj = 1.
+ * WHAT THE BITS DO NOT DEPEND ON: "krylov_check_every" (unused here: the host polls once per phase), the rotation
+ * kernel's form and tiling ("eigsh_rotate"), the batch of basis vectors in the dots and updates, ldx, the stream.
+ *
+ * On the device the step is GMRES's kernels, the step's scalars (h + c, the column of S, hn, jj and the
+ * flags) one workgroup; hn == 0, a hn that is not finite and jj == m are decided there, and every later launch of the
+ * phase returns before it writes -- nothing waits, nothing spins.  The host copies the head and the columns of the
+ * phase down (one poll per phase), solves the projected problem and decides.  The rotation V <- V Y is one kernel in one
+ * of two forms with the same bits.  Option "eigsh_rotate" on `a` (spal_*_set_option): 2 = LDS row tiles: a workgroup stages
+ * a tile of rows x m basis values in LDS (about 16 KiB; 64 rows at least, so up to 128 KiB at m = 256 in f64) and emits
+ * all keep outputs from it, in place, no second basis; 1 = batched passes, eight outputs per pass over the basis, out of
+ * place into a second basis of ncv + 1 vectors; 0 = automatic = 2, the faster of the two in every case measured (n = 1M
+ * and 10M, ncv = 30, f32 and f64: DESIGN 3.25); anything else SPAL_ERR_INVALID_ARGUMENT.
+ * Arguments: theta and resid are k HOST values in every form; x may be NULL (values only), else it is n x k ROW-MAJOR with
+ * leading dimension ldx >= k and X[i, k..ldx) is never written; v0 may be NULL (the default vector from `seed`).
+ * The _dev forms take v0_dev and x_dev as device pointers, SYNCHRONISE `stream` and are refused on a capturing stream.
+ * The basis (ncv + 1 vectors), w, and with "eigsh_rotate" = 1 a second basis come from the caching allocator in ONE
+ * block per call on 256-byte strides.  CSC handles run on their CSR twin.
+ * info: restarts, products, converged, reason (0 converged or exhausted with jj >= k, 1 maxit restarts, 2 not finite,
+ * 3 exhausted with jj < k), solve_ms = device time from the first to the last launch.
+ * SPAL_ERR_INVALID_ARGUMENT before any device work: null a, theta, resid or info; k == 0; ncv <= k; ncv > 256; which
+ * outside {0, 1}; tol negative or not finite; ldx < k; an _f64 entry on an f32 handle or the reverse; a matrix that is
+ * not square; ncv > nrows; the host forms: v0_len != nrows (with v0), theta_len != k, resid_len != k, x_rows != nrows
+ * (with x).  SPAL_ERR_UNSUPPORTED: a handle held as row blocks.  SPAL_ERR_OUT_OF_MEMORY: no room for the basis, with the
+ * byte count.  Nothing leaks on any failure.
+ * describe() on `a` gains "eigsh" after a call: {k, which, ncv, keep, restarts, products, converged, reason, polls,
+ * rotate, rotate_tile_rows, basis_bytes, rotate_ms = device time of the restarts' rotations, solve_ms}.
+ * Not provided: interior eigenvalues and shift-invert, which = LM / BE, nonsymmetric matrices, a generalised problem,
+ * block Lanczos, several GPUs, capture into a graph. */
+enum { SPAL_EIGSH_LA = 0, SPAL_EIGSH_SA = 1 };
+typedef struct spal_eigsh_info {
+    uint64_t restarts, products, converged;
+    int reason;
+    double solve_ms;
+} spal_eigsh_info;
+int spal_eigsh_jacobi(uint64_t m, const double *s, double *theta, double *y, uint64_t *sweeps);   /* host only */
+int spal_csr_eigsh_f64(spal_csr_t a, uint64_t k, int which, uint64_t ncv, const double *v0, uint64_t v0_len,
+                       uint64_t seed, double tol, uint64_t maxit, double *theta, uint64_t theta_len, double *resid,
+                       uint64_t resid_len, double *x, uint64_t ldx, uint64_t x_rows, spal_eigsh_info *info);
+int spal_csr_eigsh_f32(spal_csr_t a, uint64_t k, int which, uint64_t ncv, const float *v0, uint64_t v0_len,
+                       uint64_t seed, double tol, uint64_t maxit, float *theta, uint64_t theta_len, float *resid,
+                       uint64_t resid_len, float *x, uint64_t ldx, uint64_t x_rows, spal_eigsh_info *info);
+int spal_csr_eigsh_dev_f64(spal_csr_t a, uint64_t k, int which, uint64_t ncv, const double *v0_dev, uint64_t seed,
+                           double tol, uint64_t maxit, double *theta, double *resid, double *x_dev, uint64_t ldx,
+                           void *stream, spal_eigsh_info *info);                  /* synchronises */
+int spal_csr_eigsh_dev_f32(spal_csr_t a, uint64_t k, int which, uint64_t ncv, const float *v0_dev, uint64_t seed,
+                           double tol, uint64_t maxit, float *theta, float *resid, float *x_dev, uint64_t ldx,
+                           void *stream, spal_eigsh_info *info);
+int spal_csc_eigsh_f64(spal_csc_t a, uint64_t k, int which, uint64_t ncv, const double *v0, uint64_t v0_len,
+                       uint64_t seed, double tol, uint64_t maxit, double *theta, uint64_t theta_len, double *resid,
+                       uint64_t resid_len, double *x, uint64_t ldx, uint64_t x_rows, spal_eigsh_info *info);
+int spal_csc_eigsh_f32(spal_csc_t a, uint64_t k, int which, uint64_t ncv, const float *v0, uint64_t v0_len,
+                       uint64_t seed, double tol, uint64_t maxit, float *theta, uint64_t theta_len, float *resid,
+                       uint64_t resid_len, float *x, uint64_t ldx, uint64_t x_rows, spal_eigsh_info *info);
+int spal_csc_eigsh_dev_f64(spal_csc_t a, uint64_t k, int which, uint64_t ncv, const double *v0_dev, uint64_t seed,
+                           double tol, uint64_t maxit, double *theta, double *resid, double *x_dev, uint64_t ldx,
+                           void *stream, spal_eigsh_info *info);
+int spal_csc_eigsh_dev_f32(spal_csc_t a, uint64_t k, int which, uint64_t ncv, const float *v0_dev, uint64_t seed,
+                           double tol, uint64_t maxit, float *theta, float *resid, float *x_dev, uint64_t ldx,
+                           void *stream, spal_eigsh_info *info);
+
 /* ---- multicolour reordering: greedy colouring and B = P A P^T -------------------------------------------
  * Not in the reference.  An exact triangular solve costs one launch step per level; numbering the rows
  * colour by colour leaves both triangles of P A P^T with at most as many levels as there are colours.

@@ -19,6 +19,7 @@
 //   a.solve(b, method, M, x0, tol, maxit), dot(a, b)     not in the reference: CG / BiCGStab and their dot product
 //                                                        (include/spal.h, spal_*_krylov_*, spal_*_krylov_block_*, spal_dot_*)
 //   a.gmres(b, restart, M, x0, tol, maxit)               not in the reference: restarted GMRES (spal_*_gmres_*)
+//   a.eigsh(k, which, ncv, v0, seed, tol, maxit)         not in the reference: extreme eigenpairs of a symmetric matrix (spal_*_eigsh_*)
 //   a.gmres_block(B, k, restart, M, X0, tol, maxit)      not in the reference: GMRES on k right-hand sides (spal_*_gmres_block_*)
 //   a.colour(seed), a.permute(perm), a.multicolour(seed), p.ordering(), p.to_order(v), p.from_order(v),
 //   colour_greedy(n, rowptr, colind, seed), perm_from_colours(colours)
@@ -33,7 +34,9 @@
 // T is exactly the two `Scalar` impls: float, double (src/scalar.rs:56-57).
 #pragma once
 
+#include <algorithm>
 #include <cstdint>
+#include <limits>
 #include <memory>
 #include <stdexcept>
 #include <string>
@@ -78,6 +81,7 @@ template <> struct Abi<double> {
     static constexpr auto csr_krylov_block = spal_csr_krylov_block_f64;
     static constexpr auto csr_gmres = spal_csr_gmres_f64;
     static constexpr auto csr_gmres_block = spal_csr_gmres_block_f64;
+    static constexpr auto csr_eigsh = spal_csr_eigsh_f64;
     static constexpr auto csr_permute_vec = spal_csr_permute_vec_f64;
     static constexpr auto dot = spal_dot_f64;
     static constexpr auto csr_download = spal_csr_download_f64;
@@ -92,6 +96,7 @@ template <> struct Abi<double> {
     static constexpr auto csc_krylov_block = spal_csc_krylov_block_f64;
     static constexpr auto csc_gmres = spal_csc_gmres_f64;
     static constexpr auto csc_gmres_block = spal_csc_gmres_block_f64;
+    static constexpr auto csc_eigsh = spal_csc_eigsh_f64;
     static constexpr auto csc_permute_vec = spal_csc_permute_vec_f64;
     static constexpr auto coo_to_csr = spal_coo_to_csr_f64;
     static constexpr auto coo_to_csc = spal_coo_to_csc_f64;
@@ -109,6 +114,7 @@ template <> struct Abi<float> {
     static constexpr auto csr_krylov_block = spal_csr_krylov_block_f32;
     static constexpr auto csr_gmres = spal_csr_gmres_f32;
     static constexpr auto csr_gmres_block = spal_csr_gmres_block_f32;
+    static constexpr auto csr_eigsh = spal_csr_eigsh_f32;
     static constexpr auto csr_permute_vec = spal_csr_permute_vec_f32;
     static constexpr auto dot = spal_dot_f32;
     static constexpr auto csr_download = spal_csr_download_f32;
@@ -123,6 +129,7 @@ template <> struct Abi<float> {
     static constexpr auto csc_krylov_block = spal_csc_krylov_block_f32;
     static constexpr auto csc_gmres = spal_csc_gmres_f32;
     static constexpr auto csc_gmres_block = spal_csc_gmres_block_f32;
+    static constexpr auto csc_eigsh = spal_csc_eigsh_f32;
     static constexpr auto csc_permute_vec = spal_csc_permute_vec_f32;
     static constexpr auto coo_to_csr = spal_coo_to_csr_f32;
     static constexpr auto coo_to_csc = spal_coo_to_csc_f32;
@@ -152,6 +159,17 @@ struct Solution {
     usize iterations;
     int reason;   // 0 converged (dot(r, r) <= tol^2 dot(b, b)), 1 maxit reached, 2 breakdown / not finite
     double residual_sq, rhs_sq, solve_ms;
+};
+
+// What eigsh returns: `pairs` eigenvalues in the order asked for (LA descending, SA ascending), their estimates
+// |hn * Y[m-1, i]|, and X row-major (element (i, j) at i * pairs + j; empty when no vectors were asked for).
+enum class Which : int { LA = SPAL_EIGSH_LA, SA = SPAL_EIGSH_SA };
+template <typename T>
+struct Eigenpairs {
+    std::vector<T> theta, resid, x;
+    usize pairs, restarts, products, converged;
+    int reason;   // 0 converged (or the space exhausted with >= k pairs), 1 maxit restarts, 2 not finite, 3 exhausted below k
+    double solve_ms;
 };
 
 // What solve_block returns: X row-major (element (i, j) at i * k + j) and one record per column, as Solution holds one.
@@ -478,6 +496,46 @@ class CsrMatrix {
         return s;
     }
 
+    // The k largest (Which::LA) or smallest (Which::SA) eigenpairs of this SYMMETRIC matrix (not checked) by thick-restart
+    // Lanczos with full orthogonalisation on the device; bit for bit the text of include/spal.h (spal_csr_eigsh_*).  ncv = 0:
+    // min(n, max(2k + 1, 20)); tol = 0: the element type's machine epsilon; v0 empty: the text's start vector from `seed`.
+    // An eigenvalue of multiplicity > 1 is returned ONCE.  Panics on a matrix that is not square, k == 0, ncv <= k,
+    // ncv > 256 or ncv > n.
+    Eigenpairs<T> eigsh(usize k = 6, Which which = Which::LA, usize ncv = 0, const std::vector<T> &v0 = {}, usize seed = 0,
+                        double tol = 0.0, usize maxit = 1000, bool vectors = true) const {
+        if (nrows_ != ncols_)
+            throw Panic(SPAL_ERR_INVALID_ARGUMENT, "eigsh: the matrix is not square (" + std::to_string(nrows_) + " x " +
+                                                       std::to_string(ncols_) + ")");
+        if (ncv == 0) ncv = std::min<usize>(nrows_, std::max<usize>(2 * k + 1, 20));
+        if (k == 0 || ncv <= k || ncv > 256 || ncv > nrows_)
+            throw Panic(SPAL_ERR_INVALID_ARGUMENT, "eigsh: k = " + std::to_string(k) + " and ncv = " + std::to_string(ncv) +
+                                                       " must satisfy 0 < k < ncv <= min(256, " + std::to_string(nrows_) + ")");
+        if (!v0.empty() && v0.size() != nrows_)
+            throw Panic(SPAL_ERR_INVALID_ARGUMENT, "eigsh: v0.len() = " + std::to_string(v0.size()) + " but the matrix has " +
+                                                       std::to_string(nrows_) + " rows");
+        if (tol == 0.0) tol = static_cast<double>(std::numeric_limits<T>::epsilon());
+        Eigenpairs<T> e{std::vector<T>(k, T(0)), std::vector<T>(k, T(0)), std::vector<T>(vectors ? nrows_ * k : 0, T(0)), 0, 0, 0, 0, 0, 0.0};
+        spal_eigsh_info info;
+        detail::check(detail::Abi<T>::csr_eigsh(device_handle(), k, static_cast<int>(which), ncv, v0.empty() ? nullptr : v0.data(),
+                                                 v0.size(), seed, tol, maxit, e.theta.data(), k, e.resid.data(), k,
+                                                 vectors ? e.x.data() : nullptr, k, nrows_, &info));
+        e.pairs = info.reason == 2 ? 0 : info.reason == 3 ? info.converged : k;
+        e.restarts = info.restarts;
+        e.products = info.products;
+        e.converged = info.converged;
+        e.reason = info.reason;
+        e.solve_ms = info.solve_ms;
+        if (e.pairs < k) {   // pack the columns that were written
+            std::vector<T> x(vectors ? nrows_ * e.pairs : 0);
+            for (usize i = 0; vectors && i < nrows_; ++i)
+                for (usize j = 0; j < e.pairs; ++j) x[i * e.pairs + j] = e.x[i * k + j];
+            e.x.swap(x);
+            e.theta.resize(e.pairs);
+            e.resid.resize(e.pairs);
+        }
+        return e;
+    }
+
     // X with A X = B for a ROW-MAJOR block of k right-hand sides by restarted GMRES(restart): k independent iterations in
     // lockstep on shared launches, with cycles common to the block (spal_csr_gmres_block_*, include/spal.h).  Column j
     // of the result and columns[j] are bit for bit gmres()'s text on column j of B, whatever k and the other columns are.
@@ -793,6 +851,46 @@ class CscMatrix {
         s.rhs_sq = info.rhs_sq;
         s.solve_ms = info.solve_ms;
         return s;
+    }
+
+    // The k largest (Which::LA) or smallest (Which::SA) eigenpairs of this SYMMETRIC matrix (not checked) by thick-restart
+    // Lanczos with full orthogonalisation on the device; bit for bit the text of include/spal.h (spal_csc_eigsh_*).  ncv = 0:
+    // min(n, max(2k + 1, 20)); tol = 0: the element type's machine epsilon; v0 empty: the text's start vector from `seed`.
+    // An eigenvalue of multiplicity > 1 is returned ONCE.  Panics on a matrix that is not square, k == 0, ncv <= k,
+    // ncv > 256 or ncv > n.
+    Eigenpairs<T> eigsh(usize k = 6, Which which = Which::LA, usize ncv = 0, const std::vector<T> &v0 = {}, usize seed = 0,
+                        double tol = 0.0, usize maxit = 1000, bool vectors = true) const {
+        if (nrows_ != ncols_)
+            throw Panic(SPAL_ERR_INVALID_ARGUMENT, "eigsh: the matrix is not square (" + std::to_string(nrows_) + " x " +
+                                                       std::to_string(ncols_) + ")");
+        if (ncv == 0) ncv = std::min<usize>(nrows_, std::max<usize>(2 * k + 1, 20));
+        if (k == 0 || ncv <= k || ncv > 256 || ncv > nrows_)
+            throw Panic(SPAL_ERR_INVALID_ARGUMENT, "eigsh: k = " + std::to_string(k) + " and ncv = " + std::to_string(ncv) +
+                                                       " must satisfy 0 < k < ncv <= min(256, " + std::to_string(nrows_) + ")");
+        if (!v0.empty() && v0.size() != nrows_)
+            throw Panic(SPAL_ERR_INVALID_ARGUMENT, "eigsh: v0.len() = " + std::to_string(v0.size()) + " but the matrix has " +
+                                                       std::to_string(nrows_) + " rows");
+        if (tol == 0.0) tol = static_cast<double>(std::numeric_limits<T>::epsilon());
+        Eigenpairs<T> e{std::vector<T>(k, T(0)), std::vector<T>(k, T(0)), std::vector<T>(vectors ? nrows_ * k : 0, T(0)), 0, 0, 0, 0, 0, 0.0};
+        spal_eigsh_info info;
+        detail::check(detail::Abi<T>::csc_eigsh(device_handle(), k, static_cast<int>(which), ncv, v0.empty() ? nullptr : v0.data(),
+                                                 v0.size(), seed, tol, maxit, e.theta.data(), k, e.resid.data(), k,
+                                                 vectors ? e.x.data() : nullptr, k, nrows_, &info));
+        e.pairs = info.reason == 2 ? 0 : info.reason == 3 ? info.converged : k;
+        e.restarts = info.restarts;
+        e.products = info.products;
+        e.converged = info.converged;
+        e.reason = info.reason;
+        e.solve_ms = info.solve_ms;
+        if (e.pairs < k) {   // pack the columns that were written
+            std::vector<T> x(vectors ? nrows_ * e.pairs : 0);
+            for (usize i = 0; vectors && i < nrows_; ++i)
+                for (usize j = 0; j < e.pairs; ++j) x[i * e.pairs + j] = e.x[i * k + j];
+            e.x.swap(x);
+            e.theta.resize(e.pairs);
+            e.resid.resize(e.pairs);
+        }
+        return e;
     }
 
     // X with A X = B for a ROW-MAJOR block of k right-hand sides by restarted GMRES(restart): k independent iterations in

@@ -30,6 +30,11 @@ pub struct spal_krylov_info { pub iterations: u64, pub reason: c_int, pub residu
 /// The parameters of spal_*_amg_setup; spal_amg_default_params fills in {0, 16, 64, 2, 16, 1, 2/3, 1}.
 #[repr(C)] #[derive(Clone, Copy, Debug, Default)]
 pub struct spal_amg_params { pub seed: u64, pub max_levels: u64, pub coarse_rows: u64, pub nu: u64, pub coarse_sweeps: u64, pub gamma: u64, pub omega: f64, pub alpha: f64 }
+pub const SPAL_EIGSH_LA: c_int = 0;
+pub const SPAL_EIGSH_SA: c_int = 1;
+/// What spal_*_eigsh_* report: reason 0 converged, 1 maxit restarts, 2 not finite, 3 space exhausted below k.
+#[repr(C)] #[derive(Clone, Copy, Debug, Default)]
+pub struct spal_eigsh_info { pub restarts: u64, pub products: u64, pub converged: u64, pub reason: c_int, pub solve_ms: f64 }
 
 #[link(name = "spal_hip")]
 extern "C" {
@@ -152,6 +157,15 @@ extern "C" {
     pub fn spal_csc_gmres_block_f32(a: *mut spal_csc, m: *mut spal_csc, k: u64, b: *const f32, ldb: u64, b_rows: u64, x: *mut f32, ldx: u64, x_rows: u64, restart: u64, tol: f64, maxit: u64, info: *mut spal_krylov_info) -> c_int;
     pub fn spal_csc_gmres_block_dev_f64(a: *mut spal_csc, m: *mut spal_csc, k: u64, b_dev: *const f64, ldb: u64, x_dev: *mut f64, ldx: u64, restart: u64, tol: f64, maxit: u64, stream: *mut c_void, info: *mut spal_krylov_info) -> c_int;
     pub fn spal_csc_gmres_block_dev_f32(a: *mut spal_csc, m: *mut spal_csc, k: u64, b_dev: *const f32, ldb: u64, x_dev: *mut f32, ldx: u64, restart: u64, tol: f64, maxit: u64, stream: *mut c_void, info: *mut spal_krylov_info) -> c_int;
+    pub fn spal_eigsh_jacobi(m: u64, s: *const f64, theta: *mut f64, y: *mut f64, sweeps: *mut u64) -> c_int;
+    pub fn spal_csr_eigsh_f64(a: *mut spal_csr, k: u64, which: c_int, ncv: u64, v0: *const f64, v0_len: u64, seed: u64, tol: f64, maxit: u64, theta: *mut f64, theta_len: u64, resid: *mut f64, resid_len: u64, x: *mut f64, ldx: u64, x_rows: u64, info: *mut spal_eigsh_info) -> c_int;
+    pub fn spal_csr_eigsh_f32(a: *mut spal_csr, k: u64, which: c_int, ncv: u64, v0: *const f32, v0_len: u64, seed: u64, tol: f64, maxit: u64, theta: *mut f32, theta_len: u64, resid: *mut f32, resid_len: u64, x: *mut f32, ldx: u64, x_rows: u64, info: *mut spal_eigsh_info) -> c_int;
+    pub fn spal_csr_eigsh_dev_f64(a: *mut spal_csr, k: u64, which: c_int, ncv: u64, v0_dev: *const f64, seed: u64, tol: f64, maxit: u64, theta: *mut f64, resid: *mut f64, x_dev: *mut f64, ldx: u64, stream: *mut c_void, info: *mut spal_eigsh_info) -> c_int;
+    pub fn spal_csr_eigsh_dev_f32(a: *mut spal_csr, k: u64, which: c_int, ncv: u64, v0_dev: *const f32, seed: u64, tol: f64, maxit: u64, theta: *mut f32, resid: *mut f32, x_dev: *mut f32, ldx: u64, stream: *mut c_void, info: *mut spal_eigsh_info) -> c_int;
+    pub fn spal_csc_eigsh_f64(a: *mut spal_csc, k: u64, which: c_int, ncv: u64, v0: *const f64, v0_len: u64, seed: u64, tol: f64, maxit: u64, theta: *mut f64, theta_len: u64, resid: *mut f64, resid_len: u64, x: *mut f64, ldx: u64, x_rows: u64, info: *mut spal_eigsh_info) -> c_int;
+    pub fn spal_csc_eigsh_f32(a: *mut spal_csc, k: u64, which: c_int, ncv: u64, v0: *const f32, v0_len: u64, seed: u64, tol: f64, maxit: u64, theta: *mut f32, theta_len: u64, resid: *mut f32, resid_len: u64, x: *mut f32, ldx: u64, x_rows: u64, info: *mut spal_eigsh_info) -> c_int;
+    pub fn spal_csc_eigsh_dev_f64(a: *mut spal_csc, k: u64, which: c_int, ncv: u64, v0_dev: *const f64, seed: u64, tol: f64, maxit: u64, theta: *mut f64, resid: *mut f64, x_dev: *mut f64, ldx: u64, stream: *mut c_void, info: *mut spal_eigsh_info) -> c_int;
+    pub fn spal_csc_eigsh_dev_f32(a: *mut spal_csc, k: u64, which: c_int, ncv: u64, v0_dev: *const f32, seed: u64, tol: f64, maxit: u64, theta: *mut f32, resid: *mut f32, x_dev: *mut f32, ldx: u64, stream: *mut c_void, info: *mut spal_eigsh_info) -> c_int;
     pub fn spal_colour_greedy(n: u64, rowptr: *const u64, colind: *const u64, seed: u64, colour: *mut u64, ncolours: *mut u64) -> c_int;
     pub fn spal_perm_from_colours(n: u64, colour: *const u64, perm: *mut u64) -> c_int;
     pub fn spal_csr_colour(a: *mut spal_csr, seed: u64, stream: *mut c_void, colour_host: *mut u64, ncolours: *mut u64, rounds: *mut u64) -> c_int;

@@ -1,0 +1,603 @@
+// spal_eigsh.hip -- extreme eigenpairs of a symmetric matrix on the device: thick-restart Lanczos with full
+// orthogonalisation.  The contract is the sequential text in include/spal.h; the device returns its bits in
+// f32 and f64.
+//
+// ONE STEP IS GMRES'S INNER STEP WITHOUT THE ROTATIONS: w = A v_j, two passes of classical Gram-Schmidt against the whole
+// basis (mdot / mfinish / mupdate of gmres_kernels.hpp, launched from the same text as spal_gmres.hip), hn = sqrt(dot(w, w)),
+// v_{j+1} = w / hn (scale).  The step's scalar kernel (`lanczos_scalars`, one workgroup) adds c to h, stores the column of
+// the projected matrix, sets hn and the flags GMRES uses: `jj`, `cyc_end` (the phase is over: ncv vectors, or hn == 0) and
+// `done` (hn not finite).  Every kernel of step j returns before it writes unless the device is exactly there; nothing
+// waits, nothing spins.  The host polls ONCE PER PHASE: the head and the columns of the phase come down, the projected
+// problem is solved on the host in double (eigsh_host.hpp: cyclic Jacobi), and the host decides: stop, or restart.
+//
+// THE RESTART MOVES THE WHOLE BASIS: v_c <- sum_t Y[t, c] v_t for c < keep, ascending t, every product rounded.  Two forms
+// of that rotation, the same bits:
+//   rotate_lds    a workgroup stages a tile of R rows x m basis values in LDS (dynamic, up to 128 KiB of gfx950's 160 KiB),
+//                 then emits all keep outputs from LDS, eight accumulators per thread and LDS read: V is read ONCE and
+//                 the rotation is IN PLACE (a tile's rows are read before any of them is written, and nobody else touches
+//                 them); the same launch carries v_m into v_keep.
+//   rotate_batch  combine's shape: a thread keeps four rows and eight accumulators each, and walks the basis once per
+//                 batch of eight outputs: V is read ceil(keep / 8) times, out of place into a second basis.
+// Option "eigsh_rotate" on `a` picks one: 0 = automatic = the LDS form, which measured faster in all six cases of
+// tools/bench_eigsh.py at ncv = 30 (f64: 0.102 against 0.139 ms at n = 1M, 1.00 against 1.70 ms at n = 10M; f32: 0.069
+// against 0.073 and 0.66 against 0.73 ms) and needs no second basis; 1 = the batched passes.  The tile is kept
+// SMALL on purpose (about 16 KiB): with tiles of 64 KiB, two workgroups per CU, the same kernel took 0.173 ms where it now
+// takes 0.102 -- staging and the sums alternate inside a workgroup, and only other workgroups on the CU overlap them.  The
+// Ritz vectors at the end are the same kernel writing into x (row-major, leading dimension ldx).
+#include "eigsh_host.hpp"
+#include "gmres_kernels.hpp"
+
+#pragma clang fp contract(off)
+
+namespace spal {
+namespace {
+
+constexpr uint64_t kMaxNcv = 256;        // one column element per thread of the scalar workgroup
+constexpr int kRotBatch = 8;             // outputs per accumulator batch of both rotation forms
+constexpr unsigned kRotMinRows = 64;     // rows of the smallest LDS tile: one wave
+constexpr size_t kRotLdsTarget = 16 * 1024;   // a tile doubles its rows while it stays within this (eight or more workgroups per CU); never below kRotMinRows rows
+constexpr unsigned kRotMaxGrid = 8192;
+
+// ---- the start vector -----------------------------------------------------------------------------------------------
+// v[i] = T((mix32((i + seed) mod 2^32) >> 8) + 1) / T(2^24): exact in f32
+template <typename T>
+__global__ __launch_bounds__(kThreads) void default_start(T *v, uint64_t n, uint32_t seed) {
+    for (uint64_t i = (uint64_t)blockIdx.x * kThreads + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kThreads)
+        v[i] = T((colour_mix32((uint32_t)i + seed) >> 8) + 1u) / T(16777216);
+}
+
+// part[tile] = the tile's sum of v[i] * v[i]
+template <typename T>
+__global__ __launch_bounds__(kThreads) void square_tiles(const T *v, T *part, uint64_t n, uint64_t tiles) {
+    __shared__ T lds[kThreads];
+    for (uint64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+        const uint64_t i = tile * kTile + threadIdx.x;
+        T x[4];
+        load4<T>(v, i, n, x);
+        const T s = tile_sum<T>(x[0] * x[0], x[1] * x[1], x[2] * x[2], x[3] * x[3], lds);
+        if (threadIdx.x == 0) part[tile] = s;
+    }
+}
+
+// beta = sqrt(dot(v0, v0)); jj = 0
+template <typename T>
+__global__ __launch_bounds__(kThreads) void start_scalars(GHead<T> *s, T *part, uint64_t c1) {
+    __shared__ T lds[kThreads];
+    const T vv = upper_levels<T>(part, c1, lds);
+    if (threadIdx.x == 0) {
+        s->beta = sqrt(vv);
+        s->jj = 0;
+        s->cyc_end = 0;
+    }
+}
+
+// a phase begins at step `keep` (after a restart)
+template <typename T>
+__global__ void phase_start(GHead<T> *s, unsigned keep) {
+    if (s->done != 0) return;
+    s->jj = keep;
+    s->cyc_end = 0;
+}
+
+// ---- the step's scalars -----------------------------------------------------------------------------------------------
+// ww = dot(w, w);  h += c;  column j of the projected matrix;  hn;  the end of the phase;  jj, it
+template <typename T>
+__global__ __launch_bounds__(kThreads) void lanczos_scalars(GHead<T> *s, T *h, const T *c, T *H, unsigned m, unsigned j, T *part0,
+                                                            uint64_t c1) {
+    __shared__ T lds[kThreads];
+    if (!at_step(s, j)) return;
+    const T ww = upper_levels<T>(part0, c1, lds);
+    const unsigned t = threadIdx.x;
+    if (t <= j) {
+        const T v = h[t] + c[t];
+        h[t] = v;
+        H[(uint64_t)j * m + t] = v;
+    }
+    __syncthreads();   // every thread has read the flags before thread 0 moves them
+    if (t == 0) {
+        const T hn = sqrt(ww);
+        s->hn = hn;
+        s->it += 1;
+        s->jj = j + 1;
+        if (!isfinite(hn)) {
+            s->done = 1;
+            s->reason = 2;
+        } else if (hn == T(0) || j + 1 == m) {
+            s->cyc_end = 1;
+        }
+    }
+}
+
+// ---- the rotation -----------------------------------------------------------------------------------------------------
+// element (r, c) of the result at p[c * cs + r * rs]: basis vectors (cs = stride, rs = 1) or a row-major block (1, ld)
+template <typename T>
+struct RotOut {
+    T *p;
+    uint64_t cs, rs;
+};
+
+// out(r, c) = (..((Y[0, c] * v_0[r]) + (Y[1, c] * v_1[r])) ..) + (Y[m-1, c] * v_{m-1}[r]) for c < nc.  Y is m x ldy by
+// rows, ldy a multiple of kRotBatch (the padding holds zeros and its results are not stored).  A tile of R rows (a power
+// of two, >= 64, so a wave shares its batch of outputs) x m values is staged in LDS as lds[t * R + r], then read back
+// once per batch of eight outputs.  `out` may be the basis itself: the tile's rows were all read before the barrier.
+// carry_dst[r] = carry_src[r] rides along (v_keep = the old v_m; carry_dst may be one of the staged vectors).
+template <typename T>
+__global__ __launch_bounds__(kThreads) void rotate_lds(Basis<T> V, unsigned m, const T *__restrict__ Y, unsigned ldy, unsigned nc,
+                                                       RotOut<T> out, unsigned R, unsigned logR, const T *carry_src, T *carry_dst) {
+    extern __shared__ __align__(16) unsigned char rot_raw[];
+    T *lds = reinterpret_cast<T *>(rot_raw);
+    const uint64_t ntiles = (V.n + R - 1) / R;
+    const unsigned groups = (nc + kRotBatch - 1) / kRotBatch;
+    for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        const uint64_t row0 = tile * R;
+        const unsigned rows = (unsigned)(V.n - row0 < R ? V.n - row0 : R);
+        for (unsigned e = threadIdx.x; e < m * R; e += kThreads) {
+            const unsigned t = e >> logR, r = e & (R - 1);
+            lds[e] = r < rows ? V.v[(uint64_t)t * V.stride + row0 + r] : T(0);
+        }
+        __syncthreads();
+        if (carry_src)
+            for (unsigned r = threadIdx.x; r < rows; r += kThreads) carry_dst[row0 + r] = carry_src[row0 + r];
+        for (unsigned u = threadIdx.x; u < groups * R; u += kThreads) {
+            const unsigned g = __builtin_amdgcn_readfirstlane(u >> logR), r = u & (R - 1);
+            const unsigned c0 = g * kRotBatch;
+            T acc[kRotBatch];
+            const T *y = Y + c0;
+            for (unsigned t = 0; t < m; ++t, y += ldy) {
+                const T x = lds[t * R + r];
+#pragma unroll
+                for (int b = 0; b < kRotBatch; ++b) {
+                    const T p = y[b] * x;
+                    acc[b] = t == 0 ? p : acc[b] + p;
+                }
+            }
+            if (r < rows) {
+#pragma unroll
+                for (int b = 0; b < kRotBatch; ++b)
+                    if (c0 + b < nc) out.p[(uint64_t)(c0 + b) * out.cs + (row0 + r) * out.rs] = acc[b];
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// The same sums, combine's way: a thread keeps its four rows of a tile of 1024 and eight accumulators for each, and walks
+// the basis once per batch of eight outputs.  `out` must not overlap the basis.
+template <typename T>
+__global__ __launch_bounds__(kThreads) void rotate_batch(Basis<T> V, unsigned m, const T *__restrict__ Y, unsigned ldy, unsigned nc,
+                                                         RotOut<T> out) {
+    for (uint64_t tile = blockIdx.x; tile < V.tiles; tile += gridDim.x) {
+        const uint64_t i = tile * kTile + threadIdx.x;
+        for (unsigned c0 = 0; c0 < nc; c0 += kRotBatch) {
+            T acc[kRotBatch][4];
+            const T *y = Y + c0;
+            for (unsigned t = 0; t < m; ++t, y += ldy) {
+                T v[4];
+                load4<T>(V.v + (uint64_t)t * V.stride, i, V.n, v);
+#pragma unroll
+                for (int b = 0; b < kRotBatch; ++b) {
+                    const T yb = y[b];
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        const T p = yb * v[k];
+                        acc[b][k] = t == 0 ? p : acc[b][k] + p;
+                    }
+                }
+            }
+#pragma unroll
+            for (int b = 0; b < kRotBatch; ++b) {
+                if (c0 + b >= nc) continue;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const uint64_t e = i + (uint64_t)k * kThreads;
+                    if (e < V.n) out.p[(uint64_t)(c0 + b) * out.cs + e * out.rs] = acc[b][k];
+                }
+            }
+        }
+    }
+}
+
+// rows of an LDS tile for m basis vectors of T: doubles from one wave's 64 while the doubled tile stays within the target
+template <typename T>
+unsigned rot_tile_rows(uint64_t m) {
+    unsigned r = kRotMinRows;
+    while (r < kTile && (size_t)2 * r * m * sizeof(T) <= kRotLdsTarget) r *= 2;
+    return r;
+}
+
+std::atomic<uint64_t> g_lds_f64{0}, g_lds_f32{0};
+template <typename T> std::atomic<uint64_t> &lds_done();
+template <> std::atomic<uint64_t> &lds_done<double>() { return g_lds_f64; }
+template <> std::atomic<uint64_t> &lds_done<float>() { return g_lds_f32; }
+
+// ---- the driver -------------------------------------------------------------------------------------------------------
+struct Record {
+    uint64_t k = 0, ncv = 0, keep = 0, restarts = 0, products = 0, converged = 0, polls = 0, basis_bytes = 0;
+    int which = 0, reason = 0, rotate = 0;
+    unsigned tile_rows = 0;
+    double rotate_ms = 0.0, solve_ms = 0.0;
+};
+std::string info_json(const Record &r) {
+    char buf[640];
+    snprintf(buf, sizeof buf,
+             "{\"k\": %llu, \"which\": \"%s\", \"ncv\": %llu, \"keep\": %llu, \"restarts\": %llu, \"products\": %llu, "
+             "\"converged\": %llu, \"reason\": %d, \"polls\": %llu, \"rotate\": \"%s\", \"rotate_tile_rows\": %u, "
+             "\"basis_bytes\": %llu, \"rotate_ms\": %.4f, \"solve_ms\": %.4f}",
+             (unsigned long long)r.k, r.which == SPAL_EIGSH_LA ? "LA" : "SA", (unsigned long long)r.ncv, (unsigned long long)r.keep,
+             (unsigned long long)r.restarts, (unsigned long long)r.products, (unsigned long long)r.converged, r.reason,
+             (unsigned long long)r.polls, r.rotate == 1 ? "batch" : "lds", r.tile_rows, (unsigned long long)r.basis_bytes,
+             r.rotate_ms, r.solve_ms);
+    return buf;
+}
+
+struct PinnedBuf {
+    void *p = nullptr;
+    PinnedBuf() = default;
+    PinnedBuf(const PinnedBuf &) = delete;
+    PinnedBuf &operator=(const PinnedBuf &) = delete;
+    ~PinnedBuf() { if (p) (void)hipHostFree(p); }
+    hipError_t alloc(size_t bytes) { return hipHostMalloc(&p, bytes ? bytes : 1, hipHostMallocDefault); }
+    template <typename U> U *as() { return reinterpret_cast<U *>(p); }
+};
+
+template <typename T>
+struct Run {
+    const char *fn;
+    spal_csr *a;
+    hipStream_t st;
+    uint64_t n = 0, m = 0, c1 = 0, pe = 0, stride = 0;
+    unsigned grid = 1;
+    int form = 2, device = 0;
+    GHead<T> *s = nullptr;
+    T *h = nullptr, *c = nullptr, *H = nullptr;      // the scalar block: h, c (m + 1 each), the m x m columns
+    T *basis = nullptr, *alt = nullptr, *w = nullptr, *part = nullptr, *y_dev = nullptr, *y_pin = nullptr;
+    Basis<T> V;
+    unsigned tile_rows = 0;
+
+    T *v_at(uint64_t k) const { return basis + k * stride; }
+
+    // v_0 = v0 / sqrt(dot(v0, v0))
+    int start(const T *v0, uint64_t seed) {
+        if (!v0) {
+            KRYLOV_LAUNCH((default_start<T>), grid, v_at(0), n, (uint32_t)seed);
+            v0 = v_at(0);
+        }
+        KRYLOV_LAUNCH((square_tiles<T>), grid, v0, part, n, V.tiles);
+        KRYLOV_LAUNCH((start_scalars<T>), 1, s, part, c1);
+        KRYLOV_LAUNCH((scale<T>), grid, s, v0, v_at(0), -1, n);
+        return SPAL_OK;
+    }
+    int step(unsigned j) {
+        SPAL_TRY(mul_dev(a, (const T *)v_at(j), w, st));
+        KRYLOV_LAUNCH((mdot<T>), grid, s, V, j, w, part, pe);
+        KRYLOV_LAUNCH((mfinish<T>), j + 1, s, j, part, pe, c1, h);
+        KRYLOV_LAUNCH((mupdate<T, false>), grid, s, V, j, h, w, part);
+        KRYLOV_LAUNCH((mdot<T>), grid, s, V, j, w, part, pe);
+        KRYLOV_LAUNCH((mfinish<T>), j + 1, s, j, part, pe, c1, c);
+        KRYLOV_LAUNCH((mupdate<T, true>), grid, s, V, j, c, w, part);
+        KRYLOV_LAUNCH((lanczos_scalars<T>), 1, s, h, c, H, (unsigned)m, j, part, c1);
+        KRYLOV_LAUNCH((scale<T>), grid, s, w, v_at(j + 1), (int)j, n);
+        return SPAL_OK;
+    }
+    // Y (jj x jj doubles by rows, its first nc columns) goes up rounded to T; out(r, c) = sum_t Y[t, c] v_t[r], t < jj
+    int rotate(const RitzPairs &rp, uint64_t jj, uint64_t nc, RotOut<T> out, const T *carry_src, T *carry_dst) {
+        const unsigned ldy = (unsigned)((nc + kRotBatch - 1) / kRotBatch * kRotBatch);
+        for (uint64_t t = 0; t < jj; ++t)
+            for (unsigned cc = 0; cc < ldy; ++cc) y_pin[t * ldy + cc] = cc < nc ? (T)rp.Y[t * jj + cc] : T(0);
+        SPAL_HIP_TRY(hipMemcpyAsync(y_dev, y_pin, jj * ldy * sizeof(T), hipMemcpyHostToDevice, st));
+        if (form == 1) {
+            KRYLOV_LAUNCH((rotate_batch<T>), grid, V, (unsigned)jj, (const T *)y_dev, ldy, (unsigned)nc, out);
+            if (carry_src) SPAL_HIP_TRY(hipMemcpyAsync(carry_dst, carry_src, n * sizeof(T), hipMemcpyDeviceToDevice, st));
+            return SPAL_OK;
+        }
+        const unsigned R = rot_tile_rows<T>(jj);
+        unsigned logR = 0;
+        while ((1u << logR) < R) ++logR;
+        const size_t lds_bytes = (size_t)R * jj * sizeof(T);
+        if (lds_bytes > 48 * 1024)
+            SPAL_HIP_TRY(lds_opt_in(reinterpret_cast<const void *>(&rotate_lds<T>), device, lds_done<T>()));
+        const unsigned g = (unsigned)std::min<uint64_t>((n + R - 1) / R, kRotMaxGrid);
+        tile_rows = R;
+        hipLaunchKernelGGL((rotate_lds<T>), dim3(std::max(g, 1u)), dim3(kThreads), lds_bytes, st, V, (unsigned)jj, (const T *)y_dev, ldy,
+                           (unsigned)nc, out, R, logR, carry_src, carry_dst);
+        const hipError_t le = hipGetLastError();
+        if (le != hipSuccess) return fail(SPAL_ERR_HIP, "%s: launch failed: %s", fn, hipGetErrorString(le));
+        return SPAL_OK;
+    }
+};
+
+template <typename H>
+int rotate_form_of(H *a) {
+    std::lock_guard<std::mutex> lock(solve_handle(a)->mu);
+    return a->ops.eigsh_rotate ? a->ops.eigsh_rotate : 2;   // the faster one where both were measured
+}
+
+// x_dev: n x ldx by rows, or nullptr; theta, resid: k host values
+template <typename T, typename H>
+int eigsh_run(const char *fn, H *a, uint64_t k, int which, uint64_t ncv, const T *v0_dev, uint64_t seed, double tol,
+              uint64_t maxit, T *theta, T *resid, T *x_dev, uint64_t ldx, hipStream_t st, spal_eigsh_info *info) {
+    const uint64_t n = a->nrows, m = ncv;
+    SPAL_TRY(refuse_capture(fn, st, "the call polls and synchronises"));
+    SPAL_TRY(product_plan(solve_handle(a)));
+    const int form = rotate_form_of(a);
+
+    // the basis (m + 1 vectors), w, and for the out-of-place rotation a second basis, in one block
+    const uint64_t nvec = (m + 1) + 1 + (form == 1 ? m + 1 : 0);
+    const uint64_t stride = (n + 63) & ~(uint64_t)63;   // every vector on a 256-byte boundary at least
+    const uint64_t basis_bytes = nvec * stride * sizeof(T);
+    DevBuf vecs, parts, scal, ydev;
+    PinnedBuf hpin, ypin;
+    SolveFrame<GHead<T>> F;
+    EventSpans rev;
+    {
+        const hipError_t e = vecs.alloc((size_t)basis_bytes);
+        if (e == hipErrorOutOfMemory)
+            return fail(SPAL_ERR_OUT_OF_MEMORY, "%s: no memory for the basis: %llu vectors of %llu elements (%llu bytes)", fn,
+                        (unsigned long long)nvec, (unsigned long long)n, (unsigned long long)basis_bytes);
+        SPAL_HIP_TRY(e);
+    }
+    const uint64_t pe = scratch_elems(n);
+    SPAL_HIP_TRY(parts.alloc(std::max<uint64_t>(m, 2) * pe * sizeof(T)));
+    const size_t scal_bytes = sizeof(GHead<T>) + (2 * (m + 1) + m * m) * sizeof(T);
+    SPAL_HIP_TRY(scal.alloc(scal_bytes));
+    SPAL_HIP_TRY(ydev.alloc(m * kMaxNcv * sizeof(T)));
+    SPAL_HIP_TRY(hpin.alloc(m * m * sizeof(T)));
+    SPAL_HIP_TRY(ypin.alloc(m * kMaxNcv * sizeof(T)));
+    SPAL_TRY(F.create(st, 1));
+    SPAL_HIP_TRY(rev.create(1));
+
+    Run<T> R;
+    R.fn = fn;
+    R.a = solve_handle(a);
+    R.st = st;
+    R.n = n;
+    R.m = m;
+    R.c1 = tiles_of(n);
+    R.pe = pe;
+    R.stride = stride;
+    R.grid = first_level_grid(n);
+    R.form = form;
+    R.device = a->device;
+    R.s = scal.as<GHead<T>>();
+    R.h = reinterpret_cast<T *>(reinterpret_cast<char *>(scal.p) + sizeof(GHead<T>));
+    R.c = R.h + (m + 1);
+    R.H = R.c + (m + 1);
+    R.basis = vecs.as<T>();
+    R.w = R.basis + (m + 1) * stride;
+    R.alt = form == 1 ? R.w + stride : nullptr;
+    R.part = parts.as<T>();
+    R.y_dev = ydev.as<T>();
+    R.y_pin = ypin.as<T>();
+    R.V.v = R.basis;
+    R.V.stride = stride;
+    R.V.n = n;
+    R.V.tiles = tiles_of(n);
+
+    const GHead<T> *h = F.h;
+    const T *cols = hpin.as<T>();
+    SPAL_TRY(F.begin(scal.p, scal_bytes));
+    SPAL_TRY(R.start(v0_dev, seed));
+
+    std::vector<double> S(m * m, 0.0), Sw;
+    RitzPairs rp;
+    uint64_t keep = 0, restarts = 0, jj = 0, conv = 0;
+    int reason = 0;
+    double rotate_ms = 0.0;
+    bool rotating = false;
+    for (;;) {
+        for (uint64_t j = keep; j < m; ++j) SPAL_TRY(R.step((unsigned)j));
+        SPAL_HIP_TRY(hipMemcpyAsync(hpin.p, R.H, m * m * sizeof(T), hipMemcpyDeviceToHost, st));
+        SPAL_TRY(F.poll());   // one poll per phase: the head, and the columns with it
+        if (rotating) {
+            float ms = 0.f;
+            if (rev.span(0, &ms) == hipSuccess) rotate_ms += ms;
+            rotating = false;
+        }
+        if (h->done) {
+            reason = (int)h->reason;
+            break;
+        }
+        if (!h->cyc_end) return fail(SPAL_ERR_HIP, "%s: the device did not end a phase of %llu steps", fn, (unsigned long long)(m - keep));
+        jj = h->jj;
+        for (uint64_t j = keep; j < jj; ++j)
+            for (uint64_t t = 0; t <= j; ++t) S[t * m + j] = S[j * m + t] = (double)cols[j * m + t];   // exact
+        Sw.resize(jj * jj);
+        for (uint64_t r = 0; r < jj; ++r)
+            for (uint64_t q = 0; q < jj; ++q) Sw[r * jj + q] = S[r * m + q];
+        if (!eigsh_ritz(jj, Sw.data(), (double)h->hn, which, &rp)) {
+            reason = 2;
+            break;
+        }
+        conv = eigsh_converged(rp, std::min(k, jj), tol);
+        if (h->hn == T(0)) {   // the space is exhausted: the pairs are final
+            reason = jj >= k ? 0 : 3;
+            break;
+        }
+        if (conv == k) {
+            reason = 0;
+            break;
+        }
+        if (restarts == maxit) {
+            reason = 1;
+            break;
+        }
+        keep = eigsh_keep(k, m);
+        SPAL_HIP_TRY(hipEventRecord(rev.e[0], st));
+        if (form == 1) {
+            SPAL_TRY(R.rotate(rp, m, keep, RotOut<T>{R.alt, stride, 1}, R.v_at(m), R.alt + keep * stride));
+            std::swap(R.basis, R.alt);
+            R.V.v = R.basis;
+        } else {
+            SPAL_TRY(R.rotate(rp, m, keep, RotOut<T>{R.basis, stride, 1}, R.v_at(m), R.v_at(keep)));
+        }
+        SPAL_HIP_TRY(hipEventRecord(rev.e[1], st));
+        rotating = true;
+        KRYLOV_LAUNCH((phase_start<T>), 1, R.s, (unsigned)keep);
+        std::fill(S.begin(), S.end(), 0.0);
+        for (uint64_t i = 0; i < keep; ++i) S[i * m + i] = rp.theta[i];
+        ++restarts;
+    }
+    const uint64_t nk = reason == 2 ? 0 : std::min(k, jj);
+    if (nk && x_dev) SPAL_TRY(R.rotate(rp, jj, nk, RotOut<T>{x_dev, 1, ldx}, nullptr, nullptr));
+    float ms = 0.f;
+    SPAL_TRY(F.end(&ms));
+    for (uint64_t i = 0; i < nk; ++i) {
+        theta[i] = (T)rp.theta[i];
+        resid[i] = (T)rp.res[i];
+    }
+    info->restarts = restarts;
+    info->products = h->it;
+    info->converged = reason == 2 ? 0 : conv;
+    info->reason = reason;
+    info->solve_ms = (double)ms;
+    Record rec;
+    rec.k = k;
+    rec.which = which;
+    rec.ncv = ncv;
+    rec.keep = eigsh_keep(k, m);
+    rec.restarts = restarts;
+    rec.products = info->products;
+    rec.converged = info->converged;
+    rec.reason = reason;
+    rec.polls = F.polls;
+    rec.rotate = form;
+    rec.tile_rows = form == 1 ? 0 : rot_tile_rows<T>(m);
+    rec.basis_bytes = basis_bytes;
+    rec.rotate_ms = rotate_ms;
+    rec.solve_ms = info->solve_ms;
+    store_info(a, &OpState::eigsh_info, info_json(rec));
+    return SPAL_OK;
+}
+
+// Every refusal that needs no device.  What needs nothing of the handle comes first.
+template <typename T, typename H>
+int eigsh_check(const char *fn, H *a, uint64_t k, int which, uint64_t ncv, double tol, T *theta, T *resid, const T *x, uint64_t ldx,
+                spal_eigsh_info *info) {
+    if (!a || !theta || !resid || !info) return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: null argument", fn);
+    if (k == 0) return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: k = 0 (at least one eigenpair)", fn);
+    if (ncv <= k)
+        return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: ncv = %llu must be greater than k = %llu", fn, (unsigned long long)ncv,
+                    (unsigned long long)k);
+    if (ncv > kMaxNcv)
+        return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: ncv = %llu must be at most %llu (one column element per thread of the scalar workgroup)",
+                    fn, (unsigned long long)ncv, (unsigned long long)kMaxNcv);
+    if (which != SPAL_EIGSH_LA && which != SPAL_EIGSH_SA)
+        return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: which = %d must be 0 (LA) or 1 (SA)", fn, which);
+    if (!(tol >= 0.0) || !std::isfinite(tol)) return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: tol = %g must be finite and >= 0", fn, tol);
+    if (x && ldx < k)
+        return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: ldx = %llu is less than k = %llu", fn, (unsigned long long)ldx, (unsigned long long)k);
+    SPAL_TRY(check_dtype<T>(fn, a->elem_size));
+    if (a->nrows != a->ncols)
+        return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: the matrix is not square (%llu x %llu)", fn, (unsigned long long)a->nrows,
+                    (unsigned long long)a->ncols);
+    if (ncv > a->nrows)
+        return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: ncv = %llu exceeds the matrix's %llu rows", fn, (unsigned long long)ncv,
+                    (unsigned long long)a->nrows);
+    if (row_blocks(a)) return refuse_row_blocks(fn);
+    return SPAL_OK;
+}
+
+template <typename T, typename H>
+int eigsh_dev(const char *fn, H *a, uint64_t k, int which, uint64_t ncv, const T *v0_dev, uint64_t seed, double tol, uint64_t maxit,
+              T *theta, T *resid, T *x_dev, uint64_t ldx, void *stream, spal_eigsh_info *info) {
+    SPAL_TRY((eigsh_check<T, H>(fn, a, k, which, ncv, tol, theta, resid, x_dev, ldx, info)));
+    DeviceGuard guard(a->device);
+    if (guard.status != SPAL_OK) return guard.status;
+    return eigsh_run<T, H>(fn, a, k, which, ncv, v0_dev, seed, tol, maxit, theta, resid, x_dev, ldx, (hipStream_t)stream, info);
+}
+
+template <typename T, typename H>
+int eigsh_host(const char *fn, H *a, uint64_t k, int which, uint64_t ncv, const T *v0, uint64_t v0_len, uint64_t seed, double tol,
+               uint64_t maxit, T *theta, uint64_t theta_len, T *resid, uint64_t resid_len, T *x, uint64_t ldx, uint64_t x_rows,
+               spal_eigsh_info *info) {
+    SPAL_TRY((eigsh_check<T, H>(fn, a, k, which, ncv, tol, theta, resid, x, ldx, info)));
+    const uint64_t n = a->nrows;
+    if ((v0 && v0_len != n) || theta_len != k || resid_len != k || (x && x_rows != n))
+        return fail(SPAL_ERR_INVALID_ARGUMENT,
+                    "%s: v0.len() = %llu and X has %llu rows but the matrix has %llu rows; theta.len() = %llu and resid.len() = %llu but "
+                    "k = %llu", fn, (unsigned long long)v0_len, (unsigned long long)x_rows, (unsigned long long)n,
+                    (unsigned long long)theta_len, (unsigned long long)resid_len, (unsigned long long)k);
+    DeviceGuard guard(a->device);
+    if (guard.status != SPAL_OK) return guard.status;
+    size_t bytes = 0;
+    if (!bytes_of(n, k, sizeof(T), 1, &bytes))
+        return fail(SPAL_ERR_OUT_OF_MEMORY, "%s: no room for a block of %llu x %llu", fn, (unsigned long long)n, (unsigned long long)k);
+    const size_t row = (size_t)k * sizeof(T);
+    DevBuf dv, dx;
+    PooledStream ps;   // a stream of the call's own
+    if (v0) SPAL_HIP_TRY(dv.alloc(n * sizeof(T)));
+    if (x) SPAL_HIP_TRY(dx.alloc(bytes));
+    SPAL_HIP_TRY(stream_acquire(&ps.s));
+    if (v0) SPAL_HIP_TRY(hipMemcpyAsync(dv.p, v0, n * sizeof(T), hipMemcpyHostToDevice, ps.s));
+    SPAL_TRY((eigsh_run<T, H>(fn, a, k, which, ncv, v0 ? (const T *)dv.p : nullptr, seed, tol, maxit, theta, resid,
+                              x ? dx.as<T>() : nullptr, k, ps.s, info)));
+    // the columns the call produced, and only those: reason 2 leaves X as it was, reason 3 has `converged` = jj < k pairs
+    const uint64_t got = info->reason == 2 ? 0 : info->reason == 3 ? info->converged : k;
+    if (x && got) {
+        SPAL_HIP_TRY(hipMemcpy2DAsync(x, (size_t)ldx * sizeof(T), dx.p, row, (size_t)got * sizeof(T), n, hipMemcpyDeviceToHost, ps.s));
+        SPAL_HIP_TRY(hipStreamSynchronize(ps.s));
+    }
+    return SPAL_OK;
+}
+
+}  // namespace
+
+int eigsh_option(spal_csr *a, const char *key, int64_t value, OpState &s, int *status) {
+    if (strcmp(key, "eigsh_rotate")) return 0;
+    if (value < 0 || value > 2) {
+        *status = fail(SPAL_ERR_INVALID_ARGUMENT, "eigsh_rotate must be 0 (automatic), 1 (batched passes) or 2 (LDS row tiles)");
+        return 1;
+    }
+    std::lock_guard<std::mutex> lock(a->mu);
+    s.eigsh_rotate = (int)value;
+    *status = SPAL_OK;
+    return 1;
+}
+
+int eigsh_describe_append(char *buf, size_t buf_len, const OpState &s, spal_csr *solve) {
+    return info_describe_append(buf, buf_len, s, solve, "eigsh", &OpState::eigsh_info);
+}
+
+}  // namespace spal
+
+using namespace spal;
+
+extern "C" {
+
+int spal_eigsh_jacobi(uint64_t m, const double *s, double *theta, double *y, uint64_t *sweeps) {
+    if (!s || !theta || !y) return fail(SPAL_ERR_INVALID_ARGUMENT, "spal_eigsh_jacobi: null argument");
+    if (m == 0 || m > kMaxNcv)
+        return fail(SPAL_ERR_INVALID_ARGUMENT, "spal_eigsh_jacobi: m = %llu must be 1 .. %llu", (unsigned long long)m,
+                    (unsigned long long)kMaxNcv);
+    std::vector<double> w(s, s + m * m);
+    for (uint64_t i = 0; i < m; ++i)
+        for (uint64_t j = 0; j < m; ++j)
+            if (!std::isfinite(w[i * m + j]) || w[i * m + j] != w[j * m + i])
+                return fail(SPAL_ERR_INVALID_ARGUMENT, "spal_eigsh_jacobi: S[%llu, %llu] is not finite or S is not symmetric",
+                            (unsigned long long)i, (unsigned long long)j);
+    const unsigned n = eigsh_jacobi(m, w.data(), y);
+    for (uint64_t i = 0; i < m; ++i) theta[i] = w[i * m + i];
+    if (sweeps) *sweeps = n;
+    return SPAL_OK;
+}
+
+#define SPAL_EIGSH_ENTRIES(kind, sfx, T)                                                                               \
+    int spal_##kind##_eigsh_##sfx(spal_##kind##_t a, uint64_t k, int which, uint64_t ncv, const T *v0, uint64_t v0_len, \
+                                  uint64_t seed, double tol, uint64_t maxit, T *theta, uint64_t theta_len, T *resid,   \
+                                  uint64_t resid_len, T *x, uint64_t ldx, uint64_t x_rows, spal_eigsh_info *info) {    \
+        return eigsh_host<T, spal_##kind>("spal_" #kind "_eigsh", a, k, which, ncv, v0, v0_len, seed, tol, maxit,      \
+                                          theta, theta_len, resid, resid_len, x, ldx, x_rows, info);                   \
+    }                                                                                                                  \
+    int spal_##kind##_eigsh_dev_##sfx(spal_##kind##_t a, uint64_t k, int which, uint64_t ncv, const T *v0_dev,         \
+                                      uint64_t seed, double tol, uint64_t maxit, T *theta, T *resid, T *x_dev,         \
+                                      uint64_t ldx, void *stream, spal_eigsh_info *info) {                             \
+        return eigsh_dev<T, spal_##kind>("spal_" #kind "_eigsh_dev", a, k, which, ncv, v0_dev, seed, tol, maxit,       \
+                                         theta, resid, x_dev, ldx, stream, info);                                      \
+    }
+SPAL_EIGSH_ENTRIES(csr, f64, double)
+SPAL_EIGSH_ENTRIES(csr, f32, float)
+SPAL_EIGSH_ENTRIES(csc, f64, double)
+SPAL_EIGSH_ENTRIES(csc, f32, float)
+#undef SPAL_EIGSH_ENTRIES
+
+}  // extern "C"

@@ -31,49 +31,8 @@
 namespace spal {
 namespace {
 
-constexpr int kDotBatch = 8;          // basis vectors per batch of mdot / mupdate / combine ("dot_batch")
-
-// (GHead, GBlock, block_elems and the three scalar steps are in gmres_kernels.hpp, shared with spal_gmres_block.hip.)
-
-// The basis and one of its passes.
-template <typename T>
-struct Basis {
-    const T *v;        // v_k at v + k * stride
-    uint64_t stride, n, tiles;
-};
-
-// thread t's four elements of a tile; the padding is +0.0
-template <typename T>
-__device__ __forceinline__ void load4(const T *p, uint64_t i, uint64_t n, T (&out)[4]) {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) out[k] = i + (uint64_t)k * kThreads < n ? p[i + (uint64_t)k * kThreads] : T(0);
-}
-
-// tile_sum for kDotBatch independent sums at once: the same operand order for each, three barriers for all
-template <typename T>
-__device__ __forceinline__ void tile_sum_batch(T (&a)[kDotBatch], T (*lds)[kThreads]) {
-    const unsigned t = threadIdx.x;
-#pragma unroll
-    for (int b = 0; b < kDotBatch; ++b) lds[b][t] = a[b];
-    __syncthreads();
-    if (t < 128) {
-#pragma unroll
-        for (int b = 0; b < kDotBatch; ++b) {
-            a[b] = lds[b][t] + lds[b][t + 128];      // h = 128
-            if (t >= 64) lds[b][t] = a[b];
-        }
-    }
-    __syncthreads();
-    if (t < 64) {
-#pragma unroll
-        for (int b = 0; b < kDotBatch; ++b) {
-            a[b] = a[b] + lds[b][t + 64];            // h = 64
-#pragma unroll
-            for (int h = 32; h >= 1; h >>= 1) a[b] = a[b] + __shfl_down(a[b], h, 64);
-        }
-    }
-    __syncthreads();
-}
+// (GHead, GBlock, block_elems and the three scalar steps are in gmres_kernels.hpp, shared with spal_gmres_block.hip; so
+// are kDotBatch, Basis, load4, tile_sum_batch, scale, mdot, mfinish and mupdate, shared with spal_eigsh.hip.)
 
 // ---- the head of a cycle --------------------------------------------------------------------------------------------
 // r = b - q;  first levels of rr = dot(r, r) and bb = dot(b, b)
@@ -115,96 +74,6 @@ __global__ __launch_bounds__(kThreads) void cycle_start(GBlock<T> B, T *part0, T
     const T rr = upper_levels<T>(part0, c1, lds);
     const T bb = upper_levels<T>(part1, c1, lds);
     if (threadIdx.x == 0) cycle_start_scalars<T>(B, rr, bb, tol2, maxit);
-}
-
-// dst = src / beta (step < 0: v_0, in place) or dst = src / hn (v_{step + 1} = w / hn, after step's scalars)
-template <typename T>
-__global__ __launch_bounds__(kThreads) void scale(const GHead<T> *s, const T *src, T *dst, int step, uint64_t n) {
-    if (s->done != 0) return;
-    if (step >= 0 && s->jj != (unsigned)step + 1) return;
-    const T d = step < 0 ? s->beta : s->hn;
-    for (uint64_t i = (uint64_t)blockIdx.x * kThreads + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kThreads) dst[i] = src[i] / d;
-}
-
-// ---- the orthogonalisation ------------------------------------------------------------------------------------------
-// part[k * pe + tile] = the tile's sum of v_k . w for k = 0 .. j
-template <typename T>
-__global__ __launch_bounds__(kThreads) void mdot(const GHead<T> *s, Basis<T> V, unsigned j, const T *w, T *part, uint64_t pe) {
-    __shared__ T lds[kDotBatch][kThreads];
-    if (!at_step(s, j)) return;
-    const unsigned nk = j + 1;
-    for (uint64_t tile = blockIdx.x; tile < V.tiles; tile += gridDim.x) {
-        const uint64_t i = tile * kTile + threadIdx.x;
-        T wv[4];
-        load4<T>(w, i, V.n, wv);
-        for (unsigned k0 = 0; k0 < nk; k0 += kDotBatch) {
-            T v[kDotBatch][4];
-#pragma unroll
-            for (int b = 0; b < kDotBatch; ++b) {   // every load of the batch before the first product
-                if (k0 + b < nk) {
-                    load4<T>(V.v + (uint64_t)(k0 + b) * V.stride, i, V.n, v[b]);
-                } else {
-                    v[b][0] = v[b][1] = v[b][2] = v[b][3] = T(0);
-                }
-            }
-            T a[kDotBatch];
-#pragma unroll
-            for (int b = 0; b < kDotBatch; ++b)
-                a[b] = ((v[b][0] * wv[0]) + (v[b][2] * wv[2])) + ((v[b][1] * wv[1]) + (v[b][3] * wv[3]));   // h = 512, 256
-            tile_sum_batch<T>(a, lds);
-            if (threadIdx.x == 0) {
-#pragma unroll
-                for (int b = 0; b < kDotBatch; ++b)
-                    if (k0 + b < nk) part[(uint64_t)(k0 + b) * pe + tile] = a[b];
-            }
-        }
-    }
-}
-
-// workgroup k: dst[k] = the upper levels of dot k
-template <typename T>
-__global__ __launch_bounds__(kThreads) void mfinish(const GHead<T> *s, unsigned j, T *part, uint64_t pe, uint64_t c1, T *dst) {
-    __shared__ T lds[kThreads];
-    if (!at_step(s, j)) return;
-    const T d = upper_levels<T>(part + (uint64_t)blockIdx.x * pe, c1, lds);
-    if (threadIdx.x == 0) dst[blockIdx.x] = d;
-}
-
-// w[i] = (..((w[i] - (f[0] * v_0[i])) - (f[1] * v_1[i])) ..) - (f[j] * v_j[i]);  DOT: part0 = the first level of dot(w, w)
-template <typename T, bool DOT>
-__global__ __launch_bounds__(kThreads) void mupdate(const GHead<T> *s, Basis<T> V, unsigned j, const T *f, T *w, T *part0) {
-    __shared__ T lds[kThreads];
-    if (!at_step(s, j)) return;
-    const unsigned nk = j + 1;
-    for (uint64_t tile = blockIdx.x; tile < V.tiles; tile += gridDim.x) {
-        const uint64_t i = tile * kTile + threadIdx.x;
-        T wv[4];
-        load4<T>(w, i, V.n, wv);
-        for (unsigned k0 = 0; k0 < nk; k0 += kDotBatch) {
-            T v[kDotBatch][4];
-#pragma unroll
-            for (int b = 0; b < kDotBatch; ++b)
-                if (k0 + b < nk) load4<T>(V.v + (uint64_t)(k0 + b) * V.stride, i, V.n, v[b]);
-#pragma unroll
-            for (int b = 0; b < kDotBatch; ++b) {
-                if (k0 + b < nk) {
-                    const T fk = f[k0 + b];
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) wv[k] = wv[k] - (fk * v[b][k]);
-                }
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            if (i + (uint64_t)k * kThreads < V.n) w[i + (uint64_t)k * kThreads] = wv[k];
-        if (DOT) {
-            T p[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) p[k] = i + (uint64_t)k * kThreads < V.n ? wv[k] * wv[k] : T(0);
-            const T sum = tile_sum<T>(p[0], p[1], p[2], p[3], lds);
-            if (threadIdx.x == 0) part0[tile] = sum;
-        }
-    }
 }
 
 // ww = dot(w, w);  h += c;  hn;  the rotations;  g;  est;  the end of the cycle;  jj, it

@@ -1,5 +1,5 @@
 // spal_ops.hpp -- the host layer the sparse operations share: spal_spgemm.hip, spal_spadd.hip,
-// spal_spmm.hip, spal_trsv.hip, spal_trsv_sweep.hip, spal_trsm.hip, spal_ilu.hip, spal_ilu_sweep.hip, spal_krylov.hip, spal_krylov_block.hip, spal_gmres.hip, spal_gmres_block.hip, spal_colour.hip and spal_amg.hip keep their kernels, their driver, their option's validation and their
+// spal_spmm.hip, spal_trsv.hip, spal_trsv_sweep.hip, spal_trsm.hip, spal_ilu.hip, spal_ilu_sweep.hip, spal_krylov.hip, spal_krylov_block.hip, spal_gmres.hip, spal_gmres_block.hip, spal_eigsh.hip, spal_colour.hip and spal_amg.hip keep their kernels, their driver, their option's validation and their
 // info JSON; what surrounds a launch the same way in each of them is here, once.  (Not installed.)
 #pragma once
 
@@ -194,12 +194,13 @@ int trsm_option(spal_csr *a, const char *key, int64_t value, int *status);    //
 int ilu_option(spal_csr *a, const char *key, int64_t value, int *status);     // "ilu_wide_work"
 int krylov_option(spal_csr *a, const char *key, int64_t value, OpState &s, int *status);   // "krylov_check_every"
 int krylov_block_option(spal_csr *a, const char *key, int64_t value, OpState &s, int *status);   // "krylov_tile"
+int eigsh_option(spal_csr *a, const char *key, int64_t value, OpState &s, int *status);   // "eigsh_rotate"
 inline int ops_set_option(OpState &s, spal_csr *solve, const char *key, int64_t value, int *status) {
     return spgemm_option(key, value, s, status) || spadd_option(key, value, s, status) ||
            spmm_option(key, value, s, status) || trsv_option(solve, key, value, status) ||
            trsv_sweep_option(solve, key, value, status) || trsm_option(solve, key, value, status) ||
            ilu_option(solve, key, value, status) || krylov_option(solve, key, value, s, status) ||
-           krylov_block_option(solve, key, value, s, status);
+           krylov_block_option(solve, key, value, s, status) || eigsh_option(solve, key, value, s, status);
 }
 
 // (describe_append itself is host code: spal_host.cpp, declared in spal_internal.hpp)
@@ -218,6 +219,8 @@ int krylov_block_describe_append(char *buf, size_t buf_len, const OpState &s, sp
 int gmres_describe_append(char *buf, size_t buf_len, const OpState &s, spal_csr *solve);
 // the "gmres_block" object of a handle spal_*_gmres_block_* ran with as A (spal_gmres_block.hip; the same lock)
 int gmres_block_describe_append(char *buf, size_t buf_len, const OpState &s, spal_csr *solve);
+// the "eigsh" object of a handle spal_*_eigsh_* ran with as A (spal_eigsh.hip; the same lock)
+int eigsh_describe_append(char *buf, size_t buf_len, const OpState &s, spal_csr *solve);
 inline int ops_describe_append(char *buf, size_t buf_len, const OpState &s, spal_csr *solve) {
     SPAL_TRY(describe_append(buf, buf_len, "spgemm", s.spgemm_info));   // a product of spal_*_mul: how it was built
     SPAL_TRY(describe_append(buf, buf_len, "spadd", s.spadd_info));     // a result of spal_*_add / _sub / _neg
@@ -231,6 +234,7 @@ inline int ops_describe_append(char *buf, size_t buf_len, const OpState &s, spal
     SPAL_TRY(krylov_block_describe_append(buf, buf_len, s, solve));     // spal_*_krylov_block_* ran with it as A: the last call
     SPAL_TRY(gmres_describe_append(buf, buf_len, s, solve));            // spal_*_gmres_* ran with it as A: the last call
     SPAL_TRY(gmres_block_describe_append(buf, buf_len, s, solve));      // spal_*_gmres_block_* ran with it as A: the last call
+    SPAL_TRY(eigsh_describe_append(buf, buf_len, s, solve));            // spal_*_eigsh_* ran with it as A: the last call
     return describe_append(buf, buf_len, "ordering", s.ordering_info);  // a result of spal_*_permute / _multicolour
 }
 

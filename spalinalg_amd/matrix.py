@@ -93,9 +93,56 @@ def _krylov_method(method) -> int:
     return int(method)
 
 
+def _eigsh_info(c, resid) -> "EigshInfo":
+    return EigshInfo(restarts=int(c.restarts), products=int(c.products), converged=int(c.converged), reason=int(c.reason),
+                     resid=np.array(resid, copy=True), solve_ms=float(c.solve_ms))
+
+
 def _krylov_info(c: _KrylovInfoC) -> KrylovInfo:
     return KrylovInfo(iterations=int(c.iterations), reason=int(c.reason), residual_sq=float(c.residual_sq),
                       rhs_sq=float(c.rhs_sq), solve_ms=float(c.solve_ms))
+
+
+class _EigshInfoC(C.Structure):
+    """spal_eigsh_info"""
+    _fields_ = [("restarts", C.c_uint64), ("products", C.c_uint64), ("converged", C.c_uint64), ("reason", C.c_int),
+                ("solve_ms", C.c_double)]
+
+
+class EigshInfo(dict):
+    """What eigsh() reports: restarts, products (with A), converged (leading pairs whose estimate met tol), reason (0
+    converged or the space exhausted with at least k pairs, 1 maxit restarts, 2 not finite, 3 exhausted with fewer than
+    k pairs), resid (the estimates |hn * Y[m-1, i]| of the pairs returned), solve_ms."""
+    __getattr__ = dict.__getitem__
+
+
+_EIGSH_WHICH = {"LA": 0, "SA": 1}
+
+
+def _eigsh_which(which) -> int:
+    if isinstance(which, str):
+        if which.upper() not in _EIGSH_WHICH:
+            raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT, f"eigsh: which = {which!r} must be 'LA' or 'SA'")
+        return _EIGSH_WHICH[which.upper()]
+    return int(which)
+
+
+def _eigsh_args(n: int, ncols: int, k, ncv, tol, dtype):
+    """(k, ncv, tol) resolved and refused as the library does, before anything touches a device."""
+    k = int(k)
+    if n != ncols:
+        raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT, f"eigsh: the matrix is not square ({n} x {ncols})")
+    ncv = min(n, max(2 * k + 1, 20)) if ncv is None else int(ncv)
+    if k < 1:
+        raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT, "eigsh: k = 0 (at least one eigenpair)")
+    if ncv <= k:
+        raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT, f"eigsh: ncv = {ncv} must be greater than k = {k} (a matrix of {n} rows)")
+    if ncv > 256 or ncv > n:
+        raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT, f"eigsh: ncv = {ncv} must be at most 256 and at most the matrix's {n} rows")
+    tol = float(tol)
+    if not (tol >= 0.0) or not np.isfinite(tol):
+        raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT, f"eigsh: tol = {tol} must be finite and >= 0")
+    return k, ncv, tol if tol > 0.0 else float(np.finfo(dtype).eps)
 
 
 def dot(a, b):
@@ -621,6 +668,52 @@ class _DeviceMatrix:
                                                               vp(b_ptr), u64(ldb), vp(x_ptr), u64(ldx), u64(restart),
                                                               C.c_double(tol), u64(maxit), _stream_ptr(stream), infos))
         return [_krylov_info(c) for c in infos[:int(k)]]
+
+    def eigsh(self, k: int = 6, which="LA", ncv=None, v0=None, seed: int = 0, tol: float = 0, maxit: int = 1000,
+              return_eigenvectors: bool = True):
+        """The k largest (which="LA") or smallest ("SA") eigenvalues of this symmetric matrix and their vectors, by
+        thick-restart Lanczos with full orthogonalisation on the device (spal_*_eigsh_*); symmetry is not
+        checked.  Returns (theta, X, info): theta in the order of `which` (LA descending, SA ascending), X of shape
+        (n, pairs) or None, info an EigshInfo.  ncv=None is min(n, max(2k + 1, 20)); tol=0 is the dtype's machine
+        epsilon; a pair counts as converged when its estimate is <= tol * max|theta|.  v0=None is the text's start
+        vector from `seed`.  Bit for bit the text of include/spal.h.  An eigenvalue of multiplicity > 1 is returned
+        ONCE: a single-vector Lanczos iteration sees one direction of its eigenspace.  pairs = k unless the space was
+        exhausted earlier (reason 3) or a value was not finite (reason 2: no pair)."""
+        n, ncols, _ = self.shape()
+        k, ncv, tol = _eigsh_args(n, ncols, k, ncv, tol, self.dtype)
+        w = _eigsh_which(which)
+        if v0 is not None:
+            v0 = np.ascontiguousarray(v0, dtype=self.dtype)
+            if v0.shape != (n,):
+                raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT, f"eigsh: v0 has shape {v0.shape} but the matrix has {n} rows")
+        theta = np.zeros(k, dtype=self.dtype)
+        resid = np.zeros(k, dtype=self.dtype)
+        X = np.zeros((n, k), dtype=self.dtype) if return_eigenvectors else None
+        info = _EigshInfoC()
+        check(self._fn(f"eigsh_{_sfx(self.dtype)}")(self._h, u64(k), C.c_int(w), u64(ncv), None if v0 is None else _p(v0),
+                                                    u64(0 if v0 is None else n), u64(seed), C.c_double(tol), u64(maxit),
+                                                    _p(theta), u64(k), _p(resid), u64(k), None if X is None else _p(X),
+                                                    u64(k), u64(n), C.byref(info)))
+        pairs = 0 if info.reason == 2 else int(info.converged) if info.reason == 3 else k
+        out = _eigsh_info(info, resid[:pairs])
+        return theta[:pairs], (None if X is None else X[:, :pairs]), out
+
+    def eigsh_dev(self, k: int, theta, resid, x_ptr: int, ldx: int, which="LA", ncv=None, v0_ptr: int = 0, seed: int = 0,
+                  tol: float = 0, maxit: int = 1000, stream=None):
+        """Device pointers: v0_ptr (0: the text's start vector) and x_ptr (0: values only; else n x k row-major with
+        leading dimension ldx); theta and resid are host arrays of k values of the handle's dtype, written in place.
+        The call polls, so it synchronises `stream`.  Returns the EigshInfo."""
+        n, ncols, _ = self.shape()
+        k, ncv, tol = _eigsh_args(n, ncols, k, ncv, tol, self.dtype)
+        for a in (theta, resid):
+            if not isinstance(a, np.ndarray) or a.dtype != self.dtype or a.shape != (k,) or not a.flags.c_contiguous:
+                raise TypeError(f"theta and resid must be contiguous arrays of {k} {self.dtype} values")
+        info = _EigshInfoC()
+        check(self._fn(f"eigsh_dev_{_sfx(self.dtype)}")(self._h, u64(k), C.c_int(_eigsh_which(which)), u64(ncv), vp(v0_ptr or None),
+                                                        u64(seed), C.c_double(tol), u64(maxit), _p(theta), _p(resid),
+                                                        vp(x_ptr or None), u64(ldx), _stream_ptr(stream), C.byref(info)))
+        pairs = 0 if info.reason == 2 else int(info.converged) if info.reason == 3 else k
+        return _eigsh_info(info, resid[:pairs])
 
     def amg(self, seed: int = 0, max_levels: int = 16, coarse_rows: int = 64, nu: int = 2, coarse_sweeps: int = 16,
             cycle: str = "v", omega: float = 2.0 / 3.0, alpha: float = 1.0, stream=None) -> Amg:
@@ -1252,6 +1345,22 @@ class _Compressed:
                 raise TypeError("precond_sweeps needs M, the factor it is an option of")
             M.device(device).set_option("trsv_sweeps", int(precond_sweeps))
         return self.device(device).gmres(b, None if M is None else M.device(device), x0, int(restart), tol, maxit)
+
+    def eigsh(self, k: int = 6, which="LA", ncv=None, v0=None, seed: int = 0, tol: float = 0, maxit: int = 1000,
+              return_eigenvectors: bool = True, device: int = 0):
+        """theta, X, info = a.eigsh(k): the k largest (which="LA") or smallest ("SA") eigenvalues of this SYMMETRIC
+        matrix and their vectors, by thick-restart Lanczos with full orthogonalisation on the device (DESIGN 3.25);
+        symmetry is not checked, as with CG.  theta comes in the order of `which`, X has shape (n, k) (None with
+        return_eigenvectors=False), info is an EigshInfo (restarts, products, converged, reason, resid, solve_ms).
+        ncv=None means min(n, max(2k + 1, 20)) basis vectors, at most 256; tol=0 means the dtype's machine epsilon, as
+        scipy does; maxit bounds the restarts.  An eigenvalue of multiplicity > 1 is returned ONCE (a single-vector
+        Lanczos iteration sees one direction of its eigenspace).  Refused on a matrix that is not square or has fewer
+        than ncv rows before anything is copied to a device.  Bit for bit the text of include/spal.h."""
+        _eigsh_args(self._nrows, self._ncols, k, ncv, tol, self.dtype)
+        _eigsh_which(which)
+        if v0 is not None and np.shape(v0) != (self._nrows,):
+            raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT, f"eigsh: v0 has shape {np.shape(v0)} but the matrix has {self._nrows} rows")
+        return self.device(device).eigsh(k, which, ncv, v0, seed, tol, maxit, return_eigenvectors)
 
     def gmres_block(self, B, M=None, X0=None, restart: int = 30, tol: float = 1e-8, maxit: int = 1000, device: int = 0,
                     precond_sweeps=None):

@@ -15,7 +15,8 @@ OUT = os.path.join(ROOT, "rust_shim", "src", "ffi.rs")
 
 SCALARS = {"int": "c_int", "uint64_t": "u64", "uint32_t": "u32", "int64_t": "i64", "size_t": "usize", "double": "f64",
            "float": "f32", "void": "c_void", "char": "c_char"}
-STRUCTS = {"spal_krylov_info": "spal_krylov_info", "spal_amg_params": "spal_amg_params"}   # plain structs passed by pointer, declared in render()
+STRUCTS = {"spal_krylov_info": "spal_krylov_info", "spal_amg_params": "spal_amg_params",
+           "spal_eigsh_info": "spal_eigsh_info"}   # plain structs passed by pointer, declared in render()
 HANDLES = {"spal_csr_t": "spal_csr", "spal_csc_t": "spal_csc", "spal_coo_t": "spal_coo", "spal_mg_t": "spal_mg",
            "spal_mg_csr_t": "spal_mg_csr", "spal_amg_t": "spal_amg"}
 
@@ -88,6 +89,12 @@ def render(fns) -> str:
               '#[repr(C)] #[derive(Clone, Copy, Debug, Default)]',
               'pub struct spal_amg_params { pub seed: u64, pub max_levels: u64, pub coarse_rows: u64, pub nu: u64, '
               'pub coarse_sweeps: u64, pub gamma: u64, pub omega: f64, pub alpha: f64 }',
+              'pub const SPAL_EIGSH_LA: c_int = 0;',
+              'pub const SPAL_EIGSH_SA: c_int = 1;',
+              '/// What spal_*_eigsh_* report: reason 0 converged, 1 maxit restarts, 2 not finite, 3 space exhausted below k.',
+              '#[repr(C)] #[derive(Clone, Copy, Debug, Default)]',
+              'pub struct spal_eigsh_info { pub restarts: u64, pub products: u64, pub converged: u64, pub reason: c_int, '
+              'pub solve_ms: f64 }',
               '',
               '#[link(name = "spal_hip")]',
               'extern "C" {']
