@@ -11,6 +11,7 @@ import pytest
 
 import spalinalg_amd as sp
 from spalinalg_amd import _ffi
+from tests import amg_cases as ac
 from tests import amg_ref as ar
 from tests import trsv_ref as tr
 
@@ -92,7 +93,7 @@ def _check_hierarchy(g, h):
         tr.assert_same_bits(m.values(), lv.values)
         if lv.agg is not None:
             assert np.array_equal(g.aggregates(l), lv.agg.astype(np.uint64))
-            assert d["rounds"][l] >= 1
+            assert d["rounds"][l] == ac.level_rounds(lv, h.p["seed"])    # the round rule decides every vertex's round
     with pytest.raises(sp.Panic, match="no coarser level"):
         g.aggregates(len(h.levels) - 1)
 

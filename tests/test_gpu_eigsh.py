@@ -67,12 +67,12 @@ def make(kind, mat):
 
 
 def check(a, n, dtype, k, which, ncv, tol, maxit, v0=None, seed=0, jacobi_fn=None, rotate=None):
-    """One call against the text on the device's own product; returns (got, ref)."""
+    """One call against the text on the device's own product (tol = 0 is the machine epsilon); returns (got, ref)."""
     dev = a.device()
     if rotate is not None:
         dev.set_option("eigsh_rotate", rotate)
     theta, X, info = a.eigsh(k, which, ncv, v0, seed, tol, maxit)
-    ref = er.eigsh(lambda v: dev.spmv(v), n, dtype, k, which, ncv, tol, maxit, v0, seed, jacobi_fn)
+    ref = er.eigsh(lambda v: dev.spmv(v), n, dtype, k, which, ncv, tol or float(np.finfo(dtype).eps), maxit, v0, seed, jacobi_fn)
     assert (info.restarts, info.products, info.converged, info.reason) == \
         (ref["restarts"], ref["products"], ref["converged"], ref["reason"])
     tr.assert_same_bits(theta, ref["theta"])
