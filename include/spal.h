@@ -1010,8 +1010,9 @@ int spal_csc_gmres_block_dev_f32(spal_csc_t a, spal_csc_t m, uint64_t k, const f
  * byte count.  Nothing leaks on any failure.
  * describe() on `a` gains "eigsh" after a call: {k, which, ncv, keep, restarts, products, converged, reason, polls,
  * rotate, rotate_tile_rows, basis_bytes, rotate_ms = device time of the restarts' rotations, solve_ms}.
- * Not provided: interior eigenvalues and shift-invert, which = LM / BE, nonsymmetric matrices, a generalised problem,
- * block Lanczos, several GPUs, capture into a graph. */
+ * Not provided: interior eigenvalues and shift-invert (clustered EXTREME values have the polynomial filter of the next
+ * section, spal_*_eigsh_filtered_*), which = LM / BE, nonsymmetric matrices, a generalised problem, block Lanczos,
+ * several GPUs, capture into a graph. */
 enum { SPAL_EIGSH_LA = 0, SPAL_EIGSH_SA = 1 };
 typedef struct spal_eigsh_info {
     uint64_t restarts, products, converged;
@@ -1043,6 +1044,143 @@ int spal_csc_eigsh_dev_f64(spal_csc_t a, uint64_t k, int which, uint64_t ncv, co
 int spal_csc_eigsh_dev_f32(spal_csc_t a, uint64_t k, int which, uint64_t ncv, const float *v0_dev, uint64_t seed,
                            double tol, uint64_t maxit, float *theta, float *resid, float *x_dev, uint64_t ldx,
                            void *stream, spal_eigsh_info *info);
+
+/* ---- the Chebyshev filter: cheb_apply, gershgorin, and eigsh on a polynomial of A ---------------------------
+ * Not in the reference.  Where the wanted eigenvalues are clustered, eigsh above spends its time in Gram-Schmidt passes
+ * and restarts; Lanczos on p(A), a scaled Chebyshev polynomial that is small on the unwanted part of the spectrum and
+ * grows monotonically towards the wanted end, needs 10-30 times fewer of both for about as many products.
+ * The contract is again a sequential text the device returns bit for bit, f32 and f64.  Vectors and a step's scalars
+ * are T; every product is rounded before the sum or difference it enters (no FMA); dot is the dot above.
+ *
+ *   THE PRODUCT ORDER IS THE FILTER'S OWN and does not depend on the handle's plan:
+ *     rowsum(y, r) = (..((+0.0 + (a[p]*y[col[p]])) + (a[p+1]*y[col[p+1]])) ..)
+ *   over the stored entries of row r of the CSR form in storage order; a CSC handle uses its CSR twin (a row's entries
+ *   in column order).
+ *
+ *   coefficients (host doubles; T(.) is the one conversion):
+ *     c = (lo+hi)/2;  e = (hi-lo)/2;  s_1 = e/(a0 - c);  s_i = 1/(2/s_1 - s_{i-1})
+ *     alpha_1 = T(s_1/e);  beta_1 = 0;   alpha_i = T((2*s_i)/e);  beta_i = T(s_{i-1}*s_i);   cT = T(c)
+ *   a0 lies outside [lo, hi]: p(a0) = 1, |s_i| < 1, and nothing overflows in f32 at any degree.
+ *
+ *   cheb_apply(x; d, lo, hi, a0) = t_d:
+ *     t_0 = x
+ *     t_1[r] = alpha_1 * (rowsum(t_0, r) - (cT*t_0[r]))
+ *     t_i[r] = (alpha_i * (rowsum(t_{i-1}, r) - (cT*t_{i-1}[r]))) - (beta_i*t_{i-2}[r])          i = 2..d
+ *
+ *   gershgorin(A) = (glo, ghi), in double (f32 values convert exactly): per row r, d = the stored entry (r, r), 0 where
+ *   there is none; s = the |off-diagonal entries| added in storage order onto +0.0; glo = min_r (d - s), ghi =
+ *   max_r (d + s): enclosures of the spectrum of a symmetric A up to double rounding.  If any row's d - s or d + s is
+ *   not finite, both are NaN.
+ *
+ *   filtered eigsh = the text of eigsh above with five changes (tol == 0 stands for 256 * eps(T) here: a TRUE residual
+ *   does not reach eps * scale; the floors the text reaches are in DESIGN 3.26):
+ *   1. (glo, ghi) = gershgorin(A); not finite: stop 2 at once.  a0 = ghi for LA, glo for SA; scale = max(|glo|, |ghi|).
+ *   2. The interval.  Given [lo, hi]: refused unless lo < hi and a0 lies strictly outside it on the wanted side (a0 > hi
+ *      for LA, a0 < lo for SA).  Automatic: the eigsh text above UNCHANGED -- its product is the handle's -- with
+ *      maxit = min(warmup, maxit); theta, resid and X are written by it.  A reason other than 1: that result is the
+ *      call's (warm_restarts = restarts, warm_products = products; lo = hi = 0).  Else cut = double(theta[k-1]);
+ *      unless glo < cut < ghi the warm-up's result is again the call's; else [lo, hi] = [glo, cut] for LA, [cut, ghi]
+ *      for SA, and the iteration starts again from the same v0 with restarts = products = 0.
+ *   3. In step(j), w = cheb_apply(v_j; d, lo, hi, a0) and products += d.  The pairs (mu, Y) of the projected problem are
+ *      ordered DESCENDING for both values of `which`: p is largest at the wanted end.
+ *   4. At the end of a phase (after the test of S for values that are not finite), ROTATE FIRST, so that a restart
+ *      goes on from the same columns:  kc = min(keep, jj);  x_c[i] = the sum of eigsh's rotation over t < jj, c < kc.
+ *      Then for c < nk = min(k, jj):
+ *        q_c[r] = rowsum(x_c, r);  products += 1;   th_c = dot(x_c, q_c)
+ *        r_c[i] = q_c[i] - (th_c*x_c[i]);           res_c = sqrt(dot(r_c, r_c))
+ *      any th_c or res_c not finite: stop 2.  converged = the number of leading c < nk with double(res_c) <= tol * scale.
+ *      exhausted (hn == 0, jj <= m): stop 0 if jj >= k, else stop 3 with converged = nk, as in eigsh.
+ *      converged == k: stop 0;  restarts == maxit: stop 1;  else new v_c = x_c for c < keep, new v_keep = the old v_m,
+ *      S = diag(mu_0 .. mu_{keep-1}), restarts += 1.
+ *   5. stop 0, 1, 3:  theta[c] = th_c, resid[c] = res_c, X[:, c] = x_c for c < nk.  stop 2: nothing is written (after an
+ *      automatic warm-up theta, resid and X hold the warm-up's values); converged = 0.
+ *   th_c is the Rayleigh quotient's numerator: x_c has norm 1 up to rounding (eigsh's consequence 3).
+ * WHAT THE BITS DO NOT DEPEND ON: the handle's plan (after the warm-up), the chunk of the step kernel ("cheb_chunk"),
+ * "eigsh_rotate", ldx, the stream.
+ *
+ * On the device (spal_cheb.hip) one recurrence step is one launch of a streaming kernel: a workgroup owns
+ * 256 consecutive rows, walks their contiguous entries in chunks, its lanes load values and columns coalesced, gather
+ * the vector and write the rounded products to LDS, and each row's thread adds its own products in order, its
+ * accumulator carried across chunks -- any row length gives the text's bits.  The d launches are ordered by the stream,
+ * the coefficients are kernel arguments, nothing waits and nothing is polled inside a step.  The same kernel without
+ * the epilogue gives q_c.  A filtered phase polls twice: the columns of S, then the nk true pairs.  Option
+ * "cheb_chunk" on `a`: entries per chunk, 0 = 16 KiB of products (2048 f64, 4096 f32), else 256, 512, 1024, 2048 or 4096.
+ *
+ * spal_*_cheb_apply_*: x and out are n values (host forms: x_len = out_len = nrows); the _dev forms enqueue `degree`
+ * launches on `stream`, take one work vector from the stream's scratch (degree >= 2) and do not synchronise.
+ * SPAL_ERR_INVALID_ARGUMENT before any device work: null a, x or out; degree outside 1 .. 256; lo, hi or a0 not finite;
+ * lo >= hi; a0 inside [lo, hi]; a dtype mismatch; a matrix that is not square; out overlapping x; wrong lengths.
+ * spal_*_gershgorin: square matrices with at least one row; synchronises.
+ * spal_*_eigsh_filtered_*: eigsh's arguments plus degree (1 .. 256), automatic (1: lo and hi are ignored; 0: the given
+ * interval) and warmup (restarts of the warm-up; the bindings default to 5).  Refused before any device work as eigsh is,
+ * and for a degree outside 1 .. 256, automatic outside {0, 1}, a given interval that is not finite or has lo >= hi, a
+ * null info; the place of a0 needs Gershgorin's bounds and is refused right after them.  Refused on a capturing stream
+ * and on row-block handles as eigsh is.  The recurrence's work vector joins eigsh's one allocation per call.
+ * info: eigsh's fields for the filtered iteration (products = d per step + 1 per true residual), or the warm-up's when
+ * its result is the call's; warm_restarts, warm_products; lo, hi (0, 0: no filtered phase ran), a0, degree; solve_ms
+ * covers both.  describe() on `a` gains "eigsh_filter" after a call: {k, which, ncv, keep, degree, interval, lo, hi,
+ * a0, glo, ghi, warm_restarts, warm_products, restarts, products, converged, reason, polls, chunk, basis_bytes,
+ * residual_ms, solve_ms}; an automatic call's warm-up also rewrites "eigsh", being an eigsh call.
+ * Not provided: shift-invert, interior eigenvalues, an interval updated between restarts (it breaks the Lanczos
+ * relation), Chebyshev as a smoother or preconditioner (cheb_apply is the piece for it), several GPUs, graph capture. */
+typedef struct spal_eigsh_filter_info {
+    uint64_t restarts, products, converged;
+    int reason;
+    double solve_ms;
+    uint64_t warm_restarts, warm_products;
+    double lo, hi, a0;
+    uint64_t degree;
+} spal_eigsh_filter_info;
+int spal_csr_cheb_apply_f64(spal_csr_t a, const double *x, uint64_t x_len, double *out, uint64_t out_len, uint64_t degree,
+                            double lo, double hi, double a0);
+int spal_csr_cheb_apply_f32(spal_csr_t a, const float *x, uint64_t x_len, float *out, uint64_t out_len, uint64_t degree,
+                            double lo, double hi, double a0);
+int spal_csr_cheb_apply_dev_f64(spal_csr_t a, const double *x_dev, double *out_dev, uint64_t degree, double lo, double hi,
+                                double a0, void *stream);                          /* not synchronised */
+int spal_csr_cheb_apply_dev_f32(spal_csr_t a, const float *x_dev, float *out_dev, uint64_t degree, double lo, double hi,
+                                double a0, void *stream);
+int spal_csc_cheb_apply_f64(spal_csc_t a, const double *x, uint64_t x_len, double *out, uint64_t out_len, uint64_t degree,
+                            double lo, double hi, double a0);
+int spal_csc_cheb_apply_f32(spal_csc_t a, const float *x, uint64_t x_len, float *out, uint64_t out_len, uint64_t degree,
+                            double lo, double hi, double a0);
+int spal_csc_cheb_apply_dev_f64(spal_csc_t a, const double *x_dev, double *out_dev, uint64_t degree, double lo, double hi,
+                                double a0, void *stream);
+int spal_csc_cheb_apply_dev_f32(spal_csc_t a, const float *x_dev, float *out_dev, uint64_t degree, double lo, double hi,
+                                double a0, void *stream);
+int spal_csr_gershgorin(spal_csr_t a, double *glo, double *ghi);                    /* synchronises */
+int spal_csc_gershgorin(spal_csc_t a, double *glo, double *ghi);
+int spal_csr_eigsh_filtered_f64(spal_csr_t a, uint64_t k, int which, uint64_t ncv, const double *v0, uint64_t v0_len,
+                                uint64_t seed, double tol, uint64_t maxit, uint64_t degree, int automatic, double lo,
+                                double hi, uint64_t warmup, double *theta, uint64_t theta_len, double *resid,
+                                uint64_t resid_len, double *x, uint64_t ldx, uint64_t x_rows, spal_eigsh_filter_info *info);
+int spal_csr_eigsh_filtered_f32(spal_csr_t a, uint64_t k, int which, uint64_t ncv, const float *v0, uint64_t v0_len,
+                                uint64_t seed, double tol, uint64_t maxit, uint64_t degree, int automatic, double lo,
+                                double hi, uint64_t warmup, float *theta, uint64_t theta_len, float *resid,
+                                uint64_t resid_len, float *x, uint64_t ldx, uint64_t x_rows, spal_eigsh_filter_info *info);
+int spal_csr_eigsh_filtered_dev_f64(spal_csr_t a, uint64_t k, int which, uint64_t ncv, const double *v0_dev, uint64_t seed,
+                                    double tol, uint64_t maxit, uint64_t degree, int automatic, double lo, double hi,
+                                    uint64_t warmup, double *theta, double *resid, double *x_dev, uint64_t ldx,
+                                    void *stream, spal_eigsh_filter_info *info);   /* synchronises */
+int spal_csr_eigsh_filtered_dev_f32(spal_csr_t a, uint64_t k, int which, uint64_t ncv, const float *v0_dev, uint64_t seed,
+                                    double tol, uint64_t maxit, uint64_t degree, int automatic, double lo, double hi,
+                                    uint64_t warmup, float *theta, float *resid, float *x_dev, uint64_t ldx, void *stream,
+                                    spal_eigsh_filter_info *info);
+int spal_csc_eigsh_filtered_f64(spal_csc_t a, uint64_t k, int which, uint64_t ncv, const double *v0, uint64_t v0_len,
+                                uint64_t seed, double tol, uint64_t maxit, uint64_t degree, int automatic, double lo,
+                                double hi, uint64_t warmup, double *theta, uint64_t theta_len, double *resid,
+                                uint64_t resid_len, double *x, uint64_t ldx, uint64_t x_rows, spal_eigsh_filter_info *info);
+int spal_csc_eigsh_filtered_f32(spal_csc_t a, uint64_t k, int which, uint64_t ncv, const float *v0, uint64_t v0_len,
+                                uint64_t seed, double tol, uint64_t maxit, uint64_t degree, int automatic, double lo,
+                                double hi, uint64_t warmup, float *theta, uint64_t theta_len, float *resid,
+                                uint64_t resid_len, float *x, uint64_t ldx, uint64_t x_rows, spal_eigsh_filter_info *info);
+int spal_csc_eigsh_filtered_dev_f64(spal_csc_t a, uint64_t k, int which, uint64_t ncv, const double *v0_dev, uint64_t seed,
+                                    double tol, uint64_t maxit, uint64_t degree, int automatic, double lo, double hi,
+                                    uint64_t warmup, double *theta, double *resid, double *x_dev, uint64_t ldx,
+                                    void *stream, spal_eigsh_filter_info *info);
+int spal_csc_eigsh_filtered_dev_f32(spal_csc_t a, uint64_t k, int which, uint64_t ncv, const float *v0_dev, uint64_t seed,
+                                    double tol, uint64_t maxit, uint64_t degree, int automatic, double lo, double hi,
+                                    uint64_t warmup, float *theta, float *resid, float *x_dev, uint64_t ldx, void *stream,
+                                    spal_eigsh_filter_info *info);
 
 /* ---- multicolour reordering: greedy colouring and B = P A P^T -------------------------------------------
  * Not in the reference.  An exact triangular solve costs one launch step per level; numbering the rows

@@ -20,6 +20,7 @@
 //                                                        (include/spal.h, spal_*_krylov_*, spal_*_krylov_block_*, spal_dot_*)
 //   a.gmres(b, restart, M, x0, tol, maxit)               not in the reference: restarted GMRES (spal_*_gmres_*)
 //   a.eigsh(k, which, ncv, v0, seed, tol, maxit)         not in the reference: extreme eigenpairs of a symmetric matrix (spal_*_eigsh_*)
+//   a.eigsh_filtered(k, degree, ...), a.cheb_apply(x, degree, lo, hi, a0), a.gershgorin()    not in the reference: the Chebyshev filter (spal_*_eigsh_filtered_*, _cheb_apply_*, _gershgorin)
 //   a.gmres_block(B, k, restart, M, X0, tol, maxit)      not in the reference: GMRES on k right-hand sides (spal_*_gmres_block_*)
 //   a.colour(seed), a.permute(perm), a.multicolour(seed), p.ordering(), p.to_order(v), p.from_order(v),
 //   colour_greedy(n, rowptr, colind, seed), perm_from_colours(colours)
@@ -82,6 +83,8 @@ template <> struct Abi<double> {
     static constexpr auto csr_gmres = spal_csr_gmres_f64;
     static constexpr auto csr_gmres_block = spal_csr_gmres_block_f64;
     static constexpr auto csr_eigsh = spal_csr_eigsh_f64;
+    static constexpr auto csr_eigsh_filtered = spal_csr_eigsh_filtered_f64;
+    static constexpr auto csr_cheb_apply = spal_csr_cheb_apply_f64;
     static constexpr auto csr_permute_vec = spal_csr_permute_vec_f64;
     static constexpr auto dot = spal_dot_f64;
     static constexpr auto csr_download = spal_csr_download_f64;
@@ -97,6 +100,8 @@ template <> struct Abi<double> {
     static constexpr auto csc_gmres = spal_csc_gmres_f64;
     static constexpr auto csc_gmres_block = spal_csc_gmres_block_f64;
     static constexpr auto csc_eigsh = spal_csc_eigsh_f64;
+    static constexpr auto csc_eigsh_filtered = spal_csc_eigsh_filtered_f64;
+    static constexpr auto csc_cheb_apply = spal_csc_cheb_apply_f64;
     static constexpr auto csc_permute_vec = spal_csc_permute_vec_f64;
     static constexpr auto coo_to_csr = spal_coo_to_csr_f64;
     static constexpr auto coo_to_csc = spal_coo_to_csc_f64;
@@ -115,6 +120,8 @@ template <> struct Abi<float> {
     static constexpr auto csr_gmres = spal_csr_gmres_f32;
     static constexpr auto csr_gmres_block = spal_csr_gmres_block_f32;
     static constexpr auto csr_eigsh = spal_csr_eigsh_f32;
+    static constexpr auto csr_eigsh_filtered = spal_csr_eigsh_filtered_f32;
+    static constexpr auto csr_cheb_apply = spal_csr_cheb_apply_f32;
     static constexpr auto csr_permute_vec = spal_csr_permute_vec_f32;
     static constexpr auto dot = spal_dot_f32;
     static constexpr auto csr_download = spal_csr_download_f32;
@@ -130,6 +137,8 @@ template <> struct Abi<float> {
     static constexpr auto csc_gmres = spal_csc_gmres_f32;
     static constexpr auto csc_gmres_block = spal_csc_gmres_block_f32;
     static constexpr auto csc_eigsh = spal_csc_eigsh_f32;
+    static constexpr auto csc_eigsh_filtered = spal_csc_eigsh_filtered_f32;
+    static constexpr auto csc_cheb_apply = spal_csc_cheb_apply_f32;
     static constexpr auto csc_permute_vec = spal_csc_permute_vec_f32;
     static constexpr auto coo_to_csr = spal_coo_to_csr_f32;
     static constexpr auto coo_to_csc = spal_coo_to_csc_f32;
@@ -170,6 +179,15 @@ struct Eigenpairs {
     usize pairs, restarts, products, converged;
     int reason;   // 0 converged (or the space exhausted with >= k pairs), 1 maxit restarts, 2 not finite, 3 exhausted below k
     double solve_ms;
+};
+
+// What eigsh_filtered adds to eigsh's result: resid holds TRUE residual norms; the warm-up's counts (automatic interval),
+// the interval the polynomial is small on (0, 0: the warm-up's result was returned), a0 and the degree.
+template <typename T>
+struct FilteredEigenpairs {
+    Eigenpairs<T> pairs;
+    usize warm_restarts, warm_products, degree;
+    double lo, hi, a0;
 };
 
 // What solve_block returns: X row-major (element (i, j) at i * k + j) and one record per column, as Solution holds one.
@@ -536,6 +554,69 @@ class CsrMatrix {
         return e;
     }
 
+    // eigsh on a Chebyshev polynomial of A of `degree` (1 .. 256), for CLUSTERED extreme eigenvalues (spal_csr_eigsh_filtered_*,
+    // include/spal.h): automatic = true takes the interval to damp from `warmup` restarts of eigsh's own iteration, false
+    // uses [lo, hi].  Convergence is decided on true residuals against tol * max(|glo|, |ghi|); tol = 0: 256 epsilons.
+    FilteredEigenpairs<T> eigsh_filtered(usize k, usize degree, Which which = Which::LA, usize ncv = 0, bool automatic = true,
+                                         double lo = 0.0, double hi = 0.0, usize warmup = 5, const std::vector<T> &v0 = {},
+                                         usize seed = 0, double tol = 0.0, usize maxit = 1000, bool vectors = true) const {
+        if (nrows_ != ncols_)
+            throw Panic(SPAL_ERR_INVALID_ARGUMENT, "eigsh_filtered: the matrix is not square (" + std::to_string(nrows_) + " x " +
+                                                       std::to_string(ncols_) + ")");
+        if (ncv == 0) ncv = std::min<usize>(nrows_, std::max<usize>(2 * k + 1, 20));
+        if (k == 0 || ncv <= k || ncv > 256 || ncv > nrows_)
+            throw Panic(SPAL_ERR_INVALID_ARGUMENT, "eigsh_filtered: k = " + std::to_string(k) + " and ncv = " + std::to_string(ncv) +
+                                                       " must satisfy 0 < k < ncv <= min(256, " + std::to_string(nrows_) + ")");
+        if (degree < 1 || degree > 256)
+            throw Panic(SPAL_ERR_INVALID_ARGUMENT, "eigsh_filtered: degree = " + std::to_string(degree) + " must be 1 .. 256");
+        if (!v0.empty() && v0.size() != nrows_)
+            throw Panic(SPAL_ERR_INVALID_ARGUMENT, "eigsh_filtered: v0.len() = " + std::to_string(v0.size()) + " but the matrix has " +
+                                                       std::to_string(nrows_) + " rows");
+        FilteredEigenpairs<T> f{{std::vector<T>(k, T(0)), std::vector<T>(k, T(0)), std::vector<T>(vectors ? nrows_ * k : 0, T(0)), 0, 0, 0, 0, 0, 0.0},
+                                0, 0, degree, 0.0, 0.0, 0.0};
+        Eigenpairs<T> &e = f.pairs;
+        spal_eigsh_filter_info info;
+        detail::check(detail::Abi<T>::csr_eigsh_filtered(device_handle(), k, static_cast<int>(which), ncv, v0.empty() ? nullptr : v0.data(),
+                                                          v0.size(), seed, tol, maxit, degree, automatic ? 1 : 0, lo, hi, warmup,
+                                                          e.theta.data(), k, e.resid.data(), k, vectors ? e.x.data() : nullptr, k,
+                                                          nrows_, &info));
+        e.pairs = info.reason == 2 ? 0 : info.reason == 3 ? info.converged : k;
+        e.restarts = info.restarts;
+        e.products = info.products;
+        e.converged = info.converged;
+        e.reason = info.reason;
+        e.solve_ms = info.solve_ms;
+        f.warm_restarts = info.warm_restarts;
+        f.warm_products = info.warm_products;
+        f.lo = info.lo;
+        f.hi = info.hi;
+        f.a0 = info.a0;
+        if (e.pairs < k) {   // pack the columns that were written
+            std::vector<T> x(vectors ? nrows_ * e.pairs : 0);
+            for (usize i = 0; vectors && i < nrows_; ++i)
+                for (usize j = 0; j < e.pairs; ++j) x[i * e.pairs + j] = e.x[i * k + j];
+            e.x.swap(x);
+            e.theta.resize(e.pairs);
+            e.resid.resize(e.pairs);
+        }
+        return f;
+    }
+
+    // t_d = p(A) x: the Chebyshev polynomial of `degree` that is small on [lo, hi] and 1 at a0, outside the interval
+    // (spal_csr_cheb_apply_*): the text of include/spal.h bit for bit.  Panics as the library refuses.
+    std::vector<T> cheb_apply(const std::vector<T> &x, usize degree, double lo, double hi, double a0) const {
+        std::vector<T> out(nrows_, T(0));
+        detail::check(detail::Abi<T>::csr_cheb_apply(device_handle(), x.data(), x.size(), out.data(), out.size(), degree, lo, hi, a0));
+        return out;
+    }
+
+    // (glo, ghi): Gershgorin's enclosure of the spectrum, in double (spal_csr_gershgorin)
+    std::pair<double, double> gershgorin() const {
+        double lo = 0.0, hi = 0.0;
+        detail::check(spal_csr_gershgorin(device_handle(), &lo, &hi));
+        return {lo, hi};
+    }
+
     // X with A X = B for a ROW-MAJOR block of k right-hand sides by restarted GMRES(restart): k independent iterations in
     // lockstep on shared launches, with cycles common to the block (spal_csr_gmres_block_*, include/spal.h).  Column j
     // of the result and columns[j] are bit for bit gmres()'s text on column j of B, whatever k and the other columns are.
@@ -891,6 +972,69 @@ class CscMatrix {
             e.resid.resize(e.pairs);
         }
         return e;
+    }
+
+    // eigsh on a Chebyshev polynomial of A of `degree` (1 .. 256), for CLUSTERED extreme eigenvalues (spal_csc_eigsh_filtered_*,
+    // include/spal.h): automatic = true takes the interval to damp from `warmup` restarts of eigsh's own iteration, false
+    // uses [lo, hi].  Convergence is decided on true residuals against tol * max(|glo|, |ghi|); tol = 0: 256 epsilons.
+    FilteredEigenpairs<T> eigsh_filtered(usize k, usize degree, Which which = Which::LA, usize ncv = 0, bool automatic = true,
+                                         double lo = 0.0, double hi = 0.0, usize warmup = 5, const std::vector<T> &v0 = {},
+                                         usize seed = 0, double tol = 0.0, usize maxit = 1000, bool vectors = true) const {
+        if (nrows_ != ncols_)
+            throw Panic(SPAL_ERR_INVALID_ARGUMENT, "eigsh_filtered: the matrix is not square (" + std::to_string(nrows_) + " x " +
+                                                       std::to_string(ncols_) + ")");
+        if (ncv == 0) ncv = std::min<usize>(nrows_, std::max<usize>(2 * k + 1, 20));
+        if (k == 0 || ncv <= k || ncv > 256 || ncv > nrows_)
+            throw Panic(SPAL_ERR_INVALID_ARGUMENT, "eigsh_filtered: k = " + std::to_string(k) + " and ncv = " + std::to_string(ncv) +
+                                                       " must satisfy 0 < k < ncv <= min(256, " + std::to_string(nrows_) + ")");
+        if (degree < 1 || degree > 256)
+            throw Panic(SPAL_ERR_INVALID_ARGUMENT, "eigsh_filtered: degree = " + std::to_string(degree) + " must be 1 .. 256");
+        if (!v0.empty() && v0.size() != nrows_)
+            throw Panic(SPAL_ERR_INVALID_ARGUMENT, "eigsh_filtered: v0.len() = " + std::to_string(v0.size()) + " but the matrix has " +
+                                                       std::to_string(nrows_) + " rows");
+        FilteredEigenpairs<T> f{{std::vector<T>(k, T(0)), std::vector<T>(k, T(0)), std::vector<T>(vectors ? nrows_ * k : 0, T(0)), 0, 0, 0, 0, 0, 0.0},
+                                0, 0, degree, 0.0, 0.0, 0.0};
+        Eigenpairs<T> &e = f.pairs;
+        spal_eigsh_filter_info info;
+        detail::check(detail::Abi<T>::csc_eigsh_filtered(device_handle(), k, static_cast<int>(which), ncv, v0.empty() ? nullptr : v0.data(),
+                                                          v0.size(), seed, tol, maxit, degree, automatic ? 1 : 0, lo, hi, warmup,
+                                                          e.theta.data(), k, e.resid.data(), k, vectors ? e.x.data() : nullptr, k,
+                                                          nrows_, &info));
+        e.pairs = info.reason == 2 ? 0 : info.reason == 3 ? info.converged : k;
+        e.restarts = info.restarts;
+        e.products = info.products;
+        e.converged = info.converged;
+        e.reason = info.reason;
+        e.solve_ms = info.solve_ms;
+        f.warm_restarts = info.warm_restarts;
+        f.warm_products = info.warm_products;
+        f.lo = info.lo;
+        f.hi = info.hi;
+        f.a0 = info.a0;
+        if (e.pairs < k) {   // pack the columns that were written
+            std::vector<T> x(vectors ? nrows_ * e.pairs : 0);
+            for (usize i = 0; vectors && i < nrows_; ++i)
+                for (usize j = 0; j < e.pairs; ++j) x[i * e.pairs + j] = e.x[i * k + j];
+            e.x.swap(x);
+            e.theta.resize(e.pairs);
+            e.resid.resize(e.pairs);
+        }
+        return f;
+    }
+
+    // t_d = p(A) x: the Chebyshev polynomial of `degree` that is small on [lo, hi] and 1 at a0, outside the interval
+    // (spal_csc_cheb_apply_*): the text of include/spal.h bit for bit.  Panics as the library refuses.
+    std::vector<T> cheb_apply(const std::vector<T> &x, usize degree, double lo, double hi, double a0) const {
+        std::vector<T> out(nrows_, T(0));
+        detail::check(detail::Abi<T>::csc_cheb_apply(device_handle(), x.data(), x.size(), out.data(), out.size(), degree, lo, hi, a0));
+        return out;
+    }
+
+    // (glo, ghi): Gershgorin's enclosure of the spectrum, in double (spal_csc_gershgorin)
+    std::pair<double, double> gershgorin() const {
+        double lo = 0.0, hi = 0.0;
+        detail::check(spal_csc_gershgorin(device_handle(), &lo, &hi));
+        return {lo, hi};
     }
 
     // X with A X = B for a ROW-MAJOR block of k right-hand sides by restarted GMRES(restart): k independent iterations in

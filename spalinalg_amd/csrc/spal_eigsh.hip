@@ -24,6 +24,11 @@
 // SMALL on purpose (about 16 KiB): with tiles of 64 KiB, two workgroups per CU, the same kernel took 0.173 ms where it now
 // takes 0.102 -- staging and the sums alternate inside a workgroup, and only other workgroups on the CU overlap them.  The
 // Ritz vectors at the end are the same kernel writing into x (row-major, leading dimension ldx).
+//
+// FILTERED EIGSH (spal_*_eigsh_filtered_*) is the same Run on p(A): the step's product becomes the Chebyshev
+// recurrence of spal_cheb.hip (d launches, stream-ordered), and a phase ends with the rotation FIRST and then the true
+// residuals of the leading columns (one rowsum launch, two dots per column) behind a second poll.  The plain driver and
+// its bits are untouched: the filter is a host-side branch in Run::step.
 #include "eigsh_host.hpp"
 #include "gmres_kernels.hpp"
 
@@ -253,6 +258,9 @@ struct Run {
     T *basis = nullptr, *alt = nullptr, *w = nullptr, *part = nullptr, *y_dev = nullptr, *y_pin = nullptr;
     Basis<T> V;
     unsigned tile_rows = 0;
+    const ChebCoeffs<T> *filter = nullptr;   // filtered eigsh: w = cheb_apply(v_j) through `work`
+    T *work = nullptr;
+    unsigned chunk = 0;
 
     T *v_at(uint64_t k) const { return basis + k * stride; }
 
@@ -268,7 +276,8 @@ struct Run {
         return SPAL_OK;
     }
     int step(unsigned j) {
-        SPAL_TRY(mul_dev(a, (const T *)v_at(j), w, st));
+        if (filter) SPAL_TRY(cheb_apply_enqueue<T>(fn, a, *filter, (const T *)v_at(j), w, work, chunk, st));
+        else SPAL_TRY(mul_dev(a, (const T *)v_at(j), w, st));
         KRYLOV_LAUNCH((mdot<T>), grid, s, V, j, w, part, pe);
         KRYLOV_LAUNCH((mfinish<T>), j + 1, s, j, part, pe, c1, h);
         KRYLOV_LAUNCH((mupdate<T, false>), grid, s, V, j, h, w, part);
@@ -540,6 +549,397 @@ int eigsh_host(const char *fn, H *a, uint64_t k, int which, uint64_t ncv, const 
     return SPAL_OK;
 }
 
+// ---- filtered eigsh ---------------------------------------------------------------------------------------
+// Lanczos on p(A), a Chebyshev polynomial of A (spal_cheb.hip): the step above with w = cheb_apply(v_j).  The projected
+// problem then holds values of p, so convergence is decided on TRUE residuals with A: at a phase end the host rotates
+// first (the columns are the restart's), then per leading column one product, two dots and two scalar launches, and a
+// second poll brings the nk pairs (th, res) down.
+
+template <typename T>
+struct TruePair {
+    T th, res;
+};
+
+// part[tile] = the tile's sum of a[i] * b[i]
+template <typename T>
+__global__ __launch_bounds__(kThreads) void dot_tiles(const T *a, const T *b, T *part, uint64_t n, uint64_t tiles) {
+    __shared__ T lds[kThreads];
+    for (uint64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+        const uint64_t i = tile * kTile + threadIdx.x;
+        T x[4], y[4];
+        load4<T>(a, i, n, x);
+        load4<T>(b, i, n, y);
+        const T s = tile_sum<T>(x[0] * y[0], x[1] * y[1], x[2] * y[2], x[3] * y[3], lds);
+        if (threadIdx.x == 0) part[tile] = s;
+    }
+}
+
+// part[tile] = the tile's sum of r[i] * r[i], r[i] = q[i] - (th * x[i]); the padding is +0.0 whatever th is
+template <typename T>
+__global__ __launch_bounds__(kThreads) void resid_tiles(const T *q, const T *x, const T *th_p, T *part, uint64_t n, uint64_t tiles) {
+    __shared__ T lds[kThreads];
+    const T th = *th_p;
+    for (uint64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+        const uint64_t i = tile * kTile + threadIdx.x;
+        T p[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const uint64_t e = i + (uint64_t)k * kThreads;
+            T r = T(0);
+            if (e < n) r = q[e] - (th * x[e]);
+            p[k] = r * r;
+        }
+        const T s = tile_sum<T>(p[0], p[1], p[2], p[3], lds);
+        if (threadIdx.x == 0) part[tile] = s;
+    }
+}
+
+// *dst = the dot whose first level is in part (ROOT: its square root)
+template <typename T, bool ROOT>
+__global__ __launch_bounds__(kThreads) void finish_dot(T *part, uint64_t c1, T *dst) {
+    __shared__ T lds[kThreads];
+    const T d = upper_levels<T>(part, c1, lds);
+    if (threadIdx.x == 0) *dst = ROOT ? sqrt(d) : d;
+}
+
+// x[i * ldx + c] = v_c[i] for c < nc
+template <typename T>
+__global__ __launch_bounds__(kThreads) void columns_out(Basis<T> V, unsigned nc, T *x, uint64_t ldx) {
+    for (uint64_t i = (uint64_t)blockIdx.x * kThreads + threadIdx.x; i < V.n; i += (uint64_t)gridDim.x * kThreads)
+        for (unsigned c = 0; c < nc; ++c) x[i * ldx + c] = V.v[(uint64_t)c * V.stride + i];
+}
+
+struct FilterRecord {
+    Record r;
+    uint64_t degree = 0, warm_restarts = 0, warm_products = 0, chunk = 0;
+    int automatic = 0;
+    double lo = 0.0, hi = 0.0, a0 = 0.0, glo = 0.0, ghi = 0.0, residual_ms = 0.0;
+};
+// a double as JSON: a value that is not finite (Gershgorin's bounds of a matrix that holds one) is null
+std::string json_number(double v) {
+    if (!std::isfinite(v)) return "null";
+    char buf[40];
+    snprintf(buf, sizeof buf, "%.17g", v);
+    return buf;
+}
+std::string filter_json(const FilterRecord &f) {
+    char buf[1280];
+    const Record &r = f.r;
+    snprintf(buf, sizeof buf,
+             "{\"k\": %llu, \"which\": \"%s\", \"ncv\": %llu, \"keep\": %llu, \"degree\": %llu, \"interval\": \"%s\", \"lo\": %s, "
+             "\"hi\": %s, \"a0\": %s, \"glo\": %s, \"ghi\": %s, \"warm_restarts\": %llu, \"warm_products\": %llu, "
+             "\"restarts\": %llu, \"products\": %llu, \"converged\": %llu, \"reason\": %d, \"polls\": %llu, \"chunk\": %llu, "
+             "\"basis_bytes\": %llu, \"residual_ms\": %.4f, \"solve_ms\": %.4f}",
+             (unsigned long long)r.k, r.which == SPAL_EIGSH_LA ? "LA" : "SA", (unsigned long long)r.ncv, (unsigned long long)r.keep,
+             (unsigned long long)f.degree, f.automatic ? "auto" : "given", json_number(f.lo).c_str(), json_number(f.hi).c_str(),
+             json_number(f.a0).c_str(), json_number(f.glo).c_str(), json_number(f.ghi).c_str(),
+             (unsigned long long)f.warm_restarts, (unsigned long long)f.warm_products, (unsigned long long)r.restarts,
+             (unsigned long long)r.products, (unsigned long long)r.converged, r.reason, (unsigned long long)r.polls,
+             (unsigned long long)f.chunk, (unsigned long long)r.basis_bytes, f.residual_ms, r.solve_ms);
+    return buf;
+}
+
+template <typename H>
+unsigned cheb_chunk_of(H *a) {
+    std::lock_guard<std::mutex> lock(solve_handle(a)->mu);
+    return (unsigned)a->ops.cheb_chunk;
+}
+
+// The filtered phases on [lo, hi]; fi holds a0, degree and the warm-up's counts already.
+template <typename T, typename H>
+int filtered_phases(const char *fn, H *a, uint64_t k, int which, uint64_t ncv, const T *v0_dev, uint64_t seed, double tol_scale,
+                    uint64_t maxit, const ChebCoeffs<T> &coef, T *theta, T *resid, T *x_dev, uint64_t ldx, hipStream_t st,
+                    spal_eigsh_filter_info *fi, FilterRecord *rec) {
+    const uint64_t n = a->nrows, m = ncv, degree = coef.alpha.size();
+    const int form = rotate_form_of(a);
+    // the basis (m + 1 vectors), w, the recurrence's work vector, and for the out-of-place rotation a second basis
+    const uint64_t nvec = (m + 1) + 2 + (form == 1 ? m + 1 : 0);
+    const uint64_t stride = (n + 63) & ~(uint64_t)63;
+    const uint64_t basis_bytes = nvec * stride * sizeof(T);
+    DevBuf vecs, parts, scal, ydev;
+    PinnedBuf hpin, ypin, tpin;
+    SolveFrame<GHead<T>> F;
+    EventSpans rev;
+    {
+        const hipError_t e = vecs.alloc((size_t)basis_bytes);
+        if (e == hipErrorOutOfMemory)
+            return fail(SPAL_ERR_OUT_OF_MEMORY, "%s: no memory for the basis: %llu vectors of %llu elements (%llu bytes)", fn,
+                        (unsigned long long)nvec, (unsigned long long)n, (unsigned long long)basis_bytes);
+        SPAL_HIP_TRY(e);
+    }
+    const uint64_t pe = scratch_elems(n);
+    SPAL_HIP_TRY(parts.alloc(std::max<uint64_t>(m, 2) * pe * sizeof(T)));
+    // the scalars: the head, h, c, the columns, then the k true pairs
+    const size_t pair_off = sizeof(GHead<T>) + (2 * (m + 1) + m * m) * sizeof(T);
+    const size_t scal_bytes = pair_off + k * sizeof(TruePair<T>);
+    SPAL_HIP_TRY(scal.alloc(scal_bytes));
+    SPAL_HIP_TRY(ydev.alloc(m * kMaxNcv * sizeof(T)));
+    SPAL_HIP_TRY(hpin.alloc(m * m * sizeof(T)));
+    SPAL_HIP_TRY(ypin.alloc(m * kMaxNcv * sizeof(T)));
+    SPAL_HIP_TRY(tpin.alloc(k * sizeof(TruePair<T>)));
+    SPAL_TRY(F.create(st, 1));
+    SPAL_HIP_TRY(rev.create(1));
+
+    Run<T> R;
+    R.fn = fn;
+    R.a = solve_handle(a);
+    R.st = st;
+    R.n = n;
+    R.m = m;
+    R.c1 = tiles_of(n);
+    R.pe = pe;
+    R.stride = stride;
+    R.grid = first_level_grid(n);
+    R.form = form;
+    R.device = a->device;
+    R.s = scal.as<GHead<T>>();
+    R.h = reinterpret_cast<T *>(reinterpret_cast<char *>(scal.p) + sizeof(GHead<T>));
+    R.c = R.h + (m + 1);
+    R.H = R.c + (m + 1);
+    R.basis = vecs.as<T>();
+    R.w = R.basis + (m + 1) * stride;
+    R.work = R.w + stride;
+    R.alt = form == 1 ? R.work + stride : nullptr;
+    R.part = parts.as<T>();
+    R.y_dev = ydev.as<T>();
+    R.y_pin = ypin.as<T>();
+    R.V.v = R.basis;
+    R.V.stride = stride;
+    R.V.n = n;
+    R.V.tiles = tiles_of(n);
+    R.filter = &coef;
+    R.chunk = cheb_chunk_of(a);
+    TruePair<T> *pairs_dev = reinterpret_cast<TruePair<T> *>(reinterpret_cast<char *>(scal.p) + pair_off);
+    const TruePair<T> *pairs = tpin.as<TruePair<T>>();
+
+    const GHead<T> *h = F.h;
+    const T *cols = hpin.as<T>();
+    SPAL_TRY(F.begin(scal.p, scal_bytes));
+    SPAL_TRY(R.start(v0_dev, seed));
+
+    std::vector<double> S(m * m, 0.0), Sw;
+    RitzPairs rp;
+    uint64_t keep = 0, restarts = 0, jj = 0, conv = 0, nk = 0, true_products = 0, polls = 0;
+    int reason = 0;
+    double residual_ms = 0.0;
+    for (;;) {
+        for (uint64_t j = keep; j < m; ++j) SPAL_TRY(R.step((unsigned)j));
+        SPAL_HIP_TRY(hipMemcpyAsync(hpin.p, R.H, m * m * sizeof(T), hipMemcpyDeviceToHost, st));
+        SPAL_TRY(F.poll());   // the first poll of the phase: the head and the columns
+        if (h->done) {
+            reason = (int)h->reason;
+            break;
+        }
+        if (!h->cyc_end) return fail(SPAL_ERR_HIP, "%s: the device did not end a phase of %llu steps", fn, (unsigned long long)(m - keep));
+        jj = h->jj;
+        for (uint64_t j = keep; j < jj; ++j)
+            for (uint64_t t = 0; t <= j; ++t) S[t * m + j] = S[j * m + t] = (double)cols[j * m + t];   // exact
+        Sw.resize(jj * jj);
+        for (uint64_t r = 0; r < jj; ++r)
+            for (uint64_t q = 0; q < jj; ++q) Sw[r * jj + q] = S[r * m + q];
+        if (!eigsh_ritz(jj, Sw.data(), (double)h->hn, SPAL_EIGSH_LA, &rp)) {   // p is largest at the wanted end: descending
+            reason = 2;
+            break;
+        }
+        const bool exhausted = h->hn == T(0);
+        nk = std::min(k, jj);
+        const uint64_t kc = std::min(eigsh_keep(k, m), jj);
+        // rotate first: x_c = the new v_c, and a restart goes on from these columns
+        if (form == 1) {
+            SPAL_TRY(R.rotate(rp, jj, kc, RotOut<T>{R.alt, stride, 1}, exhausted ? nullptr : R.v_at(m), R.alt + kc * stride));
+            std::swap(R.basis, R.alt);
+            R.V.v = R.basis;
+        } else {
+            SPAL_TRY(R.rotate(rp, jj, kc, RotOut<T>{R.basis, stride, 1}, exhausted ? nullptr : R.v_at(m), R.v_at(kc)));
+        }
+        SPAL_HIP_TRY(hipEventRecord(rev.e[0], st));
+        for (uint64_t c = 0; c < nk; ++c) {
+            SPAL_TRY(cheb_rowsum_enqueue<T>(fn, R.a, (const T *)R.v_at(c), R.w, R.chunk, st));
+            KRYLOV_LAUNCH((dot_tiles<T>), R.grid, (const T *)R.v_at(c), (const T *)R.w, R.part, n, R.V.tiles);
+            KRYLOV_LAUNCH((finish_dot<T, false>), 1, R.part, R.c1, &pairs_dev[c].th);
+            KRYLOV_LAUNCH((resid_tiles<T>), R.grid, (const T *)R.w, (const T *)R.v_at(c), (const T *)&pairs_dev[c].th, R.part, n, R.V.tiles);
+            KRYLOV_LAUNCH((finish_dot<T, true>), 1, R.part, R.c1, &pairs_dev[c].res);
+        }
+        true_products += nk;
+        SPAL_HIP_TRY(hipEventRecord(rev.e[1], st));
+        SPAL_HIP_TRY(hipMemcpyAsync(tpin.p, pairs_dev, nk * sizeof(TruePair<T>), hipMemcpyDeviceToHost, st));
+        SPAL_HIP_TRY(hipStreamSynchronize(st));   // the second poll: the true pairs
+        ++polls;
+        {
+            float ms = 0.f;
+            if (rev.span(0, &ms) == hipSuccess) residual_ms += ms;
+        }
+        bool finite = true;
+        for (uint64_t c = 0; c < nk; ++c) finite = finite && std::isfinite((double)pairs[c].th) && std::isfinite((double)pairs[c].res);
+        if (!finite) {
+            reason = 2;
+            break;
+        }
+        conv = 0;
+        while (conv < nk && (double)pairs[conv].res <= tol_scale) ++conv;
+        if (exhausted) {   // the space is exhausted: the pairs are final
+            reason = jj >= k ? 0 : 3;
+            if (reason == 3) conv = nk;
+            break;
+        }
+        if (conv == k) {
+            reason = 0;
+            break;
+        }
+        if (restarts == maxit) {
+            reason = 1;
+            break;
+        }
+        keep = kc;
+        KRYLOV_LAUNCH((phase_start<T>), 1, R.s, (unsigned)keep);
+        std::fill(S.begin(), S.end(), 0.0);
+        for (uint64_t i = 0; i < keep; ++i) S[i * m + i] = rp.theta[i];
+        ++restarts;
+    }
+    if (reason == 2) nk = 0;
+    if (nk && x_dev) KRYLOV_LAUNCH((columns_out<T>), R.grid, R.V, (unsigned)nk, x_dev, ldx);
+    float ms = 0.f;
+    SPAL_TRY(F.end(&ms));
+    for (uint64_t i = 0; i < nk; ++i) {
+        theta[i] = pairs[i].th;
+        resid[i] = pairs[i].res;
+    }
+    fi->restarts = restarts;
+    fi->products = h->it * degree + true_products;
+    fi->converged = reason == 2 ? 0 : conv;
+    fi->reason = reason;
+    fi->solve_ms += (double)ms;
+    rec->r.keep = eigsh_keep(k, m);
+    rec->r.polls = F.polls + polls;
+    rec->r.basis_bytes = basis_bytes;
+    rec->chunk = R.chunk;
+    rec->residual_ms = residual_ms;
+    return SPAL_OK;
+}
+
+// x_dev: n x ldx by rows, or nullptr; theta, resid: k host values
+template <typename T, typename H>
+int eigsh_filtered_run(const char *fn, H *a, uint64_t k, int which, uint64_t ncv, const T *v0_dev, uint64_t seed, double tol,
+                       uint64_t maxit, uint64_t degree, int automatic, double lo, double hi, uint64_t warmup, T *theta, T *resid,
+                       T *x_dev, uint64_t ldx, hipStream_t st, spal_eigsh_filter_info *fi) {
+    SPAL_TRY(refuse_capture(fn, st, "the call polls and synchronises"));
+    SPAL_TRY(product_plan(solve_handle(a)));
+    *fi = spal_eigsh_filter_info{};
+    fi->degree = degree;
+    tol = cheb_tol<T>(tol);
+    double glo = 0.0, ghi = 0.0;
+    SPAL_TRY(gershgorin_run(fn, solve_handle(a), st, &glo, &ghi));
+    FilterRecord rec;
+    rec.degree = degree;
+    rec.automatic = automatic;
+    rec.glo = glo;
+    rec.ghi = ghi;
+    auto finish = [&]() {
+        rec.r.k = k;
+        rec.r.which = which;
+        rec.r.ncv = ncv;
+        rec.r.restarts = fi->restarts;
+        rec.r.products = fi->products;
+        rec.r.converged = fi->converged;
+        rec.r.reason = fi->reason;
+        rec.r.solve_ms = fi->solve_ms;
+        rec.lo = fi->lo;
+        rec.hi = fi->hi;
+        rec.a0 = fi->a0;
+        rec.warm_restarts = fi->warm_restarts;
+        rec.warm_products = fi->warm_products;
+        store_info(a, &OpState::eigsh_filter_info, filter_json(rec));
+        return SPAL_OK;
+    };
+    if (!std::isfinite(glo) || !std::isfinite(ghi)) {   // a value of the matrix is not finite
+        fi->a0 = (double)NAN;
+        fi->reason = 2;
+        return finish();
+    }
+    const double a0 = cheb_a0(which, glo, ghi);
+    fi->a0 = a0;
+    if (automatic) {
+        spal_eigsh_info warm;
+        SPAL_TRY((eigsh_run<T, H>(fn, a, k, which, ncv, v0_dev, seed, tol, std::min(warmup, maxit), theta, resid, x_dev, ldx, st, &warm)));
+        fi->warm_restarts = fi->restarts = warm.restarts;
+        fi->warm_products = fi->products = warm.products;
+        fi->converged = warm.converged;
+        fi->reason = warm.reason;
+        fi->solve_ms = warm.solve_ms;
+        if (warm.reason != 1) return finish();
+        if (!cheb_auto_interval(which, glo, ghi, (double)theta[k - 1], &lo, &hi)) return finish();
+    } else if (cheb_check(degree, lo, hi, a0) != CHEB_OK || !cheb_wanted_side(which, lo, hi, a0)) {
+        return fail(SPAL_ERR_INVALID_ARGUMENT,
+                    "%s: a0 = %.17g (Gershgorin's %s bound) must lie strictly %s the interval [%.17g, %.17g]", fn, a0,
+                    which == SPAL_EIGSH_LA ? "upper" : "lower", which == SPAL_EIGSH_LA ? "above" : "below", lo, hi);
+    }
+    fi->lo = lo;
+    fi->hi = hi;
+    const ChebCoeffs<T> coef = cheb_coefficients<T>(degree, lo, hi, a0);
+    SPAL_TRY((filtered_phases<T, H>(fn, a, k, which, ncv, v0_dev, seed, tol * cheb_scale(glo, ghi), maxit, coef, theta, resid, x_dev,
+                                    ldx, st, fi, &rec)));
+    return finish();
+}
+
+template <typename T, typename H>
+int eigsh_filtered_check(const char *fn, H *a, uint64_t k, int which, uint64_t ncv, double tol, uint64_t degree, int automatic,
+                         double lo, double hi, T *theta, T *resid, const T *x, uint64_t ldx, spal_eigsh_filter_info *fi) {
+    if (!fi) return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: null argument", fn);
+    if (degree < 1 || degree > kChebMaxDegree)
+        return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: degree = %llu must be 1 .. %llu", fn, (unsigned long long)degree,
+                    (unsigned long long)kChebMaxDegree);
+    if (automatic != 0 && automatic != 1) return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: auto = %d must be 0 or 1", fn, automatic);
+    if (!automatic && (!std::isfinite(lo) || !std::isfinite(hi) || !(lo < hi)))
+        return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: the interval [%g, %g] must be finite with lo < hi", fn, lo, hi);
+    spal_eigsh_info plain;
+    return eigsh_check<T, H>(fn, a, k, which, ncv, tol, theta, resid, x, ldx, &plain);
+}
+
+template <typename T, typename H>
+int eigsh_filtered_dev(const char *fn, H *a, uint64_t k, int which, uint64_t ncv, const T *v0_dev, uint64_t seed, double tol,
+                       uint64_t maxit, uint64_t degree, int automatic, double lo, double hi, uint64_t warmup, T *theta, T *resid,
+                       T *x_dev, uint64_t ldx, void *stream, spal_eigsh_filter_info *fi) {
+    SPAL_TRY((eigsh_filtered_check<T, H>(fn, a, k, which, ncv, tol, degree, automatic, lo, hi, theta, resid, x_dev, ldx, fi)));
+    DeviceGuard guard(a->device);
+    if (guard.status != SPAL_OK) return guard.status;
+    return eigsh_filtered_run<T, H>(fn, a, k, which, ncv, v0_dev, seed, tol, maxit, degree, automatic, lo, hi, warmup, theta, resid,
+                                    x_dev, ldx, (hipStream_t)stream, fi);
+}
+
+template <typename T, typename H>
+int eigsh_filtered_host(const char *fn, H *a, uint64_t k, int which, uint64_t ncv, const T *v0, uint64_t v0_len, uint64_t seed,
+                        double tol, uint64_t maxit, uint64_t degree, int automatic, double lo, double hi, uint64_t warmup, T *theta,
+                        uint64_t theta_len, T *resid, uint64_t resid_len, T *x, uint64_t ldx, uint64_t x_rows,
+                        spal_eigsh_filter_info *fi) {
+    SPAL_TRY((eigsh_filtered_check<T, H>(fn, a, k, which, ncv, tol, degree, automatic, lo, hi, theta, resid, x, ldx, fi)));
+    const uint64_t n = a->nrows;
+    if ((v0 && v0_len != n) || theta_len != k || resid_len != k || (x && x_rows != n))
+        return fail(SPAL_ERR_INVALID_ARGUMENT,
+                    "%s: v0.len() = %llu and X has %llu rows but the matrix has %llu rows; theta.len() = %llu and resid.len() = %llu but "
+                    "k = %llu", fn, (unsigned long long)v0_len, (unsigned long long)x_rows, (unsigned long long)n,
+                    (unsigned long long)theta_len, (unsigned long long)resid_len, (unsigned long long)k);
+    DeviceGuard guard(a->device);
+    if (guard.status != SPAL_OK) return guard.status;
+    size_t bytes = 0;
+    if (!bytes_of(n, k, sizeof(T), 1, &bytes))
+        return fail(SPAL_ERR_OUT_OF_MEMORY, "%s: no room for a block of %llu x %llu", fn, (unsigned long long)n, (unsigned long long)k);
+    const size_t row = (size_t)k * sizeof(T);
+    DevBuf dv, dx;
+    PooledStream ps;   // a stream of the call's own
+    if (v0) SPAL_HIP_TRY(dv.alloc(n * sizeof(T)));
+    if (x) SPAL_HIP_TRY(dx.alloc(bytes));
+    SPAL_HIP_TRY(stream_acquire(&ps.s));
+    if (v0) SPAL_HIP_TRY(hipMemcpyAsync(dv.p, v0, n * sizeof(T), hipMemcpyHostToDevice, ps.s));
+    SPAL_TRY((eigsh_filtered_run<T, H>(fn, a, k, which, ncv, v0 ? (const T *)dv.p : nullptr, seed, tol, maxit, degree, automatic, lo, hi,
+                                       warmup, theta, resid, x ? dx.as<T>() : nullptr, k, ps.s, fi)));
+    const uint64_t got = fi->reason == 2 ? 0 : fi->reason == 3 ? fi->converged : k;
+    if (x && got) {
+        SPAL_HIP_TRY(hipMemcpy2DAsync(x, (size_t)ldx * sizeof(T), dx.p, row, (size_t)got * sizeof(T), n, hipMemcpyDeviceToHost, ps.s));
+        SPAL_HIP_TRY(hipStreamSynchronize(ps.s));
+    }
+    return SPAL_OK;
+}
+
 }  // namespace
 
 int eigsh_option(spal_csr *a, const char *key, int64_t value, OpState &s, int *status) {
@@ -556,6 +956,10 @@ int eigsh_option(spal_csr *a, const char *key, int64_t value, OpState &s, int *s
 
 int eigsh_describe_append(char *buf, size_t buf_len, const OpState &s, spal_csr *solve) {
     return info_describe_append(buf, buf_len, s, solve, "eigsh", &OpState::eigsh_info);
+}
+
+int eigsh_filter_describe_append(char *buf, size_t buf_len, const OpState &s, spal_csr *solve) {
+    return info_describe_append(buf, buf_len, s, solve, "eigsh_filter", &OpState::eigsh_filter_info);
 }
 
 }  // namespace spal
@@ -599,5 +1003,29 @@ SPAL_EIGSH_ENTRIES(csr, f32, float)
 SPAL_EIGSH_ENTRIES(csc, f64, double)
 SPAL_EIGSH_ENTRIES(csc, f32, float)
 #undef SPAL_EIGSH_ENTRIES
+
+#define SPAL_EIGSH_FILTERED_ENTRIES(kind, sfx, T)                                                                          \
+    int spal_##kind##_eigsh_filtered_##sfx(spal_##kind##_t a, uint64_t k, int which, uint64_t ncv, const T *v0,             \
+                                           uint64_t v0_len, uint64_t seed, double tol, uint64_t maxit, uint64_t degree,     \
+                                           int automatic, double lo, double hi, uint64_t warmup, T *theta,                  \
+                                           uint64_t theta_len, T *resid, uint64_t resid_len, T *x, uint64_t ldx,            \
+                                           uint64_t x_rows, spal_eigsh_filter_info *info) {                                 \
+        return eigsh_filtered_host<T, spal_##kind>("spal_" #kind "_eigsh_filtered", a, k, which, ncv, v0, v0_len, seed,     \
+                                                   tol, maxit, degree, automatic, lo, hi, warmup, theta, theta_len, resid,  \
+                                                   resid_len, x, ldx, x_rows, info);                                        \
+    }                                                                                                                       \
+    int spal_##kind##_eigsh_filtered_dev_##sfx(spal_##kind##_t a, uint64_t k, int which, uint64_t ncv, const T *v0_dev,     \
+                                               uint64_t seed, double tol, uint64_t maxit, uint64_t degree, int automatic,   \
+                                               double lo, double hi, uint64_t warmup, T *theta, T *resid, T *x_dev,         \
+                                               uint64_t ldx, void *stream, spal_eigsh_filter_info *info) {                  \
+        return eigsh_filtered_dev<T, spal_##kind>("spal_" #kind "_eigsh_filtered_dev", a, k, which, ncv, v0_dev, seed,      \
+                                                  tol, maxit, degree, automatic, lo, hi, warmup, theta, resid, x_dev, ldx,  \
+                                                  stream, info);                                                            \
+    }
+SPAL_EIGSH_FILTERED_ENTRIES(csr, f64, double)
+SPAL_EIGSH_FILTERED_ENTRIES(csr, f32, float)
+SPAL_EIGSH_FILTERED_ENTRIES(csc, f64, double)
+SPAL_EIGSH_FILTERED_ENTRIES(csc, f32, float)
+#undef SPAL_EIGSH_FILTERED_ENTRIES
 
 }  // extern "C"

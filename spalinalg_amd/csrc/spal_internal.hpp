@@ -331,6 +331,8 @@ struct OpState {
     std::string gmres_block_info;  // "gmres_block": the last spal_*_gmres_block_* call with this handle as A (the same lock)
     int eigsh_rotate = 0;          // option "eigsh_rotate": the restart's rotation kernel, 0 = automatic, 1 = batched passes, 2 = LDS row tiles (spal_eigsh.hip)
     std::string eigsh_info;        // "eigsh": the last spal_*_eigsh_* call with this handle as A (the same lock)
+    int cheb_chunk = 0;            // option "cheb_chunk": entries per chunk of the Chebyshev step kernel, 0 = 16 KiB of products (spal_cheb.hip)
+    std::string eigsh_filter_info; // "eigsh_filter": the last spal_*_eigsh_filtered_* call with this handle as A (the same lock)
     // a result of spal_*_permute / _multicolour (spal_colour.hip): written once, before the handle is
     // returned, and only read afterwards
     uint32_t *d_perm = nullptr;    // nrows: new -> old; freed by ordering_free (csr_free, csc_free)

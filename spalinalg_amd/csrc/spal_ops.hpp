@@ -1,5 +1,5 @@
 // spal_ops.hpp -- the host layer the sparse operations share: spal_spgemm.hip, spal_spadd.hip,
-// spal_spmm.hip, spal_trsv.hip, spal_trsv_sweep.hip, spal_trsm.hip, spal_ilu.hip, spal_ilu_sweep.hip, spal_krylov.hip, spal_krylov_block.hip, spal_gmres.hip, spal_gmres_block.hip, spal_eigsh.hip, spal_colour.hip and spal_amg.hip keep their kernels, their driver, their option's validation and their
+// spal_spmm.hip, spal_trsv.hip, spal_trsv_sweep.hip, spal_trsm.hip, spal_ilu.hip, spal_ilu_sweep.hip, spal_krylov.hip, spal_krylov_block.hip, spal_gmres.hip, spal_gmres_block.hip, spal_eigsh.hip, spal_cheb.hip, spal_colour.hip and spal_amg.hip keep their kernels, their driver, their option's validation and their
 // info JSON; what surrounds a launch the same way in each of them is here, once.  (Not installed.)
 #pragma once
 
@@ -9,6 +9,7 @@
 #include <rocprim/device/device_scan.hpp>
 #endif
 
+#include "cheb_host.hpp"
 #include "spal_internal.hpp"
 
 namespace spal {
@@ -182,6 +183,17 @@ int64_t trsv_sweeps_of(spal_csr *a);   // the option "trsv_sweeps" of a solve ha
 int amg_check_match(const char *fn, const spal_amg *g, uint64_t nrows, int device, int elem_size);
 int amg_apply_enqueue(const char *fn, spal_amg *g, const void *b, void *x, hipStream_t st);
 
+// ---- the Chebyshev filter's launches (spal_cheb.hip), for spal_eigsh.hip -----------------------------------
+// All on a solve handle's plain arrays, enqueued on `st`, allocating and synchronising nothing.  chunk: the option
+// "cheb_chunk" (0 = default).  rowsum: out = rowsum(y), out != y.  apply: out = t_d through `work` (n elements, unused
+// at degree 1); x, out and work are distinct.  gershgorin_run synchronises `st`.
+template <typename T>
+int cheb_rowsum_enqueue(const char *fn, spal_csr *a, const T *y, T *out, unsigned chunk, hipStream_t st);
+template <typename T>
+int cheb_apply_enqueue(const char *fn, spal_csr *a, const ChebCoeffs<T> &k, const T *x, T *out, T *work, unsigned chunk,
+                       hipStream_t st);
+int gershgorin_run(const char *fn, spal_csr *a, hipStream_t st, double *glo, double *ghi);
+
 // ---- per-operation state of a handle (spal_internal.hpp: OpState), set and described in one place -------------------
 // Each operation file implements its own: 1 = the key is this operation's and *status says how setting it went, 0 =
 // another key.  The solve's and ILU(0)'s options live on the solve handle, under its `mu`.
@@ -195,12 +207,14 @@ int ilu_option(spal_csr *a, const char *key, int64_t value, int *status);     //
 int krylov_option(spal_csr *a, const char *key, int64_t value, OpState &s, int *status);   // "krylov_check_every"
 int krylov_block_option(spal_csr *a, const char *key, int64_t value, OpState &s, int *status);   // "krylov_tile"
 int eigsh_option(spal_csr *a, const char *key, int64_t value, OpState &s, int *status);   // "eigsh_rotate"
+int cheb_option(spal_csr *a, const char *key, int64_t value, OpState &s, int *status);    // "cheb_chunk"
 inline int ops_set_option(OpState &s, spal_csr *solve, const char *key, int64_t value, int *status) {
     return spgemm_option(key, value, s, status) || spadd_option(key, value, s, status) ||
            spmm_option(key, value, s, status) || trsv_option(solve, key, value, status) ||
            trsv_sweep_option(solve, key, value, status) || trsm_option(solve, key, value, status) ||
            ilu_option(solve, key, value, status) || krylov_option(solve, key, value, s, status) ||
-           krylov_block_option(solve, key, value, s, status) || eigsh_option(solve, key, value, s, status);
+           krylov_block_option(solve, key, value, s, status) || eigsh_option(solve, key, value, s, status) ||
+           cheb_option(solve, key, value, s, status);
 }
 
 // (describe_append itself is host code: spal_host.cpp, declared in spal_internal.hpp)
@@ -221,6 +235,8 @@ int gmres_describe_append(char *buf, size_t buf_len, const OpState &s, spal_csr 
 int gmres_block_describe_append(char *buf, size_t buf_len, const OpState &s, spal_csr *solve);
 // the "eigsh" object of a handle spal_*_eigsh_* ran with as A (spal_eigsh.hip; the same lock)
 int eigsh_describe_append(char *buf, size_t buf_len, const OpState &s, spal_csr *solve);
+// the "eigsh_filter" object of a handle spal_*_eigsh_filtered_* ran with as A (spal_eigsh.hip; the same lock)
+int eigsh_filter_describe_append(char *buf, size_t buf_len, const OpState &s, spal_csr *solve);
 inline int ops_describe_append(char *buf, size_t buf_len, const OpState &s, spal_csr *solve) {
     SPAL_TRY(describe_append(buf, buf_len, "spgemm", s.spgemm_info));   // a product of spal_*_mul: how it was built
     SPAL_TRY(describe_append(buf, buf_len, "spadd", s.spadd_info));     // a result of spal_*_add / _sub / _neg
@@ -235,6 +251,7 @@ inline int ops_describe_append(char *buf, size_t buf_len, const OpState &s, spal
     SPAL_TRY(gmres_describe_append(buf, buf_len, s, solve));            // spal_*_gmres_* ran with it as A: the last call
     SPAL_TRY(gmres_block_describe_append(buf, buf_len, s, solve));      // spal_*_gmres_block_* ran with it as A: the last call
     SPAL_TRY(eigsh_describe_append(buf, buf_len, s, solve));            // spal_*_eigsh_* ran with it as A: the last call
+    SPAL_TRY(eigsh_filter_describe_append(buf, buf_len, s, solve));     // spal_*_eigsh_filtered_* ran with it as A: the last call
     return describe_append(buf, buf_len, "ordering", s.ordering_info);  // a result of spal_*_permute / _multicolour
 }
 

@@ -116,6 +116,36 @@ class EigshInfo(dict):
     __getattr__ = dict.__getitem__
 
 
+class _EigshFilterInfoC(C.Structure):
+    """spal_eigsh_filter_info"""
+    _fields_ = [("restarts", C.c_uint64), ("products", C.c_uint64), ("converged", C.c_uint64), ("reason", C.c_int),
+                ("solve_ms", C.c_double), ("warm_restarts", C.c_uint64), ("warm_products", C.c_uint64), ("lo", C.c_double),
+                ("hi", C.c_double), ("a0", C.c_double), ("degree", C.c_uint64)]
+
+
+def _eigsh_filter_info(c, resid) -> "EigshInfo":
+    out = _eigsh_info(c, resid)
+    out.update(warm_restarts=int(c.warm_restarts), warm_products=int(c.warm_products), lo=float(c.lo), hi=float(c.hi),
+               a0=float(c.a0), degree=int(c.degree))
+    return out
+
+
+def _filter_args(filter_degree, filter_interval, filter_warmup):
+    """(degree, automatic, lo, hi, warmup) of a filtered eigsh call, refused as the library does"""
+    degree = int(filter_degree)
+    if not 1 <= degree <= 256:
+        raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT, f"eigsh: filter_degree = {degree} must be 0 (no filter) or 1 .. 256")
+    warmup = int(filter_warmup)
+    if warmup < 0:
+        raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT, f"eigsh: filter_warmup = {warmup} must be >= 0")
+    if filter_interval is None:
+        return degree, 1, 0.0, 0.0, warmup
+    lo, hi = (float(v) for v in filter_interval)
+    if not (np.isfinite(lo) and np.isfinite(hi) and lo < hi):
+        raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT, f"eigsh: filter_interval = [{lo}, {hi}] must be finite with lo < hi")
+    return degree, 0, lo, hi, warmup
+
+
 _EIGSH_WHICH = {"LA": 0, "SA": 1}
 
 
@@ -669,8 +699,42 @@ class _DeviceMatrix:
                                                               C.c_double(tol), u64(maxit), _stream_ptr(stream), infos))
         return [_krylov_info(c) for c in infos[:int(k)]]
 
+    def cheb_apply(self, x, degree: int, lo: float, hi: float, a0: float) -> np.ndarray:
+        """t_d = p(A) x for the Chebyshev polynomial of `degree` on [lo, hi] scaled to p(a0) = 1 (spal_*_cheb_apply_*,
+        DESIGN 3.26): host vector in, host vector out.  a0 lies outside [lo, hi]; p is small on the interval and grows
+        monotonically towards a0.  Bit for bit the text of include/spal.h, whatever the handle's plan is."""
+        x = np.ascontiguousarray(x, dtype=self.dtype)
+        out = np.empty(self.shape()[0], dtype=self.dtype)
+        check(self._fn(f"cheb_apply_{_sfx(self.dtype)}")(self._h, _p(x), u64(x.size), _p(out), u64(out.size), u64(degree),
+                                                         C.c_double(lo), C.c_double(hi), C.c_double(a0)))
+        return out
+
+    def cheb_apply_dev(self, x_ptr: int, out_ptr: int, degree: int, lo: float, hi: float, a0: float, stream=None) -> None:
+        """Device pointers (out must not overlap x); `degree` launches enqueued on `stream`, not synchronised."""
+        check(self._fn(f"cheb_apply_dev_{_sfx(self.dtype)}")(self._h, vp(x_ptr or None), vp(out_ptr or None), u64(degree),
+                                                             C.c_double(lo), C.c_double(hi), C.c_double(a0), _stream_ptr(stream)))
+
+    def gershgorin(self):
+        """(glo, ghi): Gershgorin's enclosure of this square matrix's spectrum, in double (spal_*_gershgorin)."""
+        lo, hi = C.c_double(), C.c_double()
+        check(self._fn("gershgorin")(self._h, C.byref(lo), C.byref(hi)))
+        return lo.value, hi.value
+
+    def _eigsh_filtered(self, k, w, ncv, v0, seed, tol, maxit, return_eigenvectors, degree, automatic, lo, hi, warmup):
+        n = self.shape()[0]
+        theta = np.zeros(k, dtype=self.dtype)
+        resid = np.zeros(k, dtype=self.dtype)
+        X = np.zeros((n, k), dtype=self.dtype) if return_eigenvectors else None
+        info = _EigshFilterInfoC()
+        check(self._fn(f"eigsh_filtered_{_sfx(self.dtype)}")(
+            self._h, u64(k), C.c_int(w), u64(ncv), None if v0 is None else _p(v0), u64(0 if v0 is None else n), u64(seed),
+            C.c_double(tol), u64(maxit), u64(degree), C.c_int(automatic), C.c_double(lo), C.c_double(hi), u64(warmup), _p(theta),
+            u64(k), _p(resid), u64(k), None if X is None else _p(X), u64(k), u64(n), C.byref(info)))
+        pairs = 0 if info.reason == 2 else int(info.converged) if info.reason == 3 else k
+        return theta[:pairs], (None if X is None else X[:, :pairs]), _eigsh_filter_info(info, resid[:pairs])
+
     def eigsh(self, k: int = 6, which="LA", ncv=None, v0=None, seed: int = 0, tol: float = 0, maxit: int = 1000,
-              return_eigenvectors: bool = True):
+              return_eigenvectors: bool = True, filter_degree: int = 0, filter_interval=None, filter_warmup: int = 5):
         """The k largest (which="LA") or smallest ("SA") eigenvalues of this symmetric matrix and their vectors, by
         thick-restart Lanczos with full orthogonalisation on the device (spal_*_eigsh_*); symmetry is not
         checked.  Returns (theta, X, info): theta in the order of `which` (LA descending, SA ascending), X of shape
@@ -678,14 +742,23 @@ class _DeviceMatrix:
         epsilon; a pair counts as converged when its estimate is <= tol * max|theta|.  v0=None is the text's start
         vector from `seed`.  Bit for bit the text of include/spal.h.  An eigenvalue of multiplicity > 1 is returned
         ONCE: a single-vector Lanczos iteration sees one direction of its eigenspace.  pairs = k unless the space was
-        exhausted earlier (reason 3) or a value was not finite (reason 2: no pair)."""
+        exhausted earlier (reason 3) or a value was not finite (reason 2: no pair).
+        filter_degree > 0 runs Lanczos on a Chebyshev polynomial of A of that degree instead (spal_*_eigsh_filtered_*,
+        DESIGN 3.26), the remedy for CLUSTERED extreme eigenvalues: filter_interval=None takes the interval to damp from
+        `filter_warmup` restarts of the plain iteration, (lo, hi) gives it; convergence is then decided on true
+        residuals, <= tol * max(|glo|, |ghi|) of Gershgorin's bounds, tol=0 is 256 machine epsilons, info.resid holds
+        them and info gains warm_restarts, warm_products, lo, hi, a0, degree.  filter_degree=0 is the plain call."""
         n, ncols, _ = self.shape()
+        tol_given = float(tol)
         k, ncv, tol = _eigsh_args(n, ncols, k, ncv, tol, self.dtype)
         w = _eigsh_which(which)
         if v0 is not None:
             v0 = np.ascontiguousarray(v0, dtype=self.dtype)
             if v0.shape != (n,):
                 raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT, f"eigsh: v0 has shape {v0.shape} but the matrix has {n} rows")
+        if filter_degree:
+            return self._eigsh_filtered(k, w, ncv, v0, seed, tol_given, maxit, return_eigenvectors,
+                                        *_filter_args(filter_degree, filter_interval, filter_warmup))
         theta = np.zeros(k, dtype=self.dtype)
         resid = np.zeros(k, dtype=self.dtype)
         X = np.zeros((n, k), dtype=self.dtype) if return_eigenvectors else None
@@ -699,15 +772,27 @@ class _DeviceMatrix:
         return theta[:pairs], (None if X is None else X[:, :pairs]), out
 
     def eigsh_dev(self, k: int, theta, resid, x_ptr: int, ldx: int, which="LA", ncv=None, v0_ptr: int = 0, seed: int = 0,
-                  tol: float = 0, maxit: int = 1000, stream=None):
+                  tol: float = 0, maxit: int = 1000, stream=None, filter_degree: int = 0, filter_interval=None,
+                  filter_warmup: int = 5):
         """Device pointers: v0_ptr (0: the text's start vector) and x_ptr (0: values only; else n x k row-major with
         leading dimension ldx); theta and resid are host arrays of k values of the handle's dtype, written in place.
-        The call polls, so it synchronises `stream`.  Returns the EigshInfo."""
+        The call polls, so it synchronises `stream`.  Returns the EigshInfo.  filter_degree > 0: the filtered call, as
+        in eigsh()."""
         n, ncols, _ = self.shape()
+        tol_given = float(tol)
         k, ncv, tol = _eigsh_args(n, ncols, k, ncv, tol, self.dtype)
         for a in (theta, resid):
             if not isinstance(a, np.ndarray) or a.dtype != self.dtype or a.shape != (k,) or not a.flags.c_contiguous:
                 raise TypeError(f"theta and resid must be contiguous arrays of {k} {self.dtype} values")
+        if filter_degree:
+            degree, automatic, lo, hi, warmup = _filter_args(filter_degree, filter_interval, filter_warmup)
+            finfo = _EigshFilterInfoC()
+            check(self._fn(f"eigsh_filtered_dev_{_sfx(self.dtype)}")(
+                self._h, u64(k), C.c_int(_eigsh_which(which)), u64(ncv), vp(v0_ptr or None), u64(seed), C.c_double(tol_given),
+                u64(maxit), u64(degree), C.c_int(automatic), C.c_double(lo), C.c_double(hi), u64(warmup), _p(theta), _p(resid),
+                vp(x_ptr or None), u64(ldx), _stream_ptr(stream), C.byref(finfo)))
+            pairs = 0 if finfo.reason == 2 else int(finfo.converged) if finfo.reason == 3 else k
+            return _eigsh_filter_info(finfo, resid[:pairs])
         info = _EigshInfoC()
         check(self._fn(f"eigsh_dev_{_sfx(self.dtype)}")(self._h, u64(k), C.c_int(_eigsh_which(which)), u64(ncv), vp(v0_ptr or None),
                                                         u64(seed), C.c_double(tol), u64(maxit), _p(theta), _p(resid),
@@ -1346,8 +1431,35 @@ class _Compressed:
             M.device(device).set_option("trsv_sweeps", int(precond_sweeps))
         return self.device(device).gmres(b, None if M is None else M.device(device), x0, int(restart), tol, maxit)
 
+    def cheb_apply(self, x, degree: int, lo: float, hi: float, a0: float, device: int = 0) -> np.ndarray:
+        """p(A) x for the Chebyshev polynomial of `degree` that is small on [lo, hi] and 1 at a0, which lies outside the
+        interval: the text of include/spal.h bit for bit.  Refused before anything is copied to a device:
+        a degree outside 1 .. 256, values that are not finite, lo >= hi, a0 inside [lo, hi], a matrix that is not
+        square, an x of another length."""
+        degree, lo, hi, a0 = int(degree), float(lo), float(hi), float(a0)
+        if not 1 <= degree <= 256:
+            raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT, f"cheb_apply: degree = {degree} must be 1 .. 256")
+        if not (np.isfinite(lo) and np.isfinite(hi) and np.isfinite(a0)):
+            raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT, "cheb_apply: lo, hi and a0 must be finite")
+        if not lo < hi:
+            raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT, f"cheb_apply: lo = {lo} must be less than hi = {hi}")
+        if lo <= a0 <= hi:
+            raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT, f"cheb_apply: a0 = {a0} must lie outside [{lo}, {hi}]")
+        if self._nrows != self._ncols:
+            raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT, f"cheb_apply: the matrix is not square ({self._nrows} x {self._ncols})")
+        if np.shape(x) != (self._nrows,):
+            raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT, f"cheb_apply: x has shape {np.shape(x)} but the matrix has {self._nrows} rows")
+        return self.device(device).cheb_apply(x, degree, lo, hi, a0)
+
+    def gershgorin(self, device: int = 0):
+        """(glo, ghi): Gershgorin's enclosure of the spectrum, in double, computed on the device."""
+        if self._nrows != self._ncols:
+            raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT, f"gershgorin: the matrix is not square ({self._nrows} x {self._ncols})")
+        return self.device(device).gershgorin()
+
     def eigsh(self, k: int = 6, which="LA", ncv=None, v0=None, seed: int = 0, tol: float = 0, maxit: int = 1000,
-              return_eigenvectors: bool = True, device: int = 0):
+              return_eigenvectors: bool = True, device: int = 0, filter_degree: int = 0, filter_interval=None,
+              filter_warmup: int = 5):
         """theta, X, info = a.eigsh(k): the k largest (which="LA") or smallest ("SA") eigenvalues of this SYMMETRIC
         matrix and their vectors, by thick-restart Lanczos with full orthogonalisation on the device (DESIGN 3.25);
         symmetry is not checked, as with CG.  theta comes in the order of `which`, X has shape (n, k) (None with
@@ -1355,12 +1467,19 @@ class _Compressed:
         ncv=None means min(n, max(2k + 1, 20)) basis vectors, at most 256; tol=0 means the dtype's machine epsilon, as
         scipy does; maxit bounds the restarts.  An eigenvalue of multiplicity > 1 is returned ONCE (a single-vector
         Lanczos iteration sees one direction of its eigenspace).  Refused on a matrix that is not square or has fewer
-        than ncv rows before anything is copied to a device.  Bit for bit the text of include/spal.h."""
+        than ncv rows before anything is copied to a device.  Bit for bit the text of include/spal.h.
+        CLUSTERED extreme eigenvalues: filter_degree > 0 runs the iteration on a Chebyshev polynomial of A of that degree
+        (DESIGN 3.26), which needs many times fewer restarts; filter_interval=None finds the interval to damp with
+        filter_warmup plain restarts, (lo, hi) gives it.  Convergence is then decided on true residuals against
+        tol * max(|glo|, |ghi|) of Gershgorin's bounds, and tol=0 means 256 machine epsilons."""
         _eigsh_args(self._nrows, self._ncols, k, ncv, tol, self.dtype)
         _eigsh_which(which)
         if v0 is not None and np.shape(v0) != (self._nrows,):
             raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT, f"eigsh: v0 has shape {np.shape(v0)} but the matrix has {self._nrows} rows")
-        return self.device(device).eigsh(k, which, ncv, v0, seed, tol, maxit, return_eigenvectors)
+        if filter_degree:
+            _filter_args(filter_degree, filter_interval, filter_warmup)
+        return self.device(device).eigsh(k, which, ncv, v0, seed, tol, maxit, return_eigenvectors, filter_degree,
+                                         filter_interval, filter_warmup)
 
     def gmres_block(self, B, M=None, X0=None, restart: int = 30, tol: float = 1e-8, maxit: int = 1000, device: int = 0,
                     precond_sweeps=None):
