@@ -787,6 +787,98 @@ int spal_csc_krylov_block_dev_f32(spal_csc_t a, int method, spal_csc_t m, uint64
                                   uint64_t ldb, float *x_dev, uint64_t ldx, double tol, uint64_t maxit, void *stream,
                                   spal_krylov_info *info);
 
+/* ---- (A - shift I) x = b on the device: MINRES for symmetric indefinite systems ---------------------------
+ * Not in the reference.  CG needs a positive definite matrix; BiCGStab and GMRES take anything but waste symmetry.
+ * MINRES (Paige-Saunders) runs a three-term Lanczos recurrence: one product per step, a fixed number of vectors, and
+ * a residual estimate that never grows, so reason 1 at maxit still returns the best iterate.  Solves
+ * (A - shift I) x = b with A symmetric and M symmetric positive definite; neither is checked, as with CG.  The
+ * contract is again a sequential text the device reproduces bit for bit, f32 and f64.
+ *
+ * All scalars are T.  sg = T(shift) is rounded once; shift is a double.  Every product is rounded before the sum it
+ * enters (no FMA); sqrt and / are IEEE, correctly rounded.  dot, T(tol * tol) and M^-1 (two exact solves on m, or
+ * "trsv_sweeps" sweeps per triangle, or v itself when m == NULL) are those of the CG / BiCGStab section above.
+ *
+ *   zb = M^-1 b;  bb = dot(b, zb);  thr = T(tol * tol) * bb
+ *   q = A x;  r2[i] = b[i] - (q[i] - (sg * x[i]));  y = M^-1 r2
+ *   beta = sqrt(dot(r2, y));  phibar = beta;  pp = phibar * phibar;  it = 0;  test
+ *   oldb = dbar = epsln = 0;  cs = -1;  sn = 0;  r1 = w = w2 = 0
+ *   s = 1 / beta;  v[i] = y[i] * s
+ *   while not stopped:
+ *     q = A v;  c1 = (it == 0 ? 0 : beta / oldb)
+ *     t[i] = (q[i] - (sg * v[i])) - (c1 * r1[i]);  alfa = dot(v, t)
+ *     c2 = alfa / beta;  t[i] = t[i] - (c2 * r2[i]);  r1 = r2;  r2 = t
+ *     y = M^-1 r2;  oldb = beta;  beta = sqrt(dot(r2, y));  it += 1
+ *     oldeps = epsln;  delta = (cs * dbar) + (sn * alfa);  gbar = (sn * dbar) - (cs * alfa)
+ *     epsln = sn * beta;  dbar = -(cs * beta);  gamma = sqrt((gbar * gbar) + (beta * beta))
+ *     cs = gbar / gamma;  sn = beta / gamma;  phi = cs * phibar;  phibar = sn * phibar;  denom = 1 / gamma
+ *     w1 = w2;  w2 = w;  w[i] = ((v[i] - (oldeps * w1[i])) - (delta * w2[i])) * denom
+ *     x[i] = x[i] + (phi * w[i])
+ *     pp = phibar * phibar;  test                                   -- x already holds this iteration's update
+ *     s = 1 / beta;  v[i] = y[i] * s
+ *   test (on pp):  pp <= thr: stop, reason 0;  else pp not finite: stop, reason 2;  else it == maxit: stop, reason 1
+ *
+ * pp is the recurrence's estimate of ||r||^2 in the M^-1 norm and bb the same norm of b; without m these are ||r||^2
+ * and dot(b, b), CG's criterion.  info.residual_sq = pp and info.rhs_sq = bb.
+ * No value raises an error: an indefinite M (dot(r2, y) < 0, so sqrt gives NaN), a singular A - shift I (gamma == 0)
+ * or an overflow all reach pp as NaN and stop with reason 2.  The lucky breakdown beta == 0 gives sn = 0, so
+ * pp = 0 <= thr: the iteration stops with reason 0 before 1 / beta is formed.  There is no max(gamma, eps) clamp and
+ * no second set of stopping rules: one test, as everywhere else in the library.
+ *
+ * spal_*_minres_*: the arguments of spal_*_krylov_* without `method` and with `double shift` after m; the _dev forms
+ * SYNCHRONISE `stream` and are refused on a capturing stream.  spal_*_minres_block_*: the arguments of
+ * spal_*_krylov_block_* without `method`, with one shift for all columns: k independent iterations in lockstep on
+ * shared launches.  Column j and infos[j] are the vector text's bits for B[:, j] (with SpMM's products and the block
+ * solves as M^-1, as in the block section above), whatever k, the leading dimensions, "krylov_tile",
+ * "krylov_check_every" and the other columns are; a stopped column is frozen, and a NaN in one column never reaches
+ * another.  Refusals, status codes, spal_krylov_info, the options read, the plans built before the first iteration
+ * and the locks (none held across a product) are those of the CG / BiCGStab entries; additionally a shift that is NaN
+ * or infinite is SPAL_ERR_INVALID_ARGUMENT.  The messages begin "spal_csr_minres" / "spal_csr_minres_block" (csc
+ * alike).  Work vectors: v, three for r1 / r2 / t, two for w1 / w2 (w is written over w1), y only with m; with m a
+ * block call whose ldb > k packs B once.
+ * describe()["krylov"] (the block calls: ["krylov_block"]) after a call has "method": "minres" and gains "shift".
+ * Not provided: an AMG hierarchy as M, shift-invert eigsh on top of this, MINRES-QLP for singular systems, capture
+ * into a graph. */
+int spal_csr_minres_f64(spal_csr_t a, spal_csr_t m, double shift, const double *b, uint64_t b_len, double *x,
+                        uint64_t x_len, double tol, uint64_t maxit, spal_krylov_info *info);
+int spal_csr_minres_f32(spal_csr_t a, spal_csr_t m, double shift, const float *b, uint64_t b_len, float *x,
+                        uint64_t x_len, double tol, uint64_t maxit, spal_krylov_info *info);
+int spal_csr_minres_dev_f64(spal_csr_t a, spal_csr_t m, double shift, const double *b_dev, double *x_dev, double tol,
+                            uint64_t maxit, void *stream, spal_krylov_info *info);   /* synchronises */
+int spal_csr_minres_dev_f32(spal_csr_t a, spal_csr_t m, double shift, const float *b_dev, float *x_dev, double tol,
+                            uint64_t maxit, void *stream, spal_krylov_info *info);
+int spal_csc_minres_f64(spal_csc_t a, spal_csc_t m, double shift, const double *b, uint64_t b_len, double *x,
+                        uint64_t x_len, double tol, uint64_t maxit, spal_krylov_info *info);
+int spal_csc_minres_f32(spal_csc_t a, spal_csc_t m, double shift, const float *b, uint64_t b_len, float *x,
+                        uint64_t x_len, double tol, uint64_t maxit, spal_krylov_info *info);
+int spal_csc_minres_dev_f64(spal_csc_t a, spal_csc_t m, double shift, const double *b_dev, double *x_dev, double tol,
+                            uint64_t maxit, void *stream, spal_krylov_info *info);
+int spal_csc_minres_dev_f32(spal_csc_t a, spal_csc_t m, double shift, const float *b_dev, float *x_dev, double tol,
+                            uint64_t maxit, void *stream, spal_krylov_info *info);
+int spal_csr_minres_block_f64(spal_csr_t a, spal_csr_t m, double shift, uint64_t k, const double *b, uint64_t ldb,
+                              uint64_t b_rows, double *x, uint64_t ldx, uint64_t x_rows, double tol, uint64_t maxit,
+                              spal_krylov_info *info);                            /* host blocks; info: k records */
+int spal_csr_minres_block_f32(spal_csr_t a, spal_csr_t m, double shift, uint64_t k, const float *b, uint64_t ldb,
+                              uint64_t b_rows, float *x, uint64_t ldx, uint64_t x_rows, double tol, uint64_t maxit,
+                              spal_krylov_info *info);
+int spal_csr_minres_block_dev_f64(spal_csr_t a, spal_csr_t m, double shift, uint64_t k, const double *b_dev,
+                                  uint64_t ldb, double *x_dev, uint64_t ldx, double tol, uint64_t maxit, void *stream,
+                                  spal_krylov_info *info);                        /* synchronises; info on the host */
+int spal_csr_minres_block_dev_f32(spal_csr_t a, spal_csr_t m, double shift, uint64_t k, const float *b_dev,
+                                  uint64_t ldb, float *x_dev, uint64_t ldx, double tol, uint64_t maxit, void *stream,
+                                  spal_krylov_info *info);
+int spal_csc_minres_block_f64(spal_csc_t a, spal_csc_t m, double shift, uint64_t k, const double *b, uint64_t ldb,
+                              uint64_t b_rows, double *x, uint64_t ldx, uint64_t x_rows, double tol, uint64_t maxit,
+                              spal_krylov_info *info);
+int spal_csc_minres_block_f32(spal_csc_t a, spal_csc_t m, double shift, uint64_t k, const float *b, uint64_t ldb,
+                              uint64_t b_rows, float *x, uint64_t ldx, uint64_t x_rows, double tol, uint64_t maxit,
+                              spal_krylov_info *info);
+int spal_csc_minres_block_dev_f64(spal_csc_t a, spal_csc_t m, double shift, uint64_t k, const double *b_dev,
+                                  uint64_t ldb, double *x_dev, uint64_t ldx, double tol, uint64_t maxit, void *stream,
+                                  spal_krylov_info *info);
+int spal_csc_minres_block_dev_f32(spal_csc_t a, spal_csc_t m, double shift, uint64_t k, const float *b_dev,
+                                  uint64_t ldb, float *x_dev, uint64_t ldx, double tol, uint64_t maxit, void *stream,
+                                  spal_krylov_info *info);
+
 /* ---- A x = b on the device: restarted GMRES(m), right-preconditioned ------------------------------------
  * Not in the reference.  For matrices that are not symmetric, where BiCGStab can break down (on the cyclic shift with
  * b = e0 it returns reason 2 after one iteration; GMRES solves that system in n steps).  The contract is again a

@@ -22,6 +22,8 @@
 //   a.eigsh(k, which, ncv, v0, seed, tol, maxit)         not in the reference: extreme eigenpairs of a symmetric matrix (spal_*_eigsh_*)
 //   a.eigsh_filtered(k, degree, ...), a.cheb_apply(x, degree, lo, hi, a0), a.gershgorin()    not in the reference: the Chebyshev filter (spal_*_eigsh_filtered_*, _cheb_apply_*, _gershgorin)
 //   a.gmres_block(B, k, restart, M, X0, tol, maxit)      not in the reference: GMRES on k right-hand sides (spal_*_gmres_block_*)
+//   a.minres(b, M, shift, x0, tol, maxit)                not in the reference: MINRES on (A - shift I) x = b, A symmetric (spal_*_minres_*)
+//   a.minres_block(B, k, M, shift, X0, tol, maxit)       not in the reference: the same on k right-hand sides (spal_*_minres_block_*)
 //   a.colour(seed), a.permute(perm), a.multicolour(seed), p.ordering(), p.to_order(v), p.from_order(v),
 //   colour_greedy(n, rowptr, colind, seed), perm_from_colours(colours)
 //                                                        not in the reference: the multicolour ordering
@@ -82,6 +84,8 @@ template <> struct Abi<double> {
     static constexpr auto csr_krylov_block = spal_csr_krylov_block_f64;
     static constexpr auto csr_gmres = spal_csr_gmres_f64;
     static constexpr auto csr_gmres_block = spal_csr_gmres_block_f64;
+    static constexpr auto csr_minres = spal_csr_minres_f64;
+    static constexpr auto csr_minres_block = spal_csr_minres_block_f64;
     static constexpr auto csr_eigsh = spal_csr_eigsh_f64;
     static constexpr auto csr_eigsh_filtered = spal_csr_eigsh_filtered_f64;
     static constexpr auto csr_cheb_apply = spal_csr_cheb_apply_f64;
@@ -99,6 +103,8 @@ template <> struct Abi<double> {
     static constexpr auto csc_krylov_block = spal_csc_krylov_block_f64;
     static constexpr auto csc_gmres = spal_csc_gmres_f64;
     static constexpr auto csc_gmres_block = spal_csc_gmres_block_f64;
+    static constexpr auto csc_minres = spal_csc_minres_f64;
+    static constexpr auto csc_minres_block = spal_csc_minres_block_f64;
     static constexpr auto csc_eigsh = spal_csc_eigsh_f64;
     static constexpr auto csc_eigsh_filtered = spal_csc_eigsh_filtered_f64;
     static constexpr auto csc_cheb_apply = spal_csc_cheb_apply_f64;
@@ -119,6 +125,8 @@ template <> struct Abi<float> {
     static constexpr auto csr_krylov_block = spal_csr_krylov_block_f32;
     static constexpr auto csr_gmres = spal_csr_gmres_f32;
     static constexpr auto csr_gmres_block = spal_csr_gmres_block_f32;
+    static constexpr auto csr_minres = spal_csr_minres_f32;
+    static constexpr auto csr_minres_block = spal_csr_minres_block_f32;
     static constexpr auto csr_eigsh = spal_csr_eigsh_f32;
     static constexpr auto csr_eigsh_filtered = spal_csr_eigsh_filtered_f32;
     static constexpr auto csr_cheb_apply = spal_csr_cheb_apply_f32;
@@ -136,6 +144,8 @@ template <> struct Abi<float> {
     static constexpr auto csc_krylov_block = spal_csc_krylov_block_f32;
     static constexpr auto csc_gmres = spal_csc_gmres_f32;
     static constexpr auto csc_gmres_block = spal_csc_gmres_block_f32;
+    static constexpr auto csc_minres = spal_csc_minres_f32;
+    static constexpr auto csc_minres_block = spal_csc_minres_block_f32;
     static constexpr auto csc_eigsh = spal_csc_eigsh_f32;
     static constexpr auto csc_eigsh_filtered = spal_csc_eigsh_filtered_f32;
     static constexpr auto csc_cheb_apply = spal_csc_cheb_apply_f32;
@@ -638,6 +648,52 @@ class CsrMatrix {
         return s;
     }
 
+    // x with (A - shift I) x = b by MINRES on the device, for a SYMMETRIC matrix that may be indefinite (not checked); M,
+    // when given, symmetric positive definite and applied as solve() applies it; bit for bit the text of include/spal.h
+    // (spal_csr_minres_*).  The residual estimate never grows, so reason 1 still returns the best iterate.  Panics as
+    // solve() does, and on a shift that is not finite.
+    Solution<T> minres(const std::vector<T> &b, const CsrMatrix *M = nullptr, double shift = 0.0, const std::vector<T> &x0 = {},
+                       double tol = 1e-8, usize maxit = 1000) const {
+        if (nrows_ != ncols_)
+            throw Panic(SPAL_ERR_INVALID_ARGUMENT, "minres: the matrix is not square (" + std::to_string(nrows_) + " x " +
+                                                       std::to_string(ncols_) + ")");
+        if (b.size() != nrows_ || (!x0.empty() && x0.size() != nrows_))
+            throw Panic(SPAL_ERR_INVALID_ARGUMENT, "minres: b.len() = " + std::to_string(b.size()) + " and x0.len() = " +
+                                                       std::to_string(x0.size()) + " but the matrix has " +
+                                                       std::to_string(nrows_) + " rows");
+        if (!(shift - shift == 0.0)) throw Panic(SPAL_ERR_INVALID_ARGUMENT, "minres: shift must be finite");
+        Solution<T> s{x0.empty() ? std::vector<T>(nrows_, T(0)) : x0, 0, 0, 0.0, 0.0, 0.0};
+        spal_krylov_info info;
+        detail::check(detail::Abi<T>::csr_minres(device_handle(), M ? M->device_handle() : nullptr, shift, b.data(),
+                                                  b.size(), s.x.data(), s.x.size(), tol, maxit, &info));
+        s.iterations = info.iterations;
+        s.reason = info.reason;
+        s.residual_sq = info.residual_sq;
+        s.rhs_sq = info.rhs_sq;
+        s.solve_ms = info.solve_ms;
+        return s;
+    }
+
+    // X with (A - shift I) X = B for a ROW-MAJOR block of k right-hand sides by MINRES: k independent iterations in
+    // lockstep on shared launches (spal_csr_minres_block_*, include/spal.h).  Column j of the result and columns[j] are
+    // bit for bit minres()'s text on column j of B, whatever k and the other columns are.  X0 empty: zeros.  Panics as
+    // minres() does, and when k == 0 or B / X0 are not nrows x k.
+    BlockSolution<T> minres_block(const std::vector<T> &B, usize k, const CsrMatrix *M = nullptr, double shift = 0.0,
+                                  const std::vector<T> &X0 = {}, double tol = 1e-8, usize maxit = 1000) const {
+        check_block("minres_block", B.size(), k);
+        if (!X0.empty() && X0.size() != B.size())
+            throw Panic(SPAL_ERR_INVALID_ARGUMENT, "minres_block: X0.len() = " + std::to_string(X0.size()) +
+                                                       " but B.len() = " + std::to_string(B.size()));
+        if (!(shift - shift == 0.0)) throw Panic(SPAL_ERR_INVALID_ARGUMENT, "minres_block: shift must be finite");
+        BlockSolution<T> s{X0.empty() ? std::vector<T>(B.size(), T(0)) : X0, {}};
+        std::vector<spal_krylov_info> info(k);
+        detail::check(detail::Abi<T>::csr_minres_block(device_handle(), M ? M->device_handle() : nullptr, shift, k, B.data(),
+                                                        k, nrows_, s.x.data(), k, nrows_, tol, maxit, info.data()));
+        for (const spal_krylov_info &c : info)
+            s.columns.push_back(ColumnResult{c.iterations, c.reason, c.residual_sq, c.rhs_sq, c.solve_ms});
+        return s;
+    }
+
     // CsrMatrix::from(&coo): assembled on the device, bit-identical to the reference.
     static CsrMatrix from(const CooMatrix<T> &coo, int device = 0);
     // CsrMatrix::from(&csc)  (src/csr/conv/csc.rs:4-52): device stable sort by row.
@@ -1053,6 +1109,52 @@ class CscMatrix {
         std::vector<spal_krylov_info> info(k);
         detail::check(detail::Abi<T>::csc_gmres_block(device_handle(), M ? M->device_handle() : nullptr, k, B.data(), k,
                                                        nrows_, s.x.data(), k, nrows_, restart, tol, maxit, info.data()));
+        for (const spal_krylov_info &c : info)
+            s.columns.push_back(ColumnResult{c.iterations, c.reason, c.residual_sq, c.rhs_sq, c.solve_ms});
+        return s;
+    }
+
+    // x with (A - shift I) x = b by MINRES on the device, for a SYMMETRIC matrix that may be indefinite (not checked); M,
+    // when given, symmetric positive definite and applied as solve() applies it; bit for bit the text of include/spal.h
+    // (spal_csc_minres_*).  The residual estimate never grows, so reason 1 still returns the best iterate.  Panics as
+    // solve() does, and on a shift that is not finite.
+    Solution<T> minres(const std::vector<T> &b, const CscMatrix *M = nullptr, double shift = 0.0, const std::vector<T> &x0 = {},
+                       double tol = 1e-8, usize maxit = 1000) const {
+        if (nrows_ != ncols_)
+            throw Panic(SPAL_ERR_INVALID_ARGUMENT, "minres: the matrix is not square (" + std::to_string(nrows_) + " x " +
+                                                       std::to_string(ncols_) + ")");
+        if (b.size() != nrows_ || (!x0.empty() && x0.size() != nrows_))
+            throw Panic(SPAL_ERR_INVALID_ARGUMENT, "minres: b.len() = " + std::to_string(b.size()) + " and x0.len() = " +
+                                                       std::to_string(x0.size()) + " but the matrix has " +
+                                                       std::to_string(nrows_) + " rows");
+        if (!(shift - shift == 0.0)) throw Panic(SPAL_ERR_INVALID_ARGUMENT, "minres: shift must be finite");
+        Solution<T> s{x0.empty() ? std::vector<T>(nrows_, T(0)) : x0, 0, 0, 0.0, 0.0, 0.0};
+        spal_krylov_info info;
+        detail::check(detail::Abi<T>::csc_minres(device_handle(), M ? M->device_handle() : nullptr, shift, b.data(),
+                                                  b.size(), s.x.data(), s.x.size(), tol, maxit, &info));
+        s.iterations = info.iterations;
+        s.reason = info.reason;
+        s.residual_sq = info.residual_sq;
+        s.rhs_sq = info.rhs_sq;
+        s.solve_ms = info.solve_ms;
+        return s;
+    }
+
+    // X with (A - shift I) X = B for a ROW-MAJOR block of k right-hand sides by MINRES: k independent iterations in
+    // lockstep on shared launches (spal_csc_minres_block_*, include/spal.h).  Column j of the result and columns[j] are
+    // bit for bit minres()'s text on column j of B, whatever k and the other columns are.  X0 empty: zeros.  Panics as
+    // minres() does, and when k == 0 or B / X0 are not nrows x k.
+    BlockSolution<T> minres_block(const std::vector<T> &B, usize k, const CscMatrix *M = nullptr, double shift = 0.0,
+                                  const std::vector<T> &X0 = {}, double tol = 1e-8, usize maxit = 1000) const {
+        check_block("minres_block", B.size(), k);
+        if (!X0.empty() && X0.size() != B.size())
+            throw Panic(SPAL_ERR_INVALID_ARGUMENT, "minres_block: X0.len() = " + std::to_string(X0.size()) +
+                                                       " but B.len() = " + std::to_string(B.size()));
+        if (!(shift - shift == 0.0)) throw Panic(SPAL_ERR_INVALID_ARGUMENT, "minres_block: shift must be finite");
+        BlockSolution<T> s{X0.empty() ? std::vector<T>(B.size(), T(0)) : X0, {}};
+        std::vector<spal_krylov_info> info(k);
+        detail::check(detail::Abi<T>::csc_minres_block(device_handle(), M ? M->device_handle() : nullptr, shift, k, B.data(),
+                                                        k, nrows_, s.x.data(), k, nrows_, tol, maxit, info.data()));
         for (const spal_krylov_info &c : info)
             s.columns.push_back(ColumnResult{c.iterations, c.reason, c.residual_sq, c.rhs_sq, c.solve_ms});
         return s;

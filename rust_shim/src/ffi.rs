@@ -144,6 +144,22 @@ extern "C" {
     pub fn spal_csc_krylov_block_f32(a: *mut spal_csc, method: c_int, m: *mut spal_csc, k: u64, b: *const f32, ldb: u64, b_rows: u64, x: *mut f32, ldx: u64, x_rows: u64, tol: f64, maxit: u64, info: *mut spal_krylov_info) -> c_int;
     pub fn spal_csc_krylov_block_dev_f64(a: *mut spal_csc, method: c_int, m: *mut spal_csc, k: u64, b_dev: *const f64, ldb: u64, x_dev: *mut f64, ldx: u64, tol: f64, maxit: u64, stream: *mut c_void, info: *mut spal_krylov_info) -> c_int;
     pub fn spal_csc_krylov_block_dev_f32(a: *mut spal_csc, method: c_int, m: *mut spal_csc, k: u64, b_dev: *const f32, ldb: u64, x_dev: *mut f32, ldx: u64, tol: f64, maxit: u64, stream: *mut c_void, info: *mut spal_krylov_info) -> c_int;
+    pub fn spal_csr_minres_f64(a: *mut spal_csr, m: *mut spal_csr, shift: f64, b: *const f64, b_len: u64, x: *mut f64, x_len: u64, tol: f64, maxit: u64, info: *mut spal_krylov_info) -> c_int;
+    pub fn spal_csr_minres_f32(a: *mut spal_csr, m: *mut spal_csr, shift: f64, b: *const f32, b_len: u64, x: *mut f32, x_len: u64, tol: f64, maxit: u64, info: *mut spal_krylov_info) -> c_int;
+    pub fn spal_csr_minres_dev_f64(a: *mut spal_csr, m: *mut spal_csr, shift: f64, b_dev: *const f64, x_dev: *mut f64, tol: f64, maxit: u64, stream: *mut c_void, info: *mut spal_krylov_info) -> c_int;
+    pub fn spal_csr_minres_dev_f32(a: *mut spal_csr, m: *mut spal_csr, shift: f64, b_dev: *const f32, x_dev: *mut f32, tol: f64, maxit: u64, stream: *mut c_void, info: *mut spal_krylov_info) -> c_int;
+    pub fn spal_csc_minres_f64(a: *mut spal_csc, m: *mut spal_csc, shift: f64, b: *const f64, b_len: u64, x: *mut f64, x_len: u64, tol: f64, maxit: u64, info: *mut spal_krylov_info) -> c_int;
+    pub fn spal_csc_minres_f32(a: *mut spal_csc, m: *mut spal_csc, shift: f64, b: *const f32, b_len: u64, x: *mut f32, x_len: u64, tol: f64, maxit: u64, info: *mut spal_krylov_info) -> c_int;
+    pub fn spal_csc_minres_dev_f64(a: *mut spal_csc, m: *mut spal_csc, shift: f64, b_dev: *const f64, x_dev: *mut f64, tol: f64, maxit: u64, stream: *mut c_void, info: *mut spal_krylov_info) -> c_int;
+    pub fn spal_csc_minres_dev_f32(a: *mut spal_csc, m: *mut spal_csc, shift: f64, b_dev: *const f32, x_dev: *mut f32, tol: f64, maxit: u64, stream: *mut c_void, info: *mut spal_krylov_info) -> c_int;
+    pub fn spal_csr_minres_block_f64(a: *mut spal_csr, m: *mut spal_csr, shift: f64, k: u64, b: *const f64, ldb: u64, b_rows: u64, x: *mut f64, ldx: u64, x_rows: u64, tol: f64, maxit: u64, info: *mut spal_krylov_info) -> c_int;
+    pub fn spal_csr_minres_block_f32(a: *mut spal_csr, m: *mut spal_csr, shift: f64, k: u64, b: *const f32, ldb: u64, b_rows: u64, x: *mut f32, ldx: u64, x_rows: u64, tol: f64, maxit: u64, info: *mut spal_krylov_info) -> c_int;
+    pub fn spal_csr_minres_block_dev_f64(a: *mut spal_csr, m: *mut spal_csr, shift: f64, k: u64, b_dev: *const f64, ldb: u64, x_dev: *mut f64, ldx: u64, tol: f64, maxit: u64, stream: *mut c_void, info: *mut spal_krylov_info) -> c_int;
+    pub fn spal_csr_minres_block_dev_f32(a: *mut spal_csr, m: *mut spal_csr, shift: f64, k: u64, b_dev: *const f32, ldb: u64, x_dev: *mut f32, ldx: u64, tol: f64, maxit: u64, stream: *mut c_void, info: *mut spal_krylov_info) -> c_int;
+    pub fn spal_csc_minres_block_f64(a: *mut spal_csc, m: *mut spal_csc, shift: f64, k: u64, b: *const f64, ldb: u64, b_rows: u64, x: *mut f64, ldx: u64, x_rows: u64, tol: f64, maxit: u64, info: *mut spal_krylov_info) -> c_int;
+    pub fn spal_csc_minres_block_f32(a: *mut spal_csc, m: *mut spal_csc, shift: f64, k: u64, b: *const f32, ldb: u64, b_rows: u64, x: *mut f32, ldx: u64, x_rows: u64, tol: f64, maxit: u64, info: *mut spal_krylov_info) -> c_int;
+    pub fn spal_csc_minres_block_dev_f64(a: *mut spal_csc, m: *mut spal_csc, shift: f64, k: u64, b_dev: *const f64, ldb: u64, x_dev: *mut f64, ldx: u64, tol: f64, maxit: u64, stream: *mut c_void, info: *mut spal_krylov_info) -> c_int;
+    pub fn spal_csc_minres_block_dev_f32(a: *mut spal_csc, m: *mut spal_csc, shift: f64, k: u64, b_dev: *const f32, ldb: u64, x_dev: *mut f32, ldx: u64, tol: f64, maxit: u64, stream: *mut c_void, info: *mut spal_krylov_info) -> c_int;
     pub fn spal_csr_gmres_f64(a: *mut spal_csr, m: *mut spal_csr, b: *const f64, b_len: u64, x: *mut f64, x_len: u64, restart: u64, tol: f64, maxit: u64, info: *mut spal_krylov_info) -> c_int;
     pub fn spal_csr_gmres_f32(a: *mut spal_csr, m: *mut spal_csr, b: *const f32, b_len: u64, x: *mut f32, x_len: u64, restart: u64, tol: f64, maxit: u64, info: *mut spal_krylov_info) -> c_int;
     pub fn spal_csr_gmres_dev_f64(a: *mut spal_csr, m: *mut spal_csr, b_dev: *const f64, x_dev: *mut f64, restart: u64, tol: f64, maxit: u64, stream: *mut c_void, info: *mut spal_krylov_info) -> c_int;

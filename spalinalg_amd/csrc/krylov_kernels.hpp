@@ -77,26 +77,74 @@ struct Scal {
     T rr, bb, thr, rz, alpha, beta, omega, rho;
     unsigned long long it;
     unsigned done, reason, half, pad;
+    // MINRES (rr holds pp): the Lanczos and rotation state, then what the vector updates read
+    T lbeta, oldb, dbar, epsln, cs, sn, phibar, alfa;
+    T c1, c2, oldeps, delta, denom, phi, sinv;
 };
 
+// The scalars an update reads, loaded once per launch (per column of a block); `go`: the call has not stopped.
+template <typename T>
+struct Coef {
+    T alpha, beta, omega, c3, c4;
+    bool go;
+};
+// Whether update OP still runs: everything freezes at the stop, except the one update that the stop left behind --
+// V_BI_HALF runs only then, V_MR_WX runs then too (without its last part).
+template <typename T, int OP>
+__device__ __forceinline__ bool op_live(const Scal<T> *s) {
+    if (OP == V_BI_HALF) return s->half != 0;
+    if (OP == V_MR_WX) return s->done == 0 || s->half != 0;
+    return s->done == 0;
+}
+template <typename T, int OP>
+__device__ __forceinline__ Coef<T> op_coef(const Scal<T> *s, T sg) {
+    if (OP == V_MR_WX) return {s->oldeps, s->delta, s->denom, s->phi, s->sinv, s->done == 0};
+    if (OP >= V_MR_R0) return {sg, s->c1, s->c2, s->sinv, T(0), true};
+    return {s->alpha, s->beta, s->omega, T(0), T(0), true};
+}
+
 // (the updates by name, VecOp, and the scalar steps by name, FinOp: krylov_loops.hpp)
-template <int OP> struct Dots { static constexpr int n = (OP == V_CG_P || OP == V_BI_P || OP == V_BI_HALF) ? 0 : (OP == V_DOT2 || OP == V_INIT) ? 2 : 1; };
+template <int OP> struct Dots {
+    static constexpr int n = (OP == V_CG_P || OP == V_BI_P || OP == V_BI_HALF || OP == V_MR_V || OP == V_MR_T2_PRE || OP == V_MR_WX) ? 0
+                             : (OP == V_DOT2 || OP == V_INIT || OP == V_MR_R0)                                                       ? 2
+                                                                                                                                     : 1;
+};
 
 // What update OP reads and writes of an element, and its arithmetic on the values alone: x and y come in as loaded (or
 // as anything, where OP does not read them) and go out as what OP stores.  p0 / p1: the element's products for d0 / d1.
+// z is the third written operand, V_MR_WX's alone.
 template <int OP> struct Reads {
-    static constexpr bool c = OP == V_BI_XR, d = OP == V_BI_XR;
-    static constexpr bool x = OP == V_CG_XR || OP == V_BI_HALF || OP == V_BI_XR;
-    static constexpr bool y = OP == V_CG_XR || OP == V_CG_P || OP == V_BI_P;
-    static constexpr bool b = OP != V_CG_P;   // every OP reads a
+    static constexpr bool c = OP == V_BI_XR || OP == V_MR_R0, d = OP == V_BI_XR;
+    static constexpr bool x = OP == V_CG_XR || OP == V_BI_HALF || OP == V_BI_XR || OP == V_MR_WX;
+    static constexpr bool y = OP == V_CG_XR || OP == V_CG_P || OP == V_BI_P || OP == V_MR_T1 || OP == V_MR_T2 || OP == V_MR_T2_PRE || OP == V_MR_WX;
+    static constexpr bool b = OP != V_CG_P && OP != V_MR_V && OP != V_MR_T2 && OP != V_MR_T2_PRE;   // every OP reads a
+    static constexpr bool z = OP == V_MR_WX;
 };
 template <int OP> struct Writes {
     static constexpr bool x = Reads<OP>::x;
     static constexpr bool y = OP != V_DOT && OP != V_DOT2;
+    static constexpr bool z = Reads<OP>::z;
 };
 template <typename T, int OP>
-__device__ __forceinline__ void vec_value(T a, T b, T c, T d, T &x, T &y, T alpha, T beta, T omega, T &p0, T &p1) {
-    if (OP == V_DOT) {
+__device__ __forceinline__ void vec_value(T a, T b, T c, T d, T &x, T &y, T &z, const Coef<T> &k, T &p0, T &p1) {
+    const T alpha = k.alpha, beta = k.beta, omega = k.omega;
+    if (OP == V_MR_R0) {
+        y = a - (b - alpha * c);           // alpha: sg
+        p0 = y * y;
+        p1 = a * a;
+    } else if (OP == V_MR_V) {
+        y = a * k.c3;                      // c3: s
+    } else if (OP == V_MR_T1) {
+        y = (y - alpha * a) - beta * b;    // beta: c1
+        p0 = a * y;
+    } else if (OP == V_MR_T2 || OP == V_MR_T2_PRE) {
+        y = y - omega * a;                 // omega: c2
+        p0 = y * y;
+    } else if (OP == V_MR_WX) {            // alpha, beta, omega, c3, c4: oldeps, delta, denom, phi, s
+        y = ((z - alpha * y) - beta * b) * omega;
+        x = x + k.c3 * y;
+        if (k.go) z = a * k.c4;            // stopped: v stays
+    } else if (OP == V_DOT) {
         p0 = a * b;
     } else if (OP == V_DOT2) {
         p0 = a * b;
@@ -134,13 +182,14 @@ __device__ __forceinline__ void vec_value(T a, T b, T c, T d, T &x, T &y, T alph
 // operands are either the same array (z is r, ph is p, sh is s -- all of them only read) or disjoint, and an element's
 // update touches that element's index alone, so loading everything before the first store changes nothing.
 template <typename T, int OP>
-__device__ __forceinline__ void vec_update(const T *a, const T *b, const T *c, const T *d, T *x, T *y, T alpha, T beta,
-                                           T omega, T &p0, T &p1) {
+__device__ __forceinline__ void vec_update(const T *a, const T *b, const T *c, const T *d, T *x, T *y, T *z, const Coef<T> &k,
+                                           T &p0, T &p1) {
     const T av = *a, bv = Reads<OP>::b ? *b : T(0), cv = Reads<OP>::c ? *c : T(0), dv = Reads<OP>::d ? *d : T(0);
-    T xv = Reads<OP>::x ? *x : T(0), yv = Reads<OP>::y ? *y : T(0);
-    vec_value<T, OP>(av, bv, cv, dv, xv, yv, alpha, beta, omega, p0, p1);
+    T xv = Reads<OP>::x ? *x : T(0), yv = Reads<OP>::y ? *y : T(0), zv = Reads<OP>::z ? *z : T(0);
+    vec_value<T, OP>(av, bv, cv, dv, xv, yv, zv, k, p0, p1);
     if (Writes<OP>::x) *x = xv;
     if (Writes<OP>::y) *y = yv;
+    if (Writes<OP>::z) *z = zv;
 }
 
 // ---- the scalar step that follows a dot: thread 0 of the launch that walked the upper levels --------------------------
@@ -201,6 +250,45 @@ __device__ __forceinline__ void scalar_step(Scal<T> *s, T d0, T d1, T tol2, uint
         s->omega = d0 / d1;
     } else if (OP == F_TEST_BI) {
         stop_test<T>(s, d0, maxit);
+    } else if (OP == F_MR_BB) {
+        s->bb = d0;
+    } else if (OP == F_MR_INIT) {
+        const T bb = unpreconditioned ? d1 : s->bb;
+        s->bb = bb;
+        s->thr = tol2 * bb;
+        s->it = 0;
+        const T beta = sqrt(d0);   // IEEE, correctly rounded, as is every / below
+        s->lbeta = s->phibar = beta;
+        s->oldb = s->dbar = s->epsln = s->sn = s->c1 = T(0);
+        s->cs = T(-1);
+        stop_test<T>(s, beta * beta, maxit);
+        if (!s->done) s->sinv = T(1) / beta;
+    } else if (OP == F_MR_ALFA) {
+        s->alfa = d0;
+        s->c2 = d0 / s->lbeta;
+    } else if (OP == F_MR_ROT) {
+        const T oldb = s->lbeta, beta = sqrt(d0), cs = s->cs, sn = s->sn, dbar = s->dbar, alfa = s->alfa;
+        s->oldb = oldb;
+        s->lbeta = beta;
+        s->it += 1;
+        s->oldeps = s->epsln;
+        s->delta = (cs * dbar) + (sn * alfa);
+        const T gbar = (sn * dbar) - (cs * alfa);
+        s->epsln = sn * beta;
+        s->dbar = -(cs * beta);
+        const T gamma = sqrt((gbar * gbar) + (beta * beta));
+        s->cs = gbar / gamma;
+        s->sn = beta / gamma;
+        s->phi = s->cs * s->phibar;
+        s->phibar = s->sn * s->phibar;
+        s->denom = T(1) / gamma;
+        stop_test<T>(s, s->phibar * s->phibar, maxit);
+        if (s->done) {
+            s->half = 1;   // V_MR_WX behind this launch still applies this iteration's w and x
+        } else {
+            s->sinv = T(1) / beta;
+            s->c1 = beta / oldb;   // the next iteration's: its beta / oldb are these
+        }
     }
 }
 

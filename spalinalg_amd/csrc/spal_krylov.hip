@@ -1,4 +1,4 @@
-// spal_krylov.hip -- the dot product, CG and BiCGStab on the device.  The contracts are written out in
+// spal_krylov.hip -- the dot product, CG, BiCGStab and MINRES on the device.  The contracts are written out in
 // include/spal.h: dot(a, b, n) = reduce(p), p[i] = a[i] * b[i] rounded; reduce pads with +0.0 to whole tiles of 1024,
 // halves every tile (h = 512 .. 1: e[t] = e[t] + e[t + h]) and, when there is more than one tile, reduces the tile sums
 // the same way.  The order depends on n alone, so every kernel here returns the bits of the sequential text.
@@ -23,7 +23,8 @@
 // values at the stop whatever the poll interval ("krylov_check_every") is.  Products and solves enqueued after the stop
 // still run, into work vectors nobody reads again.  BiCGStab's half-step exit needs one vector update AFTER the stop
 // was decided (x += alpha * ph): `half` is set with `done`, the next `vec` launch (V_BI_HALF) applies it, and the
-// scalar launch after that clears it.
+// scalar launch after that clears it.  MINRES (the spal_*_minres_* entry points) reuses the word: its
+// test sits in F_MR_ROT, and V_MR_WX behind it still applies that iteration's w and x -- without the next v.
 //
 // THE DRIVER HOLDS NO HANDLE LOCK ACROSS A PRODUCT OR A SOLVE: it calls the spal_*_spmv_dev_* / spal_*_trsv_dev_* entry
 // points, each of which takes what it needs itself (f5b9766: re-entering a handle's lock deadlocks).  A factor whose
@@ -48,31 +49,31 @@ struct VecArgs {
     const Scal<T> *s;   // nullptr: the stand-alone dot
     T *part0, *part1;   // tile sums of d0 / d1
     uint64_t n;
+    T *z;               // the third written operand (V_MR_WX)
+    T sg;               // MINRES: T(shift)
 };
 
 template <typename T, int OP>
-__device__ __forceinline__ void element(const VecArgs<T> &g, uint64_t i, T alpha, T beta, T omega, T &p0, T &p1) {
+__device__ __forceinline__ void element(const VecArgs<T> &g, uint64_t i, const Coef<T> &k, T &p0, T &p1) {
     p0 = T(0);
     p1 = T(0);
     if (i >= g.n) return;   // the padding: +0.0, and it is added
-    vec_update<T, OP>(g.a + i, g.b + i, g.c + i, g.d + i, g.x + i, g.y + i, alpha, beta, omega, p0, p1);
+    vec_update<T, OP>(g.a + i, g.b + i, g.c + i, g.d + i, g.x + i, g.y + i, g.z + i, k, p0, p1);
 }
 
 template <typename T, int OP>
 __global__ __launch_bounds__(kThreads) void vec(VecArgs<T> g, uint64_t tiles) {
     __shared__ T lds[2][kThreads];
-    T alpha = T(0), beta = T(0), omega = T(0);
+    Coef<T> coef = {T(0), T(0), T(0), T(0), T(0), true};
     if (g.s) {   // uniform: one word for the whole grid, written by an earlier launch
-        if (OP == V_BI_HALF ? g.s->half == 0 : g.s->done != 0) return;
-        alpha = g.s->alpha;
-        beta = g.s->beta;
-        omega = g.s->omega;
+        if (!op_live<T, OP>(g.s)) return;
+        coef = op_coef<T, OP>(g.s, g.sg);
     }
     for (uint64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
         const uint64_t i = tile * kTile + threadIdx.x;
         T p[4], q[4];
 #pragma unroll
-        for (int k = 0; k < 4; ++k) element<T, OP>(g, i + (uint64_t)k * kThreads, alpha, beta, omega, p[k], q[k]);
+        for (int k = 0; k < 4; ++k) element<T, OP>(g, i + (uint64_t)k * kThreads, coef, p[k], q[k]);
         if (Dots<OP>::n >= 1) {
             const T s = tile_sum<T>(p[0], p[1], p[2], p[3], lds[0]);
             if (threadIdx.x == 0) g.part0[tile] = s;
@@ -101,12 +102,13 @@ __global__ __launch_bounds__(kThreads) void finish(FinArgs<T> g) {
     __shared__ T lds[kThreads];
     Scal<T> *s = g.s;
     if (OP != F_STORE) {
-        if (OP == F_OMEGA && threadIdx.x == 0) s->half = 0;   // the half step, if there was one, has been applied
+        // the update the stop left behind (BiCGStab's half step, MINRES's w and x), if there was one, has been applied
+        if ((OP == F_OMEGA || OP == F_MR_ALFA) && threadIdx.x == 0) s->half = 0;
         if (s->done != 0) return;                             // uniform; this launch does not write `done` before here
     }
     const T d0 = upper_levels<T>(g.part0, g.c1, lds);
     T d1 = T(0);
-    if (OP == F_INIT || OP == F_OMEGA) d1 = upper_levels<T>(g.part1, g.c1, lds);
+    if (OP == F_INIT || OP == F_OMEGA || OP == F_MR_INIT) d1 = upper_levels<T>(g.part1, g.c1, lds);
     if (threadIdx.x != 0) return;
     if (OP == F_STORE)
         *g.out = d0;
@@ -176,21 +178,25 @@ int dot_dev(const char *fn, int device, const T *a, const T *b, uint64_t n, T *o
     return launch_finish<T, F_STORE>(fn, f, st);
 }
 
+constexpr int kMinres = 2;   // the method of the spal_*_minres_* entry points in here; spal_*_krylov_* refuse it
+
 struct Record {
     int method = 0, preconditioned = 0, reason = 0, amg = 0;
     int64_t precond_sweeps = -1;
     uint64_t iterations = 0, polls = 0;
     int64_t check_every = 0;
-    double solve_ms = 0.0;
+    double solve_ms = 0.0, shift = 0.0;
 };
 std::string info_json(const Record &r) {
-    char buf[384];
+    char buf[448], shift[64] = "";
+    if (r.method == kMinres) snprintf(shift, sizeof shift, ", \"shift\": %.17g", r.shift);
     snprintf(buf, sizeof buf,
              "{\"method\": \"%s\", \"preconditioned\": %d, \"iterations\": %llu, \"reason\": %d, \"check_every\": %lld, "
-             "\"polls\": %llu, \"solve_ms\": %.4f, \"precond_sweeps\": %lld%s}",
-             r.method == SPAL_KRYLOV_CG ? "cg" : "bicgstab", r.preconditioned, (unsigned long long)r.iterations, r.reason,
-             (long long)r.check_every, (unsigned long long)r.polls, r.solve_ms, (long long)r.precond_sweeps,
-             r.amg ? ", \"precond\": \"amg\"" : "");   // (the objects written without a hierarchy do not change)
+             "\"polls\": %llu, \"solve_ms\": %.4f, \"precond_sweeps\": %lld%s%s}",
+             r.method == SPAL_KRYLOV_CG ? "cg" : r.method == kMinres ? "minres" : "bicgstab", r.preconditioned,
+             (unsigned long long)r.iterations, r.reason, (long long)r.check_every, (unsigned long long)r.polls, r.solve_ms,
+             (long long)r.precond_sweeps, r.amg ? ", \"precond\": \"amg\"" : "",
+             shift);   // (the objects written by CG and BiCGStab without a hierarchy do not change)
     return buf;
 }
 
@@ -211,7 +217,7 @@ struct Run {
     Precond<H> pc;
     hipStream_t st;
     uint64_t n = 0, maxit = 0, c1 = 0, stride = 0;
-    T tol2 = T(0);
+    T tol2 = T(0), sg = T(0);       // sg: MINRES's T(shift)
     Scal<T> *s = nullptr;
     T *part0 = nullptr, *part1 = nullptr;
     int64_t sweeps = -1;            // m's option "trsv_sweeps"
@@ -233,8 +239,8 @@ struct Run {
         return pc.g ? amg_apply_enqueue(fn, pc.g, v, out, st) : prec_dev<T, H>(fn, pc.m, sweeps, v, out, w0, w1, st);
     }
     template <int OP>
-    int v(const T *va, const T *vb, const T *vc, const T *vd, T *vx, T *vy) {
-        return launch_vec<T, OP>(fn, VecArgs<T>{va, vb, vc, vd, vx, vy, s, part0, part1, n}, st);
+    int v(const T *va, const T *vb, const T *vc, const T *vd, T *vx, T *vy, T *vz = nullptr) {
+        return launch_vec<T, OP>(fn, VecArgs<T>{va, vb, vc, vd, vx, vy, s, part0, part1, n, vz, sg}, st);
     }
     template <int OP>
     int f(int unpreconditioned = 0) {
@@ -258,7 +264,7 @@ struct Run {
 };
 
 template <typename T, typename H>
-int krylov_run(const char *fn, H *a, int method, Precond<H> pc, const T *b, T *x, double tol, uint64_t maxit,
+int krylov_run(const char *fn, H *a, int method, Precond<H> pc, double shift, const T *b, T *x, double tol, uint64_t maxit,
                hipStream_t st, spal_krylov_info *info) {
     const uint64_t n = a->nrows;
     const bool pre = (bool)pc;
@@ -268,7 +274,8 @@ int krylov_run(const char *fn, H *a, int method, Precond<H> pc, const T *b, T *x
     SPAL_TRY(krylov_prepare(fn, a, pc.m, st, &sweeps));
     // work vectors, scratch, scalars
     const bool cg = method == SPAL_KRYLOV_CG;
-    const int nwork = cg ? (pre ? 4 : 3) : (pre ? 8 : 6);
+    const bool minres = method == kMinres;   // v, r1 / r2 / t, w1 / w2, and y with a preconditioner
+    const int nwork = minres ? (pre ? 7 : 6) : cg ? (pre ? 4 : 3) : (pre ? 8 : 6);
     const int nvec = nwork + (sweeps >= 0 ? 2 : 0);
     DevBuf vecs, parts, scal;
     const uint64_t stride = (n + 63) & ~(uint64_t)63;   // every vector on a 256-byte boundary at least
@@ -288,6 +295,7 @@ int krylov_run(const char *fn, H *a, int method, Precond<H> pc, const T *b, T *x
     R.c1 = tiles_of(n);
     R.stride = stride;
     R.tol2 = (T)(tol * tol);
+    R.sg = (T)shift;
     R.s = scal.as<Scal<T>>();
     R.part0 = parts.as<T>();
     R.part1 = parts.as<T>() + pe;
@@ -301,8 +309,13 @@ int krylov_run(const char *fn, H *a, int method, Precond<H> pc, const T *b, T *x
     R.x = x;
 
     SPAL_TRY(R.frame.begin(R.s, sizeof(Scal<T>)));
-    SPAL_TRY(krylov_start(R));
-    SPAL_TRY(cg ? cg_loop(R, maxit, (uint64_t)check_every) : bicgstab_loop(R, maxit, (uint64_t)check_every));
+    if (minres) {
+        SPAL_TRY(minres_start(R));
+        SPAL_TRY(minres_loop(R, maxit, (uint64_t)check_every));
+    } else {
+        SPAL_TRY(krylov_start(R));
+        SPAL_TRY(cg ? cg_loop(R, maxit, (uint64_t)check_every) : bicgstab_loop(R, maxit, (uint64_t)check_every));
+    }
     float ms = 0.f;
     SPAL_TRY(R.frame.end(&ms));
     if (!R.stopped) return fail(SPAL_ERR_HIP, "%s: the device did not stop after %llu iterations", fn, (unsigned long long)maxit);
@@ -317,37 +330,41 @@ int krylov_run(const char *fn, H *a, int method, Precond<H> pc, const T *b, T *x
     rec.polls = R.frame.polls;
     rec.check_every = check_every;
     rec.solve_ms = info->solve_ms;
+    rec.shift = shift;
     store_info(a, &OpState::krylov_info, info_json(rec));
     return SPAL_OK;
 }
 
 // every refusal that needs no device (a hierarchy has to agree with a in rows, device and element type)
+// (shift: 0 for CG and BiCGStab, whose entry points have none; `method` is the caller's, or kMinres from the MINRES entries)
 template <typename T, typename H>
-int krylov_check(const char *fn, H *a, int method, Precond<H> pc, const T *b, T *x, double tol, spal_krylov_info *info) {
+int krylov_check(const char *fn, H *a, int method, bool minres, Precond<H> pc, double shift, const T *b, T *x, double tol,
+                 spal_krylov_info *info) {
     if (!a || !b || !x || !info) return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: null argument", fn);
     SPAL_TRY(check_dtype<T>(fn, a->elem_size));
-    if (method != SPAL_KRYLOV_CG && method != SPAL_KRYLOV_BICGSTAB)
+    if (!minres && method != SPAL_KRYLOV_CG && method != SPAL_KRYLOV_BICGSTAB)
         return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: method = %d must be 0 (CG) or 1 (BiCGStab)", fn, method);
+    if (!std::isfinite(shift)) return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: shift = %g must be finite", fn, shift);
     SPAL_TRY((krylov_check_operands<T, H>(fn, a, pc.m, tol)));
     return pc.g ? amg_check_match(fn, pc.g, a->nrows, a->device, a->elem_size) : SPAL_OK;
 }
 
 template <typename T, typename H>
-int krylov_dev(const char *fn, H *a, int method, Precond<H> pc, const T *b, T *x, double tol, uint64_t maxit, void *stream,
-               spal_krylov_info *info) {
-    SPAL_TRY((krylov_check<T, H>(fn, a, method, pc, b, x, tol, info)));
+int krylov_dev(const char *fn, H *a, int method, bool minres, Precond<H> pc, double shift, const T *b, T *x, double tol,
+               uint64_t maxit, void *stream, spal_krylov_info *info) {
+    SPAL_TRY((krylov_check<T, H>(fn, a, method, minres, pc, shift, b, x, tol, info)));
     if (x == b) return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: x_dev == b_dev (b is read in every test of the residual)", fn);
     DeviceGuard guard(a->device);
     if (guard.status != SPAL_OK) return guard.status;
-    return krylov_run<T, H>(fn, a, method, pc, b, x, tol, maxit, (hipStream_t)stream, info);
+    return krylov_run<T, H>(fn, a, minres ? kMinres : method, pc, shift, b, x, tol, maxit, (hipStream_t)stream, info);
 }
 
 template <typename T, typename H>
-int krylov_host(const char *fn, H *a, int method, Precond<H> pc, const T *b, uint64_t b_len, T *x, uint64_t x_len, double tol,
-                uint64_t maxit, spal_krylov_info *info) {
-    SPAL_TRY((krylov_check<T, H>(fn, a, method, pc, b, x, tol, info)));
+int krylov_host(const char *fn, H *a, int method, bool minres, Precond<H> pc, double shift, const T *b, uint64_t b_len, T *x,
+                uint64_t x_len, double tol, uint64_t maxit, spal_krylov_info *info) {
+    SPAL_TRY((krylov_check<T, H>(fn, a, method, minres, pc, shift, b, x, tol, info)));
     return with_host_vectors(fn, a, b, b_len, x, x_len, [&](const T *b_dev, T *x_dev, hipStream_t st) {
-        return krylov_run<T, H>(fn, a, method, pc, b_dev, x_dev, tol, maxit, st, info);
+        return krylov_run<T, H>(fn, a, minres ? kMinres : method, pc, shift, b_dev, x_dev, tol, maxit, st, info);
     });
 }
 
@@ -391,15 +408,28 @@ int spal_dot_dev_f32(int device, const float *a_dev, const float *b_dev, uint64_
                                      uint64_t x_len, double tol, uint64_t maxit, spal_krylov_info *info) {             \
         const char *fn = "spal_" #kind "_" #name;                                                                      \
         if (NEEDS_M && !m) return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: null argument", fn);                            \
-        return krylov_host<T, spal_##kind>(fn, a, method, PRECOND, b, b_len, x, x_len, tol, maxit, info);              \
+        return krylov_host<T, spal_##kind>(fn, a, method, false, PRECOND, 0.0, b, b_len, x, x_len, tol, maxit, info);             \
     }                                                                                                                  \
     int spal_##kind##_##name##_dev_##sfx(spal_##kind##_t a, int method, M m, const T *b_dev, T *x_dev, double tol,     \
                                          uint64_t maxit, void *stream, spal_krylov_info *info) {                       \
         const char *fn = "spal_" #kind "_" #name "_dev";                                                               \
         if (NEEDS_M && !m) return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: null argument", fn);                            \
-        return krylov_dev<T, spal_##kind>(fn, a, method, PRECOND, b_dev, x_dev, tol, maxit, stream, info);             \
+        return krylov_dev<T, spal_##kind>(fn, a, method, false, PRECOND, 0.0, b_dev, x_dev, tol, maxit, stream, info);           \
+    }
+// MINRES on (A - shift I) x = b: the arguments of spal_*_krylov_* without `method`, with `shift` after m
+#define SPAL_MINRES_ENTRIES(kind, sfx, T)                                                                              \
+    int spal_##kind##_minres_##sfx(spal_##kind##_t a, spal_##kind##_t m, double shift, const T *b, uint64_t b_len,     \
+                                   T *x, uint64_t x_len, double tol, uint64_t maxit, spal_krylov_info *info) {         \
+        return krylov_host<T, spal_##kind>("spal_" #kind "_minres", a, 0, true, Precond<spal_##kind>{m, nullptr},      \
+                                           shift, b, b_len, x, x_len, tol, maxit, info);                               \
+    }                                                                                                                  \
+    int spal_##kind##_minres_dev_##sfx(spal_##kind##_t a, spal_##kind##_t m, double shift, const T *b_dev, T *x_dev,   \
+                                       double tol, uint64_t maxit, void *stream, spal_krylov_info *info) {             \
+        return krylov_dev<T, spal_##kind>("spal_" #kind "_minres_dev", a, 0, true, Precond<spal_##kind>{m, nullptr},   \
+                                          shift, b_dev, x_dev, tol, maxit, stream, info);                              \
     }
 #define SPAL_KRYLOV_KINDS(kind, sfx, T)                                                                                \
+    SPAL_MINRES_ENTRIES(kind, sfx, T)                                                                                  \
     SPAL_KRYLOV_ENTRIES(kind, krylov, sfx, T, spal_##kind##_t, false, (Precond<spal_##kind>{m, nullptr}))              \
     SPAL_KRYLOV_ENTRIES(kind, krylov_amg, sfx, T, spal_amg_t, true, (Precond<spal_##kind>{nullptr, m}))
 SPAL_KRYLOV_KINDS(csr, f64, double)
@@ -408,5 +438,6 @@ SPAL_KRYLOV_KINDS(csc, f64, double)
 SPAL_KRYLOV_KINDS(csc, f32, float)
 #undef SPAL_KRYLOV_KINDS
 #undef SPAL_KRYLOV_ENTRIES
+#undef SPAL_MINRES_ENTRIES
 
 }  // extern "C"

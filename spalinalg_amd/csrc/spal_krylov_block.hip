@@ -1,4 +1,4 @@
-// spal_krylov_block.hip -- CG and BiCGStab for a block of k right-hand sides: k INDEPENDENT iterations run
+// spal_krylov_block.hip -- CG, BiCGStab and MINRES for a block of k right-hand sides: k INDEPENDENT iterations run
 // in lockstep on shared launches.  B and X are n x k, dense and row-major (element (i, j) at [i * ld + j], ld >= k): the
 // layout of SpMM and of the block triangular solves.  Column j follows the loops written out in include/spal.h exactly
 // as spal_*_krylov_* does -- its own bb, thr, scalars, it, stop test and reason -- with A v the value spal_*_spmm_*
@@ -57,6 +57,8 @@ struct BlockVecArgs {
     T *part0, *part1;   // tile sums of d0 / d1: part[column * pe + tile]
     uint64_t n, pe;
     uint32_t k;
+    Mat<T> z;           // the third written operand (V_MR_WX)
+    T sg;               // MINRES: T(shift)
 };
 
 template <typename T, int OP, int KT>
@@ -73,13 +75,11 @@ __global__ __launch_bounds__(kThreads) void vec_block(BlockVecArgs<T> g, uint64_
         const uint64_t col = ct * KT + j;
         // per column, hence per lane: a masked lane skips its loads and stores and still reaches every barrier
         bool live = col < g.k;
-        T alpha = T(0), beta = T(0), omega = T(0);
+        Coef<T> coef = {T(0), T(0), T(0), T(0), T(0), true};
         if (live) {
             const Scal<T> *s = g.s + col;   // written by an earlier launch
-            live = OP == V_BI_HALF ? s->half != 0 : s->done == 0;
-            alpha = s->alpha;
-            beta = s->beta;
-            omega = s->omega;
+            live = op_live<T, OP>(s);
+            coef = op_coef<T, OP>(s, g.sg);
         }
         for (uint64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
             const uint64_t row0 = tile * kTile + grp;
@@ -92,14 +92,14 @@ __global__ __launch_bounds__(kThreads) void vec_block(BlockVecArgs<T> g, uint64_
                 T p[CH], q[CH];
 #pragma unroll
                 for (int m0 = 0; m0 < CH; m0 += U) {   // U elements: every load, then the arithmetic, then the stores
-                    T av[U], bv[U], cv[U], dv[U], xv[U], yv[U];
+                    T av[U], bv[U], cv[U], dv[U], xv[U], yv[U], zv[U];
                     uint64_t i[U];
                     bool in[U];
 #pragma unroll
                     for (int u = 0; u < U; ++u) {
                         i[u] = row0 + (uint64_t)(o + (m0 + u) * C) * G;
                         in[u] = live && i[u] < g.n;
-                        av[u] = bv[u] = cv[u] = dv[u] = xv[u] = yv[u] = T(0);
+                        av[u] = bv[u] = cv[u] = dv[u] = xv[u] = yv[u] = zv[u] = T(0);
                         if (in[u]) {
                             av[u] = g.a.p[i[u] * g.a.ld + col];
                             if (Reads<OP>::b) bv[u] = g.b.p[i[u] * g.b.ld + col];
@@ -107,6 +107,7 @@ __global__ __launch_bounds__(kThreads) void vec_block(BlockVecArgs<T> g, uint64_
                             if (Reads<OP>::d) dv[u] = g.d.p[i[u] * g.d.ld + col];
                             if (Reads<OP>::x) xv[u] = g.x.p[i[u] * g.x.ld + col];
                             if (Reads<OP>::y) yv[u] = g.y.p[i[u] * g.y.ld + col];
+                            if (Reads<OP>::z) zv[u] = g.z.p[i[u] * g.z.ld + col];
                         }
                     }
 #pragma unroll
@@ -114,13 +115,14 @@ __global__ __launch_bounds__(kThreads) void vec_block(BlockVecArgs<T> g, uint64_
                         p[m0 + u] = T(0);   // the padding, and a masked column: +0.0, and it is added
                         q[m0 + u] = T(0);
                         if (in[u])
-                            vec_value<T, OP>(av[u], bv[u], cv[u], dv[u], xv[u], yv[u], alpha, beta, omega, p[m0 + u], q[m0 + u]);
+                            vec_value<T, OP>(av[u], bv[u], cv[u], dv[u], xv[u], yv[u], zv[u], coef, p[m0 + u], q[m0 + u]);
                     }
 #pragma unroll
                     for (int u = 0; u < U; ++u) {
                         if (in[u]) {
                             if (Writes<OP>::x) g.x.p[i[u] * g.x.ld + col] = xv[u];
                             if (Writes<OP>::y) g.y.p[i[u] * g.y.ld + col] = yv[u];
+                            if (Writes<OP>::z) g.z.p[i[u] * g.z.ld + col] = zv[u];
                         }
                     }
                 }
@@ -177,11 +179,12 @@ __global__ __launch_bounds__(kThreads) void finish_block(BlockFinArgs<T> g) {
         Scal<T> *s = g.s + col;
         const bool done = s->done != 0;   // uniform over the workgroup: one column
         __syncthreads();                  // every thread has read it before thread 0 may write it
-        if (OP == F_OMEGA && threadIdx.x == 0) s->half = 0;   // the half step, if there was one, has been applied
+        // the update the stop left behind (BiCGStab's half step, MINRES's w and x), if there was one, has been applied
+        if ((OP == F_OMEGA || OP == F_MR_ALFA) && threadIdx.x == 0) s->half = 0;
         if (done) continue;
         const T d0 = upper_levels<T>(g.part0 + col * g.pe, g.c1, lds);
         T d1 = T(0);
-        if (OP == F_INIT || OP == F_OMEGA) d1 = upper_levels<T>(g.part1 + col * g.pe, g.c1, lds);
+        if (OP == F_INIT || OP == F_OMEGA || OP == F_MR_INIT) d1 = upper_levels<T>(g.part1 + col * g.pe, g.c1, lds);
         if (threadIdx.x == 0) scalar_step<T, OP>(s, d0, d1, g.tol2, g.maxit, g.unpreconditioned);
     }
 }
@@ -202,21 +205,25 @@ int launch_finish_block(const char *fn, const BlockFinArgs<T> &g, hipStream_t st
     return SPAL_OK;
 }
 
+constexpr int kMinres = 2;   // the method of the spal_*_minres_block_* entry points in here; spal_*_krylov_block_* refuse it
+
 struct Record {
     int method = 0, preconditioned = 0, tile = 0;
     int64_t precond_sweeps = -1, check_every = 0;
     uint64_t k = 0, iterations_min = 0, iterations_max = 0, converged = 0, polls = 0;
-    double solve_ms = 0.0;
+    double solve_ms = 0.0, shift = 0.0;
 };
 std::string info_json(const Record &r) {
-    char buf[512];
+    char buf[576], shift[64] = "";
+    if (r.method == kMinres) snprintf(shift, sizeof shift, ", \"shift\": %.17g", r.shift);
     snprintf(buf, sizeof buf,
              "{\"method\": \"%s\", \"k\": %llu, \"preconditioned\": %d, \"precond_sweeps\": %lld, \"tile\": %d, "
              "\"iterations_min\": %llu, \"iterations_max\": %llu, \"converged\": %llu, \"check_every\": %lld, "
-             "\"polls\": %llu, \"solve_ms\": %.4f}",
-             r.method == SPAL_KRYLOV_CG ? "cg" : "bicgstab", (unsigned long long)r.k, r.preconditioned,
-             (long long)r.precond_sweeps, r.tile, (unsigned long long)r.iterations_min, (unsigned long long)r.iterations_max,
-             (unsigned long long)r.converged, (long long)r.check_every, (unsigned long long)r.polls, r.solve_ms);
+             "\"polls\": %llu, \"solve_ms\": %.4f%s}",
+             r.method == SPAL_KRYLOV_CG ? "cg" : r.method == kMinres ? "minres" : "bicgstab", (unsigned long long)r.k,
+             r.preconditioned, (long long)r.precond_sweeps, r.tile, (unsigned long long)r.iterations_min,
+             (unsigned long long)r.iterations_max, (unsigned long long)r.converged, (long long)r.check_every,
+             (unsigned long long)r.polls, r.solve_ms, shift);   // (the objects written by CG and BiCGStab do not change)
     return buf;
 }
 
@@ -230,7 +237,7 @@ struct Run {
     uint64_t n = 0, maxit = 0, c1 = 0, pe = 0, stride = 0;
     uint32_t k = 0;
     int tile = 1;
-    T tol2 = T(0);
+    T tol2 = T(0), sg = T(0);   // sg: MINRES's T(shift)
     Scal<T> *s = nullptr;
     T *part0 = nullptr, *part1 = nullptr;
     int64_t sweeps = -1;   // m's option "trsv_sweeps"
@@ -247,11 +254,14 @@ struct Run {
     bool preconditioned() const { return m != nullptr; }
     int mul(Mat<T> v, Mat<T> out) { return mul_block(a, k, v.p, v.ld, out.p, out.ld, st); }
     // out = M^-1 v (out != v, both packed); without a preconditioner the loops use v itself
-    int prec(Mat<T> v, Mat<T> out) { return prec_block<T, H>(m, sweeps, k, v.p, out.p, st); }
+    // (packed: MINRES applies M^-1 to B itself, so a preconditioned MINRES call takes B with ldb == k -- block_run copies)
+    template <typename A>   // A: T, or const T where the operand is B
+    int prec(Mat<A> v, Mat<T> out) { return prec_block<T, H>(m, sweeps, k, (const T *)v.p, out.p, st); }
     template <int OP, typename A>   // A: T, or const T where the operand is B
-    int v(Mat<A> va, Mat<T> vb, Mat<T> vc, Mat<T> vd, Mat<T> vx, Mat<T> vy) {
+    int v(Mat<A> va, Mat<T> vb, Mat<T> vc, Mat<T> vd, Mat<T> vx, Mat<T> vy, Mat<T> vz = {nullptr, 0}) {
         return launch_vec_block<T, OP>(
-            fn, BlockVecArgs<T>{{va.p, va.ld}, {vb.p, vb.ld}, {vc.p, vc.ld}, {vd.p, vd.ld}, vx, vy, s, part0, part1, n, pe, k}, tile, st);
+            fn, BlockVecArgs<T>{{va.p, va.ld}, {vb.p, vb.ld}, {vc.p, vc.ld}, {vd.p, vd.ld}, vx, vy, s, part0, part1, n, pe, k, vz, sg},
+            tile, st);
     }
     template <int OP>
     int f(int unpreconditioned = 0) {
@@ -276,7 +286,7 @@ struct Run {
 };
 
 template <typename T, typename H>
-int block_run(const char *fn, H *a, int method, H *m, uint32_t k, const T *b, uint64_t ldb, T *x, uint64_t ldx,
+int block_run(const char *fn, H *a, int method, H *m, double shift, uint32_t k, const T *b, uint64_t ldb, T *x, uint64_t ldx,
               double tol, uint64_t maxit, hipStream_t st, spal_krylov_info *info) {
     const uint64_t n = a->nrows;
     const int64_t check_every = krylov_check_every_of(a, m != nullptr);
@@ -286,7 +296,8 @@ int block_run(const char *fn, H *a, int method, H *m, uint32_t k, const T *b, ui
     SPAL_TRY(krylov_prepare(fn, a, m, st, &sweeps));
     // work blocks, scratch, scalars: all at once, before the first iteration
     const bool cg = method == SPAL_KRYLOV_CG;
-    const int nwork = cg ? (m ? 4 : 3) : (m ? 8 : 6);
+    const bool minres = method == kMinres;   // v, r1 / r2 / t, w1 / w2, and y with a preconditioner
+    const int nwork = minres ? (m ? 7 : 6) : cg ? (m ? 4 : 3) : (m ? 8 : 6);
     const uint64_t pe = scratch_elems(n);
     size_t work_bytes = 0, part_bytes = 0, sweep_bytes = 0;
     if (n > (std::numeric_limits<uint64_t>::max() - 63) / k)
@@ -315,6 +326,7 @@ int block_run(const char *fn, H *a, int method, H *m, uint32_t k, const T *b, ui
     R.k = k;
     R.tile = tile;
     R.tol2 = (T)(tol * tol);
+    R.sg = (T)shift;
     R.s = scal.as<Scal<T>>();
     R.part0 = parts.as<T>();
     R.part1 = parts.as<T>() + pe * k;
@@ -322,10 +334,23 @@ int block_run(const char *fn, H *a, int method, H *m, uint32_t k, const T *b, ui
     R.blocks = blocks.as<T>();
     R.b = {b, ldb};
     R.x = {x, ldx};
+    // M^-1 takes packed blocks, and MINRES applies it to B itself (bb = dot(b, M^-1 b)): a B with padding is packed once
+    DevBuf packed;
+    if (minres && m && ldb != k && n) {
+        SPAL_HIP_TRY(packed.alloc((size_t)stride * sizeof(T)));
+        SPAL_HIP_TRY(hipMemcpy2DAsync(packed.p, (size_t)k * sizeof(T), b, (size_t)ldb * sizeof(T), (size_t)k * sizeof(T), n,
+                                      hipMemcpyDeviceToDevice, st));
+        R.b = {(const T *)packed.p, (uint64_t)k};
+    }
 
     SPAL_TRY(R.frame.begin(R.s, (size_t)k * sizeof(Scal<T>)));
-    SPAL_TRY(krylov_start(R));
-    SPAL_TRY(cg ? cg_loop(R, maxit, (uint64_t)check_every) : bicgstab_loop(R, maxit, (uint64_t)check_every));
+    if (minres) {
+        SPAL_TRY(minres_start(R));
+        SPAL_TRY(minres_loop(R, maxit, (uint64_t)check_every));
+    } else {
+        SPAL_TRY(krylov_start(R));
+        SPAL_TRY(cg ? cg_loop(R, maxit, (uint64_t)check_every) : bicgstab_loop(R, maxit, (uint64_t)check_every));
+    }
     float ms = 0.f;
     SPAL_TRY(R.frame.end(&ms));
     if (R.stopped < k)
@@ -347,6 +372,7 @@ int block_run(const char *fn, H *a, int method, H *m, uint32_t k, const T *b, ui
     rec.polls = R.frame.polls;
     rec.check_every = check_every;
     rec.solve_ms = (double)ms;
+    rec.shift = shift;
     store_info(a, &OpState::krylov_block_info, info_json(rec));
     return SPAL_OK;
 }
@@ -354,32 +380,34 @@ int block_run(const char *fn, H *a, int method, H *m, uint32_t k, const T *b, ui
 // Every refusal that needs no device; `who` begins the messages ("spal_csr_krylov_block").  The method and the block's
 // geometry come first: they need nothing of the handles.
 template <typename T, typename H>
-int block_check(const char *who, H *a, int method, H *m, uint64_t k, const T *b, uint64_t ldb, T *x, uint64_t ldx,
-                double tol, spal_krylov_info *info) {
+int block_check(const char *who, H *a, int method, bool minres, H *m, double shift, uint64_t k, const T *b, uint64_t ldb,
+                T *x, uint64_t ldx, double tol, spal_krylov_info *info) {
     if (!a || !b || !x || !info) return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: null argument", who);
-    if (method != SPAL_KRYLOV_CG && method != SPAL_KRYLOV_BICGSTAB)
+    if (!minres && method != SPAL_KRYLOV_CG && method != SPAL_KRYLOV_BICGSTAB)
         return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: method = %d must be 0 (CG) or 1 (BiCGStab)", who, method);
+    if (!std::isfinite(shift)) return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: shift = %g must be finite", who, shift);
     SPAL_TRY(check_block_geometry(who, k, ldb, ldx));
     SPAL_TRY(check_dtype<T>(who, a->elem_size));
     return krylov_check_operands<T, H>(who, a, m, tol);
 }
 
 template <typename T, typename H>
-int block_dev(const char *who, H *a, int method, H *m, uint64_t k, const T *b, uint64_t ldb, T *x, uint64_t ldx,
-              double tol, uint64_t maxit, void *stream, spal_krylov_info *info) {
-    SPAL_TRY((block_check<T, H>(who, a, method, m, k, b, ldb, x, ldx, tol, info)));
+int block_dev(const char *who, H *a, int method, bool minres, H *m, double shift, uint64_t k, const T *b, uint64_t ldb, T *x,
+              uint64_t ldx, double tol, uint64_t maxit, void *stream, spal_krylov_info *info) {
+    SPAL_TRY((block_check<T, H>(who, a, method, minres, m, shift, k, b, ldb, x, ldx, tol, info)));
     if (x == b) return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: x_dev == b_dev (B is read in every test of the residual)", who);
     DeviceGuard guard(a->device);
     if (guard.status != SPAL_OK) return guard.status;
-    return block_run<T, H>(who, a, method, m, (uint32_t)k, b, ldb, x, ldx, tol, maxit, (hipStream_t)stream, info);
+    return block_run<T, H>(who, a, minres ? kMinres : method, m, shift, (uint32_t)k, b, ldb, x, ldx, tol, maxit,
+                           (hipStream_t)stream, info);
 }
 
 template <typename T, typename H>
-int block_host(const char *who, H *a, int method, H *m, uint64_t k, const T *b, uint64_t ldb, uint64_t b_rows, T *x,
-               uint64_t ldx, uint64_t x_rows, double tol, uint64_t maxit, spal_krylov_info *info) {
-    SPAL_TRY((block_check<T, H>(who, a, method, m, k, b, ldb, x, ldx, tol, info)));
+int block_host(const char *who, H *a, int method, bool minres, H *m, double shift, uint64_t k, const T *b, uint64_t ldb,
+               uint64_t b_rows, T *x, uint64_t ldx, uint64_t x_rows, double tol, uint64_t maxit, spal_krylov_info *info) {
+    SPAL_TRY((block_check<T, H>(who, a, method, minres, m, shift, k, b, ldb, x, ldx, tol, info)));
     return with_host_block(who, a, k, b, ldb, b_rows, x, ldx, x_rows, [&](const T *b_dev, T *x_dev, hipStream_t st) {
-        return block_run<T, H>(who, a, method, m, (uint32_t)k, b_dev, k, x_dev, k, tol, maxit, st, info);
+        return block_run<T, H>(who, a, minres ? kMinres : method, m, shift, (uint32_t)k, b_dev, k, x_dev, k, tol, maxit, st, info);
     });
 }
 
@@ -411,14 +439,27 @@ extern "C" {
     int spal_##kind##_krylov_block_##sfx(spal_##kind##_t a, int method, spal_##kind##_t m, uint64_t k, const T *b,     \
                                          uint64_t ldb, uint64_t b_rows, T *x, uint64_t ldx, uint64_t x_rows,           \
                                          double tol, uint64_t maxit, spal_krylov_info *info) {                         \
-        return block_host<T, spal_##kind>("spal_" #kind "_krylov_block", a, method, m, k, b, ldb, b_rows, x, ldx,      \
-                                          x_rows, tol, maxit, info);                                                   \
+        return block_host<T, spal_##kind>("spal_" #kind "_krylov_block", a, method, false, m, 0.0, k, b, ldb, b_rows,  \
+                                          x, ldx, x_rows, tol, maxit, info);                                           \
     }                                                                                                                  \
     int spal_##kind##_krylov_block_dev_##sfx(spal_##kind##_t a, int method, spal_##kind##_t m, uint64_t k,             \
                                              const T *b_dev, uint64_t ldb, T *x_dev, uint64_t ldx, double tol,         \
                                              uint64_t maxit, void *stream, spal_krylov_info *info) {                   \
-        return block_dev<T, spal_##kind>("spal_" #kind "_krylov_block", a, method, m, k, b_dev, ldb, x_dev, ldx, tol,  \
-                                         maxit, stream, info);                                                         \
+        return block_dev<T, spal_##kind>("spal_" #kind "_krylov_block", a, method, false, m, 0.0, k, b_dev, ldb,       \
+                                         x_dev, ldx, tol, maxit, stream, info);                                        \
+    }                                                                                                                  \
+    /* MINRES on (A - shift I) X = B: the same arguments without `method`, with one `shift` for all columns */         \
+    int spal_##kind##_minres_block_##sfx(spal_##kind##_t a, spal_##kind##_t m, double shift, uint64_t k, const T *b,   \
+                                         uint64_t ldb, uint64_t b_rows, T *x, uint64_t ldx, uint64_t x_rows,           \
+                                         double tol, uint64_t maxit, spal_krylov_info *info) {                         \
+        return block_host<T, spal_##kind>("spal_" #kind "_minres_block", a, 0, true, m, shift, k, b, ldb, b_rows, x,   \
+                                          ldx, x_rows, tol, maxit, info);                                              \
+    }                                                                                                                  \
+    int spal_##kind##_minres_block_dev_##sfx(spal_##kind##_t a, spal_##kind##_t m, double shift, uint64_t k,           \
+                                             const T *b_dev, uint64_t ldb, T *x_dev, uint64_t ldx, double tol,         \
+                                             uint64_t maxit, void *stream, spal_krylov_info *info) {                   \
+        return block_dev<T, spal_##kind>("spal_" #kind "_minres_block", a, 0, true, m, shift, k, b_dev, ldb, x_dev,    \
+                                         ldx, tol, maxit, stream, info);                                               \
     }
 SPAL_KRYLOV_BLOCK_ENTRIES(csr, f64, double)
 SPAL_KRYLOV_BLOCK_ENTRIES(csr, f32, float)

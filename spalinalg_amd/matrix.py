@@ -641,6 +641,65 @@ class _DeviceMatrix:
                                                                _stream_ptr(stream), infos))
         return [_krylov_info(c) for c in infos[:int(k)]]
 
+    def minres(self, b, M=None, shift: float = 0.0, x0=None, tol: float = 1e-8, maxit: int = 1000):
+        """Solves (A - shift I) x = b by MINRES on the device (spal_*_minres_*): A symmetric, possibly
+        indefinite; `M`, a factor handle of this class, symmetric positive definite and applied as krylov() applies it.
+        Host vectors; returns (x, KrylovInfo).  Bit for bit the text written out in include/spal.h, whatever
+        "krylov_check_every" is."""
+        _refuse_amg(M, "minres()")
+        b = np.ascontiguousarray(b)
+        if b.dtype not in (np.float32, np.float64):
+            b = b.astype(self.dtype)
+        if b.ndim != 1:
+            raise TypeError("minres() takes one right-hand side, a 1-D vector")
+        x = np.zeros_like(b) if x0 is None else np.array(x0, dtype=b.dtype, order="C", copy=True)
+        if M is not None and type(M) is not type(self):
+            raise TypeError(f"M must be a {type(self).__name__} (the factor of a matrix of the same format)")
+        info = _KrylovInfoC()
+        check(self._fn(f"minres_{_sfx(b.dtype)}")(self._h, M._h if M is not None else None, C.c_double(shift), _p(b),
+                                                  u64(b.size), _p(x), u64(x.size), C.c_double(tol), u64(maxit),
+                                                  C.byref(info)))
+        return x, _krylov_info(info)
+
+    def minres_dev(self, b_ptr: int, x_ptr: int, M=None, shift: float = 0.0, tol: float = 1e-8, maxit: int = 1000,
+                   stream=None) -> KrylovInfo:
+        """Device pointers: x holds x0 on entry and the result on exit; the call polls, so it synchronises `stream`."""
+        info = _KrylovInfoC()
+        check(self._fn(f"minres_dev_{_sfx(self.dtype)}")(self._h, M._h if M is not None else None, C.c_double(shift),
+                                                         vp(b_ptr), vp(x_ptr), C.c_double(tol), u64(maxit),
+                                                         _stream_ptr(stream), C.byref(info)))
+        return _krylov_info(info)
+
+    def minres_block(self, B, M=None, shift: float = 0.0, X0=None, tol: float = 1e-8, maxit: int = 1000):
+        """Solves (A - shift I) X = B for a host block B of shape (n, k) by MINRES: k independent iterations in lockstep
+        on shared launches (spal_*_minres_block_*).  Column j is, bit for bit, the text of include/spal.h
+        on B[:, j] with SpMM's products and the block solves as M^-1; a column that has stopped is frozen while the
+        others run on.  Returns (X, [KrylovInfo] * k)."""
+        _refuse_amg(M, "minres_block()")
+        B = self._block(B, "minres_block")
+        n, k = B.shape
+        X = np.zeros_like(B) if X0 is None else np.array(X0, dtype=B.dtype, order="C", copy=True)
+        if X.shape != B.shape:
+            raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT, f"minres_block: X0 has shape {X.shape} but B {B.shape}")
+        if M is not None and type(M) is not type(self):
+            raise TypeError(f"M must be a {type(self).__name__} (the factor of a matrix of the same format)")
+        infos = (_KrylovInfoC * max(k, 1))()
+        check(self._fn(f"minres_block_{_sfx(B.dtype)}")(self._h, M._h if M is not None else None, C.c_double(shift),
+                                                        u64(k), _p(B), u64(k), u64(n), _p(X), u64(k), u64(n),
+                                                        C.c_double(tol), u64(maxit), infos))
+        return X, [_krylov_info(c) for c in infos[:k]]
+
+    def minres_block_dev(self, k: int, b_ptr: int, ldb: int, x_ptr: int, ldx: int, M=None, shift: float = 0.0,
+                         tol: float = 1e-8, maxit: int = 1000, stream=None):
+        """Device pointers of row-major blocks (element (i, j) at i * ld + j): X holds X0 on entry and the result on
+        exit; the call polls, so it synchronises `stream`.  Returns the k KrylovInfo records."""
+        infos = (_KrylovInfoC * max(int(k), 1))()
+        check(self._fn(f"minres_block_dev_{_sfx(self.dtype)}")(self._h, M._h if M is not None else None,
+                                                               C.c_double(shift), u64(k), vp(b_ptr), u64(ldb), vp(x_ptr),
+                                                               u64(ldx), C.c_double(tol), u64(maxit),
+                                                               _stream_ptr(stream), infos))
+        return [_krylov_info(c) for c in infos[:int(k)]]
+
     def gmres(self, b, M=None, x0=None, restart: int = 30, tol: float = 1e-8, maxit: int = 1000):
         """Solves A x = b by restarted GMRES(restart) on the device (spal_*_gmres_*), right-preconditioned
         by `M` as krylov() is (an ILU(0) factor handle of this class: two solves, or "trsv_sweeps" sweeps per triangle).
@@ -1404,6 +1463,52 @@ class _Compressed:
                 raise TypeError("precond_sweeps needs M, the factor it is an option of")
             M.device(device).set_option("trsv_sweeps", int(precond_sweeps))
         return self.device(device).krylov_block(B, method, None if M is None else M.device(device), X0, tol, maxit)
+
+    def _minres_args(self, who, M, shift, precond_sweeps, device):
+        """What minres() and minres_block() refuse alike before any device copy is made; returns M's device handle."""
+        _refuse_amg(M, f"{who}()")
+        if self._nrows != self._ncols:
+            raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT, f"{who}: the matrix is not square ({self._nrows} x {self._ncols})")
+        if not np.isfinite(float(shift)):
+            raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT, f"{who}: shift = {float(shift)} must be finite")
+        if M is not None and type(M) is not type(self):
+            raise TypeError(f"M must be a {type(self).__name__}, e.g. self.ilu0()")
+        if precond_sweeps is not None:
+            if M is None:
+                raise TypeError("precond_sweeps needs M, the factor it is an option of")
+            M.device(device).set_option("trsv_sweeps", int(precond_sweeps))
+        return None if M is None else M.device(device)
+
+    def minres(self, b, M=None, shift: float = 0.0, x0=None, tol: float = 1e-8, maxit: int = 1000, device: int = 0,
+               precond_sweeps=None):
+        """x with (A - shift I) x = b by MINRES on the device, for a SYMMETRIC matrix that may be indefinite (a saddle
+        point, or A - shift I with the shift inside the spectrum), where CG does not apply; symmetry is not checked.
+        `M`, when given, must be symmetric positive definite; `precond_sweeps` as in solve() (`M=D, precond_sweeps=0`
+        with D a diagonal matrix of |a_ii| is the Jacobi preconditioner).  Returns (x, info) as solve() does, with
+        info.residual_sq the recurrence's estimate of the squared residual norm, which never grows: reason 1 at maxit
+        still returns the best iterate.  Bit for bit the text of include/spal.h."""
+        b = np.asarray(b)
+        m = self._minres_args("minres", M, shift, precond_sweeps, device)
+        if b.ndim != 1 or b.shape[0] != self._nrows:
+            raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT, f"minres: b has shape {b.shape} but the matrix has {self._nrows} rows")
+        if x0 is not None and np.shape(x0) != b.shape:
+            raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT, f"minres: x0 has shape {np.shape(x0)} but b {b.shape}")
+        return self.device(device).minres(b, m, float(shift), x0, tol, maxit)
+
+    def minres_block(self, B, M=None, shift: float = 0.0, X0=None, tol: float = 1e-8, maxit: int = 1000, device: int = 0,
+                     precond_sweeps=None):
+        """X with (A - shift I) X = B for a block of right-hand sides B of shape (n, k): k independent MINRES iterations
+        in lockstep, one pass over the matrix per product for all k columns (spal_*_minres_block_*).
+        Returns (X, infos) like solve_block(); column j of X and infos[j] are bit for bit the text of include/spal.h on
+        B[:, j], whatever k, the other columns or the options are.  `M`, `shift` and `precond_sweeps` as in minres()."""
+        B = np.asarray(B)
+        m = self._minres_args("minres_block", M, shift, precond_sweeps, device)
+        if B.ndim != 2 or B.shape[0] != self._nrows:
+            raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT,
+                        f"minres_block: B has shape {B.shape} but the matrix has {self._nrows} rows")
+        if X0 is not None and np.shape(X0) != B.shape:
+            raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT, f"minres_block: X0 has shape {np.shape(X0)} but B {B.shape}")
+        return self.device(device).minres_block(B, m, float(shift), X0, tol, maxit)
 
     def gmres(self, b, M=None, x0=None, restart: int = 30, tol: float = 1e-8, maxit: int = 1000, device: int = 0,
               precond_sweeps=None):
