@@ -1102,8 +1102,8 @@ int spal_csc_gmres_block_dev_f32(spal_csc_t a, spal_csc_t m, uint64_t k, const f
  * byte count.  Nothing leaks on any failure.
  * describe() on `a` gains "eigsh" after a call: {k, which, ncv, keep, restarts, products, converged, reason, polls,
  * rotate, rotate_tile_rows, basis_bytes, rotate_ms = device time of the restarts' rotations, solve_ms}.
- * Not provided: interior eigenvalues and shift-invert (clustered EXTREME values have the polynomial filter of the next
- * section, spal_*_eigsh_filtered_*), which = LM / BE, nonsymmetric matrices, a generalised problem, block Lanczos,
+ * Not provided: shift-invert (clustered EXTREME values have the polynomial filter of the next section,
+ * spal_*_eigsh_filtered_*, INTERIOR ones the delta filter after it, spal_*_eigsh_near_*), which = LM / BE, nonsymmetric matrices, a generalised problem, block Lanczos,
  * several GPUs, capture into a graph. */
 enum { SPAL_EIGSH_LA = 0, SPAL_EIGSH_SA = 1 };
 typedef struct spal_eigsh_info {
@@ -1213,7 +1213,8 @@ int spal_csc_eigsh_dev_f32(spal_csc_t a, uint64_t k, int which, uint64_t ncv, co
  * covers both.  describe() on `a` gains "eigsh_filter" after a call: {k, which, ncv, keep, degree, interval, lo, hi,
  * a0, glo, ghi, warm_restarts, warm_products, restarts, products, converged, reason, polls, chunk, basis_bytes,
  * residual_ms, solve_ms}; an automatic call's warm-up also rewrites "eigsh", being an eigsh call.
- * Not provided: shift-invert, interior eigenvalues, an interval updated between restarts (it breaks the Lanczos
+ * Not provided: shift-invert (interior eigenvalues have the delta filter of the next section), Rayleigh-Ritz on A in
+ * the filtered space, automatic choice of the degree, an interval updated between restarts (it breaks the Lanczos
  * relation), Chebyshev as a smoother or preconditioner (cheb_apply is the piece for it), several GPUs, graph capture. */
 typedef struct spal_eigsh_filter_info {
     uint64_t restarts, products, converged;
@@ -1273,6 +1274,130 @@ int spal_csc_eigsh_filtered_dev_f32(spal_csc_t a, uint64_t k, int which, uint64_
                                     double tol, uint64_t maxit, uint64_t degree, int automatic, double lo, double hi,
                                     uint64_t warmup, float *theta, float *resid, float *x_dev, uint64_t ldx, void *stream,
                                     spal_eigsh_filter_info *info);
+
+/* ---- the Chebyshev series, the delta filter, and eigsh near sigma --------------------------------------------
+ * Not in the reference.  eigsh and its filter above reach the ENDS of the spectrum.  The k eigenvalues nearest a given
+ * sigma INSIDE it come from Lanczos on rho(A), rho a damped Chebyshev expansion of a delta function at sigma: the
+ * eigenvalues nearest sigma are the largest of rho(A).  Only products with A are needed: there is no shift-invert (the
+ * library has no sparse direct solver, and no Krylov solver of it solves a mid-spectrum shifted system: README).  The
+ * series sum_i coef_i T_i(A) x this stands on is a call of its own: the building block of matrix functions and spectral
+ * densities.  Sequential texts again, returned bit for bit in f32 and f64; T is the handle's type, every product is
+ * rounded before the sum or difference it enters (no FMA), rowsum and dot are the ones above.
+ *
+ *   cheb_series(x; d, lo, hi, coef[0..d]) = s, coef host doubles, T(.) the one conversion:
+ *     c = (lo+hi)/2;  e = (hi-lo)/2;  a1 = T(1/e);  a2 = T(2/e);  cT = T(c);  k_i = T(coef[i])
+ *     t_0 = x                                                   s[r] = k_0 * t_0[r]
+ *     t_1[r] = a1 * (rowsum(t_0, r) - (cT*t_0[r]))              s[r] = s[r] + (k_1 * t_1[r])
+ *     t_i[r] = (a2 * (rowsum(t_{i-1}, r) - (cT*t_{i-1}[r]))) - t_{i-2}[r]
+ *                                                               s[r] = s[r] + (k_i * t_i[r])     i = 2..d
+ *   The T_i are unscaled: |t_i| <= |x| while the spectrum lies in [lo, hi], so nothing overflows in f32.  An eigenvalue
+ *   outside the interval makes the t_i grow: the caller's error; it ends in values that are not finite.
+ *
+ *   cheb_delta_coefficients(d, gamma), -1 < gamma < 1, host doubles, only + - * / (no libm call):
+ *     m_0 = 1;  m_1 = gamma;  m_i = ((2*gamma)*m_{i-1}) - m_{i-2}
+ *     g_i = double(d+1-i) / double(d+1)                    (Fejer damping: the kernel is nonnegative)
+ *     u_i = g_i * m_i   for i = 0,   g_i * (2*m_i)   for i >= 1
+ *     nrm = (..((0 + u_0*m_0) + u_1*m_1) .. + u_d*m_d)     (= rho(gamma) before scaling)
+ *     coef_i = u_i / nrm
+ *   (Jackson damping needs cos(pi*i/(d+2)) and its bits would hang on a libm; the series takes any coefficients.)
+ *
+ *   eigsh near sigma = the filtered eigsh text above with these changes:
+ *   1. (glo, ghi) = gershgorin(A); not finite: stop 2.  scale = max(|glo|, |ghi|).
+ *   2. The interval.  Automatic: m = (ghi - glo)/1024, lo = glo - m, hi = ghi + m (an eigenvalue rounding has put a hair
+ *      outside Gershgorin's bounds stays inside [-1, 1]).  Given: lo < hi, both finite; the caller vouches that it
+ *      encloses the spectrum.  Either way lo < sigma < hi or the call is refused.  gamma = (sigma - c)/e;
+ *      coef = cheb_delta_coefficients(d, gamma); nrm zero or not finite: refused.
+ *   3. There is no warm-up.
+ *   4. In step(j), w = cheb_series(v_j; d, lo, hi, coef) and products += d.  The pairs of the projected problem are
+ *      ordered descending.
+ *   5. The phase end (rotate first, q_c, th_c, r_c, res_c, converged, the stops, the restart) and the outputs are the
+ *      filtered text's.  theta, resid and X so come back in DESCENDING ORDER OF THE FILTER VALUE: inside the main lobe
+ *      that is ascending distance from sigma.  The text does not re-sort.
+ *   THE TWO-TO-ONE LIMITATION: rho(lambda) = rho(lambda') for two eigenvalues at the same filter value -- exactly so for
+ *   a spectrum symmetric about sigma (the 1-D Laplacian at sigma = 2).  rho(A) then has double eigenvalues, single-vector
+ *   Lanczos sees one mixed direction per pair, and the call ends with reason 1 and residuals that do not fall.  Move
+ *   sigma off the centre of symmetry.  (A block iteration would cure it; a Rayleigh-Ritz step on A would not.)
+ * WHAT THE BITS DO NOT DEPEND ON: the handle's plan (no warm-up runs: the plan plays no part at all), "cheb_chunk",
+ * "cheb_series_form", "eigsh_rotate", ldx, the stream.
+ *
+ * On the device (spal_cheb.hip) a series step is ONE launch of the streaming step kernel above with the
+ * accumulation in its epilogue: the row's thread holds t_i[r], reads s[r], adds k_i * t_i[r] and writes it back.  Option
+ * "cheb_series_form" on `a`: 0 = automatic = 1 = that fused form; 2 = the recurrence step and a separate accumulation
+ * launch (the same bits; kept for the measurement in DESIGN 3.28).
+ *
+ * spal_*_cheb_series_*: x and out are n values (host forms: x_len = out_len = nrows), coef is coef_len = degree + 1 host
+ * doubles.  The _dev forms enqueue `degree` launches on `stream`, take two work vectors from the stream's scratch, only
+ * read x, and do not synchronise.  SPAL_ERR_INVALID_ARGUMENT before any device work: null a, x, out or coef; degree
+ * outside 1 .. 4096; coef_len != degree + 1; lo, hi or a coefficient not finite; lo >= hi; a dtype mismatch; a matrix
+ * that is not square; out overlapping x; wrong lengths.  Capturing streams and row-block handles are refused.
+ * spal_cheb_delta_coefficients: host only.  Refused: a null coef; degree outside 1 .. 4096; coef_len != degree + 1;
+ * gamma not strictly inside (-1, 1); nrm zero or not finite.  coef is written only on success.
+ * spal_*_eigsh_near_*: the filtered eigsh's arguments with sigma in place of which, and no warmup.  Refused before any
+ * device work as eigsh is, and for a degree outside 2 .. 4096, a sigma that is not finite, automatic outside {0, 1}, a
+ * given interval that is not finite, is empty or does not hold sigma strictly inside, a null info; with an automatic
+ * interval the place of sigma is refused right after Gershgorin's bounds.  Capturing streams and row-block handles are
+ * refused as eigsh refuses them.  info: eigsh's fields (products = d per step + 1 per true residual), lo, hi (0, 0:
+ * stop 2 before an interval was there), sigma, gamma, degree.  describe() on `a` gains "eigsh_near" after a call:
+ * {k, sigma, gamma, ncv, keep, degree, interval, lo, hi, glo, ghi, restarts, products, converged, reason, polls, chunk,
+ * form, basis_bytes, residual_ms, solve_ms}.
+ * Not provided: shift-invert, a block or LOBPCG-type iteration (which would cure exact ties), Rayleigh-Ritz on A in the
+ * filtered space, automatic choice of the degree, graph capture, several GPUs. */
+typedef struct spal_eigsh_near_info {
+    uint64_t restarts, products, converged;
+    int reason;
+    double solve_ms;
+    double lo, hi, sigma, gamma;
+    uint64_t degree;
+} spal_eigsh_near_info;
+int spal_cheb_delta_coefficients(uint64_t degree, double gamma, double *coef, uint64_t coef_len);   /* host only */
+int spal_csr_cheb_series_f64(spal_csr_t a, const double *x, uint64_t x_len, double *out, uint64_t out_len, uint64_t degree,
+                             double lo, double hi, const double *coef, uint64_t coef_len);
+int spal_csr_cheb_series_dev_f64(spal_csr_t a, const double *x_dev, double *out_dev, uint64_t degree, double lo, double hi,
+                                 const double *coef, uint64_t coef_len, void *stream);   /* not synchronised */
+int spal_csr_cheb_series_f32(spal_csr_t a, const float *x, uint64_t x_len, float *out, uint64_t out_len, uint64_t degree,
+                             double lo, double hi, const double *coef, uint64_t coef_len);
+int spal_csr_cheb_series_dev_f32(spal_csr_t a, const float *x_dev, float *out_dev, uint64_t degree, double lo, double hi,
+                                 const double *coef, uint64_t coef_len, void *stream);   /* not synchronised */
+int spal_csc_cheb_series_f64(spal_csc_t a, const double *x, uint64_t x_len, double *out, uint64_t out_len, uint64_t degree,
+                             double lo, double hi, const double *coef, uint64_t coef_len);
+int spal_csc_cheb_series_dev_f64(spal_csc_t a, const double *x_dev, double *out_dev, uint64_t degree, double lo, double hi,
+                                 const double *coef, uint64_t coef_len, void *stream);   /* not synchronised */
+int spal_csc_cheb_series_f32(spal_csc_t a, const float *x, uint64_t x_len, float *out, uint64_t out_len, uint64_t degree,
+                             double lo, double hi, const double *coef, uint64_t coef_len);
+int spal_csc_cheb_series_dev_f32(spal_csc_t a, const float *x_dev, float *out_dev, uint64_t degree, double lo, double hi,
+                                 const double *coef, uint64_t coef_len, void *stream);   /* not synchronised */
+int spal_csr_eigsh_near_f64(spal_csr_t a, uint64_t k, double sigma, uint64_t ncv, const double *v0, uint64_t v0_len,
+                            uint64_t seed, double tol, uint64_t maxit, uint64_t degree, int automatic, double lo, double hi,
+                            double *theta, uint64_t theta_len, double *resid, uint64_t resid_len, double *x, uint64_t ldx,
+                            uint64_t x_rows, spal_eigsh_near_info *info);
+int spal_csr_eigsh_near_dev_f64(spal_csr_t a, uint64_t k, double sigma, uint64_t ncv, const double *v0_dev, uint64_t seed,
+                                double tol, uint64_t maxit, uint64_t degree, int automatic, double lo, double hi,
+                                double *theta, double *resid, double *x_dev, uint64_t ldx, void *stream,
+                                spal_eigsh_near_info *info);   /* synchronises */
+int spal_csr_eigsh_near_f32(spal_csr_t a, uint64_t k, double sigma, uint64_t ncv, const float *v0, uint64_t v0_len,
+                            uint64_t seed, double tol, uint64_t maxit, uint64_t degree, int automatic, double lo, double hi,
+                            float *theta, uint64_t theta_len, float *resid, uint64_t resid_len, float *x, uint64_t ldx,
+                            uint64_t x_rows, spal_eigsh_near_info *info);
+int spal_csr_eigsh_near_dev_f32(spal_csr_t a, uint64_t k, double sigma, uint64_t ncv, const float *v0_dev, uint64_t seed,
+                                double tol, uint64_t maxit, uint64_t degree, int automatic, double lo, double hi,
+                                float *theta, float *resid, float *x_dev, uint64_t ldx, void *stream,
+                                spal_eigsh_near_info *info);   /* synchronises */
+int spal_csc_eigsh_near_f64(spal_csc_t a, uint64_t k, double sigma, uint64_t ncv, const double *v0, uint64_t v0_len,
+                            uint64_t seed, double tol, uint64_t maxit, uint64_t degree, int automatic, double lo, double hi,
+                            double *theta, uint64_t theta_len, double *resid, uint64_t resid_len, double *x, uint64_t ldx,
+                            uint64_t x_rows, spal_eigsh_near_info *info);
+int spal_csc_eigsh_near_dev_f64(spal_csc_t a, uint64_t k, double sigma, uint64_t ncv, const double *v0_dev, uint64_t seed,
+                                double tol, uint64_t maxit, uint64_t degree, int automatic, double lo, double hi,
+                                double *theta, double *resid, double *x_dev, uint64_t ldx, void *stream,
+                                spal_eigsh_near_info *info);   /* synchronises */
+int spal_csc_eigsh_near_f32(spal_csc_t a, uint64_t k, double sigma, uint64_t ncv, const float *v0, uint64_t v0_len,
+                            uint64_t seed, double tol, uint64_t maxit, uint64_t degree, int automatic, double lo, double hi,
+                            float *theta, uint64_t theta_len, float *resid, uint64_t resid_len, float *x, uint64_t ldx,
+                            uint64_t x_rows, spal_eigsh_near_info *info);
+int spal_csc_eigsh_near_dev_f32(spal_csc_t a, uint64_t k, double sigma, uint64_t ncv, const float *v0_dev, uint64_t seed,
+                                double tol, uint64_t maxit, uint64_t degree, int automatic, double lo, double hi,
+                                float *theta, float *resid, float *x_dev, uint64_t ldx, void *stream,
+                                spal_eigsh_near_info *info);   /* synchronises */
 
 /* ---- multicolour reordering: greedy colouring and B = P A P^T -------------------------------------------
  * Not in the reference.  An exact triangular solve costs one launch step per level; numbering the rows

@@ -7,8 +7,8 @@ CPU fallback.
 """
 from ._ffi import Panic, SpalError, cache_trim, device_count  # noqa: F401
 from .matrix import (Amg, CooMatrix, CscMatrix, CsrMatrix, DeviceCoo, DeviceCsr, DeviceCsc, EigshInfo, KrylovInfo, MultiGpuCsr,  # noqa: F401
-                     amg_aggregate, dot, dot_dev)
+                     amg_aggregate, cheb_delta_coefficients, dot, dot_dev)
 
 __all__ = ["CsrMatrix", "CscMatrix", "CooMatrix", "DeviceCsr", "DeviceCsc", "DeviceCoo", "MultiGpuCsr", "Panic",
            "SpalError", "device_count", "cache_trim", "dot", "dot_dev", "KrylovInfo", "EigshInfo", "Amg",
-           "amg_aggregate"]
+           "amg_aggregate", "cheb_delta_coefficients"]

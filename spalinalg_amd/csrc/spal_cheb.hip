@@ -23,6 +23,11 @@
 //     which other workgroups gather.  cheb_apply_enqueue rotates two buffers on that: t_i overwrites t_{i-2}.
 // Option "cheb_chunk" on `a`: entries per chunk (0 = the default above, else 256, 512, 1024, 2048 or 4096).  It moves
 // the chunk boundaries and nothing else: the bits do not depend on it.
+//
+// THE SERIES: s = sum_i k_i t_i over the unscaled recurrence, spal_*_cheb_series_*, is the same step with the
+// accumulation in its epilogue (cheb_series_step), d launches for degree d; spal_cheb_delta_coefficients is host only.
+// Option "cheb_series_form" on `a`: 0 = automatic = 1 = that fused step; 2 = the recurrence step and a separate
+// accumulation launch, the same bits (DESIGN 3.28 measured the fused form faster on both bench matrices).
 #include "krylov_kernels.hpp"
 
 #pragma clang fp contract(off)
@@ -36,14 +41,11 @@ constexpr unsigned kChebLoads = 4;         // entries a lane has in flight per b
 
 enum ChebMode { CHEB_PLAIN = 0, CHEB_FIRST = 1, CHEB_STEP = 2 };
 
-// MODE PLAIN: out[r] = rowsum(y, r).  FIRST: out[r] = alpha * (rowsum(y, r) - (cT * y[r])).  STEP: the full step.
-// The variants are separate code, not arguments: beta = 0 would turn a -0.0 into +0.0 and 0 * inf into NaN.
-template <typename T, int MODE>
-__global__ __launch_bounds__(kChebThreads) void cheb_step(const uint32_t *__restrict__ ptr, const uint32_t *__restrict__ ind,
-                                                          const T *__restrict__ val, uint64_t n, const T *y, const T *x, T *out,
-                                                          T alpha, T beta, T cT, uint32_t chunk) {
-    extern __shared__ __align__(16) unsigned char cheb_raw[];
-    T *prod = reinterpret_cast<T *>(cheb_raw);
+// rowsum(y, row) of the workgroup's 256 rows, row = blockIdx.x * 256 + threadIdx.x (+0.0 for a row >= n): the streaming
+// walk described above.  Every thread of the workgroup calls it (it holds barriers).
+template <typename T>
+__device__ __forceinline__ T cheb_rowsum(const uint32_t *__restrict__ ptr, const uint32_t *__restrict__ ind,
+                                         const T *__restrict__ val, uint64_t n, const T *y, uint32_t chunk, T *prod) {
     const uint32_t t = threadIdx.x;
     const uint64_t row0 = (uint64_t)blockIdx.x * kChebThreads, row = row0 + t;
     const uint64_t rend = row0 + kChebThreads < n ? row0 + kChebThreads : n;
@@ -81,6 +83,18 @@ __global__ __launch_bounds__(kChebThreads) void cheb_step(const uint32_t *__rest
         for (uint32_t q = lo; q < hi; ++q) acc = acc + prod[q - c0];
         __syncthreads();
     }
+    return acc;
+}
+
+// MODE PLAIN: out[r] = rowsum(y, r).  FIRST: out[r] = alpha * (rowsum(y, r) - (cT * y[r])).  STEP: the full step.
+// The variants are separate code, not arguments: beta = 0 would turn a -0.0 into +0.0 and 0 * inf into NaN.
+template <typename T, int MODE>
+__global__ __launch_bounds__(kChebThreads) void cheb_step(const uint32_t *__restrict__ ptr, const uint32_t *__restrict__ ind,
+                                                          const T *__restrict__ val, uint64_t n, const T *y, const T *x, T *out,
+                                                          T alpha, T beta, T cT, uint32_t chunk) {
+    extern __shared__ __align__(16) unsigned char cheb_raw[];
+    const T acc = cheb_rowsum<T>(ptr, ind, val, n, y, chunk, reinterpret_cast<T *>(cheb_raw));
+    const uint64_t row = (uint64_t)blockIdx.x * kChebThreads + threadIdx.x;
     if (row >= n) return;
     if (MODE == CHEB_PLAIN) {
         out[row] = acc;
@@ -89,6 +103,41 @@ __global__ __launch_bounds__(kChebThreads) void cheb_step(const uint32_t *__rest
     } else {
         out[row] = (alpha * (acc - (cT * y[row]))) - (beta * x[row]);
     }
+}
+
+// THE SERIES STEP: the step above on the UNSCALED recurrence, with the accumulation s += k_i * t_i in its
+// epilogue -- the row's thread holds t_i[r], so the series costs one read and one write of s[r] more per step and no
+// launch of its own.  FIRST: t[r] = a * (rowsum(y, r) - (cT*y[r])) and s[r] = (k0*y[r]) + (k*t[r]).  STEP: t[r] =
+// (a * (rowsum(y, r) - (cT*y[r]))) - x[r] and s[r] = s[r] + (k*t[r]).  Separate kernels from cheb_step, whose
+// instantiations and launches stay what they were.  `t` may be `x`, as out may above; s is touched by its row's thread alone.
+enum ChebSeriesMode { SERIES_FIRST = 0, SERIES_STEP = 1 };
+
+template <typename T, int MODE>
+__global__ __launch_bounds__(kChebThreads) void cheb_series_step(const uint32_t *__restrict__ ptr, const uint32_t *__restrict__ ind,
+                                                                 const T *__restrict__ val, uint64_t n, const T *y, const T *x, T *t,
+                                                                 T *s, T a, T cT, T k0, T k, uint32_t chunk) {
+    extern __shared__ __align__(16) unsigned char cheb_raw[];
+    const T acc = cheb_rowsum<T>(ptr, ind, val, n, y, chunk, reinterpret_cast<T *>(cheb_raw));
+    const uint64_t row = (uint64_t)blockIdx.x * kChebThreads + threadIdx.x;
+    if (row >= n) return;
+    if (MODE == SERIES_FIRST) {
+        const T yr = y[row];
+        const T ti = a * (acc - (cT * yr));
+        t[row] = ti;
+        s[row] = (k0 * yr) + (k * ti);
+    } else {
+        const T ti = (a * (acc - (cT * y[row]))) - x[row];
+        t[row] = ti;
+        s[row] = s[row] + (k * ti);
+    }
+}
+
+// The unfused form's accumulation: s[r] = (k0 * x[r]) + (k * t[r]) when FIRST, else s[r] = s[r] + (k * t[r]).
+template <typename T, bool FIRST>
+__global__ __launch_bounds__(kChebThreads) void cheb_series_accumulate(uint64_t n, const T *x, const T *t, T *s, T k0, T k) {
+    const uint64_t row = (uint64_t)blockIdx.x * kChebThreads + threadIdx.x;
+    if (row >= n) return;
+    s[row] = FIRST ? (k0 * x[row]) + (k * t[row]) : s[row] + (k * t[row]);
 }
 
 // Gershgorin: per row d = the stored diagonal (0 without one), sum = the |off-diagonal entries| in storage order onto
@@ -209,6 +258,99 @@ int apply_host(const char *fn, H *a, const T *x, uint64_t x_len, T *out, uint64_
     return SPAL_OK;
 }
 
+// ---- the series ------------------------------------------------------------------------------------------
+template <typename T, int MODE>
+int launch_series_step(const char *fn, const spal_csr *a, const T *y, const T *x, T *t, T *s, T alpha, T cT, T k0, T k,
+                       unsigned chunk_opt, hipStream_t st) {
+    const unsigned chunk = chunk_entries(chunk_opt, sizeof(T));
+    hipLaunchKernelGGL((cheb_series_step<T, MODE>), dim3(grid_of(a->nrows, kChebThreads)), dim3(kChebThreads), (size_t)chunk * sizeof(T),
+                       st, (const uint32_t *)a->d_rowptr, (const uint32_t *)a->d_colind, (const T *)a->d_values, a->nrows, y, x, t, s,
+                       alpha, cT, k0, k, chunk);
+    const hipError_t le = hipGetLastError();
+    if (le != hipSuccess) return fail(SPAL_ERR_HIP, "%s: launch failed: %s", fn, hipGetErrorString(le));
+    return SPAL_OK;
+}
+
+template <typename T, bool FIRST>
+int launch_series_accumulate(const char *fn, const spal_csr *a, const T *x, const T *t, T *s, T k0, T k, hipStream_t st) {
+    hipLaunchKernelGGL((cheb_series_accumulate<T, FIRST>), dim3(grid_of(a->nrows, kChebThreads)), dim3(kChebThreads), 0, st, a->nrows, x,
+                       t, s, k0, k);
+    const hipError_t le = hipGetLastError();
+    if (le != hipSuccess) return fail(SPAL_ERR_HIP, "%s: launch failed: %s", fn, hipGetErrorString(le));
+    return SPAL_OK;
+}
+
+// the refusals that need no device
+template <typename T, typename H>
+int series_check(const char *fn, H *a, const T *x, T *out, uint64_t degree, double lo, double hi, const double *coef,
+                 uint64_t coef_len) {
+    if (!a || !x || !out || !coef) return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: null argument", fn);
+    const ChebSeriesRefusal r = cheb_series_check(degree, lo, hi, coef, coef_len);
+    if (r != CHEB_SERIES_OK)
+        return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: %s (degree = %llu, coef_len = %llu, lo = %g, hi = %g)", fn,
+                    cheb_series_refusal_text(r), (unsigned long long)degree, (unsigned long long)coef_len, lo, hi);
+    SPAL_TRY(check_dtype<T>(fn, a->elem_size));
+    if (a->nrows != a->ncols)
+        return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: the matrix is not square (%llu x %llu)", fn, (unsigned long long)a->nrows,
+                    (unsigned long long)a->ncols);
+    if (row_blocks(a)) return refuse_row_blocks(fn);
+    if (overlap(x, out, (size_t)std::max<uint64_t>(a->nrows, 1) * sizeof(T)))
+        return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: out overlaps x (every step gathers the previous one)", fn);
+    return SPAL_OK;
+}
+
+template <typename H>
+void series_options_of(H *a, unsigned *chunk, int *form) {
+    std::lock_guard<std::mutex> lock(solve_handle(a)->mu);
+    *chunk = (unsigned)a->ops.cheb_chunk;
+    *form = a->ops.cheb_series_form;
+}
+
+template <typename T, typename H>
+int series_dev(const char *fn, H *a, const T *x_dev, T *out_dev, uint64_t degree, double lo, double hi, const double *coef,
+               uint64_t coef_len, void *stream) {
+    SPAL_TRY((series_check<T, H>(fn, a, x_dev, out_dev, degree, lo, hi, coef, coef_len)));
+    DeviceGuard guard(a->device);
+    if (guard.status != SPAL_OK) return guard.status;
+    const hipStream_t st = (hipStream_t)stream;
+    SPAL_TRY(refuse_capture(fn, st, "the call takes its work vectors from the stream's scratch"));
+    const ChebSeries<T> k = cheb_series_scalars<T>(lo, hi, coef, coef_len);
+    const uint64_t stride = (std::max<uint64_t>(a->nrows, 1) + 63) & ~(uint64_t)63;
+    StreamWork work;
+    SPAL_TRY(work.take(fn, st, (size_t)(2 * stride) * sizeof(T)));
+    unsigned chunk = 0;
+    int form = 0;
+    series_options_of(a, &chunk, &form);
+    return cheb_series_enqueue<T>(fn, solve_handle(a), k, x_dev, out_dev, work.as<T>(), work.as<T>() + stride, chunk, form, st);
+}
+
+template <typename T, typename H>
+int series_host(const char *fn, H *a, const T *x, uint64_t x_len, T *out, uint64_t out_len, uint64_t degree, double lo, double hi,
+                const double *coef, uint64_t coef_len) {
+    SPAL_TRY((series_check<T, H>(fn, a, x, out, degree, lo, hi, coef, coef_len)));
+    const uint64_t n = a->nrows;
+    if (x_len != n || out_len != n)
+        return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: x.len() = %llu and out.len() = %llu but the matrix has %llu rows", fn,
+                    (unsigned long long)x_len, (unsigned long long)out_len, (unsigned long long)n);
+    DeviceGuard guard(a->device);
+    if (guard.status != SPAL_OK) return guard.status;
+    const ChebSeries<T> k = cheb_series_scalars<T>(lo, hi, coef, coef_len);
+    DevBuf vecs;
+    PooledStream ps;
+    const uint64_t stride = (n + 63) & ~(uint64_t)63;
+    SPAL_HIP_TRY(vecs.alloc((size_t)std::max<uint64_t>(4 * stride, 1) * sizeof(T)));
+    SPAL_HIP_TRY(stream_acquire(&ps.s));
+    T *dx = vecs.as<T>(), *dout = dx + stride, *dw1 = dout + stride, *dw2 = dw1 + stride;
+    unsigned chunk = 0;
+    int form = 0;
+    series_options_of(a, &chunk, &form);
+    SPAL_HIP_TRY(hipMemcpyAsync(dx, x, n * sizeof(T), hipMemcpyHostToDevice, ps.s));
+    SPAL_TRY(cheb_series_enqueue<T>(fn, solve_handle(a), k, dx, dout, dw1, dw2, chunk, form, ps.s));
+    SPAL_HIP_TRY(hipMemcpyAsync(out, dout, n * sizeof(T), hipMemcpyDeviceToHost, ps.s));
+    SPAL_HIP_TRY(hipStreamSynchronize(ps.s));
+    return SPAL_OK;
+}
+
 template <typename H>
 int gershgorin_entry(const char *fn, H *a, double *glo, double *ghi) {
     if (!a || !glo || !ghi) return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: null argument", fn);
@@ -252,6 +394,36 @@ template int cheb_apply_enqueue<double>(const char *, spal_csr *, const ChebCoef
 template int cheb_apply_enqueue<float>(const char *, spal_csr *, const ChebCoeffs<float> &, const float *, float *, float *, unsigned,
                                        hipStream_t);
 
+// s = cheb_series(x) on `st`: d launches in the fused form (form 0 or 1), 2 d in the unfused one (form 2), the same bits.
+// t_i lands in w1 for odd i and in w2 for even i, so t_i overwrites t_{i-2} (except t_2, whose t_0 is the caller's x,
+// which is only read).  x, s, w1 and w2 are distinct vectors of n elements.
+template <typename T>
+int cheb_series_enqueue(const char *fn, spal_csr *a, const ChebSeries<T> &k, const T *x, T *s, T *w1, T *w2, unsigned chunk,
+                        int form, hipStream_t st) {
+    if (a->nrows == 0) return SPAL_OK;
+    const uint64_t d = k.k.size() - 1;
+    auto buf = [&](uint64_t i) { return i % 2 ? w1 : w2; };
+    if (form == 2) {
+        SPAL_TRY((launch_step<T, CHEB_FIRST>(fn, a, x, nullptr, w1, k.a1, T(0), k.cT, chunk, st)));
+        SPAL_TRY((launch_series_accumulate<T, true>(fn, a, x, (const T *)w1, s, k.k[0], k.k[1], st)));
+        for (uint64_t i = 2; i <= d; ++i) {
+            SPAL_TRY((launch_step<T, CHEB_STEP>(fn, a, (const T *)buf(i - 1), i == 2 ? x : (const T *)buf(i), buf(i), k.a2, T(1), k.cT,
+                                                chunk, st)));   // 1 * t_{i-2} is t_{i-2}: the unscaled recurrence
+            SPAL_TRY((launch_series_accumulate<T, false>(fn, a, nullptr, (const T *)buf(i), s, T(0), k.k[i], st)));
+        }
+        return SPAL_OK;
+    }
+    SPAL_TRY((launch_series_step<T, SERIES_FIRST>(fn, a, x, nullptr, w1, s, k.a1, k.cT, k.k[0], k.k[1], chunk, st)));
+    for (uint64_t i = 2; i <= d; ++i)
+        SPAL_TRY((launch_series_step<T, SERIES_STEP>(fn, a, (const T *)buf(i - 1), i == 2 ? x : (const T *)buf(i), buf(i), s, k.a2, k.cT,
+                                                     T(0), k.k[i], chunk, st)));
+    return SPAL_OK;
+}
+template int cheb_series_enqueue<double>(const char *, spal_csr *, const ChebSeries<double> &, const double *, double *, double *,
+                                         double *, unsigned, int, hipStream_t);
+template int cheb_series_enqueue<float>(const char *, spal_csr *, const ChebSeries<float> &, const float *, float *, float *, float *,
+                                        unsigned, int, hipStream_t);
+
 // (glo, ghi) of a square matrix with rows; synchronises `st`.  Both are NaN when a row's value is not finite.
 int gershgorin_run(const char *fn, spal_csr *a, hipStream_t st, double *glo, double *ghi) {
     const uint64_t n = a->nrows;
@@ -285,6 +457,16 @@ int gershgorin_run(const char *fn, spal_csr *a, hipStream_t st, double *glo, dou
 }
 
 int cheb_option(spal_csr *a, const char *key, int64_t value, OpState &s, int *status) {
+    if (!strcmp(key, "cheb_series_form")) {
+        if (value < 0 || value > 2) {
+            *status = fail(SPAL_ERR_INVALID_ARGUMENT, "cheb_series_form must be 0 (automatic), 1 (fused step) or 2 (step and a separate accumulation)");
+            return 1;
+        }
+        std::lock_guard<std::mutex> lock(a->mu);
+        s.cheb_series_form = (int)value;
+        *status = SPAL_OK;
+        return 1;
+    }
     if (strcmp(key, "cheb_chunk")) return 0;
     if (value != 0 && value != 256 && value != 512 && value != 1024 && value != 2048 && value != 4096) {
         *status = fail(SPAL_ERR_INVALID_ARGUMENT, "cheb_chunk must be 0 (16 KiB of products) or 256, 512, 1024, 2048 or 4096 entries");
@@ -316,6 +498,41 @@ SPAL_CHEB_ENTRIES(csr, f32, float)
 SPAL_CHEB_ENTRIES(csc, f64, double)
 SPAL_CHEB_ENTRIES(csc, f32, float)
 #undef SPAL_CHEB_ENTRIES
+
+#define SPAL_CHEB_SERIES_ENTRIES(kind, sfx, T)                                                                            \
+    int spal_##kind##_cheb_series_##sfx(spal_##kind##_t a, const T *x, uint64_t x_len, T *out, uint64_t out_len,            \
+                                        uint64_t degree, double lo, double hi, const double *coef, uint64_t coef_len) {     \
+        return series_host<T, spal_##kind>("spal_" #kind "_cheb_series", a, x, x_len, out, out_len, degree, lo, hi, coef,   \
+                                           coef_len);                                                                       \
+    }                                                                                                                       \
+    int spal_##kind##_cheb_series_dev_##sfx(spal_##kind##_t a, const T *x_dev, T *out_dev, uint64_t degree, double lo,      \
+                                            double hi, const double *coef, uint64_t coef_len, void *stream) {               \
+        return series_dev<T, spal_##kind>("spal_" #kind "_cheb_series_dev", a, x_dev, out_dev, degree, lo, hi, coef,        \
+                                          coef_len, stream);                                                                \
+    }
+SPAL_CHEB_SERIES_ENTRIES(csr, f64, double)
+SPAL_CHEB_SERIES_ENTRIES(csr, f32, float)
+SPAL_CHEB_SERIES_ENTRIES(csc, f64, double)
+SPAL_CHEB_SERIES_ENTRIES(csc, f32, float)
+#undef SPAL_CHEB_SERIES_ENTRIES
+
+int spal_cheb_delta_coefficients(uint64_t degree, double gamma, double *coef, uint64_t coef_len) {
+    const char *fn = "spal_cheb_delta_coefficients";
+    if (!coef) return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: null argument", fn);
+    ChebSeriesRefusal r = degree < 1 || degree > kChebSeriesMaxDegree ? CHEB_SERIES_DEGREE
+                          : coef_len != degree + 1                   ? CHEB_SERIES_LEN
+                                                                     : CHEB_SERIES_OK;
+    std::vector<double> c;
+    if (r == CHEB_SERIES_OK) {
+        c.resize(degree + 1);
+        r = cheb_delta_coefficients(degree, gamma, c.data());
+    }
+    if (r != CHEB_SERIES_OK)
+        return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: %s (degree = %llu, coef_len = %llu, gamma = %.17g)", fn,
+                    cheb_series_refusal_text(r), (unsigned long long)degree, (unsigned long long)coef_len, gamma);
+    std::copy(c.begin(), c.end(), coef);
+    return SPAL_OK;
+}
 
 int spal_csr_gershgorin(spal_csr_t a, double *glo, double *ghi) { return gershgorin_entry("spal_csr_gershgorin", a, glo, ghi); }
 int spal_csc_gershgorin(spal_csc_t a, double *glo, double *ghi) { return gershgorin_entry("spal_csc_gershgorin", a, glo, ghi); }

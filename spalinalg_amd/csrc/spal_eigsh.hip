@@ -29,6 +29,9 @@
 // recurrence of spal_cheb.hip (d launches, stream-ordered), and a phase ends with the rotation FIRST and then the true
 // residuals of the leading columns (one rowsum launch, two dots per column) behind a second poll.  The plain driver and
 // its bits are untouched: the filter is a host-side branch in Run::step.
+//
+// EIGSH NEAR SIGMA (spal_*_eigsh_near_*) is the filtered Run again with the step's product a Chebyshev SERIES,
+// the delta filter at sigma (cheb_host.hpp has its coefficients and the interval); no warm-up, the same phase end.
 #include "eigsh_host.hpp"
 #include "gmres_kernels.hpp"
 
@@ -260,6 +263,9 @@ struct Run {
     unsigned tile_rows = 0;
     const ChebCoeffs<T> *filter = nullptr;   // filtered eigsh: w = cheb_apply(v_j) through `work`
     T *work = nullptr;
+    const ChebSeries<T> *series = nullptr;   // eigsh near sigma: w = cheb_series(v_j) through `work` and `work2`
+    T *work2 = nullptr;
+    int series_form = 0;
     unsigned chunk = 0;
 
     T *v_at(uint64_t k) const { return basis + k * stride; }
@@ -276,7 +282,8 @@ struct Run {
         return SPAL_OK;
     }
     int step(unsigned j) {
-        if (filter) SPAL_TRY(cheb_apply_enqueue<T>(fn, a, *filter, (const T *)v_at(j), w, work, chunk, st));
+        if (series) SPAL_TRY(cheb_series_enqueue<T>(fn, a, *series, (const T *)v_at(j), w, work, work2, chunk, series_form, st));
+        else if (filter) SPAL_TRY(cheb_apply_enqueue<T>(fn, a, *filter, (const T *)v_at(j), w, work, chunk, st));
         else SPAL_TRY(mul_dev(a, (const T *)v_at(j), w, st));
         KRYLOV_LAUNCH((mdot<T>), grid, s, V, j, w, part, pe);
         KRYLOV_LAUNCH((mfinish<T>), j + 1, s, j, part, pe, c1, h);
@@ -645,15 +652,17 @@ unsigned cheb_chunk_of(H *a) {
     return (unsigned)a->ops.cheb_chunk;
 }
 
-// The filtered phases on [lo, hi]; fi holds a0, degree and the warm-up's counts already.
+// The filtered phases on [lo, hi]; fi holds a0, degree and the warm-up's counts already.  The step's product is the
+// recurrence with `coef`, or, where `series` is given (eigsh near sigma), the series with its coefficients.
 template <typename T, typename H>
 int filtered_phases(const char *fn, H *a, uint64_t k, int which, uint64_t ncv, const T *v0_dev, uint64_t seed, double tol_scale,
-                    uint64_t maxit, const ChebCoeffs<T> &coef, T *theta, T *resid, T *x_dev, uint64_t ldx, hipStream_t st,
-                    spal_eigsh_filter_info *fi, FilterRecord *rec) {
-    const uint64_t n = a->nrows, m = ncv, degree = coef.alpha.size();
+                    uint64_t maxit, const ChebCoeffs<T> *coef, const ChebSeries<T> *series, T *theta, T *resid, T *x_dev,
+                    uint64_t ldx, hipStream_t st, spal_eigsh_filter_info *fi, FilterRecord *rec) {
+    const uint64_t n = a->nrows, m = ncv, degree = series ? series->k.size() - 1 : coef->alpha.size();
     const int form = rotate_form_of(a);
-    // the basis (m + 1 vectors), w, the recurrence's work vector, and for the out-of-place rotation a second basis
-    const uint64_t nvec = (m + 1) + 2 + (form == 1 ? m + 1 : 0);
+    // the basis (m + 1 vectors), w, the recurrence's work vector (the series' two), and for the out-of-place rotation a
+    // second basis
+    const uint64_t nvec = (m + 1) + 2 + (series ? 1 : 0) + (form == 1 ? m + 1 : 0);
     const uint64_t stride = (n + 63) & ~(uint64_t)63;
     const uint64_t basis_bytes = nvec * stride * sizeof(T);
     DevBuf vecs, parts, scal, ydev;
@@ -699,7 +708,8 @@ int filtered_phases(const char *fn, H *a, uint64_t k, int which, uint64_t ncv, c
     R.basis = vecs.as<T>();
     R.w = R.basis + (m + 1) * stride;
     R.work = R.w + stride;
-    R.alt = form == 1 ? R.work + stride : nullptr;
+    R.work2 = series ? R.work + stride : nullptr;
+    R.alt = form == 1 ? R.work + (series ? 2 : 1) * stride : nullptr;
     R.part = parts.as<T>();
     R.y_dev = ydev.as<T>();
     R.y_pin = ypin.as<T>();
@@ -707,8 +717,13 @@ int filtered_phases(const char *fn, H *a, uint64_t k, int which, uint64_t ncv, c
     R.V.stride = stride;
     R.V.n = n;
     R.V.tiles = tiles_of(n);
-    R.filter = &coef;
+    R.filter = coef;
+    R.series = series;
     R.chunk = cheb_chunk_of(a);
+    if (series) {
+        std::lock_guard<std::mutex> lock(solve_handle(a)->mu);
+        R.series_form = a->ops.cheb_series_form;
+    }
     TruePair<T> *pairs_dev = reinterpret_cast<TruePair<T> *>(reinterpret_cast<char *>(scal.p) + pair_off);
     const TruePair<T> *pairs = tpin.as<TruePair<T>>();
 
@@ -876,8 +891,8 @@ int eigsh_filtered_run(const char *fn, H *a, uint64_t k, int which, uint64_t ncv
     fi->lo = lo;
     fi->hi = hi;
     const ChebCoeffs<T> coef = cheb_coefficients<T>(degree, lo, hi, a0);
-    SPAL_TRY((filtered_phases<T, H>(fn, a, k, which, ncv, v0_dev, seed, tol * cheb_scale(glo, ghi), maxit, coef, theta, resid, x_dev,
-                                    ldx, st, fi, &rec)));
+    SPAL_TRY((filtered_phases<T, H>(fn, a, k, which, ncv, v0_dev, seed, tol * cheb_scale(glo, ghi), maxit, &coef,
+                                    (const ChebSeries<T> *)nullptr, theta, resid, x_dev, ldx, st, fi, &rec)));
     return finish();
 }
 
@@ -940,6 +955,143 @@ int eigsh_filtered_host(const char *fn, H *a, uint64_t k, int which, uint64_t nc
     return SPAL_OK;
 }
 
+// ---- eigsh near sigma -------------------------------------------------------------------------------------
+// The filtered phases on rho(A), the Fejer-damped delta function at sigma as a Chebyshev series (spal_cheb.hip): no
+// warm-up, the interval is Gershgorin's with a margin or the caller's, everything else is the filtered call's.
+std::string near_json(const FilterRecord &f, double sigma, double gamma, int series_form) {
+    char buf[1280];
+    const Record &r = f.r;
+    snprintf(buf, sizeof buf,
+             "{\"k\": %llu, \"sigma\": %s, \"gamma\": %s, \"ncv\": %llu, \"keep\": %llu, \"degree\": %llu, \"interval\": \"%s\", "
+             "\"lo\": %s, \"hi\": %s, \"glo\": %s, \"ghi\": %s, \"restarts\": %llu, \"products\": %llu, \"converged\": %llu, "
+             "\"reason\": %d, \"polls\": %llu, \"chunk\": %llu, \"form\": \"%s\", \"basis_bytes\": %llu, \"residual_ms\": %.4f, "
+             "\"solve_ms\": %.4f}",
+             (unsigned long long)r.k, json_number(sigma).c_str(), json_number(gamma).c_str(), (unsigned long long)r.ncv,
+             (unsigned long long)r.keep, (unsigned long long)f.degree, f.automatic ? "auto" : "given", json_number(f.lo).c_str(),
+             json_number(f.hi).c_str(), json_number(f.glo).c_str(), json_number(f.ghi).c_str(), (unsigned long long)r.restarts,
+             (unsigned long long)r.products, (unsigned long long)r.converged, r.reason, (unsigned long long)r.polls,
+             (unsigned long long)f.chunk, series_form == 2 ? "unfused" : "fused", (unsigned long long)r.basis_bytes, f.residual_ms,
+             r.solve_ms);
+    return buf;
+}
+
+// x_dev: n x ldx by rows, or nullptr; theta, resid: k host values
+template <typename T, typename H>
+int eigsh_near_run(const char *fn, H *a, uint64_t k, double sigma, uint64_t ncv, const T *v0_dev, uint64_t seed, double tol,
+                   uint64_t maxit, uint64_t degree, int automatic, double lo, double hi, T *theta, T *resid, T *x_dev, uint64_t ldx,
+                   hipStream_t st, spal_eigsh_near_info *ni) {
+    SPAL_TRY(refuse_capture(fn, st, "the call polls and synchronises"));
+    *ni = spal_eigsh_near_info{};
+    ni->degree = degree;
+    ni->sigma = sigma;
+    tol = cheb_tol<T>(tol);
+    double glo = 0.0, ghi = 0.0;
+    SPAL_TRY(gershgorin_run(fn, solve_handle(a), st, &glo, &ghi));
+    FilterRecord rec;
+    rec.degree = degree;
+    rec.automatic = automatic;
+    rec.glo = glo;
+    rec.ghi = ghi;
+    rec.r.k = k;
+    rec.r.ncv = ncv;
+    int series_form = 0;
+    {
+        std::lock_guard<std::mutex> lock(solve_handle(a)->mu);
+        series_form = a->ops.cheb_series_form;
+    }
+    if (!std::isfinite(glo) || !std::isfinite(ghi)) {   // a value of the matrix is not finite
+        ni->reason = 2;
+        rec.r.reason = 2;
+        store_info(a, &OpState::eigsh_near_info, near_json(rec, sigma, 0.0, series_form));
+        return SPAL_OK;
+    }
+    if (automatic) cheb_near_auto_interval(glo, ghi, &lo, &hi);
+    std::vector<double> coef(degree + 1);
+    double gamma = 0.0;
+    const ChebSeriesRefusal r = cheb_near_filter(degree, sigma, lo, hi, &gamma, coef.data());
+    if (r != CHEB_SERIES_OK)
+        return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: %s (sigma = %.17g, the interval [%.17g, %.17g]%s)", fn, cheb_series_refusal_text(r),
+                    sigma, lo, hi, automatic ? ", Gershgorin's with its margin" : "");
+    ni->lo = lo;
+    ni->hi = hi;
+    ni->gamma = gamma;
+    const ChebSeries<T> series = cheb_series_scalars<T>(lo, hi, coef.data(), coef.size());
+    spal_eigsh_filter_info fi{};
+    SPAL_TRY((filtered_phases<T, H>(fn, a, k, SPAL_EIGSH_LA, ncv, v0_dev, seed, tol * cheb_scale(glo, ghi), maxit,
+                                    (const ChebCoeffs<T> *)nullptr, &series, theta, resid, x_dev, ldx, st, &fi, &rec)));
+    ni->restarts = fi.restarts;
+    ni->products = fi.products;
+    ni->converged = fi.converged;
+    ni->reason = fi.reason;
+    ni->solve_ms = fi.solve_ms;
+    rec.r.restarts = fi.restarts;
+    rec.r.products = fi.products;
+    rec.r.converged = fi.converged;
+    rec.r.reason = fi.reason;
+    rec.r.solve_ms = fi.solve_ms;
+    rec.lo = lo;
+    rec.hi = hi;
+    store_info(a, &OpState::eigsh_near_info, near_json(rec, sigma, gamma, series_form));
+    return SPAL_OK;
+}
+
+template <typename T, typename H>
+int eigsh_near_check(const char *fn, H *a, uint64_t k, double sigma, uint64_t ncv, double tol, uint64_t degree, int automatic,
+                     double lo, double hi, T *theta, T *resid, const T *x, uint64_t ldx, spal_eigsh_near_info *ni) {
+    if (!ni) return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: null argument", fn);
+    if (automatic != 0 && automatic != 1) return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: auto = %d must be 0 or 1", fn, automatic);
+    const ChebSeriesRefusal r = cheb_near_check(degree, sigma, automatic, lo, hi);
+    if (r != CHEB_SERIES_OK)
+        return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: %s (degree = %llu, sigma = %g, the interval [%g, %g])", fn,
+                    cheb_series_refusal_text(r), (unsigned long long)degree, sigma, lo, hi);
+    spal_eigsh_info plain;
+    return eigsh_check<T, H>(fn, a, k, SPAL_EIGSH_LA, ncv, tol, theta, resid, x, ldx, &plain);
+}
+
+template <typename T, typename H>
+int eigsh_near_dev(const char *fn, H *a, uint64_t k, double sigma, uint64_t ncv, const T *v0_dev, uint64_t seed, double tol,
+                   uint64_t maxit, uint64_t degree, int automatic, double lo, double hi, T *theta, T *resid, T *x_dev, uint64_t ldx,
+                   void *stream, spal_eigsh_near_info *ni) {
+    SPAL_TRY((eigsh_near_check<T, H>(fn, a, k, sigma, ncv, tol, degree, automatic, lo, hi, theta, resid, x_dev, ldx, ni)));
+    DeviceGuard guard(a->device);
+    if (guard.status != SPAL_OK) return guard.status;
+    return eigsh_near_run<T, H>(fn, a, k, sigma, ncv, v0_dev, seed, tol, maxit, degree, automatic, lo, hi, theta, resid, x_dev, ldx,
+                                (hipStream_t)stream, ni);
+}
+
+template <typename T, typename H>
+int eigsh_near_host(const char *fn, H *a, uint64_t k, double sigma, uint64_t ncv, const T *v0, uint64_t v0_len, uint64_t seed,
+                    double tol, uint64_t maxit, uint64_t degree, int automatic, double lo, double hi, T *theta, uint64_t theta_len,
+                    T *resid, uint64_t resid_len, T *x, uint64_t ldx, uint64_t x_rows, spal_eigsh_near_info *ni) {
+    SPAL_TRY((eigsh_near_check<T, H>(fn, a, k, sigma, ncv, tol, degree, automatic, lo, hi, theta, resid, x, ldx, ni)));
+    const uint64_t n = a->nrows;
+    if ((v0 && v0_len != n) || theta_len != k || resid_len != k || (x && x_rows != n))
+        return fail(SPAL_ERR_INVALID_ARGUMENT,
+                    "%s: v0.len() = %llu and X has %llu rows but the matrix has %llu rows; theta.len() = %llu and resid.len() = %llu but "
+                    "k = %llu", fn, (unsigned long long)v0_len, (unsigned long long)x_rows, (unsigned long long)n,
+                    (unsigned long long)theta_len, (unsigned long long)resid_len, (unsigned long long)k);
+    DeviceGuard guard(a->device);
+    if (guard.status != SPAL_OK) return guard.status;
+    size_t bytes = 0;
+    if (!bytes_of(n, k, sizeof(T), 1, &bytes))
+        return fail(SPAL_ERR_OUT_OF_MEMORY, "%s: no room for a block of %llu x %llu", fn, (unsigned long long)n, (unsigned long long)k);
+    const size_t row = (size_t)k * sizeof(T);
+    DevBuf dv, dx;
+    PooledStream ps;   // a stream of the call's own
+    if (v0) SPAL_HIP_TRY(dv.alloc(n * sizeof(T)));
+    if (x) SPAL_HIP_TRY(dx.alloc(bytes));
+    SPAL_HIP_TRY(stream_acquire(&ps.s));
+    if (v0) SPAL_HIP_TRY(hipMemcpyAsync(dv.p, v0, n * sizeof(T), hipMemcpyHostToDevice, ps.s));
+    SPAL_TRY((eigsh_near_run<T, H>(fn, a, k, sigma, ncv, v0 ? (const T *)dv.p : nullptr, seed, tol, maxit, degree, automatic, lo, hi,
+                                   theta, resid, x ? dx.as<T>() : nullptr, k, ps.s, ni)));
+    const uint64_t got = ni->reason == 2 ? 0 : ni->reason == 3 ? ni->converged : k;
+    if (x && got) {
+        SPAL_HIP_TRY(hipMemcpy2DAsync(x, (size_t)ldx * sizeof(T), dx.p, row, (size_t)got * sizeof(T), n, hipMemcpyDeviceToHost, ps.s));
+        SPAL_HIP_TRY(hipStreamSynchronize(ps.s));
+    }
+    return SPAL_OK;
+}
+
 }  // namespace
 
 int eigsh_option(spal_csr *a, const char *key, int64_t value, OpState &s, int *status) {
@@ -960,6 +1112,10 @@ int eigsh_describe_append(char *buf, size_t buf_len, const OpState &s, spal_csr 
 
 int eigsh_filter_describe_append(char *buf, size_t buf_len, const OpState &s, spal_csr *solve) {
     return info_describe_append(buf, buf_len, s, solve, "eigsh_filter", &OpState::eigsh_filter_info);
+}
+
+int eigsh_near_describe_append(char *buf, size_t buf_len, const OpState &s, spal_csr *solve) {
+    return info_describe_append(buf, buf_len, s, solve, "eigsh_near", &OpState::eigsh_near_info);
 }
 
 }  // namespace spal
@@ -1027,5 +1183,28 @@ SPAL_EIGSH_FILTERED_ENTRIES(csr, f32, float)
 SPAL_EIGSH_FILTERED_ENTRIES(csc, f64, double)
 SPAL_EIGSH_FILTERED_ENTRIES(csc, f32, float)
 #undef SPAL_EIGSH_FILTERED_ENTRIES
+
+#define SPAL_EIGSH_NEAR_ENTRIES(kind, sfx, T)                                                                              \
+    int spal_##kind##_eigsh_near_##sfx(spal_##kind##_t a, uint64_t k, double sigma, uint64_t ncv, const T *v0,              \
+                                       uint64_t v0_len, uint64_t seed, double tol, uint64_t maxit, uint64_t degree,         \
+                                       int automatic, double lo, double hi, T *theta, uint64_t theta_len, T *resid,         \
+                                       uint64_t resid_len, T *x, uint64_t ldx, uint64_t x_rows,                             \
+                                       spal_eigsh_near_info *info) {                                                        \
+        return eigsh_near_host<T, spal_##kind>("spal_" #kind "_eigsh_near", a, k, sigma, ncv, v0, v0_len, seed, tol, maxit, \
+                                               degree, automatic, lo, hi, theta, theta_len, resid, resid_len, x, ldx,       \
+                                               x_rows, info);                                                               \
+    }                                                                                                                       \
+    int spal_##kind##_eigsh_near_dev_##sfx(spal_##kind##_t a, uint64_t k, double sigma, uint64_t ncv, const T *v0_dev,      \
+                                           uint64_t seed, double tol, uint64_t maxit, uint64_t degree, int automatic,       \
+                                           double lo, double hi, T *theta, T *resid, T *x_dev, uint64_t ldx, void *stream,  \
+                                           spal_eigsh_near_info *info) {                                                    \
+        return eigsh_near_dev<T, spal_##kind>("spal_" #kind "_eigsh_near_dev", a, k, sigma, ncv, v0_dev, seed, tol, maxit,  \
+                                              degree, automatic, lo, hi, theta, resid, x_dev, ldx, stream, info);           \
+    }
+SPAL_EIGSH_NEAR_ENTRIES(csr, f64, double)
+SPAL_EIGSH_NEAR_ENTRIES(csr, f32, float)
+SPAL_EIGSH_NEAR_ENTRIES(csc, f64, double)
+SPAL_EIGSH_NEAR_ENTRIES(csc, f32, float)
+#undef SPAL_EIGSH_NEAR_ENTRIES
 
 }  // extern "C"

@@ -333,6 +333,8 @@ struct OpState {
     std::string eigsh_info;        // "eigsh": the last spal_*_eigsh_* call with this handle as A (the same lock)
     int cheb_chunk = 0;            // option "cheb_chunk": entries per chunk of the Chebyshev step kernel, 0 = 16 KiB of products (spal_cheb.hip)
     std::string eigsh_filter_info; // "eigsh_filter": the last spal_*_eigsh_filtered_* call with this handle as A (the same lock)
+    int cheb_series_form = 0;      // option "cheb_series_form": 0 = automatic, 1 = the fused series step, 2 = step and accumulation apart (spal_cheb.hip)
+    std::string eigsh_near_info;   // "eigsh_near": the last spal_*_eigsh_near_* call with this handle as A (the same lock)
     // a result of spal_*_permute / _multicolour (spal_colour.hip): written once, before the handle is
     // returned, and only read afterwards
     uint32_t *d_perm = nullptr;    // nrows: new -> old; freed by ordering_free (csr_free, csc_free)

@@ -193,6 +193,11 @@ template <typename T>
 int cheb_apply_enqueue(const char *fn, spal_csr *a, const ChebCoeffs<T> &k, const T *x, T *out, T *work, unsigned chunk,
                        hipStream_t st);
 int gershgorin_run(const char *fn, spal_csr *a, hipStream_t st, double *glo, double *ghi);
+// series: s = cheb_series(x) through w1 and w2; x, s, w1 and w2 are distinct vectors of n elements, x is
+// only read.  form: the option "cheb_series_form" (0 or 1 = the fused step, 2 = step and accumulation apart; the same bits).
+template <typename T>
+int cheb_series_enqueue(const char *fn, spal_csr *a, const ChebSeries<T> &k, const T *x, T *s, T *w1, T *w2, unsigned chunk,
+                        int form, hipStream_t st);
 
 // ---- per-operation state of a handle (spal_internal.hpp: OpState), set and described in one place -------------------
 // Each operation file implements its own: 1 = the key is this operation's and *status says how setting it went, 0 =
@@ -207,7 +212,7 @@ int ilu_option(spal_csr *a, const char *key, int64_t value, int *status);     //
 int krylov_option(spal_csr *a, const char *key, int64_t value, OpState &s, int *status);   // "krylov_check_every"
 int krylov_block_option(spal_csr *a, const char *key, int64_t value, OpState &s, int *status);   // "krylov_tile"
 int eigsh_option(spal_csr *a, const char *key, int64_t value, OpState &s, int *status);   // "eigsh_rotate"
-int cheb_option(spal_csr *a, const char *key, int64_t value, OpState &s, int *status);    // "cheb_chunk"
+int cheb_option(spal_csr *a, const char *key, int64_t value, OpState &s, int *status);    // "cheb_chunk", "cheb_series_form"
 inline int ops_set_option(OpState &s, spal_csr *solve, const char *key, int64_t value, int *status) {
     return spgemm_option(key, value, s, status) || spadd_option(key, value, s, status) ||
            spmm_option(key, value, s, status) || trsv_option(solve, key, value, status) ||
@@ -237,6 +242,8 @@ int gmres_block_describe_append(char *buf, size_t buf_len, const OpState &s, spa
 int eigsh_describe_append(char *buf, size_t buf_len, const OpState &s, spal_csr *solve);
 // the "eigsh_filter" object of a handle spal_*_eigsh_filtered_* ran with as A (spal_eigsh.hip; the same lock)
 int eigsh_filter_describe_append(char *buf, size_t buf_len, const OpState &s, spal_csr *solve);
+// the "eigsh_near" object of a handle spal_*_eigsh_near_* ran with as A (spal_eigsh.hip; the same lock)
+int eigsh_near_describe_append(char *buf, size_t buf_len, const OpState &s, spal_csr *solve);
 inline int ops_describe_append(char *buf, size_t buf_len, const OpState &s, spal_csr *solve) {
     SPAL_TRY(describe_append(buf, buf_len, "spgemm", s.spgemm_info));   // a product of spal_*_mul: how it was built
     SPAL_TRY(describe_append(buf, buf_len, "spadd", s.spadd_info));     // a result of spal_*_add / _sub / _neg
@@ -252,6 +259,7 @@ inline int ops_describe_append(char *buf, size_t buf_len, const OpState &s, spal
     SPAL_TRY(gmres_block_describe_append(buf, buf_len, s, solve));      // spal_*_gmres_block_* ran with it as A: the last call
     SPAL_TRY(eigsh_describe_append(buf, buf_len, s, solve));            // spal_*_eigsh_* ran with it as A: the last call
     SPAL_TRY(eigsh_filter_describe_append(buf, buf_len, s, solve));     // spal_*_eigsh_filtered_* ran with it as A: the last call
+    SPAL_TRY(eigsh_near_describe_append(buf, buf_len, s, solve));       // spal_*_eigsh_near_* ran with it as A: the last call
     return describe_append(buf, buf_len, "ordering", s.ordering_info);  // a result of spal_*_permute / _multicolour
 }
 

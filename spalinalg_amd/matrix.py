@@ -146,6 +146,63 @@ def _filter_args(filter_degree, filter_interval, filter_warmup):
     return degree, 0, lo, hi, warmup
 
 
+class _EigshNearInfoC(C.Structure):
+    """spal_eigsh_near_info"""
+    _fields_ = [("restarts", C.c_uint64), ("products", C.c_uint64), ("converged", C.c_uint64), ("reason", C.c_int),
+                ("solve_ms", C.c_double), ("lo", C.c_double), ("hi", C.c_double), ("sigma", C.c_double), ("gamma", C.c_double),
+                ("degree", C.c_uint64)]
+
+
+def _eigsh_near_info(c, resid) -> "EigshInfo":
+    out = _eigsh_info(c, resid)
+    out.update(lo=float(c.lo), hi=float(c.hi), sigma=float(c.sigma), gamma=float(c.gamma), degree=int(c.degree))
+    return out
+
+
+def _near_args(sigma, which, filter_degree, filter_interval):
+    """(sigma, degree, automatic, lo, hi) of an eigsh(sigma=...) call.  What scipy would answer with shift-invert is a
+    ValueError here; the rest is refused as the library does."""
+    if _eigsh_which(which) != 0 or int(filter_degree) < 2:
+        raise ValueError("eigsh: sigma is served by a Chebyshev delta filter, there is no shift-invert: it needs "
+                         "filter_degree >= 2 (the degree sets the resolution) and takes no which='SA'")
+    sigma, degree = float(sigma), int(filter_degree)
+    if degree > 4096:
+        raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT, f"eigsh: filter_degree = {degree} must be 2 .. 4096 with sigma")
+    if not np.isfinite(sigma):
+        raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT, f"eigsh: sigma = {sigma} must be finite")
+    if filter_interval is None:
+        return sigma, degree, 1, 0.0, 0.0
+    lo, hi = (float(v) for v in filter_interval)
+    if not (np.isfinite(lo) and np.isfinite(hi) and lo < hi):
+        raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT, f"eigsh: filter_interval = [{lo}, {hi}] must be finite with lo < hi")
+    if not lo < sigma < hi:
+        raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT, f"eigsh: sigma = {sigma} must lie strictly inside filter_interval = [{lo}, {hi}]")
+    return sigma, degree, 0, lo, hi
+
+
+def _series_args(coef, lo, hi):
+    """(coef as contiguous doubles, degree, lo, hi) of a cheb_series call, refused as the library does"""
+    coef = np.ascontiguousarray(coef, dtype=np.float64)
+    lo, hi = float(lo), float(hi)
+    if coef.ndim != 1 or not 2 <= coef.size <= 4097:
+        raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT, f"cheb_series: coef has shape {coef.shape}: degree + 1 values, degree 1 .. 4096")
+    if not (np.isfinite(lo) and np.isfinite(hi)) or not np.all(np.isfinite(coef)):
+        raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT, "cheb_series: lo, hi and every coefficient must be finite")
+    if not lo < hi:
+        raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT, f"cheb_series: lo = {lo} must be less than hi = {hi}")
+    return coef, coef.size - 1, lo, hi
+
+
+def cheb_delta_coefficients(degree: int, gamma: float) -> np.ndarray:
+    """The degree + 1 Chebyshev coefficients of the Fejer-damped delta function at gamma in (-1, 1), scaled so that the
+    series is 1 at gamma (spal_cheb_delta_coefficients): host only, only + - * / on doubles.  With
+    gamma = (sigma - (lo+hi)/2) / ((hi-lo)/2) they are the filter of eigsh(sigma=...); pass them to cheb_series()."""
+    degree = int(degree)
+    coef = np.empty(max(degree, 0) + 1, dtype=np.float64)
+    check(_ffi.lib().spal_cheb_delta_coefficients(u64(max(degree, 0)), C.c_double(gamma), _p(coef), u64(coef.size)))
+    return coef
+
+
 _EIGSH_WHICH = {"LA": 0, "SA": 1}
 
 
@@ -773,6 +830,27 @@ class _DeviceMatrix:
         check(self._fn(f"cheb_apply_dev_{_sfx(self.dtype)}")(self._h, vp(x_ptr or None), vp(out_ptr or None), u64(degree),
                                                              C.c_double(lo), C.c_double(hi), C.c_double(a0), _stream_ptr(stream)))
 
+    def cheb_series(self, x, coef, lo: float, hi: float) -> np.ndarray:
+        """s = sum_i coef[i] T_i(B) x, B = A mapped from [lo, hi] onto [-1, 1], T_i the unscaled Chebyshev polynomials
+        (spal_*_cheb_series_*): host vector in, host vector out, coef = degree + 1 doubles.  The building
+        block of matrix functions and spectral densities.  [lo, hi] must enclose the spectrum, else the T_i grow.  Bit
+        for bit the text of include/spal.h, whatever the handle's plan is."""
+        x = np.ascontiguousarray(x, dtype=self.dtype)
+        coef = np.ascontiguousarray(coef, dtype=np.float64)
+        out = np.empty(self.shape()[0], dtype=self.dtype)
+        check(self._fn(f"cheb_series_{_sfx(self.dtype)}")(self._h, _p(x), u64(x.size), _p(out), u64(out.size),
+                                                          u64(max(coef.size, 1) - 1), C.c_double(lo), C.c_double(hi), _p(coef),
+                                                          u64(coef.size)))
+        return out
+
+    def cheb_series_dev(self, x_ptr: int, out_ptr: int, coef, lo: float, hi: float, stream=None) -> None:
+        """Device pointers (out must not overlap x, which is only read); degree launches enqueued on `stream`, not
+        synchronised.  coef is read before the call returns."""
+        coef = np.ascontiguousarray(coef, dtype=np.float64)
+        check(self._fn(f"cheb_series_dev_{_sfx(self.dtype)}")(self._h, vp(x_ptr or None), vp(out_ptr or None),
+                                                              u64(max(coef.size, 1) - 1), C.c_double(lo), C.c_double(hi), _p(coef),
+                                                              u64(coef.size), _stream_ptr(stream)))
+
     def gershgorin(self):
         """(glo, ghi): Gershgorin's enclosure of this square matrix's spectrum, in double (spal_*_gershgorin)."""
         lo, hi = C.c_double(), C.c_double()
@@ -792,8 +870,22 @@ class _DeviceMatrix:
         pairs = 0 if info.reason == 2 else int(info.converged) if info.reason == 3 else k
         return theta[:pairs], (None if X is None else X[:, :pairs]), _eigsh_filter_info(info, resid[:pairs])
 
+    def _eigsh_near(self, k, ncv, v0, seed, tol, maxit, return_eigenvectors, sigma, degree, automatic, lo, hi):
+        n = self.shape()[0]
+        theta = np.zeros(k, dtype=self.dtype)
+        resid = np.zeros(k, dtype=self.dtype)
+        X = np.zeros((n, k), dtype=self.dtype) if return_eigenvectors else None
+        info = _EigshNearInfoC()
+        check(self._fn(f"eigsh_near_{_sfx(self.dtype)}")(
+            self._h, u64(k), C.c_double(sigma), u64(ncv), None if v0 is None else _p(v0), u64(0 if v0 is None else n), u64(seed),
+            C.c_double(tol), u64(maxit), u64(degree), C.c_int(automatic), C.c_double(lo), C.c_double(hi), _p(theta), u64(k),
+            _p(resid), u64(k), None if X is None else _p(X), u64(k), u64(n), C.byref(info)))
+        pairs = 0 if info.reason == 2 else int(info.converged) if info.reason == 3 else k
+        return theta[:pairs], (None if X is None else X[:, :pairs]), _eigsh_near_info(info, resid[:pairs])
+
     def eigsh(self, k: int = 6, which="LA", ncv=None, v0=None, seed: int = 0, tol: float = 0, maxit: int = 1000,
-              return_eigenvectors: bool = True, filter_degree: int = 0, filter_interval=None, filter_warmup: int = 5):
+              return_eigenvectors: bool = True, filter_degree: int = 0, filter_interval=None, filter_warmup: int = 5,
+              sigma=None):
         """The k largest (which="LA") or smallest ("SA") eigenvalues of this symmetric matrix and their vectors, by
         thick-restart Lanczos with full orthogonalisation on the device (spal_*_eigsh_*); symmetry is not
         checked.  Returns (theta, X, info): theta in the order of `which` (LA descending, SA ascending), X of shape
@@ -806,15 +898,25 @@ class _DeviceMatrix:
         DESIGN 3.26), the remedy for CLUSTERED extreme eigenvalues: filter_interval=None takes the interval to damp from
         `filter_warmup` restarts of the plain iteration, (lo, hi) gives it; convergence is then decided on true
         residuals, <= tol * max(|glo|, |ghi|) of Gershgorin's bounds, tol=0 is 256 machine epsilons, info.resid holds
-        them and info gains warm_restarts, warm_products, lo, hi, a0, degree.  filter_degree=0 is the plain call."""
+        them and info gains warm_restarts, warm_products, lo, hi, a0, degree.  filter_degree=0 is the plain call.
+        sigma=s returns the k eigenvalues NEAREST s, inside the spectrum too (spal_*_eigsh_near_*): Lanczos
+        on a Chebyshev delta filter of degree filter_degree >= 2 at s -- there is no shift-invert, so a degree is
+        required, and which="SA" is a ValueError.  filter_interval=None is Gershgorin's interval with a margin, (lo, hi)
+        must enclose the spectrum; s lies strictly inside.  filter_warmup is ignored.  The pairs come in DESCENDING ORDER
+        OF THE FILTER VALUE, which near s is ascending distance from s; convergence is on true residuals as above and
+        info gains lo, hi, sigma, gamma, degree.  TWO-TO-ONE: eigenvalues at the same filter value -- mirror images in a
+        spectrum symmetric about s -- are not separated; the call then ends with reason 1.  Move s off the centre."""
         n, ncols, _ = self.shape()
         tol_given = float(tol)
+        near = None if sigma is None else _near_args(sigma, which, filter_degree, filter_interval)
         k, ncv, tol = _eigsh_args(n, ncols, k, ncv, tol, self.dtype)
         w = _eigsh_which(which)
         if v0 is not None:
             v0 = np.ascontiguousarray(v0, dtype=self.dtype)
             if v0.shape != (n,):
                 raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT, f"eigsh: v0 has shape {v0.shape} but the matrix has {n} rows")
+        if near is not None:
+            return self._eigsh_near(k, ncv, v0, seed, tol_given, maxit, return_eigenvectors, *near)
         if filter_degree:
             return self._eigsh_filtered(k, w, ncv, v0, seed, tol_given, maxit, return_eigenvectors,
                                         *_filter_args(filter_degree, filter_interval, filter_warmup))
@@ -832,17 +934,27 @@ class _DeviceMatrix:
 
     def eigsh_dev(self, k: int, theta, resid, x_ptr: int, ldx: int, which="LA", ncv=None, v0_ptr: int = 0, seed: int = 0,
                   tol: float = 0, maxit: int = 1000, stream=None, filter_degree: int = 0, filter_interval=None,
-                  filter_warmup: int = 5):
+                  filter_warmup: int = 5, sigma=None):
         """Device pointers: v0_ptr (0: the text's start vector) and x_ptr (0: values only; else n x k row-major with
         leading dimension ldx); theta and resid are host arrays of k values of the handle's dtype, written in place.
         The call polls, so it synchronises `stream`.  Returns the EigshInfo.  filter_degree > 0: the filtered call, as
-        in eigsh()."""
+        in eigsh(); sigma: the k pairs nearest sigma, as in eigsh()."""
         n, ncols, _ = self.shape()
         tol_given = float(tol)
+        near = None if sigma is None else _near_args(sigma, which, filter_degree, filter_interval)
         k, ncv, tol = _eigsh_args(n, ncols, k, ncv, tol, self.dtype)
         for a in (theta, resid):
             if not isinstance(a, np.ndarray) or a.dtype != self.dtype or a.shape != (k,) or not a.flags.c_contiguous:
                 raise TypeError(f"theta and resid must be contiguous arrays of {k} {self.dtype} values")
+        if near is not None:
+            sg, degree, automatic, lo, hi = near
+            ninfo = _EigshNearInfoC()
+            check(self._fn(f"eigsh_near_dev_{_sfx(self.dtype)}")(
+                self._h, u64(k), C.c_double(sg), u64(ncv), vp(v0_ptr or None), u64(seed), C.c_double(tol_given), u64(maxit),
+                u64(degree), C.c_int(automatic), C.c_double(lo), C.c_double(hi), _p(theta), _p(resid), vp(x_ptr or None), u64(ldx),
+                _stream_ptr(stream), C.byref(ninfo)))
+            pairs = 0 if ninfo.reason == 2 else int(ninfo.converged) if ninfo.reason == 3 else k
+            return _eigsh_near_info(ninfo, resid[:pairs])
         if filter_degree:
             degree, automatic, lo, hi, warmup = _filter_args(filter_degree, filter_interval, filter_warmup)
             finfo = _EigshFilterInfoC()
@@ -1556,6 +1668,19 @@ class _Compressed:
             raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT, f"cheb_apply: x has shape {np.shape(x)} but the matrix has {self._nrows} rows")
         return self.device(device).cheb_apply(x, degree, lo, hi, a0)
 
+    def cheb_series(self, x, coef, lo: float, hi: float, device: int = 0) -> np.ndarray:
+        """sum_i coef[i] T_i(B) x with B = A mapped from [lo, hi] onto [-1, 1] and T_i the unscaled Chebyshev polynomials
+        (DESIGN 3.28): the text of include/spal.h bit for bit.  coef holds degree + 1 doubles, degree 1 .. 4096
+        (cheb_delta_coefficients() gives the delta filter's); [lo, hi] must enclose the spectrum.  Refused before
+        anything is copied to a device: a bad degree, values that are not finite, lo >= hi, a matrix that is not square,
+        an x of another length."""
+        coef, _, lo, hi = _series_args(coef, lo, hi)
+        if self._nrows != self._ncols:
+            raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT, f"cheb_series: the matrix is not square ({self._nrows} x {self._ncols})")
+        if np.shape(x) != (self._nrows,):
+            raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT, f"cheb_series: x has shape {np.shape(x)} but the matrix has {self._nrows} rows")
+        return self.device(device).cheb_series(x, coef, lo, hi)
+
     def gershgorin(self, device: int = 0):
         """(glo, ghi): Gershgorin's enclosure of the spectrum, in double, computed on the device."""
         if self._nrows != self._ncols:
@@ -1564,7 +1689,7 @@ class _Compressed:
 
     def eigsh(self, k: int = 6, which="LA", ncv=None, v0=None, seed: int = 0, tol: float = 0, maxit: int = 1000,
               return_eigenvectors: bool = True, device: int = 0, filter_degree: int = 0, filter_interval=None,
-              filter_warmup: int = 5):
+              filter_warmup: int = 5, sigma=None):
         """theta, X, info = a.eigsh(k): the k largest (which="LA") or smallest ("SA") eigenvalues of this SYMMETRIC
         matrix and their vectors, by thick-restart Lanczos with full orthogonalisation on the device (DESIGN 3.25);
         symmetry is not checked, as with CG.  theta comes in the order of `which`, X has shape (n, k) (None with
@@ -1576,15 +1701,26 @@ class _Compressed:
         CLUSTERED extreme eigenvalues: filter_degree > 0 runs the iteration on a Chebyshev polynomial of A of that degree
         (DESIGN 3.26), which needs many times fewer restarts; filter_interval=None finds the interval to damp with
         filter_warmup plain restarts, (lo, hi) gives it.  Convergence is then decided on true residuals against
-        tol * max(|glo|, |ghi|) of Gershgorin's bounds, and tol=0 means 256 machine epsilons."""
+        tol * max(|glo|, |ghi|) of Gershgorin's bounds, and tol=0 means 256 machine epsilons.
+        INTERIOR eigenvalues: sigma=s returns the k eigenvalues nearest s by Lanczos on a Chebyshev delta filter at s
+        (DESIGN 3.28).  There is no shift-invert: filter_degree >= 2 is required (it sets the resolution: the filter
+        separates eigenvalues about (hi - lo) / degree apart) and which="SA" raises ValueError.  filter_interval=None is
+        Gershgorin's interval with a margin; a given (lo, hi) must enclose the spectrum and hold s strictly inside;
+        filter_warmup is ignored.  The pairs come in DESCENDING ORDER OF THE FILTER VALUE -- near s that is ascending
+        distance from s -- and are not re-sorted; convergence is on true residuals.  THE TWO-TO-ONE LIMITATION: two
+        eigenvalues with the same filter value (mirror images in a spectrum symmetric about s, such as the 1-D
+        Laplacian's about 2) cannot be separated by a single-vector iteration; the call ends with reason 1 and
+        residuals that do not fall.  Move s off the centre of symmetry."""
+        if sigma is not None:
+            _near_args(sigma, which, filter_degree, filter_interval)
         _eigsh_args(self._nrows, self._ncols, k, ncv, tol, self.dtype)
         _eigsh_which(which)
         if v0 is not None and np.shape(v0) != (self._nrows,):
             raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT, f"eigsh: v0 has shape {np.shape(v0)} but the matrix has {self._nrows} rows")
-        if filter_degree:
+        if filter_degree and sigma is None:
             _filter_args(filter_degree, filter_interval, filter_warmup)
         return self.device(device).eigsh(k, which, ncv, v0, seed, tol, maxit, return_eigenvectors, filter_degree,
-                                         filter_interval, filter_warmup)
+                                         filter_interval, filter_warmup, sigma)
 
     def gmres_block(self, B, M=None, X0=None, restart: int = 30, tol: float = 1e-8, maxit: int = 1000, device: int = 0,
                     precond_sweeps=None):

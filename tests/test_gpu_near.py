@@ -1,0 +1,425 @@
+"""The Chebyshev series and eigsh near sigma on the device against their sequential texts (tests/near_ref.py): raw bits,
+f64 and f32, CSR and CSC.
+
+The series step is the streaming step kernel of the filter with the accumulation in its epilogue: a workgroup owns 256
+rows and walks their entries in chunks ("cheb_chunk").  The shapes below put rows, empty rows and whole workgroups on
+every side of those sizes; "cheb_series_form" 2 runs the same text as a recurrence step and a separate accumulation."""
+import ctypes as C
+import functools
+import zlib
+
+import numpy as np
+import pytest
+
+import spalinalg_amd as sp
+from spalinalg_amd import _ffi
+from tests import cheb_ref as cr
+from tests import eigsh_ref as er
+from tests import near_ref as nr
+from tests import trsv_ref as tr
+from tests.test_gpu_cheb import from_rows, laplacian, make, sfx, some
+from tests.test_gpu_eigsh import lib_jacobi, named
+
+pytestmark = pytest.mark.gpu
+
+DTYPES = [np.float64, np.float32]
+IDS = ["f64", "f32"]
+ROWS = 256
+DEGREES = (1, 2, 3, 17)
+LO, HI = -1.0, 1.0                             # every row's |entries| sum to at most 1
+DESCRIBE_KEYS = {"k", "sigma", "gamma", "ncv", "keep", "degree", "interval", "lo", "hi", "glo", "ghi", "restarts", "products",
+                 "converged", "reason", "polls", "chunk", "form", "basis_bytes", "residual_ms", "solve_ms"}
+u = C.c_uint64
+dbl = C.c_double
+
+
+@functools.lru_cache(maxsize=None)
+def shape(name, dtype):
+    """(n, rowptr, colind, values); shared, read-only"""
+    rng = np.random.default_rng(zlib.crc32(f"near/{name}".encode()))
+    if name.startswith("n="):                   # 1 + r % 7 entries per row
+        n = int(name[2:])
+        mat = from_rows(n, {r: some(rng, n, 1 + r % 7) for r in range(n)}, dtype, rng)
+    elif name == "empty-rows":                  # empty at the start, across a workgroup's edge, at the end
+        n = 3 * ROWS - 20
+        mat = from_rows(n, {r: some(rng, n, 5) for r in range(n) if 9 < r < 250 or 262 < r < n - 10}, dtype, rng)
+    elif name == "row-300":                     # one row of 300 entries after 100 of 2: it crosses 256 at entry 56 of its own
+        n = 600
+        rows = {r: some(rng, n, 2) for r in range(n)}
+        rows[100] = some(rng, n, 300)
+        mat = from_rows(n, rows, dtype, rng)
+    elif name == "block=chunk":                 # 2 entries per row: a workgroup's 512 entries end exactly on a chunk of 256 or 512
+        n = 2 * ROWS + 5
+        mat = from_rows(n, {r: some(rng, n, 2) for r in range(n)}, dtype, rng)
+    else:
+        raise KeyError(name)
+    for a in mat[1:]:
+        a.setflags(write=False)
+    return mat
+
+
+def vector(n, dtype):
+    return np.random.default_rng(n).uniform(-1, 1, n).astype(dtype)
+
+
+def coefficients(degree, seed=0):
+    return np.random.default_rng(100 * degree + seed).uniform(-1, 1, degree + 1)
+
+
+# ---- 1. the series ---------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
+@pytest.mark.parametrize("kind", ["csr", "csc"])
+@pytest.mark.parametrize("name", ["n=1", "n=255", "n=256", "n=257", "n=70001", "empty-rows", "row-300", "block=chunk"])
+def test_cheb_series_is_the_text(name, kind, dtype):
+    mat = shape(name, dtype)
+    n = mat[0]
+    a = make(kind, mat)
+    x = vector(n, dtype)
+    for degree in DEGREES:
+        coef = coefficients(degree)
+        tr.assert_same_bits(a.cheb_series(x, coef, LO, HI), nr.cheb_series(mat[1], mat[2], mat[3], x, LO, HI, coef))
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
+@pytest.mark.parametrize("name", ["row-300", "block=chunk", "empty-rows"])
+def test_the_chunk_and_the_form_do_not_change_the_bits(name, dtype):
+    mat = shape(name, dtype)
+    a = make("csr", mat)
+    dev = a.device()
+    x = vector(mat[0], dtype)
+    coef = coefficients(5)
+    want = nr.cheb_series(mat[1], mat[2], mat[3], x, LO, HI, coef)
+    for form in (0, 1, 2):
+        dev.set_option("cheb_series_form", form)
+        for chunk in (256, 512, 4096, 0):
+            dev.set_option("cheb_chunk", chunk)
+            tr.assert_same_bits(a.cheb_series(x, coef, LO, HI), want)
+    with pytest.raises(sp.Panic, match="cheb_series_form must be 0"):
+        dev.set_option("cheb_series_form", 3)
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
+def test_degree_4096_on_257_rows(dtype):
+    """The 1-D Laplacian of 257 rows on Gershgorin's interval with its margin: the T_i stay bounded by |x| at any degree."""
+    rowptr, colind, values = cr.laplace_1d_csr(257, dtype)
+    a = make("csr", (257, rowptr, colind, values))
+    x = vector(257, dtype)
+    lo, hi = nr.auto_interval(0.0, 4.0)
+    coef = nr.delta_coefficients(4096, 0.3)
+    got = a.cheb_series(x, coef, lo, hi)
+    tr.assert_same_bits(got, nr.cheb_series(rowptr, colind, values, x, lo, hi, coef))
+    assert np.all(np.isfinite(got)) and np.abs(got).max() <= 4.0 * np.abs(x).max()
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
+@pytest.mark.parametrize("kind", ["csr", "csc"])
+def test_zero_coefficients_and_special_values_go_where_the_text_says(kind, dtype):
+    mat = shape("n=257", dtype)
+    n, rowptr, colind, values = mat
+    a = make(kind, mat)
+    coef = np.array([0.0, 0.5, -0.0, 0.0, 0.25, -0.0])
+    x = vector(n, dtype)
+    tr.assert_same_bits(a.cheb_series(x, coef, LO, HI), nr.cheb_series(rowptr, colind, values, x, LO, HI, coef))
+    # coef = e_d: the series is the unscaled t_d (plus the +0.0 terms before it)
+    for degree in (1, 2, 3, 17):
+        unit = np.zeros(degree + 1)
+        unit[degree] = 1.0
+        s, t = nr.cheb_series(rowptr, colind, values, x, LO, HI, unit, keep_t=True)
+        got = a.cheb_series(x, unit, LO, HI)
+        tr.assert_same_bits(got, s)
+        assert np.array_equal(got, t)
+    x = x.copy()
+    x[3], x[100], x[200] = -0.0, np.nan, np.inf
+    rows = np.repeat(np.arange(n), np.diff(rowptr.astype(np.int64)))
+    cols = colind.astype(np.int64)
+    one = a.cheb_series(x, np.array([0.5, 0.25]), LO, HI)
+    tr.assert_same_bits(one, nr.cheb_series(rowptr, colind, values, x, LO, HI, np.array([0.5, 0.25])))
+    # one step: exactly the rows that hold or gather the two values
+    touched = set(rows[np.isin(cols, (100, 200))].tolist()) | {100, 200}
+    assert set(np.flatnonzero(~np.isfinite(one)).tolist()) == touched
+    for degree in (2, 3, 17):
+        coef = coefficients(degree, 1)
+        tr.assert_same_bits(a.cheb_series(x, coef, LO, HI), nr.cheb_series(rowptr, colind, values, x, LO, HI, coef))
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
+@pytest.mark.parametrize("kind", ["csr", "csc"])
+def test_the_device_form_on_two_streams(kind, dtype):
+    import torch
+    mat = shape("block=chunk", dtype)
+    n, rowptr, colind, values = mat
+    dev = make(kind, mat).device()
+    tt = torch.float64 if dtype == np.float64 else torch.float32
+    size = np.dtype(dtype).itemsize
+    xs = [vector(n, dtype), vector(n + 1, dtype)[:n]]
+    coefs = [coefficients(3), coefficients(4)]
+    xin = [torch.full((n + 37,), 7, dtype=tt, device="cuda") for _ in xs]
+    outs = [torch.full((n + 11,), 7, dtype=tt, device="cuda") for _ in xs]
+    for t, x in zip(xin, xs):
+        t[5:5 + n] = torch.from_numpy(x).cuda()
+    streams = [torch.cuda.Stream(), torch.cuda.Stream()]
+    for s in streams:
+        s.wait_stream(torch.cuda.current_stream())
+    for _ in range(2):                          # the second call reuses each stream's scratch
+        for s, t, o, coef in zip(streams, xin, outs, coefs):
+            dev.cheb_series_dev(t.data_ptr() + 5 * size, o.data_ptr() + 3 * size, coef, LO, HI, stream=s)
+    for s in streams:
+        s.synchronize()
+    torch.cuda.synchronize()
+    free = torch.cuda.mem_get_info()[0]
+    for s, t, o, coef in zip(streams, xin, outs, coefs):
+        dev.cheb_series_dev(t.data_ptr() + 5 * size, o.data_ptr() + 3 * size, coef, LO, HI, stream=s)
+        s.synchronize()
+    assert torch.cuda.mem_get_info()[0] == free
+    for t, o, x, coef in zip(xin, outs, xs, coefs):
+        got = o.cpu().numpy()
+        tr.assert_same_bits(got[3:3 + n], nr.cheb_series(rowptr, colind, values, x, LO, HI, coef))
+        assert np.all(got[:3] == 7) and np.all(got[3 + n:] == 7)
+        back = t.cpu().numpy()
+        assert np.all(back[:5] == 7) and np.all(back[5 + n:] == 7) and np.array_equal(back[5:5 + n], x)      # x is only read
+    with pytest.raises(sp.Panic, match="out overlaps x"):
+        dev.cheb_series_dev(xin[0].data_ptr(), xin[0].data_ptr() + 8 * size, coefs[0], LO, HI)
+
+
+@pytest.mark.parametrize("kind", ["csr", "csc"])
+def test_series_refusals_that_read_the_handle_and_a_capturing_stream(kind):
+    import torch
+    lib = _ffi.lib()
+    mat = shape("n=257", np.float64)
+    n = mat[0]
+    a = make(kind, mat)
+    dev = a.device()
+    inv = _ffi.SPAL_ERR_INVALID_ARGUMENT
+    coef = np.array([1.0, 0.5, 0.25])
+    cp = coef.ctypes.data_as(_ffi.f64p)
+    x32, out32 = np.ones(n, np.float32), np.zeros(n, np.float32)
+    assert getattr(lib, f"spal_{kind}_cheb_series_f32")(dev._h, x32.ctypes.data_as(_ffi.f32p), u(n), out32.ctypes.data_as(_ffi.f32p), u(n),
+                                                        u(2), dbl(LO), dbl(HI), cp, u(3)) == inv
+    assert "handle holds f64 values" in lib.spal_last_error().decode() and not out32.any()
+    x, out = np.ones(n), np.zeros(n)
+    p = lambda v: v.ctypes.data_as(_ffi.f64p)                                                  # noqa: E731
+    fn = getattr(lib, f"spal_{kind}_cheb_series_f64")
+    assert fn(dev._h, p(x), u(n - 1), p(out), u(n), u(2), dbl(LO), dbl(HI), cp, u(3)) == inv
+    assert fn(dev._h, p(x), u(n), p(out), u(n + 1), u(2), dbl(LO), dbl(HI), cp, u(3)) == inv
+    assert fn(dev._h, p(x), u(n), p(x), u(n), u(2), dbl(LO), dbl(HI), cp, u(3)) == inv and not out.any()
+    wide = sp.CsrMatrix(3, 4, [0, 1, 2, 3], [0, 1, 3], np.ones(3)) if kind == "csr" else sp.CscMatrix(3, 4, [0, 1, 2, 2, 3], [0, 1, 2], np.ones(3))
+    with pytest.raises(sp.Panic, match=r"not square \(3 x 4\)"):
+        wide.device().cheb_series(np.ones(4), coef, LO, HI)
+    xt = torch.zeros(n, dtype=torch.float64, device="cuda")
+    vin = torch.ones(n, dtype=torch.float64, device="cuda")
+    th, rs = np.zeros(2), np.zeros(2)
+    cinfo = sp.matrix._EigshNearInfoC()
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()               # never replayed
+    with torch.cuda.graph(graph):
+        xt.fill_(0.0)                            # (so that the graph is not empty)
+        capturing = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        s1 = getattr(lib, f"spal_{kind}_cheb_series_dev_f64")(dev._h, C.c_void_p(vin.data_ptr()), C.c_void_p(xt.data_ptr()), u(2),
+                                                              dbl(LO), dbl(HI), cp, u(3), capturing)
+        m1 = lib.spal_last_error().decode()
+        s2 = getattr(lib, f"spal_{kind}_eigsh_near_dev_f64")(dev._h, u(2), dbl(0.1), u(8), None, u(0), dbl(1e-8), u(3), u(8), C.c_int(1),
+                                                             dbl(0.0), dbl(0.0), p(th), p(rs), None, u(2), capturing, C.byref(cinfo))
+        m2 = lib.spal_last_error().decode()
+    torch.cuda.synchronize()
+    assert s1 == inv and "cannot be captured into a graph" in m1, (s1, m1)
+    assert s2 == inv and "cannot be captured into a graph" in m2, (s2, m2)
+    del graph
+    assert not th.any()
+
+
+def test_row_block_handles_are_refused(monkeypatch):
+    import spal_synth as synth
+    rp, ci, va = synth.banded_csr(2000, 2000, 4, 64, 3)
+    monkeypatch.setenv("SPAL_CSR_PART_ENTRIES", "3000")
+    big = sp.CsrMatrix(2000, 2000, rp, ci, va)
+    assert big.device().describe()["kernel"] == "row_blocks"
+    monkeypatch.delenv("SPAL_CSR_PART_ENTRIES")
+    for call, who in ((lambda: big.eigsh(2, ncv=8, maxit=3, sigma=0.5, filter_degree=4), "spal_csr_eigsh_near"),
+                      (lambda: big.cheb_series(np.ones(2000), np.ones(3), 0.0, 1.0), "spal_csr_cheb_series")):
+        with pytest.raises(sp.SpalError, match=who + r": an operand of more than 2\^32 - 65537 entries \(row blocks\)") as e:
+            call()
+        assert e.value.status == _ffi.SPAL_ERR_UNSUPPORTED
+    assert "eigsh_near" not in big.device().describe()
+
+
+# ---- 2. eigsh near sigma ---------------------------------------------------------------------------------------------------
+N, K, NCV, DEGREE = 400, 4, 20, 64
+TOL = {np.float64: 1e-10, np.float32: 1e-5}
+LAMBDA = 2.0 - 2.0 * np.cos(np.arange(1, N + 1) * np.pi / (N + 1))
+
+
+@functools.lru_cache(maxsize=None)
+def text(which, dtype, k, sigma, ncv, tol, maxit, degree, interval=None, v0=None, seed=0):
+    mat = laplacian(dtype) if which == "laplacian" else named("A2", dtype)
+    return nr.eigsh_near(mat[1:], dtype, k, sigma, ncv, tol, maxit, degree, interval, None if v0 is None else np.array(v0, dtype),
+                         seed, lib_jacobi)
+
+
+def check(a, ref, dtype, k, sigma, ncv, tol, maxit, degree, interval=None, v0=None, seed=0):
+    """one call against the text: every output and every count"""
+    theta, X, info = a.eigsh(k, "LA", ncv, v0, seed, tol, maxit, sigma=sigma, filter_degree=degree, filter_interval=interval)
+    assert (info.restarts, info.products, info.converged, info.reason, info.degree) == \
+        (ref["restarts"], ref["products"], ref["converged"], ref["reason"], degree)
+    assert (info.lo, info.hi, info.sigma, info.gamma) == (ref["lo"], ref["hi"], ref["sigma"], ref["gamma"])
+    tr.assert_same_bits(theta, ref["theta"])
+    tr.assert_same_bits(info.resid, ref["resid"])
+    tr.assert_same_bits(X, ref["X"])
+    d = a.device().describe()["eigsh_near"]
+    assert set(d) == DESCRIBE_KEYS
+    assert (d["k"], d["ncv"], d["degree"], d["interval"], d["sigma"]) == (k, ncv, degree, "auto" if interval is None else "given", sigma)
+    assert (d["restarts"], d["products"], d["reason"], d["lo"], d["hi"]) == (info.restarts, info.products, info.reason, info.lo, info.hi)
+    return theta, X, info
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
+@pytest.mark.parametrize("sigma", [1.0, 3.3])
+@pytest.mark.parametrize("kind", ["csr", "csc"])
+def test_eigsh_near_is_the_text_and_finds_the_nearest(kind, sigma, dtype):
+    tol = TOL[dtype]
+    mat = laplacian(dtype)
+    ref = text("laplacian", dtype, K, sigma, NCV, tol, 60, DEGREE)
+    theta, X, info = check(make(kind, mat), ref, dtype, K, sigma, NCV, tol, 60, DEGREE)
+    assert info.reason == 0 and info.converged == K
+    want = np.sort(LAMBDA[np.argsort(np.abs(LAMBDA - sigma), kind="stable")[:K]])
+    assert np.abs(np.sort(theta.astype(np.float64)) - want).max() <= (1e-9 if dtype == np.float64 else 1e-5)
+    assert "eigsh_filter" not in make(kind, mat).device().describe()
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
+@pytest.mark.parametrize("interval", [None, (-0.5, 7.0)])
+@pytest.mark.parametrize("kind", ["csr", "csc"])
+def test_eigsh_near_on_the_2d_laplacian_automatic_and_given_interval(kind, interval, dtype):
+    mat = named("A2", dtype)                     # Gershgorin: within [0, 9)
+    ref = text("A2", dtype, 3, 2.7, 14, TOL[dtype], 3, 24, interval)
+    check(make(kind, mat), ref, dtype, 3, 2.7, 14, TOL[dtype], 3, 24, interval)
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
+def test_rotation_chunk_form_plan_and_ldx_do_not_change_the_bits(dtype):
+    import torch
+    tol = TOL[dtype]
+    mat = laplacian(dtype)
+    ref = text("laplacian", dtype, K, 1.0, NCV, tol, 1, 16)
+    assert ref["restarts"] == 1 and ref["reason"] == 1
+    for chunk, rotate, form, kernel in ((256, 0, 0, None), (4096, 1, 2, 1), (0, 2, 1, 2)):
+        b = make("csr", mat)
+        dev = b.device()
+        dev.set_option("cheb_chunk", chunk)
+        dev.set_option("eigsh_rotate", rotate)
+        dev.set_option("cheb_series_form", form)
+        if kernel is not None:
+            dev.set_option("kernel", kernel)     # another SpMV plan: no warm-up runs, so the plan plays no part
+        check(b, ref, dtype, K, 1.0, NCV, tol, 1, 16)
+        d = dev.describe()["eigsh_near"]
+        assert (d["chunk"], d["form"]) == (chunk, "unfused" if form == 2 else "fused")
+    a = make("csr", mat)
+    theta, X, info = a.eigsh(K, ncv=NCV, tol=tol, maxit=1, sigma=1.0, filter_degree=16, return_eigenvectors=False)
+    assert X is None
+    tr.assert_same_bits(theta, ref["theta"])
+    xt = torch.full((N, K + 1), 7, dtype=torch.float64 if dtype == np.float64 else torch.float32, device="cuda")
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    th, rs = np.zeros(K, dtype), np.zeros(K, dtype)
+    info2 = a.device().eigsh_dev(K, th, rs, xt.data_ptr(), K + 1, ncv=NCV, tol=tol, maxit=1, stream=s, sigma=1.0, filter_degree=16)
+    got = xt.cpu().numpy()                      # the call has synchronised its stream
+    tr.assert_same_bits(got[:, :K], ref["X"])
+    assert np.all(got[:, K] == 7) and (info2.restarts, info2.reason, info2.products) == (1, 1, ref["products"])
+    tr.assert_same_bits(th, ref["theta"])
+    tr.assert_same_bits(rs, ref["resid"])
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
+def test_a_given_start_vector_and_maxit_0(dtype):
+    mat = laplacian(dtype)
+    v0 = tuple(np.random.default_rng(5).uniform(-1, 1, N).astype(dtype).tolist())
+    ref = text("laplacian", dtype, K, 3.3, NCV, TOL[dtype], 0, 8, None, v0)
+    theta, X, info = check(make("csr", mat), ref, dtype, K, 3.3, NCV, TOL[dtype], 0, 8, None, np.array(v0, dtype))
+    assert (info.reason, info.restarts, info.products) == (1, 0, NCV * 8 + K) and theta.size == K
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
+def test_the_two_to_one_limitation_ends_with_reason_1(dtype):
+    mat = laplacian(dtype)
+    ref = text("laplacian", dtype, K, 2.0, NCV, TOL[dtype], 10, DEGREE)
+    theta, X, info = check(make("csr", mat), ref, dtype, K, 2.0, NCV, TOL[dtype], 10, DEGREE)
+    assert (info.reason, info.converged, info.restarts) == (1, 0, 10)
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
+def test_exhaustion_on_a_diagonal_matrix_with_few_distinct_eigenvalues(dtype):
+    """diag(1, 2, 3, 1, 2, 3, ..): three distinct eigenvalues, so hn == 0 (or a value that rounding left of it) ends the
+    first phase long before ncv = 8 steps; whatever the text does there, the device does."""
+    n = 30
+    mat = (n, np.arange(n + 1, dtype=np.uint64), np.arange(n, dtype=np.uint64), (np.arange(n) % 3 + 1).astype(dtype))
+    v0 = np.ones(n, dtype=dtype)
+    ref = nr.eigsh_near(mat[1:], dtype, 2, 2.25, 8, TOL[dtype], 5, 6, None, v0, 0, lib_jacobi)
+    check(make("csr", mat), ref, dtype, 2, 2.25, 8, TOL[dtype], 5, 6, None, v0)
+    # hn == 0 exactly: from v0 = e_0 the first product is a multiple of e_0 and Gram-Schmidt leaves +0.0: the space is
+    # exhausted at jj = 1, which is stop 0 for k = 1 and stop 3 with one pair for k = 2
+    v0 = np.zeros(n, dtype=dtype)
+    v0[0] = 1.0
+    for k, reason in ((1, 0), (2, 3)):
+        ref = nr.eigsh_near(mat[1:], dtype, k, 1.25, 8, TOL[dtype], 5, 6, (0.0, 4.0), v0, 0, lib_jacobi)
+        theta, X, info = check(make("csr", mat), ref, dtype, k, 1.25, 8, TOL[dtype], 5, 6, (0.0, 4.0), v0)
+        assert (info.restarts, info.reason, info.converged, theta.size) == (0, reason, 1, 1) and info.products == 6 + 1
+        assert theta[0] == 1.0 and X.shape == (n, 1)
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
+def test_a_nan_in_the_matrix_stops_with_reason_2_and_writes_nothing(dtype):
+    mat = laplacian(dtype)
+    values = mat[3].copy()
+    values[7] = np.nan
+    bad = (N, mat[1], mat[2], values)
+    ref = nr.eigsh_near(bad[1:], dtype, K, 1.0, NCV, TOL[dtype], 5, 16, None, None, 0, lib_jacobi)
+    theta, X, info = check(make("csr", bad), ref, dtype, K, 1.0, NCV, TOL[dtype], 5, 16)
+    assert info.reason == 2 and theta.size == 0 and X.shape == (N, 0) and info.products == 0
+    d = make("csr", bad).device()
+    d.eigsh(K, ncv=NCV, maxit=5, sigma=1.0, filter_degree=16)
+    d = d.describe()["eigsh_near"]
+    assert (d["glo"], d["ghi"], d["reason"]) == (None, None, 2)
+    # through the C entry: theta, resid and x are left as they were
+    dev = make("csr", bad).device()
+    ct = _ffi.f64p if dtype == np.float64 else _ffi.f32p
+    th, rs, x = np.full(K, 9, dtype), np.full(K, 9, dtype), np.full((N, K), 9, dtype)
+    cinfo = sp.matrix._EigshNearInfoC()
+    fn = getattr(_ffi.lib(), f"spal_csr_eigsh_near_{sfx(dtype)}")
+    assert fn(dev._h, u(K), dbl(1.0), u(NCV), None, u(0), u(0), dbl(TOL[dtype]), u(5), u(16), C.c_int(1), dbl(0.0), dbl(0.0),
+              th.ctypes.data_as(ct), u(K), rs.ctypes.data_as(ct), u(K), x.ctypes.data_as(ct), u(K), u(N), C.byref(cinfo)) == 0
+    assert cinfo.reason == 2 and np.all(th == 9) and np.all(rs == 9) and np.all(x == 9)
+    # a start vector that is not finite: the first step stops it
+    v0 = np.ones(N, dtype=dtype)
+    v0[5] = np.inf
+    ref = nr.eigsh_near(mat[1:], dtype, K, 1.0, NCV, TOL[dtype], 5, 16, None, v0, 0, lib_jacobi)
+    theta, X, info = check(make("csr", mat), ref, dtype, K, 1.0, NCV, TOL[dtype], 5, 16, None, v0)
+    assert info.reason == 2 and theta.size == 0 and info.products == 16
+
+
+def test_sigma_outside_gershgorins_interval_is_refused_after_it():
+    a = make("csr", laplacian(np.float64))
+    for sigma in (-0.5, 4.5, 4.0 + 4.0 / 1024):
+        with pytest.raises(sp.Panic, match="sigma must lie strictly inside the interval.*Gershgorin"):
+            a.eigsh(K, ncv=NCV, sigma=sigma, filter_degree=16)
+    theta, _, info = a.eigsh(K, ncv=NCV, maxit=0, sigma=4.001, filter_degree=16)         # inside the margin: served
+    assert info.gamma < 1.0 and theta.size == K
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
+def test_eigsh_without_sigma_is_what_it_was(dtype):
+    """the dispatch: sigma=None, with and without filter_degree, is the parent's call"""
+    mat = named("A1", dtype)
+    n = mat[0]
+    a = make("csr", mat)
+    tol = TOL[dtype]
+    t0, x0, i0 = a.eigsh(3, "SA", 12, tol=tol, maxit=4, sigma=None)
+    ref = er.eigsh(lambda v: a.device().spmv(v), n, dtype, 3, "SA", 12, tol, 4, jacobi_fn=lib_jacobi)
+    tr.assert_same_bits(t0, ref["theta"])
+    tr.assert_same_bits(x0, ref["X"])
+    assert (i0.restarts, i0.products, i0.reason) == (ref["restarts"], ref["products"], ref["reason"]) and "sigma" not in i0
+    t1, x1, i1 = a.eigsh(3, "SA", 12, tol=tol, maxit=4, filter_degree=8, filter_interval=(1.0, 14.0), sigma=None)
+    ref = cr.eigsh_filtered(mat[1:], dtype, 3, "SA", 12, tol, 4, 8, (1.0, 14.0), 5, None, 0, lib_jacobi)
+    tr.assert_same_bits(t1, ref["theta"])
+    tr.assert_same_bits(x1, ref["X"])
+    assert (i1.restarts, i1.products, i1.reason) == (ref["restarts"], ref["products"], ref["reason"]) and "sigma" not in i1
+    assert "eigsh_near" not in a.device().describe()

@@ -17,7 +17,8 @@ SCALARS = {"int": "c_int", "uint64_t": "u64", "uint32_t": "u32", "int64_t": "i64
            "float": "f32", "void": "c_void", "char": "c_char"}
 STRUCTS = {"spal_krylov_info": "spal_krylov_info", "spal_amg_params": "spal_amg_params",
            "spal_eigsh_info": "spal_eigsh_info",
-           "spal_eigsh_filter_info": "spal_eigsh_filter_info"}   # plain structs passed by pointer, declared in render()
+           "spal_eigsh_filter_info": "spal_eigsh_filter_info",
+           "spal_eigsh_near_info": "spal_eigsh_near_info"}   # plain structs passed by pointer, declared in render()
 HANDLES = {"spal_csr_t": "spal_csr", "spal_csc_t": "spal_csc", "spal_coo_t": "spal_coo", "spal_mg_t": "spal_mg",
            "spal_mg_csr_t": "spal_mg_csr", "spal_amg_t": "spal_amg"}
 
@@ -101,6 +102,10 @@ def render(fns) -> str:
               'pub struct spal_eigsh_filter_info { pub restarts: u64, pub products: u64, pub converged: u64, pub reason: c_int, '
               'pub solve_ms: f64, pub warm_restarts: u64, pub warm_products: u64, pub lo: f64, pub hi: f64, pub a0: f64, '
               'pub degree: u64 }',
+              '/// What spal_*_eigsh_near_* report: eigsh\'s fields, the interval, sigma, its place gamma in [-1, 1], the degree.',
+              '#[repr(C)] #[derive(Clone, Copy, Debug, Default)]',
+              'pub struct spal_eigsh_near_info { pub restarts: u64, pub products: u64, pub converged: u64, pub reason: c_int, '
+              'pub solve_ms: f64, pub lo: f64, pub hi: f64, pub sigma: f64, pub gamma: f64, pub degree: u64 }',
               '',
               '#[link(name = "spal_hip")]',
               'extern "C" {']
