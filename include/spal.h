@@ -1399,6 +1399,93 @@ int spal_csc_eigsh_near_dev_f32(spal_csc_t a, uint64_t k, double sigma, uint64_t
                                 float *theta, float *resid, float *x_dev, uint64_t ldx, void *stream,
                                 spal_eigsh_near_info *info);   /* synchronises */
 
+/* ---- KPM moments: the spectral density and eigenvalue counts ---------------------------------------------------
+ * Not in the reference.  The calls above need a degree and a number of wanted pairs; what says whether they are adequate
+ * is HOW MANY EIGENVALUES LIE IN AN INTERVAL, and more generally the spectral density.  The kernel polynomial method
+ * gives both from products with A alone: the Chebyshev moments mu_i = z^T T_i(A) z of k random probe columns estimate
+ * trace(T_i(A)), the damped series of the moments is the density, and its integral over [a, b] the count.  This call
+ * returns the moments; the damping, the density and the count are host arithmetic on them (the Python layer's
+ * kpm_damping, kpm_density, kpm_count: host doubles with cos, NOT bit-pinned).  A sequential text again, returned bit
+ * for bit in f32 and f64; T is the handle's type, every product is rounded before the sum or difference it enters (no
+ * FMA); rowsum, dot, mix32 and gershgorin are the ones above.
+ *
+ *   probes.  Given by the caller (an n x k block, row-major, leading dimension ldz >= k), or hashed:
+ *       h(i) = mix32((i + seed) mod 2^32);   z[i, j] = mix32((h(i) + j) mod 2^32) >> 31 ? T(-1) : T(+1)
+ *     (Rademacher entries; only seed mod 2^32 enters, as for the colouring.)
+ *
+ *   interval.  Automatic: gershgorin's with the margin of eigsh-near (m = (ghi-glo)/1024, lo = glo-m, hi = ghi+m),
+ *     not finite: refused as there.  Given: lo < hi, finite; the caller vouches that it encloses the spectrum.
+ *     c, e, a1 = T(1/e), a2 = T(2/e), cT = T(c) as in cheb_series.
+ *
+ *   kpm_moments(A; d, Z) for one column z (columns are independent; d >= 1; m = ceil(d/2)):
+ *       t_0 = z
+ *       t_1[r] = a1 * (rowsum(t_0, r) - (cT*t_0[r]))
+ *       t_i[r] = (a2 * (rowsum(t_{i-1}, r) - (cT*t_{i-1}[r]))) - t_{i-2}[r]              i = 2..m
+ *       mu_0 = dot(t_0, t_0);   mu_1 = dot(t_1, t_0)
+ *       mu_{2i}   = (T(2)*dot(t_i, t_i))     - mu_0      1 <= i,  2i   <= d
+ *       mu_{2i+1} = (T(2)*dot(t_{i+1}, t_i)) - mu_1      1 <= i,  2i+1 <= d
+ *     out[i*k + j] = double(mu_i of column j)   (exact conversions);   products = m per column.
+ *
+ *   The doubling identities T_{2i} = 2 T_i^2 - 1 and T_{2i+1} = 2 T_{i+1} T_i - T_1 need a symmetric A (not checked, as
+ *   for CG and eigsh); they halve the passes over the matrix.  An eigenvalue outside the interval makes the t_i grow:
+ *   the caller's error; it ends in values that are not finite, which are returned as they are.  A NaN or inf in one
+ *   column never reaches another column.  A matrix without rows has every moment +0.0 (given interval only).
+ * WHAT THE BITS DO NOT DEPEND ON: k, ldz, the other columns' contents, "cheb_chunk", "kpm_tile", "kpm_form", the
+ * handle's plan (it plays no part), the stream.
+ *
+ * On the device (spal_kpm.hip) a step is ONE launch that advances a tile of columns on one pass over the
+ * matrix, with the recurrence and the first level of both dots in its epilogue (a workgroup owns whole tiles of 1024
+ * rows), and one small launch that walks the dots' upper levels and writes the step's moments into a device table.
+ * Option "kpm_tile" on `a`: the column tile, 0 = automatic (the narrowest of 1, 2, 4, 8 that holds k), else 1, 2, 4 or
+ * 8; k beyond the tile takes one pass of the matrix per tile.  Option "kpm_form": 0 = automatic = 1 = the fused kernel;
+ * 2 = the same block step without the dots, followed by a block dot launch (the same bits; kept for the measurement in
+ * DESIGN 3.29).  "cheb_chunk" applies, clipped so that a chunk's products of one tile stay within 32 KiB of LDS.
+ *
+ * spal_*_kpm_moments_*: z is NULL (hashed probes from seed) or z_rows x ldz values of which the first k of every row
+ * are read; mu receives mu_len = (degree + 1) * k doubles.  The _dev forms take z_dev (NULL or device memory, n rows)
+ * and a stream, and their work blocks from the stream's scratch (a second identical call takes no new device memory);
+ * the host forms take theirs from the caching allocator.  Both enqueue everything, copy the moments back and
+ * synchronise ONCE, at the end; nothing is polled.  (With an automatic interval Gershgorin's bounds are read back
+ * first, as eigsh near sigma reads them.)  SPAL_ERR_INVALID_ARGUMENT before any device work: a null a, mu or info;
+ * degree outside 1 .. 4096; k outside 1 .. 256; mu_len != (degree + 1) * k; ldz < k; z_rows != nrows; automatic outside
+ * {0, 1}; a given interval that is not finite or has lo >= hi; a dtype mismatch; a matrix that is not square.
+ * Capturing streams and row-block handles are refused as cheb_series refuses them.  Nothing leaks on failure.
+ * info: products (per column), lo, hi, glo, ghi (0, 0 when the interval was given), degree, probes, solve_ms (device
+ * time of the launches).  describe() on `a` gains "kpm" after a call: {degree, probes, steps, tile, form, chunk, lo,
+ * hi, launches, solve_ms}.
+ * Not provided: the damping and the density on the device, probes other than +-1 generated on the device, a stochastic
+ * error bound in the C ABI (the Python layer's kpm_count reports the spread over the probes), several GPUs. */
+typedef struct spal_kpm_info {
+    uint64_t products;
+    double lo, hi, glo, ghi;
+    uint64_t degree, probes;
+    double solve_ms;
+} spal_kpm_info;
+int spal_csr_kpm_moments_f64(spal_csr_t a, uint64_t degree, uint64_t k, uint64_t seed, int automatic, double lo, double hi,
+                             const double *z, uint64_t z_rows, uint64_t ldz, double *mu, uint64_t mu_len,
+                             spal_kpm_info *info);
+int spal_csr_kpm_moments_dev_f64(spal_csr_t a, uint64_t degree, uint64_t k, uint64_t seed, int automatic, double lo,
+                                 double hi, const double *z_dev, uint64_t ldz, double *mu, uint64_t mu_len, void *stream,
+                                 spal_kpm_info *info);   /* synchronises */
+int spal_csr_kpm_moments_f32(spal_csr_t a, uint64_t degree, uint64_t k, uint64_t seed, int automatic, double lo, double hi,
+                             const float *z, uint64_t z_rows, uint64_t ldz, double *mu, uint64_t mu_len,
+                             spal_kpm_info *info);
+int spal_csr_kpm_moments_dev_f32(spal_csr_t a, uint64_t degree, uint64_t k, uint64_t seed, int automatic, double lo,
+                                 double hi, const float *z_dev, uint64_t ldz, double *mu, uint64_t mu_len, void *stream,
+                                 spal_kpm_info *info);   /* synchronises */
+int spal_csc_kpm_moments_f64(spal_csc_t a, uint64_t degree, uint64_t k, uint64_t seed, int automatic, double lo, double hi,
+                             const double *z, uint64_t z_rows, uint64_t ldz, double *mu, uint64_t mu_len,
+                             spal_kpm_info *info);
+int spal_csc_kpm_moments_dev_f64(spal_csc_t a, uint64_t degree, uint64_t k, uint64_t seed, int automatic, double lo,
+                                 double hi, const double *z_dev, uint64_t ldz, double *mu, uint64_t mu_len, void *stream,
+                                 spal_kpm_info *info);   /* synchronises */
+int spal_csc_kpm_moments_f32(spal_csc_t a, uint64_t degree, uint64_t k, uint64_t seed, int automatic, double lo, double hi,
+                             const float *z, uint64_t z_rows, uint64_t ldz, double *mu, uint64_t mu_len,
+                             spal_kpm_info *info);
+int spal_csc_kpm_moments_dev_f32(spal_csc_t a, uint64_t degree, uint64_t k, uint64_t seed, int automatic, double lo,
+                                 double hi, const float *z_dev, uint64_t ldz, double *mu, uint64_t mu_len, void *stream,
+                                 spal_kpm_info *info);   /* synchronises */
+
 /* ---- multicolour reordering: greedy colouring and B = P A P^T -------------------------------------------
  * Not in the reference.  An exact triangular solve costs one launch step per level; numbering the rows
  * colour by colour leaves both triangles of P A P^T with at most as many levels as there are colours.

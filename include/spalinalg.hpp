@@ -21,6 +21,7 @@
 //   a.gmres(b, restart, M, x0, tol, maxit)               not in the reference: restarted GMRES (spal_*_gmres_*)
 //   a.eigsh(k, which, ncv, v0, seed, tol, maxit)         not in the reference: extreme eigenpairs of a symmetric matrix (spal_*_eigsh_*)
 //   a.eigsh_filtered(k, degree, ...), a.cheb_apply(x, degree, lo, hi, a0), a.gershgorin()    not in the reference: the Chebyshev filter (spal_*_eigsh_filtered_*, _cheb_apply_*, _gershgorin)
+//   a.kpm_moments(degree, k, seed, ...), a.kpm_moments_dev(...)    not in the reference: Chebyshev moments for the spectral density and eigenvalue counts (spal_*_kpm_moments_*)
 //   a.gmres_block(B, k, restart, M, X0, tol, maxit)      not in the reference: GMRES on k right-hand sides (spal_*_gmres_block_*)
 //   a.minres(b, M, shift, x0, tol, maxit)                not in the reference: MINRES on (A - shift I) x = b, A symmetric (spal_*_minres_*)
 //   a.minres_block(B, k, M, shift, X0, tol, maxit)       not in the reference: the same on k right-hand sides (spal_*_minres_block_*)
@@ -89,6 +90,8 @@ template <> struct Abi<double> {
     static constexpr auto csr_eigsh = spal_csr_eigsh_f64;
     static constexpr auto csr_eigsh_filtered = spal_csr_eigsh_filtered_f64;
     static constexpr auto csr_cheb_apply = spal_csr_cheb_apply_f64;
+    static constexpr auto csr_kpm_moments = spal_csr_kpm_moments_f64;
+    static constexpr auto csr_kpm_moments_dev = spal_csr_kpm_moments_dev_f64;
     static constexpr auto csr_permute_vec = spal_csr_permute_vec_f64;
     static constexpr auto dot = spal_dot_f64;
     static constexpr auto csr_download = spal_csr_download_f64;
@@ -108,6 +111,8 @@ template <> struct Abi<double> {
     static constexpr auto csc_eigsh = spal_csc_eigsh_f64;
     static constexpr auto csc_eigsh_filtered = spal_csc_eigsh_filtered_f64;
     static constexpr auto csc_cheb_apply = spal_csc_cheb_apply_f64;
+    static constexpr auto csc_kpm_moments = spal_csc_kpm_moments_f64;
+    static constexpr auto csc_kpm_moments_dev = spal_csc_kpm_moments_dev_f64;
     static constexpr auto csc_permute_vec = spal_csc_permute_vec_f64;
     static constexpr auto coo_to_csr = spal_coo_to_csr_f64;
     static constexpr auto coo_to_csc = spal_coo_to_csc_f64;
@@ -130,6 +135,8 @@ template <> struct Abi<float> {
     static constexpr auto csr_eigsh = spal_csr_eigsh_f32;
     static constexpr auto csr_eigsh_filtered = spal_csr_eigsh_filtered_f32;
     static constexpr auto csr_cheb_apply = spal_csr_cheb_apply_f32;
+    static constexpr auto csr_kpm_moments = spal_csr_kpm_moments_f32;
+    static constexpr auto csr_kpm_moments_dev = spal_csr_kpm_moments_dev_f32;
     static constexpr auto csr_permute_vec = spal_csr_permute_vec_f32;
     static constexpr auto dot = spal_dot_f32;
     static constexpr auto csr_download = spal_csr_download_f32;
@@ -149,6 +156,8 @@ template <> struct Abi<float> {
     static constexpr auto csc_eigsh = spal_csc_eigsh_f32;
     static constexpr auto csc_eigsh_filtered = spal_csc_eigsh_filtered_f32;
     static constexpr auto csc_cheb_apply = spal_csc_cheb_apply_f32;
+    static constexpr auto csc_kpm_moments = spal_csc_kpm_moments_f32;
+    static constexpr auto csc_kpm_moments_dev = spal_csc_kpm_moments_dev_f32;
     static constexpr auto csc_permute_vec = spal_csc_permute_vec_f32;
     static constexpr auto coo_to_csr = spal_coo_to_csr_f32;
     static constexpr auto coo_to_csc = spal_coo_to_csc_f32;
@@ -178,6 +187,12 @@ struct Solution {
     usize iterations;
     int reason;   // 0 converged (dot(r, r) <= tol^2 dot(b, b)), 1 maxit reached, 2 breakdown / not finite
     double residual_sq, rhs_sq, solve_ms;
+};
+
+// What kpm_moments returns: mu[i * probes + j] = moment i of probe column j, and the call's report (include/spal.h).
+struct KpmMoments {
+    std::vector<double> mu;
+    spal_kpm_info info{};
 };
 
 // What eigsh returns: `pairs` eigenvalues in the order asked for (LA descending, SA ascending), their estimates
@@ -625,6 +640,29 @@ class CsrMatrix {
         double lo = 0.0, hi = 0.0;
         detail::check(spal_csr_gershgorin(device_handle(), &lo, &hi));
         return {lo, hi};
+    }
+
+    // The KPM moments mu[i * k + j] = z_j^T T_i(B) z_j, i = 0 .. degree, of k probe columns (spal_csr_kpm_moments_*,
+    // include/spal.h): the text bit for bit, in double.  z empty: hashed +-1 probes from `seed`, else a ROW-MAJOR
+    // nrows x k block.  automatic: Gershgorin's bounds with a margin, else [lo, hi], which must enclose the spectrum.
+    // The matrix must be symmetric (not checked).  Panics as the library refuses.
+    KpmMoments kpm_moments(usize degree, usize k = 8, usize seed = 0, bool automatic = true, double lo = 0.0, double hi = 0.0,
+                           const std::vector<T> &z = {}) const {
+        KpmMoments out;
+        out.mu.assign((degree + 1) * k, 0.0);
+        detail::check(detail::Abi<T>::csr_kpm_moments(device_handle(), degree, k, seed, automatic ? 1 : 0, lo, hi,
+                                                      z.empty() ? nullptr : z.data(), k ? z.size() / k : 0, k, out.mu.data(),
+                                                      out.mu.size(), &out.info));
+        return out;
+    }
+    // ... with the probes in device memory (z_dev == nullptr: hashed), enqueued on `stream`; synchronises once, at its end
+    KpmMoments kpm_moments_dev(usize degree, usize k, usize seed, bool automatic, double lo, double hi, const T *z_dev, usize ldz,
+                               void *stream) const {
+        KpmMoments out;
+        out.mu.assign((degree + 1) * k, 0.0);
+        detail::check(detail::Abi<T>::csr_kpm_moments_dev(device_handle(), degree, k, seed, automatic ? 1 : 0, lo, hi, z_dev, ldz,
+                                                          out.mu.data(), out.mu.size(), stream, &out.info));
+        return out;
     }
 
     // X with A X = B for a ROW-MAJOR block of k right-hand sides by restarted GMRES(restart): k independent iterations in
@@ -1091,6 +1129,29 @@ class CscMatrix {
         double lo = 0.0, hi = 0.0;
         detail::check(spal_csc_gershgorin(device_handle(), &lo, &hi));
         return {lo, hi};
+    }
+
+    // The KPM moments mu[i * k + j] = z_j^T T_i(B) z_j, i = 0 .. degree, of k probe columns (spal_csc_kpm_moments_*,
+    // include/spal.h): the text bit for bit, in double.  z empty: hashed +-1 probes from `seed`, else a ROW-MAJOR
+    // nrows x k block.  automatic: Gershgorin's bounds with a margin, else [lo, hi], which must enclose the spectrum.
+    // The matrix must be symmetric (not checked).  Panics as the library refuses.
+    KpmMoments kpm_moments(usize degree, usize k = 8, usize seed = 0, bool automatic = true, double lo = 0.0, double hi = 0.0,
+                           const std::vector<T> &z = {}) const {
+        KpmMoments out;
+        out.mu.assign((degree + 1) * k, 0.0);
+        detail::check(detail::Abi<T>::csc_kpm_moments(device_handle(), degree, k, seed, automatic ? 1 : 0, lo, hi,
+                                                      z.empty() ? nullptr : z.data(), k ? z.size() / k : 0, k, out.mu.data(),
+                                                      out.mu.size(), &out.info));
+        return out;
+    }
+    // ... with the probes in device memory (z_dev == nullptr: hashed), enqueued on `stream`; synchronises once, at its end
+    KpmMoments kpm_moments_dev(usize degree, usize k, usize seed, bool automatic, double lo, double hi, const T *z_dev, usize ldz,
+                               void *stream) const {
+        KpmMoments out;
+        out.mu.assign((degree + 1) * k, 0.0);
+        detail::check(detail::Abi<T>::csc_kpm_moments_dev(device_handle(), degree, k, seed, automatic ? 1 : 0, lo, hi, z_dev, ldz,
+                                                          out.mu.data(), out.mu.size(), stream, &out.info));
+        return out;
     }
 
     // X with A X = B for a ROW-MAJOR block of k right-hand sides by restarted GMRES(restart): k independent iterations in

@@ -41,6 +41,9 @@ pub struct spal_eigsh_filter_info { pub restarts: u64, pub products: u64, pub co
 /// What spal_*_eigsh_near_* report: eigsh's fields, the interval, sigma, its place gamma in [-1, 1], the degree.
 #[repr(C)] #[derive(Clone, Copy, Debug, Default)]
 pub struct spal_eigsh_near_info { pub restarts: u64, pub products: u64, pub converged: u64, pub reason: c_int, pub solve_ms: f64, pub lo: f64, pub hi: f64, pub sigma: f64, pub gamma: f64, pub degree: u64 }
+/// What spal_*_kpm_moments_* report: the products per column, the interval, Gershgorin's bounds, the degree, the probes.
+#[repr(C)] #[derive(Clone, Copy, Debug, Default)]
+pub struct spal_kpm_info { pub products: u64, pub lo: f64, pub hi: f64, pub glo: f64, pub ghi: f64, pub degree: u64, pub probes: u64, pub solve_ms: f64 }
 
 #[link(name = "spal_hip")]
 extern "C" {
@@ -223,6 +226,14 @@ extern "C" {
     pub fn spal_csc_eigsh_near_dev_f64(a: *mut spal_csc, k: u64, sigma: f64, ncv: u64, v0_dev: *const f64, seed: u64, tol: f64, maxit: u64, degree: u64, automatic: c_int, lo: f64, hi: f64, theta: *mut f64, resid: *mut f64, x_dev: *mut f64, ldx: u64, stream: *mut c_void, info: *mut spal_eigsh_near_info) -> c_int;
     pub fn spal_csc_eigsh_near_f32(a: *mut spal_csc, k: u64, sigma: f64, ncv: u64, v0: *const f32, v0_len: u64, seed: u64, tol: f64, maxit: u64, degree: u64, automatic: c_int, lo: f64, hi: f64, theta: *mut f32, theta_len: u64, resid: *mut f32, resid_len: u64, x: *mut f32, ldx: u64, x_rows: u64, info: *mut spal_eigsh_near_info) -> c_int;
     pub fn spal_csc_eigsh_near_dev_f32(a: *mut spal_csc, k: u64, sigma: f64, ncv: u64, v0_dev: *const f32, seed: u64, tol: f64, maxit: u64, degree: u64, automatic: c_int, lo: f64, hi: f64, theta: *mut f32, resid: *mut f32, x_dev: *mut f32, ldx: u64, stream: *mut c_void, info: *mut spal_eigsh_near_info) -> c_int;
+    pub fn spal_csr_kpm_moments_f64(a: *mut spal_csr, degree: u64, k: u64, seed: u64, automatic: c_int, lo: f64, hi: f64, z: *const f64, z_rows: u64, ldz: u64, mu: *mut f64, mu_len: u64, info: *mut spal_kpm_info) -> c_int;
+    pub fn spal_csr_kpm_moments_dev_f64(a: *mut spal_csr, degree: u64, k: u64, seed: u64, automatic: c_int, lo: f64, hi: f64, z_dev: *const f64, ldz: u64, mu: *mut f64, mu_len: u64, stream: *mut c_void, info: *mut spal_kpm_info) -> c_int;
+    pub fn spal_csr_kpm_moments_f32(a: *mut spal_csr, degree: u64, k: u64, seed: u64, automatic: c_int, lo: f64, hi: f64, z: *const f32, z_rows: u64, ldz: u64, mu: *mut f64, mu_len: u64, info: *mut spal_kpm_info) -> c_int;
+    pub fn spal_csr_kpm_moments_dev_f32(a: *mut spal_csr, degree: u64, k: u64, seed: u64, automatic: c_int, lo: f64, hi: f64, z_dev: *const f32, ldz: u64, mu: *mut f64, mu_len: u64, stream: *mut c_void, info: *mut spal_kpm_info) -> c_int;
+    pub fn spal_csc_kpm_moments_f64(a: *mut spal_csc, degree: u64, k: u64, seed: u64, automatic: c_int, lo: f64, hi: f64, z: *const f64, z_rows: u64, ldz: u64, mu: *mut f64, mu_len: u64, info: *mut spal_kpm_info) -> c_int;
+    pub fn spal_csc_kpm_moments_dev_f64(a: *mut spal_csc, degree: u64, k: u64, seed: u64, automatic: c_int, lo: f64, hi: f64, z_dev: *const f64, ldz: u64, mu: *mut f64, mu_len: u64, stream: *mut c_void, info: *mut spal_kpm_info) -> c_int;
+    pub fn spal_csc_kpm_moments_f32(a: *mut spal_csc, degree: u64, k: u64, seed: u64, automatic: c_int, lo: f64, hi: f64, z: *const f32, z_rows: u64, ldz: u64, mu: *mut f64, mu_len: u64, info: *mut spal_kpm_info) -> c_int;
+    pub fn spal_csc_kpm_moments_dev_f32(a: *mut spal_csc, degree: u64, k: u64, seed: u64, automatic: c_int, lo: f64, hi: f64, z_dev: *const f32, ldz: u64, mu: *mut f64, mu_len: u64, stream: *mut c_void, info: *mut spal_kpm_info) -> c_int;
     pub fn spal_colour_greedy(n: u64, rowptr: *const u64, colind: *const u64, seed: u64, colour: *mut u64, ncolours: *mut u64) -> c_int;
     pub fn spal_perm_from_colours(n: u64, colour: *const u64, perm: *mut u64) -> c_int;
     pub fn spal_csr_colour(a: *mut spal_csr, seed: u64, stream: *mut c_void, colour_host: *mut u64, ncolours: *mut u64, rounds: *mut u64) -> c_int;

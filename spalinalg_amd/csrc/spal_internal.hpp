@@ -335,6 +335,9 @@ struct OpState {
     std::string eigsh_filter_info; // "eigsh_filter": the last spal_*_eigsh_filtered_* call with this handle as A (the same lock)
     int cheb_series_form = 0;      // option "cheb_series_form": 0 = automatic, 1 = the fused series step, 2 = step and accumulation apart (spal_cheb.hip)
     std::string eigsh_near_info;   // "eigsh_near": the last spal_*_eigsh_near_* call with this handle as A (the same lock)
+    int kpm_tile = 0;              // option "kpm_tile": column tile of the KPM block step, 0 = automatic (spal_kpm.hip)
+    int kpm_form = 0;              // option "kpm_form": 0 = automatic, 1 = dots fused into the step, 2 = step and dot launches apart
+    std::string kpm_info;          // "kpm": the last spal_*_kpm_moments_* call with this handle as A (the same lock)
     // a result of spal_*_permute / _multicolour (spal_colour.hip): written once, before the handle is
     // returned, and only read afterwards
     uint32_t *d_perm = nullptr;    // nrows: new -> old; freed by ordering_free (csr_free, csc_free)

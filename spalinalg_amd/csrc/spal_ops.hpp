@@ -1,5 +1,5 @@
 // spal_ops.hpp -- the host layer the sparse operations share: spal_spgemm.hip, spal_spadd.hip,
-// spal_spmm.hip, spal_trsv.hip, spal_trsv_sweep.hip, spal_trsm.hip, spal_ilu.hip, spal_ilu_sweep.hip, spal_krylov.hip, spal_krylov_block.hip, spal_gmres.hip, spal_gmres_block.hip, spal_eigsh.hip, spal_cheb.hip, spal_colour.hip and spal_amg.hip keep their kernels, their driver, their option's validation and their
+// spal_spmm.hip, spal_trsv.hip, spal_trsv_sweep.hip, spal_trsm.hip, spal_ilu.hip, spal_ilu_sweep.hip, spal_krylov.hip, spal_krylov_block.hip, spal_gmres.hip, spal_gmres_block.hip, spal_eigsh.hip, spal_cheb.hip, spal_kpm.hip, spal_colour.hip and spal_amg.hip keep their kernels, their driver, their option's validation and their
 // info JSON; what surrounds a launch the same way in each of them is here, once.  (Not installed.)
 #pragma once
 
@@ -213,13 +213,14 @@ int krylov_option(spal_csr *a, const char *key, int64_t value, OpState &s, int *
 int krylov_block_option(spal_csr *a, const char *key, int64_t value, OpState &s, int *status);   // "krylov_tile"
 int eigsh_option(spal_csr *a, const char *key, int64_t value, OpState &s, int *status);   // "eigsh_rotate"
 int cheb_option(spal_csr *a, const char *key, int64_t value, OpState &s, int *status);    // "cheb_chunk", "cheb_series_form"
+int kpm_option(spal_csr *a, const char *key, int64_t value, OpState &s, int *status);     // "kpm_tile", "kpm_form"
 inline int ops_set_option(OpState &s, spal_csr *solve, const char *key, int64_t value, int *status) {
     return spgemm_option(key, value, s, status) || spadd_option(key, value, s, status) ||
            spmm_option(key, value, s, status) || trsv_option(solve, key, value, status) ||
            trsv_sweep_option(solve, key, value, status) || trsm_option(solve, key, value, status) ||
            ilu_option(solve, key, value, status) || krylov_option(solve, key, value, s, status) ||
            krylov_block_option(solve, key, value, s, status) || eigsh_option(solve, key, value, s, status) ||
-           cheb_option(solve, key, value, s, status);
+           cheb_option(solve, key, value, s, status) || kpm_option(solve, key, value, s, status);
 }
 
 // (describe_append itself is host code: spal_host.cpp, declared in spal_internal.hpp)
@@ -244,6 +245,8 @@ int eigsh_describe_append(char *buf, size_t buf_len, const OpState &s, spal_csr 
 int eigsh_filter_describe_append(char *buf, size_t buf_len, const OpState &s, spal_csr *solve);
 // the "eigsh_near" object of a handle spal_*_eigsh_near_* ran with as A (spal_eigsh.hip; the same lock)
 int eigsh_near_describe_append(char *buf, size_t buf_len, const OpState &s, spal_csr *solve);
+// the "kpm" object of a handle spal_*_kpm_moments_* ran with as A (spal_kpm.hip; the same lock)
+int kpm_describe_append(char *buf, size_t buf_len, const OpState &s, spal_csr *solve);
 inline int ops_describe_append(char *buf, size_t buf_len, const OpState &s, spal_csr *solve) {
     SPAL_TRY(describe_append(buf, buf_len, "spgemm", s.spgemm_info));   // a product of spal_*_mul: how it was built
     SPAL_TRY(describe_append(buf, buf_len, "spadd", s.spadd_info));     // a result of spal_*_add / _sub / _neg
@@ -260,6 +263,7 @@ inline int ops_describe_append(char *buf, size_t buf_len, const OpState &s, spal
     SPAL_TRY(eigsh_describe_append(buf, buf_len, s, solve));            // spal_*_eigsh_* ran with it as A: the last call
     SPAL_TRY(eigsh_filter_describe_append(buf, buf_len, s, solve));     // spal_*_eigsh_filtered_* ran with it as A: the last call
     SPAL_TRY(eigsh_near_describe_append(buf, buf_len, s, solve));       // spal_*_eigsh_near_* ran with it as A: the last call
+    SPAL_TRY(kpm_describe_append(buf, buf_len, s, solve));              // spal_*_kpm_moments_* ran with it as A: the last call
     return describe_append(buf, buf_len, "ordering", s.ordering_info);  // a result of spal_*_permute / _multicolour
 }
 

@@ -203,6 +203,121 @@ def cheb_delta_coefficients(degree: int, gamma: float) -> np.ndarray:
     return coef
 
 
+# --------------------------------------------------------------------------
+# KPM moments, the spectral density and eigenvalue counts (include/spal.h)
+# --------------------------------------------------------------------------
+class _KpmInfoC(C.Structure):
+    """spal_kpm_info"""
+    _fields_ = [("products", C.c_uint64), ("lo", C.c_double), ("hi", C.c_double), ("glo", C.c_double), ("ghi", C.c_double),
+                ("degree", C.c_uint64), ("probes", C.c_uint64), ("solve_ms", C.c_double)]
+
+
+class KpmInfo(dict):
+    """What a kpm_moments call reports: products (per column), lo, hi, glo, ghi (0, 0 with a given interval), degree,
+    probes, solve_ms."""
+    __getattr__ = dict.__getitem__
+
+
+def _kpm_info(c: _KpmInfoC) -> KpmInfo:
+    return KpmInfo(products=int(c.products), lo=float(c.lo), hi=float(c.hi), glo=float(c.glo), ghi=float(c.ghi),
+                   degree=int(c.degree), probes=int(c.probes), solve_ms=float(c.solve_ms))
+
+
+def _mix32(x: np.ndarray) -> np.ndarray:
+    """mix32 of include/spal.h on an array of uint32 words"""
+    x = x.astype(np.uint32, copy=True)
+    x ^= x >> np.uint32(16)
+    x *= np.uint32(0x7feb352d)
+    x ^= x >> np.uint32(15)
+    x *= np.uint32(0x846ca68b)
+    x ^= x >> np.uint32(16)
+    return x
+
+
+def kpm_probes(n: int, k: int, seed: int = 0, dtype=np.float64) -> np.ndarray:
+    """The hashed Rademacher probes of kpm_moments, an (n, k) block of +-1 (include/spal.h): on the host, exact.
+    z[i, j] = -1 where the top bit of mix32(mix32(i + seed) + j) is set; only seed mod 2^32 enters."""
+    n, k = int(n), int(k)
+    with np.errstate(over="ignore"):
+        h = _mix32((np.arange(n, dtype=np.uint64) + np.uint64(int(seed) % 2**32)).astype(np.uint32))
+        w = _mix32(h[:, None] + np.arange(k, dtype=np.uint32)[None, :])
+    return np.where(w >> np.uint32(31), -1.0, 1.0).astype(np.dtype(dtype))
+
+
+def _kpm_args(what, degree, k, interval):
+    """(degree, k, automatic, lo, hi) of a kpm_moments call, refused as the library does"""
+    degree, k = int(degree), int(k)
+    if not 1 <= degree <= 4096:
+        raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT, f"{what}: degree = {degree} must be 1 .. 4096")
+    if not 1 <= k <= 256:
+        raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT, f"{what}: probes = {k} must be 1 .. 256")
+    if interval is None:
+        return degree, k, 1, 0.0, 0.0
+    lo, hi = (float(v) for v in interval)
+    if not (np.isfinite(lo) and np.isfinite(hi) and lo < hi):
+        raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT, f"{what}: interval = [{lo}, {hi}] must be finite with lo < hi")
+    return degree, k, 0, lo, hi
+
+
+def kpm_damping(degree: int, kind: str = "jackson") -> np.ndarray:
+    """g[0 .. degree], the damping factors of a truncated Chebyshev series: "jackson" (the usual choice: a nonnegative
+    kernel of width ~ pi/degree) or "fejer" (g_i = (d+1-i)/(d+1)), or "none".  Host doubles with cos: not bit-pinned."""
+    d = int(degree)
+    i = np.arange(d + 1, dtype=np.float64)
+    if kind == "jackson":
+        q = np.pi / (d + 2)
+        return ((d + 2 - i) * np.cos(i * q) + np.sin(i * q) / np.tan(q)) / (d + 2)
+    if kind == "fejer":
+        return (d + 1 - i) / (d + 1)
+    if kind in (None, "none"):
+        return np.ones(d + 1)
+    raise ValueError(f"kpm_damping: kind = {kind!r} must be 'jackson', 'fejer' or 'none'")
+
+
+def _kpm_damped(mu, damping):
+    mu = np.asarray(mu, dtype=np.float64)
+    if mu.ndim == 1:
+        mu = mu[:, None]
+    if mu.ndim != 2 or mu.shape[0] < 2:
+        raise ValueError(f"mu has shape {mu.shape}: (degree + 1, probes) moments, degree >= 1")
+    g = kpm_damping(mu.shape[0] - 1, damping) if isinstance(damping, str) or damping is None else np.asarray(damping, float)
+    return mu * g[:, None]
+
+
+def kpm_density(mu, lo: float, hi: float, points, damping="jackson") -> np.ndarray:
+    """The spectral density at `points` from the moments of kpm_moments on [lo, hi], averaged over the probes and
+    normalised to integrate to n (mu[0] is n for +-1 probes):
+        rho(x) = (g_0 mu_0 + 2 sum_i g_i mu_i T_i(t)) / (pi e sqrt(1 - t^2)),   t = (x - c)/e.
+    Points outside (lo, hi) give 0.  Host double arithmetic: not bit-pinned."""
+    m = _kpm_damped(mu, damping).mean(axis=1)
+    c, e = (lo + hi) / 2.0, (hi - lo) / 2.0
+    t = (np.asarray(points, dtype=np.float64) - c) / e
+    inside = np.abs(t) < 1.0
+    th = np.arccos(np.where(inside, t, 0.0))
+    i = np.arange(m.size, dtype=np.float64)
+    w = m * np.where(i == 0, 1.0, 2.0)
+    series = np.cos(th[..., None] * i) @ w
+    return np.where(inside, series / (np.pi * e * np.sin(th)), 0.0)
+
+
+def kpm_count(mu, lo: float, hi: float, a: float, b: float, damping="jackson"):
+    """(estimate, standard_error) of the number of eigenvalues in [a, b] from the moments of kpm_moments on [lo, hi]:
+    the damped series integrated in closed form,
+        count = (g_0 mu_0 (th_a - th_b) + 2 sum_i g_i mu_i (sin(i th_a) - sin(i th_b))/i) / pi,   th = arccos((x - c)/e),
+    a and b clipped to [lo, hi].  The estimate is the probes' mean; the standard error is the spread of the per-probe
+    estimates over sqrt(probes) (0 for one probe).  Host double arithmetic: not bit-pinned."""
+    m = _kpm_damped(mu, damping)
+    c, e = (lo + hi) / 2.0, (hi - lo) / 2.0
+    ta, tb = (float(np.clip((v - c) / e, -1.0, 1.0)) for v in (a, b))
+    tha, thb = np.arccos(ta), np.arccos(tb)
+    i = np.arange(1, m.shape[0], dtype=np.float64)
+    w = np.concatenate([[tha - thb], 2.0 * (np.sin(i * tha) - np.sin(i * thb)) / i]) / np.pi
+    per_probe = w @ m
+    k = per_probe.size
+    err = float(per_probe.std(ddof=1) / np.sqrt(k)) if k > 1 else 0.0
+    return float(per_probe.mean()), err
+
+
 _EIGSH_WHICH = {"LA": 0, "SA": 1}
 
 
@@ -850,6 +965,40 @@ class _DeviceMatrix:
         check(self._fn(f"cheb_series_dev_{_sfx(self.dtype)}")(self._h, vp(x_ptr or None), vp(out_ptr or None),
                                                               u64(max(coef.size, 1) - 1), C.c_double(lo), C.c_double(hi), _p(coef),
                                                               u64(coef.size), _stream_ptr(stream)))
+
+    def kpm_moments(self, degree: int, probes: int = 8, seed: int = 0, interval=None, Z=None):
+        """(mu, info): the Chebyshev moments mu[i, j] = z_j^T T_i(B) z_j, i = 0 .. degree, of `probes` probe columns, B =
+        this symmetric matrix mapped from the interval onto [-1, 1] (spal_*_kpm_moments_*).  mu is float64
+        of shape (degree + 1, probes): bit for bit the text of include/spal.h.  Z = None: hashed +-1 probes from `seed`
+        (kpm_probes gives the same block); else an (n, probes) block of this matrix's dtype.  interval = None:
+        Gershgorin's bounds with the margin of eigsh(sigma=...); else (lo, hi), which must enclose the spectrum."""
+        n = self.shape()[0]
+        if Z is not None:
+            Z = np.asarray(Z, dtype=self.dtype)
+            if Z.ndim != 2 or Z.shape[0] != n:
+                raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT, f"kpm_moments: Z has shape {Z.shape} but the matrix has {n} rows")
+            if Z.strides[1] != Z.itemsize or Z.strides[0] % Z.itemsize or Z.strides[0] < Z.shape[1] * Z.itemsize:
+                Z = np.ascontiguousarray(Z)
+            probes = Z.shape[1]
+        degree, k, automatic, lo, hi = _kpm_args("kpm_moments", degree, probes, interval)
+        mu = np.empty((degree + 1, k), dtype=np.float64)
+        info = _KpmInfoC()
+        ldz = k if Z is None else Z.strides[0] // Z.itemsize
+        check(self._fn(f"kpm_moments_{_sfx(self.dtype)}")(
+            self._h, u64(degree), u64(k), u64(int(seed) % 2**64), C.c_int(automatic), C.c_double(lo), C.c_double(hi),
+            None if Z is None else Z.ctypes.data_as(vp), u64(n), u64(ldz), _p(mu), u64(mu.size), C.byref(info)))
+        return mu, _kpm_info(info)
+
+    def kpm_moments_dev(self, degree: int, probes: int, seed: int = 0, interval=None, z_ptr: int = 0, ldz: int = 0, stream=None):
+        """(mu, info) as kpm_moments, with the probes in device memory at z_ptr (leading dimension ldz >= probes; 0 =
+        hashed probes) and everything enqueued on `stream`; the call synchronises the stream once, at its end."""
+        degree, k, automatic, lo, hi = _kpm_args("kpm_moments_dev", degree, probes, interval)
+        mu = np.empty((degree + 1, k), dtype=np.float64)
+        info = _KpmInfoC()
+        check(self._fn(f"kpm_moments_dev_{_sfx(self.dtype)}")(
+            self._h, u64(degree), u64(k), u64(int(seed) % 2**64), C.c_int(automatic), C.c_double(lo), C.c_double(hi),
+            vp(z_ptr or None), u64(ldz if z_ptr else k), _p(mu), u64(mu.size), _stream_ptr(stream), C.byref(info)))
+        return mu, _kpm_info(info)
 
     def gershgorin(self):
         """(glo, ghi): Gershgorin's enclosure of this square matrix's spectrum, in double (spal_*_gershgorin)."""
@@ -1680,6 +1829,35 @@ class _Compressed:
         if np.shape(x) != (self._nrows,):
             raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT, f"cheb_series: x has shape {np.shape(x)} but the matrix has {self._nrows} rows")
         return self.device(device).cheb_series(x, coef, lo, hi)
+
+    def kpm_moments(self, degree: int, probes: int = 8, seed: int = 0, interval=None, Z=None, device: int = 0):
+        """(mu, info): the Chebyshev moments of `probes` probe columns, mu of shape (degree + 1, probes) in float64
+        (DESIGN 3.29): the text of include/spal.h bit for bit.  The matrix must be symmetric (not checked).  Z = None:
+        hashed +-1 probes from `seed` (kpm_probes); interval = None: Gershgorin's bounds with a margin, else (lo, hi)
+        enclosing the spectrum.  kpm_density and kpm_count turn the moments into the spectral density and into the
+        number of eigenvalues in an interval.  Refused before anything is copied to a device: a degree outside
+        1 .. 4096, probes outside 1 .. 256, an interval that is not finite or is empty, a matrix that is not square,
+        a Z of another shape."""
+        k = probes if Z is None else (np.shape(Z)[1] if np.ndim(Z) == 2 else -1)
+        if Z is not None and (np.ndim(Z) != 2 or np.shape(Z)[0] != self._nrows):
+            raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT, f"kpm_moments: Z has shape {np.shape(Z)} but the matrix has {self._nrows} rows")
+        _kpm_args("kpm_moments", degree, k, interval)
+        if self._nrows != self._ncols:
+            raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT, f"kpm_moments: the matrix is not square ({self._nrows} x {self._ncols})")
+        return self.device(device).kpm_moments(degree, probes, seed, interval, Z)
+
+    def eig_count(self, a: float, b: float, degree: int = 128, probes: int = 32, seed: int = 0, interval=None,
+                  damping="jackson", device: int = 0):
+        """(estimate, standard_error) of the number of eigenvalues of this symmetric matrix in [a, b]: kpm_count of
+        kpm_moments(degree, probes, seed, interval).  The resolution is about pi (hi - lo) / (2 degree)."""
+        mu, info = self.kpm_moments(degree, probes, seed, interval, device=device)
+        return kpm_count(mu, info.lo, info.hi, a, b, damping)
+
+    def spectral_density(self, points, degree: int = 128, probes: int = 32, seed: int = 0, interval=None,
+                         damping="jackson", device: int = 0) -> np.ndarray:
+        """The spectral density at `points`, normalised to integrate to n: kpm_density of kpm_moments(...)."""
+        mu, info = self.kpm_moments(degree, probes, seed, interval, device=device)
+        return kpm_density(mu, info.lo, info.hi, points, damping)
 
     def gershgorin(self, device: int = 0):
         """(glo, ghi): Gershgorin's enclosure of the spectrum, in double, computed on the device."""

@@ -18,7 +18,7 @@ SCALARS = {"int": "c_int", "uint64_t": "u64", "uint32_t": "u32", "int64_t": "i64
 STRUCTS = {"spal_krylov_info": "spal_krylov_info", "spal_amg_params": "spal_amg_params",
            "spal_eigsh_info": "spal_eigsh_info",
            "spal_eigsh_filter_info": "spal_eigsh_filter_info",
-           "spal_eigsh_near_info": "spal_eigsh_near_info"}   # plain structs passed by pointer, declared in render()
+           "spal_eigsh_near_info": "spal_eigsh_near_info", "spal_kpm_info": "spal_kpm_info"}   # plain structs passed by pointer, declared in render()
 HANDLES = {"spal_csr_t": "spal_csr", "spal_csc_t": "spal_csc", "spal_coo_t": "spal_coo", "spal_mg_t": "spal_mg",
            "spal_mg_csr_t": "spal_mg_csr", "spal_amg_t": "spal_amg"}
 
@@ -106,6 +106,10 @@ def render(fns) -> str:
               '#[repr(C)] #[derive(Clone, Copy, Debug, Default)]',
               'pub struct spal_eigsh_near_info { pub restarts: u64, pub products: u64, pub converged: u64, pub reason: c_int, '
               'pub solve_ms: f64, pub lo: f64, pub hi: f64, pub sigma: f64, pub gamma: f64, pub degree: u64 }',
+              '/// What spal_*_kpm_moments_* report: the products per column, the interval, Gershgorin\'s bounds, the degree, the probes.',
+              '#[repr(C)] #[derive(Clone, Copy, Debug, Default)]',
+              'pub struct spal_kpm_info { pub products: u64, pub lo: f64, pub hi: f64, pub glo: f64, pub ghi: f64, pub degree: u64, '
+              'pub probes: u64, pub solve_ms: f64 }',
               '',
               '#[link(name = "spal_hip")]',
               'extern "C" {']
