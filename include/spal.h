@@ -48,6 +48,7 @@ typedef struct spal_coo *spal_coo_t; /* mirrors CooMatrix<T>, src/coo.rs:53-57 (
 typedef struct spal_mg *spal_mg_t;          /* the GPUs of one node + their RCCL communicators */
 typedef struct spal_mg_csr *spal_mg_csr_t;  /* a CsrMatrix partitioned by rows over them */
 typedef struct spal_amg *spal_amg_t;        /* an aggregation multigrid hierarchy (below) */
+typedef struct spal_fsai *spal_fsai_t;      /* a factorised sparse approximate inverse (below) */
 
 /* ---- library ---------------------------------------------------------- */
 const char *spal_last_error(void);   /* thread-local, never NULL */
@@ -1665,6 +1666,112 @@ int spal_csc_krylov_amg_dev_f64(spal_csc_t a, int method, spal_amg_t g, const do
                                 uint64_t maxit, void *stream, spal_krylov_info *info);
 int spal_csc_krylov_amg_dev_f32(spal_csc_t a, int method, spal_amg_t g, const float *b_dev, float *x_dev, double tol,
                                 uint64_t maxit, void *stream, spal_krylov_info *info);
+
+/* ---- FSAI: a factorised sparse approximate inverse, applied by two SpMVs ---------------------------------
+ * Not in the reference.  G ~ L^-1 on a prescribed lower-triangular pattern (Kolotilina - Yeremin), M^-1 = Gt * G: every
+ * row of G comes from one small dense SPD system, independent of every other row.  The contract is again
+ * a sequential text the device reproduces bit for bit, in f32 and f64; T is the handle's element type.
+ *
+ * fsai(A, S; cap) for a square handle A and a pattern S of the same kind, shape, device and element type (NULL: A
+ * itself); S's values are never read.  Only entries on or below the diagonal of A and of S are read: symmetry is
+ * assumed, not checked, as with CG.  Every row of S must store its diagonal.  Every product is rounded before the sum
+ * or difference it enters (no FMA); sqrt and / are the correctly rounded ones.
+ *
+ *   structure of G = the entries (i, j), j <= i, of S, in S's storage order (columns ascending)
+ *   row i:  Q = the columns of row i of G;  P = the last min(|Q|, cap) of them (so P ends in i);  m = |P|
+ *           G[i, j] = +0.0 for j in Q \ P                        (stored zeros: the structure does not depend on cap)
+ *           B[s, t] = the stored entry (P[s], P[t]) of A for s >= t, +0.0 where there is none
+ *           for j = 0..m-1:                                       (Cholesky by columns, B = C Ct)
+ *               d = B[j,j];  for k = 0..j-1:  d = d - (C[j,k]*C[j,k])
+ *               if not (d > 0 and d finite):  REJECT row i
+ *               C[j,j] = sqrt(d)
+ *               for r = j+1..m-1:  t = B[r,j];  for k = 0..j-1:  t = t - (C[r,k]*C[j,k]);   C[r,j] = t / C[j,j]
+ *           g[m-1] = 1 / C[m-1,m-1]                               (Ct g = e_m)
+ *           for t = m-2 down to 0:  s = +0.0;  for u = t+1..m-1:  s = s + (C[u,t]*g[u]);   g[t] = (0 - s) / C[t,t]
+ *           if any g[t] is not finite:  REJECT row i
+ *           G[i, P[t]] = g[t]
+ *   REJECT row i:  G[i, j] = +0.0 for j != i;  G[i,i] = 1/sqrt(a_ii) if a_ii > 0 and finite and 1/sqrt(a_ii) finite,
+ *           else 1;  rejected += 1                                (a_ii = B[m-1,m-1]: the stored (i, i) of A, or +0.0)
+ *   Gt = the transpose of G as a CSR matrix (values moved bit for bit)
+ *   apply(v) = Gt * (G * v), two products of the handles G and Gt
+ *
+ * Every element of C has one fixed order of operations.  Consequences: for SPD A no row is rejected, G A Gt has unit
+ * diagonal up to rounding, and Gt G is SPD.  Rejection makes the result a well-defined, still SPD, locally Jacobi
+ * preconditioner instead of a source of NaN.  THE BITS OF G DO NOT DEPEND ON the stream, which kernel form a row took,
+ * a's plan, or CSR or CSC (a CSC handle runs on its CSR twin, as eigsh does).  apply's bits are those of the two
+ * handles' own spmv: they equal the sequential row sums of the text wherever the handle's SpMV sums rows in sequence,
+ * which is what the solvers say about a's products too.
+ * cap is the option "fsai_max_row" on `a` (spal_*_set_option): default 32, valid 1 .. 64, anything else
+ * SPAL_ERR_INVALID_ARGUMENT.  It is read when setup is called.
+ *
+ * Host, no device: spal_fsai_row_* run the text's Cholesky and back-substitution (and its rejected row) on ONE local
+ * system, b_lower = B's lower triangle packed by rows (m (m + 1) / 2 values, 1 <= m <= 64), g = m values, *rejected =
+ * 0 or 1: a diagnostic aid of the kind of spal_eigsh_jacobi.
+ *
+ * Device (spal_fsai.hip).  Setup is ordered by the stream alone (no flags, no spins): the counts of S's entries with
+ * column <= row, a scan, G's columns, the factor kernel in two forms chosen per row by m (a thread per row with the
+ * triangle in registers for m <= thread_form_max; one wave per row with the triangle packed in LDS above it; the
+ * rows of the second form are listed by the structure pass), the existing device transpose for Gt, and the plans of
+ * both factors, so the first application pays nothing.  Setup synchronises `stream`; f holds its own matrices and
+ * outlives `a`.  spal_fsai_apply_* take host vectors; spal_fsai_apply_dev_* are enqueued on `stream` and not
+ * synchronised (x_dev == b_dev is refused): two products and nothing else, u = G b in the stream's own scratch block,
+ * so, like every call that takes that block, they are refused on a capturing stream.  No lock of f is held across a
+ * product; concurrent applies and solves on one f share nothing but its two matrices.
+ * spal_fsai_describe: {dtype, rows, nnz, cap, max_row (the largest m), capped_rows, rejected, rows_thread_form,
+ * rows_wave_form, block_rows, thread_form_max, setup_ms, structure_ms, kernel_ms, transpose_ms, plan_ms}.
+ * spal_fsai_factor_csr returns an independent handle holding G (transposed = 0) or Gt (1).
+ * spal_*_krylov_fsai_* / spal_*_minres_fsai_*: the arguments of spal_*_krylov_* / spal_*_minres_* with `f` where `m`
+ * stands; f is not NULL and matches `a` in rows, device and element type.  u is one more work vector of the call.
+ * describe()["krylov"] of such a call additionally carries "precond": "fsai".
+ * SPAL_ERR_INVALID_ARGUMENT: a null `a` or `out`, a matrix that is not square, a pattern of another shape, device or
+ * element type, a pattern row without a stored diagonal (the message names the first such row), an _f64 entry on an
+ * f32 handle or the reverse, wrong lengths, x_dev == b_dev.  SPAL_ERR_UNSUPPORTED: a handle held as row blocks.  Every
+ * refusal is made before or without leaving anything allocated.
+ * Not provided: FSAI inside spal_*_gmres_* and the block solvers, adaptive patterns and dropping, a second factor for
+ * nonsymmetric A, several GPUs, graph capture of setup. */
+int spal_csr_fsai_setup(spal_csr_t a, spal_csr_t pattern /* NULL: a */, void *stream, spal_fsai_t *out);
+int spal_csc_fsai_setup(spal_csc_t a, spal_csc_t pattern /* NULL: a */, void *stream, spal_fsai_t *out);
+int spal_fsai_destroy(spal_fsai_t f);                                             /* NULL is fine */
+int spal_fsai_describe(spal_fsai_t f, char *buf, size_t buf_len);
+int spal_fsai_factor_csr(spal_fsai_t f, int transposed, spal_csr_t *copy);
+int spal_fsai_apply_f64(spal_fsai_t f, const double *b, uint64_t b_len, double *x, uint64_t x_len);
+int spal_fsai_apply_f32(spal_fsai_t f, const float *b, uint64_t b_len, float *x, uint64_t x_len);
+int spal_fsai_apply_dev_f64(spal_fsai_t f, const double *b_dev, double *x_dev, void *stream);
+int spal_fsai_apply_dev_f32(spal_fsai_t f, const float *b_dev, float *x_dev, void *stream);
+int spal_fsai_row_f64(uint64_t m, const double *b_lower, double *g, int *rejected);   /* host only */
+int spal_fsai_row_f32(uint64_t m, const float *b_lower, float *g, int *rejected);     /* host only */
+int spal_csr_krylov_fsai_f64(spal_csr_t a, int method, spal_fsai_t f, const double *b, uint64_t b_len, double *x,
+                             uint64_t x_len, double tol, uint64_t maxit, spal_krylov_info *info);
+int spal_csr_krylov_fsai_f32(spal_csr_t a, int method, spal_fsai_t f, const float *b, uint64_t b_len, float *x,
+                             uint64_t x_len, double tol, uint64_t maxit, spal_krylov_info *info);
+int spal_csr_krylov_fsai_dev_f64(spal_csr_t a, int method, spal_fsai_t f, const double *b_dev, double *x_dev, double tol,
+                                 uint64_t maxit, void *stream, spal_krylov_info *info);
+int spal_csr_krylov_fsai_dev_f32(spal_csr_t a, int method, spal_fsai_t f, const float *b_dev, float *x_dev, double tol,
+                                 uint64_t maxit, void *stream, spal_krylov_info *info);
+int spal_csc_krylov_fsai_f64(spal_csc_t a, int method, spal_fsai_t f, const double *b, uint64_t b_len, double *x,
+                             uint64_t x_len, double tol, uint64_t maxit, spal_krylov_info *info);
+int spal_csc_krylov_fsai_f32(spal_csc_t a, int method, spal_fsai_t f, const float *b, uint64_t b_len, float *x,
+                             uint64_t x_len, double tol, uint64_t maxit, spal_krylov_info *info);
+int spal_csc_krylov_fsai_dev_f64(spal_csc_t a, int method, spal_fsai_t f, const double *b_dev, double *x_dev, double tol,
+                                 uint64_t maxit, void *stream, spal_krylov_info *info);
+int spal_csc_krylov_fsai_dev_f32(spal_csc_t a, int method, spal_fsai_t f, const float *b_dev, float *x_dev, double tol,
+                                 uint64_t maxit, void *stream, spal_krylov_info *info);
+int spal_csr_minres_fsai_f64(spal_csr_t a, spal_fsai_t f, double shift, const double *b, uint64_t b_len, double *x,
+                             uint64_t x_len, double tol, uint64_t maxit, spal_krylov_info *info);
+int spal_csr_minres_fsai_f32(spal_csr_t a, spal_fsai_t f, double shift, const float *b, uint64_t b_len, float *x,
+                             uint64_t x_len, double tol, uint64_t maxit, spal_krylov_info *info);
+int spal_csr_minres_fsai_dev_f64(spal_csr_t a, spal_fsai_t f, double shift, const double *b_dev, double *x_dev,
+                                 double tol, uint64_t maxit, void *stream, spal_krylov_info *info);
+int spal_csr_minres_fsai_dev_f32(spal_csr_t a, spal_fsai_t f, double shift, const float *b_dev, float *x_dev,
+                                 double tol, uint64_t maxit, void *stream, spal_krylov_info *info);
+int spal_csc_minres_fsai_f64(spal_csc_t a, spal_fsai_t f, double shift, const double *b, uint64_t b_len, double *x,
+                             uint64_t x_len, double tol, uint64_t maxit, spal_krylov_info *info);
+int spal_csc_minres_fsai_f32(spal_csc_t a, spal_fsai_t f, double shift, const float *b, uint64_t b_len, float *x,
+                             uint64_t x_len, double tol, uint64_t maxit, spal_krylov_info *info);
+int spal_csc_minres_fsai_dev_f64(spal_csc_t a, spal_fsai_t f, double shift, const double *b_dev, double *x_dev,
+                                 double tol, uint64_t maxit, void *stream, spal_krylov_info *info);
+int spal_csc_minres_fsai_dev_f32(spal_csc_t a, spal_fsai_t f, double shift, const float *b_dev, float *x_dev,
+                                 double tol, uint64_t maxit, void *stream, spal_krylov_info *info);
 
 /* ---- CSR <-> CSC on the device ------------------------------------------------
  * Replace `impl From<&CscMatrix<T>> for CsrMatrix<T>` (src/csr/conv/csc.rs:4-52)

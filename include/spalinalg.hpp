@@ -25,6 +25,9 @@
 //   a.gmres_block(B, k, restart, M, X0, tol, maxit)      not in the reference: GMRES on k right-hand sides (spal_*_gmres_block_*)
 //   a.minres(b, M, shift, x0, tol, maxit)                not in the reference: MINRES on (A - shift I) x = b, A symmetric (spal_*_minres_*)
 //   a.minres_block(B, k, M, shift, X0, tol, maxit)       not in the reference: the same on k right-hand sides (spal_*_minres_block_*)
+//   Fsai<T> f(a, &pattern), f.apply(v), f.solve(a, b, ...), f.minres(a, b, shift, ...), fsai_row(b_lower)
+//                                                        not in the reference: the factorised sparse approximate inverse
+//                                                        as a preconditioner (spal_*_fsai_setup, spal_fsai_*)
 //   a.colour(seed), a.permute(perm), a.multicolour(seed), p.ordering(), p.to_order(v), p.from_order(v),
 //   colour_greedy(n, rowptr, colind, seed), perm_from_colours(colours)
 //                                                        not in the reference: the multicolour ordering
@@ -1341,5 +1344,108 @@ CscMatrix<T> CscMatrix<T>::from(const CooMatrix<T> &coo, int device) {
                                              coo.rows().data(), coo.cols().data(), coo.vals().data(), &h));
     return adopt(h);
 }
+
+// ---------------------------------------------------------------------------
+// Fsai<T>: G ~ L^-1 on a prescribed pattern, M^-1 = Gt G    not in the reference (include/spal.h, spal_fsai_*)
+// ---------------------------------------------------------------------------
+namespace detail {
+struct FsaiDeleter { void operator()(spal_fsai *h) const { spal_fsai_destroy(h); } };
+inline int fsai_apply(spal_fsai_t f, const double *b, usize n, double *x) { return spal_fsai_apply_f64(f, b, n, x, n); }
+inline int fsai_apply(spal_fsai_t f, const float *b, usize n, float *x) { return spal_fsai_apply_f32(f, b, n, x, n); }
+inline int fsai_row(usize m, const double *b, double *g, int *rej) { return spal_fsai_row_f64(m, b, g, rej); }
+inline int fsai_row(usize m, const float *b, float *g, int *rej) { return spal_fsai_row_f32(m, b, g, rej); }
+#define SPALINALG_FSAI_SOLVERS(kind, T, sfx)                                                                            \
+    inline int krylov_fsai(spal_##kind##_t a, int method, spal_fsai_t f, const T *b, usize n, T *x, double tol,         \
+                           usize maxit, spal_krylov_info *info) {                                                       \
+        return spal_##kind##_krylov_fsai_##sfx(a, method, f, b, n, x, n, tol, maxit, info);                             \
+    }                                                                                                                   \
+    inline int minres_fsai(spal_##kind##_t a, spal_fsai_t f, double shift, const T *b, usize n, T *x, double tol,       \
+                           usize maxit, spal_krylov_info *info) {                                                       \
+        return spal_##kind##_minres_fsai_##sfx(a, f, shift, b, n, x, n, tol, maxit, info);                              \
+    }
+SPALINALG_FSAI_SOLVERS(csr, double, f64)
+SPALINALG_FSAI_SOLVERS(csr, float, f32)
+SPALINALG_FSAI_SOLVERS(csc, double, f64)
+SPALINALG_FSAI_SOLVERS(csc, float, f32)
+#undef SPALINALG_FSAI_SOLVERS
+}  // namespace detail
+
+// (g, rejected): the text's Cholesky and back-substitution on ONE local system, on the host (spal_fsai_row_*); b_lower
+// is the lower triangle packed by rows, m (m + 1) / 2 values.
+template <typename T>
+std::pair<std::vector<T>, bool> fsai_row(usize m, const std::vector<T> &b_lower) {
+    if (b_lower.size() != m * (m + 1) / 2)
+        throw Panic(SPAL_ERR_INVALID_ARGUMENT, "fsai_row: b_lower.len() = " + std::to_string(b_lower.size()) + " is not m (m + 1) / 2");
+    std::vector<T> g(m);
+    int rejected = 0;
+    detail::check(detail::fsai_row(m, b_lower.data(), g.data(), &rejected));
+    return {std::move(g), rejected != 0};
+}
+
+// The FSAI factor of a square, symmetric positive definite matrix on the lower triangle of `pattern`'s structure
+// (nullptr: the matrix's own), built on the device and owned by this object; it outlives the matrix.  The matrix's
+// option "fsai_max_row" (1 .. 64, default 32) caps a row's local system.  apply(v) = Gt (G v), two SpMVs; solve() and
+// minres() are a.solve() / a.minres() with this factor as M, bit for bit the texts of include/spal.h.
+template <typename T>
+class Fsai {
+  public:
+    explicit Fsai(const CsrMatrix<T> &a, const CsrMatrix<T> *pattern = nullptr, int device = 0) : nrows_(a.nrows()) {
+        spal_fsai_t h = nullptr;
+        detail::check(spal_csr_fsai_setup(a.device_handle(device), pattern ? pattern->device_handle(device) : nullptr, nullptr, &h));
+        h_.reset(h);
+    }
+    explicit Fsai(const CscMatrix<T> &a, const CscMatrix<T> *pattern = nullptr, int device = 0) : nrows_(a.nrows()) {
+        spal_fsai_t h = nullptr;
+        detail::check(spal_csc_fsai_setup(a.device_handle(device), pattern ? pattern->device_handle(device) : nullptr, nullptr, &h));
+        h_.reset(h);
+    }
+    spal_fsai_t handle() const { return h_.get(); }
+    usize nrows() const { return nrows_; }
+    std::string describe() const {
+        std::string buf(4096, '\0');
+        detail::check(spal_fsai_describe(h_.get(), &buf[0], buf.size()));
+        buf.resize(buf.find('\0'));
+        return buf;
+    }
+    std::vector<T> apply(const std::vector<T> &b) const {
+        std::vector<T> x(b.size());
+        detail::check(detail::fsai_apply(h_.get(), b.data(), b.size(), x.data()));
+        return x;
+    }
+    template <typename Matrix>
+    Solution<T> solve(const Matrix &a, const std::vector<T> &b, Method method = Method::Cg, const std::vector<T> &x0 = {},
+                      double tol = 1e-8, usize maxit = 1000) const {
+        Solution<T> s = start("solve", b, x0);
+        spal_krylov_info info;
+        detail::check(detail::krylov_fsai(a.device_handle(), (int)method, h_.get(), b.data(), b.size(), s.x.data(), tol, maxit, &info));
+        return finish(std::move(s), info);
+    }
+    template <typename Matrix>
+    Solution<T> minres(const Matrix &a, const std::vector<T> &b, double shift = 0.0, const std::vector<T> &x0 = {},
+                       double tol = 1e-8, usize maxit = 1000) const {
+        Solution<T> s = start("minres", b, x0);
+        spal_krylov_info info;
+        detail::check(detail::minres_fsai(a.device_handle(), h_.get(), shift, b.data(), b.size(), s.x.data(), tol, maxit, &info));
+        return finish(std::move(s), info);
+    }
+
+  private:
+    Solution<T> start(const char *what, const std::vector<T> &b, const std::vector<T> &x0) const {
+        if (b.size() != nrows_ || (!x0.empty() && x0.size() != nrows_))
+            throw Panic(SPAL_ERR_INVALID_ARGUMENT, std::string(what) + ": b.len() = " + std::to_string(b.size()) + " and x0.len() = " +
+                                                       std::to_string(x0.size()) + " but the factor has " + std::to_string(nrows_) + " rows");
+        return Solution<T>{x0.empty() ? std::vector<T>(nrows_, T(0)) : x0, 0, 0, 0.0, 0.0, 0.0};
+    }
+    static Solution<T> finish(Solution<T> s, const spal_krylov_info &info) {
+        s.iterations = info.iterations;
+        s.reason = info.reason;
+        s.residual_sq = info.residual_sq;
+        s.rhs_sq = info.rhs_sq;
+        s.solve_ms = info.solve_ms;
+        return s;
+    }
+    usize nrows_;
+    std::unique_ptr<spal_fsai, detail::FsaiDeleter> h_;
+};
 
 }  // namespace spalinalg

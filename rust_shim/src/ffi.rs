@@ -12,6 +12,7 @@ use std::os::raw::{c_char, c_int, c_void};
 #[repr(C)] pub struct spal_mg { _private: [u8; 0] }
 #[repr(C)] pub struct spal_mg_csr { _private: [u8; 0] }
 #[repr(C)] pub struct spal_amg { _private: [u8; 0] }
+#[repr(C)] pub struct spal_fsai { _private: [u8; 0] }
 
 pub const SPAL_OK: c_int = 0;
 pub const SPAL_ERR_INVALID_ARGUMENT: c_int = 1;
@@ -273,6 +274,33 @@ extern "C" {
     pub fn spal_csc_krylov_amg_f32(a: *mut spal_csc, method: c_int, g: *mut spal_amg, b: *const f32, b_len: u64, x: *mut f32, x_len: u64, tol: f64, maxit: u64, info: *mut spal_krylov_info) -> c_int;
     pub fn spal_csc_krylov_amg_dev_f64(a: *mut spal_csc, method: c_int, g: *mut spal_amg, b_dev: *const f64, x_dev: *mut f64, tol: f64, maxit: u64, stream: *mut c_void, info: *mut spal_krylov_info) -> c_int;
     pub fn spal_csc_krylov_amg_dev_f32(a: *mut spal_csc, method: c_int, g: *mut spal_amg, b_dev: *const f32, x_dev: *mut f32, tol: f64, maxit: u64, stream: *mut c_void, info: *mut spal_krylov_info) -> c_int;
+    pub fn spal_csr_fsai_setup(a: *mut spal_csr, pattern: *mut spal_csr, stream: *mut c_void, out: *mut *mut spal_fsai) -> c_int;
+    pub fn spal_csc_fsai_setup(a: *mut spal_csc, pattern: *mut spal_csc, stream: *mut c_void, out: *mut *mut spal_fsai) -> c_int;
+    pub fn spal_fsai_destroy(f: *mut spal_fsai) -> c_int;
+    pub fn spal_fsai_describe(f: *mut spal_fsai, buf: *mut c_char, buf_len: usize) -> c_int;
+    pub fn spal_fsai_factor_csr(f: *mut spal_fsai, transposed: c_int, copy: *mut *mut spal_csr) -> c_int;
+    pub fn spal_fsai_apply_f64(f: *mut spal_fsai, b: *const f64, b_len: u64, x: *mut f64, x_len: u64) -> c_int;
+    pub fn spal_fsai_apply_f32(f: *mut spal_fsai, b: *const f32, b_len: u64, x: *mut f32, x_len: u64) -> c_int;
+    pub fn spal_fsai_apply_dev_f64(f: *mut spal_fsai, b_dev: *const f64, x_dev: *mut f64, stream: *mut c_void) -> c_int;
+    pub fn spal_fsai_apply_dev_f32(f: *mut spal_fsai, b_dev: *const f32, x_dev: *mut f32, stream: *mut c_void) -> c_int;
+    pub fn spal_fsai_row_f64(m: u64, b_lower: *const f64, g: *mut f64, rejected: *mut c_int) -> c_int;
+    pub fn spal_fsai_row_f32(m: u64, b_lower: *const f32, g: *mut f32, rejected: *mut c_int) -> c_int;
+    pub fn spal_csr_krylov_fsai_f64(a: *mut spal_csr, method: c_int, f: *mut spal_fsai, b: *const f64, b_len: u64, x: *mut f64, x_len: u64, tol: f64, maxit: u64, info: *mut spal_krylov_info) -> c_int;
+    pub fn spal_csr_krylov_fsai_f32(a: *mut spal_csr, method: c_int, f: *mut spal_fsai, b: *const f32, b_len: u64, x: *mut f32, x_len: u64, tol: f64, maxit: u64, info: *mut spal_krylov_info) -> c_int;
+    pub fn spal_csr_krylov_fsai_dev_f64(a: *mut spal_csr, method: c_int, f: *mut spal_fsai, b_dev: *const f64, x_dev: *mut f64, tol: f64, maxit: u64, stream: *mut c_void, info: *mut spal_krylov_info) -> c_int;
+    pub fn spal_csr_krylov_fsai_dev_f32(a: *mut spal_csr, method: c_int, f: *mut spal_fsai, b_dev: *const f32, x_dev: *mut f32, tol: f64, maxit: u64, stream: *mut c_void, info: *mut spal_krylov_info) -> c_int;
+    pub fn spal_csc_krylov_fsai_f64(a: *mut spal_csc, method: c_int, f: *mut spal_fsai, b: *const f64, b_len: u64, x: *mut f64, x_len: u64, tol: f64, maxit: u64, info: *mut spal_krylov_info) -> c_int;
+    pub fn spal_csc_krylov_fsai_f32(a: *mut spal_csc, method: c_int, f: *mut spal_fsai, b: *const f32, b_len: u64, x: *mut f32, x_len: u64, tol: f64, maxit: u64, info: *mut spal_krylov_info) -> c_int;
+    pub fn spal_csc_krylov_fsai_dev_f64(a: *mut spal_csc, method: c_int, f: *mut spal_fsai, b_dev: *const f64, x_dev: *mut f64, tol: f64, maxit: u64, stream: *mut c_void, info: *mut spal_krylov_info) -> c_int;
+    pub fn spal_csc_krylov_fsai_dev_f32(a: *mut spal_csc, method: c_int, f: *mut spal_fsai, b_dev: *const f32, x_dev: *mut f32, tol: f64, maxit: u64, stream: *mut c_void, info: *mut spal_krylov_info) -> c_int;
+    pub fn spal_csr_minres_fsai_f64(a: *mut spal_csr, f: *mut spal_fsai, shift: f64, b: *const f64, b_len: u64, x: *mut f64, x_len: u64, tol: f64, maxit: u64, info: *mut spal_krylov_info) -> c_int;
+    pub fn spal_csr_minres_fsai_f32(a: *mut spal_csr, f: *mut spal_fsai, shift: f64, b: *const f32, b_len: u64, x: *mut f32, x_len: u64, tol: f64, maxit: u64, info: *mut spal_krylov_info) -> c_int;
+    pub fn spal_csr_minres_fsai_dev_f64(a: *mut spal_csr, f: *mut spal_fsai, shift: f64, b_dev: *const f64, x_dev: *mut f64, tol: f64, maxit: u64, stream: *mut c_void, info: *mut spal_krylov_info) -> c_int;
+    pub fn spal_csr_minres_fsai_dev_f32(a: *mut spal_csr, f: *mut spal_fsai, shift: f64, b_dev: *const f32, x_dev: *mut f32, tol: f64, maxit: u64, stream: *mut c_void, info: *mut spal_krylov_info) -> c_int;
+    pub fn spal_csc_minres_fsai_f64(a: *mut spal_csc, f: *mut spal_fsai, shift: f64, b: *const f64, b_len: u64, x: *mut f64, x_len: u64, tol: f64, maxit: u64, info: *mut spal_krylov_info) -> c_int;
+    pub fn spal_csc_minres_fsai_f32(a: *mut spal_csc, f: *mut spal_fsai, shift: f64, b: *const f32, b_len: u64, x: *mut f32, x_len: u64, tol: f64, maxit: u64, info: *mut spal_krylov_info) -> c_int;
+    pub fn spal_csc_minres_fsai_dev_f64(a: *mut spal_csc, f: *mut spal_fsai, shift: f64, b_dev: *const f64, x_dev: *mut f64, tol: f64, maxit: u64, stream: *mut c_void, info: *mut spal_krylov_info) -> c_int;
+    pub fn spal_csc_minres_fsai_dev_f32(a: *mut spal_csc, f: *mut spal_fsai, shift: f64, b_dev: *const f32, x_dev: *mut f32, tol: f64, maxit: u64, stream: *mut c_void, info: *mut spal_krylov_info) -> c_int;
     pub fn spal_csc_to_csr(a: *mut spal_csc, out: *mut *mut spal_csr) -> c_int;
     pub fn spal_csr_to_csc(a: *mut spal_csr, out: *mut *mut spal_csc) -> c_int;
     pub fn spal_csr_mul(a: *mut spal_csr, b: *mut spal_csr, stream: *mut c_void, out: *mut *mut spal_csr) -> c_int;

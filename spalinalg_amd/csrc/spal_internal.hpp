@@ -338,6 +338,7 @@ struct OpState {
     int kpm_tile = 0;              // option "kpm_tile": column tile of the KPM block step, 0 = automatic (spal_kpm.hip)
     int kpm_form = 0;              // option "kpm_form": 0 = automatic, 1 = dots fused into the step, 2 = step and dot launches apart
     std::string kpm_info;          // "kpm": the last spal_*_kpm_moments_* call with this handle as A (the same lock)
+    int64_t fsai_max_row = 32;     // option "fsai_max_row": the largest local system of a row of G, 1 .. 64 (spal_fsai.hip)
     // a result of spal_*_permute / _multicolour (spal_colour.hip): written once, before the handle is
     // returned, and only read afterwards
     uint32_t *d_perm = nullptr;    // nrows: new -> old; freed by ordering_free (csr_free, csc_free)

@@ -31,7 +31,9 @@
 // option "trsv_sweeps" is s >= 0 is applied by s Jacobi sweeps per triangle instead (trsv_sweep_enqueue),
 // through two more work vectors of the call.  The spal_*_krylov_amg_* entry points run the same two loops with an AMG
 // hierarchy `g` in m's place (Precond): M^-1 v is one multigrid cycle (amg_apply_enqueue, spal_amg.hip),
-// enqueued into the hierarchy's own work vectors under its own lock.  Plans are built before the first iteration; work
+// enqueued into the hierarchy's own work vectors under its own lock.  The spal_*_krylov_fsai_* / spal_*_minres_fsai_*
+// entry points put an FSAI factor `f` there (spal_fsai.hip): M^-1 v = Gt (G v), two products through one
+// more work vector of the call, so concurrent calls on one f share nothing but its two matrices.  Plans are built before the first iteration; work
 // vectors, the scratch and the scalar block come from the caching allocator per call, so concurrent calls on one handle
 // share nothing but the matrix.
 #include "krylov_kernels.hpp"
@@ -181,7 +183,7 @@ int dot_dev(const char *fn, int device, const T *a, const T *b, uint64_t n, T *o
 constexpr int kMinres = 2;   // the method of the spal_*_minres_* entry points in here; spal_*_krylov_* refuse it
 
 struct Record {
-    int method = 0, preconditioned = 0, reason = 0, amg = 0;
+    int method = 0, preconditioned = 0, reason = 0, amg = 0, fsai = 0;
     int64_t precond_sweeps = -1;
     uint64_t iterations = 0, polls = 0;
     int64_t check_every = 0;
@@ -195,17 +197,19 @@ std::string info_json(const Record &r) {
              "\"polls\": %llu, \"solve_ms\": %.4f, \"precond_sweeps\": %lld%s%s}",
              r.method == SPAL_KRYLOV_CG ? "cg" : r.method == kMinres ? "minres" : "bicgstab", r.preconditioned,
              (unsigned long long)r.iterations, r.reason, (long long)r.check_every, (unsigned long long)r.polls, r.solve_ms,
-             (long long)r.precond_sweeps, r.amg ? ", \"precond\": \"amg\"" : "",
-             shift);   // (the objects written by CG and BiCGStab without a hierarchy do not change)
+             (long long)r.precond_sweeps, r.amg ? ", \"precond\": \"amg\"" : r.fsai ? ", \"precond\": \"fsai\"" : "",
+             shift);   // (the objects written without a hierarchy or an FSAI factor do not change)
     return buf;
 }
 
-// The preconditioner of a call: an ILU(0) factor m, an AMG hierarchy g (spal_amg.hip), or neither.  Never both.
+// The preconditioner of a call: an ILU(0) factor m, an AMG hierarchy g (spal_amg.hip), an FSAI factor f (spal_fsai.hip),
+// or none.  Never two.
 template <typename H>
 struct Precond {
     H *m;
     spal_amg *g;
-    explicit operator bool() const { return m || g; }   // M^-1 is there: z, ph and sh are vectors of their own
+    spal_fsai *f = nullptr;
+    explicit operator bool() const { return m || g || f; }   // M^-1 is there: z, ph and sh are vectors of their own
 };
 
 // The driver the loops of krylov_loops.hpp run on: an operand is a device vector; the scalar block, the scratch of two
@@ -223,6 +227,7 @@ struct Run {
     int64_t sweeps = -1;            // m's option "trsv_sweeps"
     T *vecs = nullptr;              // work vector i at vecs + i * stride
     T *w0 = nullptr, *w1 = nullptr; // the sweeps' ping-pong vectors
+    T *fu = nullptr;                // FSAI: u = G v, between the two products
     const T *b = nullptr;
     T *x = nullptr;
     SolveFrame<Scal<T>> frame;
@@ -236,6 +241,7 @@ struct Run {
     int mul(const T *v, T *out) { return mul_dev(a, v, out, st); }
     // out = M^-1 v (out != v); without a preconditioner the loops use v itself
     int prec(const T *v, T *out) {
+        if (pc.f) return fsai_apply_enqueue(fn, pc.f, v, fu, out, st);
         return pc.g ? amg_apply_enqueue(fn, pc.g, v, out, st) : prec_dev<T, H>(fn, pc.m, sweeps, v, out, w0, w1, st);
     }
     template <int OP>
@@ -276,7 +282,7 @@ int krylov_run(const char *fn, H *a, int method, Precond<H> pc, double shift, co
     const bool cg = method == SPAL_KRYLOV_CG;
     const bool minres = method == kMinres;   // v, r1 / r2 / t, w1 / w2, and y with a preconditioner
     const int nwork = minres ? (pre ? 7 : 6) : cg ? (pre ? 4 : 3) : (pre ? 8 : 6);
-    const int nvec = nwork + (sweeps >= 0 ? 2 : 0);
+    const int nvec = nwork + (sweeps >= 0 ? 2 : 0) + (pc.f ? 1 : 0);
     DevBuf vecs, parts, scal;
     const uint64_t stride = (n + 63) & ~(uint64_t)63;   // every vector on a 256-byte boundary at least
     SPAL_HIP_TRY(vecs.alloc((size_t)nvec * stride * sizeof(T)));
@@ -305,6 +311,7 @@ int krylov_run(const char *fn, H *a, int method, Precond<H> pc, double shift, co
         R.w0 = R.work(nwork);
         R.w1 = R.work(nwork + 1);
     }
+    if (pc.f) R.fu = R.work(nvec - 1);
     R.b = b;
     R.x = x;
 
@@ -324,6 +331,7 @@ int krylov_run(const char *fn, H *a, int method, Precond<H> pc, double shift, co
     rec.method = method;
     rec.preconditioned = pre ? 1 : 0;
     rec.amg = pc.g ? 1 : 0;
+    rec.fsai = pc.f ? 1 : 0;
     rec.precond_sweeps = sweeps;
     rec.reason = info->reason;
     rec.iterations = info->iterations;
@@ -346,6 +354,7 @@ int krylov_check(const char *fn, H *a, int method, bool minres, Precond<H> pc, d
         return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: method = %d must be 0 (CG) or 1 (BiCGStab)", fn, method);
     if (!std::isfinite(shift)) return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: shift = %g must be finite", fn, shift);
     SPAL_TRY((krylov_check_operands<T, H>(fn, a, pc.m, tol)));
+    if (pc.f) return fsai_check_match(fn, pc.f, a->nrows, a->device, a->elem_size);
     return pc.g ? amg_check_match(fn, pc.g, a->nrows, a->device, a->elem_size) : SPAL_OK;
 }
 
@@ -416,22 +425,27 @@ int spal_dot_dev_f32(int device, const float *a_dev, const float *b_dev, uint64_
         if (NEEDS_M && !m) return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: null argument", fn);                            \
         return krylov_dev<T, spal_##kind>(fn, a, method, false, PRECOND, 0.0, b_dev, x_dev, tol, maxit, stream, info);           \
     }
-// MINRES on (A - shift I) x = b: the arguments of spal_*_krylov_* without `method`, with `shift` after m
-#define SPAL_MINRES_ENTRIES(kind, sfx, T)                                                                              \
-    int spal_##kind##_minres_##sfx(spal_##kind##_t a, spal_##kind##_t m, double shift, const T *b, uint64_t b_len,     \
-                                   T *x, uint64_t x_len, double tol, uint64_t maxit, spal_krylov_info *info) {         \
-        return krylov_host<T, spal_##kind>("spal_" #kind "_minres", a, 0, true, Precond<spal_##kind>{m, nullptr},      \
-                                           shift, b, b_len, x, x_len, tol, maxit, info);                               \
+// MINRES on (A - shift I) x = b: the arguments of spal_*_krylov_* without `method`, with `shift` after m.  name =
+// minres: m is a factor or NULL.  name = minres_fsai: m is an FSAI factor, which is not optional.
+#define SPAL_MINRES_ENTRIES(kind, name, sfx, T, M, NEEDS_M, PRECOND)                                                   \
+    int spal_##kind##_##name##_##sfx(spal_##kind##_t a, M m, double shift, const T *b, uint64_t b_len, T *x,           \
+                                     uint64_t x_len, double tol, uint64_t maxit, spal_krylov_info *info) {             \
+        const char *fn = "spal_" #kind "_" #name;                                                                      \
+        if (NEEDS_M && !m) return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: null argument", fn);                            \
+        return krylov_host<T, spal_##kind>(fn, a, 0, true, PRECOND, shift, b, b_len, x, x_len, tol, maxit, info);      \
     }                                                                                                                  \
-    int spal_##kind##_minres_dev_##sfx(spal_##kind##_t a, spal_##kind##_t m, double shift, const T *b_dev, T *x_dev,   \
-                                       double tol, uint64_t maxit, void *stream, spal_krylov_info *info) {             \
-        return krylov_dev<T, spal_##kind>("spal_" #kind "_minres_dev", a, 0, true, Precond<spal_##kind>{m, nullptr},   \
-                                          shift, b_dev, x_dev, tol, maxit, stream, info);                              \
+    int spal_##kind##_##name##_dev_##sfx(spal_##kind##_t a, M m, double shift, const T *b_dev, T *x_dev, double tol,   \
+                                         uint64_t maxit, void *stream, spal_krylov_info *info) {                       \
+        const char *fn = "spal_" #kind "_" #name "_dev";                                                               \
+        if (NEEDS_M && !m) return fail(SPAL_ERR_INVALID_ARGUMENT, "%s: null argument", fn);                            \
+        return krylov_dev<T, spal_##kind>(fn, a, 0, true, PRECOND, shift, b_dev, x_dev, tol, maxit, stream, info);     \
     }
 #define SPAL_KRYLOV_KINDS(kind, sfx, T)                                                                                \
-    SPAL_MINRES_ENTRIES(kind, sfx, T)                                                                                  \
+    SPAL_MINRES_ENTRIES(kind, minres, sfx, T, spal_##kind##_t, false, (Precond<spal_##kind>{m, nullptr}))              \
+    SPAL_MINRES_ENTRIES(kind, minres_fsai, sfx, T, spal_fsai_t, true, (Precond<spal_##kind>{nullptr, nullptr, m}))     \
     SPAL_KRYLOV_ENTRIES(kind, krylov, sfx, T, spal_##kind##_t, false, (Precond<spal_##kind>{m, nullptr}))              \
-    SPAL_KRYLOV_ENTRIES(kind, krylov_amg, sfx, T, spal_amg_t, true, (Precond<spal_##kind>{nullptr, m}))
+    SPAL_KRYLOV_ENTRIES(kind, krylov_amg, sfx, T, spal_amg_t, true, (Precond<spal_##kind>{nullptr, m}))                \
+    SPAL_KRYLOV_ENTRIES(kind, krylov_fsai, sfx, T, spal_fsai_t, true, (Precond<spal_##kind>{nullptr, nullptr, m}))
 SPAL_KRYLOV_KINDS(csr, f64, double)
 SPAL_KRYLOV_KINDS(csr, f32, float)
 SPAL_KRYLOV_KINDS(csc, f64, double)

@@ -1,5 +1,5 @@
 // spal_ops.hpp -- the host layer the sparse operations share: spal_spgemm.hip, spal_spadd.hip,
-// spal_spmm.hip, spal_trsv.hip, spal_trsv_sweep.hip, spal_trsm.hip, spal_ilu.hip, spal_ilu_sweep.hip, spal_krylov.hip, spal_krylov_block.hip, spal_gmres.hip, spal_gmres_block.hip, spal_eigsh.hip, spal_cheb.hip, spal_kpm.hip, spal_colour.hip and spal_amg.hip keep their kernels, their driver, their option's validation and their
+// spal_spmm.hip, spal_trsv.hip, spal_trsv_sweep.hip, spal_trsm.hip, spal_ilu.hip, spal_ilu_sweep.hip, spal_krylov.hip, spal_krylov_block.hip, spal_gmres.hip, spal_gmres_block.hip, spal_eigsh.hip, spal_cheb.hip, spal_kpm.hip, spal_colour.hip, spal_amg.hip and spal_fsai.hip keep their kernels, their driver, their option's validation and their
 // info JSON; what surrounds a launch the same way in each of them is here, once.  (Not installed.)
 #pragma once
 
@@ -183,6 +183,12 @@ int64_t trsv_sweeps_of(spal_csr *a);   // the option "trsv_sweeps" of a solve ha
 int amg_check_match(const char *fn, const spal_amg *g, uint64_t nrows, int device, int elem_size);
 int amg_apply_enqueue(const char *fn, spal_amg *g, const void *b, void *x, hipStream_t st);
 
+// ---- the FSAI factor as a preconditioner (spal_fsai.hip), for spal_krylov.hip ------------------------------
+// match: as amg_check_match.  enqueue: x = Gt * (G * b) on `st` through u (b, u and x distinct device vectors of f's
+// element type): two products of planned handles; takes no lock of f, allocates and synchronises nothing.
+int fsai_check_match(const char *fn, const spal_fsai *f, uint64_t nrows, int device, int elem_size);
+int fsai_apply_enqueue(const char *fn, spal_fsai *f, const void *b, void *u, void *x, hipStream_t st);
+
 // ---- the Chebyshev filter's launches (spal_cheb.hip), for spal_eigsh.hip -----------------------------------
 // All on a solve handle's plain arrays, enqueued on `st`, allocating and synchronising nothing.  chunk: the option
 // "cheb_chunk" (0 = default).  rowsum: out = rowsum(y), out != y.  apply: out = t_d through `work` (n elements, unused
@@ -214,13 +220,15 @@ int krylov_block_option(spal_csr *a, const char *key, int64_t value, OpState &s,
 int eigsh_option(spal_csr *a, const char *key, int64_t value, OpState &s, int *status);   // "eigsh_rotate"
 int cheb_option(spal_csr *a, const char *key, int64_t value, OpState &s, int *status);    // "cheb_chunk", "cheb_series_form"
 int kpm_option(spal_csr *a, const char *key, int64_t value, OpState &s, int *status);     // "kpm_tile", "kpm_form"
+int fsai_option(spal_csr *a, const char *key, int64_t value, OpState &s, int *status);    // "fsai_max_row"
 inline int ops_set_option(OpState &s, spal_csr *solve, const char *key, int64_t value, int *status) {
     return spgemm_option(key, value, s, status) || spadd_option(key, value, s, status) ||
            spmm_option(key, value, s, status) || trsv_option(solve, key, value, status) ||
            trsv_sweep_option(solve, key, value, status) || trsm_option(solve, key, value, status) ||
            ilu_option(solve, key, value, status) || krylov_option(solve, key, value, s, status) ||
            krylov_block_option(solve, key, value, s, status) || eigsh_option(solve, key, value, s, status) ||
-           cheb_option(solve, key, value, s, status) || kpm_option(solve, key, value, s, status);
+           cheb_option(solve, key, value, s, status) || kpm_option(solve, key, value, s, status) ||
+           fsai_option(solve, key, value, s, status);
 }
 
 // (describe_append itself is host code: spal_host.cpp, declared in spal_internal.hpp)

@@ -468,10 +468,111 @@ class Amg:
         return agg
 
 
+# --------------------------------------------------------------------------
+# FSAI (include/spal.h)
+# --------------------------------------------------------------------------
+def fsai_row(B_lower, dtype=None):
+    """(g, rejected): the text's Cholesky and back-substitution of include/spal.h on ONE local system, on the host
+    (spal_fsai_row_*): no device needed.  `B_lower` is the lower triangle of B packed by rows (m (m + 1) / 2 values) or
+    a square 2-D array, whose lower triangle is taken."""
+    b = np.asarray(B_lower)
+    dt = np.dtype(dtype) if dtype is not None else (b.dtype if b.dtype in (np.float32, np.float64) else np.dtype(np.float64))
+    if b.ndim == 2:
+        if b.shape[0] != b.shape[1]:
+            raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT, f"fsai_row: B has shape {b.shape}")
+        b = b[np.tril_indices(b.shape[0])]
+    b = np.ascontiguousarray(b, dtype=dt)
+    m = int((np.sqrt(8.0 * b.size + 1.0) - 1.0) / 2.0 + 0.5)
+    if b.ndim != 1 or m * (m + 1) // 2 != b.size:
+        raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT, f"fsai_row: {b.size} values are no packed lower triangle")
+    g = np.empty(m, dtype=dt)
+    rejected = C.c_int(0)
+    check(getattr(_ffi.lib(), f"spal_fsai_row_{_sfx(dt)}")(u64(m), _p(b), _p(g), C.byref(rejected)))
+    return g, rejected.value
+
+
+class Fsai:
+    """A factorised sparse approximate inverse on the device (spal_*_fsai_setup): G ~ L^-1 on a prescribed pattern, bit
+    for bit the text of include/spal.h; apply(b) = Gt (G b), two SpMVs on planned handles; `a.solve(b, M=f)` and
+    `a.minres(b, M=f)` precondition CG / BiCGStab / MINRES with it.  It holds its own matrices and outlives the matrix
+    it was built from."""
+
+    def __init__(self, handle, dtype, device: int, nrows: int):
+        self._h = handle
+        self.dtype = np.dtype(dtype)
+        self.device = device
+        self._nrows = int(nrows)
+        self._factors = {}
+
+    def close(self):
+        if self._h is not None:
+            _ffi.lib().spal_fsai_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def nrows(self) -> int:
+        return self._nrows
+
+    def describe(self) -> dict:
+        buf = C.create_string_buffer(4096)
+        check(_ffi.lib().spal_fsai_describe(self._h, buf, C.c_size_t(len(buf))))
+        return json.loads(buf.value.decode())
+
+    @property
+    def rejected(self) -> int:
+        return int(self.describe()["rejected"])
+
+    def _factor(self, transposed: int) -> "CsrMatrix":
+        if transposed not in self._factors:
+            out = vp()
+            check(_ffi.lib().spal_fsai_factor_csr(self._h, C.c_int(transposed), C.byref(out)))
+            dev = DeviceCsr(out, self.dtype, self.device)
+            n = dev.shape()[0]
+            ptr, ind, val = dev.download()
+            m = CsrMatrix._trusted(n, n, ptr, ind, val)
+            m._dev[self.device] = dev
+            self._factors[transposed] = m
+        return self._factors[transposed]
+
+    @property
+    def G(self) -> "CsrMatrix":
+        """G as a CsrMatrix (an independent copy, downloaded; it keeps its device handle)."""
+        return self._factor(0)
+
+    @property
+    def Gt(self) -> "CsrMatrix":
+        """The transpose of G, likewise."""
+        return self._factor(1)
+
+    def apply(self, b) -> np.ndarray:
+        """x = Gt (G b) for a host vector of the factor's dtype."""
+        b = np.ascontiguousarray(b)
+        if b.dtype not in (np.float32, np.float64):
+            b = b.astype(self.dtype)
+        if b.ndim != 1:
+            raise TypeError("apply() takes one 1-D vector")
+        x = np.empty_like(b)
+        check(getattr(_ffi.lib(), f"spal_fsai_apply_{_sfx(b.dtype)}")(self._h, _p(b), u64(b.size), _p(x), u64(x.size)))
+        return x
+
+    def apply_dev(self, b_ptr: int, x_ptr: int, stream=None, dtype=None) -> None:
+        """Device pointers (x != b): two products enqueued on `stream`, not synchronised."""
+        dt = self.dtype if dtype is None else np.dtype(dtype)
+        check(getattr(_ffi.lib(), f"spal_fsai_apply_dev_{_sfx(dt)}")(self._h, vp(b_ptr), vp(x_ptr), _stream_ptr(stream)))
+
+
 def _refuse_amg(M, what: str) -> None:
     if isinstance(M, Amg):
         raise TypeError(f"{what} takes an ILU(0) factor as M, not an Amg: an AMG hierarchy preconditions solve() "
                         "(method 'cg' or 'bicgstab') only")
+    if isinstance(M, Fsai) and what != "minres()":   # (solve() dispatches on an Fsai before it asks here)
+        raise TypeError(f"{what} takes an ILU(0) factor as M, not an Fsai: an FSAI factor preconditions solve() "
+                        "(method 'cg' or 'bicgstab') and minres() only")
 
 
 # --------------------------------------------------------------------------
@@ -506,6 +607,8 @@ class _DeviceMatrix:
 
     def set_option(self, key: str, value: int) -> None:
         check(self._fn("set_option")(self._h, key.encode(), C.c_int64(value)))
+        if key == "fsai_max_row":
+            self._fsai_max_row = int(value)   # (what fsai(max_row=...) restores)
 
     def describe(self) -> dict:
         buf = C.create_string_buffer(16384)
@@ -762,6 +865,11 @@ class _DeviceMatrix:
                                                           u64(b.size), _p(x), u64(x.size), C.c_double(tol), u64(maxit),
                                                           C.byref(info)))
             return x, _krylov_info(info)
+        if isinstance(M, Fsai):   # ... with M^-1 v = Gt (G v) (spal_*_krylov_fsai_*)
+            check(self._fn(f"krylov_fsai_{_sfx(b.dtype)}")(self._h, C.c_int(_krylov_method(method)), M._h, _p(b),
+                                                           u64(b.size), _p(x), u64(x.size), C.c_double(tol), u64(maxit),
+                                                           C.byref(info)))
+            return x, _krylov_info(info)
         if M is not None and type(M) is not type(self):
             raise TypeError(f"M must be a {type(self).__name__} (the factor of a matrix of the same format)")
         check(self._fn(f"krylov_{_sfx(b.dtype)}")(self._h, C.c_int(_krylov_method(method)), M._h if M is not None else None,
@@ -777,6 +885,11 @@ class _DeviceMatrix:
             check(self._fn(f"krylov_amg_dev_{_sfx(self.dtype)}")(self._h, C.c_int(_krylov_method(method)), M._h,
                                                                  vp(b_ptr), vp(x_ptr), C.c_double(tol), u64(maxit),
                                                                  _stream_ptr(stream), C.byref(info)))
+            return _krylov_info(info)
+        if isinstance(M, Fsai):
+            check(self._fn(f"krylov_fsai_dev_{_sfx(self.dtype)}")(self._h, C.c_int(_krylov_method(method)), M._h,
+                                                                  vp(b_ptr), vp(x_ptr), C.c_double(tol), u64(maxit),
+                                                                  _stream_ptr(stream), C.byref(info)))
             return _krylov_info(info)
         check(self._fn(f"krylov_dev_{_sfx(self.dtype)}")(self._h, C.c_int(_krylov_method(method)),
                                                          M._h if M is not None else None, vp(b_ptr), vp(x_ptr),
@@ -825,9 +938,13 @@ class _DeviceMatrix:
         if b.ndim != 1:
             raise TypeError("minres() takes one right-hand side, a 1-D vector")
         x = np.zeros_like(b) if x0 is None else np.array(x0, dtype=b.dtype, order="C", copy=True)
+        info = _KrylovInfoC()
+        if isinstance(M, Fsai):   # M^-1 v = Gt (G v), symmetric positive definite by construction (spal_*_minres_fsai_*)
+            check(self._fn(f"minres_fsai_{_sfx(b.dtype)}")(self._h, M._h, C.c_double(shift), _p(b), u64(b.size), _p(x),
+                                                           u64(x.size), C.c_double(tol), u64(maxit), C.byref(info)))
+            return x, _krylov_info(info)
         if M is not None and type(M) is not type(self):
             raise TypeError(f"M must be a {type(self).__name__} (the factor of a matrix of the same format)")
-        info = _KrylovInfoC()
         check(self._fn(f"minres_{_sfx(b.dtype)}")(self._h, M._h if M is not None else None, C.c_double(shift), _p(b),
                                                   u64(b.size), _p(x), u64(x.size), C.c_double(tol), u64(maxit),
                                                   C.byref(info)))
@@ -837,6 +954,11 @@ class _DeviceMatrix:
                    stream=None) -> KrylovInfo:
         """Device pointers: x holds x0 on entry and the result on exit; the call polls, so it synchronises `stream`."""
         info = _KrylovInfoC()
+        if isinstance(M, Fsai):
+            check(self._fn(f"minres_fsai_dev_{_sfx(self.dtype)}")(self._h, M._h, C.c_double(shift), vp(b_ptr), vp(x_ptr),
+                                                                  C.c_double(tol), u64(maxit), _stream_ptr(stream),
+                                                                  C.byref(info)))
+            return _krylov_info(info)
         check(self._fn(f"minres_dev_{_sfx(self.dtype)}")(self._h, M._h if M is not None else None, C.c_double(shift),
                                                          vp(b_ptr), vp(x_ptr), C.c_double(tol), u64(maxit),
                                                          _stream_ptr(stream), C.byref(info)))
@@ -1128,6 +1250,24 @@ class _DeviceMatrix:
         out = vp()
         check(self._fn("amg_setup")(self._h, C.byref(params), _stream_ptr(stream), C.byref(out)))
         return Amg(out, self.dtype, self.device, self.shape()[0])
+
+    def fsai(self, pattern=None, max_row=None, stream=None) -> Fsai:
+        """The FSAI factor of this square matrix on the pattern of `pattern`, a handle of this class (None: this
+        matrix's own), an Fsai (spal_*_fsai_setup).  `max_row` sets the option "fsai_max_row" (1 .. 64,
+        default 32) for this call and restores it afterwards; synchronises `stream`."""
+        if pattern is not None and type(pattern) is not type(self):
+            raise TypeError(f"pattern must be a {type(self).__name__} (a matrix of the same format)")
+        keep = getattr(self, "_fsai_max_row", 32)
+        out = vp()
+        if max_row is not None:
+            self.set_option("fsai_max_row", int(max_row))
+        try:
+            check(self._fn("fsai_setup")(self._h, pattern._h if pattern is not None else None, _stream_ptr(stream),
+                                         C.byref(out)))
+        finally:
+            if max_row is not None:
+                self.set_option("fsai_max_row", keep)
+        return Fsai(out, self.dtype, self.device, self.shape()[0])
 
     def colour(self, seed: int = 0, stream=None):
         """The greedy colouring of this square matrix's graph by hashed priority (spal_*_colour): exactly
@@ -1690,6 +1830,10 @@ class _Compressed:
             if precond_sweeps is not None:
                 raise TypeError("precond_sweeps is an option of an ILU(0) factor: an Amg has no triangular sweeps")
             return self.device(device).krylov(b, method, M, x0, tol, maxit)
+        if isinstance(M, Fsai):   # M^-1 v = Gt (G v), two SpMVs: `M = a.fsai()`
+            if precond_sweeps is not None:
+                raise TypeError("precond_sweeps is an option of an ILU(0) factor: an Fsai has no triangular sweeps")
+            return self.device(device).krylov(b, method, M, x0, tol, maxit)
         if M is not None and type(M) is not type(self):
             raise TypeError(f"M must be a {type(self).__name__}, e.g. self.ilu0()")
         if precond_sweeps is not None:
@@ -1732,6 +1876,10 @@ class _Compressed:
             raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT, f"{who}: the matrix is not square ({self._nrows} x {self._ncols})")
         if not np.isfinite(float(shift)):
             raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT, f"{who}: shift = {float(shift)} must be finite")
+        if isinstance(M, Fsai):   # (minres() only: minres_block() has refused it above)
+            if precond_sweeps is not None:
+                raise TypeError("precond_sweeps is an option of an ILU(0) factor: an Fsai has no triangular sweeps")
+            return M
         if M is not None and type(M) is not type(self):
             raise TypeError(f"M must be a {type(self).__name__}, e.g. self.ilu0()")
         if precond_sweeps is not None:
@@ -2022,6 +2170,27 @@ class _Compressed:
         self._square("amg")
         _amg_params(seed, max_levels, coarse_rows, nu, coarse_sweeps, cycle, omega, alpha)   # refused before any upload
         return self.device(device).amg(seed, max_levels, coarse_rows, nu, coarse_sweeps, cycle, omega, alpha)
+
+    def fsai(self, pattern=None, max_row=None, device: int = 0) -> Fsai:
+        """The factorised sparse approximate inverse of this square, symmetric positive definite matrix, an
+        :class:`Fsai` (spal_*_fsai_setup): G ~ L^-1 on the lower triangle of `pattern`'s structure (a
+        matrix of this class and shape, None: this matrix's own), M^-1 = Gt G, symmetric positive definite by
+        construction and applied by two SpMVs.  Every row of the pattern must store its diagonal; `max_row` (1 .. 64,
+        default 32) caps a row's local system.  A denser pattern buys iterations with the library's own product::
+
+            f = a.fsai(pattern=a @ a)
+            x, info = a.solve(b, M=f)
+            x, info = a.minres(b, M=f, shift=0.5)
+        """
+        self._square("fsai")
+        if pattern is not None and type(pattern) is not type(self):
+            raise TypeError(f"pattern must be a {type(self).__name__} (a matrix of the same format)")
+        if pattern is not None and (pattern._nrows, pattern._ncols) != (self._nrows, self._ncols):
+            raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT, f"fsai: the pattern is {pattern._nrows} x {pattern._ncols} but the "
+                                                        f"matrix {self._nrows} x {self._ncols}")
+        if max_row is not None and not 1 <= int(max_row) <= 64:
+            raise Panic(_ffi.SPAL_ERR_INVALID_ARGUMENT, f"fsai: max_row = {int(max_row)} must be 1 .. 64")
+        return self.device(device).fsai(None if pattern is None else pattern.device(device), max_row)
 
     def _square(self, what: str) -> None:
         if self._nrows != self._ncols:

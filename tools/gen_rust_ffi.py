@@ -20,7 +20,7 @@ STRUCTS = {"spal_krylov_info": "spal_krylov_info", "spal_amg_params": "spal_amg_
            "spal_eigsh_filter_info": "spal_eigsh_filter_info",
            "spal_eigsh_near_info": "spal_eigsh_near_info", "spal_kpm_info": "spal_kpm_info"}   # plain structs passed by pointer, declared in render()
 HANDLES = {"spal_csr_t": "spal_csr", "spal_csc_t": "spal_csc", "spal_coo_t": "spal_coo", "spal_mg_t": "spal_mg",
-           "spal_mg_csr_t": "spal_mg_csr", "spal_amg_t": "spal_amg"}
+           "spal_mg_csr_t": "spal_mg_csr", "spal_amg_t": "spal_amg", "spal_fsai_t": "spal_fsai"}
 
 
 def rust_type(ctype: str) -> str:
