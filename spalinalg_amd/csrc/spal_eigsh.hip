@@ -27,11 +27,17 @@
 //
 // FILTERED EIGSH (spal_*_eigsh_filtered_*) is the same Run on p(A): the step's product becomes the Chebyshev
 // recurrence of spal_cheb.hip (d launches, stream-ordered), and a phase ends with the rotation FIRST and then the true
-// residuals of the leading columns (one rowsum launch, two dots per column) behind a second poll.  The plain driver and
-// its bits are untouched: the filter is a host-side branch in Run::step.
+// residuals of the leading columns (one rowsum launch, two dots per column) behind a second poll.  The plain call's bits
+// are untouched: the filter is a host-side branch in Run::step.
 //
 // EIGSH NEAR SIGMA (spal_*_eigsh_near_*) is the filtered Run again with the step's product a Chebyshev SERIES,
 // the delta filter at sigma (cheb_host.hpp has its coefficients and the interval); no warm-up, the same phase end.
+//
+// WHAT THE THREE CALLS SHARE, each written once: `Run` (what is enqueued: start, step, the rotations), `Workspace` (every
+// allocation of a run of phases and the pointers into them; `phase`: steps keep .. m, the poll, S, the projected problem;
+// `restart`), `eigsh_staged` (the host form: lengths, v0 and X through device buffers on a stream of the call's own) and
+// `Described` (what a describe object holds beside the public info).  What differs stays apart: `eigsh_run` decides on
+// Ritz residuals and rotates only to restart; `filtered_phases` rotates first and decides on true residuals.
 #include "eigsh_host.hpp"
 #include "gmres_kernels.hpp"
 
@@ -218,26 +224,7 @@ template <typename T> std::atomic<uint64_t> &lds_done();
 template <> std::atomic<uint64_t> &lds_done<double>() { return g_lds_f64; }
 template <> std::atomic<uint64_t> &lds_done<float>() { return g_lds_f32; }
 
-// ---- the driver -------------------------------------------------------------------------------------------------------
-struct Record {
-    uint64_t k = 0, ncv = 0, keep = 0, restarts = 0, products = 0, converged = 0, polls = 0, basis_bytes = 0;
-    int which = 0, reason = 0, rotate = 0;
-    unsigned tile_rows = 0;
-    double rotate_ms = 0.0, solve_ms = 0.0;
-};
-std::string info_json(const Record &r) {
-    char buf[640];
-    snprintf(buf, sizeof buf,
-             "{\"k\": %llu, \"which\": \"%s\", \"ncv\": %llu, \"keep\": %llu, \"restarts\": %llu, \"products\": %llu, "
-             "\"converged\": %llu, \"reason\": %d, \"polls\": %llu, \"rotate\": \"%s\", \"rotate_tile_rows\": %u, "
-             "\"basis_bytes\": %llu, \"rotate_ms\": %.4f, \"solve_ms\": %.4f}",
-             (unsigned long long)r.k, r.which == SPAL_EIGSH_LA ? "LA" : "SA", (unsigned long long)r.ncv, (unsigned long long)r.keep,
-             (unsigned long long)r.restarts, (unsigned long long)r.products, (unsigned long long)r.converged, r.reason,
-             (unsigned long long)r.polls, r.rotate == 1 ? "batch" : "lds", r.tile_rows, (unsigned long long)r.basis_bytes,
-             r.rotate_ms, r.solve_ms);
-    return buf;
-}
-
+// ---- the run: what a call enqueues -------------------------------------------------------------------------------------
 struct PinnedBuf {
     void *p = nullptr;
     PinnedBuf() = default;
@@ -246,6 +233,12 @@ struct PinnedBuf {
     ~PinnedBuf() { if (p) (void)hipHostFree(p); }
     hipError_t alloc(size_t bytes) { return hipHostMalloc(&p, bytes ? bytes : 1, hipHostMallocDefault); }
     template <typename U> U *as() { return reinterpret_cast<U *>(p); }
+};
+
+// the true pair of a leading column in the filtered calls: th = x . A x, res = || A x - th x ||
+template <typename T>
+struct TruePair {
+    T th, res;
 };
 
 template <typename T>
@@ -320,6 +313,16 @@ struct Run {
         if (le != hipSuccess) return fail(SPAL_ERR_HIP, "%s: launch failed: %s", fn, hipGetErrorString(le));
         return SPAL_OK;
     }
+    // The basis becomes its own first nc rotated columns: v_c <- sum_t Y[t, c] v_t, t < jj; with `carry`, v_nc <- the old
+    // v_m.  Form 1 rotates out of place, so the two bases change places; form 2 rotates where the basis is.
+    int rotate_basis(const RitzPairs &rp, uint64_t jj, uint64_t nc, bool carry) {
+        const T *carry_src = carry ? v_at(m) : nullptr;
+        if (form != 1) return rotate(rp, jj, nc, RotOut<T>{basis, stride, 1}, carry_src, v_at(nc));
+        SPAL_TRY(rotate(rp, jj, nc, RotOut<T>{alt, stride, 1}, carry_src, alt + nc * stride));
+        std::swap(basis, alt);
+        V.v = basis;
+        return SPAL_OK;
+    }
 };
 
 template <typename H>
@@ -328,160 +331,221 @@ int rotate_form_of(H *a) {
     return a->ops.eigsh_rotate ? a->ops.eigsh_rotate : 2;   // the faster one where both were measured
 }
 
-// x_dev: n x ldx by rows, or nullptr; theta, resid: k host values
-template <typename T, typename H>
-int eigsh_run(const char *fn, H *a, uint64_t k, int which, uint64_t ncv, const T *v0_dev, uint64_t seed, double tol,
-              uint64_t maxit, T *theta, T *resid, T *x_dev, uint64_t ldx, hipStream_t st, spal_eigsh_info *info) {
-    const uint64_t n = a->nrows, m = ncv;
-    SPAL_TRY(refuse_capture(fn, st, "the call polls and synchronises"));
-    SPAL_TRY(product_plan(solve_handle(a)));
-    const int form = rotate_form_of(a);
+// ---- the workspace: what a run of phases owns, and the part of a phase that every call shares ---------------------------
+enum class PhaseEnd { pairs_ready, device_stopped, ritz_failed };
 
-    // the basis (m + 1 vectors), w, and for the out-of-place rotation a second basis, in one block
-    const uint64_t nvec = (m + 1) + 1 + (form == 1 ? m + 1 : 0);
-    const uint64_t stride = (n + 63) & ~(uint64_t)63;   // every vector on a 256-byte boundary at least
-    const uint64_t basis_bytes = nvec * stride * sizeof(T);
+// The vectors in one block: the basis (m + 1 vectors), w, `extra_vectors` work vectors (none for the plain product, one
+// for the recurrence, two for the series) and, for the out-of-place rotation, a second basis.  The scalars in one block:
+// the head, h, c, the m x m columns, then `true_pairs` TruePairs.  The host's half of the phases lives here too: S, the
+// projected matrix in double, and its Ritz pairs.
+template <typename T>
+struct Workspace {
     DevBuf vecs, parts, scal, ydev;
-    PinnedBuf hpin, ypin;
+    PinnedBuf hpin, ypin, tpin;
     SolveFrame<GHead<T>> F;
-    EventSpans rev;
-    {
-        const hipError_t e = vecs.alloc((size_t)basis_bytes);
-        if (e == hipErrorOutOfMemory)
-            return fail(SPAL_ERR_OUT_OF_MEMORY, "%s: no memory for the basis: %llu vectors of %llu elements (%llu bytes)", fn,
-                        (unsigned long long)nvec, (unsigned long long)n, (unsigned long long)basis_bytes);
-        SPAL_HIP_TRY(e);
-    }
-    const uint64_t pe = scratch_elems(n);
-    SPAL_HIP_TRY(parts.alloc(std::max<uint64_t>(m, 2) * pe * sizeof(T)));
-    const size_t scal_bytes = sizeof(GHead<T>) + (2 * (m + 1) + m * m) * sizeof(T);
-    SPAL_HIP_TRY(scal.alloc(scal_bytes));
-    SPAL_HIP_TRY(ydev.alloc(m * kMaxNcv * sizeof(T)));
-    SPAL_HIP_TRY(hpin.alloc(m * m * sizeof(T)));
-    SPAL_HIP_TRY(ypin.alloc(m * kMaxNcv * sizeof(T)));
-    SPAL_TRY(F.create(st, 1));
-    SPAL_HIP_TRY(rev.create(1));
-
+    EventSpans rev;   // one span for the driver: the rotation's time, or the true residuals'
     Run<T> R;
-    R.fn = fn;
-    R.a = solve_handle(a);
-    R.st = st;
-    R.n = n;
-    R.m = m;
-    R.c1 = tiles_of(n);
-    R.pe = pe;
-    R.stride = stride;
-    R.grid = first_level_grid(n);
-    R.form = form;
-    R.device = a->device;
-    R.s = scal.as<GHead<T>>();
-    R.h = reinterpret_cast<T *>(reinterpret_cast<char *>(scal.p) + sizeof(GHead<T>));
-    R.c = R.h + (m + 1);
-    R.H = R.c + (m + 1);
-    R.basis = vecs.as<T>();
-    R.w = R.basis + (m + 1) * stride;
-    R.alt = form == 1 ? R.w + stride : nullptr;
-    R.part = parts.as<T>();
-    R.y_dev = ydev.as<T>();
-    R.y_pin = ypin.as<T>();
-    R.V.v = R.basis;
-    R.V.stride = stride;
-    R.V.n = n;
-    R.V.tiles = tiles_of(n);
-
-    const GHead<T> *h = F.h;
-    const T *cols = hpin.as<T>();
-    SPAL_TRY(F.begin(scal.p, scal_bytes));
-    SPAL_TRY(R.start(v0_dev, seed));
-
-    std::vector<double> S(m * m, 0.0), Sw;
+    uint64_t m = 0, basis_bytes = 0;
+    size_t scal_bytes = 0;
+    TruePair<T> *pairs_dev = nullptr;
+    std::vector<double> S, Sw;
     RitzPairs rp;
-    uint64_t keep = 0, restarts = 0, jj = 0, conv = 0;
-    int reason = 0;
-    double rotate_ms = 0.0;
-    bool rotating = false;
-    for (;;) {
+    uint64_t keep = 0, restarts = 0, jj = 0;   // the phase runs steps keep .. m; jj vectors span the space after it
+
+    template <typename H>
+    int create(const char *fn, H *a, uint64_t ncv, int form, uint64_t extra_vectors, uint64_t true_pairs, hipStream_t st) {
+        const uint64_t n = a->nrows;
+        m = ncv;
+        const uint64_t nvec = (m + 1) + 1 + extra_vectors + (form == 1 ? m + 1 : 0);
+        const uint64_t stride = (n + 63) & ~(uint64_t)63;   // every vector on a 256-byte boundary at least
+        basis_bytes = nvec * stride * sizeof(T);
+        {
+            const hipError_t e = vecs.alloc((size_t)basis_bytes);
+            if (e == hipErrorOutOfMemory)
+                return fail(SPAL_ERR_OUT_OF_MEMORY, "%s: no memory for the basis: %llu vectors of %llu elements (%llu bytes)", fn,
+                            (unsigned long long)nvec, (unsigned long long)n, (unsigned long long)basis_bytes);
+            SPAL_HIP_TRY(e);
+        }
+        const uint64_t pe = scratch_elems(n);
+        SPAL_HIP_TRY(parts.alloc(std::max<uint64_t>(m, 2) * pe * sizeof(T)));
+        const size_t pair_off = sizeof(GHead<T>) + (2 * (m + 1) + m * m) * sizeof(T);
+        scal_bytes = pair_off + true_pairs * sizeof(TruePair<T>);
+        SPAL_HIP_TRY(scal.alloc(scal_bytes));
+        SPAL_HIP_TRY(ydev.alloc(m * kMaxNcv * sizeof(T)));
+        SPAL_HIP_TRY(hpin.alloc(m * m * sizeof(T)));
+        SPAL_HIP_TRY(ypin.alloc(m * kMaxNcv * sizeof(T)));
+        if (true_pairs) SPAL_HIP_TRY(tpin.alloc(true_pairs * sizeof(TruePair<T>)));
+        SPAL_TRY(F.create(st, 1));
+        SPAL_HIP_TRY(rev.create(1));
+
+        R.fn = fn;
+        R.a = solve_handle(a);
+        R.st = st;
+        R.n = n;
+        R.m = m;
+        R.c1 = tiles_of(n);
+        R.pe = pe;
+        R.stride = stride;
+        R.grid = first_level_grid(n);
+        R.form = form;
+        R.device = a->device;
+        R.s = scal.as<GHead<T>>();
+        R.h = reinterpret_cast<T *>(reinterpret_cast<char *>(scal.p) + sizeof(GHead<T>));
+        R.c = R.h + (m + 1);
+        R.H = R.c + (m + 1);
+        pairs_dev = reinterpret_cast<TruePair<T> *>(reinterpret_cast<char *>(scal.p) + pair_off);
+        R.basis = vecs.as<T>();
+        R.w = R.basis + (m + 1) * stride;
+        R.work = extra_vectors >= 1 ? R.w + stride : nullptr;
+        R.work2 = extra_vectors >= 2 ? R.work + stride : nullptr;
+        R.alt = form == 1 ? R.w + (1 + extra_vectors) * stride : nullptr;
+        R.part = parts.as<T>();
+        R.y_dev = ydev.as<T>();
+        R.y_pin = ypin.as<T>();
+        R.V.v = R.basis;
+        R.V.stride = stride;
+        R.V.n = n;
+        R.V.tiles = tiles_of(n);
+        S.assign(m * m, 0.0);
+        return SPAL_OK;
+    }
+
+    // the span "solve_ms" reports begins; the scalars are zeroed and v_0 is set
+    int begin(const T *v0_dev, uint64_t seed) {
+        SPAL_TRY(F.begin(scal.p, scal_bytes));
+        return R.start(v0_dev, seed);
+    }
+
+    // Steps keep .. m, then ONE poll: the head, and the columns with it.  S takes the new columns and the projected
+    // problem is solved with `which`: rp holds the pairs, jj their number, F.h->hn the coupling.  The call ends where
+    // the device stopped (F.h->reason says why) or the projected problem has no solution (the call's reason 2).
+    int phase(int which, PhaseEnd *end) {
         for (uint64_t j = keep; j < m; ++j) SPAL_TRY(R.step((unsigned)j));
-        SPAL_HIP_TRY(hipMemcpyAsync(hpin.p, R.H, m * m * sizeof(T), hipMemcpyDeviceToHost, st));
-        SPAL_TRY(F.poll());   // one poll per phase: the head, and the columns with it
-        if (rotating) {
-            float ms = 0.f;
-            if (rev.span(0, &ms) == hipSuccess) rotate_ms += ms;
-            rotating = false;
-        }
+        SPAL_HIP_TRY(hipMemcpyAsync(hpin.p, R.H, m * m * sizeof(T), hipMemcpyDeviceToHost, R.st));
+        SPAL_TRY(F.poll());
+        const GHead<T> *h = F.h;
         if (h->done) {
-            reason = (int)h->reason;
-            break;
+            *end = PhaseEnd::device_stopped;
+            return SPAL_OK;
         }
-        if (!h->cyc_end) return fail(SPAL_ERR_HIP, "%s: the device did not end a phase of %llu steps", fn, (unsigned long long)(m - keep));
+        if (!h->cyc_end)
+            return fail(SPAL_ERR_HIP, "%s: the device did not end a phase of %llu steps", R.fn, (unsigned long long)(m - keep));
         jj = h->jj;
+        const T *cols = hpin.as<T>();
         for (uint64_t j = keep; j < jj; ++j)
             for (uint64_t t = 0; t <= j; ++t) S[t * m + j] = S[j * m + t] = (double)cols[j * m + t];   // exact
         Sw.resize(jj * jj);
         for (uint64_t r = 0; r < jj; ++r)
             for (uint64_t q = 0; q < jj; ++q) Sw[r * jj + q] = S[r * m + q];
-        if (!eigsh_ritz(jj, Sw.data(), (double)h->hn, which, &rp)) {
-            reason = 2;
+        *end = eigsh_ritz(jj, Sw.data(), (double)h->hn, which, &rp) ? PhaseEnd::pairs_ready : PhaseEnd::ritz_failed;
+        return SPAL_OK;
+    }
+
+    // the next phase begins at step `kept`, on a basis that was rotated: S = diag(theta)
+    int restart(uint64_t kept) {
+        const char *fn = R.fn;
+        hipStream_t st = R.st;
+        keep = kept;
+        KRYLOV_LAUNCH((phase_start<T>), 1, R.s, (unsigned)keep);
+        std::fill(S.begin(), S.end(), 0.0);
+        for (uint64_t i = 0; i < keep; ++i) S[i * m + i] = rp.theta[i];
+        ++restarts;
+        return SPAL_OK;
+    }
+};
+
+// ---- the describe objects ---------------------------------------------------------------------------------------------
+// What a describe object reports beside the call's arguments and its public info.  The workspace's values stay zero
+// where a call ended before it had one.
+struct Described {
+    uint64_t keep = 0, polls = 0, basis_bytes = 0, chunk = 0;
+    double phase_ms = 0.0;   // the rotations of the plain call ("rotate_ms"), the true residuals of the others ("residual_ms")
+    double glo = 0.0, ghi = 0.0;
+};
+std::string info_json(uint64_t k, int which, uint64_t ncv, int form, unsigned tile_rows, const spal_eigsh_info &i, const Described &d) {
+    char buf[640];
+    snprintf(buf, sizeof buf,
+             "{\"k\": %llu, \"which\": \"%s\", \"ncv\": %llu, \"keep\": %llu, \"restarts\": %llu, \"products\": %llu, "
+             "\"converged\": %llu, \"reason\": %d, \"polls\": %llu, \"rotate\": \"%s\", \"rotate_tile_rows\": %u, "
+             "\"basis_bytes\": %llu, \"rotate_ms\": %.4f, \"solve_ms\": %.4f}",
+             (unsigned long long)k, which == SPAL_EIGSH_LA ? "LA" : "SA", (unsigned long long)ncv, (unsigned long long)d.keep,
+             (unsigned long long)i.restarts, (unsigned long long)i.products, (unsigned long long)i.converged, i.reason,
+             (unsigned long long)d.polls, form == 1 ? "batch" : "lds", tile_rows, (unsigned long long)d.basis_bytes, d.phase_ms,
+             i.solve_ms);
+    return buf;
+}
+
+// ---- plain eigsh -----------------------------------------------------------------------------------------
+// The stop is decided on the Ritz residuals of the projected problem; the basis is rotated only to restart, and once more
+// into x.  x_dev: n x ldx by rows, or nullptr; theta, resid: k host values
+template <typename T, typename H>
+int eigsh_run(const char *fn, H *a, uint64_t k, int which, uint64_t ncv, const T *v0_dev, uint64_t seed, double tol,
+              uint64_t maxit, T *theta, T *resid, T *x_dev, uint64_t ldx, hipStream_t st, spal_eigsh_info *info) {
+    const uint64_t m = ncv;
+    SPAL_TRY(refuse_capture(fn, st, "the call polls and synchronises"));
+    SPAL_TRY(product_plan(solve_handle(a)));
+    const int form = rotate_form_of(a);
+    Workspace<T> W;
+    SPAL_TRY(W.create(fn, a, m, form, 0, 0, st));
+    Run<T> &R = W.R;
+    const GHead<T> *h = W.F.h;   // as of the last poll
+    SPAL_TRY(W.begin(v0_dev, seed));
+
+    uint64_t conv = 0;
+    int reason = 0;
+    double rotate_ms = 0.0;
+    bool rotating = false;
+    for (;;) {
+        PhaseEnd end;
+        SPAL_TRY(W.phase(which, &end));
+        if (rotating) {   // the poll has waited for the restart's rotation
+            float ms = 0.f;
+            if (W.rev.span(0, &ms) == hipSuccess) rotate_ms += ms;
+            rotating = false;
+        }
+        if (end != PhaseEnd::pairs_ready) {
+            reason = end == PhaseEnd::device_stopped ? (int)h->reason : 2;
             break;
         }
-        conv = eigsh_converged(rp, std::min(k, jj), tol);
+        conv = eigsh_converged(W.rp, std::min(k, W.jj), tol);
         if (h->hn == T(0)) {   // the space is exhausted: the pairs are final
-            reason = jj >= k ? 0 : 3;
+            reason = W.jj >= k ? 0 : 3;
             break;
         }
         if (conv == k) {
             reason = 0;
             break;
         }
-        if (restarts == maxit) {
+        if (W.restarts == maxit) {
             reason = 1;
             break;
         }
-        keep = eigsh_keep(k, m);
-        SPAL_HIP_TRY(hipEventRecord(rev.e[0], st));
-        if (form == 1) {
-            SPAL_TRY(R.rotate(rp, m, keep, RotOut<T>{R.alt, stride, 1}, R.v_at(m), R.alt + keep * stride));
-            std::swap(R.basis, R.alt);
-            R.V.v = R.basis;
-        } else {
-            SPAL_TRY(R.rotate(rp, m, keep, RotOut<T>{R.basis, stride, 1}, R.v_at(m), R.v_at(keep)));
-        }
-        SPAL_HIP_TRY(hipEventRecord(rev.e[1], st));
+        const uint64_t keep = eigsh_keep(k, m);
+        SPAL_HIP_TRY(hipEventRecord(W.rev.e[0], st));
+        SPAL_TRY(R.rotate_basis(W.rp, m, keep, true));
+        SPAL_HIP_TRY(hipEventRecord(W.rev.e[1], st));
         rotating = true;
-        KRYLOV_LAUNCH((phase_start<T>), 1, R.s, (unsigned)keep);
-        std::fill(S.begin(), S.end(), 0.0);
-        for (uint64_t i = 0; i < keep; ++i) S[i * m + i] = rp.theta[i];
-        ++restarts;
+        SPAL_TRY(W.restart(keep));
     }
-    const uint64_t nk = reason == 2 ? 0 : std::min(k, jj);
-    if (nk && x_dev) SPAL_TRY(R.rotate(rp, jj, nk, RotOut<T>{x_dev, 1, ldx}, nullptr, nullptr));
+    const uint64_t nk = reason == 2 ? 0 : std::min(k, W.jj);
+    if (nk && x_dev) SPAL_TRY(R.rotate(W.rp, W.jj, nk, RotOut<T>{x_dev, 1, ldx}, nullptr, nullptr));
     float ms = 0.f;
-    SPAL_TRY(F.end(&ms));
+    SPAL_TRY(W.F.end(&ms));
     for (uint64_t i = 0; i < nk; ++i) {
-        theta[i] = (T)rp.theta[i];
-        resid[i] = (T)rp.res[i];
+        theta[i] = (T)W.rp.theta[i];
+        resid[i] = (T)W.rp.res[i];
     }
-    info->restarts = restarts;
+    info->restarts = W.restarts;
     info->products = h->it;
     info->converged = reason == 2 ? 0 : conv;
     info->reason = reason;
     info->solve_ms = (double)ms;
-    Record rec;
-    rec.k = k;
-    rec.which = which;
-    rec.ncv = ncv;
-    rec.keep = eigsh_keep(k, m);
-    rec.restarts = restarts;
-    rec.products = info->products;
-    rec.converged = info->converged;
-    rec.reason = reason;
-    rec.polls = F.polls;
-    rec.rotate = form;
-    rec.tile_rows = form == 1 ? 0 : rot_tile_rows<T>(m);
-    rec.basis_bytes = basis_bytes;
-    rec.rotate_ms = rotate_ms;
-    rec.solve_ms = info->solve_ms;
-    store_info(a, &OpState::eigsh_info, info_json(rec));
+    Described d;
+    d.keep = eigsh_keep(k, m);
+    d.polls = W.F.polls;
+    d.basis_bytes = W.basis_bytes;
+    d.phase_ms = rotate_ms;
+    store_info(a, &OpState::eigsh_info, info_json(k, which, ncv, form, form == 1 ? 0 : rot_tile_rows<T>(m), *info, d));
     return SPAL_OK;
 }
 
@@ -513,20 +577,12 @@ int eigsh_check(const char *fn, H *a, uint64_t k, int which, uint64_t ncv, doubl
     return SPAL_OK;
 }
 
-template <typename T, typename H>
-int eigsh_dev(const char *fn, H *a, uint64_t k, int which, uint64_t ncv, const T *v0_dev, uint64_t seed, double tol, uint64_t maxit,
-              T *theta, T *resid, T *x_dev, uint64_t ldx, void *stream, spal_eigsh_info *info) {
-    SPAL_TRY((eigsh_check<T, H>(fn, a, k, which, ncv, tol, theta, resid, x_dev, ldx, info)));
-    DeviceGuard guard(a->device);
-    if (guard.status != SPAL_OK) return guard.status;
-    return eigsh_run<T, H>(fn, a, k, which, ncv, v0_dev, seed, tol, maxit, theta, resid, x_dev, ldx, (hipStream_t)stream, info);
-}
-
-template <typename T, typename H>
-int eigsh_host(const char *fn, H *a, uint64_t k, int which, uint64_t ncv, const T *v0, uint64_t v0_len, uint64_t seed, double tol,
-               uint64_t maxit, T *theta, uint64_t theta_len, T *resid, uint64_t resid_len, T *x, uint64_t ldx, uint64_t x_rows,
-               spal_eigsh_info *info) {
-    SPAL_TRY((eigsh_check<T, H>(fn, a, k, which, ncv, tol, theta, resid, x, ldx, info)));
+// The host form of all three calls, after the call's own check: the lengths, the device, v0 and X staged on a stream of
+// the call's own, `run(v0_dev, x_dev, ldx = k, stream)`, and the columns the call produced copied back -- only those:
+// reason 2 leaves X as it was, reason 3 has `converged` = jj < k pairs.
+template <typename T, typename H, typename Info, typename Call>
+int eigsh_staged(const char *fn, H *a, uint64_t k, const T *v0, uint64_t v0_len, uint64_t theta_len, uint64_t resid_len, T *x,
+                 uint64_t ldx, uint64_t x_rows, const Info *info, Call run) {
     const uint64_t n = a->nrows;
     if ((v0 && v0_len != n) || theta_len != k || resid_len != k || (x && x_rows != n))
         return fail(SPAL_ERR_INVALID_ARGUMENT,
@@ -545,9 +601,7 @@ int eigsh_host(const char *fn, H *a, uint64_t k, int which, uint64_t ncv, const 
     if (x) SPAL_HIP_TRY(dx.alloc(bytes));
     SPAL_HIP_TRY(stream_acquire(&ps.s));
     if (v0) SPAL_HIP_TRY(hipMemcpyAsync(dv.p, v0, n * sizeof(T), hipMemcpyHostToDevice, ps.s));
-    SPAL_TRY((eigsh_run<T, H>(fn, a, k, which, ncv, v0 ? (const T *)dv.p : nullptr, seed, tol, maxit, theta, resid,
-                              x ? dx.as<T>() : nullptr, k, ps.s, info)));
-    // the columns the call produced, and only those: reason 2 leaves X as it was, reason 3 has `converged` = jj < k pairs
+    SPAL_TRY(run(v0 ? (const T *)dv.p : nullptr, x ? dx.as<T>() : nullptr, k, ps.s));
     const uint64_t got = info->reason == 2 ? 0 : info->reason == 3 ? info->converged : k;
     if (x && got) {
         SPAL_HIP_TRY(hipMemcpy2DAsync(x, (size_t)ldx * sizeof(T), dx.p, row, (size_t)got * sizeof(T), n, hipMemcpyDeviceToHost, ps.s));
@@ -556,16 +610,32 @@ int eigsh_host(const char *fn, H *a, uint64_t k, int which, uint64_t ncv, const 
     return SPAL_OK;
 }
 
+template <typename T, typename H>
+int eigsh_dev(const char *fn, H *a, uint64_t k, int which, uint64_t ncv, const T *v0_dev, uint64_t seed, double tol, uint64_t maxit,
+              T *theta, T *resid, T *x_dev, uint64_t ldx, void *stream, spal_eigsh_info *info) {
+    SPAL_TRY((eigsh_check<T, H>(fn, a, k, which, ncv, tol, theta, resid, x_dev, ldx, info)));
+    DeviceGuard guard(a->device);
+    if (guard.status != SPAL_OK) return guard.status;
+    return eigsh_run<T, H>(fn, a, k, which, ncv, v0_dev, seed, tol, maxit, theta, resid, x_dev, ldx, (hipStream_t)stream, info);
+}
+
+template <typename T, typename H>
+int eigsh_host(const char *fn, H *a, uint64_t k, int which, uint64_t ncv, const T *v0, uint64_t v0_len, uint64_t seed, double tol,
+               uint64_t maxit, T *theta, uint64_t theta_len, T *resid, uint64_t resid_len, T *x, uint64_t ldx, uint64_t x_rows,
+               spal_eigsh_info *info) {
+    SPAL_TRY((eigsh_check<T, H>(fn, a, k, which, ncv, tol, theta, resid, x, ldx, info)));
+    return eigsh_staged<T>(fn, a, k, v0, v0_len, theta_len, resid_len, x, ldx, x_rows, info,
+                           [&](const T *v0_dev, T *x_dev, uint64_t ld, hipStream_t st) {
+                               return eigsh_run<T, H>(fn, a, k, which, ncv, v0_dev, seed, tol, maxit, theta, resid, x_dev, ld, st, info);
+                           });
+}
+
+
 // ---- filtered eigsh ---------------------------------------------------------------------------------------
 // Lanczos on p(A), a Chebyshev polynomial of A (spal_cheb.hip): the step above with w = cheb_apply(v_j).  The projected
 // problem then holds values of p, so convergence is decided on TRUE residuals with A: at a phase end the host rotates
 // first (the columns are the restart's), then per leading column one product, two dots and two scalar launches, and a
 // second poll brings the nk pairs (th, res) down.
-
-template <typename T>
-struct TruePair {
-    T th, res;
-};
 
 // part[tile] = the tile's sum of a[i] * b[i]
 template <typename T>
@@ -616,12 +686,6 @@ __global__ __launch_bounds__(kThreads) void columns_out(Basis<T> V, unsigned nc,
         for (unsigned c = 0; c < nc; ++c) x[i * ldx + c] = V.v[(uint64_t)c * V.stride + i];
 }
 
-struct FilterRecord {
-    Record r;
-    uint64_t degree = 0, warm_restarts = 0, warm_products = 0, chunk = 0;
-    int automatic = 0;
-    double lo = 0.0, hi = 0.0, a0 = 0.0, glo = 0.0, ghi = 0.0, residual_ms = 0.0;
-};
 // a double as JSON: a value that is not finite (Gershgorin's bounds of a matrix that holds one) is null
 std::string json_number(double v) {
     if (!std::isfinite(v)) return "null";
@@ -629,20 +693,19 @@ std::string json_number(double v) {
     snprintf(buf, sizeof buf, "%.17g", v);
     return buf;
 }
-std::string filter_json(const FilterRecord &f) {
+std::string filter_json(uint64_t k, int which, uint64_t ncv, int automatic, const spal_eigsh_filter_info &i, const Described &d) {
     char buf[1280];
-    const Record &r = f.r;
     snprintf(buf, sizeof buf,
              "{\"k\": %llu, \"which\": \"%s\", \"ncv\": %llu, \"keep\": %llu, \"degree\": %llu, \"interval\": \"%s\", \"lo\": %s, "
              "\"hi\": %s, \"a0\": %s, \"glo\": %s, \"ghi\": %s, \"warm_restarts\": %llu, \"warm_products\": %llu, "
              "\"restarts\": %llu, \"products\": %llu, \"converged\": %llu, \"reason\": %d, \"polls\": %llu, \"chunk\": %llu, "
              "\"basis_bytes\": %llu, \"residual_ms\": %.4f, \"solve_ms\": %.4f}",
-             (unsigned long long)r.k, r.which == SPAL_EIGSH_LA ? "LA" : "SA", (unsigned long long)r.ncv, (unsigned long long)r.keep,
-             (unsigned long long)f.degree, f.automatic ? "auto" : "given", json_number(f.lo).c_str(), json_number(f.hi).c_str(),
-             json_number(f.a0).c_str(), json_number(f.glo).c_str(), json_number(f.ghi).c_str(),
-             (unsigned long long)f.warm_restarts, (unsigned long long)f.warm_products, (unsigned long long)r.restarts,
-             (unsigned long long)r.products, (unsigned long long)r.converged, r.reason, (unsigned long long)r.polls,
-             (unsigned long long)f.chunk, (unsigned long long)r.basis_bytes, f.residual_ms, r.solve_ms);
+             (unsigned long long)k, which == SPAL_EIGSH_LA ? "LA" : "SA", (unsigned long long)ncv, (unsigned long long)d.keep,
+             (unsigned long long)i.degree, automatic ? "auto" : "given", json_number(i.lo).c_str(), json_number(i.hi).c_str(),
+             json_number(i.a0).c_str(), json_number(d.glo).c_str(), json_number(d.ghi).c_str(),
+             (unsigned long long)i.warm_restarts, (unsigned long long)i.warm_products, (unsigned long long)i.restarts,
+             (unsigned long long)i.products, (unsigned long long)i.converged, i.reason, (unsigned long long)d.polls,
+             (unsigned long long)d.chunk, (unsigned long long)d.basis_bytes, d.phase_ms, i.solve_ms);
     return buf;
 }
 
@@ -652,122 +715,43 @@ unsigned cheb_chunk_of(H *a) {
     return (unsigned)a->ops.cheb_chunk;
 }
 
-// The filtered phases on [lo, hi]; fi holds a0, degree and the warm-up's counts already.  The step's product is the
-// recurrence with `coef`, or, where `series` is given (eigsh near sigma), the series with its coefficients.
-template <typename T, typename H>
-int filtered_phases(const char *fn, H *a, uint64_t k, int which, uint64_t ncv, const T *v0_dev, uint64_t seed, double tol_scale,
-                    uint64_t maxit, const ChebCoeffs<T> *coef, const ChebSeries<T> *series, T *theta, T *resid, T *x_dev,
-                    uint64_t ldx, hipStream_t st, spal_eigsh_filter_info *fi, FilterRecord *rec) {
+// The filtered phases; `info` (the filtered call's or the near call's) may hold a warm-up's solve_ms already.  The step's
+// product is the recurrence with `coef`, or, where `series` is given (eigsh near sigma), the series with its coefficients
+// in the form `series_form`.  The projected problem holds values of the polynomial, which is largest at the wanted end:
+// its pairs are taken descending, and the stop is decided on the true pairs, behind the phase's second poll.
+template <typename T, typename H, typename Info>
+int filtered_phases(const char *fn, H *a, uint64_t k, uint64_t ncv, const T *v0_dev, uint64_t seed, double tol_scale, uint64_t maxit,
+                    const ChebCoeffs<T> *coef, const ChebSeries<T> *series, int series_form, T *theta, T *resid, T *x_dev,
+                    uint64_t ldx, hipStream_t st, Info *info, Described *d) {
     const uint64_t n = a->nrows, m = ncv, degree = series ? series->k.size() - 1 : coef->alpha.size();
-    const int form = rotate_form_of(a);
-    // the basis (m + 1 vectors), w, the recurrence's work vector (the series' two), and for the out-of-place rotation a
-    // second basis
-    const uint64_t nvec = (m + 1) + 2 + (series ? 1 : 0) + (form == 1 ? m + 1 : 0);
-    const uint64_t stride = (n + 63) & ~(uint64_t)63;
-    const uint64_t basis_bytes = nvec * stride * sizeof(T);
-    DevBuf vecs, parts, scal, ydev;
-    PinnedBuf hpin, ypin, tpin;
-    SolveFrame<GHead<T>> F;
-    EventSpans rev;
-    {
-        const hipError_t e = vecs.alloc((size_t)basis_bytes);
-        if (e == hipErrorOutOfMemory)
-            return fail(SPAL_ERR_OUT_OF_MEMORY, "%s: no memory for the basis: %llu vectors of %llu elements (%llu bytes)", fn,
-                        (unsigned long long)nvec, (unsigned long long)n, (unsigned long long)basis_bytes);
-        SPAL_HIP_TRY(e);
-    }
-    const uint64_t pe = scratch_elems(n);
-    SPAL_HIP_TRY(parts.alloc(std::max<uint64_t>(m, 2) * pe * sizeof(T)));
-    // the scalars: the head, h, c, the columns, then the k true pairs
-    const size_t pair_off = sizeof(GHead<T>) + (2 * (m + 1) + m * m) * sizeof(T);
-    const size_t scal_bytes = pair_off + k * sizeof(TruePair<T>);
-    SPAL_HIP_TRY(scal.alloc(scal_bytes));
-    SPAL_HIP_TRY(ydev.alloc(m * kMaxNcv * sizeof(T)));
-    SPAL_HIP_TRY(hpin.alloc(m * m * sizeof(T)));
-    SPAL_HIP_TRY(ypin.alloc(m * kMaxNcv * sizeof(T)));
-    SPAL_HIP_TRY(tpin.alloc(k * sizeof(TruePair<T>)));
-    SPAL_TRY(F.create(st, 1));
-    SPAL_HIP_TRY(rev.create(1));
-
-    Run<T> R;
-    R.fn = fn;
-    R.a = solve_handle(a);
-    R.st = st;
-    R.n = n;
-    R.m = m;
-    R.c1 = tiles_of(n);
-    R.pe = pe;
-    R.stride = stride;
-    R.grid = first_level_grid(n);
-    R.form = form;
-    R.device = a->device;
-    R.s = scal.as<GHead<T>>();
-    R.h = reinterpret_cast<T *>(reinterpret_cast<char *>(scal.p) + sizeof(GHead<T>));
-    R.c = R.h + (m + 1);
-    R.H = R.c + (m + 1);
-    R.basis = vecs.as<T>();
-    R.w = R.basis + (m + 1) * stride;
-    R.work = R.w + stride;
-    R.work2 = series ? R.work + stride : nullptr;
-    R.alt = form == 1 ? R.work + (series ? 2 : 1) * stride : nullptr;
-    R.part = parts.as<T>();
-    R.y_dev = ydev.as<T>();
-    R.y_pin = ypin.as<T>();
-    R.V.v = R.basis;
-    R.V.stride = stride;
-    R.V.n = n;
-    R.V.tiles = tiles_of(n);
+    Workspace<T> W;
+    SPAL_TRY(W.create(fn, a, m, rotate_form_of(a), series ? 2 : 1, k, st));
+    Run<T> &R = W.R;
     R.filter = coef;
     R.series = series;
+    R.series_form = series_form;
     R.chunk = cheb_chunk_of(a);
-    if (series) {
-        std::lock_guard<std::mutex> lock(solve_handle(a)->mu);
-        R.series_form = a->ops.cheb_series_form;
-    }
-    TruePair<T> *pairs_dev = reinterpret_cast<TruePair<T> *>(reinterpret_cast<char *>(scal.p) + pair_off);
-    const TruePair<T> *pairs = tpin.as<TruePair<T>>();
+    const GHead<T> *h = W.F.h;   // as of the last poll
+    TruePair<T> *pairs_dev = W.pairs_dev;
+    const TruePair<T> *pairs = W.tpin.template as<TruePair<T>>();
+    SPAL_TRY(W.begin(v0_dev, seed));
 
-    const GHead<T> *h = F.h;
-    const T *cols = hpin.as<T>();
-    SPAL_TRY(F.begin(scal.p, scal_bytes));
-    SPAL_TRY(R.start(v0_dev, seed));
-
-    std::vector<double> S(m * m, 0.0), Sw;
-    RitzPairs rp;
-    uint64_t keep = 0, restarts = 0, jj = 0, conv = 0, nk = 0, true_products = 0, polls = 0;
+    uint64_t conv = 0, nk = 0, true_products = 0;
     int reason = 0;
     double residual_ms = 0.0;
     for (;;) {
-        for (uint64_t j = keep; j < m; ++j) SPAL_TRY(R.step((unsigned)j));
-        SPAL_HIP_TRY(hipMemcpyAsync(hpin.p, R.H, m * m * sizeof(T), hipMemcpyDeviceToHost, st));
-        SPAL_TRY(F.poll());   // the first poll of the phase: the head and the columns
-        if (h->done) {
-            reason = (int)h->reason;
-            break;
-        }
-        if (!h->cyc_end) return fail(SPAL_ERR_HIP, "%s: the device did not end a phase of %llu steps", fn, (unsigned long long)(m - keep));
-        jj = h->jj;
-        for (uint64_t j = keep; j < jj; ++j)
-            for (uint64_t t = 0; t <= j; ++t) S[t * m + j] = S[j * m + t] = (double)cols[j * m + t];   // exact
-        Sw.resize(jj * jj);
-        for (uint64_t r = 0; r < jj; ++r)
-            for (uint64_t q = 0; q < jj; ++q) Sw[r * jj + q] = S[r * m + q];
-        if (!eigsh_ritz(jj, Sw.data(), (double)h->hn, SPAL_EIGSH_LA, &rp)) {   // p is largest at the wanted end: descending
-            reason = 2;
+        PhaseEnd end;
+        SPAL_TRY(W.phase(SPAL_EIGSH_LA, &end));
+        if (end != PhaseEnd::pairs_ready) {
+            reason = end == PhaseEnd::device_stopped ? (int)h->reason : 2;
             break;
         }
         const bool exhausted = h->hn == T(0);
-        nk = std::min(k, jj);
-        const uint64_t kc = std::min(eigsh_keep(k, m), jj);
+        nk = std::min(k, W.jj);
+        const uint64_t kc = std::min(eigsh_keep(k, m), W.jj);
         // rotate first: x_c = the new v_c, and a restart goes on from these columns
-        if (form == 1) {
-            SPAL_TRY(R.rotate(rp, jj, kc, RotOut<T>{R.alt, stride, 1}, exhausted ? nullptr : R.v_at(m), R.alt + kc * stride));
-            std::swap(R.basis, R.alt);
-            R.V.v = R.basis;
-        } else {
-            SPAL_TRY(R.rotate(rp, jj, kc, RotOut<T>{R.basis, stride, 1}, exhausted ? nullptr : R.v_at(m), R.v_at(kc)));
-        }
-        SPAL_HIP_TRY(hipEventRecord(rev.e[0], st));
+        SPAL_TRY(R.rotate_basis(W.rp, W.jj, kc, !exhausted));
+        SPAL_HIP_TRY(hipEventRecord(W.rev.e[0], st));
         for (uint64_t c = 0; c < nk; ++c) {
             SPAL_TRY(cheb_rowsum_enqueue<T>(fn, R.a, (const T *)R.v_at(c), R.w, R.chunk, st));
             KRYLOV_LAUNCH((dot_tiles<T>), R.grid, (const T *)R.v_at(c), (const T *)R.w, R.part, n, R.V.tiles);
@@ -776,13 +760,13 @@ int filtered_phases(const char *fn, H *a, uint64_t k, int which, uint64_t ncv, c
             KRYLOV_LAUNCH((finish_dot<T, true>), 1, R.part, R.c1, &pairs_dev[c].res);
         }
         true_products += nk;
-        SPAL_HIP_TRY(hipEventRecord(rev.e[1], st));
-        SPAL_HIP_TRY(hipMemcpyAsync(tpin.p, pairs_dev, nk * sizeof(TruePair<T>), hipMemcpyDeviceToHost, st));
+        SPAL_HIP_TRY(hipEventRecord(W.rev.e[1], st));
+        SPAL_HIP_TRY(hipMemcpyAsync(W.tpin.p, pairs_dev, nk * sizeof(TruePair<T>), hipMemcpyDeviceToHost, st));
         SPAL_HIP_TRY(hipStreamSynchronize(st));   // the second poll: the true pairs
-        ++polls;
+        ++W.F.polls;
         {
             float ms = 0.f;
-            if (rev.span(0, &ms) == hipSuccess) residual_ms += ms;
+            if (W.rev.span(0, &ms) == hipSuccess) residual_ms += ms;
         }
         bool finite = true;
         for (uint64_t c = 0; c < nk; ++c) finite = finite && std::isfinite((double)pairs[c].th) && std::isfinite((double)pairs[c].res);
@@ -793,7 +777,7 @@ int filtered_phases(const char *fn, H *a, uint64_t k, int which, uint64_t ncv, c
         conv = 0;
         while (conv < nk && (double)pairs[conv].res <= tol_scale) ++conv;
         if (exhausted) {   // the space is exhausted: the pairs are final
-            reason = jj >= k ? 0 : 3;
+            reason = W.jj >= k ? 0 : 3;
             if (reason == 3) conv = nk;
             break;
         }
@@ -801,34 +785,30 @@ int filtered_phases(const char *fn, H *a, uint64_t k, int which, uint64_t ncv, c
             reason = 0;
             break;
         }
-        if (restarts == maxit) {
+        if (W.restarts == maxit) {
             reason = 1;
             break;
         }
-        keep = kc;
-        KRYLOV_LAUNCH((phase_start<T>), 1, R.s, (unsigned)keep);
-        std::fill(S.begin(), S.end(), 0.0);
-        for (uint64_t i = 0; i < keep; ++i) S[i * m + i] = rp.theta[i];
-        ++restarts;
+        SPAL_TRY(W.restart(kc));
     }
     if (reason == 2) nk = 0;
     if (nk && x_dev) KRYLOV_LAUNCH((columns_out<T>), R.grid, R.V, (unsigned)nk, x_dev, ldx);
     float ms = 0.f;
-    SPAL_TRY(F.end(&ms));
+    SPAL_TRY(W.F.end(&ms));
     for (uint64_t i = 0; i < nk; ++i) {
         theta[i] = pairs[i].th;
         resid[i] = pairs[i].res;
     }
-    fi->restarts = restarts;
-    fi->products = h->it * degree + true_products;
-    fi->converged = reason == 2 ? 0 : conv;
-    fi->reason = reason;
-    fi->solve_ms += (double)ms;
-    rec->r.keep = eigsh_keep(k, m);
-    rec->r.polls = F.polls + polls;
-    rec->r.basis_bytes = basis_bytes;
-    rec->chunk = R.chunk;
-    rec->residual_ms = residual_ms;
+    info->restarts = W.restarts;
+    info->products = h->it * degree + true_products;
+    info->converged = reason == 2 ? 0 : conv;
+    info->reason = reason;
+    info->solve_ms += (double)ms;
+    d->keep = eigsh_keep(k, m);
+    d->polls = W.F.polls;
+    d->basis_bytes = W.basis_bytes;
+    d->chunk = R.chunk;
+    d->phase_ms = residual_ms;
     return SPAL_OK;
 }
 
@@ -842,36 +822,18 @@ int eigsh_filtered_run(const char *fn, H *a, uint64_t k, int which, uint64_t ncv
     *fi = spal_eigsh_filter_info{};
     fi->degree = degree;
     tol = cheb_tol<T>(tol);
-    double glo = 0.0, ghi = 0.0;
-    SPAL_TRY(gershgorin_run(fn, solve_handle(a), st, &glo, &ghi));
-    FilterRecord rec;
-    rec.degree = degree;
-    rec.automatic = automatic;
-    rec.glo = glo;
-    rec.ghi = ghi;
+    Described d;
+    SPAL_TRY(gershgorin_run(fn, solve_handle(a), st, &d.glo, &d.ghi));
     auto finish = [&]() {
-        rec.r.k = k;
-        rec.r.which = which;
-        rec.r.ncv = ncv;
-        rec.r.restarts = fi->restarts;
-        rec.r.products = fi->products;
-        rec.r.converged = fi->converged;
-        rec.r.reason = fi->reason;
-        rec.r.solve_ms = fi->solve_ms;
-        rec.lo = fi->lo;
-        rec.hi = fi->hi;
-        rec.a0 = fi->a0;
-        rec.warm_restarts = fi->warm_restarts;
-        rec.warm_products = fi->warm_products;
-        store_info(a, &OpState::eigsh_filter_info, filter_json(rec));
+        store_info(a, &OpState::eigsh_filter_info, filter_json(k, which, ncv, automatic, *fi, d));
         return SPAL_OK;
     };
-    if (!std::isfinite(glo) || !std::isfinite(ghi)) {   // a value of the matrix is not finite
+    if (!std::isfinite(d.glo) || !std::isfinite(d.ghi)) {   // a value of the matrix is not finite
         fi->a0 = (double)NAN;
         fi->reason = 2;
         return finish();
     }
-    const double a0 = cheb_a0(which, glo, ghi);
+    const double a0 = cheb_a0(which, d.glo, d.ghi);
     fi->a0 = a0;
     if (automatic) {
         spal_eigsh_info warm;
@@ -882,7 +844,7 @@ int eigsh_filtered_run(const char *fn, H *a, uint64_t k, int which, uint64_t ncv
         fi->reason = warm.reason;
         fi->solve_ms = warm.solve_ms;
         if (warm.reason != 1) return finish();
-        if (!cheb_auto_interval(which, glo, ghi, (double)theta[k - 1], &lo, &hi)) return finish();
+        if (!cheb_auto_interval(which, d.glo, d.ghi, (double)theta[k - 1], &lo, &hi)) return finish();
     } else if (cheb_check(degree, lo, hi, a0) != CHEB_OK || !cheb_wanted_side(which, lo, hi, a0)) {
         return fail(SPAL_ERR_INVALID_ARGUMENT,
                     "%s: a0 = %.17g (Gershgorin's %s bound) must lie strictly %s the interval [%.17g, %.17g]", fn, a0,
@@ -891,8 +853,8 @@ int eigsh_filtered_run(const char *fn, H *a, uint64_t k, int which, uint64_t ncv
     fi->lo = lo;
     fi->hi = hi;
     const ChebCoeffs<T> coef = cheb_coefficients<T>(degree, lo, hi, a0);
-    SPAL_TRY((filtered_phases<T, H>(fn, a, k, which, ncv, v0_dev, seed, tol * cheb_scale(glo, ghi), maxit, &coef,
-                                    (const ChebSeries<T> *)nullptr, theta, resid, x_dev, ldx, st, fi, &rec)));
+    SPAL_TRY((filtered_phases<T, H>(fn, a, k, ncv, v0_dev, seed, tol * cheb_scale(d.glo, d.ghi), maxit, &coef,
+                                    (const ChebSeries<T> *)nullptr, 0, theta, resid, x_dev, ldx, st, fi, &d)));
     return finish();
 }
 
@@ -927,51 +889,29 @@ int eigsh_filtered_host(const char *fn, H *a, uint64_t k, int which, uint64_t nc
                         uint64_t theta_len, T *resid, uint64_t resid_len, T *x, uint64_t ldx, uint64_t x_rows,
                         spal_eigsh_filter_info *fi) {
     SPAL_TRY((eigsh_filtered_check<T, H>(fn, a, k, which, ncv, tol, degree, automatic, lo, hi, theta, resid, x, ldx, fi)));
-    const uint64_t n = a->nrows;
-    if ((v0 && v0_len != n) || theta_len != k || resid_len != k || (x && x_rows != n))
-        return fail(SPAL_ERR_INVALID_ARGUMENT,
-                    "%s: v0.len() = %llu and X has %llu rows but the matrix has %llu rows; theta.len() = %llu and resid.len() = %llu but "
-                    "k = %llu", fn, (unsigned long long)v0_len, (unsigned long long)x_rows, (unsigned long long)n,
-                    (unsigned long long)theta_len, (unsigned long long)resid_len, (unsigned long long)k);
-    DeviceGuard guard(a->device);
-    if (guard.status != SPAL_OK) return guard.status;
-    size_t bytes = 0;
-    if (!bytes_of(n, k, sizeof(T), 1, &bytes))
-        return fail(SPAL_ERR_OUT_OF_MEMORY, "%s: no room for a block of %llu x %llu", fn, (unsigned long long)n, (unsigned long long)k);
-    const size_t row = (size_t)k * sizeof(T);
-    DevBuf dv, dx;
-    PooledStream ps;   // a stream of the call's own
-    if (v0) SPAL_HIP_TRY(dv.alloc(n * sizeof(T)));
-    if (x) SPAL_HIP_TRY(dx.alloc(bytes));
-    SPAL_HIP_TRY(stream_acquire(&ps.s));
-    if (v0) SPAL_HIP_TRY(hipMemcpyAsync(dv.p, v0, n * sizeof(T), hipMemcpyHostToDevice, ps.s));
-    SPAL_TRY((eigsh_filtered_run<T, H>(fn, a, k, which, ncv, v0 ? (const T *)dv.p : nullptr, seed, tol, maxit, degree, automatic, lo, hi,
-                                       warmup, theta, resid, x ? dx.as<T>() : nullptr, k, ps.s, fi)));
-    const uint64_t got = fi->reason == 2 ? 0 : fi->reason == 3 ? fi->converged : k;
-    if (x && got) {
-        SPAL_HIP_TRY(hipMemcpy2DAsync(x, (size_t)ldx * sizeof(T), dx.p, row, (size_t)got * sizeof(T), n, hipMemcpyDeviceToHost, ps.s));
-        SPAL_HIP_TRY(hipStreamSynchronize(ps.s));
-    }
-    return SPAL_OK;
+    return eigsh_staged<T>(fn, a, k, v0, v0_len, theta_len, resid_len, x, ldx, x_rows, fi,
+                           [&](const T *v0_dev, T *x_dev, uint64_t ld, hipStream_t st) {
+                               return eigsh_filtered_run<T, H>(fn, a, k, which, ncv, v0_dev, seed, tol, maxit, degree, automatic, lo, hi,
+                                                               warmup, theta, resid, x_dev, ld, st, fi);
+                           });
 }
 
 // ---- eigsh near sigma -------------------------------------------------------------------------------------
 // The filtered phases on rho(A), the Fejer-damped delta function at sigma as a Chebyshev series (spal_cheb.hip): no
 // warm-up, the interval is Gershgorin's with a margin or the caller's, everything else is the filtered call's.
-std::string near_json(const FilterRecord &f, double sigma, double gamma, int series_form) {
+std::string near_json(uint64_t k, uint64_t ncv, int automatic, int series_form, const spal_eigsh_near_info &i, const Described &d) {
     char buf[1280];
-    const Record &r = f.r;
     snprintf(buf, sizeof buf,
              "{\"k\": %llu, \"sigma\": %s, \"gamma\": %s, \"ncv\": %llu, \"keep\": %llu, \"degree\": %llu, \"interval\": \"%s\", "
              "\"lo\": %s, \"hi\": %s, \"glo\": %s, \"ghi\": %s, \"restarts\": %llu, \"products\": %llu, \"converged\": %llu, "
              "\"reason\": %d, \"polls\": %llu, \"chunk\": %llu, \"form\": \"%s\", \"basis_bytes\": %llu, \"residual_ms\": %.4f, "
              "\"solve_ms\": %.4f}",
-             (unsigned long long)r.k, json_number(sigma).c_str(), json_number(gamma).c_str(), (unsigned long long)r.ncv,
-             (unsigned long long)r.keep, (unsigned long long)f.degree, f.automatic ? "auto" : "given", json_number(f.lo).c_str(),
-             json_number(f.hi).c_str(), json_number(f.glo).c_str(), json_number(f.ghi).c_str(), (unsigned long long)r.restarts,
-             (unsigned long long)r.products, (unsigned long long)r.converged, r.reason, (unsigned long long)r.polls,
-             (unsigned long long)f.chunk, series_form == 2 ? "unfused" : "fused", (unsigned long long)r.basis_bytes, f.residual_ms,
-             r.solve_ms);
+             (unsigned long long)k, json_number(i.sigma).c_str(), json_number(i.gamma).c_str(), (unsigned long long)ncv,
+             (unsigned long long)d.keep, (unsigned long long)i.degree, automatic ? "auto" : "given", json_number(i.lo).c_str(),
+             json_number(i.hi).c_str(), json_number(d.glo).c_str(), json_number(d.ghi).c_str(), (unsigned long long)i.restarts,
+             (unsigned long long)i.products, (unsigned long long)i.converged, i.reason, (unsigned long long)d.polls,
+             (unsigned long long)d.chunk, series_form == 2 ? "unfused" : "fused", (unsigned long long)d.basis_bytes, d.phase_ms,
+             i.solve_ms);
     return buf;
 }
 
@@ -985,27 +925,22 @@ int eigsh_near_run(const char *fn, H *a, uint64_t k, double sigma, uint64_t ncv,
     ni->degree = degree;
     ni->sigma = sigma;
     tol = cheb_tol<T>(tol);
-    double glo = 0.0, ghi = 0.0;
-    SPAL_TRY(gershgorin_run(fn, solve_handle(a), st, &glo, &ghi));
-    FilterRecord rec;
-    rec.degree = degree;
-    rec.automatic = automatic;
-    rec.glo = glo;
-    rec.ghi = ghi;
-    rec.r.k = k;
-    rec.r.ncv = ncv;
+    Described d;
+    SPAL_TRY(gershgorin_run(fn, solve_handle(a), st, &d.glo, &d.ghi));
     int series_form = 0;
     {
         std::lock_guard<std::mutex> lock(solve_handle(a)->mu);
         series_form = a->ops.cheb_series_form;
     }
-    if (!std::isfinite(glo) || !std::isfinite(ghi)) {   // a value of the matrix is not finite
-        ni->reason = 2;
-        rec.r.reason = 2;
-        store_info(a, &OpState::eigsh_near_info, near_json(rec, sigma, 0.0, series_form));
+    auto finish = [&]() {
+        store_info(a, &OpState::eigsh_near_info, near_json(k, ncv, automatic, series_form, *ni, d));
         return SPAL_OK;
+    };
+    if (!std::isfinite(d.glo) || !std::isfinite(d.ghi)) {   // a value of the matrix is not finite
+        ni->reason = 2;
+        return finish();
     }
-    if (automatic) cheb_near_auto_interval(glo, ghi, &lo, &hi);
+    if (automatic) cheb_near_auto_interval(d.glo, d.ghi, &lo, &hi);
     std::vector<double> coef(degree + 1);
     double gamma = 0.0;
     const ChebSeriesRefusal r = cheb_near_filter(degree, sigma, lo, hi, &gamma, coef.data());
@@ -1016,23 +951,9 @@ int eigsh_near_run(const char *fn, H *a, uint64_t k, double sigma, uint64_t ncv,
     ni->hi = hi;
     ni->gamma = gamma;
     const ChebSeries<T> series = cheb_series_scalars<T>(lo, hi, coef.data(), coef.size());
-    spal_eigsh_filter_info fi{};
-    SPAL_TRY((filtered_phases<T, H>(fn, a, k, SPAL_EIGSH_LA, ncv, v0_dev, seed, tol * cheb_scale(glo, ghi), maxit,
-                                    (const ChebCoeffs<T> *)nullptr, &series, theta, resid, x_dev, ldx, st, &fi, &rec)));
-    ni->restarts = fi.restarts;
-    ni->products = fi.products;
-    ni->converged = fi.converged;
-    ni->reason = fi.reason;
-    ni->solve_ms = fi.solve_ms;
-    rec.r.restarts = fi.restarts;
-    rec.r.products = fi.products;
-    rec.r.converged = fi.converged;
-    rec.r.reason = fi.reason;
-    rec.r.solve_ms = fi.solve_ms;
-    rec.lo = lo;
-    rec.hi = hi;
-    store_info(a, &OpState::eigsh_near_info, near_json(rec, sigma, gamma, series_form));
-    return SPAL_OK;
+    SPAL_TRY((filtered_phases<T, H>(fn, a, k, ncv, v0_dev, seed, tol * cheb_scale(d.glo, d.ghi), maxit, (const ChebCoeffs<T> *)nullptr,
+                                    &series, series_form, theta, resid, x_dev, ldx, st, ni, &d)));
+    return finish();
 }
 
 template <typename T, typename H>
@@ -1064,33 +985,13 @@ int eigsh_near_host(const char *fn, H *a, uint64_t k, double sigma, uint64_t ncv
                     double tol, uint64_t maxit, uint64_t degree, int automatic, double lo, double hi, T *theta, uint64_t theta_len,
                     T *resid, uint64_t resid_len, T *x, uint64_t ldx, uint64_t x_rows, spal_eigsh_near_info *ni) {
     SPAL_TRY((eigsh_near_check<T, H>(fn, a, k, sigma, ncv, tol, degree, automatic, lo, hi, theta, resid, x, ldx, ni)));
-    const uint64_t n = a->nrows;
-    if ((v0 && v0_len != n) || theta_len != k || resid_len != k || (x && x_rows != n))
-        return fail(SPAL_ERR_INVALID_ARGUMENT,
-                    "%s: v0.len() = %llu and X has %llu rows but the matrix has %llu rows; theta.len() = %llu and resid.len() = %llu but "
-                    "k = %llu", fn, (unsigned long long)v0_len, (unsigned long long)x_rows, (unsigned long long)n,
-                    (unsigned long long)theta_len, (unsigned long long)resid_len, (unsigned long long)k);
-    DeviceGuard guard(a->device);
-    if (guard.status != SPAL_OK) return guard.status;
-    size_t bytes = 0;
-    if (!bytes_of(n, k, sizeof(T), 1, &bytes))
-        return fail(SPAL_ERR_OUT_OF_MEMORY, "%s: no room for a block of %llu x %llu", fn, (unsigned long long)n, (unsigned long long)k);
-    const size_t row = (size_t)k * sizeof(T);
-    DevBuf dv, dx;
-    PooledStream ps;   // a stream of the call's own
-    if (v0) SPAL_HIP_TRY(dv.alloc(n * sizeof(T)));
-    if (x) SPAL_HIP_TRY(dx.alloc(bytes));
-    SPAL_HIP_TRY(stream_acquire(&ps.s));
-    if (v0) SPAL_HIP_TRY(hipMemcpyAsync(dv.p, v0, n * sizeof(T), hipMemcpyHostToDevice, ps.s));
-    SPAL_TRY((eigsh_near_run<T, H>(fn, a, k, sigma, ncv, v0 ? (const T *)dv.p : nullptr, seed, tol, maxit, degree, automatic, lo, hi,
-                                   theta, resid, x ? dx.as<T>() : nullptr, k, ps.s, ni)));
-    const uint64_t got = ni->reason == 2 ? 0 : ni->reason == 3 ? ni->converged : k;
-    if (x && got) {
-        SPAL_HIP_TRY(hipMemcpy2DAsync(x, (size_t)ldx * sizeof(T), dx.p, row, (size_t)got * sizeof(T), n, hipMemcpyDeviceToHost, ps.s));
-        SPAL_HIP_TRY(hipStreamSynchronize(ps.s));
-    }
-    return SPAL_OK;
+    return eigsh_staged<T>(fn, a, k, v0, v0_len, theta_len, resid_len, x, ldx, x_rows, ni,
+                           [&](const T *v0_dev, T *x_dev, uint64_t ld, hipStream_t st) {
+                               return eigsh_near_run<T, H>(fn, a, k, sigma, ncv, v0_dev, seed, tol, maxit, degree, automatic, lo, hi,
+                                                           theta, resid, x_dev, ld, st, ni);
+                           });
 }
+
 
 }  // namespace
 

@@ -406,6 +406,35 @@ def test_chunk_rotation_form_and_ldx_do_not_change_the_bits(dtype):
     tr.assert_same_bits(rs, want.resid)
 
 
+@pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
+def test_the_workspace_and_the_polls_of_both_rotation_forms(dtype):
+    """n = 257, so the vectors' stride (320) is not n.  The block holds the basis (ncv + 1 vectors), w, the recurrence's
+    work vector and, for the out-of-place rotation, a second basis.  A given interval: no warm-up, and every phase polls
+    twice, for the head and for the true pairs."""
+    n, k, ncv = 257, 3, 9
+    tol, degree = CASES[dtype]
+    mat = (n, *cr.laplace_1d_csr(n, dtype))
+    got = {}
+    for rotate in (1, 2):
+        a = make("csr", mat)
+        a.device().set_option("eigsh_rotate", rotate)
+        got[rotate], _ = check(a, mat, dtype, k, "LA", ncv, tol, 2, degree, GIVEN["LA"])
+        info = got[rotate][2]
+        d = a.device().describe()["eigsh_filter"]
+        print(sfx(dtype), "rotate", rotate, "basis_bytes", d["basis_bytes"], "polls", d["polls"], "restarts", info.restarts,
+              "reason", info.reason)
+        nvec = (ncv + 1) + 2 + (ncv + 1 if rotate == 1 else 0)
+        assert d["basis_bytes"] == nvec * 320 * np.dtype(dtype).itemsize
+        assert info.reason in (0, 1, 3) and d["polls"] == 2 * (info.restarts + 1)
+        assert (info.warm_restarts, info.warm_products) == (0, 0)
+    (t1, x1, i1), (t2, x2, i2) = got[1], got[2]
+    tr.assert_same_bits(t1, t2)
+    tr.assert_same_bits(x1, x2)
+    tr.assert_same_bits(i1.resid, i2.resid)
+    assert (i1.restarts, i1.products, i1.converged, i1.reason, i1.lo, i1.hi, i1.a0) == \
+        (i2.restarts, i2.products, i2.converged, i2.reason, i2.lo, i2.hi, i2.a0)
+
+
 def test_a_second_call_takes_no_new_device_memory():
     import torch
     mat = banded(4099, np.float64)

@@ -82,6 +82,8 @@ def check(a, n, dtype, k, which, ncv, tol, maxit, v0=None, seed=0, jacobi_fn=Non
     assert set(d) == DESCRIBE_KEYS
     assert (d["k"], d["which"], d["ncv"], d["keep"]) == (k, which, ncv, er.keep_of(k, ncv))
     assert (d["restarts"], d["products"], d["reason"], d["polls"]) == (info.restarts, info.products, info.reason, info.restarts + 1)
+    nvec = (ncv + 1) + 1 + (ncv + 1 if d["rotate"] == "batch" else 0)      # the basis, w, and a second basis out of place
+    assert d["basis_bytes"] == nvec * (-(-n // 64) * 64) * np.dtype(dtype).itemsize
     return (theta, X, info), ref
 
 

@@ -330,6 +330,35 @@ def test_rotation_chunk_form_plan_and_ldx_do_not_change_the_bits(dtype):
 
 
 @pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
+@pytest.mark.parametrize("interval", [None, (-0.5, 4.5)], ids=["auto", "given"])
+def test_the_workspace_and_the_polls_of_both_rotation_forms(interval, dtype):
+    """n = 257, so the vectors' stride (320) is not n.  The block holds the basis (ncv + 1 vectors), w, the series' two
+    work vectors and, for the out-of-place rotation, a second basis.  Every phase polls twice, for the head and for the
+    true pairs."""
+    n, k, ncv = 257, 3, 9
+    mat = (n, *cr.laplace_1d_csr(n, dtype))
+    ref = nr.eigsh_near(mat[1:], dtype, k, 1.0, ncv, TOL[dtype], 2, 16, interval, None, 0, lib_jacobi)
+    got = {}
+    for rotate in (1, 2):
+        a = make("csr", mat)
+        a.device().set_option("eigsh_rotate", rotate)
+        got[rotate] = check(a, ref, dtype, k, 1.0, ncv, TOL[dtype], 2, 16, interval)
+        info = got[rotate][2]
+        d = a.device().describe()["eigsh_near"]
+        print(sfx(dtype), "rotate", rotate, "basis_bytes", d["basis_bytes"], "polls", d["polls"], "restarts", info.restarts,
+              "reason", info.reason)
+        nvec = (ncv + 1) + 2 + 1 + (ncv + 1 if rotate == 1 else 0)
+        assert d["basis_bytes"] == nvec * 320 * np.dtype(dtype).itemsize
+        assert info.reason in (0, 1, 3) and d["polls"] == 2 * (info.restarts + 1)
+    (t1, x1, i1), (t2, x2, i2) = got[1], got[2]
+    tr.assert_same_bits(t1, t2)
+    tr.assert_same_bits(x1, x2)
+    tr.assert_same_bits(i1.resid, i2.resid)
+    assert (i1.restarts, i1.products, i1.converged, i1.reason, i1.lo, i1.hi, i1.gamma) == \
+        (i2.restarts, i2.products, i2.converged, i2.reason, i2.lo, i2.hi, i2.gamma)
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
 def test_a_given_start_vector_and_maxit_0(dtype):
     mat = laplacian(dtype)
     v0 = tuple(np.random.default_rng(5).uniform(-1, 1, N).astype(dtype).tolist())
